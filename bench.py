@@ -12,23 +12,34 @@ complex samples already resident in HBM.  Steps alternate forward / inverse plan
 same buffer (inverse(forward(x)) == x, cl_fft.cpp:39-40) so the data stay O(1) instead of
 shrinking by 1/N per step into denormals; both directions are the same kernel.
 The path shards by batches: every rank owns its own 4096 transforms, no data-path
-collective ("weak" scaling, config 5 of BASELINE.json); RCCL only carries the end-of-run
-checksum and the max-over-ranks time.
+collective ("weak" scaling, config 5 of BASELINE.json); RCCL only carries the max-over-ranks
+time and, with --full, the end-of-run checksum.
+
+A plain run does only what the headline needs: set-up, config.settle_launches untimed steps and the W warm-up
+steps, the K timed steps, the outputs (--dump-outputs DIR) and the line.  Everything else it can measure or check
+runs only with --full, after the headline's timed steps unless noted.
+
+    python bench.py --full ...                             (every leg below)
+    python bench.py --dump-outputs DIR ...                 (the last timed step's outputs as DIR/<workload>.npy)
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects:
   roofline      algorithmic bytes (16 B per complex sample) / average launch
                 duration of the dominant kernel, measured here with HIP events on the launch stream
+  config.settle_launches   untimed steps worth --settle-ms (60) of device time right in front of the W warm-up
+                steps, so that the K timed steps read the chip's sustained clocks, not the tail of its ramp;
+                config.effective_warmup_launches counts what ran before the headline's timed region
+--full only:
   cpu_baseline  the CPU restatement of the reference algorithm (oracle/, "port") timed on the
-                host cores over a bounded sample — a reported baseline, not the target
+                host cores over a bounded sample — a reported baseline, not the target (null in plain runs)
   config.other_workloads   (N = 1 only) configs[2] and configs[3] of BASELINE.json — r2c + c2r of size
                 16384 x 8192 and the 256-channel partitioned convolution — timed in the same run with the
                 same machinery, each with ms_per_step and its own roofline block; plus (not a BASELINE config)
                 r2c + c2r of size 131072 x 2048, the largest real size of the reference's range
   ms_per_step_cold / roofline.frac_cold   the same K steps after the same W warm-up steps taken FIRST, before
-                the full-size self-check (the chip is still inside its ~20 ms start-up clock ramp then);
-                config.effective_warmup_launches counts what ran before the headline's timed region;
-                config.settle_launches of them are untimed steps worth --settle-ms (60) of device time right in front of
-                the W warm-up steps, so that the K timed steps read the chip's sustained clocks, not the tail of its ramp
+                the full-size self-check (the chip is still inside its ~20 ms start-up clock ramp then); both
+                run before the settle steps of the headline
+  config.out_of_place, membench, config.parity_relL2_vs_oracle, config.energy_checksum_all_ranks,
+  reference_opencl_same_gpu (null in plain runs)    (see main())
 `--workload rfft | pconv` make one of the other configurations the headline of the line instead.
 """
 import argparse
@@ -44,6 +55,8 @@ sys.path.insert(0, ROOT)
 os.environ.setdefault("OMP_WAIT_POLICY", "PASSIVE")   # idle OpenMP workers of the CPU baseline sleep, not spin
 
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: 8.0 TB/s spec
+DUMP_BYTES = 32 << 20      # --dump-outputs: bytes written per run, all ranks together
+DUMP_SEED = 20261016       # --dump-outputs: picks the sampled batch rows, the same in every run
 
 
 def parse():
@@ -53,6 +66,12 @@ def parse():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="c2c", choices=["c2c", "rfft", "pconv", "rfft131072"])
     ap.add_argument("--batch", type=int, default=0, help="override batches / channels per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also the legs beyond the headline: cold reading, full-size self-check, out of place, other workloads, "
+                         "device yardsticks, parity vs the oracle, checksum, CPU baselines, the reference on the same GPU")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<workload>.npy (float32; a fixed sample of the "
+                         "batch rows where the whole output exceeds %d MiB)" % (DUMP_BYTES >> 20))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-bandwidth", action="store_true", help="skip the device copy/read/write yardsticks")
     ap.add_argument("--no-selfcheck", action="store_true", help="skip the full-size property check before the warm-up")
@@ -60,7 +79,7 @@ def parse():
     ap.add_argument("--settle-ms", type=float, default=60.0,
                     help="device time of untimed steps in front of every workload's warm-up steps (0: none)")
     ap.add_argument("--no-other-workloads", action="store_true",
-                    help="headline workload only (profiling runs); default: N = 1 runs also time the other two configs")
+                    help="headline workload only (profiling runs); otherwise --full runs at N = 1 also time the other configs")
     ap.add_argument("--series-out", default="", help="write the per-launch times (ms) of the timed region to this file")
     return ap.parse_args()
 
@@ -360,6 +379,21 @@ class Workload:
                 "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": source,
                 "kernel": self.kernel, "avg_launch_ms": avg_ms, "algorithmic_bytes_per_launch": self.alg_bytes}
 
+    def dump_outputs(self, path, rank, world):
+        """what the last timed step returned to its caller (the in-place buffer, pconv's output block) as float32
+        path/<tkey>.npy (<tkey>_rank<r>.npy for N > 1): whole where it fits in this rank's share of DUMP_BYTES, else
+        that many batch rows picked with DUMP_SEED, in ascending order"""
+        import numpy as np
+        out = self.out if self.name == "pconv" else self.data
+        rows = out.shape[0]
+        keep = min(rows, max(1, DUMP_BYTES // world // (out[0].numel() * out.element_size())))
+        if keep < rows:
+            pick = np.sort(np.random.default_rng(DUMP_SEED).choice(rows, keep, replace=False))
+            out = out[self.torch.from_numpy(pick).to(out.device)]
+        os.makedirs(path, exist_ok=True)
+        name = self.tkey if world == 1 else "%s_rank%d" % (self.tkey, rank)
+        np.save(os.path.join(path, name + ".npy"), out.cpu().numpy().astype(np.float32, copy=False))
+
 
 def main():
     a = parse()
@@ -412,20 +446,20 @@ def main():
     wl = Workload(a.workload, fa, torch, dev, local, rank, world, a.batch, stream)
     extra = wl.extra
 
-    # 1. the contract's reading taken cold: W warm-up steps, K timed steps, nothing before them
+    # 1. (--full) the contract's reading taken cold: W warm-up steps, K timed steps, nothing before them
     cold = None
-    if not a.no_cold and not a.series_out:
+    if a.full and not a.no_cold and not a.series_out:
         with torch.cuda.stream(stream):
             wl.run(W)
         cold_s, cold_ms, _ = wl.timed(K, barrier)
         cold = {"ms_per_step": cold_s / K * 1e3, "avg_launch_ms": cold_ms}
-    elif not a.no_selfcheck and not a.series_out:
+    elif a.full and not a.no_selfcheck and not a.series_out:
         # (profiling runs, --no-cold: the guard's transforms would otherwise be the first launches of the process, at
         # start-up clocks, and weigh on the per-kernel averages of rocprofv3 --stats)
         with torch.cuda.stream(stream):
             wl.run(W)
-    # 2. the full-size guard (~15 launch-equivalents of device work with its elementwise kernels)
-    if not a.no_selfcheck:
+    # 2. (--full) the full-size guard (~15 launch-equivalents of device work with its elementwise kernels)
+    if a.full and not a.no_selfcheck:
         chk = wl.selfcheck()
         if chk is not None:
             extra["full_size_selfcheck"] = chk
@@ -435,6 +469,8 @@ def main():
         wl.run(W)
     extra["effective_warmup_launches"] = wl.launches_before_timed
     elapsed, avg_ms, per_launch_ms = wl.timed(K, barrier, series=bool(a.series_out))
+    if a.dump_outputs:
+        wl.dump_outputs(a.dump_outputs, rank, world)
     el = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     per_rank = None
     if world > 1:
@@ -458,7 +494,7 @@ def main():
     # 3b. the same workload OUT OF PLACE (extension clfa_fft_exec_dev_oop; the reference's device side is out of place
     # too, data1 -> data2, cl_fft.cpp:138-151): forward A -> B, inverse B -> A, same machinery.  Never the headline.
     oop = None
-    if a.workload == "c2c" and world == 1 and not a.series_out and not a.no_other_workloads:   # (not in profiling runs: same kernel symbol)
+    if a.full and a.workload == "c2c" and world == 1 and not a.series_out and not a.no_other_workloads:   # (not in profiling runs: same kernel symbol)
         other = torch.empty_like(wl.data)
         bufs = (wl.data, other)
         in_place_step = wl.step
@@ -480,7 +516,7 @@ def main():
 
     # 4. configs[2] and configs[3] in the same run (N = 1 only: the multi-GPU line stays the sharded headline)
     others = None
-    if world == 1 and not a.no_other_workloads and not a.series_out and a.batch == 0:
+    if a.full and world == 1 and not a.no_other_workloads and not a.series_out and a.batch == 0:
         others, other_names = {}, []
         for name in ("c2c", "rfft", "pconv", "rfft131072"):
             if name == a.workload:
@@ -511,7 +547,7 @@ def main():
     # columns), measured here, on this device, AFTER the timed regions (run before them, 150 ms of copy
     # kernels leave the chip in a lower clock state and the first ~20 FFT launches read 5-15 % slower).
     membench = None
-    if not a.no_bandwidth and rank == 0:
+    if a.full and not a.no_bandwidth and rank == 0:
         torch.cuda.synchronize()
         membench = {k: round(v, 3) for k, v in fa.bandwidth_probe(local, 1 << 30, 100).items()}
         membench["unit"] = "TB/s"
@@ -520,7 +556,7 @@ def main():
                            "four-step FFT's global access shape)")
     # parity guard, AFTER the timed region (the oracle's OpenMP pool must not be spinning on the
     # host cores while the HIP runtime threads drive the timed launches): transforms vs the oracle
-    if a.workload == "c2c":
+    if a.full and a.workload == "c2c":
         from oracle import oracle
         gq = torch.Generator(device=dev).manual_seed(99)
         nprobe = 72      # more transforms than CUs / 4: the same kernel as the timed launches
@@ -538,10 +574,11 @@ def main():
         assert extra["parity_relL2_vs_oracle"] < 1e-6
 
     # end-of-run checksum over all ranks (validates the sharded run; RCCL only here)
-    chk = (wl.data.double() ** 2).sum().reshape(1) if a.workload != "pconv" else (wl.out.double() ** 2).sum().reshape(1)
-    if world > 1:
-        dist.all_reduce(chk, op=dist.ReduceOp.SUM)
-    extra["energy_checksum_all_ranks"] = float(chk.item())
+    if a.full:
+        chk = (wl.data.double() ** 2).sum().reshape(1) if a.workload != "pconv" else (wl.out.double() ** 2).sum().reshape(1)
+        if world > 1:
+            dist.all_reduce(chk, op=dist.ReduceOp.SUM)
+        extra["energy_checksum_all_ranks"] = float(chk.item())
 
     if rank == 0:
         value = wl.units * K * world / elapsed / 1e9
@@ -562,16 +599,18 @@ def main():
             rec["config"]["per_rank"] = per_rank
         if oop is not None:
             rec["config"]["out_of_place"] = oop
-        # the unmodified reference on the same GPU (child processes, after every timed region)
-        try:
-            pci_bus = int(torch.cuda.get_device_properties(local).pci_bus_id)
-        except (AttributeError, TypeError, ValueError):
-            pci_bus = None
-        rec["reference_opencl_same_gpu"] = reference_timing({"c2c": "cfft", "rfft": "rfft", "pconv": "pconv", "rfft131072": "rfft"}[a.workload], pci_bus) if a.workload != "rfft131072" else None
-        if others is not None:
-            for leg in ("rfft", "pconv"):
-                if leg in others:
-                    others[leg]["reference_opencl_same_gpu"] = reference_timing(leg, pci_bus)
+        # (--full) the unmodified reference on the same GPU (child processes, after every timed region)
+        rec["reference_opencl_same_gpu"] = None
+        if a.full:
+            try:
+                pci_bus = int(torch.cuda.get_device_properties(local).pci_bus_id)
+            except (AttributeError, TypeError, ValueError):
+                pci_bus = None
+            rec["reference_opencl_same_gpu"] = reference_timing({"c2c": "cfft", "rfft": "rfft", "pconv": "pconv", "rfft131072": "rfft"}[a.workload], pci_bus) if a.workload != "rfft131072" else None
+            if others is not None:
+                for leg in ("rfft", "pconv"):
+                    if leg in others:
+                        others[leg]["reference_opencl_same_gpu"] = reference_timing(leg, pci_bus)
         if cold is not None:
             # the contract's W + K launches read cold (before the self-check): inside the chip's start-up clock ramp
             rec["ms_per_step_cold"] = cold["ms_per_step"]
@@ -593,7 +632,7 @@ def main():
                 f.write("# per-launch ms between HIP events on the launch stream, timed region of: bench.py "
                         "--workload %s --steps %d --warmup %d\n" % (a.workload, K, W))
                 f.write("\n".join("%.4f" % t for t in per_launch_ms) + "\n")
-        if world == 1 and not a.no_cpu_baseline and a.workload == "c2c":
+        if a.full and world == 1 and not a.no_cpu_baseline and a.workload == "c2c":
             rec["cpu_baseline"] = cpu_baseline_c2c(65536, 2048)
             if others is not None:     # the other two legs against their own restatements (bounded samples, after every timed region)
                 if "rfft" in others:

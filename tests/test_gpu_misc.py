@@ -67,7 +67,7 @@ def test_device_tensor_must_be_contiguous():
 @pytest.mark.parametrize("workload,extra", [("c2c", ["--batch", "64"]), ("rfft", ["--batch", "128"]),
                                             ("pconv", ["--batch", "8"])])
 def test_bench_contract(workload, extra):
-    out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1",
+    out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "4", "--warmup", "1",
                                    "--workload", workload] + extra, stderr=subprocess.DEVNULL, timeout=300).decode()
     line = [l for l in out.splitlines() if l.startswith("{")]
     assert len(line) == 1
@@ -117,7 +117,7 @@ def test_bench_starts_its_own_ranks():
     touches the GPU) and relays rank 0's line; rehearsed on one GPU (gloo, both ranks on device 0)"""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(CLFA_BENCH_BACKEND="gloo", CLFA_BENCH_DEVICE="0")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "4", "--warmup", "1",
                         "--batch", "256"], env=env, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=600)
     assert p.returncode == 0
     line = [l for l in p.stdout.decode().splitlines() if l.startswith("{")]
@@ -137,9 +137,9 @@ def test_randomised_parity_sweep():
 
 
 def test_bench_default_line_carries_every_single_gpu_config():
-    """the driver's command line (no --workload, no --batch): the headline (configs[1]) with its cold figure beside it,
-    configs[2] and configs[3] under config.other_workloads, each with its own roofline block"""
-    out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2"],
+    """the driver's command line (no --workload, no --batch) with --full: the headline (configs[1]) with its cold figure
+    beside it, configs[2] and configs[3] under config.other_workloads, each with its own roofline block"""
+    out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "6", "--warmup", "2"],
                                   stderr=subprocess.DEVNULL, timeout=900).decode()
     line = [l for l in out.splitlines() if l.startswith("{")]
     assert len(line) == 1
@@ -164,6 +164,37 @@ def test_bench_default_line_carries_every_single_gpu_config():
     ref = r["reference_opencl_same_gpu"]
     assert ref["kind"] == "reference" and 0.1 < ref["value"] < 10
     assert ref["source"].startswith(("tests/golden/ref/", "measured in this run"))
+
+
+def test_bench_plain_run_dumps_its_last_step(tmp_path):
+    """a plain run (no --full) times the headline alone, and --dump-outputs writes what its last timed step computed:
+    with one step and nothing in front of it, the forward transform of the benchmark's seeded input, the same in every run"""
+    import torch
+    lines, dumps = [], []
+    for run in ("a", "b"):
+        out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0",
+                                       "--settle-ms", "0", "--batch", "64", "--dump-outputs", str(tmp_path / run)],
+                                      stderr=subprocess.DEVNULL, timeout=300).decode()
+        lines += [json.loads(l) for l in out.splitlines() if l.startswith("{")]
+        dumps.append(np.load(str(tmp_path / run / "c2c65536.npy")))
+    assert len(lines) == 2
+    r = lines[0]
+    assert r["steps"] == 1 and r["warmup"] == 0 and r["ms_per_step"] > 0 and r["dtype"] == "f32"
+    assert abs(r["value"] - 64 * 65536 / (r["ms_per_step"] * 1e-3) / 1e9) <= 1e-9 * r["value"]
+    assert r["config"]["effective_warmup_launches"] == 0 and r["config"]["settle_launches"] == 0
+    assert r["cpu_baseline"] is None and r["reference_opencl_same_gpu"] is None and "ms_per_step_cold" not in r
+    for k in ("other_workloads", "out_of_place", "full_size_selfcheck", "parity_relL2_vs_oracle", "energy_checksum_all_ranks"):
+        assert k not in r["config"], k
+    assert "membench" not in r
+    y = dumps[0]
+    assert y.dtype == np.float32 and y.shape == (64, 65536, 2)
+    assert np.array_equal(dumps[0], dumps[1])
+    g = torch.Generator(device="cuda:0").manual_seed(1234)       # bench.py's input of rank 0
+    x = (torch.rand((64, 65536, 2), generator=g, device="cuda:0", dtype=torch.float32) * 2 - 1).cpu().numpy()
+    pick = [0, 37, 63]
+    xc = np.ascontiguousarray(x[pick]).view(np.complex64).reshape(len(pick), 65536)
+    yc = np.ascontiguousarray(y[pick]).view(np.complex64).reshape(len(pick), 65536)
+    assert_parity(yc, oracle.cfft(xc, True), what="dumped step vs oracle")
 
 
 def test_device_entry_points_capture_into_a_hip_graph():

@@ -5,7 +5,7 @@ TAG=$1; shift
 OUT=$PWD/gpurun_out/pmcq_$TAG; mkdir -p $OUT
 for C in FETCH_SIZE WRITE_SIZE "TCC_HIT_sum TCC_MISS_sum"; do
   D=$OUT/$(echo $C | tr ' ' '_')
-  rocprofv3 --pmc $C --kernel-trace --output-format csv -d $D -- python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline "$@" > $D.log 2>&1
+  rocprofv3 --pmc $C --kernel-trace --output-format csv -d $D -- python3 bench.py --full --steps 6 --warmup 2 --no-cpu-baseline "$@" > $D.log 2>&1
 done
 python3 - <<PY
 import csv,glob,collections

@@ -17,15 +17,15 @@ case "$*" in
   *"--workload rfft"*) STEPS=1000; WARM=300 ;;
   *"--workload pconv"*) STEPS=3000; WARM=1000 ;;
 esac
-ARGS="--steps $STEPS --warmup $WARM --no-cpu-baseline --no-bandwidth --no-other-workloads --no-cold $*"
+ARGS="--full --steps $STEPS --warmup $WARM --no-cpu-baseline --no-bandwidth --no-other-workloads --no-cold $*"
 # the driver's command line first (20 steps, 5 warm-up, yardsticks included) ...
-python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline $* > "$OUT/bench_driver_cmdline.json" 2> "$OUT/bench_unprofiled.err" || exit 1
+python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline $* > "$OUT/bench_driver_cmdline.json" 2> "$OUT/bench_unprofiled.err" || exit 1
 echo "== driver command line"; cat "$OUT/bench_driver_cmdline.json"
 python3 bench.py $ARGS > "$OUT/bench_unprofiled.json" 2>> "$OUT/bench_unprofiled.err" || exit 1
 echo "== unprofiled"; cat "$OUT/bench_unprofiled.json"
 # ... and the per-launch series of both command lines (an event after every launch: a run of its own), plus a
 # cold start without the full-size guard (the chip's start-up clock ramp)
-python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-bandwidth --no-other-workloads --series-out "$OUT/series_steps20.txt" $* > /dev/null 2>> "$OUT/bench_unprofiled.err"
+python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-bandwidth --no-other-workloads --series-out "$OUT/series_steps20.txt" $* > /dev/null 2>> "$OUT/bench_unprofiled.err"
 python3 bench.py $ARGS --series-out "$OUT/series_steps$STEPS.txt" > /dev/null 2>> "$OUT/bench_unprofiled.err"
 python3 bench.py --steps 60 --warmup 0 --settle-ms 0 --no-cpu-baseline --no-bandwidth --no-other-workloads --no-selfcheck --series-out "$OUT/series_cold_start.txt" $* > /dev/null 2>> "$OUT/bench_unprofiled.err"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 bench.py $ARGS > "$OUT/stats.log" 2>&1 || { tail -5 "$OUT/stats.log"; exit 2; }
