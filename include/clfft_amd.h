@@ -58,6 +58,7 @@ extern "C" {
 typedef struct clfa_fft clfa_fft;     /* c2c or r2c/c2r plan: Clcfft / Clrfft object */
 typedef struct clfa_pconv clfa_pconv; /* Clpconv object, `channels` independent instances */
 typedef struct clfa_dconv clfa_dconv; /* Cldconv object */
+typedef struct clfa_stft clfa_stft;   /* short-time analysis / overlap-add synthesis plan (extension) */
 
 /* ---- library / devices ---------------------------------------------------- */
 /* replaces clGetDeviceIDs(NULL, CL_DEVICE_TYPE_ALL, ...) at test_cfft.cpp:31,
@@ -193,6 +194,47 @@ CLFA_API int clfa_dconv_convolution_tv(clfa_dconv *dc, float *out, const float *
 /* device-resident variant of both (in2 may be NULL): vsize floats each, asynchronous on `stream`, one launch per
  * block; out must not be in1 or in2 */
 CLFA_API int clfa_dconv_process_dev(clfa_dconv *dc, void *out, const void *in1, const void *in2, void *stream);
+
+/* ---- short-time transforms (extension: nothing of the reference's) ----------- */
+/* A plan has size = 2^k, 64 <= size <= 16384 (the packed real sizes whose transform runs in one workgroup), a hop
+ * 1 <= hop <= size, a window w of size floats (copied at creation; NULL = rectangular) and a direction.  M = size / 2.
+ *
+ * Analysis: `channels` rows of `samples` floats, row c at signal + c * signal_stride floats (signal_stride >= samples).
+ * F = samples < size ? 0 : 1 + (samples - size) / hop frames per row (trailing samples ignored, no padding or centring:
+ * torch.stft(center=False)).  Frame (c, f) is what clfa_rfft_transform (size, forward) returns for the float32 vector
+ * fl(w[t] * x_c[f * hop + t]), t < size: the reference's packed amplitude layout and scaling (bin 0 = (DC, Nyquist), bin
+ * M/2 never conjugated).  Spectra out: channels x F x M complex64, contiguous.
+ *
+ * Synthesis: spectra channels x F x M complex64, contiguous -> rows of L = (F - 1) * hop + size floats at signal_stride.
+ * With r_f = the clfa_rfft_transform (size, inverse) output of frame f (unscaled: it gives back the windowed frame after
+ * analysis), y_c[t] = sum over the frames f that cover t, in ascending f, of w[t - f hop] * r_f[t - f hop].  normalize != 0:
+ * y_c[t] is divided by env[t] = sum of w[t - f hop]^2 over the same frames wherever env[t] > 1e-11, kept elsewhere.
+ *
+ * Device calls follow the other objects: asynchronous on `stream`, one object = one stream at a time (a change of stream
+ * waits for the previous one), capturable into a hipGraph, the current device left as found.  A direction that is not the
+ * plan's, and an output that overlaps an input even partly, are CLFA_INVALID_VALUE; F = 0 or channels = 0 is a successful
+ * no-op.  signal: any 4-byte aligned address, any stride, any hop; spectra: 8-byte aligned.  The synthesis is
+ * deterministic (no atomics): repeated calls, other streams and graph replays give the same bits. */
+/* argument errors (size, hop) are CLFA_INVALID_VALUE before any device lookup; a failed create still returns a handle */
+CLFA_API int clfa_stft_create(clfa_stft **st, int device, int size, int hop, const float *window, int forward);
+CLFA_API void clfa_stft_destroy(clfa_stft *st);
+CLFA_API int clfa_stft_get_error(const clfa_stft *st);
+CLFA_API const char *clfa_stft_get_log(const clfa_stft *st);
+/* F of `samples`, and L of `frames` (0 for frames = 0) */
+CLFA_API long clfa_stft_frames(const clfa_stft *st, long samples);
+CLFA_API long clfa_stft_samples(const clfa_stft *st, long frames);
+/* device-resident: one launch each */
+CLFA_API int clfa_stft_analyze_dev(clfa_stft *st, const void *signal, long signal_stride, long samples, long channels,
+                                   void *spectra, void *stream);
+CLFA_API int clfa_stft_synthesize_dev(clfa_stft *st, const void *spectra, long frames, long channels, void *signal,
+                                      long signal_stride, int normalize, void *stream);
+/* host arrays, copied in and out, blocking (like clfa_rfft_transform) */
+CLFA_API int clfa_stft_analyze(clfa_stft *st, const float *signal, long signal_stride, long samples, long channels,
+                               float *spectra);
+CLFA_API int clfa_stft_synthesize(clfa_stft *st, const float *spectra, long frames, long channels, float *signal,
+                                  long signal_stride, int normalize);
+CLFA_API size_t clfa_stft_workspace_bytes(const clfa_stft *st);
+CLFA_API const char *clfa_stft_kernel_name(const clfa_stft *st);
 
 #ifdef __cplusplus
 }

@@ -7,6 +7,7 @@ meaning and integer OpenCL status codes), over the C ABI of libclfft_amd.so:
     Clrfft   cl_fft.h:74-111    packed real FFT
     Clpconv  cl_conv.h:124-188  uniformly partitioned overlap-add convolution
     Cldconv  cl_dconv.h:17-66   direct convolution
+    Stft     (extension)        short-time analysis / windowed overlap-add synthesis on the Clrfft layout
 
 Like the reference, constructors never raise: a failed setup is read back with
 ``get_error()`` / ``get_cl_err()`` and every method returns the status code.
@@ -24,7 +25,8 @@ import numpy as np
 from ._lib import ClError, check, lib
 
 __all__ = ["Clcfft", "Clrfft", "Clpconv", "Cldconv", "ClError", "cl_error_string", "device_count",
-           "device_name", "bitrev_table", "twiddle_table", "r2c_twiddle_table", "reorder_device", "PI"]
+           "device_name", "bitrev_table", "twiddle_table", "r2c_twiddle_table", "reorder_device", "PI",
+           "Stft", "packed_to_onesided", "onesided_to_packed"]
 
 PI = 3.141592653589793  # cl_fft.h:24
 CL_SUCCESS = 0
@@ -192,6 +194,142 @@ class Clrfft(_Plan):
                 return CL_INVALID_VALUE
             rp = r.ctypes.data
         return lib().clfa_rfft_transform(self._h, c.ctypes.data, rp, c.size // self.N)
+
+
+def _row_view(t, what):
+    """(pointer, rows, row length, row stride) of a (rows, n) or (n,) torch tensor whose rows are contiguous"""
+    if t.dim() == 1:
+        t = t.unsqueeze(0)
+    if t.dim() != 2 or t.stride(1) != 1:
+        raise ValueError("%s: expected (channels, n) with contiguous rows" % what)
+    return t.data_ptr(), t.shape[0], t.shape[1], t.stride(0)
+
+
+class Stft:
+    """Short-time transforms on the packed real layout of Clrfft (extension, clfa_stft in clfft_amd.h).
+
+    fwd=True: analyze() frames (channels, samples) float32 rows (frame f = window * x[f*hop : f*hop + size], no
+    padding) into (channels, F, size/2) complex64 spectra, each what Clrfft(size, True) returns for that frame.
+    fwd=False: synthesize() runs Clrfft(size, False) on every frame, multiplies by the window and overlap-adds the frames
+    into rows of (F - 1) * hop + size floats, optionally divided by the window envelope sum_f w^2.
+    Like the other plans the constructor does not raise: get_error() / get_log() report a failed setup."""
+
+    def __init__(self, device_id, size, hop, window=None, fwd=True):
+        self.size, self.hop, self.forward = int(size), int(hop), bool(fwd)
+        self.M = self.size // 2
+        if window is not None:
+            if hasattr(window, "detach"):
+                window = window.detach().cpu().numpy()
+            window = np.ascontiguousarray(window, dtype=np.float32).reshape(-1)
+            if window.size != self.size:
+                raise ValueError("window must hold size = %d floats" % self.size)
+        self._win = window
+        h = C.c_void_p()
+        lib().clfa_stft_create(C.byref(h), int(device_id), self.size, self.hop,
+                               None if window is None else window.ctypes.data, int(self.forward))
+        self._h = h
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and lib is not None:
+            lib().clfa_stft_destroy(h)
+
+    def get_error(self):
+        return lib().clfa_stft_get_error(self._h)
+
+    def get_log(self):
+        return lib().clfa_stft_get_log(self._h).decode()
+
+    def kernel_name(self):
+        return lib().clfa_stft_kernel_name(self._h).decode()
+
+    def workspace_bytes(self):
+        return lib().clfa_stft_workspace_bytes(self._h)
+
+    def frames(self, samples):
+        """F = 0 if samples < size else 1 + (samples - size) // hop"""
+        return lib().clfa_stft_frames(self._h, int(samples))
+
+    def samples(self, frames):
+        """L = (frames - 1) * hop + size (0 for no frames)"""
+        return lib().clfa_stft_samples(self._h, int(frames))
+
+    def analyze(self, x):
+        """host: float32 (channels, samples) or (samples,) -> complex64 (channels, F, size/2) (leading axis kept)"""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        x2 = x.reshape(1, -1) if x.ndim == 1 else x
+        F = self.frames(x2.shape[1])
+        out = np.zeros((x2.shape[0], F, self.M), np.complex64)
+        check(lib().clfa_stft_analyze(self._h, x2.ctypes.data, x2.shape[1], x2.shape[1], x2.shape[0], out.ctypes.data),
+              "Stft.analyze")
+        return out[0] if x.ndim == 1 else out
+
+    def synthesize(self, spec, normalize=False):
+        """host: complex64 (channels, F, size/2) or (F, size/2) -> float32 (channels, (F - 1) * hop + size)"""
+        spec = np.ascontiguousarray(spec, dtype=np.complex64)
+        s3 = spec.reshape((1,) + spec.shape) if spec.ndim == 2 else spec
+        if s3.ndim != 3 or s3.shape[2] != self.M:
+            raise ValueError("spectra must be (channels, F, %d)" % self.M)
+        L = self.samples(s3.shape[1])
+        out = np.zeros((s3.shape[0], L), np.float32)
+        check(lib().clfa_stft_synthesize(self._h, s3.ctypes.data, s3.shape[1], s3.shape[0], out.ctypes.data, L,
+                                         int(bool(normalize))), "Stft.synthesize")
+        return out[0] if spec.ndim == 2 else out
+
+    def analyze_device(self, signal, out, stream=None):
+        """torch: signal (channels, samples) float32 (row stride taken from the tensor: padded rows work) ->
+        out (channels, F, size/2) complex64, contiguous; asynchronous on `stream` (default: the current stream)"""
+        p, rows, n, stride = _row_view(signal, "signal")
+        if not out.is_contiguous():
+            raise ValueError("spectra tensor must be contiguous")
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream(signal.device).cuda_stream
+        return lib().clfa_stft_analyze_dev(self._h, p, stride, n, rows, out.data_ptr(), stream)
+
+    def synthesize_device(self, spectra, out, normalize=False, stream=None):
+        """torch: spectra (channels, F, size/2) complex64, contiguous -> out (channels, >= (F - 1) * hop + size) float32,
+        row stride from the tensor; asynchronous on `stream`"""
+        if not spectra.is_contiguous():
+            raise ValueError("spectra tensor must be contiguous")
+        s3 = spectra if spectra.dim() == 3 else spectra.unsqueeze(0)
+        p, rows, _, stride = _row_view(out, "signal")
+        if rows != s3.shape[0]:
+            raise ValueError("out has %d rows for %d channels" % (rows, s3.shape[0]))
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream(out.device).cuda_stream
+        return lib().clfa_stft_synthesize_dev(self._h, spectra.data_ptr(), s3.shape[1], s3.shape[0], p, stride,
+                                              int(bool(normalize)), stream)
+
+
+def packed_to_onesided(spec):
+    """Clrfft's packed spectra (..., M) -> the M + 1 bins of np.fft.rfft / torch.stft(onesided) (numpy or torch):
+    X[0] = size Re P[0], X[M] = size Im P[0], X[M/2] = (size/2) conj(P[M/2]), X[k] = (size/2) P[k] otherwise."""
+    M = spec.shape[-1]
+    size = 2 * M
+    if hasattr(spec, "clone"):
+        import torch
+        X = torch.cat([spec * (size / 2), spec[..., :1].imag.to(spec.dtype) * size], dim=-1)
+    else:
+        X = np.concatenate([spec * (size / 2), (spec[..., :1].imag * size).astype(spec.dtype)], axis=-1)
+    X[..., 0] = spec[..., 0].real * size
+    X[..., M // 2] = spec[..., M // 2].conj() * (size / 2)
+    return X
+
+
+def onesided_to_packed(X):
+    """the inverse of packed_to_onesided: (..., M + 1) one-sided bins -> (..., M) packed (Im X[0], Im X[M] dropped)"""
+    M = X.shape[-1] - 1
+    size = 2 * M
+    P = X[..., :M] * (2.0 / size)
+    if hasattr(P, "clone"):
+        P = P.clone()
+    else:
+        P = P.copy()
+    P[..., 0] = (X[..., 0].real + 1j * X[..., M].real) / size
+    P[..., M // 2] = X[..., M // 2].conj() * (2.0 / size)
+    return P
 
 
 def bandwidth_probe(device_id=0, nbytes=1 << 30, launches=100):

@@ -65,6 +65,18 @@ SYMBOLS = [
     ("clfa_dconv_convolution", C.c_int, [_vp, _vp, _vp]),
     ("clfa_dconv_convolution_tv", C.c_int, [_vp, _vp, _vp, _vp]),
     ("clfa_dconv_process_dev", C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    ("clfa_stft_create", C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.c_int, _vp, C.c_int]),
+    ("clfa_stft_destroy", None, [_vp]),
+    ("clfa_stft_get_error", C.c_int, [_vp]),
+    ("clfa_stft_get_log", C.c_char_p, [_vp]),
+    ("clfa_stft_frames", C.c_long, [_vp, C.c_long]),
+    ("clfa_stft_samples", C.c_long, [_vp, C.c_long]),
+    ("clfa_stft_analyze_dev", C.c_int, [_vp, _vp, C.c_long, C.c_long, C.c_long, _vp, _vp]),
+    ("clfa_stft_synthesize_dev", C.c_int, [_vp, _vp, C.c_long, C.c_long, _vp, C.c_long, C.c_int, _vp]),
+    ("clfa_stft_analyze", C.c_int, [_vp, _vp, C.c_long, C.c_long, C.c_long, _vp]),
+    ("clfa_stft_synthesize", C.c_int, [_vp, _vp, C.c_long, C.c_long, _vp, C.c_long, C.c_int]),
+    ("clfa_stft_workspace_bytes", C.c_size_t, [_vp]),
+    ("clfa_stft_kernel_name", C.c_char_p, [_vp]),
 ]
 
 _LIB = None

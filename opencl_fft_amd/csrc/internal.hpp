@@ -162,6 +162,27 @@ constexpr int kPconvMaxLogBins = 15;   // pts up to 32768 (the reference harness
 hipError_t launch_pconv_pad(const float *in, long in_stride, cpx *work, int bins, int channels, hipStream_t s);
 hipError_t launch_pconv_olap(const float *work, float *tail, float *out, int bins, int channels, hipStream_t s);
 
+// ---- short-time transforms (stft_kernels.hip) --------------------------------------
+// packed real size 2^(logn + 1), logn 5..kLdsMaxLog.  forward: channels rows of `signal` (row c at c * stride floats) ->
+// spec_out, nframes = channels * F frames of n complex; inverse: spec_in (nframes frames) -> rows of `out`, L = (F - 1) hop
+// + size floats each.  window: size floats; cum (inverse, normalize only): [lo | hi] running sums of window^2 along steps
+// of hop (2 * size floats); half / w2: the Clrfft tables of the direction.  aligned8: every frame start is 8-byte aligned.
+struct StftArgs {
+  int logn = 0;
+  bool forward = true;
+  int hop = 1, F = 0;
+  long channels = 0, nframes = 0, stride = 0;
+  bool aligned8 = true;
+  int normalize = 0;
+  const float *signal = nullptr;
+  float *out = nullptr;
+  const cpx *spec_in = nullptr;
+  cpx *spec_out = nullptr;
+  const float *window = nullptr, *cum = nullptr;
+  const cpx *half = nullptr, *w2 = nullptr;
+};
+hipError_t launch_stft(const StftArgs &a, const DeviceInfo &di, hipStream_t s);
+
 // ---- direct convolution ----------------------------------------------------------
 struct DconvPlan {
   int C;    // taps per workgroup
