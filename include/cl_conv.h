@@ -47,6 +47,10 @@ class Clpconv {
   int convolution(float *output, float *input1, float *input2);
   /** device-resident extension (in2 may be NULL) */
   int convolution_device(void *out, const void *in1, const void *in2, void *stream = 0);
+  /** device-resident extension, nblocks consecutive blocks per channel (row c at c * stride floats; in2 may be NULL):
+      the same as nblocks convolution_device calls (clfa_pconv_process_blocks_dev) */
+  int convolution_blocks_device(void *out, long out_stride, const void *in1, const void *in2, long in_stride,
+                                long nblocks, void *stream = 0);
   int get_cl_err() { return cl_err; }
 };
 }  // namespace cl_conv

@@ -182,6 +182,28 @@ CLFA_API size_t clfa_pconv_state_bytes(const clfa_pconv *pc);
 /* which launch structure a block of this object takes (diagnostics and tests): "k_pconv_fused" (one launch, one
  * workgroup per channel), "k_pconv_coop" (one launch, a few channels), "chain" (forward / MAC / inverse launches) */
 CLFA_API const char *clfa_pconv_kernel_name(const clfa_pconv *pc);
+/* Many blocks per call (extension): a whole signal, or a long stretch of it, per channel.
+ * nblocks consecutive blocks per channel: block j of channel c is in1 + c*in_stride + j*pts (pts floats), same for in2
+ * and out.  The call equals nblocks calls of clfa_pconv_process_dev, one per block j in ascending order, where call j gets
+ * the channels x pts gather of block j (and of in2 when it is non-NULL, the time-varying form); the object's state
+ * afterwards (wp, wp2, both rings, the overlap-add tail) is the state those calls leave, so single-block calls and
+ * push_ir mix freely with it.  Every output bin sums the partitions in ascending order with one accumulator: results are
+ * bit-identical however a signal is split into calls, and across repeated calls, streams and graph replay; against the
+ * single-block calls they agree to rounding (which routes match them bit for bit: DESIGN.md, section 4.5).
+ * Arguments: nblocks == 0 succeeds and does nothing; in_stride >= nblocks*pts and out_stride >= nblocks*pts; addresses
+ * 4-byte aligned, any stride.  out overlapping an input even partly, or any other bad argument: CLFA_INVALID_VALUE, and
+ * the state is untouched.  Streams, the current device and hipGraph capture work as for clfa_pconv_process_dev.
+ * Workspace: allocated by the first call that needs it (clfa_pconv_blocks_workspace_bytes() = what is held), released
+ * with the object; a call under capture that would have to allocate it returns CLFA_INVALID_OPERATION.  Long calls run
+ * in sub-batches of an internal cap (time-varying: at most nparts blocks each). */
+CLFA_API int clfa_pconv_process_blocks_dev(clfa_pconv *pc, void *out, long out_stride, const void *in1, const void *in2,
+                                           long in_stride, long nblocks, void *stream);
+/* host form: rows contiguous (stride nblocks*pts), blocking */
+CLFA_API int clfa_pconv_convolution_blocks(clfa_pconv *pc, float *out, const float *in1, const float *in2, long nblocks);
+CLFA_API size_t clfa_pconv_blocks_workspace_bytes(const clfa_pconv *pc);
+/* "k_pconvb_mac" (partitions of 32..4096 samples: four launches per sub-batch), "loop" (other sizes: the single-block
+ * route once per block inside the call) */
+CLFA_API const char *clfa_pconv_blocks_kernel_name(const clfa_pconv *pc);
 
 /* ---- direct convolution: cl_conv::Cldconv ----------------------------------- */
 /* Cldconv::Cldconv(device_id, cvs, vsize, ...), cl_dconv.cpp:46-98 */

@@ -437,6 +437,57 @@ class Clpconv:
         p2 = _ptr_stream(in2, stream)[0] if in2 is not None else None
         return lib().clfa_pconv_process_dev(self._h, po, p1, p2, stream)
 
+    # ---- many blocks per call (extension): clfa_pconv_process_blocks_dev, include/clfft_amd.h
+    def blocks_kernel_name(self):
+        """"k_pconvb_mac" (partitions of 32..4096 samples) or "loop" (the single-block route once per block)"""
+        return lib().clfa_pconv_blocks_kernel_name(self._h).decode()
+
+    def blocks_workspace_bytes(self):
+        return lib().clfa_pconv_blocks_workspace_bytes(self._h)
+
+    def convolution_blocks(self, output, input1, input2=None):
+        """whole signals: float32[channels, nblocks*pts] (or 1-D for one channel); equals nblocks calls of
+        convolution(), blocking"""
+        output = _host(output, np.float32)
+        a = np.ascontiguousarray(input1, dtype=np.float32)
+        if a.ndim == 1:
+            a = a[None, :]
+        if a.ndim != 2 or a.shape[0] != self.channels or a.shape[1] % self.pts or output.size != a.size:
+            return CL_INVALID_VALUE
+        b = None
+        if input2 is not None:
+            b = np.ascontiguousarray(input2, dtype=np.float32)
+            if b.size != a.size:
+                return CL_INVALID_VALUE
+        return lib().clfa_pconv_convolution_blocks(self._h, output.ctypes.data, a.ctypes.data,
+                                                   None if b is None else b.ctypes.data, a.shape[1] // self.pts)
+
+    def process_blocks_device(self, out, in1, in2=None, stream=None):
+        """device tensors (channels, L) of float32 (1-D for one channel), stride(1) == 1, L % pts == 0; the row stride
+        of each is its stride(0) (views into longer rows are fine).  Asynchronous on `stream`."""
+        def rows(t):
+            if t.dim() == 1:
+                return t.shape[0], max(t.shape[0], 1)
+            if t.dim() != 2 or t.shape[0] != self.channels or (t.shape[1] > 1 and t.stride(1) != 1):
+                raise ValueError("expected a (channels, L) float32 tensor with stride(1) == 1")
+            return t.shape[1], t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+        ts = [out, in1] + ([in2] if in2 is not None else [])
+        for t in ts:
+            if str(t.dtype) != "torch.float32" or (t.dim() == 1 and self.channels != 1):
+                raise ValueError("expected a (channels, L) float32 tensor with stride(1) == 1")
+        (lo, so), (l1, s1) = rows(out), rows(in1)
+        s2 = rows(in2)[1] if in2 is not None else s1
+        if lo != l1 or (in2 is not None and rows(in2)[0] != l1) or l1 % self.pts:
+            return CL_INVALID_VALUE
+        if in2 is not None and s2 != s1:
+            return CL_INVALID_VALUE   # one stride for both inputs (the ABI's in_stride)
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream(in1.device).cuda_stream
+        return lib().clfa_pconv_process_blocks_dev(self._h, out.data_ptr(), so, in1.data_ptr(),
+                                                   in2.data_ptr() if in2 is not None else None, s1,
+                                                   l1 // self.pts, stream)
+
 
 class Cldconv:
     """cl_conv::Cldconv(device_id, cvs, vsize, errs=NULL, uData=NULL) (cl_dconv.h:17-66)"""

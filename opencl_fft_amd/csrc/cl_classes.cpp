@@ -83,6 +83,10 @@ int Clpconv::convolution(float *output, float *input1, float *input2) {         
 int Clpconv::convolution_device(void *out, const void *in1, const void *in2, void *stream) {
   return cl_err = clfa_pconv_process_dev(pc, out, in1, in2, stream);
 }
+int Clpconv::convolution_blocks_device(void *out, long out_stride, const void *in1, const void *in2, long in_stride,
+                                       long nblocks, void *stream) {
+  return cl_err = clfa_pconv_process_blocks_dev(pc, out, out_stride, in1, in2, in_stride, nblocks, stream);
+}
 
 // Cldconv, cl_dconv.cpp:46-153
 Cldconv::Cldconv(cl_device_id device_id, int cvs, int vsiz, void (*errs)(std::string s, void *d), void *uData)

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -302,6 +303,10 @@ struct clfa_pconv {
   PconvCoop coop{-1, 1};             // few channels: one cooperative launch per block (logs >= 0)
   DevBuf cnt;                        // ... its arrival counters (one per channel)
   FftTables big;
+  // multi-block calls (clfa_pconv_process_blocks_dev): workspaces allocated by the first call that needs them
+  int bcap = 1;                      // blocks per sub-batch (CLFA_PCONV_BLOCKS_MAX: tuning switch, read at creation)
+  int bkt = 4;                       // outputs per MAC tile
+  DevBuf bX, bXB, bY, btail, bstage; // spectra of the new blocks / second inputs, output spectra, new tail; loop staging
 };
 
 struct clfa_dconv {
@@ -1040,6 +1045,15 @@ static int pconv_setup(clfa_pconv *p, int device, int cvs, int pts, int channels
   if (e) return e;
   p->fused = pconv_fused_ok(p->g, p->di) && !getenv("CLFA_PCONV_NO_FUSE");   // tuning switch, read once
   if (!p->fused) p->coop = pconv_coop_plan(p->g, p->di);
+  {
+    // multi-block sub-batches: the three channels x cap x bins complex workspaces within ~384 MiB, at most 1024 blocks
+    const long per_block = 3L * channels * pts * (long)sizeof(cpx);
+    long cap = (384L << 20) / per_block;
+    const char *env = getenv("CLFA_PCONV_BLOCKS_MAX");   // read per object, like CLFA_PCONV_COOP_MAX_KB
+    if (env && atol(env) > 0 && atol(env) < cap) cap = atol(env);
+    p->bcap = (int)(cap < 1 ? 1 : (cap > 1024 ? 1024 : cap));
+    p->bkt = pconv_blocks_tile(p->g, p->di);
+  }
   ENTER_DEVICE(device);
   HIP_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
   std::vector<cpx> h;
@@ -1095,7 +1109,8 @@ void clfa_pconv_destroy(clfa_pconv *p) {
     (void)hipStreamDestroy(p->stream);
   }
   for (DevBuf *b : {&p->half, &p->w2f, &p->w2i, &p->ringA, &p->ringB, &p->acc, &p->tail, &p->in1, &p->in2,
-                    &p->out, &p->ir, &p->four, &p->scratch, &p->work, &p->cnt})
+                    &p->out, &p->ir, &p->four, &p->scratch, &p->work, &p->cnt, &p->bX, &p->bXB, &p->bY, &p->btail,
+                    &p->bstage})
     b->release();
   p->zin1.release();
   p->zin2.release();
@@ -1272,6 +1287,157 @@ int clfa_pconv_convolution(clfa_pconv *p, float *out, const float *in) { return 
 int clfa_pconv_convolution_tv(clfa_pconv *p, float *out, const float *in1, const float *in2) {
   if (!in2) return CLFA_INVALID_VALUE;
   return pconv_host(p, out, in1, in2);
+}
+
+// ---- many blocks per call -------------------------------------------------------
+
+static bool pconv_blocks_looped(const clfa_pconv *p) {
+  return p->g.logb < kPconvBlocksMinLog || p->g.logb > kPconvBlocksMaxLog;
+}
+
+const char *clfa_pconv_blocks_kernel_name(const clfa_pconv *p) {
+  if (!p || p->err) return "";
+  return pconv_blocks_looped(p) ? "loop" : "k_pconvb_mac";
+}
+
+size_t clfa_pconv_blocks_workspace_bytes(const clfa_pconv *p) {
+  return p ? p->bX.bytes + p->bXB.bytes + p->bY.bytes + p->btail.bytes + p->bstage.bytes : 0;
+}
+
+// rows r < rows of a at a + r * sa and of b at b + r * sb (len bytes each, strides >= len): does any row of a share a
+// byte with any row of b?  For row i of a, the rows k of b that could touch it form one interval of k.
+static bool rows_overlap(const void *a, long sa, const void *b, long sb, long rows, long len) {
+  auto fdiv = [](long x, long y) { return x >= 0 ? x / y : -((-x + y - 1) / y); };   // floor, y > 0
+  const long base = (long)((const char *)a - (const char *)b);   // (pointer difference as a plain offset)
+  if (rows <= 1) sa = sb = len;
+  for (long i = 0; i < rows; i++) {
+    const long d = base + i * sa;                  // row i of a starts d bytes after row 0 of b
+    long kmin = fdiv(d - len, sb) + 1;             // k sb > d - len
+    long kmax = -fdiv(-(d + len), sb) - 1;         // k sb < d + len
+    kmin = kmin < 0 ? 0 : kmin;
+    kmax = kmax > rows - 1 ? rows - 1 : kmax;
+    if (kmin <= kmax) return true;
+  }
+  return false;
+}
+
+// workspaces of a multi-block call: allocated once, never while the stream is captured (a hipMalloc there would be
+// outside the graph)
+static int pconv_blocks_ws(clfa_pconv *p, bool tv, hipStream_t s) {
+  const size_t ch = (size_t)p->g.channels, bins = (size_t)p->pts;
+  struct Want {
+    DevBuf *b;
+    size_t bytes;
+  };
+  std::vector<Want> want;
+  if (pconv_blocks_looped(p)) {
+    want.push_back({&p->bstage, sizeof(float) * ch * bins * 3});
+  } else {
+    const size_t frames = sizeof(cpx) * ch * (size_t)p->bcap * bins;
+    want.push_back({&p->bX, frames});
+    want.push_back({&p->bY, frames});
+    want.push_back({&p->btail, sizeof(float) * ch * bins});
+    if (tv) want.push_back({&p->bXB, frames});
+  }
+  bool missing = false;
+  for (const Want &w : want) missing = missing || w.b->bytes < w.bytes;
+  if (!missing) return CLFA_SUCCESS;
+  if (StreamOrder::capturing(s)) return CLFA_INVALID_OPERATION;
+  for (const Want &w : want) {
+    int e = w.b->ensure(w.bytes);
+    if (e) return e;
+  }
+  return CLFA_SUCCESS;
+}
+
+int clfa_pconv_process_blocks_dev(clfa_pconv *p, void *out, long out_stride, const void *in1, const void *in2,
+                                  long in_stride, long nblocks, void *stream) {
+  if (!p) return CLFA_INVALID_VALUE;
+  if (p->err) return p->err;
+  if (nblocks < 0) return CLFA_INVALID_VALUE;
+  if (nblocks == 0) return CLFA_SUCCESS;
+  const long pts = p->pts, ch = p->g.channels, nparts = p->g.nparts;
+  if (!out || !in1 || nblocks > 0x7fffffffL / pts) return CLFA_INVALID_VALUE;
+  const long len = nblocks * pts;
+  if (in_stride < len || out_stride < len) return CLFA_INVALID_VALUE;
+  auto misaligned = [](const void *q) { return ((uintptr_t)q & 3) != 0; };
+  if (misaligned(out) || misaligned(in1) || (in2 && misaligned(in2))) return CLFA_INVALID_VALUE;
+  const long lb = len * (long)sizeof(float);
+  const long osb = out_stride * (long)sizeof(float), isb = in_stride * (long)sizeof(float);
+  if (rows_overlap(out, osb, in1, isb, ch, lb) || (in2 && rows_overlap(out, osb, in2, isb, ch, lb))) return CLFA_INVALID_VALUE;
+  ENTER_DEVICE(p->di.device);
+  hipStream_t s = (hipStream_t)stream;
+  int e = pconv_blocks_ws(p, in2 != nullptr, s);
+  if (e) return e;
+  HIP_TRY(p->order.use(s));
+  const float *a1 = (const float *)in1, *a2 = (const float *)in2;
+  float *o = (float *)out;
+  if (pconv_blocks_looped(p)) {
+    // partitions outside the LDS transform sizes: block by block through clfa_pconv_process_dev, each block gathered into
+    // contiguous channels x pts staging (any alignment and stride) and scattered back
+    float *st1 = (float *)p->bstage.p, *st2 = st1 + ch * pts, *sto = st2 + ch * pts;
+    const size_t row = sizeof(float) * (size_t)pts;
+    for (long j = 0; j < nblocks; j++) {
+      HIP_TRY(hipMemcpy2DAsync(st1, row, a1 + j * pts, (size_t)isb, row, (size_t)ch, hipMemcpyDeviceToDevice, s));
+      if (a2) HIP_TRY(hipMemcpy2DAsync(st2, row, a2 + j * pts, (size_t)isb, row, (size_t)ch, hipMemcpyDeviceToDevice, s));
+      if ((e = clfa_pconv_process_dev(p, sto, st1, a2 ? st2 : nullptr, stream))) return e;
+      HIP_TRY(hipMemcpy2DAsync(o + j * pts, (size_t)osb, sto, row, row, (size_t)ch, hipMemcpyDeviceToDevice, s));
+    }
+    return CLFA_SUCCESS;
+  }
+  PconvBlocks a;
+  a.g = p->g;
+  a.cap = p->bcap;
+  a.kt = p->bkt;
+  a.in_stride = in_stride;
+  a.out_stride = out_stride;
+  a.aligned_in = ((uintptr_t)in1 & 7) == 0 && (!in2 || ((uintptr_t)in2 & 7) == 0) && (in_stride & 1) == 0;
+  a.aligned_out = ((uintptr_t)out & 7) == 0 && (out_stride & 1) == 0;
+  a.ringA = (cpx *)p->ringA.p;
+  a.ringB = (cpx *)p->ringB.p;
+  a.tail = (float *)p->tail.p;
+  a.X = (cpx *)p->bX.p;
+  a.XB = (cpx *)p->bXB.p;
+  a.Y = (cpx *)p->bY.p;
+  a.tail_ws = (float *)p->btail.p;
+  a.half = (const cpx *)p->half.p;
+  a.w2f = (const cpx *)p->w2f.p;
+  a.w2i = (const cpx *)p->w2i.p;
+  // time-varying sub-batches stay within nparts blocks: each second-input ring frame then changes at most once
+  const long kmax = in2 && nparts < p->bcap ? nparts : p->bcap;
+  for (long j0 = 0; j0 < nblocks; j0 += kmax) {
+    a.K = (int)(nblocks - j0 < kmax ? nblocks - j0 : kmax);
+    a.w = p->wp;
+    a.w2 = p->wp2;
+    a.in1 = a1 + j0 * pts;
+    a.in2 = a2 ? a2 + j0 * pts : nullptr;
+    a.out = o + j0 * pts;
+    HIP_TRY(launch_pconv_blocks(a, s));
+    p->wp = (int)((p->wp + a.K) % nparts);
+    if (a2) p->wp2 = (int)(((p->wp2 - a.K) % nparts + nparts) % nparts);
+  }
+  return CLFA_SUCCESS;
+}
+
+int clfa_pconv_convolution_blocks(clfa_pconv *p, float *out, const float *in1, const float *in2, long nblocks) {
+  if (!p) return CLFA_INVALID_VALUE;
+  if (p->err) return p->err;
+  if (nblocks < 0) return CLFA_INVALID_VALUE;
+  if (nblocks == 0) return CLFA_SUCCESS;
+  if (!out || !in1 || nblocks > 0x7fffffffL / p->pts) return CLFA_INVALID_VALUE;
+  const long len = nblocks * p->pts;
+  const size_t bytes = sizeof(float) * (size_t)len * p->g.channels;
+  if (ranges_overlap(out, in1, bytes) || (in2 && ranges_overlap(out, in2, bytes))) return CLFA_INVALID_VALUE;
+  ENTER_DEVICE(p->di.device);
+  int e;
+  if ((e = p->in1.ensure(bytes)) || (e = p->out.ensure(bytes)) || (in2 && (e = p->in2.ensure(bytes)))) return e;
+  HIP_TRY(hipMemcpyAsync(p->in1.p, in1, bytes, hipMemcpyHostToDevice, p->stream));
+  if (in2) HIP_TRY(hipMemcpyAsync(p->in2.p, in2, bytes, hipMemcpyHostToDevice, p->stream));
+  if ((e = clfa_pconv_process_blocks_dev(p, p->out.p, len, p->in1.p, in2 ? p->in2.p : nullptr, len, nblocks, p->stream)))
+    return e;
+  HIP_TRY(hipMemcpyAsync(out, p->out.p, bytes, hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return CLFA_SUCCESS;
 }
 
 // ---------------------------------------------------------------------------------

@@ -157,6 +157,28 @@ bool pconv_fused_ok(const PconvGeom &g, const DeviceInfo &di);
 hipError_t launch_pconv_fused(const PconvGeom &g, const float *in1, const float *in2, cpx *ringA, cpx *ringB,
                               float *tail, float *out, int frame1, int frame2, int wp, const cpx *half,
                               const cpx *w2f, const cpx *w2i, hipStream_t s, bool deep = false);   // deep: fewer channels than CUs
+// K consecutive blocks of every channel in four launches (pconv_blocks.hip), bins 32..4096: in1 / in2 / out point at
+// block 0 of the sub-batch (row c at c * stride floats); X, Y (and XB, time-varying) are channels x cap x bins complex
+// workspaces, tail_ws channels x bins floats.  w / w2: the object's wp / wp2 before the sub-batch; K <= cap, and
+// K <= nparts when in2 is set.  The rings and the tail are written only by the last launch, after every read.
+struct PconvBlocks {
+  PconvGeom g;
+  int K = 0, cap = 0, w = 0, w2 = 0;
+  int kt = 4;     // outputs per MAC tile: pconv_blocks_tile()
+  int run = 8;    // blocks per inverse run
+  const float *in1 = nullptr, *in2 = nullptr;
+  long in_stride = 0, out_stride = 0;
+  float *out = nullptr;
+  int aligned_in = 1, aligned_out = 1;   // every row start 8-byte aligned
+  cpx *ringA = nullptr, *ringB = nullptr;
+  float *tail = nullptr;
+  cpx *X = nullptr, *XB = nullptr, *Y = nullptr;
+  float *tail_ws = nullptr;
+  const cpx *half = nullptr, *w2f = nullptr, *w2i = nullptr;
+};
+int pconv_blocks_tile(const PconvGeom &g, const DeviceInfo &di);
+hipError_t launch_pconv_blocks(const PconvBlocks &a, hipStream_t s);
+constexpr int kPconvBlocksMinLog = 5, kPconvBlocksMaxLog = 12;
 constexpr int kPconvMaxLogBins = 15;   // pts up to 32768 (the reference harness' largest, csound/tests.py:13)
 // ends of the composed chain used when bins exceed the LDS FFT sizes
 hipError_t launch_pconv_pad(const float *in, long in_stride, cpx *work, int bins, int channels, hipStream_t s);
