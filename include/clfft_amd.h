@@ -59,6 +59,7 @@ typedef struct clfa_fft clfa_fft;     /* c2c or r2c/c2r plan: Clcfft / Clrfft ob
 typedef struct clfa_pconv clfa_pconv; /* Clpconv object, `channels` independent instances */
 typedef struct clfa_dconv clfa_dconv; /* Cldconv object */
 typedef struct clfa_stft clfa_stft;   /* short-time analysis / overlap-add synthesis plan (extension) */
+typedef struct clfa_pconv_matrix clfa_pconv_matrix; /* convolution matrix: inputs mixed into outputs (extension) */
 
 /* ---- library / devices ---------------------------------------------------- */
 /* replaces clGetDeviceIDs(NULL, CL_DEVICE_TYPE_ALL, ...) at test_cfft.cpp:31,
@@ -257,6 +258,54 @@ CLFA_API int clfa_stft_synthesize(clfa_stft *st, const float *spectra, long fram
                                   long signal_stride, int normalize);
 CLFA_API size_t clfa_stft_workspace_bytes(const clfa_stft *st);
 CLFA_API const char *clfa_stft_kernel_name(const clfa_stft *st);
+
+/* ---- convolution matrix (extension: nothing of the reference's) ------------- */
+/* Uniformly partitioned overlap-add convolution of `inputs` signals with an outputs x inputs matrix of static responses:
+ * y_o = sum over i of x_i * h_{o,i}.
+ *
+ * Creation: pts a power of two, 32..4096 (other sizes: CLFA_INVALID_VALUE), nparts = cvs / pts (floor, as Clpconv) >= 1,
+ * inputs >= 1, outputs >= 1.  A failed creation still returns a handle; get_error / get_log report the error.
+ * Responses: push_ir takes outputs x inputs rows of nparts*pts floats, row (o, i) at (o*inputs + i) * nparts*pts;
+ * push_ir_dev reads the rows at row_stride >= nparts*pts floats (4-byte aligned).  A push replaces the whole matrix and
+ * applies from the next block; the input history and the overlap-add tails are kept (as Clpconv::push_ir keeps ring A).
+ * A fresh object has zero responses and zero history.
+ *
+ * process_dev: `inputs` rows of nblocks*pts floats (row i at in + i*in_stride) -> `outputs` rows of the same length
+ * (row o at out + o*out_stride).  Block j of output o equals the sum over i of what a Clpconv(cvs, pts) instance holding
+ * h_{o,i} returns for block j of input i (in exact arithmetic).  A call of K blocks equals K calls of one block and leaves
+ * the same state.
+ *
+ * Numerics: for every output bin the products x_i(block) h_{o,i}(partition) are summed in a fixed order: the sequence
+ * r = i*nparts + p (inputs ascending, and within an input the partitions from the oldest input block to the newest) is cut
+ * at creation into S segments [floor(s*inputs*nparts/S), floor((s+1)*inputs*nparts/S)); each segment is one float32
+ * accumulator over its r ascending, and the segment sums are added as ((seg_0 + seg_1) + seg_2) + ...  S depends on the
+ * geometry alone (inputs, outputs, pts, nparts, device), never on K, the sub-batch, the split of a signal into calls, the
+ * stream or graph replay: all of these give the same bits.
+ *
+ * Arguments as clfa_pconv_process_blocks_dev: nblocks == 0 succeeds and does nothing; in_stride, out_stride >=
+ * nblocks*pts; any 4-byte aligned address and stride.  out overlapping in even partly, or any other bad argument:
+ * CLFA_INVALID_VALUE, and the state is untouched.  One object runs on one stream at a time (a change of stream waits for
+ * the previous one); capturable into a hipGraph; the current device is left as found.  Workspace: allocated by the first
+ * call that needs it (workspace_bytes() = what is held), released with the object; a call under capture that would have
+ * to allocate it returns CLFA_INVALID_OPERATION.  Long calls run in sub-batches of an internal cap (at most 1024 blocks;
+ * CLFA_PCONV_MATRIX_BLOCKS_MAX, read at creation, lowers it). */
+CLFA_API int clfa_pconv_matrix_create(clfa_pconv_matrix **m, int device, int cvs, int pts, int inputs, int outputs);
+CLFA_API void clfa_pconv_matrix_destroy(clfa_pconv_matrix *m);
+CLFA_API int clfa_pconv_matrix_get_error(const clfa_pconv_matrix *m);
+CLFA_API const char *clfa_pconv_matrix_get_log(const clfa_pconv_matrix *m);
+CLFA_API int clfa_pconv_matrix_push_ir(clfa_pconv_matrix *m, const float *ir);
+CLFA_API int clfa_pconv_matrix_push_ir_dev(clfa_pconv_matrix *m, const void *ir, long row_stride, void *stream);
+CLFA_API int clfa_pconv_matrix_process_dev(clfa_pconv_matrix *m, void *out, long out_stride, const void *in, long in_stride,
+                                           long nblocks, void *stream);
+/* host form: rows contiguous (stride nblocks*pts), blocking */
+CLFA_API int clfa_pconv_matrix_convolution(clfa_pconv_matrix *m, float *out, const float *in, long nblocks);
+/* 0 for a failed object */
+CLFA_API int clfa_pconv_matrix_nparts(const clfa_pconv_matrix *m);
+/* responses + input rings + tails; the sub-batch workspaces */
+CLFA_API size_t clfa_pconv_matrix_state_bytes(const clfa_pconv_matrix *m);
+CLFA_API size_t clfa_pconv_matrix_workspace_bytes(const clfa_pconv_matrix *m);
+/* "k_pconvm_mac" ("" for a failed object) */
+CLFA_API const char *clfa_pconv_matrix_kernel_name(const clfa_pconv_matrix *m);
 
 #ifdef __cplusplus
 }

@@ -8,6 +8,7 @@ meaning and integer OpenCL status codes), over the C ABI of libclfft_amd.so:
     Clpconv  cl_conv.h:124-188  uniformly partitioned overlap-add convolution
     Cldconv  cl_dconv.h:17-66   direct convolution
     Stft     (extension)        short-time analysis / windowed overlap-add synthesis on the Clrfft layout
+    PconvMatrix (extension)     convolution matrix: many inputs mixed into many outputs
 
 Like the reference, constructors never raise: a failed setup is read back with
 ``get_error()`` / ``get_cl_err()`` and every method returns the status code.
@@ -26,7 +27,7 @@ from ._lib import ClError, check, lib
 
 __all__ = ["Clcfft", "Clrfft", "Clpconv", "Cldconv", "ClError", "cl_error_string", "device_count",
            "device_name", "bitrev_table", "twiddle_table", "r2c_twiddle_table", "reorder_device", "PI",
-           "Stft", "packed_to_onesided", "onesided_to_packed"]
+           "Stft", "packed_to_onesided", "onesided_to_packed", "PconvMatrix"]
 
 PI = 3.141592653589793  # cl_fft.h:24
 CL_SUCCESS = 0
@@ -487,6 +488,90 @@ class Clpconv:
         return lib().clfa_pconv_process_blocks_dev(self._h, out.data_ptr(), so, in1.data_ptr(),
                                                    in2.data_ptr() if in2 is not None else None, s1,
                                                    l1 // self.pts, stream)
+
+
+class PconvMatrix:
+    """Convolution matrix (extension, clfa_pconv_matrix in clfft_amd.h): `inputs` signals mixed into `outputs` signals,
+    y_o = sum_i x_i * h_{o,i}, by uniformly partitioned overlap-add convolution with static responses.  Block j of output
+    o is the sum over i of what Clpconv(device_id, cvs, pts) holding h_{o,i} returns for block j of input i.  pts is a
+    power of two, 32..4096.  Like the other objects the constructor does not raise: get_error() / get_log() report a
+    failed setup."""
+
+    def __init__(self, device_id, cvs, pts, inputs, outputs):
+        self.cvs, self.pts, self.inputs, self.outputs = int(cvs), int(pts), int(inputs), int(outputs)
+        h = C.c_void_p()
+        lib().clfa_pconv_matrix_create(C.byref(h), int(device_id), self.cvs, self.pts, self.inputs, self.outputs)
+        self._h = h
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and lib is not None:
+            lib().clfa_pconv_matrix_destroy(h)
+
+    def get_error(self):
+        return lib().clfa_pconv_matrix_get_error(self._h)
+
+    def get_log(self):
+        return lib().clfa_pconv_matrix_get_log(self._h).decode()
+
+    nparts = property(lambda s: lib().clfa_pconv_matrix_nparts(s._h))
+
+    def state_bytes(self):
+        return lib().clfa_pconv_matrix_state_bytes(self._h)
+
+    def workspace_bytes(self):
+        return lib().clfa_pconv_matrix_workspace_bytes(self._h)
+
+    def kernel_name(self):
+        return lib().clfa_pconv_matrix_kernel_name(self._h).decode()
+
+    def push_ir(self, ir):
+        """ir: float32 (outputs, inputs, >= nparts*pts), e.g. rows of cvs samples (the remainder is ignored)"""
+        ir = np.asarray(ir, dtype=np.float32)
+        need = self.nparts * self.pts
+        if ir.ndim != 3 or ir.shape[:2] != (self.outputs, self.inputs) or ir.shape[2] < need:
+            return CL_INVALID_VALUE
+        ir = np.ascontiguousarray(ir[:, :, :need])
+        return lib().clfa_pconv_matrix_push_ir(self._h, ir.ctypes.data)
+
+    def push_ir_device(self, ir, stream=None):
+        """ir: device tensor (outputs, inputs, >= nparts*pts) of float32 whose rows are contiguous and evenly spaced
+        (stride(0) == inputs * stride(1)); the row stride is stride(1).  Asynchronous on `stream`."""
+        need = self.nparts * self.pts
+        if (ir.dim() != 3 or tuple(ir.shape[:2]) != (self.outputs, self.inputs) or ir.shape[2] < need
+                or str(ir.dtype) != "torch.float32" or ir.stride(2) != 1):
+            return CL_INVALID_VALUE
+        rs = ir.stride(1) if self.inputs > 1 else (ir.stride(0) if self.outputs > 1 else max(ir.stride(1), need))
+        if self.outputs > 1 and ir.stride(0) != self.inputs * rs:
+            return CL_INVALID_VALUE
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream(ir.device).cuda_stream
+        return lib().clfa_pconv_matrix_push_ir_dev(self._h, ir.data_ptr(), rs, stream)
+
+    def convolution(self, output, input):
+        """whole signals on the host: float32 (inputs, L) -> (outputs, L), L a multiple of pts; blocking"""
+        output = _host(output, np.float32)
+        a = np.ascontiguousarray(input, dtype=np.float32)
+        if (a.ndim != 2 or a.shape[0] != self.inputs or a.shape[1] % self.pts
+                or output.shape != (self.outputs, a.shape[1])):
+            return CL_INVALID_VALUE
+        return lib().clfa_pconv_matrix_convolution(self._h, output.ctypes.data, a.ctypes.data, a.shape[1] // self.pts)
+
+    def process_device(self, out, x, stream=None):
+        """device tensors: x (inputs, L), out (outputs, L) of float32, stride(1) == 1, L % pts == 0; the row stride of
+        each is its stride(0) (views into longer rows are fine).  Asynchronous on `stream`."""
+        def rows(t, n):
+            if str(t.dtype) != "torch.float32" or t.dim() != 2 or t.shape[0] != n or (t.shape[1] > 1 and t.stride(1) != 1):
+                raise ValueError("expected a (%d, L) float32 tensor with stride(1) == 1" % n)
+            return t.shape[1], t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+        (lo, so), (li, si) = rows(out, self.outputs), rows(x, self.inputs)
+        if lo != li or li % self.pts:
+            return CL_INVALID_VALUE
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream(x.device).cuda_stream
+        return lib().clfa_pconv_matrix_process_dev(self._h, out.data_ptr(), so, x.data_ptr(), si, li // self.pts, stream)
 
 
 class Cldconv:

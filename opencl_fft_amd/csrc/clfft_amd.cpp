@@ -1779,3 +1779,260 @@ int clfa_stft_synthesize(clfa_stft *p, const float *spectra, long frames, long c
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------
+// convolution matrix (pconv_matrix.hip)
+// ---------------------------------------------------------------------------------
+
+struct clfa_pconv_matrix {
+  DeviceInfo di;
+  int cvs = 0, pts = 0, nparts = 0, inputs = 0, outputs = 0, logb = 0;
+  int wp = 0;                    // ring A position, shared by every input
+  int err = 0;
+  char log[256];
+  hipStream_t stream = nullptr;
+  DevBuf half, w2f, w2i;         // tables of the pts-bin transforms (as Clpconv)
+  DevBuf H, ringA, tail;         // responses, input spectra rings, overlap-add tails
+  DevBuf X, Y, P, tail_ws;       // sub-batch workspaces: allocated by the first call that needs them
+  DevBuf hin, hout, hir;         // staging of the host entry points
+  PconvMatrixPlan plan;
+  int cap = 1;                   // blocks per sub-batch (CLFA_PCONV_MATRIX_BLOCKS_MAX: tuning switch, read at creation)
+  StreamOrder order;
+};
+
+static int mconv_setup(clfa_pconv_matrix *p, int device, int cvs, int pts, int inputs, int outputs) {
+  p->log[0] = 0;
+  p->cvs = cvs;
+  p->pts = pts;
+  p->inputs = inputs;
+  p->outputs = outputs;
+  if (!is_pow2(pts) || pts < (1 << kPconvBlocksMinLog) || pts > (1 << kPconvBlocksMaxLog)) {
+    snprintf(p->log, sizeof(p->log), "pts must be a power of two, %d..%d (got %d)", 1 << kPconvBlocksMinLog,
+             1 << kPconvBlocksMaxLog, pts);
+    return CLFA_INVALID_VALUE;
+  }
+  if (cvs < pts || inputs < 1 || outputs < 1) {
+    snprintf(p->log, sizeof(p->log), "need cvs >= pts, inputs >= 1, outputs >= 1 (got %d, %d, %d)", cvs, inputs, outputs);
+    return CLFA_INVALID_VALUE;
+  }
+  p->logb = ilog2(pts);
+  p->nparts = cvs / pts;   // floor, as Clpconv
+  int e = device_info(device, p->di);
+  if (e) return e;
+  p->plan = pconv_matrix_plan(pts, p->nparts, inputs, outputs, p->di);
+  // tuning switches, read per object (tools/time_mconv.py sweeps them): outputs per MAC tile, reduction segments
+  if (const char *env = getenv("CLFA_PCONV_MATRIX_TILE")) {
+    if (atoi(env) == 4 || atoi(env) == 16) p->plan.kt = atoi(env);
+  }
+  if (const char *env = getenv("CLFA_PCONV_MATRIX_SEGS")) {
+    if (atoi(env) >= 1 && atoi(env) <= 4096) p->plan.segs = atoi(env);
+  }
+  {
+    // sub-batch workspaces X, Y and the segments' partials within ~384 MiB, at most 1024 blocks
+    const long per_block = ((long)inputs + (long)outputs * p->plan.segs) * pts * (long)sizeof(cpx);
+    long cap = (384L << 20) / per_block;
+    const char *env = getenv("CLFA_PCONV_MATRIX_BLOCKS_MAX");   // read per object, like CLFA_PCONV_BLOCKS_MAX
+    if (env && atol(env) > 0 && atol(env) < cap) cap = atol(env);
+    p->cap = (int)(cap < 1 ? 1 : (cap > 1024 ? 1024 : cap));
+  }
+  ENTER_DEVICE(device);
+  HIP_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
+  std::vector<cpx> h;
+  fill_twiddle(h, pts / 2, pts, 1, -1.f);
+  if ((e = upload(p->half, h.data(), sizeof(cpx) * h.size()))) return e;
+  fill_w2(h, pts, -1.f);
+  if ((e = upload(p->w2f, h.data(), sizeof(cpx) * pts))) return e;
+  fill_w2(h, pts, 1.f);
+  if ((e = upload(p->w2i, h.data(), sizeof(cpx) * pts))) return e;
+  const size_t frame = sizeof(cpx) * (size_t)pts;
+  const size_t hbytes = frame * (size_t)outputs * inputs * p->nparts, abytes = frame * (size_t)inputs * p->nparts;
+  const size_t tbytes = sizeof(float) * (size_t)outputs * pts;
+  if ((e = p->H.ensure(hbytes)) || (e = p->ringA.ensure(abytes)) || (e = p->tail.ensure(tbytes))) return e;
+  // zero responses, history and tails
+  HIP_TRY(hipMemsetAsync(p->H.p, 0, hbytes, p->stream));
+  HIP_TRY(hipMemsetAsync(p->ringA.p, 0, abytes, p->stream));
+  HIP_TRY(hipMemsetAsync(p->tail.p, 0, tbytes, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return CLFA_SUCCESS;
+}
+
+// rows of a (ra rows at stride sa bytes) and of b (rb rows at stride sb), len bytes each: does any pair share a byte?
+// For row i of a, the rows k of b that could touch it form one interval of k.
+static bool mconv_rows_overlap(const void *a, long sa, long ra, const void *b, long sb, long rb, long len) {
+  auto fdiv = [](long x, long y) { return x >= 0 ? x / y : -((-x + y - 1) / y); };   // floor, y > 0
+  const long base = (long)((const char *)a - (const char *)b);
+  if (rb <= 1) sb = len;
+  for (long i = 0; i < ra; i++) {
+    const long d = base + i * sa;
+    long kmin = fdiv(d - len, sb) + 1;
+    long kmax = -fdiv(-(d + len), sb) - 1;
+    kmin = kmin < 0 ? 0 : kmin;
+    kmax = kmax > rb - 1 ? rb - 1 : kmax;
+    if (kmin <= kmax) return true;
+  }
+  return false;
+}
+
+static int mconv_ws(clfa_pconv_matrix *p, hipStream_t s) {
+  const size_t frames = sizeof(cpx) * (size_t)p->cap * p->pts;
+  struct Want {
+    DevBuf *b;
+    size_t bytes;
+  } want[] = {{&p->X, frames * p->inputs},
+              {&p->Y, frames * p->outputs},
+              {&p->P, frames * p->outputs * (size_t)(p->plan.segs - 1)},
+              {&p->tail_ws, sizeof(float) * (size_t)p->outputs * p->pts}};
+  bool missing = false;
+  for (const Want &w : want) missing = missing || w.b->bytes < w.bytes;
+  if (!missing) return CLFA_SUCCESS;
+  if (StreamOrder::capturing(s)) return CLFA_INVALID_OPERATION;   // a hipMalloc there would be outside the graph
+  for (const Want &w : want) {
+    int e = w.b->ensure(w.bytes);
+    if (e) return e;
+  }
+  return CLFA_SUCCESS;
+}
+
+extern "C" {
+
+int clfa_pconv_matrix_create(clfa_pconv_matrix **m, int device, int cvs, int pts, int inputs, int outputs) {
+  if (!m) return CLFA_INVALID_VALUE;
+  clfa_pconv_matrix *p = new (std::nothrow) clfa_pconv_matrix();
+  if (!p) return CLFA_OUT_OF_HOST_MEMORY;
+  p->err = mconv_setup(p, device, cvs, pts, inputs, outputs);
+  *m = p;
+  return p->err;
+}
+
+void clfa_pconv_matrix_destroy(clfa_pconv_matrix *p) {
+  if (!p) return;
+  DeviceGuard guard;
+  (void)guard.enter(p->di.device);
+  if (p->stream) {
+    (void)hipStreamSynchronize(p->stream);
+    (void)hipStreamDestroy(p->stream);
+  }
+  for (DevBuf *b : {&p->half, &p->w2f, &p->w2i, &p->H, &p->ringA, &p->tail, &p->X, &p->Y, &p->P, &p->tail_ws, &p->hin,
+                    &p->hout, &p->hir})
+    b->release();
+  delete p;
+}
+
+int clfa_pconv_matrix_get_error(const clfa_pconv_matrix *p) { return p ? p->err : CLFA_INVALID_VALUE; }
+const char *clfa_pconv_matrix_get_log(const clfa_pconv_matrix *p) { return p ? p->log : ""; }
+int clfa_pconv_matrix_nparts(const clfa_pconv_matrix *p) { return p && !p->err ? p->nparts : 0; }
+size_t clfa_pconv_matrix_state_bytes(const clfa_pconv_matrix *p) {
+  return p ? p->H.bytes + p->ringA.bytes + p->tail.bytes : 0;
+}
+size_t clfa_pconv_matrix_workspace_bytes(const clfa_pconv_matrix *p) {
+  return p ? p->X.bytes + p->Y.bytes + p->P.bytes + p->tail_ws.bytes : 0;
+}
+const char *clfa_pconv_matrix_kernel_name(const clfa_pconv_matrix *p) { return !p || p->err ? "" : "k_pconvm_mac"; }
+
+int clfa_pconv_matrix_push_ir_dev(clfa_pconv_matrix *p, const void *ir, long row_stride, void *stream) {
+  if (!p) return CLFA_INVALID_VALUE;
+  if (p->err) return p->err;
+  const long len = (long)p->nparts * p->pts;
+  if (!ir || row_stride < len || ((uintptr_t)ir & 3)) return CLFA_INVALID_VALUE;
+  ENTER_DEVICE(p->di.device);
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(p->order.use(s));
+  // every partition of every row in one forward launch: row (o, i) partition q -> H frame ((o * inputs + i) * nparts + q)
+  const int aligned = ((uintptr_t)ir & 7) == 0 && (row_stride & 1) == 0;
+  HIP_TRY(launch_pconvb_forward(p->logb, (const float *)ir, row_stride, (cpx *)p->H.p, p->nparts, p->nparts,
+                                p->outputs * p->inputs, aligned, (const cpx *)p->half.p, (const cpx *)p->w2f.p, s));
+  return CLFA_SUCCESS;
+}
+
+int clfa_pconv_matrix_push_ir(clfa_pconv_matrix *p, const float *ir) {
+  if (!p) return CLFA_INVALID_VALUE;
+  if (p->err) return p->err;
+  if (!ir) return CLFA_INVALID_VALUE;
+  ENTER_DEVICE(p->di.device);
+  const long len = (long)p->nparts * p->pts;
+  const size_t bytes = sizeof(float) * (size_t)len * p->outputs * p->inputs;
+  int e = p->hir.ensure(bytes);
+  if (e) return e;
+  HIP_TRY(hipMemcpyAsync(p->hir.p, ir, bytes, hipMemcpyHostToDevice, p->stream));
+  if ((e = clfa_pconv_matrix_push_ir_dev(p, p->hir.p, len, p->stream))) return e;
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return CLFA_SUCCESS;
+}
+
+int clfa_pconv_matrix_process_dev(clfa_pconv_matrix *p, void *out, long out_stride, const void *in, long in_stride,
+                                  long nblocks, void *stream) {
+  if (!p) return CLFA_INVALID_VALUE;
+  if (p->err) return p->err;
+  if (nblocks < 0) return CLFA_INVALID_VALUE;
+  if (nblocks == 0) return CLFA_SUCCESS;
+  const long pts = p->pts, nparts = p->nparts;
+  if (!out || !in || nblocks > 0x7fffffffL / pts) return CLFA_INVALID_VALUE;
+  const long len = nblocks * pts;
+  if (in_stride < len || out_stride < len) return CLFA_INVALID_VALUE;
+  if (((uintptr_t)out & 3) || ((uintptr_t)in & 3)) return CLFA_INVALID_VALUE;
+  const long lb = len * (long)sizeof(float);
+  if (mconv_rows_overlap(out, out_stride * (long)sizeof(float), p->outputs, in, in_stride * (long)sizeof(float), p->inputs, lb))
+    return CLFA_INVALID_VALUE;
+  ENTER_DEVICE(p->di.device);
+  hipStream_t s = (hipStream_t)stream;
+  int e = mconv_ws(p, s);
+  if (e) return e;
+  HIP_TRY(p->order.use(s));
+  PconvMatrixArgs a;
+  a.logb = p->logb;
+  a.bins = p->pts;
+  a.nparts = p->nparts;
+  a.inputs = p->inputs;
+  a.outputs = p->outputs;
+  a.plan = p->plan;
+  a.cap = p->cap;
+  a.in_stride = in_stride;
+  a.out_stride = out_stride;
+  a.aligned_in = ((uintptr_t)in & 7) == 0 && (in_stride & 1) == 0;
+  a.aligned_out = ((uintptr_t)out & 7) == 0 && (out_stride & 1) == 0;
+  a.H = (const cpx *)p->H.p;
+  a.ringA = (cpx *)p->ringA.p;
+  a.tail = (float *)p->tail.p;
+  a.X = (cpx *)p->X.p;
+  a.Y = (cpx *)p->Y.p;
+  a.P = (cpx *)p->P.p;
+  a.tail_ws = (float *)p->tail_ws.p;
+  a.half = (const cpx *)p->half.p;
+  a.w2f = (const cpx *)p->w2f.p;
+  a.w2i = (const cpx *)p->w2i.p;
+  const float *src = (const float *)in;
+  float *dst = (float *)out;
+  for (long j0 = 0; j0 < nblocks; j0 += p->cap) {
+    a.K = (int)(nblocks - j0 < p->cap ? nblocks - j0 : p->cap);
+    a.w = p->wp;
+    a.in = src + j0 * pts;
+    a.out = dst + j0 * pts;
+    HIP_TRY(launch_pconv_matrix(a, s));
+    p->wp = (int)((p->wp + a.K) % nparts);
+  }
+  return CLFA_SUCCESS;
+}
+
+int clfa_pconv_matrix_convolution(clfa_pconv_matrix *p, float *out, const float *in, long nblocks) {
+  if (!p) return CLFA_INVALID_VALUE;
+  if (p->err) return p->err;
+  if (nblocks < 0) return CLFA_INVALID_VALUE;
+  if (nblocks == 0) return CLFA_SUCCESS;
+  if (!out || !in || nblocks > 0x7fffffffL / p->pts) return CLFA_INVALID_VALUE;
+  const long len = nblocks * p->pts;
+  const size_t ib = sizeof(float) * (size_t)len * p->inputs, ob = sizeof(float) * (size_t)len * p->outputs;
+  {
+    const char *x = (const char *)out, *y = (const char *)in;
+    if (x < y + ib && y < x + ob) return CLFA_INVALID_VALUE;
+  }
+  ENTER_DEVICE(p->di.device);
+  int e;
+  if ((e = p->hin.ensure(ib)) || (e = p->hout.ensure(ob))) return e;
+  HIP_TRY(hipMemcpyAsync(p->hin.p, in, ib, hipMemcpyHostToDevice, p->stream));
+  if ((e = clfa_pconv_matrix_process_dev(p, p->hout.p, len, p->hin.p, len, nblocks, p->stream))) return e;
+  HIP_TRY(hipMemcpyAsync(out, p->hout.p, ob, hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return CLFA_SUCCESS;
+}
+
+}  // extern "C"

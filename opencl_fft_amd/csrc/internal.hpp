@@ -179,6 +179,38 @@ struct PconvBlocks {
 int pconv_blocks_tile(const PconvGeom &g, const DeviceInfo &di);
 hipError_t launch_pconv_blocks(const PconvBlocks &a, hipStream_t s);
 constexpr int kPconvBlocksMinLog = 5, kPconvBlocksMaxLog = 12;
+// the forward / inverse launches of a sub-batch on their own (pconv_blocks.hip), for the convolution matrix
+hipError_t launch_pconvb_forward(int logb, const float *in, long in_stride, cpx *X, int K, int cap, int channels, int aligned,
+                                 const cpx *half, const cpx *w2f, hipStream_t s);
+hipError_t launch_pconvb_inverse(int logb, const cpx *Y, const float *tail, float *tail_out, float *out, long out_stride, int K,
+                                 int cap, int R, int channels, int aligned, const cpx *half, const cpx *w2i, hipStream_t s);
+// Convolution matrix (pconv_matrix.hip): y_o = sum_i x_i * h_{o,i}, K consecutive blocks of every input per sub-batch.
+// Responses H: outputs x inputs x nparts x bins complex, partition q of row (o, i) at ((o * inputs + i) * nparts + q) * bins.
+// The MAC walks the reduction sequence r = i * nparts + p (p = 0 pairs with partition nparts - 1, the oldest input frame)
+// in `segs` fixed segments [r_s, r_{s+1}), r_s = floor(s * inputs * nparts / segs); segment 0 writes Y, segment s > 0 the
+// partial P[s - 1]; with segs > 1 a reduce launch adds them to Y in ascending s.
+struct PconvMatrixPlan {
+  int kt = 4;     // outputs per MAC tile (4 or 16)
+  int segs = 1;   // segments of the reduction over (input, partition)
+};
+struct PconvMatrixArgs {
+  int logb = 0, bins = 0, nparts = 0, inputs = 0, outputs = 0;
+  PconvMatrixPlan plan;
+  int K = 0, cap = 0, w = 0;
+  int run = 8;    // blocks per inverse run
+  const float *in = nullptr;
+  float *out = nullptr;
+  long in_stride = 0, out_stride = 0;
+  int aligned_in = 1, aligned_out = 1;   // every row start 8-byte aligned
+  const cpx *H = nullptr;
+  cpx *ringA = nullptr;                  // inputs x nparts x bins
+  float *tail = nullptr;                 // outputs x bins
+  cpx *X = nullptr, *Y = nullptr, *P = nullptr;   // inputs x cap, outputs x cap, (segs - 1) x outputs x cap frames
+  float *tail_ws = nullptr;              // outputs x bins
+  const cpx *half = nullptr, *w2f = nullptr, *w2i = nullptr;
+};
+PconvMatrixPlan pconv_matrix_plan(int bins, int nparts, int inputs, int outputs, const DeviceInfo &di);
+hipError_t launch_pconv_matrix(const PconvMatrixArgs &a, hipStream_t s);
 constexpr int kPconvMaxLogBins = 15;   // pts up to 32768 (the reference harness' largest, csound/tests.py:13)
 // ends of the composed chain used when bins exceed the LDS FFT sizes
 hipError_t launch_pconv_pad(const float *in, long in_stride, cpx *work, int bins, int channels, hipStream_t s);

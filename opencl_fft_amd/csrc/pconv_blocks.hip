@@ -315,15 +315,33 @@ int pconv_blocks_tile(const PconvGeom &g, const DeviceInfo &di) {
 }
 
 template <int LOGB>
-static hipError_t launch_blocks_one(const PconvBlocks &a, hipStream_t s) {
+static hipError_t fwd_one(const float *in, const float *in_b, long in_stride, cpx *X, cpx *XB, int K, int cap, int channels,
+                          int aligned, const cpx *half, const cpx *w2f, hipStream_t s) {
   using G = LdsGeom<LOGB>;
+  long groups = ((long)channels * K + G::FPW - 1) / G::FPW;
+  int grid = groups < 8192 ? (int)groups : 8192;
+  hipLaunchKernelGGL((k_pconvb_fwd<LOGB>), dim3(grid, in_b ? 2 : 1), dim3(G::WG), 0, s, in, in_b, in_stride, X, XB, K, cap,
+                     channels, aligned, half, w2f);
+  return hipGetLastError();
+}
+
+template <int LOGB>
+static hipError_t inv_one(const cpx *Y, const float *tail, float *tail_out, float *out, long out_stride, int K, int cap, int R,
+                          int channels, int aligned, const cpx *half, const cpx *w2i, hipStream_t s) {
+  using G = LdsGeom<LOGB>;
+  const int nruns = (K + R - 1) / R;
+  long groups = ((long)channels * nruns + G::FPW - 1) / G::FPW;
+  int grid = groups < 8192 ? (int)groups : 8192;
+  hipLaunchKernelGGL((k_pconvb_inv<LOGB>), dim3(grid), dim3(G::WG), 0, s, Y, tail, tail_out, out, out_stride, K, cap, R,
+                     channels, aligned, half, w2i);
+  return hipGetLastError();
+}
+
+template <int LOGB>
+static hipError_t launch_blocks_one(const PconvBlocks &a, hipStream_t s) {
   const PconvGeom &g = a.g;
   {
-    long groups = ((long)g.channels * a.K + G::FPW - 1) / G::FPW;
-    int grid = groups < 8192 ? (int)groups : 8192;
-    hipLaunchKernelGGL((k_pconvb_fwd<LOGB>), dim3(grid, a.in2 ? 2 : 1), dim3(G::WG), 0, s, a.in1, a.in2, a.in_stride, a.X,
-                       a.XB, a.K, a.cap, g.channels, a.aligned_in, a.half, a.w2f);
-    hipError_t e = hipGetLastError();
+    hipError_t e = fwd_one<LOGB>(a.in1, a.in2, a.in_stride, a.X, a.XB, a.K, a.cap, g.channels, a.aligned_in, a.half, a.w2f, s);
     if (e != hipSuccess) return e;
   }
   {
@@ -344,12 +362,8 @@ static hipError_t launch_blocks_one(const PconvBlocks &a, hipStream_t s) {
     if (e != hipSuccess) return e;
   }
   {
-    const int nruns = (a.K + a.run - 1) / a.run;
-    long groups = ((long)g.channels * nruns + G::FPW - 1) / G::FPW;
-    int grid = groups < 8192 ? (int)groups : 8192;
-    hipLaunchKernelGGL((k_pconvb_inv<LOGB>), dim3(grid), dim3(G::WG), 0, s, (const cpx *)a.Y, (const float *)a.tail, a.tail_ws,
-                       a.out, a.out_stride, a.K, a.cap, a.run, g.channels, a.aligned_out, a.half, a.w2i);
-    hipError_t e = hipGetLastError();
+    hipError_t e = inv_one<LOGB>((const cpx *)a.Y, (const float *)a.tail, a.tail_ws, a.out, a.out_stride, a.K, a.cap, a.run,
+                                 g.channels, a.aligned_out, a.half, a.w2i, s);
     if (e != hipSuccess) return e;
   }
   {
@@ -368,6 +382,33 @@ hipError_t launch_pconv_blocks(const PconvBlocks &a, hipStream_t s) {
 #define CLFA_B(L) \
   case L:         \
     return launch_blocks_one<L>(a, s);
+    CLFA_B(5) CLFA_B(6) CLFA_B(7) CLFA_B(8) CLFA_B(9) CLFA_B(10) CLFA_B(11) CLFA_B(12)
+#undef CLFA_B
+    default:
+      return hipErrorInvalidValue;
+  }
+}
+
+// the forward and inverse launches on their own, for the convolution matrix (pconv_matrix.hip)
+hipError_t launch_pconvb_forward(int logb, const float *in, long in_stride, cpx *X, int K, int cap, int channels, int aligned,
+                                 const cpx *half, const cpx *w2f, hipStream_t s) {
+  switch (logb) {
+#define CLFA_B(L) \
+  case L:         \
+    return fwd_one<L>(in, nullptr, in_stride, X, nullptr, K, cap, channels, aligned, half, w2f, s);
+    CLFA_B(5) CLFA_B(6) CLFA_B(7) CLFA_B(8) CLFA_B(9) CLFA_B(10) CLFA_B(11) CLFA_B(12)
+#undef CLFA_B
+    default:
+      return hipErrorInvalidValue;
+  }
+}
+
+hipError_t launch_pconvb_inverse(int logb, const cpx *Y, const float *tail, float *tail_out, float *out, long out_stride, int K,
+                                 int cap, int R, int channels, int aligned, const cpx *half, const cpx *w2i, hipStream_t s) {
+  switch (logb) {
+#define CLFA_B(L) \
+  case L:         \
+    return inv_one<L>(Y, tail, tail_out, out, out_stride, K, cap, R, channels, aligned, half, w2i, s);
     CLFA_B(5) CLFA_B(6) CLFA_B(7) CLFA_B(8) CLFA_B(9) CLFA_B(10) CLFA_B(11) CLFA_B(12)
 #undef CLFA_B
     default:

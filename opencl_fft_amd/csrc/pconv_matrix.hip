@@ -1,0 +1,231 @@
+// pconv_matrix.hip — convolution matrix: `inputs` signals mixed into `outputs` signals through an outputs x inputs matrix of
+// partitioned responses, y_o = sum_i x_i * h_{o,i} (clfa_pconv_matrix), partitions of 32..4096 samples.
+//
+// Per sub-batch of K blocks, whatever K:
+//   k_pconvb_fwd      spectra of the inputs x K new blocks -> workspace X (pconv_blocks.hip, channels = inputs)
+//   k_pconvm_mac      Y_{o,j} = sum_i sum_p F_i(j, p) (.) H_{o,i}(nparts - 1 - p) over one segment of the sequence
+//                     r = i * nparts + p: the response frame (o, i, p) is loaded ONCE for a tile of KT consecutive
+//                     outputs j, and input i's frames slide through a register window by one per partition
+//   k_pconvm_reduce   (segs > 1) Y += P[0], Y += P[1], ... in ascending segment order
+//   k_pconvb_inv      c2r + inverse transform + overlap-add of Y into the output rows, one tail per output
+//   k_pconvm_commit   the last nparts spectra of every input -> ring A, the new tails -> the object
+// Frame algebra (block j of the sub-batch, w = the object's ring position before it): the input frame of partition p for
+// output j is m = j - (nparts - 1) + p; m >= 0: X_i[m], m < 0: ring A_i frame (w + m) mod nparts.
+// Every output bin of segment s is one accumulator over its r in ascending order; the segments are fixed per object
+// (pconv_matrix_plan), and so is the order in which they are added: results do not depend on K, the sub-batch, the split
+// of a signal into calls, the stream or graph replay.
+#include "fft_wg.hpp"
+
+namespace clfa {
+
+namespace {
+
+struct alignas(16) cpx2m {
+  cpx a, b;
+};
+
+__device__ __forceinline__ cpx2m ld_nt(const cpx2m *p) {
+  typedef float v4f __attribute__((ext_vector_type(4)));
+  v4f r = __builtin_nontemporal_load(reinterpret_cast<const v4f *>(p));
+  cpx2m o;
+  o.a = mk(r.x, r.y);
+  o.b = mk(r.z, r.w);
+  return o;
+}
+
+__device__ __forceinline__ long seg_start(long total, int s, int segs) { return total * s / segs; }
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------
+// multiply-accumulate: one wave = (64 items of two bins, tile of KT outputs, output o, segment s), flattened into x
+// ---------------------------------------------------------------------------------
+template <int KT>
+__global__ __launch_bounds__(64) void k_pconvm_mac(const cpx *__restrict__ ringA, const cpx *__restrict__ H,
+                                                   const cpx *__restrict__ X, cpx *__restrict__ Y, cpx *__restrict__ P, int K,
+                                                   int cap, int w, int bins, int nparts, int inputs, int outputs, int segs) {
+  const int hb = bins >> 1;
+  const int slices = (hb + 63) / 64, tiles = (K + KT - 1) / KT;
+  long b = blockIdx.x;
+  const int slice = (int)(b % slices);
+  b /= slices;
+  const int tile = (int)(b % tiles);
+  b /= tiles;
+  const int o = (int)(b % outputs);
+  const int s = (int)(b / outputs);
+  const int item = slice * 64 + threadIdx.x;
+  const int it = item < hb ? item : hb - 1;   // (clamped: straight-line loads; the store is guarded)
+  const int j0 = tile * KT;
+  const long total = (long)inputs * nparts;
+  const long r0 = seg_start(total, s, segs), r1 = seg_start(total, s + 1, segs);
+  const bool dc = item == 0;   // packed DC / Nyquist bin: (re*re, im*im)
+  cpx s0[KT], s1[KT];
+#pragma unroll
+  for (int t = 0; t < KT; t++) s0[t] = s1[t] = mk(0.f, 0.f);
+  auto mac = [&](int t, const cpx2m &x, const cpx2m &h) {
+    cpx pr = cmul_plain(x.a, h.a);
+    pr = mk(dc ? x.a.x * h.a.x : pr.x, dc ? x.a.y * h.a.y : pr.y);
+    s0[t] = cadd(s0[t], pr);
+    s1[t] = cadd(s1[t], cmul_plain(x.b, h.b));
+  };
+  for (int i = (int)(r0 / nparts); (long)i * nparts < r1; i++) {
+    const long ib = (long)i * nparts;
+    const int pa = r0 > ib ? (int)(r0 - ib) : 0;
+    const int pb = r1 - ib < nparts ? (int)(r1 - ib) : nparts;
+    const cpx2m *ra = reinterpret_cast<const cpx2m *>(ringA + ib * bins) + it;
+    const cpx2m *xs = reinterpret_cast<const cpx2m *>(X + (long)i * cap * bins) + it;
+    // partition q of response (o, i); step p of the walk uses q = nparts - 1 - p
+    const cpx2m *hp = reinterpret_cast<const cpx2m *>(H + ((long)o * inputs + i) * nparts * bins) + it;
+    // input frame m of the sub-batch: m >= 0 this call's spectrum X_i[m]; m < 0 ring A_i frame (w + m) mod nparts.
+    // m > K - 1 only feeds outputs past the sub-batch (never stored): clamped
+    auto frame = [&](int m) -> const cpx2m * {
+      if (m >= 0) return xs + (long)(m < K ? m : K - 1) * hb;
+      int f = w + m;
+      f = f < 0 ? f + nparts : f;
+      return ra + (long)f * hb;
+    };
+    cpx2m win[KT];
+#pragma unroll
+    for (int t = 0; t < KT; t++) win[t] = ld_nt(frame(j0 + t - (nparts - 1) + pa));
+    cpx2m hq, xq;
+    auto load = [&](int p) {
+      hq = ld_nt(hp + (long)(nparts - 1 - p) * hb);
+      xq = ld_nt(frame(j0 + KT - (nparts - 1) + p));   // enters the window after partition p
+    };
+    load(pa);
+    for (int p = pa; p < pb; p++) {
+      const cpx2m h = hq, xn = xq;
+      if (p + 1 < pb) load(p + 1);   // next partition's loads are in flight under this one's arithmetic
+#pragma unroll
+      for (int t = 0; t < KT; t++) mac(t, win[t], h);
+#pragma unroll
+      for (int t = 0; t + 1 < KT; t++) win[t] = win[t + 1];
+      win[KT - 1] = xn;
+    }
+  }
+  if (item < hb) {
+    cpx2m *dst = reinterpret_cast<cpx2m *>(s == 0 ? Y + (long)o * cap * bins : P + ((long)(s - 1) * outputs + o) * cap * bins);
+#pragma unroll
+    for (int t = 0; t < KT; t++) {
+      const int j = j0 + t;
+      if (j < K) {
+        cpx2m v;
+        v.a = s0[t];
+        v.b = s1[t];
+        dst[(long)j * hb + item] = v;
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------
+// the segments' partial sums, added in ascending segment order: Y = ((Y_0 + P_1) + P_2) + ...
+// ---------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_pconvm_reduce(cpx *__restrict__ Y, const cpx *__restrict__ P, int K, int cap, int bins,
+                                                       int outputs, int segs) {
+  const int hb = bins >> 1;
+  const long n = (long)outputs * K * hb;
+  const long pstride = (long)outputs * cap * hb;   // one segment's partials, in cpx2m
+  cpx2m *y = reinterpret_cast<cpx2m *>(Y);
+  const cpx2m *q = reinterpret_cast<const cpx2m *>(P);
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const int item = (int)(i % hb);
+    const long rest = i / hb;
+    const int j = (int)(rest % K), o = (int)(rest / K);
+    const long at = ((long)o * cap + j) * hb + item;
+    cpx2m v = y[at];
+    for (int s = 1; s < segs; s++) {
+      const cpx2m u = q[(long)(s - 1) * pstride + at];
+      v.a = cadd(v.a, u.a);
+      v.b = cadd(v.b, u.b);
+    }
+    y[at] = v;
+  }
+}
+
+// ---------------------------------------------------------------------------------
+// commit: y = 0 the last min(K, nparts) spectra of every input -> ring A frame (w + m) mod nparts; y = 1 the new tails
+// ---------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_pconvm_commit(cpx *__restrict__ ringA, float *__restrict__ tail, const cpx *__restrict__ X,
+                                                       const float *__restrict__ tail_new, int K, int cap, int w, int bins,
+                                                       int nparts, int inputs, int outputs) {
+  const int hb = bins >> 1;
+  if (blockIdx.y == 1) {
+    const long n = (long)outputs * bins;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) tail[i] = tail_new[i];
+    return;
+  }
+  const int m0 = K > nparts ? K - nparts : 0, cnt = K - m0;
+  const long n = (long)inputs * cnt * hb;
+  const cpx2m *src = reinterpret_cast<const cpx2m *>(X);
+  cpx2m *dst = reinterpret_cast<cpx2m *>(ringA);
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const int item = (int)(i % hb);
+    const long rest = i / hb;
+    const int m = m0 + (int)(rest % cnt), ch = (int)(rest / cnt);
+    const int fr = (w + m) % nparts;
+    dst[((long)ch * nparts + fr) * hb + item] = src[((long)ch * cap + m) * hb + item];
+  }
+}
+
+// ---------------------------------------------------------------------------------
+// plan and launchers
+// ---------------------------------------------------------------------------------
+PconvMatrixPlan pconv_matrix_plan(int bins, int nparts, int inputs, int outputs, const DeviceInfo &di) {
+  // The (input, partition) reduction is split until one tile of outputs has about eight waves per CU: with few outputs and
+  // bins the item x output axes alone give a handful of waves (16 -> 2 at 512 bins: 8), and each wave's chain of dependent
+  // loads is as long as its segment, so short segments hide the latency (profiles/pconv_matrix_r07.txt: 64 x 64 at 256
+  // bins, K = 1, 218 us per block with 4 segments, 125 with 16).  A segment keeps at least 16 steps, so the window refills
+  // and the partial sums stay small against the response traffic.  Long tiles once the segments alone fill the chip.
+  // Fixed per object: the order of every output bin's sums never depends on K.
+  PconvMatrixPlan pl;
+  const long slices = (bins / 2 + 63) / 64;
+  const long base = slices * outputs;
+  const long total = (long)inputs * nparts;
+  long segs = (8L * di.num_cus + base - 1) / base;
+  const long most = total / 16 > 1 ? total / 16 : 1;
+  segs = segs < most ? segs : most;
+  segs = segs < 256 ? segs : 256;
+  pl.segs = (int)(segs < 1 ? 1 : segs);
+  pl.kt = base * pl.segs >= di.num_cus ? 16 : 4;
+  return pl;
+}
+
+hipError_t launch_pconv_matrix(const PconvMatrixArgs &a, hipStream_t s) {
+  const PconvMatrixPlan &pl = a.plan;
+  if (a.K < 1 || a.K > a.cap || (pl.kt != 4 && pl.kt != 16) || pl.segs < 1 || a.run < 1 || a.logb < kPconvBlocksMinLog ||
+      a.logb > kPconvBlocksMaxLog || (pl.segs > 1 && !a.P))
+    return hipErrorInvalidValue;
+  hipError_t e = launch_pconvb_forward(a.logb, a.in, a.in_stride, a.X, a.K, a.cap, a.inputs, a.aligned_in, a.half, a.w2f, s);
+  if (e != hipSuccess) return e;
+  {
+    const long slices = (a.bins / 2 + 63) / 64, tiles = (a.K + pl.kt - 1) / pl.kt;
+    const long grid = slices * tiles * a.outputs * pl.segs;
+    if (grid > 0x7fffffffL) return hipErrorInvalidValue;
+#define CLFA_MAC(KT)                                                                                                      \
+  hipLaunchKernelGGL((k_pconvm_mac<KT>), dim3((unsigned)grid), dim3(64), 0, s, (const cpx *)a.ringA, a.H, (const cpx *)a.X, a.Y, \
+                     a.P, a.K, a.cap, a.w, a.bins, a.nparts, a.inputs, a.outputs, pl.segs)
+    if (pl.kt == 16) CLFA_MAC(16);
+    else CLFA_MAC(4);
+#undef CLFA_MAC
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  if (pl.segs > 1) {
+    const long n = (long)a.outputs * a.K * (a.bins / 2);
+    const int grid = (int)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
+    hipLaunchKernelGGL(k_pconvm_reduce, dim3(grid), dim3(256), 0, s, a.Y, (const cpx *)a.P, a.K, a.cap, a.bins, a.outputs, pl.segs);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  e = launch_pconvb_inverse(a.logb, a.Y, a.tail, a.tail_ws, a.out, a.out_stride, a.K, a.cap, a.run, a.outputs, a.aligned_out,
+                            a.half, a.w2i, s);
+  if (e != hipSuccess) return e;
+  {
+    const long n = (long)(a.inputs > a.outputs ? a.inputs : a.outputs) * a.bins;
+    const int grid = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+    hipLaunchKernelGGL(k_pconvm_commit, dim3(grid, 2), dim3(256), 0, s, a.ringA, a.tail, (const cpx *)a.X, (const float *)a.tail_ws,
+                       a.K, a.cap, a.w, a.bins, a.nparts, a.inputs, a.outputs);
+  }
+  return hipGetLastError();
+}
+
+}  // namespace clfa
