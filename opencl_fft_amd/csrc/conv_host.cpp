@@ -1,0 +1,705 @@
+// conv_host.cpp — C ABI of the convolutions (see include/clfft_amd.h): Clpconv and its multi-block route, Cldconv, and
+// the convolution matrix.  Shared plumbing: host.hpp.
+#include "host.hpp"
+
+using namespace clfa;
+
+namespace {
+
+// device staging of the blocking host entry points
+struct Staging {
+  DevBuf in1, in2, out;
+};
+// ... and for single blocks their zero-copy counterparts (mapped pinned host memory)
+struct ZeroCopy {
+  HostBuf in1, in2, out;
+};
+
+// bytes per block up to which the convolutions' blocking host calls go zero-copy: the kernels read the input from, and
+// write the output to, mapped pinned host memory (one pass each way), instead of two hipMemcpyAsync calls of 10-15 us
+// each around a kernel of a few microseconds
+constexpr size_t kZeroCopyMaxConv = (size_t)256 << 10;   // the convolutions' blocks (measured at this size only)
+// Cldconv only for blocks of up to 4096 samples: every workgroup whose ring window meets the new block reads it from there
+constexpr size_t kZeroCopyMaxDconv = (size_t)16 << 10;
+
+// A blocking host call through device staging: the inputs (ibytes each; in2 may be NULL) copied in, run(out, in1, in2)
+// enqueued on s, obytes of output copied back, one synchronisation
+template <class Run>
+int staged_call(Staging &st, hipStream_t s, void *out, size_t obytes, const void *in1, const void *in2, size_t ibytes,
+                Run run) {
+  int e;
+  if ((e = st.in1.ensure(ibytes)) || (e = st.out.ensure(obytes)) || (in2 && (e = st.in2.ensure(ibytes)))) return e;
+  HIP_TRY(hipMemcpyAsync(st.in1.p, in1, ibytes, hipMemcpyHostToDevice, s));
+  if (in2) HIP_TRY(hipMemcpyAsync(st.in2.p, in2, ibytes, hipMemcpyHostToDevice, s));
+  if ((e = run(st.out.p, st.in1.p, in2 ? st.in2.p : nullptr))) return e;
+  HIP_TRY(hipMemcpyAsync(out, st.out.p, obytes, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));   // blocking read, cl_conv.cpp:455
+  return CLFA_SUCCESS;
+}
+
+// A blocking host call of one audio block (blk bytes per input and output): up to zc_max bytes the kernels read the
+// inputs from, and write the output to, mapped pinned host memory — no copy calls, one synchronisation (cl_conv.cpp:399,
+// 455); larger blocks go through staged_call
+template <class Run>
+int block_call(ZeroCopy &z, Staging &st, size_t zc_max, hipStream_t s, float *out, const float *in1, const float *in2,
+               size_t blk, Run run) {
+  if (blk > zc_max) return staged_call(st, s, out, blk, in1, in2, blk, run);
+  int e;
+  if ((e = z.in1.ensure(blk)) || (e = z.out.ensure(blk)) || (in2 && (e = z.in2.ensure(blk)))) return e;
+  memcpy(z.in1.h, in1, blk);
+  if (in2) memcpy(z.in2.h, in2, blk);
+  if ((e = run(z.out.d, z.in1.d, in2 ? z.in2.d : nullptr))) return e;
+  HIP_TRY(hipStreamSynchronize(s));
+  memcpy(out, z.out.h, blk);
+  return CLFA_SUCCESS;
+}
+
+// tables of the pts-bin transforms of Clpconv and the matrix (cl_conv.cpp:263-287)
+int upload_conv_tables(int pts, DevBuf &half, DevBuf &w2f, DevBuf &w2i) {
+  int e;
+  if ((e = upload_half(half, pts)) || (e = upload_w2(w2f, pts, -1.f)) || (e = upload_w2(w2i, pts, 1.f))) return e;
+  return CLFA_SUCCESS;
+}
+
+// blocks per multi-block sub-batch: workspaces of per_block bytes per block within ~384 MiB, at most 1024 blocks; the
+// tuning switch `env` (read per object) may lower it
+int subbatch_cap(long per_block, const char *env_name) {
+  long cap = (384L << 20) / per_block;
+  const char *env = getenv(env_name);
+  if (env && atol(env) > 0 && atol(env) < cap) cap = atol(env);
+  return (int)(cap < 1 ? 1 : (cap > 1024 ? 1024 : cap));
+}
+
+// the count checks of a multi-block call: *len = nblocks * pts floats per row, 0 when there is nothing to do
+int blocks_len(long nblocks, long pts, const void *out, const void *in, long *len) {
+  *len = 0;
+  if (nblocks < 0) return CLFA_INVALID_VALUE;
+  if (nblocks == 0) return CLFA_SUCCESS;
+  if (!out || !in || nblocks > 0x7fffffffL / pts) return CLFA_INVALID_VALUE;
+  *len = nblocks * pts;
+  return CLFA_SUCCESS;
+}
+
+// ... and of a device-resident one: out_rows rows of out and in_rows rows of in1 (and in2), 4-byte aligned, strides of
+// at least *len floats, out overlapping no input row even partly
+int check_blocks_dev(long nblocks, long pts, const void *out, long out_stride, long out_rows, const void *in1,
+                     const void *in2, long in_stride, long in_rows, long *len) {
+  if (int e = blocks_len(nblocks, pts, out, in1, len)) return e;
+  if (!*len) return CLFA_SUCCESS;
+  if (in_stride < *len || out_stride < *len) return CLFA_INVALID_VALUE;
+  auto misaligned = [](const void *q) { return ((uintptr_t)q & 3) != 0; };
+  if (misaligned(out) || misaligned(in1) || (in2 && misaligned(in2))) return CLFA_INVALID_VALUE;
+  const long lb = *len * (long)sizeof(float);
+  const long osb = out_stride * (long)sizeof(float), isb = in_stride * (long)sizeof(float);
+  if (rows_overlap(out, osb, out_rows, in1, isb, in_rows, lb) || (in2 && rows_overlap(out, osb, out_rows, in2, isb, in_rows, lb)))
+    return CLFA_INVALID_VALUE;
+  return CLFA_SUCCESS;
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------
+// partitioned convolution
+// ---------------------------------------------------------------------------------
+
+struct clfa_pconv {
+  DeviceInfo di;
+  PconvGeom g{};
+  int cvs = 0, pts = 0;
+  int wp = 0, wp2 = 0;   // cl_conv.cpp:144
+  int err = 0;
+  hipStream_t stream = nullptr;
+  DevBuf half, w2f, w2i;             // tables (cl_conv.cpp:263-287)
+  DevBuf ringA, ringB, acc, tail;    // spec1, spec2, in1-as-accumulator, olap tail
+  Staging io;                        // staging for the host entry points
+  ZeroCopy zc;                       // ... zero-copy staging for small blocks
+  DevBuf ir;                         // ... and for push_ir
+  DevBuf four, scratch, work;        // partitions above the LDS sizes: large-N tables, scratch, work frames
+  StreamOrder order;
+  bool fused = false;                // one launch per block (resolved at creation)
+  PconvCoop coop{-1, 1};             // few channels: one cooperative launch per block (logs >= 0)
+  DevBuf cnt;                        // ... its arrival counters (one per channel)
+  FftTables big;
+  // multi-block calls (clfa_pconv_process_blocks_dev): workspaces allocated by the first call that needs them
+  int bcap = 1;                      // blocks per sub-batch (CLFA_PCONV_BLOCKS_MAX: tuning switch, read at creation)
+  int bkt = 4;                       // outputs per MAC tile
+  DevBuf bX, bXB, bY, btail, bstage; // spectra of the new blocks / second inputs, output spectra, new tail; loop staging
+};
+
+static int pconv_setup(clfa_pconv *p, int device, int cvs, int pts, int channels) {
+  p->cvs = cvs;
+  p->pts = pts;
+  if (!is_pow2(pts) || pts < 2 || pts > (1 << kPconvMaxLogBins) || cvs < pts || channels < 1)
+    return CLFA_INVALID_VALUE;
+  p->g.bins = pts;                 // cl_conv.cpp:143
+  p->g.logb = ilog2(pts);
+  p->g.nparts = cvs / pts;         // floor: remainder samples are dropped
+  p->g.channels = channels;
+  p->wp = 0;
+  p->wp2 = p->g.nparts - 1;        // cl_conv.cpp:144
+  int e = device_info(device, p->di);
+  if (e) return e;
+  p->fused = pconv_fused_ok(p->g, p->di) && !getenv("CLFA_PCONV_NO_FUSE");   // tuning switch, read once
+  if (!p->fused) p->coop = pconv_coop_plan(p->g, p->di);
+  // multi-block sub-batches: the three channels x cap x bins complex workspaces
+  // (CLFA_PCONV_BLOCKS_MAX is read per object, like CLFA_PCONV_COOP_MAX_KB)
+  p->bcap = subbatch_cap(3L * channels * pts * (long)sizeof(cpx), "CLFA_PCONV_BLOCKS_MAX");
+  p->bkt = pconv_blocks_tile(p->g, p->di);
+  ENTER_DEVICE(device);
+  HIP_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
+  if ((e = upload_conv_tables(pts, p->half, p->w2f, p->w2i))) return e;
+  if (p->g.logb > kLdsMaxLog) {
+    const int n = pts;
+    std::vector<cpx> all;
+    fill_fourstep_tables(all, p->g.logb);
+    if ((e = upload(p->four, all.data(), sizeof(cpx) * all.size()))) return e;
+    p->big.four = (const cpx *)p->four.p;
+    if ((e = p->scratch.ensure((size_t)fourstep_grid(p->di) * n * sizeof(cpx)))) return e;
+    if ((e = p->work.ensure(sizeof(cpx) * (size_t)channels * n))) return e;
+  }
+  const size_t ring = sizeof(cpx) * (size_t)channels * p->g.nparts * pts;
+  const size_t blk = sizeof(float) * (size_t)channels * pts;
+  if ((e = p->ringA.ensure(ring))) return e;
+  if ((e = p->ringB.ensure(ring))) return e;
+  const int acc_copies = p->coop.logs >= 0 ? p->coop.sparts : pconv_mac_split(p->g);
+  if ((e = p->acc.ensure(sizeof(cpx) * (size_t)channels * pts * acc_copies))) return e;
+  if ((e = p->tail.ensure(blk))) return e;
+  if (p->coop.logs >= 0) {
+    if ((e = p->cnt.ensure(sizeof(unsigned) * (size_t)channels))) return e;
+    HIP_TRY(hipMemsetAsync(p->cnt.p, 0, sizeof(unsigned) * (size_t)channels, p->stream));
+  }
+  // zero-initialised state (cl_conv.cpp:303-313)
+  HIP_TRY(hipMemsetAsync(p->ringA.p, 0, ring, p->stream));
+  HIP_TRY(hipMemsetAsync(p->ringB.p, 0, ring, p->stream));
+  HIP_TRY(hipMemsetAsync(p->tail.p, 0, blk, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return CLFA_SUCCESS;
+}
+
+// forward chain of one block for all channels: in -> spectrum frame `frame` of `ring`
+static int pconv_forward(clfa_pconv *p, const float *in, long in_stride, cpx *ring, int frame, hipStream_t s) {
+  if (p->g.logb <= kLdsMaxLog) {
+    HIP_TRY(launch_pconv_forward(p->g, in, in_stride, ring, frame, (const cpx *)p->half.p, (const cpx *)p->w2f.p, s));
+    return CLFA_SUCCESS;
+  }
+  // composed: zero-pad -> large-N forward FFT (unscaled) -> reference r2c -> place the frames in the ring
+  const int bins = p->g.bins, ch = p->g.channels;
+  cpx *work = (cpx *)p->work.p;
+  HIP_TRY(launch_pconv_pad(in, in_stride, work, bins, ch, s));
+  HIP_TRY(launch_fft_4step(p->g.logb, true, false, work, (cpx *)p->scratch.p, p->big, ch, p->di, s));
+  HIP_TRY(launch_r2c_pack(work, (const cpx *)p->w2f.p, bins, ch, s));
+  HIP_TRY(hipMemcpy2DAsync(ring + (size_t)frame * bins, sizeof(cpx) * (size_t)p->g.nparts * bins, work,
+                           sizeof(cpx) * (size_t)bins, sizeof(cpx) * (size_t)bins, ch, hipMemcpyDeviceToDevice, s));
+  return CLFA_SUCCESS;
+}
+
+// inverse chain: accumulator -> c2r -> inverse FFT -> overlap-add
+static int pconv_inverse(clfa_pconv *p, float *out, hipStream_t s) {
+  if (p->g.logb <= kLdsMaxLog) {
+    HIP_TRY(launch_pconv_inverse(p->g, (const cpx *)p->acc.p, (float *)p->tail.p, out, (const cpx *)p->half.p,
+                                 (const cpx *)p->w2i.p, s));
+    return CLFA_SUCCESS;
+  }
+  const int bins = p->g.bins, ch = p->g.channels;
+  cpx *acc = (cpx *)p->acc.p;
+  HIP_TRY(launch_c2r_unpack(acc, (const cpx *)p->w2i.p, bins, ch, s));
+  HIP_TRY(launch_fft_4step(p->g.logb, false, false, acc, (cpx *)p->scratch.p, p->big, ch, p->di, s));
+  HIP_TRY(launch_pconv_olap((const float *)acc, (float *)p->tail.p, out, bins, ch, s));
+  return CLFA_SUCCESS;
+}
+
+static bool pconv_blocks_looped(const clfa_pconv *p) {
+  return p->g.logb < kPconvBlocksMinLog || p->g.logb > kPconvBlocksMaxLog;
+}
+
+extern "C" {
+
+int clfa_pconv_create(clfa_pconv **pc, int device, int cvs, int pts, int channels) {
+  return create_object(pc, [&](clfa_pconv *p) { return pconv_setup(p, device, cvs, pts, channels); });
+}
+
+void clfa_pconv_destroy(clfa_pconv *p) { destroy_object(p); }
+
+int clfa_pconv_get_error(const clfa_pconv *p) { return p ? p->err : CLFA_INVALID_VALUE; }
+int clfa_pconv_nparts(const clfa_pconv *p) { return p ? p->g.nparts : 0; }
+int clfa_pconv_wp(const clfa_pconv *p) { return p ? p->wp : -1; }
+int clfa_pconv_wp2(const clfa_pconv *p) { return p ? p->wp2 : -1; }
+const char *clfa_pconv_kernel_name(const clfa_pconv *p) {
+  if (!p || p->err) return "";
+  return p->fused ? "k_pconv_fused" : (p->coop.logs >= 0 ? "k_pconv_coop" : "chain");
+}
+size_t clfa_pconv_state_bytes(const clfa_pconv *p) {
+  return p ? p->ringA.bytes + p->ringB.bytes + p->acc.bytes + p->tail.bytes : 0;
+}
+
+int clfa_pconv_push_ir_dev(clfa_pconv *p, const void *ir, long channel_stride, void *stream) {
+  if (int e = obj_error(p)) return e;
+  if (!ir || channel_stride < (long)p->g.nparts * p->pts) return CLFA_INVALID_VALUE;
+  ENTER_DEVICE(p->di.device);
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(p->order.use(s));
+  const long stride = channel_stride;
+  // cl_conv.cpp:358-386: partition i -> frame wp2, wp2 counts down from nparts-1
+  for (int i = 0; i < p->g.nparts; i++) {
+    int e = pconv_forward(p, (const float *)ir + (long)i * p->pts, stride, (cpx *)p->ringB.p, p->wp2, s);
+    if (e) return e;
+    p->wp2 = p->wp2 == 0 ? p->g.nparts - 1 : p->wp2 - 1;
+  }
+  return CLFA_SUCCESS;
+}
+
+int clfa_pconv_push_ir(clfa_pconv *p, const float *ir) {
+  if (int e = obj_error(p)) return e;
+  if (!ir) return CLFA_INVALID_VALUE;
+  ENTER_DEVICE(p->di.device);
+  const size_t bytes = sizeof(float) * (size_t)p->g.channels * p->g.nparts * p->pts;
+  int e = p->ir.ensure(bytes);
+  if (e) return e;
+  HIP_TRY(hipMemcpyAsync(p->ir.p, ir, bytes, hipMemcpyHostToDevice, p->stream));
+  if ((e = clfa_pconv_push_ir_dev(p, p->ir.p, (long)p->g.nparts * p->pts, p->stream))) return e;
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return CLFA_SUCCESS;
+}
+
+int clfa_pconv_process_dev(clfa_pconv *p, void *out, const void *in1, const void *in2, void *stream) {
+  if (int e = obj_error(p)) return e;
+  if (!out || !in1) return CLFA_INVALID_VALUE;
+  if (p->fused || p->coop.logs >= 0) {
+    // the one-launch routes read the inputs of ALL channels while workgroups of other channels may already write their
+    // output (the buffers are __restrict__): any overlap of out with an input — not only equal pointers — is refused.
+    // (The launch chain below has read every input when its forward launch ends, before the inverse launch writes `out`:
+    // in place is fine there, as it was for the reference's host arrays.)
+    const size_t blk = sizeof(float) * (size_t)p->pts * (size_t)p->g.channels;
+    if (spans_overlap(out, blk, in1, blk) || (in2 && spans_overlap(out, blk, in2, blk))) return CLFA_INVALID_VALUE;
+  }
+  ENTER_DEVICE(p->di.device);
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(p->order.use(s));
+  int e;
+  if (p->fused || p->coop.logs >= 0) {
+    // whole block in one launch; ring indices advance exactly as below — committed only once the launch has been accepted
+    // (a rejected launch must not skew the host's ring position against the device's rings)
+    const int frame1 = p->wp, frame2 = p->wp2;
+    const int wp_next = p->wp != p->g.nparts - 1 ? p->wp + 1 : 0;
+    const int wp2_next = in2 ? (p->wp2 == 0 ? p->g.nparts - 1 : p->wp2 - 1) : p->wp2;
+    if (!p->fused) {
+      HIP_TRY(launch_pconv_coop(p->g, p->coop, (const float *)in1, (const float *)in2, (cpx *)p->ringA.p,
+                                (cpx *)p->ringB.p, (float *)p->tail.p, (float *)out, frame1, frame2, wp_next,
+                                (const cpx *)p->half.p, (const cpx *)p->w2f.p, (const cpx *)p->w2i.p, (cpx *)p->acc.p,
+                                (unsigned *)p->cnt.p, p->di.num_cus, s));
+    } else {
+      HIP_TRY(launch_pconv_fused(p->g, (const float *)in1, (const float *)in2, (cpx *)p->ringA.p, (cpx *)p->ringB.p,
+                                 (float *)p->tail.p, (float *)out, frame1, frame2, wp_next, (const cpx *)p->half.p,
+                                 (const cpx *)p->w2f.p, (const cpx *)p->w2i.p, s, p->g.channels < p->di.num_cus));
+    }
+    p->wp = wp_next;
+    p->wp2 = wp2_next;
+    return CLFA_SUCCESS;
+  }
+  const bool lds = p->g.logb <= kLdsMaxLog;
+  // forward chain(s): cl_conv.cpp:399-419 / 465-513 (both inputs of a time-varying block in one launch)
+  if (lds && in2) {
+    HIP_TRY(launch_pconv_forward(p->g, (const float *)in1, p->pts, (cpx *)p->ringA.p, p->wp, (const cpx *)p->half.p,
+                                 (const cpx *)p->w2f.p, s, (const float *)in2, (cpx *)p->ringB.p, p->wp2));
+  } else {
+    if ((e = pconv_forward(p, (const float *)in1, p->pts, (cpx *)p->ringA.p, p->wp, s))) return e;
+    if (in2 && (e = pconv_forward(p, (const float *)in2, p->pts, (cpx *)p->ringB.p, p->wp2, s))) return e;
+  }
+  p->wp = p->wp != p->g.nparts - 1 ? p->wp + 1 : 0;            // cl_conv.cpp:424 / 516
+  if (in2) p->wp2 = p->wp2 == 0 ? p->g.nparts - 1 : p->wp2 - 1;  // cl_conv.cpp:519
+  // cl_conv.cpp:428-449.  (Adding the partial sums of a split MAC inside the single-workgroup inverse kernel
+  // instead of the wide k_pconv_reduce launch was measured: 22 -> 130 us per block for one channel.)
+  HIP_TRY(launch_pconv_mac(p->g, (const cpx *)p->ringA.p, (const cpx *)p->ringB.p, p->wp, (cpx *)p->acc.p, s));
+  if ((e = pconv_inverse(p, (float *)out, s))) return e;
+  return CLFA_SUCCESS;
+}
+
+static int pconv_host(clfa_pconv *p, float *out, const float *in1, const float *in2) {
+  if (int e = obj_error(p)) return e;
+  if (!out || !in1) return CLFA_INVALID_VALUE;
+  ENTER_DEVICE(p->di.device);
+  // one audio block of a few channels goes zero-copy
+  return block_call(p->zc, p->io, kZeroCopyMaxConv, p->stream, out, in1, in2, sizeof(float) * (size_t)p->g.channels * p->pts,
+                    [&](void *o, const void *i1, const void *i2) { return clfa_pconv_process_dev(p, o, i1, i2, p->stream); });
+}
+
+int clfa_pconv_convolution(clfa_pconv *p, float *out, const float *in) { return pconv_host(p, out, in, nullptr); }
+int clfa_pconv_convolution_tv(clfa_pconv *p, float *out, const float *in1, const float *in2) {
+  if (!in2) return CLFA_INVALID_VALUE;
+  return pconv_host(p, out, in1, in2);
+}
+
+// ---- many blocks per call -------------------------------------------------------
+
+const char *clfa_pconv_blocks_kernel_name(const clfa_pconv *p) {
+  if (!p || p->err) return "";
+  return pconv_blocks_looped(p) ? "loop" : "k_pconvb_mac";
+}
+
+size_t clfa_pconv_blocks_workspace_bytes(const clfa_pconv *p) {
+  return p ? p->bX.bytes + p->bXB.bytes + p->bY.bytes + p->btail.bytes + p->bstage.bytes : 0;
+}
+
+int clfa_pconv_process_blocks_dev(clfa_pconv *p, void *out, long out_stride, const void *in1, const void *in2,
+                                  long in_stride, long nblocks, void *stream) {
+  if (int e = obj_error(p)) return e;
+  const long pts = p->pts, ch = p->g.channels, nparts = p->g.nparts;
+  long len;
+  if (int e = check_blocks_dev(nblocks, pts, out, out_stride, ch, in1, in2, in_stride, ch, &len)) return e;
+  if (!len) return CLFA_SUCCESS;
+  ENTER_DEVICE(p->di.device);
+  hipStream_t s = (hipStream_t)stream;
+  const size_t frames = sizeof(cpx) * (size_t)ch * (size_t)p->bcap * (size_t)pts;
+  int e = pconv_blocks_looped(p)
+              ? ensure_workspaces({{&p->bstage, sizeof(float) * (size_t)ch * (size_t)pts * 3}}, s)
+              : ensure_workspaces({{&p->bX, frames}, {&p->bY, frames}, {&p->btail, sizeof(float) * (size_t)ch * (size_t)pts},
+                                   {&p->bXB, in2 ? frames : 0}}, s);
+  if (e) return e;
+  HIP_TRY(p->order.use(s));
+  const float *a1 = (const float *)in1, *a2 = (const float *)in2;
+  float *o = (float *)out;
+  if (pconv_blocks_looped(p)) {
+    // partitions outside the LDS transform sizes: block by block through clfa_pconv_process_dev, each block gathered into
+    // contiguous channels x pts staging (any alignment and stride) and scattered back
+    float *st1 = (float *)p->bstage.p, *st2 = st1 + ch * pts, *sto = st2 + ch * pts;
+    const size_t row = sizeof(float) * (size_t)pts;
+    const size_t isb = sizeof(float) * (size_t)in_stride, osb = sizeof(float) * (size_t)out_stride;
+    for (long j = 0; j < nblocks; j++) {
+      HIP_TRY(hipMemcpy2DAsync(st1, row, a1 + j * pts, isb, row, (size_t)ch, hipMemcpyDeviceToDevice, s));
+      if (a2) HIP_TRY(hipMemcpy2DAsync(st2, row, a2 + j * pts, isb, row, (size_t)ch, hipMemcpyDeviceToDevice, s));
+      if ((e = clfa_pconv_process_dev(p, sto, st1, a2 ? st2 : nullptr, stream))) return e;
+      HIP_TRY(hipMemcpy2DAsync(o + j * pts, osb, sto, row, row, (size_t)ch, hipMemcpyDeviceToDevice, s));
+    }
+    return CLFA_SUCCESS;
+  }
+  PconvBlocks a;
+  a.g = p->g;
+  a.cap = p->bcap;
+  a.kt = p->bkt;
+  a.in_stride = in_stride;
+  a.out_stride = out_stride;
+  a.aligned_in = ((uintptr_t)in1 & 7) == 0 && (!in2 || ((uintptr_t)in2 & 7) == 0) && (in_stride & 1) == 0;
+  a.aligned_out = ((uintptr_t)out & 7) == 0 && (out_stride & 1) == 0;
+  a.ringA = (cpx *)p->ringA.p;
+  a.ringB = (cpx *)p->ringB.p;
+  a.tail = (float *)p->tail.p;
+  a.X = (cpx *)p->bX.p;
+  a.XB = (cpx *)p->bXB.p;
+  a.Y = (cpx *)p->bY.p;
+  a.tail_ws = (float *)p->btail.p;
+  a.half = (const cpx *)p->half.p;
+  a.w2f = (const cpx *)p->w2f.p;
+  a.w2i = (const cpx *)p->w2i.p;
+  // time-varying sub-batches stay within nparts blocks: each second-input ring frame then changes at most once
+  const long kmax = in2 && nparts < p->bcap ? nparts : p->bcap;
+  for (long j0 = 0; j0 < nblocks; j0 += kmax) {
+    a.K = (int)(nblocks - j0 < kmax ? nblocks - j0 : kmax);
+    a.w = p->wp;
+    a.w2 = p->wp2;
+    a.in1 = a1 + j0 * pts;
+    a.in2 = a2 ? a2 + j0 * pts : nullptr;
+    a.out = o + j0 * pts;
+    HIP_TRY(launch_pconv_blocks(a, s));
+    p->wp = (int)((p->wp + a.K) % nparts);
+    if (a2) p->wp2 = (int)(((p->wp2 - a.K) % nparts + nparts) % nparts);
+  }
+  return CLFA_SUCCESS;
+}
+
+int clfa_pconv_convolution_blocks(clfa_pconv *p, float *out, const float *in1, const float *in2, long nblocks) {
+  if (int e = obj_error(p)) return e;
+  long len;
+  if (int e = blocks_len(nblocks, p->pts, out, in1, &len)) return e;
+  if (!len) return CLFA_SUCCESS;
+  const size_t bytes = sizeof(float) * (size_t)len * p->g.channels;
+  if (spans_overlap(out, bytes, in1, bytes) || (in2 && spans_overlap(out, bytes, in2, bytes))) return CLFA_INVALID_VALUE;
+  ENTER_DEVICE(p->di.device);
+  return staged_call(p->io, p->stream, out, bytes, in1, in2, bytes, [&](void *o, const void *i1, const void *i2) {
+    return clfa_pconv_process_blocks_dev(p, o, len, i1, i2, len, nblocks, p->stream);
+  });
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------
+// direct convolution
+// ---------------------------------------------------------------------------------
+
+struct clfa_dconv {
+  DeviceInfo di;
+  int irsize = 0, vsize = 0, wp = 0;
+  int err = 0;
+  hipStream_t stream = nullptr;
+  DevBuf del, coefs;
+  Staging io;          // staging of the host entry points' blocks (allocated at creation)
+  ZeroCopy zc;         // ... zero-copy staging for small blocks (mapped pinned host memory)
+  DevBuf part, cnt;    // partial sums per tap chunk and their arrival counter (plan.G > 1)
+  DconvPlan plan{64, 1, 1};
+  StreamOrder order;
+};
+
+static int dconv_setup(clfa_dconv *d, int device, int irsize, int vsize) {
+  d->irsize = irsize;
+  d->vsize = vsize;
+  if (irsize < 1 || vsize < 1 || (long)irsize * vsize > 0x7fffffffL) return CLFA_INVALID_VALUE;
+  int e = device_info(device, d->di);
+  if (e) return e;
+  ENTER_DEVICE(device);
+  HIP_TRY(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
+  const size_t ring = sizeof(float) * ((size_t)irsize + vsize), blk = sizeof(float) * (size_t)vsize;
+  d->plan = dconv_plan(irsize, vsize);
+  if ((e = d->del.ensure(ring)) || (e = d->coefs.ensure(ring)) || (e = d->io.out.ensure(blk)) || (e = d->io.in1.ensure(blk)) ||
+      (e = d->io.in2.ensure(blk)) || (e = d->part.ensure(blk * d->plan.G)) ||
+      (e = d->cnt.ensure(sizeof(unsigned) * d->plan.VB)))
+    return e;
+  // the reference leaves these uninitialised (cl_dconv.cpp:87-91); zero is the intent
+  HIP_TRY(hipMemsetAsync(d->del.p, 0, ring, d->stream));
+  HIP_TRY(hipMemsetAsync(d->coefs.p, 0, ring, d->stream));
+  HIP_TRY(hipMemsetAsync(d->cnt.p, 0, sizeof(unsigned) * d->plan.VB, d->stream));
+  HIP_TRY(hipStreamSynchronize(d->stream));
+  return CLFA_SUCCESS;
+}
+
+// one block on stream s, everything device-resident: ring write at wp with wrap-around (intent of cl_dconv.cpp:112-122;
+// the two-input form writes in2 into the coefficient ring at the same point, :134-147), wp advanced (:124), vsize
+// outputs — all in ONE launch (conv_kernels.hip, k_dconv_block)
+static int dconv_block(clfa_dconv *d, float *out, const float *in1, const float *in2, hipStream_t s) {
+  const int wp = d->wp;
+  HIP_TRY(launch_dconv_block(d->plan, out, in1, in2, (float *)d->del.p, (float *)d->coefs.p, (float *)d->part.p,
+                             (unsigned *)d->cnt.p, d->irsize, d->vsize, wp, d->di.num_cus, s));
+  d->wp = (wp + d->vsize) % (d->irsize + d->vsize);   // committed only once the launch has been accepted
+  return CLFA_SUCCESS;
+}
+
+static int dconv_host(clfa_dconv *d, float *out, const float *in1, const float *in2) {
+  if (int e = obj_error(d)) return e;
+  if (!out || !in1) return CLFA_INVALID_VALUE;
+  ENTER_DEVICE(d->di.device);
+  HIP_TRY(d->order.use(d->stream));
+  // an audio block goes zero-copy as the partitioned convolution's host path does (kZeroCopyMaxDconv)
+  return block_call(d->zc, d->io, kZeroCopyMaxDconv, d->stream, out, in1, in2, sizeof(float) * (size_t)d->vsize,
+                    [&](void *o, const void *i1, const void *i2) {
+                      return dconv_block(d, (float *)o, (const float *)i1, (const float *)i2, d->stream);
+                    });
+}
+
+extern "C" {
+
+int clfa_dconv_create(clfa_dconv **dc, int device, int irsize, int vsize) {
+  return create_object(dc, [&](clfa_dconv *d) { return dconv_setup(d, device, irsize, vsize); });
+}
+
+void clfa_dconv_destroy(clfa_dconv *d) { destroy_object(d); }
+
+int clfa_dconv_get_error(const clfa_dconv *d) { return d ? d->err : CLFA_INVALID_VALUE; }
+
+int clfa_dconv_push_ir(clfa_dconv *d, const float *ir) {
+  if (int e = obj_error(d)) return e;
+  if (!ir) return CLFA_INVALID_VALUE;
+  ENTER_DEVICE(d->di.device);
+  HIP_TRY(d->order.use(d->stream));
+  HIP_TRY(hipMemcpyAsync(d->coefs.p, ir, sizeof(float) * d->irsize, hipMemcpyHostToDevice, d->stream));
+  HIP_TRY(hipStreamSynchronize(d->stream));
+  return CLFA_SUCCESS;
+}
+
+int clfa_dconv_convolution(clfa_dconv *d, float *out, const float *in) { return dconv_host(d, out, in, nullptr); }
+
+int clfa_dconv_convolution_tv(clfa_dconv *d, float *out, const float *in1, const float *in2) {
+  if (d && !d->err && !in2) return CLFA_INVALID_VALUE;
+  return dconv_host(d, out, in1, in2);
+}
+
+int clfa_dconv_process_dev(clfa_dconv *d, void *out, const void *in1, const void *in2, void *stream) {
+  if (int e = obj_error(d)) return e;
+  if (!out || !in1) return CLFA_INVALID_VALUE;
+  // the last-arriving workgroup writes out while others may still stage their in1 / in2 windows: no overlap at all
+  const size_t blk = sizeof(float) * (size_t)d->vsize;
+  if (spans_overlap(out, blk, in1, blk) || (in2 && spans_overlap(out, blk, in2, blk))) return CLFA_INVALID_VALUE;
+  ENTER_DEVICE(d->di.device);
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(d->order.use(s));
+  return dconv_block(d, (float *)out, (const float *)in1, (const float *)in2, s);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------
+// convolution matrix (pconv_matrix.hip)
+// ---------------------------------------------------------------------------------
+
+struct clfa_pconv_matrix {
+  DeviceInfo di;
+  int cvs = 0, pts = 0, nparts = 0, inputs = 0, outputs = 0, logb = 0;
+  int wp = 0;                    // ring A position, shared by every input
+  int err = 0;
+  char log[256];
+  hipStream_t stream = nullptr;
+  DevBuf half, w2f, w2i;         // tables of the pts-bin transforms (as Clpconv)
+  DevBuf H, ringA, tail;         // responses, input spectra rings, overlap-add tails
+  DevBuf X, Y, P, tail_ws;       // sub-batch workspaces: allocated by the first call that needs them
+  Staging io;                    // staging of the host entry points (one input: io.in2 stays empty)
+  DevBuf hir;                    // ... and of push_ir
+  PconvMatrixPlan plan;
+  int cap = 1;                   // blocks per sub-batch (CLFA_PCONV_MATRIX_BLOCKS_MAX: tuning switch, read at creation)
+  StreamOrder order;
+};
+
+static int mconv_setup(clfa_pconv_matrix *p, int device, int cvs, int pts, int inputs, int outputs) {
+  p->log[0] = 0;
+  p->cvs = cvs;
+  p->pts = pts;
+  p->inputs = inputs;
+  p->outputs = outputs;
+  if (!is_pow2(pts) || pts < (1 << kPconvBlocksMinLog) || pts > (1 << kPconvBlocksMaxLog)) {
+    snprintf(p->log, sizeof(p->log), "pts must be a power of two, %d..%d (got %d)", 1 << kPconvBlocksMinLog,
+             1 << kPconvBlocksMaxLog, pts);
+    return CLFA_INVALID_VALUE;
+  }
+  if (cvs < pts || inputs < 1 || outputs < 1) {
+    snprintf(p->log, sizeof(p->log), "need cvs >= pts, inputs >= 1, outputs >= 1 (got %d, %d, %d)", cvs, inputs, outputs);
+    return CLFA_INVALID_VALUE;
+  }
+  p->logb = ilog2(pts);
+  p->nparts = cvs / pts;   // floor, as Clpconv
+  int e = device_info(device, p->di);
+  if (e) return e;
+  p->plan = pconv_matrix_plan(pts, p->nparts, inputs, outputs, p->di);
+  // tuning switches, read per object (tools/time_mconv.py sweeps them): outputs per MAC tile, reduction segments
+  if (const char *env = getenv("CLFA_PCONV_MATRIX_TILE")) {
+    if (atoi(env) == 4 || atoi(env) == 16) p->plan.kt = atoi(env);
+  }
+  if (const char *env = getenv("CLFA_PCONV_MATRIX_SEGS")) {
+    if (atoi(env) >= 1 && atoi(env) <= 4096) p->plan.segs = atoi(env);
+  }
+  // sub-batch workspaces X, Y and the segments' partials (CLFA_PCONV_MATRIX_BLOCKS_MAX: read per object, like
+  // CLFA_PCONV_BLOCKS_MAX)
+  p->cap = subbatch_cap(((long)inputs + (long)outputs * p->plan.segs) * pts * (long)sizeof(cpx), "CLFA_PCONV_MATRIX_BLOCKS_MAX");
+  ENTER_DEVICE(device);
+  HIP_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
+  if ((e = upload_conv_tables(pts, p->half, p->w2f, p->w2i))) return e;
+  const size_t frame = sizeof(cpx) * (size_t)pts;
+  const size_t hbytes = frame * (size_t)outputs * inputs * p->nparts, abytes = frame * (size_t)inputs * p->nparts;
+  const size_t tbytes = sizeof(float) * (size_t)outputs * pts;
+  if ((e = p->H.ensure(hbytes)) || (e = p->ringA.ensure(abytes)) || (e = p->tail.ensure(tbytes))) return e;
+  // zero responses, history and tails
+  HIP_TRY(hipMemsetAsync(p->H.p, 0, hbytes, p->stream));
+  HIP_TRY(hipMemsetAsync(p->ringA.p, 0, abytes, p->stream));
+  HIP_TRY(hipMemsetAsync(p->tail.p, 0, tbytes, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return CLFA_SUCCESS;
+}
+
+extern "C" {
+
+int clfa_pconv_matrix_create(clfa_pconv_matrix **m, int device, int cvs, int pts, int inputs, int outputs) {
+  return create_object(m, [&](clfa_pconv_matrix *p) { return mconv_setup(p, device, cvs, pts, inputs, outputs); });
+}
+
+void clfa_pconv_matrix_destroy(clfa_pconv_matrix *p) { destroy_object(p); }
+
+int clfa_pconv_matrix_get_error(const clfa_pconv_matrix *p) { return p ? p->err : CLFA_INVALID_VALUE; }
+const char *clfa_pconv_matrix_get_log(const clfa_pconv_matrix *p) { return p ? p->log : ""; }
+int clfa_pconv_matrix_nparts(const clfa_pconv_matrix *p) { return p && !p->err ? p->nparts : 0; }
+size_t clfa_pconv_matrix_state_bytes(const clfa_pconv_matrix *p) {
+  return p ? p->H.bytes + p->ringA.bytes + p->tail.bytes : 0;
+}
+size_t clfa_pconv_matrix_workspace_bytes(const clfa_pconv_matrix *p) {
+  return p ? p->X.bytes + p->Y.bytes + p->P.bytes + p->tail_ws.bytes : 0;
+}
+const char *clfa_pconv_matrix_kernel_name(const clfa_pconv_matrix *p) { return !p || p->err ? "" : "k_pconvm_mac"; }
+
+int clfa_pconv_matrix_push_ir_dev(clfa_pconv_matrix *p, const void *ir, long row_stride, void *stream) {
+  if (int e = obj_error(p)) return e;
+  const long len = (long)p->nparts * p->pts;
+  if (!ir || row_stride < len || ((uintptr_t)ir & 3)) return CLFA_INVALID_VALUE;
+  ENTER_DEVICE(p->di.device);
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(p->order.use(s));
+  // every partition of every row in one forward launch: row (o, i) partition q -> H frame ((o * inputs + i) * nparts + q)
+  const int aligned = ((uintptr_t)ir & 7) == 0 && (row_stride & 1) == 0;
+  HIP_TRY(launch_pconvb_forward(p->logb, (const float *)ir, row_stride, (cpx *)p->H.p, p->nparts, p->nparts,
+                                p->outputs * p->inputs, aligned, (const cpx *)p->half.p, (const cpx *)p->w2f.p, s));
+  return CLFA_SUCCESS;
+}
+
+int clfa_pconv_matrix_push_ir(clfa_pconv_matrix *p, const float *ir) {
+  if (int e = obj_error(p)) return e;
+  if (!ir) return CLFA_INVALID_VALUE;
+  ENTER_DEVICE(p->di.device);
+  const long len = (long)p->nparts * p->pts;
+  const size_t bytes = sizeof(float) * (size_t)len * p->outputs * p->inputs;
+  int e = p->hir.ensure(bytes);
+  if (e) return e;
+  HIP_TRY(hipMemcpyAsync(p->hir.p, ir, bytes, hipMemcpyHostToDevice, p->stream));
+  if ((e = clfa_pconv_matrix_push_ir_dev(p, p->hir.p, len, p->stream))) return e;
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return CLFA_SUCCESS;
+}
+
+int clfa_pconv_matrix_process_dev(clfa_pconv_matrix *p, void *out, long out_stride, const void *in, long in_stride,
+                                  long nblocks, void *stream) {
+  if (int e = obj_error(p)) return e;
+  const long pts = p->pts, nparts = p->nparts;
+  long len;
+  if (int e = check_blocks_dev(nblocks, pts, out, out_stride, p->outputs, in, nullptr, in_stride, p->inputs, &len)) return e;
+  if (!len) return CLFA_SUCCESS;
+  ENTER_DEVICE(p->di.device);
+  hipStream_t s = (hipStream_t)stream;
+  const size_t frames = sizeof(cpx) * (size_t)p->cap * p->pts;
+  int e = ensure_workspaces({{&p->X, frames * p->inputs},
+                             {&p->Y, frames * p->outputs},
+                             {&p->P, frames * p->outputs * (size_t)(p->plan.segs - 1)},
+                             {&p->tail_ws, sizeof(float) * (size_t)p->outputs * p->pts}},
+                            s);
+  if (e) return e;
+  HIP_TRY(p->order.use(s));
+  PconvMatrixArgs a;
+  a.logb = p->logb;
+  a.bins = p->pts;
+  a.nparts = p->nparts;
+  a.inputs = p->inputs;
+  a.outputs = p->outputs;
+  a.plan = p->plan;
+  a.cap = p->cap;
+  a.in_stride = in_stride;
+  a.out_stride = out_stride;
+  a.aligned_in = ((uintptr_t)in & 7) == 0 && (in_stride & 1) == 0;
+  a.aligned_out = ((uintptr_t)out & 7) == 0 && (out_stride & 1) == 0;
+  a.H = (const cpx *)p->H.p;
+  a.ringA = (cpx *)p->ringA.p;
+  a.tail = (float *)p->tail.p;
+  a.X = (cpx *)p->X.p;
+  a.Y = (cpx *)p->Y.p;
+  a.P = (cpx *)p->P.p;
+  a.tail_ws = (float *)p->tail_ws.p;
+  a.half = (const cpx *)p->half.p;
+  a.w2f = (const cpx *)p->w2f.p;
+  a.w2i = (const cpx *)p->w2i.p;
+  const float *src = (const float *)in;
+  float *dst = (float *)out;
+  for (long j0 = 0; j0 < nblocks; j0 += p->cap) {
+    a.K = (int)(nblocks - j0 < p->cap ? nblocks - j0 : p->cap);
+    a.w = p->wp;
+    a.in = src + j0 * pts;
+    a.out = dst + j0 * pts;
+    HIP_TRY(launch_pconv_matrix(a, s));
+    p->wp = (int)((p->wp + a.K) % nparts);
+  }
+  return CLFA_SUCCESS;
+}
+
+int clfa_pconv_matrix_convolution(clfa_pconv_matrix *p, float *out, const float *in, long nblocks) {
+  if (int e = obj_error(p)) return e;
+  long len;
+  if (int e = blocks_len(nblocks, p->pts, out, in, &len)) return e;
+  if (!len) return CLFA_SUCCESS;
+  const size_t ib = sizeof(float) * (size_t)len * p->inputs, ob = sizeof(float) * (size_t)len * p->outputs;
+  if (spans_overlap(out, ob, in, ib)) return CLFA_INVALID_VALUE;
+  ENTER_DEVICE(p->di.device);
+  return staged_call(p->io, p->stream, out, ob, in, nullptr, ib, [&](void *o, const void *i1, const void *) {
+    return clfa_pconv_matrix_process_dev(p, o, len, i1, len, nblocks, p->stream);
+  });
+}
+
+}  // extern "C"

@@ -1,0 +1,300 @@
+// host.hpp — plumbing shared by the host side of the C ABI (clfft_amd.cpp: FFT plans, conv_host.cpp: the
+// convolutions, stft_host.cpp: Stft): error mapping, device and stream handling, owned device / pinned buffers, the
+// exact host tables, and the prelude / creation / destruction every object shares.  Everything here is inline and
+// hidden (-fvisibility=hidden): nothing becomes an exported symbol.
+#pragma once
+#include "../../include/clfft_amd.h"
+
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <initializer_list>
+#include <new>
+#include <vector>
+
+#include "internal.hpp"
+#include "overlap.hpp"
+
+namespace clfa {
+
+inline constexpr double kPI = 3.141592653589793;  // cl_fft.h:24
+
+inline int map_hip(hipError_t e) {
+  switch (e) {
+    case hipSuccess: return CLFA_SUCCESS;
+    case hipErrorNoDevice: return CLFA_DEVICE_NOT_FOUND;
+    case hipErrorInvalidDevice: return CLFA_INVALID_DEVICE;
+    case hipErrorOutOfMemory: return CLFA_MEM_OBJECT_ALLOCATION_FAILURE;
+    case hipErrorInvalidValue: return CLFA_INVALID_VALUE;
+    case hipErrorInvalidDevicePointer: return CLFA_INVALID_MEM_OBJECT;
+    case hipErrorInvalidResourceHandle: return CLFA_INVALID_COMMAND_QUEUE;
+    case hipErrorNotInitialized:
+    case hipErrorInsufficientDriver: return CLFA_DEVICE_NOT_AVAILABLE;
+    default: return CLFA_OUT_OF_RESOURCES;
+  }
+}
+
+#define HIP_TRY(expr)                   \
+  do {                                  \
+    hipError_t _e = (expr);             \
+    if (_e != hipSuccess) {             \
+      (void)hipGetLastError();          \
+      return map_hip(_e);               \
+    }                                   \
+  } while (0)
+
+// current-device guard: every entry point works on its object's device and leaves the caller's
+// current device as it found it
+struct DeviceGuard {
+  int prev = -1;
+  bool switched = false;
+  hipError_t enter(int device) {
+    hipError_t e = hipGetDevice(&prev);
+    if (e != hipSuccess) return e;
+    if (prev == device) return hipSuccess;
+    e = hipSetDevice(device);
+    switched = e == hipSuccess;
+    return e;
+  }
+  ~DeviceGuard() {
+    if (switched) (void)hipSetDevice(prev);
+  }
+};
+#define ENTER_DEVICE(dev) \
+  DeviceGuard _guard;     \
+  HIP_TRY(_guard.enter(dev))
+
+// An object owns one device workspace: work on a second stream has to wait for the first.  Switching
+// streams is rare (the reference has one queue per object), so the wait is a host-side synchronise
+// at the switch instead of an event per launch.
+struct StreamOrder {
+  hipStream_t last = nullptr;
+  bool any = false;
+  static bool capturing(hipStream_t s) {
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &st) != hipSuccess) {
+      (void)hipGetLastError();   // a stale handle: not capturing
+      return false;
+    }
+    return st != hipStreamCaptureStatusNone;
+  }
+  hipError_t use(hipStream_t s) {
+    hipError_t e = hipSuccess;
+    if (any && s != last) {
+      // a stream under hipGraph capture must not be waited for (nor may anything else be while it
+      // captures): captured launches are ordered by the graph, and whatever the object was doing
+      // before the capture has to be complete when the graph is replayed — the caller's contract.
+      // The same holds when the PREVIOUS stream is the one under capture.
+      if (!capturing(s) && !capturing(last)) {
+        e = hipStreamSynchronize(last);
+        if (e == hipErrorInvalidHandle || e == hipErrorContextIsDestroyed || e == hipErrorInvalidResourceHandle) {
+          // the caller has destroyed its previous stream (we do not own it and cannot keep it alive): its handle is
+          // gone, its work may not be — wait for the device instead of the handle, and carry on
+          (void)hipGetLastError();
+          e = hipDeviceSynchronize();
+        }
+      }
+    }
+    last = s;
+    any = true;
+    return e;
+  }
+};
+
+inline int ilog2(int n) {
+  int l = 0;
+  while ((1 << l) < n) l++;
+  return l;
+}
+inline bool is_pow2(int n) { return n > 0 && (n & (n - 1)) == 0; }
+
+// W_n^k = (cos(2 pi k/n), -sin(2 pi k/n)) rounded from double, the expression of
+// cl_fft.cpp:89-90 (`i * 2 * PI / N`) so the float values are bit-identical.
+inline void fill_twiddle(std::vector<cpx> &v, int count, int n, int stride, float sign) {
+  v.resize(count > 0 ? count : 1);
+  for (int i = 0; i < count; i++) {
+    int k = i * stride;
+    v[i].x = (float)cos(k * 2 * kPI / n);
+    v[i].y = sign * (float)sin(k * 2 * kPI / n);
+  }
+  if (count <= 0) v[0] = mk(1.f, 0.f);
+}
+// cl_fft.cpp:236-237 (`i * PI / N`)
+inline void fill_w2(std::vector<cpx> &v, int m, float sign) {
+  v.resize(m);
+  for (int i = 0; i < m; i++) {
+    v[i].x = (float)cos(i * kPI / m);
+    v[i].y = sign * (float)sin(i * kPI / m);
+  }
+}
+
+// host tables of the four-step kernel: [half N1 | half N2 | lo: W_n^k, k < 2^loglo | hi: W_n^(k 2^loglo)]
+inline void fill_fourstep_tables(std::vector<cpx> &all, int logn) {
+  int l1, l2, llo;
+  fourstep_split(logn, &l1, &l2, &llo);
+  const int n = 1 << logn, n1 = 1 << l1, n2 = 1 << l2, lo = 1 << llo, hi = n >> llo;
+  std::vector<cpx> part;
+  all.clear();
+  fill_twiddle(part, n1 / 2, n1, 1, -1.f);
+  all.insert(all.end(), part.begin(), part.begin() + n1 / 2);
+  fill_twiddle(part, n2 / 2, n2, 1, -1.f);
+  all.insert(all.end(), part.begin(), part.begin() + n2 / 2);
+  fill_twiddle(part, lo, n, 1, -1.f);
+  all.insert(all.end(), part.begin(), part.begin() + lo);
+  fill_twiddle(part, hi, n, lo, -1.f);
+  all.insert(all.end(), part.begin(), part.begin() + hi);
+}
+
+// Device memory owned by an object, freed with it (on the current device: destroy functions delete their object while
+// the object's device is current).  Objects hold these by value and are never copied.
+struct DevBuf {
+  void *p = nullptr;
+  size_t bytes = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  ~DevBuf() { release(); }
+  int ensure(size_t want) {
+    if (want <= bytes) return 0;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    bytes = 0;
+    hipError_t e = hipMalloc(&p, want);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      p = nullptr;
+      return map_hip(e);
+    }
+    bytes = want;
+    return 0;
+  }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    bytes = 0;
+  }
+};
+
+// pinned host memory mapped into the device's address space: kernels read / write it directly over
+// PCIe.  For the few KiB of one audio block that beats three hipMemcpyAsync calls (10-15 us each).
+struct HostBuf {
+  void *h = nullptr;   // host pointer
+  void *d = nullptr;   // the same memory as the device sees it
+  size_t bytes = 0;
+  HostBuf() = default;
+  HostBuf(const HostBuf &) = delete;
+  HostBuf &operator=(const HostBuf &) = delete;
+  ~HostBuf() { release(); }
+  int ensure(size_t want) {
+    if (want <= bytes) return 0;
+    release();
+    hipError_t e = hipHostMalloc(&h, want, hipHostMallocMapped);
+    if (e == hipSuccess) e = hipHostGetDevicePointer(&d, h, 0);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      release();
+      return map_hip(e);
+    }
+    bytes = want;
+    return 0;
+  }
+  void release() {
+    if (h) (void)hipHostFree(h);
+    h = d = nullptr;
+    bytes = 0;
+  }
+};
+
+inline int upload(DevBuf &b, const void *src, size_t bytes) {
+  int e = b.ensure(bytes);
+  if (e) return e;
+  HIP_TRY(hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice));
+  return 0;
+}
+// the tables of an n-point packed real transform: W_n^k, k < n / 2 (forward sign), and the pair table of `sign`
+inline int upload_half(DevBuf &b, int n) {
+  std::vector<cpx> h;
+  fill_twiddle(h, n / 2, n, 1, -1.f);
+  return upload(b, h.data(), sizeof(cpx) * h.size());
+}
+inline int upload_w2(DevBuf &b, int n, float sign) {
+  std::vector<cpx> h;
+  fill_w2(h, n, sign);
+  return upload(b, h.data(), sizeof(cpx) * n);
+}
+
+inline int device_info(int device, DeviceInfo &di) {
+  int count = 0;
+  hipError_t e = hipGetDeviceCount(&count);
+  if (e != hipSuccess || count <= 0) {
+    (void)hipGetLastError();
+    return CLFA_DEVICE_NOT_FOUND;
+  }
+  if (device < 0 || device >= count) return CLFA_INVALID_DEVICE;
+  hipDeviceProp_t prop;
+  HIP_TRY(hipGetDeviceProperties(&prop, device));
+  di.device = device;
+  di.num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+  return 0;
+}
+
+// the prelude of an entry point: a NULL object is an invalid value, an object whose creation failed returns that error
+//   if (int e = obj_error(p)) return e;
+template <class T>
+inline int obj_error(const T *p) {
+  return !p ? CLFA_INVALID_VALUE : p->err;
+}
+
+// every *_create: allocate, set up (the object keeps the setup's code as its error), hand the object out either way
+template <class T, class Setup>
+inline int create_object(T **out, Setup setup) {
+  if (!out) return CLFA_INVALID_VALUE;
+  T *p = new (std::nothrow) T();
+  if (!p) return CLFA_OUT_OF_HOST_MEMORY;
+  p->err = setup(p);
+  *out = p;
+  return p->err;
+}
+
+// every *_destroy: on the object's device, drain and destroy its stream, run `extra` (what the object owns besides its
+// buffers), then delete it — its DevBuf / HostBuf members free themselves while that device is still current
+template <class T, class Extra>
+inline void destroy_object(T *p, Extra extra) {
+  if (!p) return;
+  DeviceGuard guard;
+  (void)guard.enter(p->di.device);
+  if (p->stream) {
+    (void)hipStreamSynchronize(p->stream);
+    (void)hipStreamDestroy(p->stream);
+  }
+  extra(p);
+  delete p;
+}
+template <class T>
+inline void destroy_object(T *p) {
+  destroy_object(p, [](T *) {});
+}
+
+// workspaces that the first call needing them allocates: refused while the stream is captured (a hipMalloc there would
+// be outside the graph).  A want of 0 bytes is never missing.
+struct Want {
+  DevBuf *b;
+  size_t bytes;
+};
+inline int ensure_workspaces(std::initializer_list<Want> want, hipStream_t s) {
+  bool missing = false;
+  for (const Want &w : want) missing = missing || w.b->bytes < w.bytes;
+  if (!missing) return CLFA_SUCCESS;
+  if (StreamOrder::capturing(s)) return CLFA_INVALID_OPERATION;
+  for (const Want &w : want) {
+    int e = w.b->ensure(w.bytes);
+    if (e) return e;
+  }
+  return CLFA_SUCCESS;
+}
+
+}  // namespace clfa
