@@ -13,7 +13,7 @@
 // The rings are channels x nparts x bins complex64, resident in HBM.
 #include <cstdlib>
 
-#include "fft_wg.hpp"
+#include "pconv_device.hpp"
 
 namespace clfa {
 
@@ -84,7 +84,7 @@ static hipError_t launch_fwd_one(const PconvGeom &g, const float *in, long in_st
                                  int frame_b) {
   using G = LdsGeom<LOGB>;
   int groups = (g.channels + G::FPW - 1) / G::FPW;
-  int grid = groups < 4096 ? groups : 4096;
+  const int grid = grid_clamp(groups, 4096);
   hipLaunchKernelGGL((k_pconv_fwd<LOGB>), dim3(grid, in_b ? 2 : 1), dim3(G::WG), 0, s, in, in_stride, ring, frame,
                      g.nparts, g.channels, half, w2f, in_b, ring_b, frame_b);
   return hipGetLastError();
@@ -93,36 +93,14 @@ static hipError_t launch_fwd_one(const PconvGeom &g, const float *in, long in_st
 hipError_t launch_pconv_forward(const PconvGeom &g, const float *in, long in_stride, cpx *ring, int frame,
                                 const cpx *half, const cpx *w2f, hipStream_t s, const float *in_b, cpx *ring_b,
                                 int frame_b) {
-  switch (g.logb) {
-#define CLFA_B(L) \
-  case L:         \
-    return launch_fwd_one<L>(g, in, in_stride, ring, frame, half, w2f, s, in_b, ring_b, frame_b);
-    CLFA_B(1) CLFA_B(2) CLFA_B(3) CLFA_B(4) CLFA_B(5) CLFA_B(6) CLFA_B(7) CLFA_B(8) CLFA_B(9) CLFA_B(10)
-    CLFA_B(11) CLFA_B(12) CLFA_B(13)
-#undef CLFA_B
-    default:
-      return hipErrorInvalidValue;
-  }
+  return dispatch_logb<1, 13>(g.logb, [&](auto L) {
+    return launch_fwd_one<decltype(L)::value>(g, in, in_stride, ring, frame, half, w2f, s, in_b, ring_b, frame_b);
+  });
 }
 
 // ---------------------------------------------------------------------------------
 // multiply-accumulate over partitions (reference convol, cl_conv_kernels.h:102-118)
 // ---------------------------------------------------------------------------------
-struct alignas(16) cpx2 {
-  cpx a, b;
-};
-
-// both rings are read exactly once per block and exceed the Infinity Cache at config 4:
-// non-temporal 16-byte loads
-__device__ __forceinline__ cpx2 ld_stream(const cpx2 *p) {
-  typedef float v4f __attribute__((ext_vector_type(4)));
-  v4f r = __builtin_nontemporal_load(reinterpret_cast<const v4f *>(p));
-  cpx2 o;
-  o.a = mk(r.x, r.y);
-  o.b = mk(r.z, r.w);
-  return o;
-}
-
 // one lane = two adjacent bins (16 B) of one channel; loops the partitions of its segment.
 // blockIdx.y = segment of the partition axis (1 segment when there are enough channels to fill
 // the chip; few channels with long filters are split and summed by k_pconv_reduce in fixed order)
@@ -149,20 +127,15 @@ __global__ __launch_bounds__(256) void k_pconv_mac(const cpx *__restrict__ A, co
       for (int u = 0; u < UNROLL; u++) {
         int f = fr + u;
         f = f < nparts ? f : f - nparts;
-        av[u] = ld_stream(a + (long)f * hb);
-        bv[u] = ld_stream(b + (long)(p + u) * hb);
+        av[u] = ld_nt(a + (long)f * hb);
+        bv[u] = ld_nt(b + (long)(p + u) * hb);
       }
 #pragma unroll
-      for (int u = 0; u < UNROLL; u++) {
-        cpx pr = cmul_plain(av[u].a, bv[u].a);
-        const bool dc = i2 == 0;  // packed DC / Nyquist bin: (re*re, im*im); a select keeps the loop body one block
-        pr = mk(dc ? av[u].a.x * bv[u].a.x : pr.x, dc ? av[u].a.y * bv[u].a.y : pr.y);
-        s0 = cadd(s0, pr);
-        s1 = cadd(s1, cmul_plain(av[u].b, bv[u].b));
-      }
+      for (int u = 0; u < UNROLL; u++) mac_term(s0, s1, av[u], bv[u], i2 == 0);
       fr += UNROLL;
       fr = fr < nparts ? fr : fr - nparts;
     }
+    // (not on mac_term: with the select form hipcc emits other arithmetic for this loop — v_mul + v_sub where it fuses today)
     for (; p < p_end; p++) {
       cpx2 av = a[(long)fr * hb], bv = b[(long)p * hb];
       if (i2 == 0) {
@@ -294,18 +267,8 @@ __global__ __launch_bounds__(LdsGeom<LOGB>::WG) void k_pconv_inv(const cpx *__re
     };
     __syncthreads();
     if (active) {
-      for (int i = t; i < N / 2; i += T) {
-        if (i == 0) {
-          cpx c0 = x(0);
-          xb[0] = mk(c0.x + c0.y, c0.x - c0.y);
-          xb[lds_pad(N / 2)] = x(N / 2);
-        } else {
-          cpx oi, oj;
-          c2r_pair(x(i), x(N - i), w2_g[i], oi, oj);
-          xb[lds_pad(i)] = oi;
-          xb[lds_pad(N - i)] = oj;
-        }
-      }
+      for (int i = t; i < N / 2; i += T)
+        c2r_unpack<N>(i, x, [&](int k) { return w2_g[k]; }, [&](int p, cpx val) { xb[lds_pad(p)] = val; });
     }
     __syncthreads();
     cpx v[E];
@@ -335,23 +298,16 @@ static hipError_t launch_inv_one(const PconvGeom &g, const cpx *acc, float *tail
                                  const cpx *w2i, hipStream_t s, int nsplit) {
   using G = LdsGeom<LOGB>;
   int groups = (g.channels + G::FPW - 1) / G::FPW;
-  int grid = groups < 4096 ? groups : 4096;
+  const int grid = grid_clamp(groups, 4096);
   hipLaunchKernelGGL((k_pconv_inv<LOGB>), dim3(grid), dim3(G::WG), 0, s, acc, tail, out, g.channels, half, w2i, nsplit);
   return hipGetLastError();
 }
 
 hipError_t launch_pconv_inverse(const PconvGeom &g, const cpx *acc, float *tail, float *out, const cpx *half,
                                 const cpx *w2i, hipStream_t s, int nsplit) {
-  switch (g.logb) {
-#define CLFA_B(L) \
-  case L:         \
-    return launch_inv_one<L>(g, acc, tail, out, half, w2i, s, nsplit);
-    CLFA_B(1) CLFA_B(2) CLFA_B(3) CLFA_B(4) CLFA_B(5) CLFA_B(6) CLFA_B(7) CLFA_B(8) CLFA_B(9) CLFA_B(10)
-    CLFA_B(11) CLFA_B(12) CLFA_B(13)
-#undef CLFA_B
-    default:
-      return hipErrorInvalidValue;
-  }
+  return dispatch_logb<1, 13>(g.logb, [&](auto L) {
+    return launch_inv_one<decltype(L)::value>(g, acc, tail, out, half, w2i, s, nsplit);
+  });
 }
 
 // ---------------------------------------------------------------------------------
@@ -423,11 +379,7 @@ __global__ __launch_bounds__(256) void k_pconv_fused(const float *__restrict__ i
       const int j = i == 0 ? N / 2 : N - i;
       const cpx ci = s_x[lds_pad(i)], cj = s_x[lds_pad(j)];
       cpx oi, oj;
-      r2c_pair(ci, cj, w2f_g[i], oi, oj);
-      if (i == 0) {
-        oi = mk((ci.x + ci.y) * .5f, (ci.x - ci.y) * .5f);
-        oj = cj;
-      }
+      r2c_pack_pair(ci, cj, w2f_g[i], i == 0, oi, oj);
       x[i] = oi;
       x[j] = oj;
     }
@@ -452,8 +404,8 @@ __global__ __launch_bounds__(256) void k_pconv_fused(const float *__restrict__ i
         const int fq = wp + q < nparts ? wp + q : wp + q - nparts;
 #pragma unroll
         for (int k = 0; k < IPT; k++) {
-          pa[q][k] = ld_stream(mac_a + (long)fq * HB + tid + 256 * k);
-          pb[q][k] = ld_stream(mac_b + (long)q * HB + tid + 256 * k);
+          pa[q][k] = ld_nt(mac_a + (long)fq * HB + tid + 256 * k);
+          pb[q][k] = ld_nt(mac_b + (long)q * HB + tid + 256 * k);
         }
       }
     }
@@ -489,8 +441,8 @@ __global__ __launch_bounds__(256) void k_pconv_fused(const float *__restrict__ i
       cpx2 av[IPT], bv[IPT];
 #pragma unroll
       for (int k = 0; k < IPT; k++) {
-        av[k] = ld_stream(a + (long)fr * HB + tid + 256 * k);
-        bv[k] = ld_stream(b + (long)p * HB + tid + 256 * k);
+        av[k] = ld_nt(a + (long)fr * HB + tid + 256 * k);
+        bv[k] = ld_nt(b + (long)p * HB + tid + 256 * k);
       }
       mac(av, bv);
       fr = fr + 1 < nparts ? fr + 1 : 0;
@@ -596,13 +548,9 @@ static hipError_t launch_fused_one(const PconvGeom &g, const float *in1, const f
 hipError_t launch_pconv_fused(const PconvGeom &g, const float *in1, const float *in2, cpx *ringA, cpx *ringB,
                               float *tail, float *out, int frame1, int frame2, int wp, const cpx *half,
                               const cpx *w2f, const cpx *w2i, hipStream_t s, bool deep) {
-  switch (g.logb) {
-    case 9: return launch_fused_one<9>(g, in1, in2, ringA, ringB, tail, out, frame1, frame2, wp, half, w2f, w2i, s, deep);
-    case 10: return launch_fused_one<10>(g, in1, in2, ringA, ringB, tail, out, frame1, frame2, wp, half, w2f, w2i, s, deep);
-    case 11: return launch_fused_one<11>(g, in1, in2, ringA, ringB, tail, out, frame1, frame2, wp, half, w2f, w2i, s, deep);
-    case 12: return launch_fused_one<12>(g, in1, in2, ringA, ringB, tail, out, frame1, frame2, wp, half, w2f, w2i, s, deep);
-    default: return hipErrorInvalidValue;
-  }
+  return dispatch_logb<9, 12>(g.logb, [&](auto L) {
+    return launch_fused_one<decltype(L)::value>(g, in1, in2, ringA, ringB, tail, out, frame1, frame2, wp, half, w2f, w2i, s, deep);
+  });
 }
 
 // ---------------------------------------------------------------------------------
@@ -702,8 +650,8 @@ __global__ __launch_bounds__(LdsGeom<LOGB>::WG) void k_pconv_coop(const float *_
     const int pc = ok ? pp : p_end - 1;
     int fr = wp + pc;
     fr = fr < nparts ? fr : fr - nparts;
-    av0[u] = ld_stream(ra + (long)fr * HB);
-    bv0[u] = ld_stream(rb + (long)pc * HB);
+    av0[u] = ld_nt(ra + (long)fr * HB);
+    bv0[u] = ld_nt(rb + (long)pc * HB);
     live0[u] = ok && pc != p1 && !(TV && pc == frame2);
   }
   const cpx2 b_p1 = rb[(long)p1 * HB];                 // ring operand of the new A frame's term
@@ -792,11 +740,7 @@ __global__ __launch_bounds__(LdsGeom<LOGB>::WG) void k_pconv_coop(const float *_
       const int j = i == 0 ? N / 2 : N - i;
       const cpx ci = sx[lds_pad(i)], cj = sx[lds_pad(j)];
       cpx oi, oj;
-      r2c_pair(ci, cj, w2f_r[q], oi, oj);
-      if (i == 0) {
-        oi = mk((ci.x + ci.y) * .5f, (ci.x - ci.y) * .5f);
-        oj = cj;
-      }
+      r2c_pack_pair(ci, cj, w2f_r[q], i == 0, oi, oj);
       if (i >= b0 && i < b0 + bw) sf[i - b0] = oi;
       if (j >= b0 && j < b0 + bw) sf[j - b0] = oj;
       if (blockIdx.x == 0) {   // filed in the ring for the blocks to come; nobody reads it from there in this launch
@@ -846,8 +790,8 @@ __global__ __launch_bounds__(LdsGeom<LOGB>::WG) void k_pconv_coop(const float *_
         const int pp = p + u * nr;
         int fr = wp + pp;
         fr = fr < nparts ? fr : fr - nparts;
-        av[u] = ld_stream(a + (long)fr * HB);
-        bv[u] = ld_stream(b + (long)pp * HB);
+        av[u] = ld_nt(a + (long)fr * HB);
+        bv[u] = ld_nt(b + (long)pp * HB);
         live[u] = pp != p1 && !(TV && pp == frame2);
       }
 #pragma unroll
@@ -856,7 +800,7 @@ __global__ __launch_bounds__(LdsGeom<LOGB>::WG) void k_pconv_coop(const float *_
     for (; p < p_end; p += nr) {
       int fr = wp + p;
       fr = fr < nparts ? fr : fr - nparts;
-      term(ld_stream(a + (long)fr * HB), ld_stream(b + (long)p * HB), p != p1 && !(TV && p == frame2));
+      term(ld_nt(a + (long)fr * HB), ld_nt(b + (long)p * HB), p != p1 && !(TV && p == frame2));
     }
     // the terms of the new frames, by the row that owns their partition
     const cpx2 *fa = reinterpret_cast<const cpx2 *>(s_fa) + li;
@@ -1028,15 +972,10 @@ static hipError_t launch_coop_one(const PconvGeom &g, PconvCoop c, const float *
 hipError_t launch_pconv_coop(const PconvGeom &g, PconvCoop c, const float *in1, const float *in2, cpx *ringA, cpx *ringB,
                              float *tail, float *out, int frame1, int frame2, int wp, const cpx *half, const cpx *w2f,
                              const cpx *w2i, cpx *xacc, unsigned *counters, int num_cus, hipStream_t s) {
-  switch (g.logb) {
-#define CLFA_B(L) \
-  case L:         \
-    return launch_coop_one<L>(g, c, in1, in2, ringA, ringB, tail, out, frame1, frame2, wp, half, w2f, w2i, xacc, counters, num_cus, s);
-    CLFA_B(5) CLFA_B(6) CLFA_B(7) CLFA_B(8) CLFA_B(9) CLFA_B(10) CLFA_B(11) CLFA_B(12)
-#undef CLFA_B
-    default:
-      return hipErrorInvalidValue;
-  }
+  return dispatch_logb<5, 12>(g.logb, [&](auto L) {
+    return launch_coop_one<decltype(L)::value>(g, c, in1, in2, ringA, ringB, tail, out, frame1, frame2, wp, half, w2f, w2i, xacc, counters,
+                                               num_cus, s);
+  });
 }
 
 // ---------------------------------------------------------------------------------

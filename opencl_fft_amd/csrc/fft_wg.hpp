@@ -1,5 +1,5 @@
-// fft_wg.hpp — workgroup-level pieces shared by fft_kernels.hip and conv_kernels.hip:
-// the LDS-exchanged pass chain, its geometry, and the reference's r2c/c2r pair maps.
+// fft_wg.hpp — workgroup-level pieces shared by the FFT, STFT and convolution kernels (fft_kernels.hip, stft_kernels.hip,
+// conv_kernels.hip, pconv_blocks.hip, pconv_matrix.hip): the LDS-exchanged pass chains and their geometry.
 #pragma once
 #include "internal.hpp"
 

@@ -14,15 +14,11 @@
 //   response of partition p for output j (time-varying): k_p = (w2 - p) mod nparts; k_p <= j: XB[k_p], else ring B[p]
 // Every output bin is one accumulator summed over p = 0, 1, ... nparts - 1 with the products of k_pconv_mac, whatever
 // the tile, the sub-batch or the split of the signal into calls: results are bit-identical across splits.
-#include "fft_wg.hpp"
+#include "pconv_device.hpp"
 
 namespace clfa {
 
 namespace {
-
-struct alignas(16) cpx2b {
-  cpx a, b;
-};
 
 __device__ __forceinline__ cpx ld_pair(const float *p, bool aligned) {
   if (aligned) return *reinterpret_cast<const cpx *>(p);
@@ -100,15 +96,6 @@ __global__ __launch_bounds__(LdsGeom<LOGB>::WG) void k_pconvb_fwd(const float *_
 // ---------------------------------------------------------------------------------
 // multiply-accumulate with reuse: one wave = (16-byte item slice, tile of KT outputs, channel)
 // ---------------------------------------------------------------------------------
-__device__ __forceinline__ cpx2b ld_nt(const cpx2b *p) {
-  typedef float v4f __attribute__((ext_vector_type(4)));
-  v4f r = __builtin_nontemporal_load(reinterpret_cast<const v4f *>(p));
-  cpx2b o;
-  o.a = mk(r.x, r.y);
-  o.b = mk(r.z, r.w);
-  return o;
-}
-
 template <int KT, bool TV>
 __global__ __launch_bounds__(64) void k_pconvb_mac(const cpx *__restrict__ ringA, const cpx *__restrict__ ringB,
                                                    const cpx *__restrict__ X, const cpx *__restrict__ XB, cpx *__restrict__ Y,
@@ -118,13 +105,13 @@ __global__ __launch_bounds__(64) void k_pconvb_mac(const cpx *__restrict__ ringA
   const int it = item < hb ? item : hb - 1;   // (clamped: straight-line loads; the store is guarded)
   const int ch = blockIdx.z;
   const int j0 = blockIdx.y * KT;
-  const cpx2b *ra = reinterpret_cast<const cpx2b *>(ringA + (long)ch * nparts * bins) + it;
-  const cpx2b *rb = reinterpret_cast<const cpx2b *>(ringB + (long)ch * nparts * bins) + it;
-  const cpx2b *xs = reinterpret_cast<const cpx2b *>(X + (long)ch * cap * bins) + it;
-  const cpx2b *xbs = reinterpret_cast<const cpx2b *>(XB + (long)ch * cap * bins) + it;
+  const cpx2 *ra = reinterpret_cast<const cpx2 *>(ringA + (long)ch * nparts * bins) + it;
+  const cpx2 *rb = reinterpret_cast<const cpx2 *>(ringB + (long)ch * nparts * bins) + it;
+  const cpx2 *xs = reinterpret_cast<const cpx2 *>(X + (long)ch * cap * bins) + it;
+  const cpx2 *xbs = reinterpret_cast<const cpx2 *>(XB + (long)ch * cap * bins) + it;
   // input frame m of the sub-batch: m >= 0 this call's spectrum X[m]; m < 0 the ring's frame (w + m) mod nparts.
   // m > K - 1 only feeds outputs past the sub-batch (never stored): clamped
-  auto frame = [&](int m) -> const cpx2b * {
+  auto frame = [&](int m) -> const cpx2 * {
     if (m >= 0) return xs + (long)(m < K ? m : K - 1) * hb;
     int f = w + m;
     f = f < 0 ? f + nparts : f;
@@ -132,20 +119,18 @@ __global__ __launch_bounds__(64) void k_pconvb_mac(const cpx *__restrict__ ringA
   };
   const bool dc = item == 0;   // packed DC / Nyquist bin: (re*re, im*im)
   cpx s0[KT], s1[KT];
-  cpx2b win[KT];
+  cpx2 win[KT];
 #pragma unroll
   for (int t = 0; t < KT; t++) {
     s0[t] = s1[t] = mk(0.f, 0.f);
     win[t] = ld_nt(frame(j0 + t - (nparts - 1)));
   }
-  auto mac = [&](int t, const cpx2b &a, const cpx2b &b) {
-    cpx pr = cmul_plain(a.a, b.a);
-    pr = mk(dc ? a.a.x * b.a.x : pr.x, dc ? a.a.y * b.a.y : pr.y);
-    s0[t] = cadd(s0[t], pr);
-    s1[t] = cadd(s1[t], cmul_plain(a.b, b.b));
+  // (the lambda stays: with mac_term called straight from the unrolled loop hipcc emits another code object)
+  auto mac = [&](int t, const cpx2 &a, const cpx2 &b) {
+    mac_term(s0[t], s1[t], a, b, dc);
   };
   // one partition: the response frame(s) of p, then the next input frame of the window
-  cpx2b bq = ld_nt(rb), bnq = bq, xq = win[0];
+  cpx2 bq = ld_nt(rb), bnq = bq, xq = win[0];
   int kq = 0;
   auto load = [&](int p) {
     bq = ld_nt(rb + (long)p * hb);
@@ -158,7 +143,7 @@ __global__ __launch_bounds__(64) void k_pconvb_mac(const cpx *__restrict__ ringA
   };
   load(0);
   for (int p = 0; p < nparts; p++) {
-    const cpx2b b = bq, bn = bnq, xn = xq;
+    const cpx2 b = bq, bn = bnq, xn = xq;
     const int k = kq;
     if (p + 1 < nparts) load(p + 1);   // next partition's loads are in flight under this one's arithmetic
 #pragma unroll
@@ -170,19 +155,17 @@ __global__ __launch_bounds__(64) void k_pconvb_mac(const cpx *__restrict__ ringA
         mac(t, win[t], b);
       }
     }
-#pragma unroll
-    for (int t = 0; t + 1 < KT; t++) win[t] = win[t + 1];
-    win[KT - 1] = xn;
+    window_shift(win, xn);
   }
   if (item < hb) {
 #pragma unroll
     for (int t = 0; t < KT; t++) {
       const int j = j0 + t;
       if (j < K) {
-        cpx2b o;
+        cpx2 o;
         o.a = s0[t];
         o.b = s1[t];
-        reinterpret_cast<cpx2b *>(Y + ((long)ch * cap + j) * bins)[item] = o;
+        reinterpret_cast<cpx2 *>(Y + ((long)ch * cap + j) * bins)[item] = o;
       }
     }
   }
@@ -230,18 +213,8 @@ __global__ __launch_bounds__(LdsGeom<LOGB>::WG) void k_pconvb_inv(const cpx *__r
       const cpx *y = Y + ((long)ch * cap + (j < 0 ? 0 : (j < K ? j : K - 1))) * N;
       __syncthreads();
       if (live) {
-        for (int i = t; i < N / 2; i += T) {
-          if (i == 0) {
-            cpx c0 = y[0];
-            xb[0] = mk(c0.x + c0.y, c0.x - c0.y);
-            xb[lds_pad(N / 2)] = y[N / 2];
-          } else {
-            cpx oi, oj;
-            c2r_pair(y[i], y[N - i], w2_g[i], oi, oj);
-            xb[lds_pad(i)] = oi;
-            xb[lds_pad(N - i)] = oj;
-          }
-        }
+        for (int i = t; i < N / 2; i += T)
+          c2r_unpack<N>(i, [&](int p) { return y[p]; }, [&](int k) { return w2_g[k]; }, [&](int p, cpx val) { xb[lds_pad(p)] = val; });
       }
       __syncthreads();
       cpx v[E];
@@ -279,29 +252,15 @@ __global__ __launch_bounds__(256) void k_pconvb_commit(cpx *__restrict__ ringA, 
                                                        const float *__restrict__ tail_new, int K, int cap, int w, int w2,
                                                        int bins, int nparts, int channels) {
   const int hb = bins >> 1;
-  if (blockIdx.y == 1) {
-    const long n = (long)channels * bins;
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) tail[i] = tail_new[i];
-    return;
-  }
+  if (blockIdx.y == 1) return commit_tail(tail, tail_new, (long)channels * bins);
   const bool b = blockIdx.y == 2;
-  const int m0 = b ? 0 : (K > nparts ? K - nparts : 0), cnt = K - m0;
-  const long n = (long)channels * cnt * hb;
-  const cpx2b *src = reinterpret_cast<const cpx2b *>(b ? XB : X);
-  cpx2b *dst = reinterpret_cast<cpx2b *>(b ? ringB : ringA);
-  for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-    const int item = (int)(i % hb);
-    const long rest = i / hb;
-    const int m = m0 + (int)(rest % cnt), ch = (int)(rest / cnt);
-    int fr;
+  commit_spectra(b ? ringB : ringA, b ? XB : X, b ? 0 : commit_first(K, nparts), K, cap, hb, nparts, channels, [&](int m) {
     if (b) {
-      fr = w2 - m;
-      fr = fr < 0 ? fr + nparts : fr;
-    } else {
-      fr = (w + m) % nparts;
+      const int fr = w2 - m;
+      return fr < 0 ? fr + nparts : fr;
     }
-    dst[((long)ch * nparts + fr) * hb + item] = src[((long)ch * cap + m) * hb + item];
-  }
+    return ring_a_frame(w, m, nparts);
+  });
 }
 
 // ---------------------------------------------------------------------------------
@@ -319,7 +278,7 @@ static hipError_t fwd_one(const float *in, const float *in_b, long in_stride, cp
                           int aligned, const cpx *half, const cpx *w2f, hipStream_t s) {
   using G = LdsGeom<LOGB>;
   long groups = ((long)channels * K + G::FPW - 1) / G::FPW;
-  int grid = groups < 8192 ? (int)groups : 8192;
+  const int grid = grid_clamp(groups, 8192);
   hipLaunchKernelGGL((k_pconvb_fwd<LOGB>), dim3(grid, in_b ? 2 : 1), dim3(G::WG), 0, s, in, in_b, in_stride, X, XB, K, cap,
                      channels, aligned, half, w2f);
   return hipGetLastError();
@@ -331,7 +290,7 @@ static hipError_t inv_one(const cpx *Y, const float *tail, float *tail_out, floa
   using G = LdsGeom<LOGB>;
   const int nruns = (K + R - 1) / R;
   long groups = ((long)channels * nruns + G::FPW - 1) / G::FPW;
-  int grid = groups < 8192 ? (int)groups : 8192;
+  const int grid = grid_clamp(groups, 8192);
   hipLaunchKernelGGL((k_pconvb_inv<LOGB>), dim3(grid), dim3(G::WG), 0, s, Y, tail, tail_out, out, out_stride, K, cap, R,
                      channels, aligned, half, w2i);
   return hipGetLastError();
@@ -368,7 +327,7 @@ static hipError_t launch_blocks_one(const PconvBlocks &a, hipStream_t s) {
   }
   {
     long n = (long)g.channels * g.bins;
-    int grid = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+    const int grid = grid_clamp((n + 255) / 256, 4096);
     hipLaunchKernelGGL(k_pconvb_commit, dim3(grid, a.in2 ? 3 : 2), dim3(256), 0, s, a.ringA, a.ringB, a.tail, (const cpx *)a.X,
                        (const cpx *)a.XB, (const float *)a.tail_ws, a.K, a.cap, a.w, a.w2, g.bins, g.nparts, g.channels);
   }
@@ -378,42 +337,23 @@ static hipError_t launch_blocks_one(const PconvBlocks &a, hipStream_t s) {
 hipError_t launch_pconv_blocks(const PconvBlocks &a, hipStream_t s) {
   if (a.K < 1 || a.K > a.cap || (a.in2 && a.K > a.g.nparts) || (a.kt != 4 && a.kt != 16) || a.run < 1)
     return hipErrorInvalidValue;
-  switch (a.g.logb) {
-#define CLFA_B(L) \
-  case L:         \
-    return launch_blocks_one<L>(a, s);
-    CLFA_B(5) CLFA_B(6) CLFA_B(7) CLFA_B(8) CLFA_B(9) CLFA_B(10) CLFA_B(11) CLFA_B(12)
-#undef CLFA_B
-    default:
-      return hipErrorInvalidValue;
-  }
+  return dispatch_logb<kPconvBlocksMinLog, kPconvBlocksMaxLog>(a.g.logb,
+                                                               [&](auto L) { return launch_blocks_one<decltype(L)::value>(a, s); });
 }
 
 // the forward and inverse launches on their own, for the convolution matrix (pconv_matrix.hip)
 hipError_t launch_pconvb_forward(int logb, const float *in, long in_stride, cpx *X, int K, int cap, int channels, int aligned,
                                  const cpx *half, const cpx *w2f, hipStream_t s) {
-  switch (logb) {
-#define CLFA_B(L) \
-  case L:         \
-    return fwd_one<L>(in, nullptr, in_stride, X, nullptr, K, cap, channels, aligned, half, w2f, s);
-    CLFA_B(5) CLFA_B(6) CLFA_B(7) CLFA_B(8) CLFA_B(9) CLFA_B(10) CLFA_B(11) CLFA_B(12)
-#undef CLFA_B
-    default:
-      return hipErrorInvalidValue;
-  }
+  return dispatch_logb<kPconvBlocksMinLog, kPconvBlocksMaxLog>(logb, [&](auto L) {
+    return fwd_one<decltype(L)::value>(in, nullptr, in_stride, X, nullptr, K, cap, channels, aligned, half, w2f, s);
+  });
 }
 
 hipError_t launch_pconvb_inverse(int logb, const cpx *Y, const float *tail, float *tail_out, float *out, long out_stride, int K,
                                  int cap, int R, int channels, int aligned, const cpx *half, const cpx *w2i, hipStream_t s) {
-  switch (logb) {
-#define CLFA_B(L) \
-  case L:         \
-    return inv_one<L>(Y, tail, tail_out, out, out_stride, K, cap, R, channels, aligned, half, w2i, s);
-    CLFA_B(5) CLFA_B(6) CLFA_B(7) CLFA_B(8) CLFA_B(9) CLFA_B(10) CLFA_B(11) CLFA_B(12)
-#undef CLFA_B
-    default:
-      return hipErrorInvalidValue;
-  }
+  return dispatch_logb<kPconvBlocksMinLog, kPconvBlocksMaxLog>(logb, [&](auto L) {
+    return inv_one<decltype(L)::value>(Y, tail, tail_out, out, out_stride, K, cap, R, channels, aligned, half, w2i, s);
+  });
 }
 
 }  // namespace clfa

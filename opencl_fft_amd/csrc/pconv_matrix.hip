@@ -14,24 +14,11 @@
 // Every output bin of segment s is one accumulator over its r in ascending order; the segments are fixed per object
 // (pconv_matrix_plan), and so is the order in which they are added: results do not depend on K, the sub-batch, the split
 // of a signal into calls, the stream or graph replay.
-#include "fft_wg.hpp"
+#include "pconv_device.hpp"
 
 namespace clfa {
 
 namespace {
-
-struct alignas(16) cpx2m {
-  cpx a, b;
-};
-
-__device__ __forceinline__ cpx2m ld_nt(const cpx2m *p) {
-  typedef float v4f __attribute__((ext_vector_type(4)));
-  v4f r = __builtin_nontemporal_load(reinterpret_cast<const v4f *>(p));
-  cpx2m o;
-  o.a = mk(r.x, r.y);
-  o.b = mk(r.z, r.w);
-  return o;
-}
 
 __device__ __forceinline__ long seg_start(long total, int s, int segs) { return total * s / segs; }
 
@@ -62,54 +49,50 @@ __global__ __launch_bounds__(64) void k_pconvm_mac(const cpx *__restrict__ ringA
   cpx s0[KT], s1[KT];
 #pragma unroll
   for (int t = 0; t < KT; t++) s0[t] = s1[t] = mk(0.f, 0.f);
-  auto mac = [&](int t, const cpx2m &x, const cpx2m &h) {
-    cpx pr = cmul_plain(x.a, h.a);
-    pr = mk(dc ? x.a.x * h.a.x : pr.x, dc ? x.a.y * h.a.y : pr.y);
-    s0[t] = cadd(s0[t], pr);
-    s1[t] = cadd(s1[t], cmul_plain(x.b, h.b));
+  // (the lambda stays: with mac_term called straight from the unrolled loop hipcc emits another code object)
+  auto mac = [&](int t, const cpx2 &x, const cpx2 &h) {
+    mac_term(s0[t], s1[t], x, h, dc);
   };
   for (int i = (int)(r0 / nparts); (long)i * nparts < r1; i++) {
     const long ib = (long)i * nparts;
     const int pa = r0 > ib ? (int)(r0 - ib) : 0;
     const int pb = r1 - ib < nparts ? (int)(r1 - ib) : nparts;
-    const cpx2m *ra = reinterpret_cast<const cpx2m *>(ringA + ib * bins) + it;
-    const cpx2m *xs = reinterpret_cast<const cpx2m *>(X + (long)i * cap * bins) + it;
+    const cpx2 *ra = reinterpret_cast<const cpx2 *>(ringA + ib * bins) + it;
+    const cpx2 *xs = reinterpret_cast<const cpx2 *>(X + (long)i * cap * bins) + it;
     // partition q of response (o, i); step p of the walk uses q = nparts - 1 - p
-    const cpx2m *hp = reinterpret_cast<const cpx2m *>(H + ((long)o * inputs + i) * nparts * bins) + it;
+    const cpx2 *hp = reinterpret_cast<const cpx2 *>(H + ((long)o * inputs + i) * nparts * bins) + it;
     // input frame m of the sub-batch: m >= 0 this call's spectrum X_i[m]; m < 0 ring A_i frame (w + m) mod nparts.
     // m > K - 1 only feeds outputs past the sub-batch (never stored): clamped
-    auto frame = [&](int m) -> const cpx2m * {
+    auto frame = [&](int m) -> const cpx2 * {
       if (m >= 0) return xs + (long)(m < K ? m : K - 1) * hb;
       int f = w + m;
       f = f < 0 ? f + nparts : f;
       return ra + (long)f * hb;
     };
-    cpx2m win[KT];
+    cpx2 win[KT];
 #pragma unroll
     for (int t = 0; t < KT; t++) win[t] = ld_nt(frame(j0 + t - (nparts - 1) + pa));
-    cpx2m hq, xq;
+    cpx2 hq, xq;
     auto load = [&](int p) {
       hq = ld_nt(hp + (long)(nparts - 1 - p) * hb);
       xq = ld_nt(frame(j0 + KT - (nparts - 1) + p));   // enters the window after partition p
     };
     load(pa);
     for (int p = pa; p < pb; p++) {
-      const cpx2m h = hq, xn = xq;
+      const cpx2 h = hq, xn = xq;
       if (p + 1 < pb) load(p + 1);   // next partition's loads are in flight under this one's arithmetic
 #pragma unroll
       for (int t = 0; t < KT; t++) mac(t, win[t], h);
-#pragma unroll
-      for (int t = 0; t + 1 < KT; t++) win[t] = win[t + 1];
-      win[KT - 1] = xn;
+      window_shift(win, xn);
     }
   }
   if (item < hb) {
-    cpx2m *dst = reinterpret_cast<cpx2m *>(s == 0 ? Y + (long)o * cap * bins : P + ((long)(s - 1) * outputs + o) * cap * bins);
+    cpx2 *dst = reinterpret_cast<cpx2 *>(s == 0 ? Y + (long)o * cap * bins : P + ((long)(s - 1) * outputs + o) * cap * bins);
 #pragma unroll
     for (int t = 0; t < KT; t++) {
       const int j = j0 + t;
       if (j < K) {
-        cpx2m v;
+        cpx2 v;
         v.a = s0[t];
         v.b = s1[t];
         dst[(long)j * hb + item] = v;
@@ -125,17 +108,17 @@ __global__ __launch_bounds__(256) void k_pconvm_reduce(cpx *__restrict__ Y, cons
                                                        int outputs, int segs) {
   const int hb = bins >> 1;
   const long n = (long)outputs * K * hb;
-  const long pstride = (long)outputs * cap * hb;   // one segment's partials, in cpx2m
-  cpx2m *y = reinterpret_cast<cpx2m *>(Y);
-  const cpx2m *q = reinterpret_cast<const cpx2m *>(P);
+  const long pstride = (long)outputs * cap * hb;   // one segment's partials, in cpx2
+  cpx2 *y = reinterpret_cast<cpx2 *>(Y);
+  const cpx2 *q = reinterpret_cast<const cpx2 *>(P);
   for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
     const int item = (int)(i % hb);
     const long rest = i / hb;
     const int j = (int)(rest % K), o = (int)(rest / K);
     const long at = ((long)o * cap + j) * hb + item;
-    cpx2m v = y[at];
+    cpx2 v = y[at];
     for (int s = 1; s < segs; s++) {
-      const cpx2m u = q[(long)(s - 1) * pstride + at];
+      const cpx2 u = q[(long)(s - 1) * pstride + at];
       v.a = cadd(v.a, u.a);
       v.b = cadd(v.b, u.b);
     }
@@ -150,22 +133,9 @@ __global__ __launch_bounds__(256) void k_pconvm_commit(cpx *__restrict__ ringA, 
                                                        const float *__restrict__ tail_new, int K, int cap, int w, int bins,
                                                        int nparts, int inputs, int outputs) {
   const int hb = bins >> 1;
-  if (blockIdx.y == 1) {
-    const long n = (long)outputs * bins;
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) tail[i] = tail_new[i];
-    return;
-  }
-  const int m0 = K > nparts ? K - nparts : 0, cnt = K - m0;
-  const long n = (long)inputs * cnt * hb;
-  const cpx2m *src = reinterpret_cast<const cpx2m *>(X);
-  cpx2m *dst = reinterpret_cast<cpx2m *>(ringA);
-  for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-    const int item = (int)(i % hb);
-    const long rest = i / hb;
-    const int m = m0 + (int)(rest % cnt), ch = (int)(rest / cnt);
-    const int fr = (w + m) % nparts;
-    dst[((long)ch * nparts + fr) * hb + item] = src[((long)ch * cap + m) * hb + item];
-  }
+  if (blockIdx.y == 1) return commit_tail(tail, tail_new, (long)outputs * bins);
+  commit_spectra(ringA, X, commit_first(K, nparts), K, cap, hb, nparts, inputs,
+                 [&](int m) { return ring_a_frame(w, m, nparts); });
 }
 
 // ---------------------------------------------------------------------------------
@@ -212,7 +182,7 @@ hipError_t launch_pconv_matrix(const PconvMatrixArgs &a, hipStream_t s) {
   }
   if (pl.segs > 1) {
     const long n = (long)a.outputs * a.K * (a.bins / 2);
-    const int grid = (int)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
+    const int grid = grid_clamp((n + 255) / 256, 8192);
     hipLaunchKernelGGL(k_pconvm_reduce, dim3(grid), dim3(256), 0, s, a.Y, (const cpx *)a.P, a.K, a.cap, a.bins, a.outputs, pl.segs);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
@@ -221,7 +191,7 @@ hipError_t launch_pconv_matrix(const PconvMatrixArgs &a, hipStream_t s) {
   if (e != hipSuccess) return e;
   {
     const long n = (long)(a.inputs > a.outputs ? a.inputs : a.outputs) * a.bins;
-    const int grid = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+    const int grid = grid_clamp((n + 255) / 256, 4096);
     hipLaunchKernelGGL(k_pconvm_commit, dim3(grid, 2), dim3(256), 0, s, a.ringA, a.tail, (const cpx *)a.X, (const float *)a.tail_ws,
                        a.K, a.cap, a.w, a.bins, a.nparts, a.inputs, a.outputs);
   }

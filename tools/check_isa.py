@@ -9,7 +9,9 @@ The kernel (opencl_fft_amd/csrc/fft_resident.hip) does two things hipcc cannot c
     compiler-generated instruction may name those registers (with compiler-allocated destinations
     hipcc was seen copying them ahead of the kernel's own s_waitcnt, i.e. before the data had landed).
 
-usage: check_isa.py file.s   (hipcc -save-temps of fft_resident.hip)
+usage: check_isa.py file.s                (hipcc -save-temps of fft_resident.hip)
+       check_isa.py --handover file.s     (conv_kernels.hip: the inter-workgroup hand-overs)
+       check_isa.py --same OLD.s NEW.s    (a refactor's proof: every kernel compiles to the instructions it had)
 """
 import re
 import sys
@@ -165,7 +167,64 @@ def check_handover(path):
     return problems
 
 
+def kernels_of(path):
+    """kernel symbol -> (basic blocks, .amdhsa_ descriptor lines) of a hipcc -save-temps .s file: comments, .loc / .file /
+    .ident / .section directives dropped, local labels renumbered in order of appearance"""
+    s = open(path).read()
+    out = {}
+    for m in re.finditer(r"^(_ZN4clfa\w+):.*?\n(.*?)^\.Lfunc_end\d+:", s, re.S | re.M):
+        code, desc, labels, in_desc = [[]], [], {}, False
+        for ln in m.group(2).split("\n"):
+            if "; %bb." in ln:
+                code.append([])   # a block the assembly falls into has no label of its own
+            t = ln.split(";")[0].strip()
+            if t.startswith(".amdhsa_kernel") or t.startswith(".end_amdhsa_kernel"):
+                in_desc = not in_desc
+            elif in_desc:
+                desc.append(" ".join(t.split()))
+            elif t and not t.startswith((".loc", ".file", ".ident", ".section", ".p2align", ".cfi")):
+                t = re.sub(r"\.L\w+", lambda l: labels.setdefault(l.group(0), ".L%d" % len(labels)), " ".join(t.split()))
+                if t.endswith(":"):
+                    code.append([])
+                code[-1].append(t)
+        out[m.group(1)] = ([b for b in code if b], desc)
+    return out
+
+
+def same(old, new, out=sys.stdout):
+    """one line per kernel: name, instructions, same / reordered / DIFFERENT.  `reordered`: the descriptor (register
+    counts, LDS, scratch) is equal and every basic block holds the same instructions in another order; its diff is
+    printed and has to be READ: the multiset rule also passes a swap of two dependent instructions, and only a person
+    can tell that the moved ones are independent.  Returns the number of kernels that are DIFFERENT, missing or new
+    (a `reordered` kernel does not count: the exit status alone is no proof of identity)."""
+    import difflib
+    a, b = kernels_of(old), kernels_of(new)
+    bad = 0
+    for name in sorted(set(a) | set(b)):
+        if name not in a or name not in b:
+            print("%s  -  %s" % (name, "MISSING in new" if name in a else "NEW kernel"), file=out)
+            bad += 1
+            continue
+        (ca, da), (cb, db) = a[name], b[name]
+        n = sum(not t.startswith(".") for blk in cb for t in blk)   # labels and directives are compared, not counted
+        if (ca, da) == (cb, db):
+            verdict = "same"
+        elif da == db and len(ca) == len(cb) and all(sorted(x) == sorted(y) for x, y in zip(ca, cb)):
+            verdict = "reordered"
+        else:
+            verdict = "DIFFERENT"
+            bad += 1
+        print("%s  %d  %s" % (name, n, verdict), file=out)
+        if verdict != "same":
+            flat = lambda c, d: [t for blk in c for t in blk] + d
+            for ln in list(difflib.unified_diff(flat(ca, da), flat(cb, db), "old", "new", n=1, lineterm=""))[:80]:
+                print("    " + ln, file=out)
+    return bad
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 3 and sys.argv[1] == "--same":
+        sys.exit(1 if same(sys.argv[2], sys.argv[3]) else 0)
     if len(sys.argv) > 2 and sys.argv[1] == "--handover":
         p = check_handover(sys.argv[2])
         for x in p:
