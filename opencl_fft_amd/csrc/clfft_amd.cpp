@@ -271,7 +271,7 @@ static int fft_setup(clfa_fft *p, int device, int n, bool real, int size, bool f
     std::vector<cpx> all, part;
     fill_twiddle(part, n1 / 2, n1, 1, -1.f);
     all.insert(all.end(), part.begin(), part.begin() + n1 / 2);
-    fill_twiddle(part, 128, n, 1, -1.f);              // W_n^e, e = e0 + 128 e1 + 16384 e2 (big_tw(), fft_kernels.hip)
+    fill_twiddle(part, 128, n, 1, -1.f);              // W_n^e, e = e0 + 128 e1 + 16384 e2 (big_tw(), fft_big.inc)
     all.insert(all.end(), part.begin(), part.begin() + 128);
     fill_twiddle(part, 128, n, 128, -1.f);
     all.insert(all.end(), part.begin(), part.begin() + 128);
@@ -407,7 +407,7 @@ static int fft_exec(clfa_fft *p, cpx *d, long off, long batch, hipStream_t s) {
       HIP_TRY(launch_c2r_unpack(d, p->tabs.w2, n, batch, s, off));   // -> the destination
       src = o;
     }
-    if (blue_lds_ok(m)) {   // one launch, one read and one write of the data (fft_kernels.hip, k_blue_lds)
+    if (blue_lds_ok(m)) {   // one launch, one read and one write of the data (fft_aux.inc, k_blue_lds)
       HIP_TRY(launch_blue_lds(m, src, o, w, bt, p->blue_f->tabs.half, n, (scale ? 1.0f / (float)n : 1.0f) / (float)m, batch, p->di, s));
       if (p->real && p->fwd) HIP_TRY(launch_r2c_pack(o, p->tabs.w2, n, batch, s));
       return CLFA_SUCCESS;

@@ -584,15 +584,12 @@ __device__ __forceinline__ void handover_acquire(int acquire) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
 }
-// The arriving lane's add carries the C++ model's release as well (CLFA_HANDOVER_RELEASE): the hand-written form above
+// The arriving lane's add carries the C++ model's release as well: the hand-written form above
 // orders the slice stores in hardware, but nothing in it tells hipcc that they must stay above the add — with the
 // release a future compiler cannot sink a slice store below the counter.  On gfx950 it costs a buffer_wbl2 sc1 and a wait
 // in ONE lane after the barrier (profiles/handover_release_r05.txt).
-#ifndef CLFA_HANDOVER_RELEASE
-#define CLFA_HANDOVER_RELEASE 1
-#endif
 __device__ __forceinline__ unsigned handover_arrive(unsigned *counter) {
-  return __hip_atomic_fetch_add(counter, 1u, CLFA_HANDOVER_RELEASE ? __ATOMIC_RELEASE : __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
 }
 __device__ __forceinline__ void st_agent(cpx *p, cpx v) {
   __hip_atomic_store(reinterpret_cast<unsigned long long *>(p), __builtin_bit_cast(unsigned long long, v), __ATOMIC_RELAXED,

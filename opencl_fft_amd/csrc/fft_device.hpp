@@ -35,11 +35,8 @@ namespace clfa {
 // x * (G / 8) + c), so that the workgroups behind one L2 stream through one compact address range.  Same windows,
 // same step, any batch; measured on the resident n = 65536 kernel: 0.871 -> 0.831 ms per 4096 transforms
 // (profiles/r04_assignment.txt; tools/res16_probe.hip PROBE_PERM sweeps the other assignments).
-#ifndef CLFA_XCD_MAP
-#define CLFA_XCD_MAP 1
-#endif
 CLFA_HD long xcd_first(unsigned i, unsigned grid) {
-  if (!CLFA_XCD_MAP || (grid & 7)) return i;
+  if (grid & 7) return i;
   return (long)(i & 7) * (grid >> 3) + (i >> 3);
 }
 
@@ -416,10 +413,7 @@ struct LaneTab14 {
   const cpx *s256;    // LDS: [256 k] = W_4096^(2^k (tid & 255)), k = 0..3
   cpx w1, w2, w3;     // W_16384^(tid), ^(2 tid), ^(3 tid) (forward sign)
 };
-#ifndef CLFA_ROW16_STRIDE
-#define CLFA_ROW16_STRIDE 18
-#endif
-constexpr int kRow16StrideDev = CLFA_ROW16_STRIDE;
+constexpr int kRow16StrideDev = 18;   // (internal.hpp, kRow16Stride, has the reason)
 // Half table plus the 16 x 16 table W_256^(j t) for the pass that starts at 16 points: that pass's twiddles are
 // W_n^(j t n / 256) = W_256^(j t) whatever n is, j = tid & 15 — read from the half table they sit t n / 128 dwords apart
 // between neighbouring lanes (n = 4096: 32 t, two bank groups for sixteen addresses, an 8-way conflict on every read);

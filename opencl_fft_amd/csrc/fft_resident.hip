@@ -42,7 +42,7 @@
 //
 // Global accesses are buffer_load/store_dwordx2 ... offen nt with the row offsets e * 32 KiB in
 // SGPRs: one instruction per access, no address arithmetic.  Both LDS exchanges write 8 x b128 and
-// read 16 x SINGLE b64 (CLFA_DS_SINGLE below: paired into ds_read2_b64, as hipcc would, every read is a 2-way bank
+// read 16 x SINGLE b64 (CLFA_RES16_TARGET below: paired into ds_read2_b64, as hipcc would, every read is a 2-way bank
 // conflict), conflict-free under MI355X_MICROARCH.md's lane-group rules (layouts below; rocprofv3 round 5:
 // SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE 0.29 -> 0.05, what is left is the spill deposit).  The four-step twiddles W_N^(n2 (t + 16 e)) =
 // b * s^e come from one two-level lookup (b), four exact table values s, s^2, s^4, s^8 and a
@@ -356,16 +356,13 @@ constexpr HookMap kMapColA{{0, -1, 1, -1, 2, -1, 3, -1}};      // column block, 
 constexpr HookMap kMapColB{{8, -1, 9, -1, 10, -1, 11, -1}};    // ... second pass: hooks 8..11 (4..7: twiddles, 12..15: four-step)
 constexpr HookMap kMapRowC{{0, 1, 2, -1, 3, 4, 5, -1}};        // row block, first pass: hooks 0..5
 constexpr HookMap kMapRowD{{10, 11, 12, -1, 13, 14, 15, -1}};  // ... second pass: hooks 10..15 (6..9: twiddles)
-#ifndef CLFA_RES16_PIN_HOOKS
-#define CLFA_RES16_PIN_HOOKS 1
-#endif
 // a hook stays where it is written: without the fences hipcc lets the arithmetic drift around the asm
 // statements and the loads end up in clusters of four
 template <int G, class H> __device__ __forceinline__ void hook_at(const H &hook) {
   if constexpr (G >= 0 && !std::is_same<H, HookNone>::value) {
-    if (CLFA_RES16_PIN_HOOKS) __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_sched_barrier(0);
     hook(ic<G>());
-    if (CLFA_RES16_PIN_HOOKS) __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_sched_barrier(0);
   }
 }
 // dft16 of fft_device.hpp with eight hook points
@@ -462,14 +459,6 @@ __device__ __forceinline__ void dft16_hp_land(cpx (&v)[16], const H &hook) {
 #define CLFA_DFT16_HT(FWD, v, hook, M, tail) \
   dft16_hp<FWD, decltype(hook), M.p[0], M.p[1], M.p[2], M.p[3], M.p[4], M.p[5], M.p[6], M.p[7], decltype(tail)>(v, hook, tail)
 
-// build switches of the second passes (A/B; the library's choice is the default)
-#ifndef CLFA_TW_AHEAD
-#define CLFA_TW_AHEAD 1     // the second pass's twiddle rows are read one group (two b128) ahead of their use: the hook
-#endif                      // points are scheduling fences, and a read issued right before its use costs one wave per
-                            // SIMD the whole LDS latency, three times per block
-#ifndef CLFA_FS_AHEAD
-#define CLFA_FS_AHEAD 1     // the four-step twiddle lookups are issued before the second pass's last butterflies
-#endif
 struct ResLane {
   int c, t;          // lane = c + 16 t
   int voff;          // byte offset of the lane inside a column / row block of global memory
@@ -483,6 +472,9 @@ struct ResLane {
 };
 
 // second pass of a block: inputs times W_256^(t j) (row t of the table); hooks H0 .. H0 + 3 after the four groups
+// AHEAD: the twiddle rows are read one group (two b128) ahead of their use: the hook points are scheduling fences, and a
+// read issued right before its use costs one wave per SIMD the whole LDS latency, three times per block
+// (profiles/ab_res16_lds_r05.txt)
 template <bool FWD, int H0, bool AHEAD, class H> __device__ __forceinline__ void res_tw_rows(cpx (&v)[16], const ResLane &L, const H &hook) {
   const f4 *pt = reinterpret_cast<const f4 *>(L.tw_row);
   if constexpr (AHEAD) {
@@ -536,7 +528,7 @@ __device__ __forceinline__ void res_col_block(cpx (&v)[16], const ResLane &L, in
   }
   if constexpr (PROBE & kProbeNoMath) return;
   // second pass: inputs times W_256^(t j) (row t of the table), then the butterflies
-  res_tw_rows<FWD, 4, CLFA_TW_AHEAD>(v, L, hook);
+  res_tw_rows<FWD, 4, true>(v, L, hook);
   // four-step twiddles W_N^(n2 (t + 16 e)) = b * s^e,  b = W_N^(n2 t),  s = W_4096^n2
   const int n2 = cb * 16 + L.c;
   const int m = n2 * L.t;   // < 4096
@@ -546,17 +538,13 @@ __device__ __forceinline__ void res_col_block(cpx (&v)[16], const ResLane &L, in
     blo = s_tab[kTabLo + (m & 255)], bhi = s_tab[kTabHi + (m >> 8)];
     s1 = ps[0], s2 = ps[256], s4 = ps[512], s8 = ps[768];
   };
-  if constexpr (CLFA_FS_AHEAD) {
-    // the six reads go out ahead of the pass's last two butterflies (a fence keeps them there)
-    auto tail = [&]() {
-      lookups();
-      __builtin_amdgcn_sched_barrier(0);
-    };
-    CLFA_DFT16_HT(FWD, v, hook, kMapColB, tail);
-  } else {
-    CLFA_DFT16_H(FWD, v, hook, kMapColB);
+  // the six reads go out ahead of the pass's last two butterflies (a fence keeps them there; -0.25 %,
+  // profiles/ab_res16_lds_r05.txt)
+  auto tail = [&]() {
     lookups();
-  }
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  CLFA_DFT16_HT(FWD, v, hook, kMapColB, tail);
   const cpx b = cmul(blo, bhi);
   // product tree in halves of four (T_r = b s^r, U_r = T_r s^8), two products per statement
   cpx T[4], U[4];
@@ -635,7 +623,7 @@ template <int RB, bool INV = false> __device__ __forceinline__ void res_fetch_st
 // ---- phase 2: one row block ---------------------------------------------------------------------
 // v[e] = Z[16 rb + t][c + 16 e] -> X[16 rb + c + 256 (t + 16 e)] left in v[e] (lane = row c, k2 = t + 16 e)
 // LAND: the results go straight into the landing registers (dft16_hp_land) instead of v
-// TWA: the twiddle rows read a group ahead (CLFA_TW_AHEAD; the packed real forward kernel has no registers for it)
+// TWA: the twiddle rows read a group ahead (res_tw_rows; the packed real forward kernel has no registers for it)
 template <bool FWD, int PROBE = 0, bool LAND = false, bool TWA = true, class H = HookNone>
 __device__ __forceinline__ void res_row_block(cpx (&v)[16], const ResLane &L, const H &hook = H()) {
   if constexpr (!(PROBE & kProbeNoMath)) CLFA_DFT16_H(FWD, v, hook, kMapRowC);
@@ -651,7 +639,7 @@ __device__ __forceinline__ void res_row_block(cpx (&v)[16], const ResLane &L, co
   for (int e = 0; e < 16; e++) v[e] = L.xb_r[18 * e];
   }
   if constexpr (PROBE & kProbeNoMath) return;
-  res_tw_rows<FWD, 6, CLFA_TW_AHEAD && TWA>(v, L, hook);
+  res_tw_rows<FWD, 6, TWA>(v, L, hook);
   if constexpr (LAND) dft16_hp_land<FWD, H, kMapRowD.p[0], kMapRowD.p[1], kMapRowD.p[2], kMapRowD.p[3], kMapRowD.p[4], kMapRowD.p[5], kMapRowD.p[6], kMapRowD.p[7]>(v, hook);
   else CLFA_DFT16_H(FWD, v, hook, kMapRowD);
 }
@@ -693,15 +681,14 @@ __device__ __forceinline__ void res_phase1_block(cpx (&v)[16], const ResLane &L,
 // Pair twiddles W_2M^i = W_2M^(16 q + c) * W_512^t * W_32^e: two lookups (the first 256 entries of the plan's w2 table
 // and every 256th) and compile-time constants.  The map's 1/2 rides on the 1/N of the table (r2c_pair_prescaled).
 
-// build switches of the packed real variants (A/B and debugging; the library's choice is the default)
+// build switch of the packed real variants (debugging)
 #ifndef CLFA_C2R_WAIT
 #define CLFA_C2R_WAIT 1      // 0: every counted wait of the two packed real variants is vmcnt(0) (tools/check_waits.py)
 #endif
-#ifndef CLFA_C2R_KEEP_A
-#define CLFA_C2R_KEEP_A 1    // its natural loads cached as well: per 1024 transforms all streaming 0.265 ms, the mirrored
-#endif                       // loads cached 0.253, all cached 0.245 (profiles/rfft131072_fused_r04.txt)
 constexpr bool kC2rWait = CLFA_C2R_WAIT;
-constexpr bool kC2rKeepA = CLFA_C2R_KEEP_A;
+// the inverse variant's natural loads cached as well: per 1024 transforms all streaming 0.265 ms, the mirrored
+// loads cached 0.253, all cached 0.245 (profiles/rfft131072_fused_r04.txt)
+constexpr bool kC2rKeepA = true;
 constexpr int kTabPair = kTabSize;   // [W_2M^k, k < 256 | W_512^t, t < 16]
 constexpr int kTabSizeR = kTabSize + 272;
 constexpr int kParkAcc = 224;        // B' results parked in a[224:255] (keep row 15's registers, fetched first)
@@ -972,14 +959,11 @@ __device__ __forceinline__ void res_probe_grid_sync(unsigned long long *dbg, uns
 // R2C: packed real transforms of size 2 kN, forward — the same transform with the reference's pair map inside phase 2
 // (above); w2_g = the plan's pair twiddles W_2M^i (cl_fft.cpp:233-238), M entries
 // C2R: ... inverse — the pair map inside phase 1 (above)
-// CLFA_DS_SINGLE: hipcc's load / store optimiser pairs the exchanges' sixteen ds_read_b64 into eight ds_read2_b64, which the
+// hipcc's load / store optimiser pairs the exchanges' sixteen ds_read_b64 into eight ds_read2_b64, which the
 // LDS serves per 16 contiguous lanes over 32 banks at half the rate (MI355X_MICROARCH.md, LDS table): in the layouts above —
 // made for the single reads, 2 x 32 lanes over 64 banks — every access is then a 2-way conflict, four times the LDS cycles
 // (rocprofv3 round 4: SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 0.29).  The pass is off for this kernel.
-#ifndef CLFA_DS_SINGLE
-#define CLFA_DS_SINGLE 1
-#endif
-#if CLFA_DS_SINGLE && defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__)
 #define CLFA_RES16_TARGET __attribute__((target("no-load-store-opt")))
 #else
 #define CLFA_RES16_TARGET

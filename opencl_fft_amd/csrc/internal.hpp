@@ -20,7 +20,7 @@ constexpr int kLane13Lds = 1280, kLane13Size = 1792;
 // sixteen DIFFERENT rows (row = tid & 15); 16 entries = 32 dwords apart they would fall on two groups of four banks (an
 // 8-way conflict, 32 LDS cycles per read — rocprofv3 round 4: SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 0.41-0.46 for
 // config 3's kernel); 18 entries = 36 dwords apart they cover the 64 banks exactly once (MI355X_MICROARCH.md, LDS table)
-constexpr int kRow16Stride = kRow16StrideDev;   // (fft_device.hpp: CLFA_ROW16_STRIDE)
+constexpr int kRow16Stride = kRow16StrideDev;   // (fft_device.hpp, which compiles on the host alone, has the value)
 static_assert(kRow16Stride >= 16 && kRow16Stride % 2 == 0, "rows stay 16-byte aligned");
 constexpr int kRow16Lds = 16 * kRow16Stride;            // the s256 part follows
 constexpr int kLaneLds = kRow16Lds + (kLane13Lds - 256);   // entries of the LDS copy
@@ -105,7 +105,7 @@ hipError_t launch_r2c_pack(cpx *data, const cpx *w2, int m, long batch, hipStrea
 hipError_t launch_c2r_unpack(cpx *data, const cpx *w2, int m, long batch, hipStream_t s, long out_off = 0);
 
 // arbitrary (non power-of-two) complex lengths, an extension: Bluestein's algorithm around two m-point
-// power-of-two transforms, m >= 2 n - 1 (fft_kernels.hip); n up to kBlueMaxN
+// power-of-two transforms, m >= 2 n - 1 (fft_aux.inc); n up to kBlueMaxN
 constexpr int kBlueMaxN = 1 << 22;
 bool blue_lds_ok(int m);
 hipError_t launch_blue_lds(int m, const cpx *x, cpx *y, const cpx *w, const cpx *bt, const cpx *tab, int n, float scale,

@@ -7,7 +7,7 @@
 //
 // Both drive the shared pass chain of the single-workgroup LDS FFT (fft_wg.hpp: pass_gather_padded, wg_passes,
 // dif_scatter_padded) with the reference's pair maps (r2c_pair / c2r_pair, cl_fft.cpp:178-205) on the natural-order LDS
-// copy — the recipe of k_fft_small (fft_kernels.hip), for every packed size 64..16384 (complex n = 32..8192).  A workgroup
+// copy — the recipe of k_fft_small (fft_lds.inc), for every packed size 64..16384 (complex n = 32..8192).  A workgroup
 // holds FPW = LdsGeom::FPW frames at once; global accesses go in chunk order (element tid + WG e of the FPW * n
 // elements), so a wave reads runs of whole frames.
 #include "fft_wg.hpp"

@@ -122,7 +122,8 @@ def test_handover_kernels_code_object_audit(tmp_path):
 
 
 def test_tiny_kernel_code_object_audit(tmp_path):
-    """fft_kernels.hip: k_fft_tiny<2> (n = 4) exchanges the halves of a transform between its two lanes through the DPP crossbar —
+    """fft_kernels.hip (fft_lds.inc, fft_big.inc): k_fft_tiny<2> (n = 4) exchanges the halves of a transform between its two lanes
+    through the DPP crossbar —
     on the compiled ISA: quad_perm:[1,0,3,2] operands, 16-byte loads and stores, no LDS instruction, no scratch; and the
     pass-to-pass twiddles of the column kernels above 65536 points come from LDS (no global table lookups: their only
     vector-memory instructions are the 16 + 16 that move a lane's data ... 32 + 32 for the two-run forms)"""
@@ -151,24 +152,5 @@ def test_tiny_kernel_code_object_audit(tmp_path):
 def test_resident_kernel_code_object_audit(tmp_path):
     """fft_resident.hip manages the accumulation registers and v[224:255] by hand; tools/check_isa.py
     verifies on the freshly compiled ISA that hipcc put nothing of its own there and uses no scratch"""
-    import importlib.util
-    src = os.path.join(ROOT, "opencl_fft_amd", "csrc", "fft_resident.hip")
-    flags = None
-    for ln in open(os.path.join(ROOT, "opencl_fft_amd", "csrc", "Makefile")):
-        if ln.startswith("CXXFLAGS"):
-            flags = ln.split("=", 1)[1].replace("$(ARCH)", "gfx950").split()
-    assert flags, "CXXFLAGS not found in the Makefile"
-    obj = str(tmp_path / "fft_resident.o")
-    hipcc = "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc on this machine: the code-object audit needs the gfx950 cross-compiler")
-    p = subprocess.run([hipcc] + flags + ["-save-temps=obj", "-c", src, "-o", obj], stdout=subprocess.PIPE,
-                       stderr=subprocess.STDOUT)
-    assert p.returncode == 0, p.stdout.decode()[-4000:]
-    asm = [f for f in os.listdir(tmp_path) if f.endswith("gfx950.s")]
-    assert len(asm) == 1, asm
-    spec = importlib.util.spec_from_file_location("check_isa", os.path.join(ROOT, "tools", "check_isa.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    problems = mod.check(str(tmp_path / asm[0]))
+    problems = _check_isa().check(_compile_to_asm(tmp_path, "fft_resident"))
     assert not problems, "\n".join(problems[:10])

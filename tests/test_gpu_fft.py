@@ -542,7 +542,7 @@ def test_config3_full_size_roundtrip():
                                     (True, 1024), (True, 2048), (True, 4096), (True, 8192)])
 def test_streaming_batches_on_the_reduced_grid(real, n):
     """1 GiB of transforms per launch and one more (ragged): from there the persistent grids of k_fft_small / k_fft_lds put
-    one or two workgroups on a CU instead of all that fit (wgs_per_cu(), fft_kernels.hip) — same transforms, longer
+    one or two workgroups on a CU instead of all that fit (wgs_per_cu(), fft_lds.inc) — same transforms, longer
     grid-stride loops: picked transforms against the oracle, all of them through the round trip"""
     import torch
     per = n * (4 if real else 8)
