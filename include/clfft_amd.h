@@ -288,20 +288,50 @@ CLFA_API const char *clfa_stft_kernel_name(const clfa_stft *st);
  * the previous one); capturable into a hipGraph; the current device is left as found.  Workspace: allocated by the first
  * call that needs it (workspace_bytes() = what is held), released with the object; a call under capture that would have
  * to allocate it returns CLFA_INVALID_OPERATION.  Long calls run in sub-batches of an internal cap (at most 1024 blocks;
- * CLFA_PCONV_MATRIX_BLOCKS_MAX, read at creation, lowers it). */
+ * CLFA_PCONV_MATRIX_BLOCKS_MAX, read at creation, lowers it).
+ *
+ * Timed crossfade (push_ir_fade, push_ir_fade_dev): a change of responses without the step of a plain push.  ir,
+ * row_stride and the row layout are those of push_ir / push_ir_dev.  Definition: let A be the responses in force at the
+ * push and B the pushed ones; block 0 the next block processed after the push; N = fade_blocks * pts; n a sample's index
+ * counted from the first sample of block 0; yA what this object would have produced without the push; yB what a second
+ * matrix of the same geometry would produce if it had held B and received every input this object has received so far
+ * (yB's overlap-add tail from the block before block 0 included).  Then
+ *   for 0 <= n < N the output sample is  yA + g(n) * (yB - yA),  evaluated in float32 in that form (a subtraction, a
+ *     multiplication, an addition, each rounded on its own), with  g(n) = (float)n / (float)N  (IEEE division, round to
+ *     nearest): exactly 0 at n = 0, rising linearly to (N-1)/N;
+ *   from sample N on the output is yB, B is the matrix in force and fade_remaining() is 0.
+ * State: the input rings are shared by both paths and written once.  During a fade the object holds a second response
+ * set and a second set of tails, primed at the push from the nparts frames the rings hold; when the last fade block has
+ * been processed they are copied over the first set on the same stream.  No device address of the object (responses,
+ * rings, tails, workspaces) ever changes: a graph captured outside a fade stays valid after one.  state_bytes() and
+ * workspace_bytes() count the second set and its workspaces once they exist (from the first fade push on).
+ * Refusals (the state is untouched in each): fade_blocks < 1, fade_blocks * pts > 2^31 - 1 or any argument error of
+ * push_ir_dev: CLFA_INVALID_VALUE; a fade push, or a plain push_ir / push_ir_dev, while fade_remaining() > 0:
+ * CLFA_INVALID_OPERATION; a fade push on a capturing stream (it allocates what the fade needs): CLFA_INVALID_OPERATION;
+ * process_dev on a capturing stream while fade_remaining() > 0 (the fade's progress is host state that a replay would
+ * not advance): CLFA_INVALID_OPERATION.  A process_dev call outside capture never allocates because of a fade.
+ * Numerics: both paths sum every output bin over the object's segments in the object's order, and a sub-batch lies
+ * wholly inside or wholly outside a fade: a fade's outputs are the same bits however its blocks are split into calls,
+ * for every sub-batch cap and on any stream; from sample N on they are the bits of a plain push of B made at the same
+ * point, and a fade from A to A gives the bits of no push at all. */
 CLFA_API int clfa_pconv_matrix_create(clfa_pconv_matrix **m, int device, int cvs, int pts, int inputs, int outputs);
 CLFA_API void clfa_pconv_matrix_destroy(clfa_pconv_matrix *m);
 CLFA_API int clfa_pconv_matrix_get_error(const clfa_pconv_matrix *m);
 CLFA_API const char *clfa_pconv_matrix_get_log(const clfa_pconv_matrix *m);
 CLFA_API int clfa_pconv_matrix_push_ir(clfa_pconv_matrix *m, const float *ir);
 CLFA_API int clfa_pconv_matrix_push_ir_dev(clfa_pconv_matrix *m, const void *ir, long row_stride, void *stream);
+CLFA_API int clfa_pconv_matrix_push_ir_fade(clfa_pconv_matrix *m, const float *ir, long fade_blocks); /* host rows, blocking */
+CLFA_API int clfa_pconv_matrix_push_ir_fade_dev(clfa_pconv_matrix *m, const void *ir, long row_stride, long fade_blocks,
+                                                void *stream);
+/* blocks of the fade not yet processed; 0 = none (and for a NULL handle) */
+CLFA_API long clfa_pconv_matrix_fade_remaining(const clfa_pconv_matrix *m);
 CLFA_API int clfa_pconv_matrix_process_dev(clfa_pconv_matrix *m, void *out, long out_stride, const void *in, long in_stride,
                                            long nblocks, void *stream);
 /* host form: rows contiguous (stride nblocks*pts), blocking */
 CLFA_API int clfa_pconv_matrix_convolution(clfa_pconv_matrix *m, float *out, const float *in, long nblocks);
 /* 0 for a failed object */
 CLFA_API int clfa_pconv_matrix_nparts(const clfa_pconv_matrix *m);
-/* responses + input rings + tails; the sub-batch workspaces */
+/* responses + input rings + tails (+ a fade's second responses and tails); the sub-batch workspaces */
 CLFA_API size_t clfa_pconv_matrix_state_bytes(const clfa_pconv_matrix *m);
 CLFA_API size_t clfa_pconv_matrix_workspace_bytes(const clfa_pconv_matrix *m);
 /* "k_pconvm_mac" ("" for a failed object) */

@@ -525,29 +525,61 @@ class PconvMatrix:
     def kernel_name(self):
         return lib().clfa_pconv_matrix_kernel_name(self._h).decode()
 
-    def push_ir(self, ir):
-        """ir: float32 (outputs, inputs, >= nparts*pts), e.g. rows of cvs samples (the remainder is ignored)"""
+    def _host_rows(self, ir):
         ir = np.asarray(ir, dtype=np.float32)
         need = self.nparts * self.pts
         if ir.ndim != 3 or ir.shape[:2] != (self.outputs, self.inputs) or ir.shape[2] < need:
+            return None
+        return np.ascontiguousarray(ir[:, :, :need])
+
+    def _device_rows(self, ir, stream):
+        """(row stride, stream) of a device tensor of responses, None for a bad one"""
+        need = self.nparts * self.pts
+        if (ir.dim() != 3 or tuple(ir.shape[:2]) != (self.outputs, self.inputs) or ir.shape[2] < need
+                or str(ir.dtype) != "torch.float32" or ir.stride(2) != 1):
+            return None
+        rs = ir.stride(1) if self.inputs > 1 else (ir.stride(0) if self.outputs > 1 else max(ir.stride(1), need))
+        if self.outputs > 1 and ir.stride(0) != self.inputs * rs:
+            return None
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream(ir.device).cuda_stream
+        return rs, stream
+
+    def push_ir(self, ir):
+        """ir: float32 (outputs, inputs, >= nparts*pts), e.g. rows of cvs samples (the remainder is ignored)"""
+        ir = self._host_rows(ir)
+        if ir is None:
             return CL_INVALID_VALUE
-        ir = np.ascontiguousarray(ir[:, :, :need])
         return lib().clfa_pconv_matrix_push_ir(self._h, ir.ctypes.data)
 
     def push_ir_device(self, ir, stream=None):
         """ir: device tensor (outputs, inputs, >= nparts*pts) of float32 whose rows are contiguous and evenly spaced
         (stride(0) == inputs * stride(1)); the row stride is stride(1).  Asynchronous on `stream`."""
-        need = self.nparts * self.pts
-        if (ir.dim() != 3 or tuple(ir.shape[:2]) != (self.outputs, self.inputs) or ir.shape[2] < need
-                or str(ir.dtype) != "torch.float32" or ir.stride(2) != 1):
+        rows = self._device_rows(ir, stream)
+        if rows is None:
             return CL_INVALID_VALUE
-        rs = ir.stride(1) if self.inputs > 1 else (ir.stride(0) if self.outputs > 1 else max(ir.stride(1), need))
-        if self.outputs > 1 and ir.stride(0) != self.inputs * rs:
+        return lib().clfa_pconv_matrix_push_ir_dev(self._h, ir.data_ptr(), rows[0], rows[1])
+
+    def push_ir_fade(self, ir, fade_blocks):
+        """push_ir as a crossfade: over the next fade_blocks blocks the output moves linearly, sample by sample, from
+        what the responses in force give to what `ir` gives on the same input history (clfft_amd.h); blocking"""
+        ir = self._host_rows(ir)
+        if ir is None:
             return CL_INVALID_VALUE
-        if stream is None:
-            import torch
-            stream = torch.cuda.current_stream(ir.device).cuda_stream
-        return lib().clfa_pconv_matrix_push_ir_dev(self._h, ir.data_ptr(), rs, stream)
+        return lib().clfa_pconv_matrix_push_ir_fade(self._h, ir.ctypes.data, int(fade_blocks))
+
+    def push_ir_fade_device(self, ir, fade_blocks, stream=None):
+        """push_ir_device as a crossfade over the next fade_blocks blocks.  Asynchronous on `stream`; not under graph
+        capture, and no other push while fade_remaining() > 0 (CL_INVALID_OPERATION)."""
+        rows = self._device_rows(ir, stream)
+        if rows is None:
+            return CL_INVALID_VALUE
+        return lib().clfa_pconv_matrix_push_ir_fade_dev(self._h, ir.data_ptr(), rows[0], int(fade_blocks), rows[1])
+
+    def fade_remaining(self):
+        """blocks of a pending crossfade that have not been processed yet; 0: none"""
+        return lib().clfa_pconv_matrix_fade_remaining(self._h)
 
     def convolution(self, output, input):
         """whole signals on the host: float32 (inputs, L) -> (outputs, L), L a multiple of pts; blocking"""

@@ -68,6 +68,9 @@ SYMBOLS = [
     ("clfa_pconv_matrix_get_log", C.c_char_p, [_vp]),
     ("clfa_pconv_matrix_push_ir", C.c_int, [_vp, _vp]),
     ("clfa_pconv_matrix_push_ir_dev", C.c_int, [_vp, _vp, C.c_long, _vp]),
+    ("clfa_pconv_matrix_push_ir_fade", C.c_int, [_vp, _vp, C.c_long]),
+    ("clfa_pconv_matrix_push_ir_fade_dev", C.c_int, [_vp, _vp, C.c_long, C.c_long, _vp]),
+    ("clfa_pconv_matrix_fade_remaining", C.c_long, [_vp]),
     ("clfa_pconv_matrix_process_dev", C.c_int, [_vp, _vp, C.c_long, _vp, C.c_long, C.c_long, _vp]),
     ("clfa_pconv_matrix_convolution", C.c_int, [_vp, _vp, _vp, C.c_long]),
     ("clfa_pconv_matrix_nparts", C.c_int, [_vp]),

@@ -543,7 +543,53 @@ struct clfa_pconv_matrix {
   PconvMatrixPlan plan;
   int cap = 1;                   // blocks per sub-batch (CLFA_PCONV_MATRIX_BLOCKS_MAX: tuning switch, read at creation)
   StreamOrder order;
+  // timed crossfade (push_ir_fade): allocated by the first fade push and kept, so that no address ever changes
+  DevBuf H2, tail2;              // the responses faded to and their path's tails; copied over H / tail when the fade ends
+  DevBuf Y2, P2, tail_ws2, mix;  // the second path's sub-batch workspaces and its samples (outputs x cap x pts floats)
+  long fade_len = 0, fade_done = 0;   // blocks of the pending fade (0: none) and how many of them have been processed
+  bool fade_two_mac = false;     // CLFA_PCONV_MATRIX_FADE_MAC=two: two launches of the plain MAC (tuning switch)
 };
+
+// the launcher's view of the object (everything but the call's rows, K and w)
+static PconvMatrixArgs mconv_args(const clfa_pconv_matrix *p) {
+  PconvMatrixArgs a;
+  a.logb = p->logb;
+  a.bins = p->pts;
+  a.nparts = p->nparts;
+  a.inputs = p->inputs;
+  a.outputs = p->outputs;
+  a.plan = p->plan;
+  a.cap = p->cap;
+  a.H = (const cpx *)p->H.p;
+  a.ringA = (cpx *)p->ringA.p;
+  a.tail = (float *)p->tail.p;
+  a.X = (cpx *)p->X.p;
+  a.Y = (cpx *)p->Y.p;
+  a.P = (cpx *)p->P.p;
+  a.tail_ws = (float *)p->tail_ws.p;
+  a.half = (const cpx *)p->half.p;
+  a.w2f = (const cpx *)p->w2f.p;
+  a.w2i = (const cpx *)p->w2i.p;
+  a.H2 = (const cpx *)p->H2.p;
+  a.tail2 = (float *)p->tail2.p;
+  a.Y2 = (cpx *)p->Y2.p;
+  a.P2 = (cpx *)p->P2.p;
+  a.tail_ws2 = (float *)p->tail_ws2.p;
+  a.mix = (float *)p->mix.p;
+  a.fade_len = p->fade_len;
+  a.two_mac = p->fade_two_mac;
+  return a;
+}
+
+// the sub-batch workspaces of a process call
+static int mconv_workspaces(clfa_pconv_matrix *p, hipStream_t s) {
+  const size_t frames = sizeof(cpx) * (size_t)p->cap * p->pts;
+  return ensure_workspaces({{&p->X, frames * p->inputs},
+                            {&p->Y, frames * p->outputs},
+                            {&p->P, frames * p->outputs * (size_t)(p->plan.segs - 1)},
+                            {&p->tail_ws, sizeof(float) * (size_t)p->outputs * p->pts}},
+                           s);
+}
 
 static int mconv_setup(clfa_pconv_matrix *p, int device, int cvs, int pts, int inputs, int outputs) {
   p->log[0] = 0;
@@ -572,6 +618,7 @@ static int mconv_setup(clfa_pconv_matrix *p, int device, int cvs, int pts, int i
   if (const char *env = getenv("CLFA_PCONV_MATRIX_SEGS")) {
     if (atoi(env) >= 1 && atoi(env) <= 4096) p->plan.segs = atoi(env);
   }
+  if (const char *env = getenv("CLFA_PCONV_MATRIX_FADE_MAC")) p->fade_two_mac = !strcmp(env, "two");
   // sub-batch workspaces X, Y and the segments' partials (CLFA_PCONV_MATRIX_BLOCKS_MAX: read per object, like
   // CLFA_PCONV_BLOCKS_MAX)
   p->cap = subbatch_cap(((long)inputs + (long)outputs * p->plan.segs) * pts * (long)sizeof(cpx), "CLFA_PCONV_MATRIX_BLOCKS_MAX");
@@ -590,6 +637,20 @@ static int mconv_setup(clfa_pconv_matrix *p, int device, int cvs, int pts, int i
   return CLFA_SUCCESS;
 }
 
+// the blocking host pushes: the rows staged on the object's stream, then the device form `push`
+template <class Push>
+static int mconv_push_host(clfa_pconv_matrix *p, const float *ir, Push push) {
+  ENTER_DEVICE(p->di.device);
+  const long len = (long)p->nparts * p->pts;
+  const size_t bytes = sizeof(float) * (size_t)len * p->outputs * p->inputs;
+  int e = p->hir.ensure(bytes);
+  if (e) return e;
+  HIP_TRY(hipMemcpyAsync(p->hir.p, ir, bytes, hipMemcpyHostToDevice, p->stream));
+  if ((e = push(p->hir.p, len))) return e;
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return CLFA_SUCCESS;
+}
+
 extern "C" {
 
 int clfa_pconv_matrix_create(clfa_pconv_matrix **m, int device, int cvs, int pts, int inputs, int outputs) {
@@ -602,17 +663,20 @@ int clfa_pconv_matrix_get_error(const clfa_pconv_matrix *p) { return p ? p->err 
 const char *clfa_pconv_matrix_get_log(const clfa_pconv_matrix *p) { return p ? p->log : ""; }
 int clfa_pconv_matrix_nparts(const clfa_pconv_matrix *p) { return p && !p->err ? p->nparts : 0; }
 size_t clfa_pconv_matrix_state_bytes(const clfa_pconv_matrix *p) {
-  return p ? p->H.bytes + p->ringA.bytes + p->tail.bytes : 0;
+  return p ? p->H.bytes + p->ringA.bytes + p->tail.bytes + p->H2.bytes + p->tail2.bytes : 0;
 }
 size_t clfa_pconv_matrix_workspace_bytes(const clfa_pconv_matrix *p) {
-  return p ? p->X.bytes + p->Y.bytes + p->P.bytes + p->tail_ws.bytes : 0;
+  return p ? p->X.bytes + p->Y.bytes + p->P.bytes + p->tail_ws.bytes + p->Y2.bytes + p->P2.bytes + p->tail_ws2.bytes + p->mix.bytes
+           : 0;
 }
+long clfa_pconv_matrix_fade_remaining(const clfa_pconv_matrix *p) { return p ? p->fade_len - p->fade_done : 0; }
 const char *clfa_pconv_matrix_kernel_name(const clfa_pconv_matrix *p) { return !p || p->err ? "" : "k_pconvm_mac"; }
 
 int clfa_pconv_matrix_push_ir_dev(clfa_pconv_matrix *p, const void *ir, long row_stride, void *stream) {
   if (int e = obj_error(p)) return e;
   const long len = (long)p->nparts * p->pts;
   if (!ir || row_stride < len || ((uintptr_t)ir & 3)) return CLFA_INVALID_VALUE;
+  if (p->fade_len) return CLFA_INVALID_OPERATION;   // a fade is pending: H is one end of it
   ENTER_DEVICE(p->di.device);
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(p->order.use(s));
@@ -626,15 +690,46 @@ int clfa_pconv_matrix_push_ir_dev(clfa_pconv_matrix *p, const void *ir, long row
 int clfa_pconv_matrix_push_ir(clfa_pconv_matrix *p, const float *ir) {
   if (int e = obj_error(p)) return e;
   if (!ir) return CLFA_INVALID_VALUE;
-  ENTER_DEVICE(p->di.device);
+  if (p->fade_len) return CLFA_INVALID_OPERATION;
+  return mconv_push_host(p, ir, [&](const void *d, long len) { return clfa_pconv_matrix_push_ir_dev(p, d, len, p->stream); });
+}
+
+int clfa_pconv_matrix_push_ir_fade_dev(clfa_pconv_matrix *p, const void *ir, long row_stride, long fade_blocks, void *stream) {
+  if (int e = obj_error(p)) return e;
   const long len = (long)p->nparts * p->pts;
-  const size_t bytes = sizeof(float) * (size_t)len * p->outputs * p->inputs;
-  int e = p->hir.ensure(bytes);
+  if (!ir || row_stride < len || ((uintptr_t)ir & 3) || fade_blocks < 1 || fade_blocks > 0x7fffffffL / p->pts)
+    return CLFA_INVALID_VALUE;
+  if (p->fade_len) return CLFA_INVALID_OPERATION;   // one fade at a time
+  ENTER_DEVICE(p->di.device);
+  hipStream_t s = (hipStream_t)stream;
+  // everything the fade needs is allocated here, so that no process call allocates because of it: refused under capture
+  if (StreamOrder::capturing(s)) return CLFA_INVALID_OPERATION;
+  int e = mconv_workspaces(p, s);
   if (e) return e;
-  HIP_TRY(hipMemcpyAsync(p->hir.p, ir, bytes, hipMemcpyHostToDevice, p->stream));
-  if ((e = clfa_pconv_matrix_push_ir_dev(p, p->hir.p, len, p->stream))) return e;
-  HIP_TRY(hipStreamSynchronize(p->stream));
+  if ((e = p->H2.ensure(p->H.bytes)) || (e = p->tail2.ensure(p->tail.bytes)) || (e = p->Y2.ensure(p->Y.bytes)) ||
+      (e = p->P2.ensure(p->P.bytes)) || (e = p->tail_ws2.ensure(p->tail_ws.bytes)) ||
+      (e = p->mix.ensure(sizeof(float) * (size_t)p->outputs * p->cap * p->pts)))
+    return e;
+  HIP_TRY(p->order.use(s));
+  // the rows' spectra into the second set (as push_ir_dev into H), then that set's tails from the ring
+  const int aligned = ((uintptr_t)ir & 7) == 0 && (row_stride & 1) == 0;
+  HIP_TRY(launch_pconvb_forward(p->logb, (const float *)ir, row_stride, (cpx *)p->H2.p, p->nparts, p->nparts,
+                                p->outputs * p->inputs, aligned, (const cpx *)p->half.p, (const cpx *)p->w2f.p, s));
+  PconvMatrixArgs a = mconv_args(p);
+  a.w = p->wp;
+  HIP_TRY(launch_pconv_matrix_prime(a, s));
+  p->fade_len = fade_blocks;
+  p->fade_done = 0;
   return CLFA_SUCCESS;
+}
+
+int clfa_pconv_matrix_push_ir_fade(clfa_pconv_matrix *p, const float *ir, long fade_blocks) {
+  if (int e = obj_error(p)) return e;
+  if (!ir || fade_blocks < 1 || fade_blocks > 0x7fffffffL / p->pts) return CLFA_INVALID_VALUE;
+  if (p->fade_len) return CLFA_INVALID_OPERATION;
+  return mconv_push_host(p, ir, [&](const void *d, long len) {
+    return clfa_pconv_matrix_push_ir_fade_dev(p, d, len, fade_blocks, p->stream);
+  });
 }
 
 int clfa_pconv_matrix_process_dev(clfa_pconv_matrix *p, void *out, long out_stride, const void *in, long in_stride,
@@ -646,45 +741,40 @@ int clfa_pconv_matrix_process_dev(clfa_pconv_matrix *p, void *out, long out_stri
   if (!len) return CLFA_SUCCESS;
   ENTER_DEVICE(p->di.device);
   hipStream_t s = (hipStream_t)stream;
-  const size_t frames = sizeof(cpx) * (size_t)p->cap * p->pts;
-  int e = ensure_workspaces({{&p->X, frames * p->inputs},
-                             {&p->Y, frames * p->outputs},
-                             {&p->P, frames * p->outputs * (size_t)(p->plan.segs - 1)},
-                             {&p->tail_ws, sizeof(float) * (size_t)p->outputs * p->pts}},
-                            s);
-  if (e) return e;
+  // the progress of a fade is host state, which a replay would not advance
+  if (p->fade_len && StreamOrder::capturing(s)) return CLFA_INVALID_OPERATION;
+  if (int e = mconv_workspaces(p, s)) return e;
   HIP_TRY(p->order.use(s));
-  PconvMatrixArgs a;
-  a.logb = p->logb;
-  a.bins = p->pts;
-  a.nparts = p->nparts;
-  a.inputs = p->inputs;
-  a.outputs = p->outputs;
-  a.plan = p->plan;
-  a.cap = p->cap;
+  PconvMatrixArgs a = mconv_args(p);
   a.in_stride = in_stride;
   a.out_stride = out_stride;
   a.aligned_in = ((uintptr_t)in & 7) == 0 && (in_stride & 1) == 0;
   a.aligned_out = ((uintptr_t)out & 7) == 0 && (out_stride & 1) == 0;
-  a.H = (const cpx *)p->H.p;
-  a.ringA = (cpx *)p->ringA.p;
-  a.tail = (float *)p->tail.p;
-  a.X = (cpx *)p->X.p;
-  a.Y = (cpx *)p->Y.p;
-  a.P = (cpx *)p->P.p;
-  a.tail_ws = (float *)p->tail_ws.p;
-  a.half = (const cpx *)p->half.p;
-  a.w2f = (const cpx *)p->w2f.p;
-  a.w2i = (const cpx *)p->w2i.p;
   const float *src = (const float *)in;
   float *dst = (float *)out;
-  for (long j0 = 0; j0 < nblocks; j0 += p->cap) {
-    a.K = (int)(nblocks - j0 < p->cap ? nblocks - j0 : p->cap);
+  for (long j0 = 0; j0 < nblocks; j0 += a.K) {
+    // a sub-batch lies wholly inside or wholly outside a fade: cut at the fade's end
+    const long fade = p->fade_len - p->fade_done;
+    long k = nblocks - j0 < p->cap ? nblocks - j0 : p->cap;
+    if (fade && fade < k) k = fade;
+    a.K = (int)k;
     a.w = p->wp;
     a.in = src + j0 * pts;
     a.out = dst + j0 * pts;
-    HIP_TRY(launch_pconv_matrix(a, s));
+    if (fade) {
+      a.fade_pos = p->fade_done;
+      HIP_TRY(launch_pconv_matrix_fade(a, s));
+      p->fade_done += k;
+    } else {
+      HIP_TRY(launch_pconv_matrix(a, s));
+    }
     p->wp = (int)((p->wp + a.K) % nparts);
+    if (fade == k) {
+      // the fade's last block: the second set becomes the first, in place (no address of the object changes)
+      p->fade_len = p->fade_done = 0;
+      HIP_TRY(hipMemcpyAsync(p->H.p, p->H2.p, p->H.bytes, hipMemcpyDeviceToDevice, s));
+      HIP_TRY(hipMemcpyAsync(p->tail.p, p->tail2.p, p->tail.bytes, hipMemcpyDeviceToDevice, s));
+    }
   }
   return CLFA_SUCCESS;
 }

@@ -208,9 +208,22 @@ struct PconvMatrixArgs {
   cpx *X = nullptr, *Y = nullptr, *P = nullptr;   // inputs x cap, outputs x cap, (segs - 1) x outputs x cap frames
   float *tail_ws = nullptr;              // outputs x bins
   const cpx *half = nullptr, *w2f = nullptr, *w2i = nullptr;
+  // a timed crossfade to a second response set (launch_pconv_matrix_fade / _prime): the set, its tails and workspaces
+  const cpx *H2 = nullptr;
+  float *tail2 = nullptr;                // outputs x bins
+  cpx *Y2 = nullptr, *P2 = nullptr;      // as Y, P
+  float *tail_ws2 = nullptr;             // outputs x bins
+  float *mix = nullptr;                  // the second path's samples: outputs rows of cap * bins floats
+  long fade_pos = 0, fade_len = 0;       // blocks of the fade before this sub-batch, blocks of the whole fade
+  bool two_mac = false;                  // two launches of the plain MAC instead of the two-response one
 };
 PconvMatrixPlan pconv_matrix_plan(int bins, int nparts, int inputs, int outputs, const DeviceInfo &di);
 hipError_t launch_pconv_matrix(const PconvMatrixArgs &a, hipStream_t s);
+// A sub-batch inside a fade (K <= fade_len - fade_pos): both paths over the shared ring, the second one's samples mixed
+// into `out` with g(n) = (float)n / (float)(fade_len * bins), n counted from the fade's first sample; ring, tail and tail2
+// committed.  _prime: tail2 = the second half of the block before the next one under H2, from ring A alone.
+hipError_t launch_pconv_matrix_fade(const PconvMatrixArgs &a, hipStream_t s);
+hipError_t launch_pconv_matrix_prime(const PconvMatrixArgs &a, hipStream_t s);
 constexpr int kPconvMaxLogBins = 15;   // pts up to 32768 (the reference harness' largest, csound/tests.py:13)
 // ends of the composed chain used when bins exceed the LDS FFT sizes
 hipError_t launch_pconv_pad(const float *in, long in_stride, cpx *work, int bins, int channels, hipStream_t s);
