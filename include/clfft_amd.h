@@ -217,6 +217,54 @@ CLFA_API int clfa_dconv_convolution_tv(clfa_dconv *dc, float *out, const float *
 /* device-resident variant of both (in2 may be NULL): vsize floats each, asynchronous on `stream`, one launch per
  * block; out must not be in1 or in2 */
 CLFA_API int clfa_dconv_process_dev(clfa_dconv *dc, void *out, const void *in1, const void *in2, void *stream);
+/* Many channels and many blocks per call (extension).
+ * clfa_dconv_create_channels: `channels` independent instances (1..65535) in one object — `channels` delay rings and
+ * coefficient rings of end = irsize + vsize floats each, one write point wp for all of them (clfa_dconv_wp).
+ * clfa_dconv_create is channels = 1.  On an object with channels > 1, clfa_dconv_push_ir takes channels x irsize floats,
+ * and clfa_dconv_convolution, clfa_dconv_convolution_tv and clfa_dconv_process_dev take channels x vsize contiguous floats
+ * and are the block call below with nblocks = 1; on channels == 1 those calls are what they were. */
+CLFA_API int clfa_dconv_create_channels(clfa_dconv **dc, int device, int irsize, int vsize, int channels);
+/* device-resident push_ir: channel c's response starts at ir + c * channel_stride floats (channel_stride >= irsize, ir
+ * 4-byte aligned), irsize floats are read of each; asynchronous on `stream` */
+CLFA_API int clfa_dconv_push_ir_dev(clfa_dconv *dc, const void *ir, long channel_stride, void *stream);
+/* nblocks consecutive blocks per channel: channel c's samples are in1 + c*in_stride (nblocks*vsize floats), same for in2
+ * and out.  Write wp0 for the write point when the call starts, and x_c[tau] for sample tau >= 0 of channel c's in1 row,
+ * for -irsize <= tau < 0 the delay ring's content at index (wp0 + tau) mod end.
+ * Static form (in2 == NULL), 0 <= t < nblocks*vsize:
+ *     out_c[t] = sum_{k=0}^{irsize-1} coef_c[k] * x_c[t - 1 - k]
+ * (the one-sample delay is the reference's, cl_dconv.cpp:40-41).
+ * Time-varying form (in2 != NULL): output block j uses coef_c^(j)[k] in that sum: with last = (j+1)*vsize - 1 and
+ * tau' = last - ((last - (k - wp0)) mod end) (non-negative mod), coef_c^(j)[k] = in2_c[tau'] when tau' >= 0, else the
+ * coefficient ring's content at index k — the reference's ring write of in2 at the write point (cl_dconv.cpp:134-147)
+ * followed by its reads of coefs[irsize-1-h].
+ * State after the call: exactly what nblocks single-block calls leave — both rings hold the last `end` samples of in1
+ * (and of in2 in the two-input form) at indices (wp0 + tau) mod end, earlier content stays where fewer than `end`
+ * samples came, and wp = (wp0 + nblocks*vsize) mod end.  So single-block calls, block calls and push_ir mix freely.
+ * Static form: one kernel over (channel, tile of consecutive outputs of the whole call, tap segment) and a launch that
+ * files the samples in the rings, per sub-batch (responses longer than 4096 taps: the segments' partial sums go to a
+ * workspace and a third launch adds them).  Every output sums its taps in ascending k in chunks of 256 taps, the chunks'
+ * sums in ascending order, then the segments' in ascending order: results are bit-identical however a signal is split
+ * into calls and sub-batches, and across repeated calls, streams and graph replay; against the single-block kernel of
+ * a one-channel object (k_dconv_block, another order) they agree to rounding.
+ * Time-varying form: the "loop" route — per block and per channel one launch of the single-block kernel, serial on the
+ * stream.  It is correct and it is not fast (nblocks x channels launches).
+ * Arguments: nblocks == 0 succeeds and does nothing; in_stride >= nblocks*vsize and out_stride >= nblocks*vsize;
+ * addresses 4-byte aligned, any stride.  out overlapping an input even partly, or any other bad argument:
+ * CLFA_INVALID_VALUE, and the state is untouched.  Streams, the current device and hipGraph capture work as for
+ * clfa_dconv_process_dev.  Workspace (segmented static route only): allocated by the first call that needs it
+ * (clfa_dconv_blocks_workspace_bytes() = what is held), released with the object; a call under capture that would have to
+ * allocate it returns CLFA_INVALID_OPERATION.  Long calls of segmented responses run in sub-batches of an internal cap. */
+CLFA_API int clfa_dconv_process_blocks_dev(clfa_dconv *dc, void *out, long out_stride, const void *in1, const void *in2,
+                                           long in_stride, long nblocks, void *stream);
+/* host form: rows contiguous (stride nblocks*vsize), blocking */
+CLFA_API int clfa_dconv_convolution_blocks(clfa_dconv *dc, float *out, const float *in1, const float *in2, long nblocks);
+/* diagnostics: channels, the write point, bytes of the rings, bytes of the block calls' workspace, and the route of a
+ * block call: "k_dconvb_fir" (static form) or "loop" (time_varying != 0) */
+CLFA_API int clfa_dconv_channels(const clfa_dconv *dc);
+CLFA_API int clfa_dconv_wp(const clfa_dconv *dc);
+CLFA_API size_t clfa_dconv_state_bytes(const clfa_dconv *dc);
+CLFA_API size_t clfa_dconv_blocks_workspace_bytes(const clfa_dconv *dc);
+CLFA_API const char *clfa_dconv_blocks_kernel_name(const clfa_dconv *dc, int time_varying);
 
 /* ---- short-time transforms (extension: nothing of the reference's) ----------- */
 /* A plan has size = 2^k, 64 <= size <= 16384 (the packed real sizes whose transform runs in one workgroup), a hop

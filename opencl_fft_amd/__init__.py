@@ -607,12 +607,13 @@ class PconvMatrix:
 
 
 class Cldconv:
-    """cl_conv::Cldconv(device_id, cvs, vsize, errs=NULL, uData=NULL) (cl_dconv.h:17-66)"""
+    """cl_conv::Cldconv(device_id, cvs, vsize, errs=NULL, uData=NULL) (cl_dconv.h:17-66); channels > 1 (extension): that
+    many independent instances in one object, blocks of float32[channels, vsize]"""
 
-    def __init__(self, device_id, cvs, vsize, errs=None, uData=None):
-        self.irsize, self.vsize = int(cvs), int(vsize)
+    def __init__(self, device_id, cvs, vsize, errs=None, uData=None, channels=1):
+        self.irsize, self.vsize, self.channels = int(cvs), int(vsize), int(channels)
         h = C.c_void_p()
-        e = lib().clfa_dconv_create(C.byref(h), int(device_id), int(cvs), int(vsize))
+        e = lib().clfa_dconv_create_channels(C.byref(h), int(device_id), int(cvs), int(vsize), int(channels))
         self._h = h
         if e != CL_SUCCESS:
             msg = cl_error_string(e)
@@ -632,32 +633,111 @@ class Cldconv:
     def get_cl_err(self):
         return lib().clfa_dconv_get_error(self._h)
 
+    wp = property(lambda s: lib().clfa_dconv_wp(s._h))
+
+    def state_bytes(self):
+        return lib().clfa_dconv_state_bytes(self._h)
+
     def push_ir(self, ir):
-        """cl_dconv.cpp:150-153"""
-        ir = np.ascontiguousarray(ir, dtype=np.float32)
+        """cl_dconv.cpp:150-153; channels > 1: float32 (channels, >= irsize)"""
+        ir = np.asarray(ir, dtype=np.float32)
+        if self.channels > 1:
+            if ir.ndim != 2 or ir.shape[0] != self.channels or ir.shape[1] < self.irsize:
+                return CL_INVALID_VALUE
+            ir = np.ascontiguousarray(ir[:, :self.irsize])
+            return lib().clfa_dconv_push_ir(self._h, ir.ctypes.data)
+        ir = np.ascontiguousarray(ir)
         if ir.size < self.irsize:
             return CL_INVALID_VALUE
         return lib().clfa_dconv_push_ir(self._h, ir.ctypes.data)
 
+    def push_ir_device(self, ir, stream=None):
+        """ir: device tensor (channels, >= irsize) of float32 (1-D for one channel), rows contiguous; asynchronous on
+        `stream`"""
+        shape, strides = tuple(ir.shape), tuple(ir.stride())
+        if ir.dim() == 1:
+            shape, strides = (1,) + shape, (shape[0],) + strides
+        if (len(shape) != 2 or shape[0] != self.channels or shape[1] < self.irsize or (shape[1] > 1 and strides[1] != 1)
+                or (shape[0] > 1 and strides[0] < self.irsize) or str(ir.dtype) != "torch.float32"):
+            return CL_INVALID_VALUE
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream(ir.device).cuda_stream
+        return lib().clfa_dconv_push_ir_dev(self._h, ir.data_ptr(), max(strides[0], self.irsize), stream)
+
     def convolution(self, out, in1, in2=None):
-        """cl_dconv.cpp:109-148"""
+        """cl_dconv.cpp:109-148; float32[channels, vsize]"""
         out = _host(out, np.float32)
         a = np.ascontiguousarray(in1, dtype=np.float32)
-        if out.size != self.vsize or a.size != self.vsize:
+        n = self.vsize * self.channels
+        if out.size != n or a.size != n:
             return CL_INVALID_VALUE
         if in2 is None:
             return lib().clfa_dconv_convolution(self._h, out.ctypes.data, a.ctypes.data)
         b = np.ascontiguousarray(in2, dtype=np.float32)
-        if b.size != self.vsize:
+        if b.size != n:
             return CL_INVALID_VALUE
         return lib().clfa_dconv_convolution_tv(self._h, out.ctypes.data, a.ctypes.data, b.ctypes.data)
 
     def process_device(self, out, in1, in2=None, stream=None):
-        """device-resident block (extension): vsize float32 each, asynchronous on `stream`; out must not be an input"""
+        """device-resident block (extension): channels x vsize float32 each, asynchronous on `stream`; out must not
+        overlap an input"""
+        n = self.vsize * self.channels
         for t in (out, in1) + ((in2,) if in2 is not None else ()):
-            if hasattr(t, "numel") and (t.numel() != self.vsize or not t.is_contiguous() or str(t.dtype) != "torch.float32"):
+            if hasattr(t, "numel") and (t.numel() != n or not t.is_contiguous() or str(t.dtype) != "torch.float32"):
                 return CL_INVALID_VALUE
         po, stream = _ptr_stream(out, stream)
         p1, _ = _ptr_stream(in1, stream)
         p2 = _ptr_stream(in2, stream)[0] if in2 is not None else None
         return lib().clfa_dconv_process_dev(self._h, po, p1, p2, stream)
+
+    # ---- many blocks per call (extension): clfa_dconv_process_blocks_dev, include/clfft_amd.h
+    def blocks_kernel_name(self, time_varying=False):
+        """"k_dconvb_fir" (static form) or "loop" (two inputs: the single-block kernel once per block and channel)"""
+        return lib().clfa_dconv_blocks_kernel_name(self._h, int(bool(time_varying))).decode()
+
+    def blocks_workspace_bytes(self):
+        return lib().clfa_dconv_blocks_workspace_bytes(self._h)
+
+    def convolution_blocks(self, output, input1, input2=None):
+        """whole signals: float32[channels, nblocks*vsize] (or 1-D for one channel); equals nblocks calls of
+        convolution(), blocking"""
+        output = _host(output, np.float32)
+        a = np.ascontiguousarray(input1, dtype=np.float32)
+        if a.ndim == 1:
+            a = a[None, :]
+        if a.ndim != 2 or a.shape[0] != self.channels or a.shape[1] % self.vsize or output.size != a.size:
+            return CL_INVALID_VALUE
+        b = None
+        if input2 is not None:
+            b = np.ascontiguousarray(input2, dtype=np.float32)
+            if b.size != a.size:
+                return CL_INVALID_VALUE
+        return lib().clfa_dconv_convolution_blocks(self._h, output.ctypes.data, a.ctypes.data,
+                                                   None if b is None else b.ctypes.data, a.shape[1] // self.vsize)
+
+    def process_blocks_device(self, out, in1, in2=None, stream=None):
+        """device tensors (channels, L) of float32 (1-D for one channel), stride(1) == 1, L % vsize == 0; the row stride
+        of each is its stride(0) (views into longer rows are fine).  Asynchronous on `stream`."""
+        def rows(t):
+            if t.dim() == 1:
+                return t.shape[0], max(t.shape[0], 1)
+            if t.dim() != 2 or t.shape[0] != self.channels or (t.shape[1] > 1 and t.stride(1) != 1):
+                raise ValueError("expected a (channels, L) float32 tensor with stride(1) == 1")
+            return t.shape[1], t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+        ts = [out, in1] + ([in2] if in2 is not None else [])
+        for t in ts:
+            if str(t.dtype) != "torch.float32" or (t.dim() == 1 and self.channels != 1):
+                raise ValueError("expected a (channels, L) float32 tensor with stride(1) == 1")
+        (lo, so), (l1, s1) = rows(out), rows(in1)
+        s2 = rows(in2)[1] if in2 is not None else s1
+        if lo != l1 or (in2 is not None and rows(in2)[0] != l1) or l1 % self.vsize:
+            return CL_INVALID_VALUE
+        if in2 is not None and s2 != s1:
+            return CL_INVALID_VALUE   # one stride for both inputs (the ABI's in_stride)
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream(in1.device).cuda_stream
+        return lib().clfa_dconv_process_blocks_dev(self._h, out.data_ptr(), so, in1.data_ptr(),
+                                                   in2.data_ptr() if in2 is not None else None, s1,
+                                                   l1 // self.vsize, stream)

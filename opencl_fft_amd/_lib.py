@@ -84,6 +84,15 @@ SYMBOLS = [
     ("clfa_dconv_convolution", C.c_int, [_vp, _vp, _vp]),
     ("clfa_dconv_convolution_tv", C.c_int, [_vp, _vp, _vp, _vp]),
     ("clfa_dconv_process_dev", C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    ("clfa_dconv_create_channels", C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.c_int, C.c_int]),
+    ("clfa_dconv_push_ir_dev", C.c_int, [_vp, _vp, C.c_long, _vp]),
+    ("clfa_dconv_process_blocks_dev", C.c_int, [_vp, _vp, C.c_long, _vp, _vp, C.c_long, C.c_long, _vp]),
+    ("clfa_dconv_convolution_blocks", C.c_int, [_vp, _vp, _vp, _vp, C.c_long]),
+    ("clfa_dconv_channels", C.c_int, [_vp]),
+    ("clfa_dconv_wp", C.c_int, [_vp]),
+    ("clfa_dconv_state_bytes", C.c_size_t, [_vp]),
+    ("clfa_dconv_blocks_workspace_bytes", C.c_size_t, [_vp]),
+    ("clfa_dconv_blocks_kernel_name", C.c_char_p, [_vp, C.c_int]),
     ("clfa_stft_create", C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.c_int, _vp, C.c_int]),
     ("clfa_stft_destroy", None, [_vp]),
     ("clfa_stft_get_error", C.c_int, [_vp]),

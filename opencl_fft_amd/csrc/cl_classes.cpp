@@ -94,6 +94,11 @@ Cldconv::Cldconv(cl_device_id device_id, int cvs, int vsiz, void (*errs)(std::st
   cl_err = clfa_dconv_create(&dc, clfa_device_ordinal(device_id), cvs, vsiz);
   if (cl_err != CL_SUCCESS) err(cl_error_string(cl_err), userData);
 }
+Cldconv::Cldconv(cl_device_id device_id, int cvs, int vsiz, int channels, void (*errs)(std::string s, void *d), void *uData)
+    : irsize(cvs), vsize(vsiz), dc(NULL), err(errs == NULL ? this->msg : errs), userData(uData), cl_err(CL_SUCCESS) {
+  cl_err = clfa_dconv_create_channels(&dc, clfa_device_ordinal(device_id), cvs, vsiz, channels);
+  if (cl_err != CL_SUCCESS) err(cl_error_string(cl_err), userData);
+}
 Cldconv::~Cldconv() { clfa_dconv_destroy(dc); }
 int Cldconv::push_ir(float *ir) { return clfa_dconv_push_ir(dc, ir); }
 int Cldconv::convolution(float *out, float *in) {
@@ -109,4 +114,15 @@ int Cldconv::convolution(float *out, float *in1, float *in2) {
 int Cldconv::convolution_device(void *out, const void *in1, const void *in2, void *stream) {
   return cl_err = clfa_dconv_process_dev(dc, out, in1, in2, stream);
 }
+int Cldconv::push_ir_device(const void *ir, long channel_stride, void *stream) {
+  return cl_err = clfa_dconv_push_ir_dev(dc, ir, channel_stride, stream);
+}
+int Cldconv::convolution_blocks(float *out, float *in1, float *in2, long nblocks) {
+  return cl_err = clfa_dconv_convolution_blocks(dc, out, in1, in2, nblocks);
+}
+int Cldconv::convolution_blocks_device(void *out, long out_stride, const void *in1, const void *in2, long in_stride,
+                                       long nblocks, void *stream) {
+  return cl_err = clfa_dconv_process_blocks_dev(dc, out, out_stride, in1, in2, in_stride, nblocks, stream);
+}
+const char *Cldconv::blocks_kernel_name(bool time_varying) { return clfa_dconv_blocks_kernel_name(dc, time_varying); }
 }  // namespace cl_conv

@@ -427,27 +427,42 @@ int clfa_pconv_convolution_blocks(clfa_pconv *p, float *out, const float *in1, c
 
 struct clfa_dconv {
   DeviceInfo di;
-  int irsize = 0, vsize = 0, wp = 0;
+  int irsize = 0, vsize = 0, wp = 0, channels = 1;
   int err = 0;
   hipStream_t stream = nullptr;
-  DevBuf del, coefs;
+  DevBuf del, coefs;   // channels rings of irsize + vsize floats each; one wp for all of them
   Staging io;          // staging of the host entry points' blocks (allocated at creation)
   ZeroCopy zc;         // ... zero-copy staging for small blocks (mapped pinned host memory)
   DevBuf part, cnt;    // partial sums per tap chunk and their arrival counter (plan.G > 1)
   DconvPlan plan{64, 1, 1};
   StreamOrder order;
+  // many blocks per call (clfa_dconv_process_blocks_dev)
+  DconvBlocksPlan bplan;   // tap segments, fixed at creation
+  int bcap = 1;            // blocks per sub-batch (CLFA_DCONV_BLOCKS_MAX: tuning switch, read at creation)
+  DevBuf bpart;            // the segments' partial sums (bplan.segs > 1): allocated by the first call that needs them
+  DevBuf ir;               // staging of push_ir (channels > 1)
 };
 
-static int dconv_setup(clfa_dconv *d, int device, int irsize, int vsize) {
+static int dconv_setup(clfa_dconv *d, int device, int irsize, int vsize, int channels) {
   d->irsize = irsize;
   d->vsize = vsize;
-  if (irsize < 1 || vsize < 1 || (long)irsize * vsize > 0x7fffffffL) return CLFA_INVALID_VALUE;
+  d->channels = channels;
+  if (irsize < 1 || vsize < 1 || (long)irsize * vsize > 0x7fffffffL || channels < 1 || channels > 65535) return CLFA_INVALID_VALUE;
   int e = device_info(device, d->di);
   if (e) return e;
   ENTER_DEVICE(device);
   HIP_TRY(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
-  const size_t ring = sizeof(float) * ((size_t)irsize + vsize), blk = sizeof(float) * (size_t)vsize;
+  const size_t ring = sizeof(float) * ((size_t)irsize + vsize) * (size_t)channels, blk = sizeof(float) * (size_t)vsize;
   d->plan = dconv_plan(irsize, vsize);
+  d->bplan = dconv_blocks_plan(irsize);
+  // (CLFA_DCONV_BLOCKS_MAX is read per object, like CLFA_PCONV_MATRIX_BLOCKS_MAX)
+  // sub-batches bound the segments' workspace; an unsegmented response has none, and its calls are cut only by the switch
+  d->bcap = subbatch_cap((long)d->bplan.segs * channels * vsize * (long)sizeof(float), "CLFA_DCONV_BLOCKS_MAX");
+  const char *cap_env = getenv("CLFA_DCONV_BLOCKS_MAX");
+  if (d->bplan.segs == 1 && !(cap_env && atol(cap_env) > 0)) d->bcap = 0x7fffffff;
+  if (const char *env = getenv("CLFA_DCONV_BLOCKS_R")) {   // tuning switch, read per object: outputs per lane, 2 or 8
+    if (atoi(env) == 2 || atoi(env) == 8) d->bplan.force_r = atoi(env);
+  }
   if ((e = d->del.ensure(ring)) || (e = d->coefs.ensure(ring)) || (e = d->io.out.ensure(blk)) || (e = d->io.in1.ensure(blk)) ||
       (e = d->io.in2.ensure(blk)) || (e = d->part.ensure(blk * d->plan.G)) ||
       (e = d->cnt.ensure(sizeof(unsigned) * d->plan.VB)))
@@ -485,33 +500,138 @@ static int dconv_host(clfa_dconv *d, float *out, const float *in1, const float *
 
 extern "C" {
 
+int clfa_dconv_create_channels(clfa_dconv **dc, int device, int irsize, int vsize, int channels) {
+  return create_object(dc, [&](clfa_dconv *d) { return dconv_setup(d, device, irsize, vsize, channels); });
+}
+
 int clfa_dconv_create(clfa_dconv **dc, int device, int irsize, int vsize) {
-  return create_object(dc, [&](clfa_dconv *d) { return dconv_setup(d, device, irsize, vsize); });
+  return clfa_dconv_create_channels(dc, device, irsize, vsize, 1);
 }
 
 void clfa_dconv_destroy(clfa_dconv *d) { destroy_object(d); }
 
 int clfa_dconv_get_error(const clfa_dconv *d) { return d ? d->err : CLFA_INVALID_VALUE; }
+int clfa_dconv_channels(const clfa_dconv *d) { return d ? d->channels : 0; }
+int clfa_dconv_wp(const clfa_dconv *d) { return d ? d->wp : -1; }
+size_t clfa_dconv_state_bytes(const clfa_dconv *d) { return d ? d->del.bytes + d->coefs.bytes : 0; }
+size_t clfa_dconv_blocks_workspace_bytes(const clfa_dconv *d) { return d ? d->bpart.bytes : 0; }
+const char *clfa_dconv_blocks_kernel_name(const clfa_dconv *d, int time_varying) {
+  if (!d || d->err) return "";
+  return time_varying ? "loop" : "k_dconvb_fir";
+}
+
+int clfa_dconv_push_ir_dev(clfa_dconv *d, const void *ir, long channel_stride, void *stream) {
+  if (int e = obj_error(d)) return e;
+  if (!ir || channel_stride < d->irsize || ((uintptr_t)ir & 3)) return CLFA_INVALID_VALUE;
+  ENTER_DEVICE(d->di.device);
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(d->order.use(s));
+  // row c -> the first irsize floats of channel c's coefficient ring
+  HIP_TRY(hipMemcpy2DAsync(d->coefs.p, sizeof(float) * ((size_t)d->irsize + d->vsize), ir, sizeof(float) * (size_t)channel_stride,
+                           sizeof(float) * (size_t)d->irsize, (size_t)d->channels, hipMemcpyDeviceToDevice, s));
+  return CLFA_SUCCESS;
+}
 
 int clfa_dconv_push_ir(clfa_dconv *d, const float *ir) {
   if (int e = obj_error(d)) return e;
   if (!ir) return CLFA_INVALID_VALUE;
   ENTER_DEVICE(d->di.device);
+  if (d->channels > 1) {
+    const size_t bytes = sizeof(float) * (size_t)d->channels * d->irsize;
+    int e = d->ir.ensure(bytes);
+    if (e) return e;
+    HIP_TRY(d->order.use(d->stream));
+    HIP_TRY(hipMemcpyAsync(d->ir.p, ir, bytes, hipMemcpyHostToDevice, d->stream));
+    if ((e = clfa_dconv_push_ir_dev(d, d->ir.p, d->irsize, d->stream))) return e;
+    HIP_TRY(hipStreamSynchronize(d->stream));
+    return CLFA_SUCCESS;
+  }
   HIP_TRY(d->order.use(d->stream));
   HIP_TRY(hipMemcpyAsync(d->coefs.p, ir, sizeof(float) * d->irsize, hipMemcpyHostToDevice, d->stream));
   HIP_TRY(hipStreamSynchronize(d->stream));
   return CLFA_SUCCESS;
 }
 
-int clfa_dconv_convolution(clfa_dconv *d, float *out, const float *in) { return dconv_host(d, out, in, nullptr); }
+int clfa_dconv_process_blocks_dev(clfa_dconv *d, void *out, long out_stride, const void *in1, const void *in2, long in_stride,
+                                  long nblocks, void *stream) {
+  if (int e = obj_error(d)) return e;
+  const long vs = d->vsize, ch = d->channels, end = (long)d->irsize + d->vsize;
+  long len;
+  if (int e = check_blocks_dev(nblocks, vs, out, out_stride, ch, in1, in2, in_stride, ch, &len)) return e;
+  if (!len) return CLFA_SUCCESS;
+  ENTER_DEVICE(d->di.device);
+  hipStream_t s = (hipStream_t)stream;
+  const float *a1 = (const float *)in1, *a2 = (const float *)in2;
+  float *o = (float *)out;
+  if (a2) {
+    // "loop": per block and channel one launch of k_dconv_block on that channel's rings.  The launches are serial on s, so
+    // the one part / cnt pair serves every channel.  Correct, not fast.
+    HIP_TRY(d->order.use(s));
+    for (long j = 0; j < nblocks; j++) {
+      for (long c = 0; c < ch; c++)
+        HIP_TRY(launch_dconv_block(d->plan, o + c * out_stride + j * vs, a1 + c * in_stride + j * vs, a2 + c * in_stride + j * vs,
+                                   (float *)d->del.p + c * end, (float *)d->coefs.p + c * end, (float *)d->part.p,
+                                   (unsigned *)d->cnt.p, d->irsize, d->vsize, d->wp, d->di.num_cus, s));
+      d->wp = (int)((d->wp + vs) % end);
+    }
+    return CLFA_SUCCESS;
+  }
+  const long kmax = nblocks < d->bcap ? nblocks : d->bcap;
+  const long part_stride = kmax * vs;
+  if (int e = ensure_workspaces({{&d->bpart, d->bplan.segs > 1 ? sizeof(float) * (size_t)d->bplan.segs * ch * part_stride : 0}}, s))
+    return e;
+  HIP_TRY(d->order.use(s));
+  DconvBlocksArgs a;
+  a.plan = d->bplan;
+  a.irsize = d->irsize;
+  a.end = (int)end;
+  a.channels = (int)ch;
+  a.in_stride = in_stride;
+  a.out_stride = out_stride;
+  a.del = (float *)d->del.p;
+  a.coefs = (const float *)d->coefs.p;
+  a.part = (float *)d->bpart.p;
+  a.part_stride = part_stride;
+  for (long j0 = 0; j0 < nblocks; j0 += kmax) {
+    const long k = nblocks - j0 < kmax ? nblocks - j0 : kmax;
+    a.L = k * vs;
+    a.wp = d->wp;
+    a.in1 = a1 + j0 * vs;
+    a.out = o + j0 * vs;
+    HIP_TRY(launch_dconv_blocks(a, d->di, s));
+    d->wp = (int)((d->wp + a.L) % end);
+  }
+  return CLFA_SUCCESS;
+}
+
+int clfa_dconv_convolution_blocks(clfa_dconv *d, float *out, const float *in1, const float *in2, long nblocks) {
+  if (int e = obj_error(d)) return e;
+  long len;
+  if (int e = blocks_len(nblocks, d->vsize, out, in1, &len)) return e;
+  if (!len) return CLFA_SUCCESS;
+  const size_t bytes = sizeof(float) * (size_t)len * d->channels;
+  if (spans_overlap(out, bytes, in1, bytes) || (in2 && spans_overlap(out, bytes, in2, bytes))) return CLFA_INVALID_VALUE;
+  ENTER_DEVICE(d->di.device);
+  return staged_call(d->io, d->stream, out, bytes, in1, in2, bytes, [&](void *o, const void *i1, const void *i2) {
+    return clfa_dconv_process_blocks_dev(d, o, len, i1, i2, len, nblocks, d->stream);
+  });
+}
+
+// (several channels: one block of each, channels x vsize contiguous floats, is the block call with nblocks = 1)
+int clfa_dconv_convolution(clfa_dconv *d, float *out, const float *in) {
+  if (d && !d->err && d->channels > 1) return clfa_dconv_convolution_blocks(d, out, in, nullptr, 1);
+  return dconv_host(d, out, in, nullptr);
+}
 
 int clfa_dconv_convolution_tv(clfa_dconv *d, float *out, const float *in1, const float *in2) {
   if (d && !d->err && !in2) return CLFA_INVALID_VALUE;
+  if (d && !d->err && d->channels > 1) return clfa_dconv_convolution_blocks(d, out, in1, in2, 1);
   return dconv_host(d, out, in1, in2);
 }
 
 int clfa_dconv_process_dev(clfa_dconv *d, void *out, const void *in1, const void *in2, void *stream) {
   if (int e = obj_error(d)) return e;
+  if (d->channels > 1) return clfa_dconv_process_blocks_dev(d, out, d->vsize, in1, in2, d->vsize, 1, stream);
   if (!out || !in1) return CLFA_INVALID_VALUE;
   // the last-arriving workgroup writes out while others may still stage their in1 / in2 windows: no overlap at all
   const size_t blk = sizeof(float) * (size_t)d->vsize;
