@@ -115,7 +115,9 @@ CLFA_API int clfa_fft_host_alloc(clfa_fft *plan, size_t bytes, void **ptr);
 CLFA_API int clfa_fft_host_free(clfa_fft *plan, void *ptr);
 /* device-resident, in place, asynchronous on `stream`: the body of
  * Clcfft::fft() (cl_fft.cpp:138-151) / the kernel part of Clrfft::transform.
- * data: batch * n complex64 (c2c) or batch * size float32 (r2c, packed in place). */
+ * data: batch * n complex64 (c2c) or batch * size float32 (r2c, packed in place).  data (and src / dst below) must be
+ * 8-byte aligned, for real plans too: the kernels move complex64 values, and real samples in pairs, as 8-byte words;
+ * 16 bytes are not required. */
 CLFA_API int clfa_fft_exec_dev(clfa_fft *plan, void *data, long batch, void *stream);
 /* the same from `src` to `dst` (extension).  The reference's device side is itself out of place — its `reorder` gathers
  * data1 -> data2 and the stages then run on data2, cl_fft.cpp:138-151.  Every plan runs

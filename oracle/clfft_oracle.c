@@ -50,6 +50,12 @@ static inline cpx c_conj(cpx a) { cpx r = {a.x, -a.y}; return r; }
 static inline cpx c_rot(cpx a) { cpx r = {-a.y, a.x}; return r; }
 
 static int is_pow2(int n) { return n > 0 && (n & (n - 1)) == 0; }
+/* The stage kernel's `g * n2` (cl_fft.cpp:32, orc_fft_stage below) is an int product that reaches n^2 / 2: above n = 65536
+ * it overflows, the butterfly indices go negative and the stage writes outside the array.  The reference's range ends
+ * there, and so does this restatement: longer transforms are refused instead of corrupting the heap. */
+#define ORC_MAX_N 65536
+static int cfft_len_ok(int n) { return is_pow2(n) && n >= 2 && n <= ORC_MAX_N; }
+static int rfft_size_ok(int size) { return is_pow2(size) && size >= 4 && size / 2 <= ORC_MAX_N; }
 
 /* ---- tables ------------------------------------------------------------ */
 
@@ -193,7 +199,7 @@ static void cplan_exec(cplan *p, float *data, int forward) {
 
 /* Clcfft::transform, cl_fft.cpp:153-161 */
 int orc_cfft(float *data, int n, int forward) {
-  if (!is_pow2(n) || n < 2) return -30; /* CL_INVALID_VALUE */
+  if (!cfft_len_ok(n)) return -30; /* CL_INVALID_VALUE */
   cplan p;
   int e = cplan_init(&p, n, forward);
   if (!e) cplan_exec(&p, data, forward);
@@ -215,7 +221,7 @@ static void rplan_exec(cplan *p, const float *w2, float *data, int forward) {
 }
 
 int orc_rfft(float *data, int size, int forward) {
-  if (!is_pow2(size) || size < 4) return -30;
+  if (!rfft_size_ok(size)) return -30;
   int m = size / 2;
   cplan p;
   int e = cplan_init(&p, m, forward);
@@ -240,7 +246,7 @@ int orc_num_threads(void) {
 /* B sequential transform() calls of the reference == one batched call here
  * (batch-major contiguous); batches spread over host threads. */
 int orc_cfft_batched(float *data, int n, long batch, int forward, int nthreads) {
-  if (!is_pow2(n) || n < 2) return -30;
+  if (!cfft_len_ok(n)) return -30;
   int err = 0;
 #ifdef _OPENMP
   if (nthreads <= 0) nthreads = omp_get_max_threads();
@@ -262,7 +268,7 @@ int orc_cfft_batched(float *data, int n, long batch, int forward, int nthreads) 
 }
 
 int orc_rfft_batched(float *data, int size, long batch, int forward, int nthreads) {
-  if (!is_pow2(size) || size < 4) return -30;
+  if (!rfft_size_ok(size)) return -30;
   int m = size / 2, err = 0;
 #ifdef _OPENMP
   if (nthreads <= 0) nthreads = omp_get_max_threads();

@@ -93,10 +93,20 @@ def reorder(x, b):
     return out
 
 
+MAX_CFFT = 65536      # ORC_MAX_N of clfft_oracle.c: the reference's stage index overflows int above it (cl_fft.cpp:32)
+
+
+def _check_len(n, lo, what):
+    if n < lo or n & (n - 1) or n > (MAX_CFFT if lo == 2 else 2 * MAX_CFFT):
+        raise ValueError("%s: length %d is outside the C oracle's range (powers of two, %d..%d)"
+                         % (what, n, lo, MAX_CFFT if lo == 2 else 2 * MAX_CFFT))
+
+
 def cfft(x, forward=True, nthreads=0):
     """Clcfft::transform (cl_fft.cpp:153-161) on the last axis; leading axes are batches."""
     x = np.array(x, dtype=np.complex64, order="C", copy=True)
     n = x.shape[-1]
+    _check_len(n, 2, "cfft")
     batch = x.size // n
     e = lib().orc_cfft_batched(_fp(x.view(np.float32)), n, batch, int(forward), nthreads)
     if e:
@@ -108,6 +118,7 @@ def rfft_forward(x, nthreads=0):
     """Clrfft::transform forward (cl_fft.cpp:272-282): real[..., size] -> packed complex64[..., size/2]"""
     x = np.array(x, dtype=np.float32, order="C", copy=True)
     size = x.shape[-1]
+    _check_len(size, 4, "rfft_forward")
     e = lib().orc_rfft_batched(_fp(x), size, x.size // size, 1, nthreads)
     if e:
         raise ValueError("orc_rfft_batched error %d" % e)
@@ -118,6 +129,7 @@ def rfft_inverse(c, nthreads=0):
     """Clrfft::transform inverse (cl_fft.cpp:283-294): packed complex64[..., M] -> real[..., 2M]"""
     c = np.array(c, dtype=np.complex64, order="C", copy=True)
     m = c.shape[-1]
+    _check_len(2 * m, 4, "rfft_inverse")
     r = c.view(np.float32)
     e = lib().orc_rfft_batched(_fp(r), 2 * m, c.size // m, 0, nthreads)
     if e:
