@@ -179,7 +179,8 @@ CLFA_API int clfa_pconv_convolution_tv(clfa_pconv *pc, float *out, const float *
 /* device-resident variants; in2 may be NULL (static IR).  `out` must not overlap an input, not even partly, on the one-launch
  * routes (clfa_pconv_kernel_name() = k_pconv_fused or k_pconv_coop: partitions up to 4096 samples), where workgroups of
  * other channels may still be reading: CL_INVALID_VALUE.  The launch chain of larger partitions reads every input before it
- * writes `out`; in place is accepted there. */
+ * writes `out`; in place is accepted there.  out, in1 and in2 are 8-byte aligned (the kernels move real samples in pairs,
+ * as for the real FFT plans above); 16 bytes are not required. */
 CLFA_API int clfa_pconv_process_dev(clfa_pconv *pc, void *out, const void *in1, const void *in2, void *stream);
 CLFA_API size_t clfa_pconv_state_bytes(const clfa_pconv *pc);
 /* which launch structure a block of this object takes (diagnostics and tests): "k_pconv_fused" (one launch, one
