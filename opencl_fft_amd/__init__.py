@@ -75,15 +75,20 @@ def r2c_twiddle_table(m, forward=True):
     return out.view(np.complex64)
 
 
+def _stream_of(tensor, stream):
+    """`stream` if it was given, else the HIP handle of the current torch stream on the tensor's device"""
+    if stream is None:
+        import torch
+        stream = torch.cuda.current_stream(tensor.device).cuda_stream
+    return stream
+
+
 def _ptr_stream(obj, stream):
     """(device pointer, hip stream handle) from a torch tensor or a raw int pointer"""
     if hasattr(obj, "data_ptr"):
         if not obj.is_contiguous():
             raise ValueError("device tensor must be contiguous")
-        if stream is None:
-            import torch
-            stream = torch.cuda.current_stream(obj.device).cuda_stream
-        return obj.data_ptr(), stream
+        return obj.data_ptr(), _stream_of(obj, stream)
     return int(obj), stream
 
 
@@ -100,13 +105,19 @@ def reorder_device(device, out, inp, n, batch, stream=None):
     return lib().clfa_reorder_dev(device, po, pi, n, batch, stream)
 
 
-class _Plan:
+class _Handle:
+    """owner of one object of the C ABI: `_h`, released with the function the subclass names in `_destroy`"""
     _h = None
+    _destroy = None
 
     def __del__(self):
         h, self._h = self._h, None
         if h and lib is not None:      # module globals are already gone at interpreter shutdown
-            lib().clfa_fft_destroy(h)
+            getattr(lib(), self._destroy)(h)
+
+
+class _Plan(_Handle):
+    _destroy = "clfa_fft_destroy"
 
     def get_error(self):
         """cl_fft.h:65"""
@@ -206,7 +217,7 @@ def _row_view(t, what):
     return t.data_ptr(), t.shape[0], t.shape[1], t.stride(0)
 
 
-class Stft:
+class Stft(_Handle):
     """Short-time transforms on the packed real layout of Clrfft (extension, clfa_stft in clfft_amd.h).
 
     fwd=True: analyze() frames (channels, samples) float32 rows (frame f = window * x[f*hop : f*hop + size], no
@@ -214,6 +225,7 @@ class Stft:
     fwd=False: synthesize() runs Clrfft(size, False) on every frame, multiplies by the window and overlap-adds the frames
     into rows of (F - 1) * hop + size floats, optionally divided by the window envelope sum_f w^2.
     Like the other plans the constructor does not raise: get_error() / get_log() report a failed setup."""
+    _destroy = "clfa_stft_destroy"
 
     def __init__(self, device_id, size, hop, window=None, fwd=True):
         self.size, self.hop, self.forward = int(size), int(hop), bool(fwd)
@@ -229,11 +241,6 @@ class Stft:
         lib().clfa_stft_create(C.byref(h), int(device_id), self.size, self.hop,
                                None if window is None else window.ctypes.data, int(self.forward))
         self._h = h
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h and lib is not None:
-            lib().clfa_stft_destroy(h)
 
     def get_error(self):
         return lib().clfa_stft_get_error(self._h)
@@ -283,10 +290,7 @@ class Stft:
         p, rows, n, stride = _row_view(signal, "signal")
         if not out.is_contiguous():
             raise ValueError("spectra tensor must be contiguous")
-        if stream is None:
-            import torch
-            stream = torch.cuda.current_stream(signal.device).cuda_stream
-        return lib().clfa_stft_analyze_dev(self._h, p, stride, n, rows, out.data_ptr(), stream)
+        return lib().clfa_stft_analyze_dev(self._h, p, stride, n, rows, out.data_ptr(), _stream_of(signal, stream))
 
     def synthesize_device(self, spectra, out, normalize=False, stream=None):
         """torch: spectra (channels, F, size/2) complex64, contiguous -> out (channels, >= (F - 1) * hop + size) float32,
@@ -297,11 +301,8 @@ class Stft:
         p, rows, _, stride = _row_view(out, "signal")
         if rows != s3.shape[0]:
             raise ValueError("out has %d rows for %d channels" % (rows, s3.shape[0]))
-        if stream is None:
-            import torch
-            stream = torch.cuda.current_stream(out.device).cuda_stream
         return lib().clfa_stft_synthesize_dev(self._h, spectra.data_ptr(), s3.shape[1], s3.shape[0], p, stride,
-                                              int(bool(normalize)), stream)
+                                              int(bool(normalize)), _stream_of(out, stream))
 
 
 def packed_to_onesided(spec):
@@ -346,26 +347,25 @@ def bandwidth_probe(device_id=0, nbytes=1 << 30, launches=100):
     return out
 
 
-class Clpconv:
-    """cl_conv::Clpconv(device_id, cvs, pts, errs=NULL, uData=NULL, ...) (cl_conv.h:124-188)
+def _block_rows(t, nrows, what, allow_1d):
+    """(row length, row stride) of a float32 device tensor of `nrows` rows whose samples are contiguous; a 1-D tensor
+    stands for one row where allow_1d.  The stride of a single row is never below its length."""
+    if str(t.dtype) == "torch.float32":
+        if t.dim() == 1 and allow_1d and nrows == 1:
+            return t.shape[0], max(t.shape[0], 1)
+        if t.dim() == 2 and t.shape[0] == nrows and (t.shape[1] <= 1 or t.stride(1) == 1):
+            return t.shape[1], t.stride(0) if nrows > 1 else max(t.stride(0), t.shape[1])
+    raise ValueError("expected a (%s, L) float32 tensor with stride(1) == 1" % what)
 
-    `channels` (extension) runs that many independent instances in one object;
-    arrays then carry a leading channel axis."""
 
-    def __init__(self, device_id, cvs, pts, errs=None, uData=None, channels=1):
-        self.pts = int(pts)
-        self.channels = int(channels)
-        self._errs, self._udata = errs, uData
-        h = C.c_void_p()
-        e = lib().clfa_pconv_create(C.byref(h), int(device_id), int(cvs), int(pts), int(channels))
-        self._h = h
-        if e != CL_SUCCESS:
-            self._report(e)
+class _BlockConv(_Handle):
+    """What Clpconv and Cldconv share: blocks of float32[channels, block length] through the C ABI functions
+    `_abi` + name, the block length being the attribute `_block` names (pts / vsize)."""
+    _abi = None
+    _block = None
 
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h and lib is not None:
-            lib().clfa_pconv_destroy(h)
+    def _fn(self, name):
+        return getattr(lib(), self._abi + name)
 
     def _report(self, e):
         # error callback by value, default prints unless user data is given (cl_conv.h:142-145)
@@ -377,6 +377,75 @@ class Clpconv:
 
     def cl_error_string(self, err):
         return cl_error_string(err)
+
+    def convolution(self, output, input1, input2=None):
+        """convolution(out, in) (cl_conv.cpp:393-458, cl_dconv.cpp:109-133) or the time-varying
+        convolution(out, in1, in2) (cl_conv.cpp:460-548, cl_dconv.cpp:134-148); float32[channels, block length]"""
+        output = _host(output, np.float32)
+        a = np.ascontiguousarray(input1, dtype=np.float32)
+        n = self.channels * getattr(self, self._block)
+        if output.size != n or a.size != n:
+            return CL_INVALID_VALUE
+        if input2 is None:
+            return self._fn("convolution")(self._h, output.ctypes.data, a.ctypes.data)
+        b = np.ascontiguousarray(input2, dtype=np.float32)
+        if b.size != n:
+            return CL_INVALID_VALUE
+        return self._fn("convolution_tv")(self._h, output.ctypes.data, a.ctypes.data, b.ctypes.data)
+
+    # ---- many blocks per call (extension): clfa_pconv_ / clfa_dconv_process_blocks_dev, include/clfft_amd.h
+    def blocks_workspace_bytes(self):
+        return self._fn("blocks_workspace_bytes")(self._h)
+
+    def convolution_blocks(self, output, input1, input2=None):
+        """whole signals: float32[channels, nblocks * block length] (or 1-D for one channel); equals nblocks calls of
+        convolution(), blocking"""
+        blk = getattr(self, self._block)
+        output = _host(output, np.float32)
+        a = np.ascontiguousarray(input1, dtype=np.float32)
+        if a.ndim == 1:
+            a = a[None, :]
+        if a.ndim != 2 or a.shape[0] != self.channels or a.shape[1] % blk or output.size != a.size:
+            return CL_INVALID_VALUE
+        b = None
+        if input2 is not None:
+            b = np.ascontiguousarray(input2, dtype=np.float32)
+            if b.size != a.size:
+                return CL_INVALID_VALUE
+        return self._fn("convolution_blocks")(self._h, output.ctypes.data, a.ctypes.data,
+                                              None if b is None else b.ctypes.data, a.shape[1] // blk)
+
+    def process_blocks_device(self, out, in1, in2=None, stream=None):
+        """device tensors (channels, L) of float32 (1-D for one channel), stride(1) == 1, L a multiple of the block
+        length; the row stride of each is its stride(0) (views into longer rows are fine).  Asynchronous on `stream`."""
+        blk = getattr(self, self._block)
+        (lo, so), (l1, s1) = (_block_rows(t, self.channels, "channels", True) for t in (out, in1))
+        l2, s2 = _block_rows(in2, self.channels, "channels", True) if in2 is not None else (l1, s1)
+        if lo != l1 or l2 != l1 or l1 % blk:
+            return CL_INVALID_VALUE
+        if s2 != s1:
+            return CL_INVALID_VALUE   # one stride for both inputs (the ABI's in_stride)
+        return self._fn("process_blocks_dev")(self._h, out.data_ptr(), so, in1.data_ptr(),
+                                              in2.data_ptr() if in2 is not None else None, s1, l1 // blk,
+                                              _stream_of(in1, stream))
+
+
+class Clpconv(_BlockConv):
+    """cl_conv::Clpconv(device_id, cvs, pts, errs=NULL, uData=NULL, ...) (cl_conv.h:124-188)
+
+    `channels` (extension) runs that many independent instances in one object;
+    arrays then carry a leading channel axis."""
+    _destroy, _abi, _block = "clfa_pconv_destroy", "clfa_pconv_", "pts"
+
+    def __init__(self, device_id, cvs, pts, errs=None, uData=None, channels=1):
+        self.pts = int(pts)
+        self.channels = int(channels)
+        self._errs, self._udata = errs, uData
+        h = C.c_void_p()
+        e = lib().clfa_pconv_create(C.byref(h), int(device_id), int(cvs), int(pts), int(channels))
+        self._h = h
+        if e != CL_SUCCESS:
+            self._report(e)
 
     def get_cl_err(self):
         """cl_conv.h:187"""
@@ -403,21 +472,6 @@ class Clpconv:
         ir = np.ascontiguousarray(ir[:, :need])
         return lib().clfa_pconv_push_ir(self._h, ir.ctypes.data)
 
-    def convolution(self, output, input1, input2=None):
-        """convolution(out, in) (cl_conv.cpp:393-458) or the time-varying
-        convolution(out, in1, in2) (cl_conv.cpp:460-548); float32[channels, pts]"""
-        output = _host(output, np.float32)
-        a = np.ascontiguousarray(input1, dtype=np.float32)
-        n = self.channels * self.pts
-        if output.size != n or a.size != n:
-            return CL_INVALID_VALUE
-        if input2 is None:
-            return lib().clfa_pconv_convolution(self._h, output.ctypes.data, a.ctypes.data)
-        b = np.ascontiguousarray(input2, dtype=np.float32)
-        if b.size != n:
-            return CL_INVALID_VALUE
-        return lib().clfa_pconv_convolution_tv(self._h, output.ctypes.data, a.ctypes.data, b.ctypes.data)
-
     def push_ir_device(self, ir, stream=None):
         """ir: device tensor (channels, >= nparts*pts) of float32, rows contiguous; a (channels, cvs)
         tensor with cvs not a multiple of pts is fine (the remainder of every row is ignored, like the
@@ -438,75 +492,24 @@ class Clpconv:
         p2 = _ptr_stream(in2, stream)[0] if in2 is not None else None
         return lib().clfa_pconv_process_dev(self._h, po, p1, p2, stream)
 
-    # ---- many blocks per call (extension): clfa_pconv_process_blocks_dev, include/clfft_amd.h
     def blocks_kernel_name(self):
         """"k_pconvb_mac" (partitions of 32..4096 samples) or "loop" (the single-block route once per block)"""
         return lib().clfa_pconv_blocks_kernel_name(self._h).decode()
 
-    def blocks_workspace_bytes(self):
-        return lib().clfa_pconv_blocks_workspace_bytes(self._h)
 
-    def convolution_blocks(self, output, input1, input2=None):
-        """whole signals: float32[channels, nblocks*pts] (or 1-D for one channel); equals nblocks calls of
-        convolution(), blocking"""
-        output = _host(output, np.float32)
-        a = np.ascontiguousarray(input1, dtype=np.float32)
-        if a.ndim == 1:
-            a = a[None, :]
-        if a.ndim != 2 or a.shape[0] != self.channels or a.shape[1] % self.pts or output.size != a.size:
-            return CL_INVALID_VALUE
-        b = None
-        if input2 is not None:
-            b = np.ascontiguousarray(input2, dtype=np.float32)
-            if b.size != a.size:
-                return CL_INVALID_VALUE
-        return lib().clfa_pconv_convolution_blocks(self._h, output.ctypes.data, a.ctypes.data,
-                                                   None if b is None else b.ctypes.data, a.shape[1] // self.pts)
-
-    def process_blocks_device(self, out, in1, in2=None, stream=None):
-        """device tensors (channels, L) of float32 (1-D for one channel), stride(1) == 1, L % pts == 0; the row stride
-        of each is its stride(0) (views into longer rows are fine).  Asynchronous on `stream`."""
-        def rows(t):
-            if t.dim() == 1:
-                return t.shape[0], max(t.shape[0], 1)
-            if t.dim() != 2 or t.shape[0] != self.channels or (t.shape[1] > 1 and t.stride(1) != 1):
-                raise ValueError("expected a (channels, L) float32 tensor with stride(1) == 1")
-            return t.shape[1], t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
-        ts = [out, in1] + ([in2] if in2 is not None else [])
-        for t in ts:
-            if str(t.dtype) != "torch.float32" or (t.dim() == 1 and self.channels != 1):
-                raise ValueError("expected a (channels, L) float32 tensor with stride(1) == 1")
-        (lo, so), (l1, s1) = rows(out), rows(in1)
-        s2 = rows(in2)[1] if in2 is not None else s1
-        if lo != l1 or (in2 is not None and rows(in2)[0] != l1) or l1 % self.pts:
-            return CL_INVALID_VALUE
-        if in2 is not None and s2 != s1:
-            return CL_INVALID_VALUE   # one stride for both inputs (the ABI's in_stride)
-        if stream is None:
-            import torch
-            stream = torch.cuda.current_stream(in1.device).cuda_stream
-        return lib().clfa_pconv_process_blocks_dev(self._h, out.data_ptr(), so, in1.data_ptr(),
-                                                   in2.data_ptr() if in2 is not None else None, s1,
-                                                   l1 // self.pts, stream)
-
-
-class PconvMatrix:
+class PconvMatrix(_Handle):
     """Convolution matrix (extension, clfa_pconv_matrix in clfft_amd.h): `inputs` signals mixed into `outputs` signals,
     y_o = sum_i x_i * h_{o,i}, by uniformly partitioned overlap-add convolution with static responses.  Block j of output
     o is the sum over i of what Clpconv(device_id, cvs, pts) holding h_{o,i} returns for block j of input i.  pts is a
     power of two, 32..4096.  Like the other objects the constructor does not raise: get_error() / get_log() report a
     failed setup."""
+    _destroy = "clfa_pconv_matrix_destroy"
 
     def __init__(self, device_id, cvs, pts, inputs, outputs):
         self.cvs, self.pts, self.inputs, self.outputs = int(cvs), int(pts), int(inputs), int(outputs)
         h = C.c_void_p()
         lib().clfa_pconv_matrix_create(C.byref(h), int(device_id), self.cvs, self.pts, self.inputs, self.outputs)
         self._h = h
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h and lib is not None:
-            lib().clfa_pconv_matrix_destroy(h)
 
     def get_error(self):
         return lib().clfa_pconv_matrix_get_error(self._h)
@@ -541,10 +544,7 @@ class PconvMatrix:
         rs = ir.stride(1) if self.inputs > 1 else (ir.stride(0) if self.outputs > 1 else max(ir.stride(1), need))
         if self.outputs > 1 and ir.stride(0) != self.inputs * rs:
             return None
-        if stream is None:
-            import torch
-            stream = torch.cuda.current_stream(ir.device).cuda_stream
-        return rs, stream
+        return rs, _stream_of(ir, stream)
 
     def push_ir(self, ir):
         """ir: float32 (outputs, inputs, >= nparts*pts), e.g. rows of cvs samples (the remainder is ignored)"""
@@ -593,42 +593,27 @@ class PconvMatrix:
     def process_device(self, out, x, stream=None):
         """device tensors: x (inputs, L), out (outputs, L) of float32, stride(1) == 1, L % pts == 0; the row stride of
         each is its stride(0) (views into longer rows are fine).  Asynchronous on `stream`."""
-        def rows(t, n):
-            if str(t.dtype) != "torch.float32" or t.dim() != 2 or t.shape[0] != n or (t.shape[1] > 1 and t.stride(1) != 1):
-                raise ValueError("expected a (%d, L) float32 tensor with stride(1) == 1" % n)
-            return t.shape[1], t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
-        (lo, so), (li, si) = rows(out, self.outputs), rows(x, self.inputs)
+        lo, so = _block_rows(out, self.outputs, self.outputs, False)
+        li, si = _block_rows(x, self.inputs, self.inputs, False)
         if lo != li or li % self.pts:
             return CL_INVALID_VALUE
-        if stream is None:
-            import torch
-            stream = torch.cuda.current_stream(x.device).cuda_stream
-        return lib().clfa_pconv_matrix_process_dev(self._h, out.data_ptr(), so, x.data_ptr(), si, li // self.pts, stream)
+        return lib().clfa_pconv_matrix_process_dev(self._h, out.data_ptr(), so, x.data_ptr(), si, li // self.pts,
+                                                   _stream_of(x, stream))
 
 
-class Cldconv:
+class Cldconv(_BlockConv):
     """cl_conv::Cldconv(device_id, cvs, vsize, errs=NULL, uData=NULL) (cl_dconv.h:17-66); channels > 1 (extension): that
     many independent instances in one object, blocks of float32[channels, vsize]"""
+    _destroy, _abi, _block = "clfa_dconv_destroy", "clfa_dconv_", "vsize"
 
     def __init__(self, device_id, cvs, vsize, errs=None, uData=None, channels=1):
         self.irsize, self.vsize, self.channels = int(cvs), int(vsize), int(channels)
+        self._errs, self._udata = errs, uData
         h = C.c_void_p()
         e = lib().clfa_dconv_create_channels(C.byref(h), int(device_id), int(cvs), int(vsize), int(channels))
         self._h = h
         if e != CL_SUCCESS:
-            msg = cl_error_string(e)
-            if errs is not None:
-                errs(msg, uData)
-            elif uData is None:
-                print(msg)
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h and lib is not None:
-            lib().clfa_dconv_destroy(h)
-
-    def cl_error_string(self, err):
-        return cl_error_string(err)
+            self._report(e)
 
     def get_cl_err(self):
         return lib().clfa_dconv_get_error(self._h)
@@ -660,24 +645,11 @@ class Cldconv:
         if (len(shape) != 2 or shape[0] != self.channels or shape[1] < self.irsize or (shape[1] > 1 and strides[1] != 1)
                 or (shape[0] > 1 and strides[0] < self.irsize) or str(ir.dtype) != "torch.float32"):
             return CL_INVALID_VALUE
-        if stream is None:
-            import torch
-            stream = torch.cuda.current_stream(ir.device).cuda_stream
-        return lib().clfa_dconv_push_ir_dev(self._h, ir.data_ptr(), max(strides[0], self.irsize), stream)
+        return lib().clfa_dconv_push_ir_dev(self._h, ir.data_ptr(), max(strides[0], self.irsize), _stream_of(ir, stream))
 
     def convolution(self, out, in1, in2=None):
         """cl_dconv.cpp:109-148; float32[channels, vsize]"""
-        out = _host(out, np.float32)
-        a = np.ascontiguousarray(in1, dtype=np.float32)
-        n = self.vsize * self.channels
-        if out.size != n or a.size != n:
-            return CL_INVALID_VALUE
-        if in2 is None:
-            return lib().clfa_dconv_convolution(self._h, out.ctypes.data, a.ctypes.data)
-        b = np.ascontiguousarray(in2, dtype=np.float32)
-        if b.size != n:
-            return CL_INVALID_VALUE
-        return lib().clfa_dconv_convolution_tv(self._h, out.ctypes.data, a.ctypes.data, b.ctypes.data)
+        return _BlockConv.convolution(self, out, in1, in2)   # (the reference's argument names, cl_dconv.h:59-61)
 
     def process_device(self, out, in1, in2=None, stream=None):
         """device-resident block (extension): channels x vsize float32 each, asynchronous on `stream`; out must not
@@ -691,53 +663,6 @@ class Cldconv:
         p2 = _ptr_stream(in2, stream)[0] if in2 is not None else None
         return lib().clfa_dconv_process_dev(self._h, po, p1, p2, stream)
 
-    # ---- many blocks per call (extension): clfa_dconv_process_blocks_dev, include/clfft_amd.h
     def blocks_kernel_name(self, time_varying=False):
         """"k_dconvb_fir" (static form) or "loop" (two inputs: the single-block kernel once per block and channel)"""
         return lib().clfa_dconv_blocks_kernel_name(self._h, int(bool(time_varying))).decode()
-
-    def blocks_workspace_bytes(self):
-        return lib().clfa_dconv_blocks_workspace_bytes(self._h)
-
-    def convolution_blocks(self, output, input1, input2=None):
-        """whole signals: float32[channels, nblocks*vsize] (or 1-D for one channel); equals nblocks calls of
-        convolution(), blocking"""
-        output = _host(output, np.float32)
-        a = np.ascontiguousarray(input1, dtype=np.float32)
-        if a.ndim == 1:
-            a = a[None, :]
-        if a.ndim != 2 or a.shape[0] != self.channels or a.shape[1] % self.vsize or output.size != a.size:
-            return CL_INVALID_VALUE
-        b = None
-        if input2 is not None:
-            b = np.ascontiguousarray(input2, dtype=np.float32)
-            if b.size != a.size:
-                return CL_INVALID_VALUE
-        return lib().clfa_dconv_convolution_blocks(self._h, output.ctypes.data, a.ctypes.data,
-                                                   None if b is None else b.ctypes.data, a.shape[1] // self.vsize)
-
-    def process_blocks_device(self, out, in1, in2=None, stream=None):
-        """device tensors (channels, L) of float32 (1-D for one channel), stride(1) == 1, L % vsize == 0; the row stride
-        of each is its stride(0) (views into longer rows are fine).  Asynchronous on `stream`."""
-        def rows(t):
-            if t.dim() == 1:
-                return t.shape[0], max(t.shape[0], 1)
-            if t.dim() != 2 or t.shape[0] != self.channels or (t.shape[1] > 1 and t.stride(1) != 1):
-                raise ValueError("expected a (channels, L) float32 tensor with stride(1) == 1")
-            return t.shape[1], t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
-        ts = [out, in1] + ([in2] if in2 is not None else [])
-        for t in ts:
-            if str(t.dtype) != "torch.float32" or (t.dim() == 1 and self.channels != 1):
-                raise ValueError("expected a (channels, L) float32 tensor with stride(1) == 1")
-        (lo, so), (l1, s1) = rows(out), rows(in1)
-        s2 = rows(in2)[1] if in2 is not None else s1
-        if lo != l1 or (in2 is not None and rows(in2)[0] != l1) or l1 % self.vsize:
-            return CL_INVALID_VALUE
-        if in2 is not None and s2 != s1:
-            return CL_INVALID_VALUE   # one stride for both inputs (the ABI's in_stride)
-        if stream is None:
-            import torch
-            stream = torch.cuda.current_stream(in1.device).cuda_stream
-        return lib().clfa_dconv_process_blocks_dev(self._h, out.data_ptr(), so, in1.data_ptr(),
-                                                   in2.data_ptr() if in2 is not None else None, s1,
-                                                   l1 // self.vsize, stream)

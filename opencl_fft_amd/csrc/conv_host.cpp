@@ -477,7 +477,7 @@ static int dconv_setup(clfa_dconv *d, int device, int irsize, int vsize, int cha
 
 // one block on stream s, everything device-resident: ring write at wp with wrap-around (intent of cl_dconv.cpp:112-122;
 // the two-input form writes in2 into the coefficient ring at the same point, :134-147), wp advanced (:124), vsize
-// outputs — all in ONE launch (conv_kernels.hip, k_dconv_block)
+// outputs — all in ONE launch (dconv_block.hip, k_dconv_block)
 static int dconv_block(clfa_dconv *d, float *out, const float *in1, const float *in2, hipStream_t s) {
   const int wp = d->wp;
   HIP_TRY(launch_dconv_block(d->plan, out, in1, in2, (float *)d->del.p, (float *)d->coefs.p, (float *)d->part.p,

@@ -1,5 +1,5 @@
 // fft_wg.hpp — workgroup-level pieces shared by the FFT, STFT and convolution kernels (fft_kernels.hip, stft_kernels.hip,
-// conv_kernels.hip, pconv_blocks.hip, pconv_matrix.hip): the LDS-exchanged pass chains and their geometry.
+// pconv_chain.hip, pconv_fused.inc, pconv_coop.hip, pconv_blocks.hip, pconv_matrix.hip): the LDS-exchanged pass chains and their geometry.
 #pragma once
 #include "internal.hpp"
 

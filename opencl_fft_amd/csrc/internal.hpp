@@ -141,7 +141,7 @@ hipError_t launch_pconv_mac(const PconvGeom &g, const cpx *ringA, const cpx *rin
 hipError_t launch_pconv_inverse(const PconvGeom &g, const cpx *acc, float *tail, float *out,
                                 const cpx *half, const cpx *w2i, hipStream_t s, int nsplit = 1);
 // one launch per block (forward + MAC + inverse in one workgroup per channel); used when
-// one launch per block for a FEW channels (conv_kernels.hip, k_pconv_coop): 2^logs bin slices x sparts segments of
+// one launch per block for a FEW channels (pconv_coop.hip, k_pconv_coop): 2^logs bin slices x sparts segments of
 // the partition axis per channel (logs = -1: the kernel does not apply); xacc: channels x sparts x bins complex
 // (hand-over of the accumulator slices), counters: one zero-initialised unsigned per channel (returned to zero by
 // every launch)

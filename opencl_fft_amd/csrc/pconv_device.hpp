@@ -1,11 +1,13 @@
-// pconv_device.hpp — device building blocks of the partitioned-convolution kernels (conv_kernels.hip, pconv_blocks.hip,
-// pconv_matrix.hip), each defined once, and the launch plumbing their launchers share.  The rules they carry exist once in
-// the reference too: bin 0 of a packed frame holds DC and Nyquist and is multiplied component-wise; partial sums are added
+// pconv_device.hpp — device building blocks of the partitioned-convolution kernels (pconv_chain.hip, pconv_fused.inc,
+// pconv_coop.hip, pconv_blocks.hip, pconv_matrix.hip), each defined once, and the launch plumbing their launchers share.
+// The rules they carry exist once in the reference too: bin 0 of a packed frame holds DC and Nyquist and is multiplied component-wise; partial sums are added
 // in a fixed ascending order; loads are clamped rather than predicated.
-// Rule for a change here: compile the three files before and after and compare them with tools/check_isa.py --same; a
+// Rule for a change here: compile these files before and after and compare them with tools/check_isa.py --same; a
 // helper is used only where the kernel keeps its instructions.  Sites that carry the bin-0 rule in their own words because
 // they did not: the c2r unpack, MAC term and overlap-add of k_pconv_fused and k_pconv_coop, the branch-form r2c pack of
-// k_pconv_fwd / k_pconvb_fwd, and the tail loop of k_pconv_mac.
+// k_pconv_fwd / k_pconvb_fwd, and the tail loop of k_pconv_mac.  The same holds for the pass chains of k_pconv_fused and
+// k_pconv_coop: each spells its forward and its inverse chain out (compute, barrier, scatter, barrier, gather, predicated on
+// tid < T / work), because a recursive helper in the manner of wg_passes changed the instructions of all 32 instantiations.
 #pragma once
 #include <type_traits>
 

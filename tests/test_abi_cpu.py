@@ -100,7 +100,7 @@ def _compile_to_asm(tmp_path, name):
     p = subprocess.run([hipcc] + flags + ["-save-temps=obj", "-c", src, "-o", str(tmp_path / (name + ".o"))],
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
     assert p.returncode == 0, p.stdout.decode()[-4000:]
-    asm = [f for f in os.listdir(tmp_path) if f.endswith("gfx950.s")]
+    asm = [f for f in os.listdir(tmp_path) if f.startswith(name + "-") and f.endswith("gfx950.s")]
     assert len(asm) == 1, asm
     return str(tmp_path / asm[0])
 
@@ -114,10 +114,11 @@ def _check_isa():
 
 
 def test_handover_kernels_code_object_audit(tmp_path):
-    """conv_kernels.hip: the hand-overs of k_pconv_coop / k_dconv_block on the compiled ISA — sc1 stores, agent-scope loads
+    """pconv_coop.hip and dconv_block.hip (handover.hpp): the hand-overs of k_pconv_coop / k_dconv_block on the compiled
+    ISA — sc1 stores, agent-scope loads
     as global_ / buffer_ loads with sc1 (never flat_), an arrival add, and the acquire for launches beyond one workgroup
     per CU (tools/check_isa.py --handover)"""
-    problems = _check_isa().check_handover(_compile_to_asm(tmp_path, "conv_kernels"))
+    problems = _check_isa().check_handover(_compile_to_asm(tmp_path, "pconv_coop"), _compile_to_asm(tmp_path, "dconv_block"))
     assert not problems, "\n".join(problems[:10])
 
 

@@ -10,7 +10,7 @@ The kernel (opencl_fft_amd/csrc/fft_resident.hip) does two things hipcc cannot c
     hipcc was seen copying them ahead of the kernel's own s_waitcnt, i.e. before the data had landed).
 
 usage: check_isa.py file.s                (hipcc -save-temps of fft_resident.hip)
-       check_isa.py --handover file.s     (conv_kernels.hip: the inter-workgroup hand-overs)
+       check_isa.py --handover a.s b.s   (pconv_coop.hip and dconv_block.hip: the inter-workgroup hand-overs of handover.hpp)
        check_isa.py --same OLD.s NEW.s    (a refactor's proof: every kernel compiles to the instructions it had)
 """
 import re
@@ -127,13 +127,15 @@ def check(path):
     return problems
 
 
-def check_handover(path):
-    """conv_kernels.hip: the inter-workgroup hand-overs of k_pconv_coop / k_dconv_block read the handed-over bytes with
+def check_handover(*paths):
+    """pconv_coop.hip + dconv_block.hip (handover.hpp), one .s file each, read as one text: the inter-workgroup hand-overs
+    of k_pconv_coop / k_dconv_block read the handed-over bytes with
     agent-scope loads that must compile to global_ / buffer_ loads with sc1 (never flat_: MI355X_MICROARCH.md, 'Valid
     forms', Consumer bullet), store them with sc1 stores, drain with s_waitcnt vmcnt(0) in front of the arrival add (which
     is an agent-scope RELEASE in the C++ model as well), and —
     for launches with more workgroups than CUs — carry an agent-scope acquire (buffer_inv sc1) for the last workgroup."""
-    s = open(path).read()
+    s = "\n".join(open(p).read() for p in paths)
+    path = " + ".join(paths)
     problems = []
     for stem, least_loads in (("k_pconv_coop", 2), ("k_dconv_block", 8)):
         names = re.findall(r"^(_ZN4clfa\d+%s[A-Za-z0-9_]*):" % stem, s, re.M)
@@ -155,7 +157,7 @@ def check_handover(path):
                 problems.append("%s: no sc1 (write-through) store of the handed-over bytes" % name)
             if not any(re.match(r"(global|buffer)_atomic_add\S*\s.*\bsc0\b", c) or re.match(r"(global|buffer)_atomic_add", c) for c in code):
                 problems.append("%s: no arrival counter add" % name)
-            # the arrival add carries an agent-scope release (conv_kernels.hip, handover_arrive): a write-back and its wait
+            # the arrival add carries an agent-scope release (handover.hpp, handover_arrive): a write-back and its wait
             # directly in front of every counter add
             adds = [i for i, c in enumerate(code) if re.match(r"(global|buffer)_atomic_add", c)]
             for i in adds:
@@ -226,7 +228,7 @@ if __name__ == "__main__":
     if len(sys.argv) > 3 and sys.argv[1] == "--same":
         sys.exit(1 if same(sys.argv[2], sys.argv[3]) else 0)
     if len(sys.argv) > 2 and sys.argv[1] == "--handover":
-        p = check_handover(sys.argv[2])
+        p = check_handover(*sys.argv[2:])
         for x in p:
             print(x)
         sys.exit(1 if p else 0)
