@@ -60,6 +60,7 @@ typedef struct clfa_pconv clfa_pconv; /* Clpconv object, `channels` independent 
 typedef struct clfa_dconv clfa_dconv; /* Cldconv object */
 typedef struct clfa_stft clfa_stft;   /* short-time analysis / overlap-add synthesis plan (extension) */
 typedef struct clfa_pconv_matrix clfa_pconv_matrix; /* convolution matrix: inputs mixed into outputs (extension) */
+typedef struct clfa_pvoc clfa_pvoc;   /* phase vocoder on the clfa_stft spectra: (amp, freq) frames both ways (extension) */
 
 /* ---- library / devices ---------------------------------------------------- */
 /* replaces clGetDeviceIDs(NULL, CL_DEVICE_TYPE_ALL, ...) at test_cfft.cpp:31,
@@ -309,6 +310,64 @@ CLFA_API int clfa_stft_synthesize(clfa_stft *st, const float *spectra, long fram
                                   long signal_stride, int normalize);
 CLFA_API size_t clfa_stft_workspace_bytes(const clfa_stft *st);
 CLFA_API const char *clfa_stft_kernel_name(const clfa_stft *st);
+
+/* ---- phase vocoder on the short-time spectra (extension: nothing of the reference's) ---- */
+/* An object has size = 2^k, 64 <= size <= 16384, M = size / 2, a hop 1 <= hop <= size, a sample rate sr > 0 (finite) and
+ * channels >= 1.  It converts between
+ *   spectra: channels x F x M complex64, contiguous — what clfa_stft_analyze_dev writes and clfa_stft_synthesize_dev reads;
+ *   frames:  channels x F x (M + 1) x 2 float32, contiguous — bin k = 0..M holds (amp, freq in Hz): the amp / freq frame of
+ *            a phase vocoder (Csound's pvs streams).
+ * Both 8-byte aligned.  F frames per channel in every call; F == 0 succeeds and does nothing.
+ *
+ * Bins as complex numbers: z[k] of a packed spectrum P is (Re P[0], 0) for k = 0, (Im P[0], 0) for k = M, conj(P[M/2]) for
+ * k = M/2 and P[k] otherwise.  Synthesis inverts the map: bin M/2 is conjugated back, Re P[0] = Re z[0], Im P[0] = Re z[M]
+ * (the imaginary parts of z[0] and z[M] are dropped).
+ *
+ * Analysis (spectra -> frames).  State: prev, M + 1 complex per channel, (1, 0) in every bin at creation and after reset;
+ * after a call it is z of the call's last frame.  Table: e[k] = exp(-2 pi i ((k hop) mod size) / size), computed in double,
+ * stored as float32 pairs.  For frame f and bin k, with z_{-1} = prev:
+ *   amp = |z_f[k]|;  d = z_f[k] conj(z_{f-1}[k]) e[k];  dev = atan2f(Im d, Re d) / (2 pi) turns, 0 where d = (0, 0);
+ *   freq = (k + dev size / hop) sr / size.
+ * A frame depends on its own spectrum and the one before: the results are the same bits however a stream of frames is cut
+ * into calls.  The products are plain float32: spectra whose |P|^2 overflows float32 are outside the contract.  One launch.
+ *
+ * Synthesis (frames -> spectra).  State: theta, one uint32 per channel and bin, in units of 2^-32 turn; 0 at creation and
+ * after reset.  kf = (float)(hop / sr), divided in double.  For frame f, every float32 operation rounded on its own:
+ *   t = freq kf;  r = t - rintf(t);  inc = (uint32)(int64)rint((double)r 2^32);  inc = 0 where freq (or t) is not finite;
+ *   theta_f = theta_{f-1} + inc (mod 2^32);  z_f[k] = amp (cos, sin)(2 pi theta_f / 2^32).
+ * The phase is an integer, so a parallel scan over frames gives the bits of the serial sum: the phase never drifts, and
+ * cutting a stream into calls changes neither the spectra nor the state.  Three launches per sub-batch: the sums of the
+ * increments per chunk of clfa_pvoc_scan_chunk() frames; per channel and bin, the chunks' bases and the new state; the
+ * walk of every chunk from its base.  No atomics, no waiting between workgroups.  With both states as defined, the
+ * synthesis of an analysis reproduces the phases of the spectra (frame 0 from the zero phase on both sides).
+ *
+ * Device calls follow the other objects: asynchronous on `stream`, one object = one stream at a time (a change of stream
+ * waits for the previous one), capturable into a hipGraph (a replay advances the states like the call it recorded), the
+ * current device left as found.  A bad argument, or an output that overlaps the input even partly, is CLFA_INVALID_VALUE
+ * and leaves both states untouched.  Workspace (the chunk sums of one sub-batch, at most about 64 MiB;
+ * CLFA_PVOC_CHUNKS_MAX, read at creation, lowers the chunks per sub-batch): allocated whole by the first synthesis, so its
+ * address never changes; workspace_bytes() = what is held; released with the object; a synthesis under capture that would
+ * have to allocate it returns CLFA_INVALID_OPERATION.  Longer calls run in sub-batches.
+ * Argument errors of create (size, hop, sr, channels) are CLFA_INVALID_VALUE before any device lookup; a failed create
+ * still returns a handle. */
+CLFA_API int clfa_pvoc_create(clfa_pvoc **pv, int device, int size, int hop, double sr, int channels);
+CLFA_API void clfa_pvoc_destroy(clfa_pvoc *pv);
+CLFA_API int clfa_pvoc_get_error(const clfa_pvoc *pv);
+CLFA_API const char *clfa_pvoc_get_log(const clfa_pvoc *pv);
+/* both states as at creation; blocking (CLFA_INVALID_OPERATION while the object's stream is being captured) */
+CLFA_API int clfa_pvoc_reset(clfa_pvoc *pv);
+CLFA_API int clfa_pvoc_analyze_dev(clfa_pvoc *pv, const void *spectra, void *frames_out, long F, void *stream);
+CLFA_API int clfa_pvoc_synthesize_dev(clfa_pvoc *pv, const void *frames, void *spectra_out, long F, void *stream);
+/* host arrays, copied in and out, blocking */
+CLFA_API int clfa_pvoc_analyze(clfa_pvoc *pv, const float *spectra, float *frames_out, long F);
+CLFA_API int clfa_pvoc_synthesize(clfa_pvoc *pv, const float *frames, float *spectra_out, long F);
+/* "k_pvoc_analyze", or with synthesis != 0 "k_pvoc_walk" ("" for a failed object) */
+CLFA_API const char *clfa_pvoc_kernel_name(const clfa_pvoc *pv, int synthesis);
+CLFA_API size_t clfa_pvoc_workspace_bytes(const clfa_pvoc *pv);
+CLFA_API int clfa_pvoc_scan_chunk(void);
+/* state diagnostics, blocking: channels x (M + 1) phases; channels x (M + 1) x (re, im) of prev */
+CLFA_API int clfa_pvoc_read_phase(clfa_pvoc *pv, unsigned *host);
+CLFA_API int clfa_pvoc_read_prev(clfa_pvoc *pv, float *host);
 
 /* ---- convolution matrix (extension: nothing of the reference's) ------------- */
 /* Uniformly partitioned overlap-add convolution of `inputs` signals with an outputs x inputs matrix of static responses:

@@ -9,6 +9,7 @@ meaning and integer OpenCL status codes), over the C ABI of libclfft_amd.so:
     Cldconv  cl_dconv.h:17-66   direct convolution
     Stft     (extension)        short-time analysis / windowed overlap-add synthesis on the Clrfft layout
     PconvMatrix (extension)     convolution matrix: many inputs mixed into many outputs
+    Pvoc     (extension)        phase vocoder on Stft's spectra: (amp, freq) frames both ways
 
 Like the reference, constructors never raise: a failed setup is read back with
 ``get_error()`` / ``get_cl_err()`` and every method returns the status code.
@@ -27,7 +28,7 @@ from ._lib import ClError, check, lib
 
 __all__ = ["Clcfft", "Clrfft", "Clpconv", "Cldconv", "ClError", "cl_error_string", "device_count",
            "device_name", "bitrev_table", "twiddle_table", "r2c_twiddle_table", "reorder_device", "PI",
-           "Stft", "packed_to_onesided", "onesided_to_packed", "PconvMatrix"]
+           "Stft", "packed_to_onesided", "onesided_to_packed", "PconvMatrix", "Pvoc"]
 
 PI = 3.141592653589793  # cl_fft.h:24
 CL_SUCCESS = 0
@@ -303,6 +304,101 @@ class Stft(_Handle):
             raise ValueError("out has %d rows for %d channels" % (rows, s3.shape[0]))
         return lib().clfa_stft_synthesize_dev(self._h, spectra.data_ptr(), s3.shape[1], s3.shape[0], p, stride,
                                               int(bool(normalize)), _stream_of(out, stream))
+
+
+class Pvoc(_Handle):
+    """Phase vocoder on the spectra of Stft (extension, clfa_pvoc in clfft_amd.h): analyze() reads (channels, F, size/2)
+    complex64 spectra as (channels, F, size/2 + 1, 2) float32 frames of (amp, freq in Hz) per bin, synthesize() turns such
+    frames back into spectra.  The object carries the last spectrum (analysis) and an integer phase per bin (synthesis)
+    from call to call, so a stream may be cut into calls anywhere; reset() returns both to their start.
+    Like the other objects the constructor does not raise, and every call returns its status."""
+    _destroy = "clfa_pvoc_destroy"
+
+    def __init__(self, device_id, size, hop, sr, channels=1):
+        self.size, self.hop, self.sr, self.channels = int(size), int(hop), float(sr), int(channels)
+        self.M = self.size // 2
+        h = C.c_void_p()
+        lib().clfa_pvoc_create(C.byref(h), int(device_id), self.size, self.hop, self.sr, self.channels)
+        self._h = h
+
+    def get_error(self):
+        return lib().clfa_pvoc_get_error(self._h)
+
+    def get_log(self):
+        return lib().clfa_pvoc_get_log(self._h).decode()
+
+    def kernel_name(self, synthesis=False):
+        return lib().clfa_pvoc_kernel_name(self._h, int(bool(synthesis))).decode()
+
+    def workspace_bytes(self):
+        return lib().clfa_pvoc_workspace_bytes(self._h)
+
+    def scan_chunk(self):
+        """frames per chunk of the synthesis' phase scan (fixed)"""
+        return lib().clfa_pvoc_scan_chunk()
+
+    def reset(self):
+        return lib().clfa_pvoc_reset(self._h)
+
+    def read_phase(self):
+        """the synthesis state: uint32 (channels, size/2 + 1), units of 2^-32 turn (blocking)"""
+        out = np.zeros((self.channels, self.M + 1), np.uint32)
+        check(lib().clfa_pvoc_read_phase(self._h, out.ctypes.data), "Pvoc.read_phase")
+        return out
+
+    def read_prev(self):
+        """the analysis state: complex64 (channels, size/2 + 1), z of the last frame analysed (blocking)"""
+        out = np.zeros((self.channels, self.M + 1), np.complex64)
+        check(lib().clfa_pvoc_read_prev(self._h, out.ctypes.data), "Pvoc.read_prev")
+        return out
+
+    def _shapes(self, spectra, frames):
+        """F if `spectra` is (channels, F, M) (or (F, M) for one channel) and `frames` the matching (.., F, M + 1, 2), else None"""
+        s, f = tuple(spectra.shape), tuple(frames.shape)
+        if len(s) == 2 and self.channels == 1:
+            s = (1,) + s
+        if len(f) == 3 and self.channels == 1:
+            f = (1,) + f
+        if len(s) != 3 or s[0] != self.channels or s[2] != self.M or f != (self.channels, s[1], self.M + 1, 2):
+            return None
+        return s[1]
+
+    def _device_call(self, fn, spectra, frames, src, dst, stream):
+        import torch
+        F = self._shapes(spectra, frames)
+        if (F is None or spectra.dtype != torch.complex64 or frames.dtype != torch.float32
+                or not spectra.is_contiguous() or not frames.is_contiguous()):
+            return CL_INVALID_VALUE
+        return fn(self._h, src.data_ptr(), dst.data_ptr(), F, _stream_of(dst, stream))
+
+    def analyze_device(self, spectra, frames_out, stream=None):
+        """torch: spectra (channels, F, size/2) complex64 -> frames_out (channels, F, size/2 + 1, 2) float32, both
+        contiguous (anything else: CL_INVALID_VALUE); asynchronous on `stream` (default: the current stream)"""
+        return self._device_call(lib().clfa_pvoc_analyze_dev, spectra, frames_out, spectra, frames_out, stream)
+
+    def synthesize_device(self, frames, spectra_out, stream=None):
+        """torch: frames (channels, F, size/2 + 1, 2) float32 -> spectra_out (channels, F, size/2) complex64"""
+        return self._device_call(lib().clfa_pvoc_synthesize_dev, spectra_out, frames, frames, spectra_out, stream)
+
+    def analyze(self, spectra):
+        """host: complex64 (channels, F, size/2) (or (F, size/2) for one channel) -> float32 (.., F, size/2 + 1, 2)"""
+        spectra = np.ascontiguousarray(spectra, dtype=np.complex64)
+        out = np.zeros(spectra.shape[:-1] + (self.M + 1, 2), np.float32)
+        F = self._shapes(spectra, out)
+        if F is None:
+            raise ValueError("spectra must be (%d, F, %d)" % (self.channels, self.M))
+        check(lib().clfa_pvoc_analyze(self._h, spectra.ctypes.data, out.ctypes.data, F), "Pvoc.analyze")
+        return out
+
+    def synthesize(self, frames):
+        """host: float32 (channels, F, size/2 + 1, 2) (or (F, size/2 + 1, 2)) -> complex64 (.., F, size/2)"""
+        frames = np.ascontiguousarray(frames, dtype=np.float32)
+        out = np.zeros(frames.shape[:-2] + (self.M,), np.complex64)
+        F = self._shapes(out, frames)
+        if F is None:
+            raise ValueError("frames must be (%d, F, %d, 2)" % (self.channels, self.M + 1))
+        check(lib().clfa_pvoc_synthesize(self._h, frames.ctypes.data, out.ctypes.data, F), "Pvoc.synthesize")
+        return out
 
 
 def packed_to_onesided(spec):

@@ -105,6 +105,20 @@ SYMBOLS = [
     ("clfa_stft_synthesize", C.c_int, [_vp, _vp, C.c_long, C.c_long, _vp, C.c_long, C.c_int]),
     ("clfa_stft_workspace_bytes", C.c_size_t, [_vp]),
     ("clfa_stft_kernel_name", C.c_char_p, [_vp]),
+    ("clfa_pvoc_create", C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.c_int, C.c_double, C.c_int]),
+    ("clfa_pvoc_destroy", None, [_vp]),
+    ("clfa_pvoc_get_error", C.c_int, [_vp]),
+    ("clfa_pvoc_get_log", C.c_char_p, [_vp]),
+    ("clfa_pvoc_reset", C.c_int, [_vp]),
+    ("clfa_pvoc_analyze_dev", C.c_int, [_vp, _vp, _vp, C.c_long, _vp]),
+    ("clfa_pvoc_synthesize_dev", C.c_int, [_vp, _vp, _vp, C.c_long, _vp]),
+    ("clfa_pvoc_analyze", C.c_int, [_vp, _vp, _vp, C.c_long]),
+    ("clfa_pvoc_synthesize", C.c_int, [_vp, _vp, _vp, C.c_long]),
+    ("clfa_pvoc_kernel_name", C.c_char_p, [_vp, C.c_int]),
+    ("clfa_pvoc_workspace_bytes", C.c_size_t, [_vp]),
+    ("clfa_pvoc_scan_chunk", C.c_int, []),
+    ("clfa_pvoc_read_phase", C.c_int, [_vp, _vp]),
+    ("clfa_pvoc_read_prev", C.c_int, [_vp, _vp]),
 ]
 
 _LIB = None

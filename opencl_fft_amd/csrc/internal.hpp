@@ -250,6 +250,29 @@ struct StftArgs {
 };
 hipError_t launch_stft(const StftArgs &a, const DeviceInfo &di, hipStream_t s);
 
+// ---- phase vocoder on the Stft spectra (pvoc_kernels.hip) ---------------------------
+// spectra: channels x F x M complex (the packed layout); frames: channels x F x (M + 1) x (amp, freq in Hz).
+constexpr int kPvocChunk = 64;   // frames per chunk of the synthesis' phase scan (fixed: clfa_pvoc_scan_chunk)
+struct PvocArgs {
+  int M = 0, channels = 0;
+  long F = 0;                      // frames per channel in the caller's buffers (the channels' rows are F frames apart)
+  const cpx *spec_in = nullptr;    // analysis
+  float *frames_out = nullptr;
+  cpx *prev = nullptr;             // channels x (M + 1): z of the frame before the call's first
+  const cpx *etab = nullptr;       // M + 1 expected advances e[k]
+  float sh = 0.f, srs = 0.f;       // size / hop, sr / size
+  const float *frames_in = nullptr;   // synthesis
+  cpx *spec_out = nullptr;
+  unsigned *theta = nullptr;       // channels x (M + 1) phases in 2^-32 turn
+  unsigned *sums = nullptr;        // channels x nchunks x (M + 1): the chunks' sums, then their bases
+  float kf = 0.f;                  // hop / sr
+};
+// one launch: frames of every channel, prev read by the lanes of frame 0 and replaced by the same lanes
+hipError_t launch_pvoc_analyze(const PvocArgs &a, const DeviceInfo &di, hipStream_t s);
+// frames [f0, f0 + nf) of every channel, nf <= the workspace's chunks x kPvocChunk: the chunks' sums of increments, then
+// (one lane per channel and bin) their bases in place and the new theta, then the walk that writes the spectra
+hipError_t launch_pvoc_synth(const PvocArgs &a, long f0, long nf, const DeviceInfo &di, hipStream_t s);
+
 // ---- direct convolution ----------------------------------------------------------
 struct DconvPlan {
   int C;    // taps per workgroup

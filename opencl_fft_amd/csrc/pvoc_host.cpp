@@ -1,0 +1,227 @@
+// pvoc_host.cpp — C ABI of the phase vocoder on the Stft spectra (see include/clfft_amd.h): Pvoc.  Shared plumbing: host.hpp.
+#include "host.hpp"
+
+using namespace clfa;
+
+// ---------------------------------------------------------------------------------
+// spectra <-> (amp, freq) frames (pvoc_kernels.hip)
+// ---------------------------------------------------------------------------------
+
+struct clfa_pvoc {
+  DeviceInfo di;
+  int size = 0, hop = 0, M = 0, channels = 0;
+  double sr = 0;
+  float sh = 0.f, srs = 0.f, kf = 0.f;   // size / hop, sr / size, hop / sr: divided in double, rounded once
+  int err = 0;
+  char log[512];
+  hipStream_t stream = nullptr;
+  DevBuf etab;            // e[k], M + 1 complex
+  DevBuf prev, theta;     // the two states: channels x (M + 1) complex / uint32
+  DevBuf ws;              // the scan's chunk sums: allocated by the first synthesis that needs it
+  long cap = 1;           // chunks per sub-batch (CLFA_PVOC_CHUNKS_MAX: tuning switch, read at creation)
+  DevBuf sspec, sframes;  // staging of the host entry points
+  StreamOrder order;
+};
+
+static size_t pvoc_bins(const clfa_pvoc *p) { return (size_t)p->channels * (p->M + 1); }
+
+// both states as at creation: prev = (1, 0), theta = 0 (on p->stream, blocking)
+static int pvoc_init_state(clfa_pvoc *p) {
+  std::vector<cpx> one(pvoc_bins(p), mk(1.f, 0.f));
+  HIP_TRY(hipMemcpyAsync(p->prev.p, one.data(), sizeof(cpx) * one.size(), hipMemcpyHostToDevice, p->stream));
+  HIP_TRY(hipMemsetAsync(p->theta.p, 0, sizeof(unsigned) * pvoc_bins(p), p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return CLFA_SUCCESS;
+}
+
+static int pvoc_setup(clfa_pvoc *p, int device, int size, int hop, double sr, int channels) {
+  p->size = size;
+  p->hop = hop;
+  p->sr = sr;
+  p->channels = channels;
+  p->log[0] = 0;
+  if (!is_pow2(size) || size < 64 || size > (2 << kLdsMaxLog)) {
+    snprintf(p->log, sizeof(p->log), "size must be a power of two, 64..%d (got %d)", 2 << kLdsMaxLog, size);
+    return CLFA_INVALID_VALUE;
+  }
+  if (hop < 1 || hop > size) {
+    snprintf(p->log, sizeof(p->log), "hop must be 1..size (got %d)", hop);
+    return CLFA_INVALID_VALUE;
+  }
+  if (!(sr > 0) || !std::isfinite(sr)) {
+    snprintf(p->log, sizeof(p->log), "sr must be positive and finite (got %g)", sr);
+    return CLFA_INVALID_VALUE;
+  }
+  if (channels < 1) {
+    snprintf(p->log, sizeof(p->log), "channels must be >= 1 (got %d)", channels);
+    return CLFA_INVALID_VALUE;
+  }
+  p->M = size / 2;
+  p->sh = (float)((double)size / hop);
+  p->srs = (float)(sr / size);
+  p->kf = (float)(hop / sr);
+  // sub-batches bound the scan's workspace (4 bytes per channel, chunk and bin) to about 64 MiB
+  p->cap = (64L << 20) / ((long)sizeof(unsigned) * (long)pvoc_bins(p));
+  p->cap = p->cap < 1 ? 1 : (p->cap > 4096 ? 4096 : p->cap);
+  if (const char *env = getenv("CLFA_PVOC_CHUNKS_MAX")) {
+    if (atol(env) > 0 && atol(env) < p->cap) p->cap = atol(env);
+  }
+  int e = device_info(device, p->di);
+  if (e) return e;
+  ENTER_DEVICE(device);
+  HIP_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
+  std::vector<cpx> tab(p->M + 1);
+  for (int k = 0; k <= p->M; k++) {
+    const double a = -2 * kPI * (double)(((long)k * hop) % size) / size;
+    tab[k] = mk((float)cos(a), (float)sin(a));
+  }
+  if ((e = upload(p->etab, tab.data(), sizeof(cpx) * tab.size()))) return e;
+  if ((e = p->prev.ensure(sizeof(cpx) * pvoc_bins(p))) || (e = p->theta.ensure(sizeof(unsigned) * pvoc_bins(p)))) return e;
+  return pvoc_init_state(p);
+}
+
+// the object's earlier work is complete (blocking); refused while its stream is being captured
+static int pvoc_quiesce(clfa_pvoc *p) {
+  if (!p->order.any) return CLFA_SUCCESS;
+  if (StreamOrder::capturing(p->order.last)) return CLFA_INVALID_OPERATION;
+  if (hipStreamSynchronize(p->order.last) != hipSuccess) {   // a stream the caller has destroyed: wait for the device
+    (void)hipGetLastError();
+    HIP_TRY(hipDeviceSynchronize());
+  }
+  return CLFA_SUCCESS;
+}
+
+// the argument rules both directions share; 1 = a successful no-op
+static int pvoc_check(const clfa_pvoc *p, const void *spectra, const void *frames, long F, size_t *sbytes, size_t *fbytes) {
+  if (F < 0 || F > 0x7fffffffL) return CLFA_INVALID_VALUE;
+  if (F == 0) return 1;
+  if (!spectra || !frames || ((uintptr_t)spectra & 7) || ((uintptr_t)frames & 7)) return CLFA_INVALID_VALUE;
+  *sbytes = sizeof(cpx) * (size_t)p->channels * F * p->M;
+  *fbytes = 2 * sizeof(float) * pvoc_bins(p) * F;
+  if (spans_overlap(spectra, *sbytes, frames, *fbytes)) return CLFA_INVALID_VALUE;
+  return CLFA_SUCCESS;
+}
+
+static PvocArgs pvoc_args(clfa_pvoc *p, long F) {
+  PvocArgs a;
+  a.M = p->M;
+  a.channels = p->channels;
+  a.F = F;
+  a.prev = (cpx *)p->prev.p;
+  a.etab = (const cpx *)p->etab.p;
+  a.theta = (unsigned *)p->theta.p;
+  a.sums = (unsigned *)p->ws.p;
+  a.sh = p->sh;
+  a.srs = p->srs;
+  a.kf = p->kf;
+  return a;
+}
+
+extern "C" {
+
+int clfa_pvoc_create(clfa_pvoc **pv, int device, int size, int hop, double sr, int channels) {
+  return create_object(pv, [&](clfa_pvoc *p) { return pvoc_setup(p, device, size, hop, sr, channels); });
+}
+
+void clfa_pvoc_destroy(clfa_pvoc *p) { destroy_object(p); }
+
+int clfa_pvoc_get_error(const clfa_pvoc *p) { return p ? p->err : CLFA_INVALID_VALUE; }
+const char *clfa_pvoc_get_log(const clfa_pvoc *p) { return p ? p->log : ""; }
+size_t clfa_pvoc_workspace_bytes(const clfa_pvoc *p) { return p ? p->ws.bytes : 0; }
+int clfa_pvoc_scan_chunk(void) { return kPvocChunk; }
+const char *clfa_pvoc_kernel_name(const clfa_pvoc *p, int synthesis) {
+  return !p || p->err ? "" : (synthesis ? "k_pvoc_walk" : "k_pvoc_analyze");
+}
+
+int clfa_pvoc_reset(clfa_pvoc *p) {
+  if (int e = obj_error(p)) return e;
+  ENTER_DEVICE(p->di.device);
+  if (int e = pvoc_quiesce(p)) return e;
+  return pvoc_init_state(p);
+}
+
+int clfa_pvoc_read_phase(clfa_pvoc *p, unsigned *host) {
+  if (int e = obj_error(p)) return e;
+  if (!host) return CLFA_INVALID_VALUE;
+  ENTER_DEVICE(p->di.device);
+  if (int e = pvoc_quiesce(p)) return e;
+  HIP_TRY(hipMemcpy(host, p->theta.p, sizeof(unsigned) * pvoc_bins(p), hipMemcpyDeviceToHost));
+  return CLFA_SUCCESS;
+}
+
+int clfa_pvoc_read_prev(clfa_pvoc *p, float *host) {
+  if (int e = obj_error(p)) return e;
+  if (!host) return CLFA_INVALID_VALUE;
+  ENTER_DEVICE(p->di.device);
+  if (int e = pvoc_quiesce(p)) return e;
+  HIP_TRY(hipMemcpy(host, p->prev.p, sizeof(cpx) * pvoc_bins(p), hipMemcpyDeviceToHost));
+  return CLFA_SUCCESS;
+}
+
+int clfa_pvoc_analyze_dev(clfa_pvoc *p, const void *spectra, void *frames_out, long F, void *stream) {
+  if (int e = obj_error(p)) return e;
+  size_t sbytes, fbytes;
+  if (int e = pvoc_check(p, spectra, frames_out, F, &sbytes, &fbytes)) return e == 1 ? CLFA_SUCCESS : e;
+  ENTER_DEVICE(p->di.device);
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(p->order.use(s));
+  PvocArgs a = pvoc_args(p, F);
+  a.spec_in = (const cpx *)spectra;
+  a.frames_out = (float *)frames_out;
+  HIP_TRY(launch_pvoc_analyze(a, p->di, s));
+  return CLFA_SUCCESS;
+}
+
+int clfa_pvoc_synthesize_dev(clfa_pvoc *p, const void *frames, void *spectra_out, long F, void *stream) {
+  if (int e = obj_error(p)) return e;
+  size_t sbytes, fbytes;
+  if (int e = pvoc_check(p, spectra_out, frames, F, &sbytes, &fbytes)) return e == 1 ? CLFA_SUCCESS : e;
+  ENTER_DEVICE(p->di.device);
+  hipStream_t s = (hipStream_t)stream;
+  const long held = p->cap;   // the whole sub-batch workspace at the first need: its address never changes afterwards
+  HIP_TRY(p->order.use(s));
+  if (int e = ensure_workspaces({{&p->ws, sizeof(unsigned) * pvoc_bins(p) * (size_t)held}}, s)) return e;
+  PvocArgs a = pvoc_args(p, F);
+  a.frames_in = (const float *)frames;
+  a.spec_out = (cpx *)spectra_out;
+  // sub-batches of at most `held` chunks: each advances the state by its frames, the next one starts from there
+  for (long f0 = 0; f0 < F; f0 += held * kPvocChunk) {
+    const long nf = F - f0 < held * kPvocChunk ? F - f0 : held * kPvocChunk;
+    HIP_TRY(launch_pvoc_synth(a, f0, nf, p->di, s));
+  }
+  return CLFA_SUCCESS;
+}
+
+int clfa_pvoc_analyze(clfa_pvoc *p, const float *spectra, float *frames_out, long F) {
+  if (int e = obj_error(p)) return e;
+  if (F < 0 || F > 0x7fffffffL || (F > 0 && (!spectra || !frames_out))) return CLFA_INVALID_VALUE;
+  if (F == 0) return CLFA_SUCCESS;
+  const size_t sbytes = sizeof(cpx) * (size_t)p->channels * F * p->M, fbytes = 2 * sizeof(float) * pvoc_bins(p) * F;
+  ENTER_DEVICE(p->di.device);
+  int e = p->sspec.ensure(sbytes);
+  if (!e) e = p->sframes.ensure(fbytes);
+  if (e) return e;
+  HIP_TRY(hipMemcpyAsync(p->sspec.p, spectra, sbytes, hipMemcpyHostToDevice, p->stream));
+  if ((e = clfa_pvoc_analyze_dev(p, p->sspec.p, p->sframes.p, F, p->stream))) return e;
+  HIP_TRY(hipMemcpyAsync(frames_out, p->sframes.p, fbytes, hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return CLFA_SUCCESS;
+}
+
+int clfa_pvoc_synthesize(clfa_pvoc *p, const float *frames, float *spectra_out, long F) {
+  if (int e = obj_error(p)) return e;
+  if (F < 0 || F > 0x7fffffffL || (F > 0 && (!frames || !spectra_out))) return CLFA_INVALID_VALUE;
+  if (F == 0) return CLFA_SUCCESS;
+  const size_t sbytes = sizeof(cpx) * (size_t)p->channels * F * p->M, fbytes = 2 * sizeof(float) * pvoc_bins(p) * F;
+  ENTER_DEVICE(p->di.device);
+  int e = p->sspec.ensure(sbytes);
+  if (!e) e = p->sframes.ensure(fbytes);
+  if (e) return e;
+  HIP_TRY(hipMemcpyAsync(p->sframes.p, frames, fbytes, hipMemcpyHostToDevice, p->stream));
+  if ((e = clfa_pvoc_synthesize_dev(p, p->sframes.p, p->sspec.p, F, p->stream))) return e;
+  HIP_TRY(hipMemcpyAsync(spectra_out, p->sspec.p, sbytes, hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return CLFA_SUCCESS;
+}
+
+}  // extern "C"

@@ -1,0 +1,204 @@
+// pvoc_kernels.hip — phase vocoder on the packed spectra of Stft (clfa_pvoc, include/clfft_amd.h).
+//
+//   k_pvoc_analyze  one launch per call: a lane takes bin k of a run of kPvocRun consecutive frames of one channel; the
+//                   frame before the run is read again (from cache: the neighbouring workgroup has just read it), the
+//                   frame before the call's first comes from the state.  The lanes of frame 0 are the only ones that
+//                   touch the state: they read it, then replace it with z of the call's last frame.
+//   k_pvoc_sums     synthesis, launch 1: per (channel, chunk of kPvocChunk frames, bin) the sum of the frames' phase
+//                   increments (uint32, units of 2^-32 turn);
+//   k_pvoc_scan     launch 2, small: per (channel, bin) the chunks' sums become their bases in place (the state plus the
+//                   sums of the chunks before), and the state takes the call's total — one workgroup reads the old state
+//                   before a barrier and one of its lanes writes the new one after it;
+//   k_pvoc_walk     launch 3: every chunk starts from its base and walks its frames, writing spectra.
+//
+// The phases are integers, and integer addition is associative: the chunked sums are the bits of the serial sum, for every
+// chunk length, sub-batch and split of a stream into calls.  No atomics, no waiting between workgroups.
+//
+// Every global access is a row of consecutive bins: 8 bytes per lane (a complex bin, or an (amp, freq) pair), 4 in the
+// sums and bases.
+#include "internal.hpp"
+
+namespace clfa {
+
+namespace {
+
+constexpr int kPvocWG = 256;    // lanes = bins per workgroup tile
+constexpr int kPvocRun = 4;     // consecutive frames per lane of the analysis
+constexpr int kScanBins = 64, kScanSegs = 16;   // k_pvoc_scan: a wave per segment of the chunk axis
+
+// z[k] of a packed row: bin 0 = (Re P[0], 0), bin M = (Im P[0], 0), bin M/2 conjugated
+__device__ __forceinline__ cpx pvoc_bin(const cpx *__restrict__ row, int k, int M) {
+  const cpx p = row[k == M ? 0 : k];
+  if (k == 0) return mk(p.x, 0.f);
+  if (k == M) return mk(p.y, 0.f);
+  if (k == (M >> 1)) return mk(p.x, -p.y);
+  return p;
+}
+
+// the phase increment of one frame in 2^-32 turn.  Every step rounds on its own: tests/pvoc_model.py restates it bit for
+// bit.  The pragma is what keeps the product and the subtraction apart — HIP's __fmul_rn / __fsub_rn are plain operators,
+// which hipcc's default contraction fuses into one fma.  r is a float in [-1/2, 1/2], so r * 2^32 is exact in double and
+// |.| <= 2^31.
+__device__ __forceinline__ unsigned pvoc_inc(float freq, float kf) {
+#pragma clang fp contract(off)
+  const float t = freq * kf;
+  const float r = t - rintf(t);
+  if (!(fabsf(r) <= 0.5f)) return 0u;   // a non-finite freq (or freq * kf): the phase stays
+  return (unsigned)(long long)rint((double)r * 4294967296.0);
+}
+
+// item -> (channel, second index, bin tile), the tile fastest: neighbouring workgroups hold neighbouring rows
+__device__ __forceinline__ void pvoc_item(long item, int tiles, long inner, int &tile, long &j, long &c) {
+  const long rest = item / tiles;
+  tile = (int)(item - rest * tiles);
+  c = rest / inner;
+  j = rest - c * inner;
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(kPvocWG) void k_pvoc_analyze(const cpx *__restrict__ spec, float *__restrict__ frames,
+                                                          cpx *prev, const cpx *__restrict__ etab, long F, int M,
+                                                          long groups, int tiles, long items, float sh, float srs) {
+#pragma unroll 1
+  for (long item = blockIdx.x; item < items; item += gridDim.x) {
+    int tile;
+    long g, c;
+    pvoc_item(item, tiles, groups, tile, g, c);
+    const int k = tile * kPvocWG + (int)threadIdx.x;
+    if (k > M) continue;
+    const long f0 = g * kPvocRun, f1 = f0 + kPvocRun < F ? f0 + kPvocRun : F;
+    const cpx *rows = spec + c * F * M;
+    cpx *state = prev + c * (M + 1) + k;
+    const cpx e = etab[k];
+    cpx zp = f0 == 0 ? *state : pvoc_bin(rows + (f0 - 1) * M, k, M);
+    cpx *out = reinterpret_cast<cpx *>(frames) + (c * F + f0) * (M + 1) + k;
+    for (long f = f0; f < f1; f++, out += M + 1) {
+      const cpx z = pvoc_bin(rows + f * M, k, M);
+      const float amp = sqrtf(z.x * z.x + z.y * z.y);
+      const float tx = z.x * zp.x + z.y * zp.y, ty = z.y * zp.x - z.x * zp.y;   // z conj(z_prev)
+      const float dx = tx * e.x - ty * e.y, dy = tx * e.y + ty * e.x;
+      const float dev = (dx == 0.f && dy == 0.f) ? 0.f : atan2f(dy, dx) * 0.15915494309189535f;   // turns
+      *out = mk(amp, ((float)k + dev * sh) * srs);
+      zp = z;
+    }
+    if (f0 == 0) *state = pvoc_bin(rows + (F - 1) * M, k, M);
+  }
+}
+
+// frames: the sub-batch's first frame of channel 0 (channel c at c * cstride pairs); nf frames in nch chunks
+__global__ __launch_bounds__(kPvocWG) void k_pvoc_sums(const cpx *__restrict__ frames, long cstride, long nf, int M,
+                                                       long nch, int tiles, long items, float kf,
+                                                       unsigned *__restrict__ sums) {
+#pragma unroll 1
+  for (long item = blockIdx.x; item < items; item += gridDim.x) {
+    int tile;
+    long j, c;
+    pvoc_item(item, tiles, nch, tile, j, c);
+    const int k = tile * kPvocWG + (int)threadIdx.x;
+    if (k > M) continue;
+    const long f0 = j * kPvocChunk, f1 = f0 + kPvocChunk < nf ? f0 + kPvocChunk : nf;
+    const cpx *in = frames + c * cstride + f0 * (M + 1) + k;
+    unsigned s = 0;
+    for (long f = f0; f < f1; f++, in += M + 1) s += pvoc_inc(in->y, kf);
+    sums[(c * nch + j) * (M + 1) + k] = s;
+  }
+}
+
+// one workgroup per (channel, tile of kScanBins bins), kScanBins x kScanSegs lanes: wave s takes the chunks [s len, (s + 1) len)
+__global__ __launch_bounds__(kScanBins *kScanSegs) void k_pvoc_scan(unsigned *__restrict__ sums, unsigned *theta, int M,
+                                                                    long nch, int tiles) {
+  __shared__ unsigned s_tot[kScanSegs][kScanBins];
+  const int lane = threadIdx.x & (kScanBins - 1), seg = threadIdx.x / kScanBins;
+  const long c = blockIdx.x / tiles;
+  const int k = (int)(blockIdx.x - c * tiles) * kScanBins + lane;
+  const bool live = k <= M;
+  const long len = (nch + kScanSegs - 1) / kScanSegs;
+  const long j0 = seg * len < nch ? seg * len : nch, j1 = j0 + len < nch ? j0 + len : nch;
+  unsigned *col = sums + c * nch * (M + 1) + k;
+  unsigned tot = 0, th = 0;
+  if (live) {
+    th = theta[c * (M + 1) + k];
+    for (long j = j0; j < j1; j++) tot += col[j * (M + 1)];
+  }
+  s_tot[seg][lane] = tot;
+  __syncthreads();   // every read of the old state is behind this barrier, its one write after it
+  if (!live) return;
+  unsigned run = th;
+  for (int s = 0; s < seg; s++) run += s_tot[s][lane];
+  if (seg == 0) {
+    unsigned all = th;
+    for (int s = 0; s < kScanSegs; s++) all += s_tot[s][lane];
+    theta[c * (M + 1) + k] = all;
+  }
+  for (long j = j0; j < j1; j++) {
+    const unsigned v = col[j * (M + 1)];
+    col[j * (M + 1)] = run;
+    run += v;
+  }
+}
+
+__global__ __launch_bounds__(kPvocWG) void k_pvoc_walk(const cpx *__restrict__ frames, long cstride, long nf, int M,
+                                                       long nch, int tiles, long items, float kf,
+                                                       const unsigned *__restrict__ bases, cpx *__restrict__ spec,
+                                                       long sstride) {
+#pragma unroll 1
+  for (long item = blockIdx.x; item < items; item += gridDim.x) {
+    int tile;
+    long j, c;
+    pvoc_item(item, tiles, nch, tile, j, c);
+    const int k = tile * kPvocWG + (int)threadIdx.x;
+    if (k > M) continue;
+    const long f0 = j * kPvocChunk, f1 = f0 + kPvocChunk < nf ? f0 + kPvocChunk : nf;
+    const cpx *in = frames + c * cstride + f0 * (M + 1) + k;
+    cpx *row = spec + c * sstride + f0 * M;
+    unsigned th = bases[(c * nch + j) * (M + 1) + k];
+    for (long f = f0; f < f1; f++, in += M + 1, row += M) {
+      const cpx af = *in;
+      th += pvoc_inc(af.y, kf);
+      float sn, cs;
+      sincospif((float)(int)th * 4.656612873077393e-10f, &sn, &cs);   // 2^-31: the phase in half turns, [-1, 1)
+      const float re = af.x * cs, im = af.x * sn;
+      // the packed layout: Re P[0] = Re z[0], Im P[0] = Re z[M], bin M/2 conjugated back
+      if (k == 0) reinterpret_cast<float *>(row)[0] = re;
+      else if (k == M) reinterpret_cast<float *>(row)[1] = re;
+      else row[k] = mk(re, k == (M >> 1) ? -im : im);
+    }
+  }
+}
+
+static int pvoc_grid(long items, const DeviceInfo &di) {
+  const long cap = (long)di.num_cus * 16;
+  return (int)(items < cap ? items : cap);
+}
+
+hipError_t launch_pvoc_analyze(const PvocArgs &a, const DeviceInfo &di, hipStream_t s) {
+  if (a.F <= 0 || a.channels <= 0) return hipSuccess;
+  const int tiles = (a.M + 1 + kPvocWG - 1) / kPvocWG;
+  const long groups = (a.F + kPvocRun - 1) / kPvocRun, items = (long)a.channels * groups * tiles;
+  hipLaunchKernelGGL(k_pvoc_analyze, dim3(pvoc_grid(items, di)), dim3(kPvocWG), 0, s, a.spec_in, a.frames_out, a.prev,
+                     a.etab, a.F, a.M, groups, tiles, items, a.sh, a.srs);
+  return hipGetLastError();
+}
+
+hipError_t launch_pvoc_synth(const PvocArgs &a, long f0, long nf, const DeviceInfo &di, hipStream_t s) {
+  if (nf <= 0 || a.channels <= 0) return hipSuccess;
+  const int tiles = (a.M + 1 + kPvocWG - 1) / kPvocWG;
+  const long nch = (nf + kPvocChunk - 1) / kPvocChunk, items = (long)a.channels * nch * tiles;
+  const long cstride = a.F * (a.M + 1), sstride = a.F * a.M;
+  const cpx *frames = reinterpret_cast<const cpx *>(a.frames_in) + f0 * (a.M + 1);
+  const int grid = pvoc_grid(items, di);
+  hipLaunchKernelGGL(k_pvoc_sums, dim3(grid), dim3(kPvocWG), 0, s, frames, cstride, nf, a.M, nch, tiles, items, a.kf,
+                     a.sums);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const int stiles = (a.M + 1 + kScanBins - 1) / kScanBins;
+  hipLaunchKernelGGL(k_pvoc_scan, dim3(stiles * a.channels), dim3(kScanBins * kScanSegs), 0, s, a.sums, a.theta, a.M, nch,
+                     stiles);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_pvoc_walk, dim3(grid), dim3(kPvocWG), 0, s, frames, cstride, nf, a.M, nch, tiles, items, a.kf,
+                     a.sums, a.spec_out + f0 * a.M, sstride);
+  return hipGetLastError();
+}
+
+}  // namespace clfa
