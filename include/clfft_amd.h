@@ -369,6 +369,68 @@ CLFA_API int clfa_pvoc_scan_chunk(void);
 CLFA_API int clfa_pvoc_read_phase(clfa_pvoc *pv, unsigned *host);
 CLFA_API int clfa_pvoc_read_prev(clfa_pvoc *pv, float *host);
 
+/* ---- operations on (amp, freq) frames: pitch scale, frequency shift, timed read ---- */
+/* Stateless: they read frames and write frames of the layout above, never touch prev or theta, and allocate nothing
+ * in a device call (their tables are built by clfa_pvoc_create), so every device call can be captured.  Rules of the
+ * object's other calls: asynchronous on `stream`, one stream at a time, the current device left as found; a frame
+ * count of 0 succeeds and does nothing; a bad argument, or an output that overlaps an input (the frames or the
+ * per-frame array) even partly, is CLFA_INVALID_VALUE and writes nothing.  Argument checks that need no device come
+ * first: on an object whose creation found no device a bad argument is still CLFA_INVALID_VALUE, a good one the
+ * object's error.  The blocking forms take host arrays and also check the per-frame values; the device forms cannot.
+ *
+ * cf = (float)(sr / size), bpf = (float)(size / sr), both divided in double.  Every float32 operation below is rounded
+ * on its own (no fused multiply-add); fl() marks a rounding.  An EMPTY output bin j is (0, fl(j cf)): silent, at its
+ * bin centre.  tests/pvoc_ops_model.py restates all of it in numpy.
+ *
+ * Pitch scale.  scale: F float32, one per frame, shared by the channels; every value finite and in [0.25, 4] (the
+ * blocking form checks; in the device form a value outside the range, or a NaN, makes bins 1..M-1 of that frame EMPTY).
+ * coefs is used with keepform only, and then 1 <= coefs < M.  Per channel and frame, s = scale[f]:
+ *   bins 0 and M are copied unchanged;
+ *   for k = 1..M-1 ascending, j = (int)floorf(fl(k s) + 0.5f); if 1 <= j <= M-1, bin j takes source k, a later k
+ *   replacing an earlier one; a bin j in 1..M-1 that no k reaches is EMPTY;
+ *   out[j] = (fl(gain amp[k]), fl(freq[k] s)), or with keepform (fl(fl(fl(gain amp[k]) / env[k]) env[j]), fl(freq[k] s)).
+ * The kernels compute the map as a gather (j -> the largest k that reaches it; k -> j is monotone): deterministic, no
+ * atomics.
+ *
+ * env, the cepstrally smoothed amplitude of the INPUT frame: L[k] = logf(fmaxf(amp[k], 1e-20f)), k = 0..M (a NaN amp
+ * takes the floor); Lext[n] = L[min(n, size - n)], n < size; c0 = mean(Lext), a_q = (2 / size) sum_n Lext[n]
+ * cos(2 pi n q / size); logE[k] = c0 + sum_{q = 1..coefs} a_q cos(2 pi k q / size); env[k] = expf(logE[k]).  The kernel
+ * computes it as the packed forward real transform of Lext (Clrfft's, scaled), every bin above coefs and the Nyquist half
+ * of bin 0 set to zero, and the unscaled inverse, both in LDS; the frame is read once and written once, no workspace.
+ *
+ * Frequency shift.  shift: F float32 in Hz, finite (the blocking form checks).  1 <= lowest_bin <= M-1.  Per frame,
+ * t = fl(shift[f] bpf), d = (int)rintf(t):
+ *   bins 0, M and 1 <= j < lowest_bin are copied unchanged;
+ *   for lowest_bin <= j <= M-1 the source is k = j - d; if lowest_bin <= k <= M-1 the bin takes the amp of k exactly as
+ *   in the pitch scale (with or without keepform) and freq = fl(freq[k] + shift[f]); otherwise it is EMPTY.  Where
+ *   |t| <= M does not hold (a shift past every bin, or a NaN in the device form) every such bin is EMPTY.
+ *
+ * Timed read.  frames_in holds Fin frames per channel, 1 <= Fin <= 2^24; pos: Fout float32 positions in frames, shared
+ * by the channels; frames_out holds Fout frames per channel.  Per output frame g:
+ *   p = fminf(fmaxf(pos[g], 0), (float)(Fin - 1)) (a NaN position reads frame 0); i = (int)floorf(p); a = p - (float)i;
+ *   i1 = min(i + 1, Fin - 1); where a == 0 amp and freq of every bin are those of frame i, copied; otherwise each is
+ *   fl(x0 + fl(a fl(x1 - x0))), x0 = in[i], x1 = in[i1].
+ *
+ * Kernels: "k_pvoc_map" (scale and shift without keepform), "k_pvoc_formant" (with keepform: one workgroup holds the
+ * frames of a group in LDS, transforms, lifters, transforms back and applies the map), "k_pvoc_read".  One launch per
+ * call.  CLFA_PVOC_OPS_GRID_MAX, read at creation, lowers the number of workgroups a launch may have (a tuning and test
+ * switch: the results do not depend on it). */
+CLFA_API int clfa_pvoc_scale_dev(clfa_pvoc *pv, const void *frames_in, void *frames_out, long F, const void *scale,
+                                 int keepform, float gain, int coefs, void *stream);
+CLFA_API int clfa_pvoc_shift_dev(clfa_pvoc *pv, const void *frames_in, void *frames_out, long F, const void *shift,
+                                 int lowest_bin, int keepform, float gain, int coefs, void *stream);
+CLFA_API int clfa_pvoc_read_dev(clfa_pvoc *pv, const void *frames_in, long Fin, const void *pos, void *frames_out,
+                                long Fout, void *stream);
+/* host arrays, copied in and out, blocking */
+CLFA_API int clfa_pvoc_scale(clfa_pvoc *pv, const float *frames_in, float *frames_out, long F, const float *scale,
+                             int keepform, float gain, int coefs);
+CLFA_API int clfa_pvoc_shift(clfa_pvoc *pv, const float *frames_in, float *frames_out, long F, const float *shift,
+                             int lowest_bin, int keepform, float gain, int coefs);
+CLFA_API int clfa_pvoc_read(clfa_pvoc *pv, const float *frames_in, long Fin, const float *pos, float *frames_out,
+                            long Fout);
+/* op: 0 = scale, 1 = shift, 2 = read; the kernel's name as above ("" for a failed object or an unknown op) */
+CLFA_API const char *clfa_pvoc_ops_kernel_name(const clfa_pvoc *pv, int op, int keepform);
+
 /* ---- convolution matrix (extension: nothing of the reference's) ------------- */
 /* Uniformly partitioned overlap-add convolution of `inputs` signals with an outputs x inputs matrix of static responses:
  * y_o = sum over i of x_i * h_{o,i}.

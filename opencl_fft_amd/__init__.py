@@ -400,6 +400,96 @@ class Pvoc(_Handle):
         check(lib().clfa_pvoc_synthesize(self._h, frames.ctypes.data, out.ctypes.data, F), "Pvoc.synthesize")
         return out
 
+    # ---- frames -> frames: pitch scale, frequency shift, timed read (stateless; clfft_amd.h) ----
+
+    def ops_kernel_name(self, op, keepform=False):
+        """op "scale", "shift" or "read" -> "k_pvoc_map" / "k_pvoc_formant" (keepform) / "k_pvoc_read" ("" for a failed object)"""
+        return lib().clfa_pvoc_ops_kernel_name(self._h, {"scale": 0, "shift": 1, "read": 2}.get(op, -1),
+                                               int(bool(keepform))).decode()
+
+    def _frames_shape(self, shape):
+        """F of a (channels, F, M + 1, 2) shape (or (F, M + 1, 2) for one channel), else None"""
+        f = tuple(shape)
+        if len(f) == 3 and self.channels == 1:
+            f = (1,) + f
+        if len(f) != 4 or f[0] != self.channels or f[2:] != (self.M + 1, 2):
+            return None
+        return f[1]
+
+    def _ops_device(self, frames_in, frames_out, par, stream):
+        """(Fin, Fout, the per-frame tensor, stream) of a device call, None for bad tensors; a plain number becomes a
+        tensor of Fout copies"""
+        import torch
+        Fin, Fout = self._frames_shape(frames_in.shape), self._frames_shape(frames_out.shape)
+        if (Fin is None or Fout is None or frames_in.dtype != torch.float32 or frames_out.dtype != torch.float32
+                or not frames_in.is_contiguous() or not frames_out.is_contiguous()):
+            return None
+        if not hasattr(par, "data_ptr"):
+            par = torch.full((Fout,), float(par), dtype=torch.float32, device=frames_out.device)
+        if par.dtype != torch.float32 or tuple(par.shape) != (Fout,) or not par.is_contiguous():
+            return None
+        return Fin, Fout, par, _stream_of(frames_out, stream)
+
+    def scale_device(self, frames_in, frames_out, scale, keepform=False, gain=1.0, coefs=80, stream=None):
+        """pitch scale (Csound's pvscale): torch frames (channels, F, size/2 + 1, 2) float32 -> frames_out of the same
+        shape; scale: a number or a float32 device tensor (F,), each in [0.25, 4]; keepform: the formants (the
+        cepstral envelope of `coefs` coefficients) stay where they are.  Asynchronous on `stream`."""
+        a = self._ops_device(frames_in, frames_out, scale, stream)
+        if a is None or a[0] != a[1]:
+            return CL_INVALID_VALUE
+        return lib().clfa_pvoc_scale_dev(self._h, frames_in.data_ptr(), frames_out.data_ptr(), a[1], a[2].data_ptr(),
+                                         int(bool(keepform)), float(gain), int(coefs), a[3])
+
+    def shift_device(self, frames_in, frames_out, shift, lowest_bin=1, keepform=False, gain=1.0, coefs=80, stream=None):
+        """frequency shift (Csound's pvshift): the bins from lowest_bin up move by shift Hz (a number or a float32
+        device tensor (F,)), rounded to whole bins; the bins below are copied"""
+        a = self._ops_device(frames_in, frames_out, shift, stream)
+        if a is None or a[0] != a[1]:
+            return CL_INVALID_VALUE
+        return lib().clfa_pvoc_shift_dev(self._h, frames_in.data_ptr(), frames_out.data_ptr(), a[1], a[2].data_ptr(),
+                                         int(lowest_bin), int(bool(keepform)), float(gain), int(coefs), a[3])
+
+    def read_device(self, frames_in, pos, frames_out, stream=None):
+        """timed read (Csound's pvsbufread): frames_out[:, g] = frames_in read at the position pos[g] in frames (float32
+        device tensor (Fout,)), clamped to the ends and interpolated linearly between neighbouring frames"""
+        a = self._ops_device(frames_in, frames_out, pos, stream)
+        if a is None or not hasattr(pos, "data_ptr"):
+            return CL_INVALID_VALUE
+        return lib().clfa_pvoc_read_dev(self._h, frames_in.data_ptr(), a[0], a[2].data_ptr(), frames_out.data_ptr(),
+                                        a[1], a[3])
+
+    def _ops_host(self, frames, par, Fout=None):
+        frames = np.ascontiguousarray(frames, dtype=np.float32)
+        Fin = self._frames_shape(frames.shape)
+        if Fin is None:
+            raise ValueError("frames must be (%d, F, %d, 2)" % (self.channels, self.M + 1))
+        Fout = Fin if Fout is None else Fout
+        par = np.ascontiguousarray(np.broadcast_to(np.asarray(par, dtype=np.float32), (Fout,)))
+        lead = frames.shape[:-3]
+        return frames, Fin, par, np.zeros(lead + (Fout, self.M + 1, 2), np.float32)
+
+    def scale(self, frames, scale, keepform=False, gain=1.0, coefs=80):
+        """host form of scale_device, blocking: returns the new frames; a value of `scale` outside [0.25, 4] raises
+        ClError(CL_INVALID_VALUE)"""
+        frames, F, par, out = self._ops_host(frames, scale)
+        check(lib().clfa_pvoc_scale(self._h, frames.ctypes.data, out.ctypes.data, F, par.ctypes.data, int(bool(keepform)),
+                                    float(gain), int(coefs)), "Pvoc.scale")
+        return out
+
+    def shift(self, frames, shift, lowest_bin=1, keepform=False, gain=1.0, coefs=80):
+        """host form of shift_device, blocking"""
+        frames, F, par, out = self._ops_host(frames, shift)
+        check(lib().clfa_pvoc_shift(self._h, frames.ctypes.data, out.ctypes.data, F, par.ctypes.data, int(lowest_bin),
+                                    int(bool(keepform)), float(gain), int(coefs)), "Pvoc.shift")
+        return out
+
+    def read(self, frames, pos):
+        """host form of read_device, blocking: pos float32 (Fout,) -> frames (.., Fout, size/2 + 1, 2)"""
+        pos = np.ascontiguousarray(pos, dtype=np.float32).reshape(-1)
+        frames, Fin, par, out = self._ops_host(frames, pos, pos.size)
+        check(lib().clfa_pvoc_read(self._h, frames.ctypes.data, Fin, par.ctypes.data, out.ctypes.data, pos.size), "Pvoc.read")
+        return out
+
 
 def packed_to_onesided(spec):
     """Clrfft's packed spectra (..., M) -> the M + 1 bins of np.fft.rfft / torch.stft(onesided) (numpy or torch):

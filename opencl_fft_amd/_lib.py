@@ -119,6 +119,13 @@ SYMBOLS = [
     ("clfa_pvoc_scan_chunk", C.c_int, []),
     ("clfa_pvoc_read_phase", C.c_int, [_vp, _vp]),
     ("clfa_pvoc_read_prev", C.c_int, [_vp, _vp]),
+    ("clfa_pvoc_scale_dev", C.c_int, [_vp, _vp, _vp, C.c_long, _vp, C.c_int, C.c_float, C.c_int, _vp]),
+    ("clfa_pvoc_shift_dev", C.c_int, [_vp, _vp, _vp, C.c_long, _vp, C.c_int, C.c_int, C.c_float, C.c_int, _vp]),
+    ("clfa_pvoc_read_dev", C.c_int, [_vp, _vp, C.c_long, _vp, _vp, C.c_long, _vp]),
+    ("clfa_pvoc_scale", C.c_int, [_vp, _vp, _vp, C.c_long, _vp, C.c_int, C.c_float, C.c_int]),
+    ("clfa_pvoc_shift", C.c_int, [_vp, _vp, _vp, C.c_long, _vp, C.c_int, C.c_int, C.c_float, C.c_int]),
+    ("clfa_pvoc_read", C.c_int, [_vp, _vp, C.c_long, _vp, _vp, C.c_long]),
+    ("clfa_pvoc_ops_kernel_name", C.c_char_p, [_vp, C.c_int, C.c_int]),
 ]
 
 _LIB = None

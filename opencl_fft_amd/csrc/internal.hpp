@@ -273,6 +273,25 @@ hipError_t launch_pvoc_analyze(const PvocArgs &a, const DeviceInfo &di, hipStrea
 // (one lane per channel and bin) their bases in place and the new theta, then the walk that writes the spectra
 hipError_t launch_pvoc_synth(const PvocArgs &a, long f0, long nf, const DeviceInfo &di, hipStream_t s);
 
+// ---- operations on (amp, freq) frames (pvoc_ops.hip): pitch scale, frequency shift, timed read ----
+enum PvocOp { PVOC_SCALE = 0, PVOC_SHIFT = 1, PVOC_READ = 2 };
+struct PvocOpsArgs {
+  int op = PVOC_SCALE;
+  int logn = 0;                    // log2(M): the formant kernel's transform length (complex)
+  int M = 0, channels = 0;
+  long F = 0;                      // output frames per channel (scale, shift: also the input's)
+  long Fin = 0;                    // read: input frames per channel
+  const cpx *in = nullptr;         // frames as (amp, freq) pairs
+  cpx *out = nullptr;
+  const float *par = nullptr;      // F values: scale, shift in Hz, or positions
+  int lowest = 1, keepform = 0, coefs = 1;
+  float gain = 1.f, cf = 0.f, bpf = 0.f;   // sr / size, size / sr
+  const cpx *half = nullptr, *w2 = nullptr;   // formant: the Clrfft tables of size (forward sign)
+  int grid_max = 0;                // > 0: at most this many workgroups
+};
+// one launch: k_pvoc_map, k_pvoc_formant<logn> (keepform) or k_pvoc_read
+hipError_t launch_pvoc_ops(const PvocOpsArgs &a, const DeviceInfo &di, hipStream_t s);
+
 // ---- direct convolution ----------------------------------------------------------
 struct DconvPlan {
   int C;    // taps per workgroup

@@ -20,6 +20,12 @@ struct clfa_pvoc {
   DevBuf ws;              // the scan's chunk sums: allocated by the first synthesis that needs it
   long cap = 1;           // chunks per sub-batch (CLFA_PVOC_CHUNKS_MAX: tuning switch, read at creation)
   DevBuf sspec, sframes;  // staging of the host entry points
+  // the frame operations (pvoc_ops.hip): size / sr, the Clrfft tables of size (forward sign) for the formant envelope,
+  // the cap on a launch's workgroups (CLFA_PVOC_OPS_GRID_MAX, 0 = none), staging of their host forms
+  float bpf = 0.f;
+  DevBuf half, w2;
+  int ops_grid_max = 0;
+  DevBuf sop_out, sop_par;
   StreamOrder order;
 };
 
@@ -60,16 +66,21 @@ static int pvoc_setup(clfa_pvoc *p, int device, int size, int hop, double sr, in
   p->sh = (float)((double)size / hop);
   p->srs = (float)(sr / size);
   p->kf = (float)(hop / sr);
+  p->bpf = (float)(size / sr);
   // sub-batches bound the scan's workspace (4 bytes per channel, chunk and bin) to about 64 MiB
   p->cap = (64L << 20) / ((long)sizeof(unsigned) * (long)pvoc_bins(p));
   p->cap = p->cap < 1 ? 1 : (p->cap > 4096 ? 4096 : p->cap);
   if (const char *env = getenv("CLFA_PVOC_CHUNKS_MAX")) {
     if (atol(env) > 0 && atol(env) < p->cap) p->cap = atol(env);
   }
+  if (const char *env = getenv("CLFA_PVOC_OPS_GRID_MAX")) {
+    if (atol(env) > 0 && atol(env) < 0x7fffffffL) p->ops_grid_max = (int)atol(env);
+  }
   int e = device_info(device, p->di);
   if (e) return e;
   ENTER_DEVICE(device);
   HIP_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
+  if ((e = upload_half(p->half, p->M)) || (e = upload_w2(p->w2, p->M, -1.f))) return e;
   std::vector<cpx> tab(p->M + 1);
   for (int k = 0; k <= p->M; k++) {
     const double a = -2 * kPI * (double)(((long)k * hop) % size) / size;
@@ -190,6 +201,115 @@ int clfa_pvoc_synthesize_dev(clfa_pvoc *p, const void *frames, void *spectra_out
     HIP_TRY(launch_pvoc_synth(a, f0, nf, p->di, s));
   }
   return CLFA_SUCCESS;
+}
+
+// ---------------------------------------------------------------------------------
+// frames -> frames: pitch scale, frequency shift, timed read (pvoc_ops.hip)
+// ---------------------------------------------------------------------------------
+
+// The checks that need no device, in the order of the header: they come before the object's own error, so that on an
+// object whose creation found no device a bad argument is still an invalid value (M != 0: the creation arguments were
+// good).  0 = go on, 1 = a successful no-op, < 0 = the error.  F: output frames, Fin: input frames (== F for scale and shift).
+static int pvoc_ops_check(const clfa_pvoc *p, int op, const void *in, long Fin, const void *par, const void *out, long F,
+                          int lowest, int keepform, int coefs, bool device_ptrs) {
+  if (!p) return CLFA_INVALID_VALUE;
+  if (!p->M) return p->err ? p->err : CLFA_INVALID_VALUE;
+  if (F < 0 || F > 0x7fffffffL) return CLFA_INVALID_VALUE;
+  if (op == PVOC_READ && (Fin < 1 || Fin > (1L << 24))) return CLFA_INVALID_VALUE;
+  if (op == PVOC_SHIFT && (lowest < 1 || lowest > p->M - 1)) return CLFA_INVALID_VALUE;
+  if (op != PVOC_READ && keepform && (coefs < 1 || coefs >= p->M)) return CLFA_INVALID_VALUE;
+  if (F == 0) return 1;
+  if (!in || !out || !par) return CLFA_INVALID_VALUE;
+  if (device_ptrs && (((uintptr_t)in & 7) || ((uintptr_t)out & 7) || ((uintptr_t)par & 3))) return CLFA_INVALID_VALUE;
+  const size_t ibytes = 2 * sizeof(float) * pvoc_bins(p) * (size_t)Fin, obytes = 2 * sizeof(float) * pvoc_bins(p) * (size_t)F;
+  if (spans_overlap(in, ibytes, out, obytes) || spans_overlap(par, sizeof(float) * (size_t)F, out, obytes))
+    return CLFA_INVALID_VALUE;
+  return CLFA_SUCCESS;
+}
+
+static int pvoc_ops_dev(clfa_pvoc *p, int op, const void *in, long Fin, const void *par, void *out, long F, int lowest,
+                        int keepform, float gain, int coefs, void *stream) {
+  const int chk = pvoc_ops_check(p, op, in, Fin, par, out, F, lowest, keepform, coefs, true);
+  if (chk < 0) return chk;
+  if (p->err) return p->err;
+  if (chk == 1) return CLFA_SUCCESS;
+  ENTER_DEVICE(p->di.device);
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(p->order.use(s));
+  PvocOpsArgs a;
+  a.op = op;
+  a.logn = ilog2(p->M);
+  a.M = p->M;
+  a.channels = p->channels;
+  a.F = F;
+  a.Fin = Fin;
+  a.in = (const cpx *)in;
+  a.out = (cpx *)out;
+  a.par = (const float *)par;
+  a.lowest = lowest;
+  a.keepform = keepform != 0;
+  a.coefs = coefs;
+  a.gain = gain;
+  a.cf = p->srs;
+  a.bpf = p->bpf;
+  a.half = (const cpx *)p->half.p;
+  a.w2 = (const cpx *)p->w2.p;
+  a.grid_max = p->ops_grid_max;
+  HIP_TRY(launch_pvoc_ops(a, p->di, s));
+  return CLFA_SUCCESS;
+}
+
+// the blocking forms: the same checks on the host arrays, then the per-frame values, then copies around the device form
+static int pvoc_ops_host(clfa_pvoc *p, int op, const float *in, long Fin, const float *par, float *out, long F, int lowest,
+                         int keepform, float gain, int coefs) {
+  const int chk = pvoc_ops_check(p, op, in, Fin, par, out, F, lowest, keepform, coefs, false);
+  if (chk < 0) return chk;
+  for (long f = 0; f < F && op != PVOC_READ; f++) {
+    if (!std::isfinite(par[f]) || (op == PVOC_SCALE && !(par[f] >= 0.25f && par[f] <= 4.f))) return CLFA_INVALID_VALUE;
+  }
+  if (p->err) return p->err;
+  if (chk == 1) return CLFA_SUCCESS;
+  const size_t ibytes = 2 * sizeof(float) * pvoc_bins(p) * (size_t)Fin, obytes = 2 * sizeof(float) * pvoc_bins(p) * (size_t)F;
+  ENTER_DEVICE(p->di.device);
+  int e = p->sframes.ensure(ibytes);
+  if (!e) e = p->sop_out.ensure(obytes);
+  if (!e) e = p->sop_par.ensure(sizeof(float) * (size_t)F);
+  if (e) return e;
+  HIP_TRY(hipMemcpyAsync(p->sframes.p, in, ibytes, hipMemcpyHostToDevice, p->stream));
+  HIP_TRY(hipMemcpyAsync(p->sop_par.p, par, sizeof(float) * (size_t)F, hipMemcpyHostToDevice, p->stream));
+  if ((e = pvoc_ops_dev(p, op, p->sframes.p, Fin, p->sop_par.p, p->sop_out.p, F, lowest, keepform, gain, coefs, p->stream)))
+    return e;
+  HIP_TRY(hipMemcpyAsync(out, p->sop_out.p, obytes, hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return CLFA_SUCCESS;
+}
+
+int clfa_pvoc_scale_dev(clfa_pvoc *p, const void *frames_in, void *frames_out, long F, const void *scale, int keepform,
+                        float gain, int coefs, void *stream) {
+  return pvoc_ops_dev(p, PVOC_SCALE, frames_in, F, scale, frames_out, F, 1, keepform, gain, coefs, stream);
+}
+int clfa_pvoc_shift_dev(clfa_pvoc *p, const void *frames_in, void *frames_out, long F, const void *shift, int lowest_bin,
+                        int keepform, float gain, int coefs, void *stream) {
+  return pvoc_ops_dev(p, PVOC_SHIFT, frames_in, F, shift, frames_out, F, lowest_bin, keepform, gain, coefs, stream);
+}
+int clfa_pvoc_read_dev(clfa_pvoc *p, const void *frames_in, long Fin, const void *pos, void *frames_out, long Fout,
+                       void *stream) {
+  return pvoc_ops_dev(p, PVOC_READ, frames_in, Fin, pos, frames_out, Fout, 1, 0, 1.f, 1, stream);
+}
+int clfa_pvoc_scale(clfa_pvoc *p, const float *frames_in, float *frames_out, long F, const float *scale, int keepform,
+                    float gain, int coefs) {
+  return pvoc_ops_host(p, PVOC_SCALE, frames_in, F, scale, frames_out, F, 1, keepform, gain, coefs);
+}
+int clfa_pvoc_shift(clfa_pvoc *p, const float *frames_in, float *frames_out, long F, const float *shift, int lowest_bin,
+                    int keepform, float gain, int coefs) {
+  return pvoc_ops_host(p, PVOC_SHIFT, frames_in, F, shift, frames_out, F, lowest_bin, keepform, gain, coefs);
+}
+int clfa_pvoc_read(clfa_pvoc *p, const float *frames_in, long Fin, const float *pos, float *frames_out, long Fout) {
+  return pvoc_ops_host(p, PVOC_READ, frames_in, Fin, pos, frames_out, Fout, 1, 0, 1.f, 1);
+}
+const char *clfa_pvoc_ops_kernel_name(const clfa_pvoc *p, int op, int keepform) {
+  if (!p || p->err || op < PVOC_SCALE || op > PVOC_READ) return "";
+  return op == PVOC_READ ? "k_pvoc_read" : (keepform ? "k_pvoc_formant" : "k_pvoc_map");
 }
 
 int clfa_pvoc_analyze(clfa_pvoc *p, const float *spectra, float *frames_out, long F) {

@@ -1,0 +1,283 @@
+// pvoc_ops.hip — operations on the (amp, freq) frames of clfa_pvoc (include/clfft_amd.h): pitch scale, frequency shift
+// and timed read.  All three are stateless, one launch per call, deterministic (gathers: no atomics).
+//
+//   k_pvoc_map      scale and shift without keepform: a lane takes output bin j of one frame, finds its source bin and
+//                   writes the pair; rows of consecutive bins, 8 bytes per lane, no LDS.
+//   k_pvoc_read     the frame sequence read at the positions pos[g]: a copy of frame i or the interpolation of frames
+//                   i and i + 1; rows of consecutive bins, 8 bytes per lane.
+//   k_pvoc_formant  scale and shift with keepform.  A workgroup holds FPW = LdsGeom::FPW frames: each frame is read once
+//                   into LDS (the pairs, and the logs of its amps as the even extension Lext), the packed forward real
+//                   transform of Lext runs on the pass chain of k_stft_analyze, the pair step lifters (forward pair map,
+//                   zeros above coefs, inverse pair map in one visit of the pair), the inverse runs on the chain of
+//                   k_stft_synth, expf turns the first M + 1 samples into env in place, and the map gathers amp, freq
+//                   and the two envelope values from LDS.  One read and one write of the frame, no workspace.  n = 8192
+//                   reads its twiddle tables from L1/L2 (k_stft_synth's LDS budget: here 70 KiB of exchange buffer and
+//                   64 KiB of frame leave no room for 48 KiB of tables).
+//
+// Every float32 step of the definitions is rounded on its own: the device functions below switch contraction off, as
+// pvoc_inc does (pvoc_kernels.hip).  tests/pvoc_ops_model.py restates them.
+#include "fft_wg.hpp"
+
+namespace clfa {
+
+namespace {
+
+constexpr int kOpsWG = 256;            // lanes = bins per workgroup tile (k_pvoc_map, k_pvoc_read)
+constexpr int kSrcEmpty = -1, kSrcCopy = -2;
+
+// the pitch scale's map k -> j
+__device__ __forceinline__ int pvoc_scale_j(int k, float s) {
+#pragma clang fp contract(off)
+  const float t = (float)k * s;
+  return (int)floorf(t + 0.5f);
+}
+
+// source bin of output bin j: k in 1..M-1, kSrcEmpty, or kSrcCopy (the bin is handed over unchanged).
+// Scale: k -> j is monotone, so the source — the last k of the serial definition — is the largest k with j(k) <= j if
+// that k lands on j; it lies next to (j + 1/2) / s, and the two loops move the estimate there (a few steps: s >= 1/4).
+__device__ __forceinline__ int pvoc_source(int op, int j, int M, int lowest, float par, float bpf) {
+#pragma clang fp contract(off)
+  if (j == 0 || j == M) return kSrcCopy;
+  if (op == PVOC_SCALE) {
+    if (!(par >= 0.25f && par <= 4.f)) return kSrcEmpty;
+    int k = (int)(((float)j + 0.5f) / par);
+    k = k < 1 ? 1 : (k > M - 1 ? M - 1 : k);
+    while (k < M - 1 && pvoc_scale_j(k + 1, par) <= j) k++;
+    while (k >= 1 && pvoc_scale_j(k, par) > j) k--;
+    return (k >= 1 && pvoc_scale_j(k, par) == j) ? k : kSrcEmpty;
+  }
+  if (j < lowest) return kSrcCopy;
+  const float t = par * bpf;
+  if (!(fabsf(t) <= (float)M)) return kSrcEmpty;   // past every bin, or not a number
+  const int k = j - (int)rintf(t);
+  return (k >= lowest && k <= M - 1) ? k : kSrcEmpty;
+}
+
+__device__ __forceinline__ cpx pvoc_empty(int j, float cf) {
+#pragma clang fp contract(off)
+  return mk(0.f, (float)j * cf);
+}
+
+// (amp, freq) of a bin that takes source sv; amp is the finished amplitude
+__device__ __forceinline__ cpx pvoc_moved(int op, cpx sv, float par, float amp) {
+#pragma clang fp contract(off)
+  return mk(amp, op == PVOC_SCALE ? sv.y * par : sv.y + par);
+}
+
+__device__ __forceinline__ float pvoc_gain(float gain, float amp) {
+#pragma clang fp contract(off)
+  return gain * amp;
+}
+
+__device__ __forceinline__ float pvoc_keepform(float gain, float amp, float env_k, float env_j) {
+#pragma clang fp contract(off)
+  const float g = gain * amp;
+  const float w = g / env_k;
+  return w * env_j;
+}
+
+__device__ __forceinline__ cpx pvoc_lerp(cpx x0, cpx x1, float a) {
+#pragma clang fp contract(off)
+  const float dx = x1.x - x0.x, dy = x1.y - x0.y;
+  const float px = a * dx, py = a * dy;
+  return mk(x0.x + px, x0.y + py);
+}
+
+}  // namespace
+
+// item -> (frame b = c * F + f, bin tile), the tile fastest
+__global__ __launch_bounds__(kOpsWG) void k_pvoc_map(const cpx *__restrict__ in, cpx *__restrict__ out,
+                                                     const float *__restrict__ par, long F, int M, int tiles, long items,
+                                                     int op, int lowest, float gain, float cf, float bpf) {
+#pragma unroll 1
+  for (long item = blockIdx.x; item < items; item += gridDim.x) {
+    const long b = item / tiles;
+    const int j = (int)(item - b * tiles) * kOpsWG + (int)threadIdx.x;
+    if (j > M) continue;
+    const float s = par[b % F];
+    const cpx *row = in + b * (M + 1);
+    const int src = pvoc_source(op, j, M, lowest, s, bpf);
+    cpx o;
+    if (src == kSrcCopy) o = row[j];
+    else if (src == kSrcEmpty) o = pvoc_empty(j, cf);
+    else {
+      const cpx sv = row[src];
+      o = pvoc_moved(op, sv, s, pvoc_gain(gain, sv.x));
+    }
+    out[b * (M + 1) + j] = o;
+  }
+}
+
+// item -> (channel, output frame g, bin tile), the tile fastest
+__global__ __launch_bounds__(kOpsWG) void k_pvoc_read(const cpx *__restrict__ in, cpx *__restrict__ out,
+                                                      const float *__restrict__ pos, long Fin, long Fout, int M,
+                                                      int tiles, long items) {
+#pragma unroll 1
+  for (long item = blockIdx.x; item < items; item += gridDim.x) {
+    const long b = item / tiles;
+    const int j = (int)(item - b * tiles) * kOpsWG + (int)threadIdx.x;
+    if (j > M) continue;
+    const long c = b / Fout, g = b - c * Fout;
+    const float p = fminf(fmaxf(pos[g], 0.f), (float)(Fin - 1));   // fmaxf(NaN, 0) = 0
+    const long i = (long)floorf(p);
+    const float a = p - (float)i;
+    const long i1 = i + 1 < Fin ? i + 1 : Fin - 1;
+    const cpx x0 = in[(c * Fin + i) * (M + 1) + j];
+    cpx o = x0;
+    if (a != 0.f) o = pvoc_lerp(x0, in[(c * Fin + i1) * (M + 1) + j], a);   // a == 0: frame i1 is not read at all
+    out[b * (M + 1) + j] = o;
+  }
+}
+
+template <int LOGN> constexpr bool pvoc_formant_tab_lds() { return LOGN <= 12; }
+
+// grid-stride over groups of FPW consecutive frames (frame index b = c * F + f; the frames are contiguous)
+template <int LOGN>
+__global__ __launch_bounds__(LdsGeom<LOGN>::WG) void k_pvoc_formant(const cpx *__restrict__ in, cpx *__restrict__ out,
+                                                                    const float *__restrict__ par, long F, long nframes,
+                                                                    int op, int lowest, int coefs, float gain, float cf,
+                                                                    float bpf, const cpx *__restrict__ tab_g,
+                                                                    const cpx *__restrict__ w2_g) {
+  using G = LdsGeom<LOGN>;
+  constexpr int N = G::N, E = G::E, T = G::T, WG = G::WG, FPW = G::FPW, B = N + 1;   // M = N, B bins per frame
+  constexpr bool TL = pvoc_formant_tab_lds<LOGN>();
+  __shared__ cpx s_tab[TL ? G::HALF : 1];
+  __shared__ cpx s_w2[TL ? N / 2 : 1];
+  __shared__ cpx s_x[FPW * G::PADN];   // the exchange buffer: Lext, its spectrum, logE, env
+  __shared__ cpx s_fr[FPW * B];        // the group's frames as read
+  const int tid = threadIdx.x;
+  const int f = tid / T, t = tid % T;
+  if constexpr (TL) {
+    for (int i = tid; i < N / 2; i += WG) {
+      s_tab[i] = tab_g[i];
+      s_w2[i] = w2_g[i];
+    }
+  }
+  const cpx *tab = TL ? s_tab : tab_g, *w2 = TL ? s_w2 : w2_g;
+  cpx *xb = s_x + f * G::PADN;
+  float *xf = reinterpret_cast<float *>(s_x);
+  // sample n of frame fi's real sequence (floats 2p, 2p + 1 of complex element p, padded)
+  auto sample = [&](int fi, int n) -> float & { return xf[2 * (fi * G::PADN + lds_pad(n >> 1)) + (n & 1)]; };
+  const long groups = (nframes + FPW - 1) / FPW;
+#pragma unroll 1
+  for (long g = blockIdx.x; g < groups; g += gridDim.x) {
+    const long b0 = g * FPW;
+    const int nv = nframes - b0 < FPW ? (int)(nframes - b0) : FPW;   // frames of a ragged last group; the other slots
+    const int live = nv * B;                                         // run the chain on stale LDS and write nothing
+    // the frames in: element idx = frame idx / B, bin idx % B; L[k] lands at samples k and size - k
+    for (int idx = tid; idx < live; idx += WG) {
+      const int fi = idx / B, k = idx - fi * B;
+      const cpx af = in[b0 * B + idx];
+      s_fr[idx] = af;
+      const float L = logf(fmaxf(af.x, 1e-20f));   // fmaxf(NaN, floor) = floor
+      sample(fi, k) = L;
+      if (k > 0 && k < N) sample(fi, 2 * N - k) = L;
+    }
+    __syncthreads();
+    cpx v[E];
+    pass_gather_padded<LOGN, G::LOGE>(v, t, xb);
+    wg_passes<LOGN, G::LOGE, 0, true>(v, t, tab, xb);
+#pragma unroll
+    for (int e = 0; e < E; e++) v[e] = cscale(v[e], 1.0f / (float)N);   // forward real plans scale by 1/M
+    __syncthreads();
+    dif_scatter_padded<LOGN, G::LOGE>(v, t, xb);
+    __syncthreads();
+    // one visit of every pair (i, N - i): the forward pair map (k_stft_analyze), the lifter on the packed bins, the
+    // inverse pair map (k_stft_synth; its table is the forward one conjugated)
+#pragma unroll
+    for (int k = 0; k < E / 2; k++) {
+      const int i = t + T * k, j = i == 0 ? N / 2 : N - i;
+      const cpx ci = xb[lds_pad(i)], cj = xb[lds_pad(j)];
+      const cpx w = w2[i];
+      const bool z = i == 0;
+      cpx oi, oj;
+      r2c_pair(ci, cj, w, oi, oj);
+      oi = mk(z ? (ci.x + ci.y) * .5f : oi.x, z ? 0.f : oi.y);   // bin 0 = (DC, Nyquist): the Nyquist half goes
+      oj = mk(z ? cj.x : oj.x, z ? cj.y : oj.y);
+      if (i > coefs) oi = mk(0.f, 0.f);
+      if (j > coefs) oj = mk(0.f, 0.f);
+      cpx ni, nj;
+      c2r_pair(oi, oj, mk(w.x, -w.y), ni, nj);
+      ni = mk(z ? oi.x + oi.y : ni.x, z ? oi.x - oi.y : ni.y);
+      nj = mk(z ? oj.x : nj.x, z ? oj.y : nj.y);
+      xb[lds_pad(i)] = ni;
+      xb[lds_pad(j)] = nj;
+    }
+    __syncthreads();
+    pass_gather_padded<LOGN, G::LOGE>(v, t, xb);
+    wg_passes<LOGN, G::LOGE, 0, false>(v, t, tab, xb);
+    __syncthreads();
+    dif_scatter_padded<LOGN, G::LOGE>(v, t, xb);
+    __syncthreads();
+    // env[k] = expf(logE[k]), k = 0..M, in place
+    for (int idx = tid; idx < live; idx += WG) {
+      const int fi = idx / B, k = idx - fi * B;
+      float &e = sample(fi, k);
+      e = expf(e);
+    }
+    __syncthreads();
+    for (int idx = tid; idx < live; idx += WG) {
+      const int fi = idx / B, j = idx - fi * B;
+      const float s = par[(b0 + fi) % F];
+      const int src = pvoc_source(op, j, N, lowest, s, bpf);
+      cpx o;
+      if (src == kSrcCopy) o = s_fr[idx];
+      else if (src == kSrcEmpty) o = pvoc_empty(j, cf);
+      else {
+        const cpx sv = s_fr[fi * B + src];
+        o = pvoc_moved(op, sv, s, pvoc_keepform(gain, sv.x, sample(fi, src), sample(fi, j)));
+      }
+      out[b0 * B + idx] = o;
+    }
+    __syncthreads();   // the group is out before the next one lands in s_fr and s_x
+  }
+}
+
+static int ops_grid(long items, long cap, int grid_max) {
+  if (grid_max > 0 && cap > grid_max) cap = grid_max;
+  return (int)(items < cap ? items : cap);
+}
+
+template <int LOGN>
+static hipError_t launch_pvoc_formant_n(const PvocOpsArgs &a, const DeviceInfo &di, hipStream_t s) {
+  using G = LdsGeom<LOGN>;
+  static int occ = 0;
+  if (!occ) {
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)k_pvoc_formant<LOGN>, G::WG, 0) != hipSuccess || nb < 1) {
+      (void)hipGetLastError();
+      nb = 1;
+    }
+    occ = nb;
+  }
+  const long nframes = (long)a.channels * a.F, groups = (nframes + G::FPW - 1) / G::FPW;
+  const int grid = ops_grid(groups, (long)di.num_cus * occ, a.grid_max);
+  hipLaunchKernelGGL((k_pvoc_formant<LOGN>), dim3(grid), dim3(G::WG), 0, s, a.in, a.out, a.par, a.F, nframes, a.op,
+                     a.lowest, a.coefs, a.gain, a.cf, a.bpf, a.half, a.w2);
+  return hipGetLastError();
+}
+
+hipError_t launch_pvoc_ops(const PvocOpsArgs &a, const DeviceInfo &di, hipStream_t s) {
+  if (a.F <= 0 || a.channels <= 0) return hipSuccess;
+  if (a.op != PVOC_READ && a.keepform) {
+    switch (a.logn) {
+#define CLFA_N(L) \
+  case L: return launch_pvoc_formant_n<L>(a, di, s);
+      CLFA_N(5) CLFA_N(6) CLFA_N(7) CLFA_N(8) CLFA_N(9) CLFA_N(10) CLFA_N(11) CLFA_N(12) CLFA_N(13)
+#undef CLFA_N
+      default:
+        return hipErrorInvalidValue;
+    }
+  }
+  const int tiles = (a.M + 1 + kOpsWG - 1) / kOpsWG;
+  const long items = (long)a.channels * a.F * tiles;
+  const int grid = ops_grid(items, (long)di.num_cus * 16, a.grid_max);
+  if (a.op == PVOC_READ)
+    hipLaunchKernelGGL(k_pvoc_read, dim3(grid), dim3(kOpsWG), 0, s, a.in, a.out, a.par, a.Fin, a.F, a.M, tiles, items);
+  else
+    hipLaunchKernelGGL(k_pvoc_map, dim3(grid), dim3(kOpsWG), 0, s, a.in, a.out, a.par, a.F, a.M, tiles, items, a.op,
+                       a.lowest, a.gain, a.cf, a.bpf);
+  return hipGetLastError();
+}
+
+}  // namespace clfa
