@@ -283,13 +283,17 @@ CLFA_API const char *clfa_dconv_blocks_kernel_name(const clfa_dconv *dc, int tim
  * Synthesis: spectra channels x F x M complex64, contiguous -> rows of L = (F - 1) * hop + size floats at signal_stride.
  * With r_f = the clfa_rfft_transform (size, inverse) output of frame f (unscaled: it gives back the windowed frame after
  * analysis), y_c[t] = sum over the frames f that cover t, in ascending f, of w[t - f hop] * r_f[t - f hop].  normalize != 0:
- * y_c[t] is divided by env[t] = sum of w[t - f hop]^2 over the same frames wherever env[t] > 1e-11, kept elsewhere.
+ * y_c[t] is divided by env[t] = sum of w[t - f hop]^2 over the same frames wherever env[t] > 1e-11, kept elsewhere.  The
+ * env[t] used is the float64 sum rounded once to float32, for every frame count (calls of fewer frames than size / hop
+ * included), so the division adds two float32 roundings to y_c[t] and nothing else.
  *
  * Device calls follow the other objects: asynchronous on `stream`, one object = one stream at a time (a change of stream
  * waits for the previous one), capturable into a hipGraph, the current device left as found.  A direction that is not the
  * plan's, and an output that overlaps an input even partly, are CLFA_INVALID_VALUE; F = 0 or channels = 0 is a successful
  * no-op.  signal: any 4-byte aligned address, any stride, any hop; spectra: 8-byte aligned.  The synthesis is
- * deterministic (no atomics): repeated calls, other streams and graph replays give the same bits. */
+ * deterministic (no atomics): repeated calls, other streams and graph replays give the same bits.
+ * CLFA_STFT_GRID_MAX, read at creation, lowers the number of workgroups a launch of either direction may have (a tuning
+ * and test switch: 0 or unset = no cap; the results do not depend on it). */
 /* argument errors (size, hop) are CLFA_INVALID_VALUE before any device lookup; a failed create still returns a handle */
 CLFA_API int clfa_stft_create(clfa_stft **st, int device, int size, int hop, const float *window, int forward);
 CLFA_API void clfa_stft_destroy(clfa_stft *st);

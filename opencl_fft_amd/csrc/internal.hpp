@@ -241,11 +241,13 @@ struct StftArgs {
   long channels = 0, nframes = 0, stride = 0;
   bool aligned8 = true;
   int normalize = 0;
+  int grid_max = 0;                // cap on a launch's workgroups (CLFA_STFT_GRID_MAX, 0 = none)
   const float *signal = nullptr;
   float *out = nullptr;
   const cpx *spec_in = nullptr;
   cpx *spec_out = nullptr;
-  const float *window = nullptr, *cum = nullptr;
+  const float *window = nullptr;
+  const double *cum = nullptr;     // the envelope's running sums (stft_plan.hpp)
   const cpx *half = nullptr, *w2 = nullptr;
 };
 hipError_t launch_stft(const StftArgs &a, const DeviceInfo &di, hipStream_t s);

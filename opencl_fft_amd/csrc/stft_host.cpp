@@ -1,5 +1,6 @@
 // stft_host.cpp — C ABI of the short-time transforms (see include/clfft_amd.h): Stft.  Shared plumbing: host.hpp.
 #include "host.hpp"
+#include "stft_plan.hpp"
 
 using namespace clfa;
 
@@ -10,11 +11,12 @@ using namespace clfa;
 struct clfa_stft {
   DeviceInfo di;
   int size = 0, hop = 0, logn = 0;
+  int grid_max = 0;   // cap on a launch's workgroups (CLFA_STFT_GRID_MAX: tuning and test switch, read at creation)
   bool fwd = true;
   int err = 0;
   char log[512];
   hipStream_t stream = nullptr;
-  DevBuf half, w2, win, cum;   // Clrfft tables of the direction, the window, its running sums of squares (synthesis)
+  DevBuf half, w2, win, cum;   // Clrfft tables of the direction, the window, its running sums of squares (synthesis, double)
   DevBuf sig, spec;            // staging of the host entry points
   StreamOrder order;
 };
@@ -34,6 +36,9 @@ static int stft_setup(clfa_stft *p, int device, int size, int hop, const float *
   }
   const int m = size / 2;
   p->logn = ilog2(m);
+  if (const char *env = getenv("CLFA_STFT_GRID_MAX")) {
+    if (atol(env) > 0 && atol(env) < 0x7fffffffL) p->grid_max = (int)atol(env);
+  }
   int e = device_info(device, p->di);
   if (e) return e;
   ENTER_DEVICE(device);
@@ -43,16 +48,10 @@ static int stft_setup(clfa_stft *p, int device, int size, int hop, const float *
   if (!window) w.assign(size, 1.0f);
   if ((e = upload(p->win, w.data(), sizeof(float) * size))) return e;
   if (!fwd) {
-    // [lo | hi]: lo[d] = sum_k w[d - k hop]^2, hi[d] = sum_k w[d + k hop]^2 (k >= 0, inside the window), in double
-    std::vector<double> lo(size), hi(size);
-    for (int d = 0; d < size; d++) lo[d] = (double)w[d] * w[d] + (d >= hop ? lo[d - hop] : 0.0);
-    for (int d = size - 1; d >= 0; d--) hi[d] = (double)w[d] * w[d] + (d + hop < size ? hi[d + hop] : 0.0);
-    std::vector<float> c(2 * (size_t)size);
-    for (int d = 0; d < size; d++) {
-      c[d] = (float)lo[d];
-      c[size + d] = (float)hi[d];
-    }
-    if ((e = upload(p->cum, c.data(), sizeof(float) * c.size()))) return e;
+    // the envelope's two running sums of w^2, kept in double: the kernel rounds once, after its lookup
+    std::vector<double> c(2 * (size_t)size);
+    stft_env_table(w.data(), size, hop, c.data());
+    if ((e = upload(p->cum, c.data(), sizeof(double) * c.size()))) return e;
   }
   return CLFA_SUCCESS;
 }
@@ -69,7 +68,8 @@ static int stft_run(clfa_stft *p, StftArgs &a, long frames, long channels, hipSt
   a.channels = channels;
   a.nframes = frames * channels;
   a.window = (const float *)p->win.p;
-  a.cum = (const float *)p->cum.p;
+  a.cum = (const double *)p->cum.p;
+  a.grid_max = p->grid_max;
   a.half = (const cpx *)p->half.p;
   a.w2 = (const cpx *)p->w2.p;
   HIP_TRY(p->order.use(s));

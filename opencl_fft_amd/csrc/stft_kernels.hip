@@ -11,6 +11,7 @@
 // holds FPW = LdsGeom::FPW frames at once; global accesses go in chunk order (element tid + WG e of the FPW * n
 // elements), so a wave reads runs of whole frames.
 #include "fft_wg.hpp"
+#include "stft_plan.hpp"
 
 namespace clfa {
 
@@ -138,7 +139,7 @@ template <int LOGN> constexpr bool stft_synth_tab_lds() { return LOGN <= 12; }  
 template <int LOGN>
 __global__ __launch_bounds__(LdsGeom<LOGN>::WG) void k_stft_synth(const cpx *__restrict__ spec, int F, int runs, int nf,
                                                                   int hop, long L, const float *__restrict__ win,
-                                                                  const float *__restrict__ cum, int normalize,
+                                                                  const double *__restrict__ cum, int normalize,
                                                                   float *__restrict__ out, long stride, long items,
                                                                   const cpx *__restrict__ tab_g,
                                                                   const cpx *__restrict__ w2_g) {
@@ -147,6 +148,7 @@ __global__ __launch_bounds__(LdsGeom<LOGN>::WG) void k_stft_synth(const cpx *__r
   constexpr int RL = 2 * CHUNK;   // ring length in floats = FPW * size >= (FPW - 1) hop + size
   constexpr bool TL = stft_synth_tab_lds<LOGN>();
   static_assert(CHUNK == WG * E, "one chunk = E rows of WG elements");
+  static_assert(FPW == stft_fpw(SIZE), "stft_plan.hpp restates FPW for the host");
   __shared__ cpx s_tab[TL ? G::HALF : 1];
   __shared__ cpx s_w2[TL ? N / 2 : 1];
   __shared__ cpx s_x[FPW * G::PADN];
@@ -170,24 +172,14 @@ __global__ __launch_bounds__(LdsGeom<LOGN>::WG) void k_stft_synth(const cpx *__r
     const int idx = tid + WG * e;
     return s_x[(idx >> LOGN) * G::PADN + lds_pad(idx & (N - 1))];
   };
-  // env[p] = sum of w[p - f hop]^2 over the frames that cover p, from the two running sums of w^2 along steps of hop
-  // (cum = [lo | hi]: lo[d] = sum w[d - k hop]^2, hi[d] = sum w[d + k hop]^2, k >= 0, inside the window)
-  auto env_at = [&](long p) -> float {
-    const long fh = p / hop < F - 1 ? p / hop : F - 1;
-    const long fl = p < SIZE ? 0 : (p - SIZE) / hop + 1;
-    const int dl = (int)(p - fh * hop), dh = (int)(p - fl * hop);
-    if (dh + hop >= SIZE) return cum[SIZE + dl];   // no frame cut off above: the tail sum from dl
-    if (dl < hop) return cum[dh];                   // none cut off below: the head sum up to dh
-    return cum[dh] - cum[dl - hop];                 // both (fewer frames than size / hop)
-  };
 #pragma unroll 1
   for (long item = blockIdx.x; item < items; item += gridDim.x) {
     const long c = item / runs;
     const int r = (int)(item - c * runs);
-    const int s = r * nf, e_end = s + nf < F ? s + nf : F;
+    const StftRun run = stft_run(r, nf, F, SIZE, hop);   // (stft_plan.hpp)
+    const int e_end = run.e_end, fw = run.fw;            // fw: the first frame that reaches sample s hop
     const bool last = e_end == F;
-    const long own_lo = (long)s * hop;
-    const int fw = own_lo >= SIZE ? (int)((own_lo - SIZE) / hop + 1) : 0;   // first frame that reaches sample s hop
+    const long own_lo = run.own_lo;
     const cpx *sp = spec + (long)c * F * N;
     float *orow = out + c * stride;
     for (int i = tid; i < RL; i += WG) s_ring[i] = 0.f;
@@ -250,7 +242,8 @@ __global__ __launch_bounds__(LdsGeom<LOGN>::WG) void k_stft_synth(const cpx *__r
         *slot = 0.f;
         if (p >= own_lo) {
           if (normalize) {
-            const float en = env_at(p);
+            // env[p], the float64 sum of w^2 over the covering frames rounded once (stft_plan.hpp)
+            const float en = stft_env_at(cum, SIZE, hop, F, p);
             if (en > 1e-11f) y = y / en;
           }
           orow[p] = y;
@@ -279,7 +272,8 @@ static hipError_t launch_stft_analyze_n(const StftArgs &a, const DeviceInfo &di,
   if (!occ8) occ8 = stft_occupancy<LOGN>((const void *)k_stft_analyze<LOGN, true>, G::WG);
   if (!occ4) occ4 = stft_occupancy<LOGN>((const void *)k_stft_analyze<LOGN, false>, G::WG);
   const long cap = (long)di.num_cus * (a.aligned8 ? occ8 : occ4);
-  const int grid = (int)(groups < cap ? groups : cap);
+  int grid = (int)(groups < cap ? groups : cap);
+  if (a.grid_max > 0 && grid > a.grid_max) grid = a.grid_max;   // CLFA_STFT_GRID_MAX
   if (a.aligned8)
     hipLaunchKernelGGL((k_stft_analyze<LOGN, true>), dim3(grid), dim3(G::WG), 0, s, a.signal, a.stride, a.hop, a.F,
                        (int)a.nframes, a.window, a.spec_out, a.half, a.w2);
@@ -295,17 +289,15 @@ static hipError_t launch_stft_synth_n(const StftArgs &a, const DeviceInfo &di, h
   static int occ = 0;
   if (!occ) occ = stft_occupancy<LOGN>((const void *)k_stft_synth<LOGN>, G::WG);
   const long slots = (long)di.num_cus * occ;
-  const int size = 2 * G::N, warm = (size + a.hop - 1) / a.hop;   // frames re-transformed at the start of a run, + 1
-  // runs: about one per resident workgroup, but at least 8 x the re-transformed frames long (overhead <= 1/8)
-  long nf = (a.nframes + slots - 1) / slots;
-  if (nf < 8L * warm) nf = 8L * warm;
-  if (nf < G::FPW) nf = G::FPW;
-  if (nf > a.F) nf = a.F;
-  const int runs = (int)((a.F + nf - 1) / nf);
+  const int size = 2 * G::N;
+  // the runs (stft_plan.hpp) depend on the device's slots alone, never on the cap of the grid
+  const int nf = stft_run_frames(a.nframes, slots, size, a.hop, G::FPW, a.F);
+  const int runs = stft_runs(a.F, nf);
   const long items = a.channels * runs;
-  const int grid = (int)(items < slots ? items : slots);
+  int grid = (int)(items < slots ? items : slots);
+  if (a.grid_max > 0 && grid > a.grid_max) grid = a.grid_max;   // CLFA_STFT_GRID_MAX
   const long L = (long)(a.F - 1) * a.hop + size;
-  hipLaunchKernelGGL((k_stft_synth<LOGN>), dim3(grid), dim3(G::WG), 0, s, a.spec_in, a.F, runs, (int)nf, a.hop,
+  hipLaunchKernelGGL((k_stft_synth<LOGN>), dim3(grid), dim3(G::WG), 0, s, a.spec_in, a.F, runs, nf, a.hop,
                      L, a.window, a.cum, a.normalize, a.out, a.stride, items, a.half, a.w2);
   return hipGetLastError();
 }

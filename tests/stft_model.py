@@ -34,3 +34,50 @@ def overlap_add(r, w, hop, normalize=False, dtype=np.float64):
         m = env > 1e-11
         y[:, m] = y[:, m] / env[m]
     return y, env
+
+
+# ---- mirror of opencl_fft_amd/csrc/stft_plan.hpp: the synthesis kernel's run split (tests/test_stft_plan_cpu.py checks
+# the header itself; this restatement lets a failing device test name the run, the group and fw of a wrong sample) ------
+# the (size, hop) pairs of tests/test_gpu_stft_synth.py, which tests/test_stft_plan_cpu.py also splits on the CPU
+SYNTH_PAIRS = [(64, 16), (64, 1), (256, 3), (1024, 255), (2048, 64), (4096, 1024), (8192, 8191), (16384, 4096),
+               (64, 64), (4096, 4096), (64, 3), (2048, 16), (2048, 1), (256, 256), (256, 64)]
+
+
+def fpw(size):
+    """frames a workgroup holds at once (stft_fpw)"""
+    return 1 if size >= 8192 else 8192 // size
+
+
+def run_frames(nframes, slots, size, hop, F):
+    """nf of stft_run_frames: frames per run"""
+    warm = -(-size // hop)
+    return min(max(-(-nframes // slots), 8 * warm, fpw(size)), F)
+
+
+def runs_of(F, nf):
+    return -(-F // nf)
+
+
+def run(r, nf, F, size, hop):
+    """(s, e_end, own_lo, fw) of stft_run"""
+    s = r * nf
+    own_lo = s * hop
+    return s, min(s + nf, F), own_lo, ((own_lo - size) // hop + 1 if own_lo >= size else 0)
+
+
+def locate(p, nf, F, size, hop):
+    """where sample p of a channel is made: (run, its fw, the group of fpw frames whose write-out holds p, the covering
+    frames [f_lo, f_hi])"""
+    r = min(p // (nf * hop), runs_of(F, nf) - 1)
+    _, e_end, _, fw = run(r, nf, F, size, hop)
+    group = (min(p // hop, e_end - 1) - fw) // fpw(size)
+    return r, fw, group, (0 if p < size else (p - size) // hop + 1, min(p // hop, F - 1))
+
+
+def env_branch(size, hop, F, p):
+    """which form of stft_env_at sample p takes (1 tail sum, 2 head sum, 3 difference: stft_env_span); p may be an array"""
+    p = np.asarray(p, np.int64)
+    fh = np.minimum(p // hop, F - 1)
+    fl = np.where(p < size, 0, (p - size) // hop + 1)
+    dl, dh = p - fh * hop, p - fl * hop
+    return np.where(dh + hop >= size, 1, np.where(dl < hop, 2, 3))

@@ -102,7 +102,10 @@ def synth_dev(size, hop, spec, w, normalize, stride_pad=0):
 
 
 @pytest.mark.parametrize("size,hop,C,F", [(64, 16, 3, 50), (256, 3, 2, 300), (1024, 256, 3, 40), (2048, 1, 1, 2100),
-                                          (4096, 4096, 2, 5), (8192, 2048, 2, 12), (16384, 4096, 2, 9), (512, 128, 200, 6)])
+                                          (4096, 4096, 2, 5), (8192, 2048, 2, 12), (16384, 4096, 2, 9), (512, 128, 200, 6),
+                                          # short calls, fewer frames than size / hop: the envelope's difference form
+                                          (2048, 16, 1, 8), (256, 3, 2, 10), (64, 1, 1, 5), (2048, 1, 1, 100),
+                                          (1024, 256, 3, 2)])
 @pytest.mark.parametrize("normalize", [False, True])
 def test_synthesis_at_least_as_accurate_as_float32_numpy(size, hop, C, F, normalize):
     rng = np.random.default_rng(size + hop + F)
