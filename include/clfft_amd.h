@@ -358,7 +358,7 @@ CLFA_API int clfa_pvoc_create(clfa_pvoc **pv, int device, int size, int hop, dou
 CLFA_API void clfa_pvoc_destroy(clfa_pvoc *pv);
 CLFA_API int clfa_pvoc_get_error(const clfa_pvoc *pv);
 CLFA_API const char *clfa_pvoc_get_log(const clfa_pvoc *pv);
-/* both states as at creation; blocking (CLFA_INVALID_OPERATION while the object's stream is being captured) */
+/* every state as at creation; blocking (CLFA_INVALID_OPERATION while the object's stream is being captured) */
 CLFA_API int clfa_pvoc_reset(clfa_pvoc *pv);
 CLFA_API int clfa_pvoc_analyze_dev(clfa_pvoc *pv, const void *spectra, void *frames_out, long F, void *stream);
 CLFA_API int clfa_pvoc_synthesize_dev(clfa_pvoc *pv, const void *frames, void *spectra_out, long F, void *stream);
@@ -372,6 +372,65 @@ CLFA_API int clfa_pvoc_scan_chunk(void);
 /* state diagnostics, blocking: channels x (M + 1) phases; channels x (M + 1) x (re, im) of prev */
 CLFA_API int clfa_pvoc_read_phase(clfa_pvoc *pv, unsigned *host);
 CLFA_API int clfa_pvoc_read_prev(clfa_pvoc *pv, float *host);
+
+/* ---- oscillator-bank resynthesis: (amp, freq) frames straight to samples ---- */
+/* The additive synthesiser next to the inverse transform (Csound's pvsadsyn): every selected bin drives an oscillator, its
+ * amplitude and frequency are interpolated sample by sample across the hop, and the output is the sum of the
+ * oscillators.  frames: channels x F x (M + 1) x 2 float32 as above.  signal: channels rows of F hop floats, row c at
+ * signal + c signal_stride, signal_stride >= F hop; frame f yields the samples [f hop, (f + 1) hop).
+ *   fmod: F float32, one per frame, shared by the channels, or NULL: no multiplication at all;
+ *   the oscillators are the bins first_bin + i step, i < nbins; step >= 1, nbins >= 1, first_bin >= 0, the last bin <= M;
+ *   gain: a float.
+ * State of its own, per channel and bin: the phase P, a uint64 in units of 2^-64 turn; W, an int32, the frequency in
+ * 2^-32 turn per sample; A, a float32 amplitude.  All 0 at creation and after clfa_pvoc_reset.  prev and theta are never
+ * touched, and the state of a bin outside the selection is left bit for bit as it was.
+ *
+ * Every float32 operation is rounded on its own (no fused multiply-add); fl() marks a rounding.
+ * ks = (float)(1 / sr), divided in double; w_j = (float)((double)j / hop), j = 1..hop, a table made at creation.
+ *   Endpoint of frame f: t = fl(fl(freq fmod[f]) ks), without fmod t = fl(freq ks).  Where |t| < 0.5 holds,
+ *     W_f = (int32)rint((double)t 2^32) and A_f = amp (a NaN amp is kept: it reaches the samples of its own channel
+ *     only).  Where it does not — NaN, infinities, anything at or above Nyquist — the endpoint is silent: W_f = 0, A_f = 0.
+ *   Start of the segment: A0, W0 = the previous frame's endpoint, or the state for the call's first frame.  Where
+ *     A0 == 0, W0 := W_f: an oscillator that was silent starts at its new frequency, without a glide.  A rule on values.
+ *   Phase, exact: with int64 d = W_f - W0, D = floor_div(d 2^30, hop) 4, the floor towards minus infinity;
+ *     phase(j) = P + j (W0 2^32) + (j (j + 1) / 2) D mod 2^64 for sample j = 1..hop; the next frame starts from
+ *     phase(hop).  The advance of a frame depends on that frame and the one before only.
+ *   Amplitude: a(j) = fl(A0 + fl(fl(A_f - A0) w_j)); a(hop) = A_f exactly, since w_hop = 1.
+ *   Sample: y = fl(gain S), S the float32 sum, from 0 and in ascending order of the selected bins, of
+ *     fl(a(j) cospif(x)), x = (float)(int32)(phase(j) >> 32) 2^-31: the top 32 bits of the phase as a signed number of
+ *     half turns, as in the synthesis.  cospif returns exactly 0, 1, -1 at the multiples of a quarter turn.
+ *   After the call the state of a selected bin is (phase(hop), W, A) of the call's last frame.
+ * Addition mod 2^64 is associative, so the chunked scan of the synthesis applies: the samples and the state are the same
+ * bits however a stream of frames is cut into calls, on any stream, under graph replay and for any grid cap.  The order of
+ * the sum depends on the selection alone.  tests/pvoc_adsyn_model.py restates all of it; the integer part is
+ * opencl_fft_amd/csrc/pvoc_adsyn_plan.hpp, shared by the kernels and the CPU test.
+ *
+ * Three launches per sub-batch: "k_adsyn_sums" (the uint64 sums of the frames' advances per chunk of
+ * clfa_pvoc_scan_chunk() frames), "k_adsyn_scan" (the chunks' bases in place and the new state), "k_adsyn_osc" (a
+ * workgroup per channel and chunk: tiles of clfa_pvoc_adsyn_tile_bins() oscillators in LDS, visited in ascending order
+ * into one accumulator per sample).  No atomics, no waiting between workgroups.  CLFA_PVOC_ADSYN_GRID_MAX, read at
+ * creation, lowers the number of workgroups a launch may have (a tuning and test switch: the results do not depend on it).
+ *
+ * The calls follow the object's rules: asynchronous on `stream`, one stream at a time, capturable, the current device left
+ * as found.  Argument errors that need no device come first (on an object whose creation found no device a bad argument
+ * is still CLFA_INVALID_VALUE, a good one the object's error): a bad argument, or an output that overlaps the frames or
+ * fmod even partly, is CLFA_INVALID_VALUE and leaves the state untouched.  F == 0 succeeds and does nothing.  Device
+ * pointers: frames 8-byte aligned, fmod and signal 4-byte.  Workspace: an allocation of its own (the 64-bit chunk sums of
+ * one sub-batch, at most about 64 MiB, CLFA_PVOC_CHUNKS_MAX lowers the chunks per sub-batch; and the endpoints a sub-batch
+ * starts from), made whole by the first call; a first call under capture returns CLFA_INVALID_OPERATION; reported by
+ * clfa_pvoc_adsyn_workspace_bytes — clfa_pvoc_workspace_bytes keeps reporting the synthesis' alone. */
+CLFA_API int clfa_pvoc_adsyn_dev(clfa_pvoc *pv, const void *frames, long F, const void *fmod, int first_bin, int nbins,
+                                 int step, float gain, void *signal, long signal_stride, void *stream);
+/* host arrays, copied in and out, blocking */
+CLFA_API int clfa_pvoc_adsyn(clfa_pvoc *pv, const float *frames, long F, const float *fmod, int first_bin, int nbins,
+                             int step, float gain, float *signal, long signal_stride);
+/* state diagnostics, blocking: channels x (M + 1) each of P, W, A */
+CLFA_API int clfa_pvoc_adsyn_read_state(clfa_pvoc *pv, unsigned long long *phase, int *w, float *amp);
+CLFA_API size_t clfa_pvoc_adsyn_workspace_bytes(const clfa_pvoc *pv);
+/* oscillators per LDS tile of k_adsyn_osc (fixed) */
+CLFA_API int clfa_pvoc_adsyn_tile_bins(void);
+/* "k_adsyn_osc" ("" for a failed object) */
+CLFA_API const char *clfa_pvoc_adsyn_kernel_name(const clfa_pvoc *pv);
 
 /* ---- operations on (amp, freq) frames: pitch scale, frequency shift, timed read ---- */
 /* Stateless: they read frames and write frames of the layout above, never touch prev or theta, and allocate nothing

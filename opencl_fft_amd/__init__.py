@@ -311,6 +311,7 @@ class Pvoc(_Handle):
     complex64 spectra as (channels, F, size/2 + 1, 2) float32 frames of (amp, freq in Hz) per bin, synthesize() turns such
     frames back into spectra.  The object carries the last spectrum (analysis) and an integer phase per bin (synthesis)
     from call to call, so a stream may be cut into calls anywhere; reset() returns both to their start.
+    adsyn() is the second way back to sound: an oscillator per bin, summed straight into samples (a state of its own).
     Like the other objects the constructor does not raise, and every call returns its status."""
     _destroy = "clfa_pvoc_destroy"
 
@@ -488,6 +489,69 @@ class Pvoc(_Handle):
         pos = np.ascontiguousarray(pos, dtype=np.float32).reshape(-1)
         frames, Fin, par, out = self._ops_host(frames, pos, pos.size)
         check(lib().clfa_pvoc_read(self._h, frames.ctypes.data, Fin, par.ctypes.data, out.ctypes.data, pos.size), "Pvoc.read")
+        return out
+
+    # ---- frames -> samples: the oscillator bank (Csound's pvsadsyn; a state of its own; clfft_amd.h) ----
+
+    def adsyn_kernel_name(self):
+        """ "k_adsyn_osc" ("" for a failed object)"""
+        return lib().clfa_pvoc_adsyn_kernel_name(self._h).decode()
+
+    def adsyn_workspace_bytes(self):
+        return lib().clfa_pvoc_adsyn_workspace_bytes(self._h)
+
+    def adsyn_tile_bins(self):
+        """oscillators per LDS tile of k_adsyn_osc (fixed)"""
+        return lib().clfa_pvoc_adsyn_tile_bins()
+
+    def adsyn_state(self):
+        """the oscillator bank's state (blocking): (P uint64 in 2^-64 turn, W int32 in 2^-32 turn per sample, A float32),
+        each (channels, size/2 + 1)"""
+        shape = (self.channels, self.M + 1)
+        P, W, A = np.zeros(shape, np.uint64), np.zeros(shape, np.int32), np.zeros(shape, np.float32)
+        check(lib().clfa_pvoc_adsyn_read_state(self._h, P.ctypes.data, W.ctypes.data, A.ctypes.data), "Pvoc.adsyn_state")
+        return P, W, A
+
+    def _selection(self, first_bin, nbins, step):
+        first_bin, step = int(first_bin), int(step)
+        if nbins is None:      # every bin from first_bin up that the step reaches
+            nbins = (self.M - first_bin) // step + 1 if step >= 1 and 0 <= first_bin <= self.M else 0
+        return first_bin, int(nbins), step
+
+    def adsyn_device(self, frames, out, fmod=None, first_bin=0, nbins=None, step=1, gain=1.0, stream=None):
+        """torch: frames (channels, F, size/2 + 1, 2) float32, contiguous -> out (channels, n >= F * hop) float32 with
+        contiguous rows (one row for one channel): frame f yields the samples [f hop, (f + 1) hop), summed over the
+        oscillators of the bins first_bin + i * step, i < nbins (default: all that fit), times gain.  fmod: a frequency
+        multiplier, a number or a float32 device tensor (F,); None: none.  Asynchronous on `stream`."""
+        import torch
+        F = self._frames_shape(frames.shape)
+        if F is None or frames.dtype != torch.float32 or out.dtype != torch.float32 or not frames.is_contiguous():
+            return CL_INVALID_VALUE
+        p, rows, n, stride = _row_view(out, "out")
+        if rows != self.channels or n < F * self.hop:
+            return CL_INVALID_VALUE
+        if fmod is not None and not hasattr(fmod, "data_ptr"):
+            fmod = torch.full((F,), float(fmod), dtype=torch.float32, device=out.device)
+        if fmod is not None and (fmod.dtype != torch.float32 or tuple(fmod.shape) != (F,) or not fmod.is_contiguous()):
+            return CL_INVALID_VALUE
+        first_bin, nbins, step = self._selection(first_bin, nbins, step)
+        return lib().clfa_pvoc_adsyn_dev(self._h, frames.data_ptr(), F, None if fmod is None else fmod.data_ptr(),
+                                         first_bin, nbins, step, float(gain), p, stride if rows > 1 else n,
+                                         _stream_of(out, stream))
+
+    def adsyn(self, frames, fmod=None, first_bin=0, nbins=None, step=1, gain=1.0):
+        """host form of adsyn_device, blocking: float32 (channels, F, size/2 + 1, 2) (or (F, size/2 + 1, 2)) -> float32
+        (.., F * hop)"""
+        frames = np.ascontiguousarray(frames, dtype=np.float32)
+        F = self._frames_shape(frames.shape)
+        if F is None:
+            raise ValueError("frames must be (%d, F, %d, 2)" % (self.channels, self.M + 1))
+        if fmod is not None:
+            fmod = np.ascontiguousarray(np.broadcast_to(np.asarray(fmod, dtype=np.float32), (F,)))
+        out = np.zeros(frames.shape[:-3] + (F * self.hop,), np.float32)
+        first_bin, nbins, step = self._selection(first_bin, nbins, step)
+        check(lib().clfa_pvoc_adsyn(self._h, frames.ctypes.data, F, None if fmod is None else fmod.ctypes.data, first_bin,
+                                    nbins, step, float(gain), out.ctypes.data, F * self.hop), "Pvoc.adsyn")
         return out
 
 

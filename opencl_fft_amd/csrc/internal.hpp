@@ -275,6 +275,29 @@ hipError_t launch_pvoc_analyze(const PvocArgs &a, const DeviceInfo &di, hipStrea
 // (one lane per channel and bin) their bases in place and the new theta, then the walk that writes the spectra
 hipError_t launch_pvoc_synth(const PvocArgs &a, long f0, long nf, const DeviceInfo &di, hipStream_t s);
 
+// ---- oscillator-bank resynthesis of (amp, freq) frames (pvoc_adsyn.hip) -------------
+constexpr int kAdsynTile = 256;    // oscillators per LDS tile of k_adsyn_osc = its lanes (clfa_pvoc_adsyn_tile_bins)
+struct PvocAdsynArgs {
+  int M = 0, channels = 0, hop = 0;
+  long F = 0;                          // frames per channel in the caller's buffers
+  const float *frames = nullptr;       // channels x F x (M + 1) x (amp, freq)
+  const float *fmod = nullptr;         // F, or NULL
+  int first = 0, nbins = 0, step = 1;  // the oscillators are the bins first + i step, i < nbins
+  float gain = 1.f, ks = 0.f;          // ks = 1 / sr
+  unsigned long long *phase = nullptr; // the state, per channel and bin: P, W, A
+  int *w = nullptr;
+  float *amp = nullptr;
+  unsigned long long *sums = nullptr;  // workspace: per channel, chunk and oscillator the chunk sums, then bases
+  int *w0 = nullptr;                   // workspace: per channel and oscillator, the endpoint the sub-batch starts from
+  float *a0 = nullptr;
+  const float *ramp = nullptr;         // w_j = (float)((double)j / hop), j = 1..hop
+  float *signal = nullptr;             // channels rows of F hop floats, sstride apart
+  long sstride = 0;
+  int grid_max = 0;                    // > 0: at most this many workgroups
+};
+// frames [f0, f0 + nf) of every channel, nf <= the workspace's chunks x kPvocChunk: k_adsyn_sums, k_adsyn_scan, k_adsyn_osc
+hipError_t launch_pvoc_adsyn(const PvocAdsynArgs &a, long f0, long nf, const DeviceInfo &di, hipStream_t s);
+
 // ---- operations on (amp, freq) frames (pvoc_ops.hip): pitch scale, frequency shift, timed read ----
 enum PvocOp { PVOC_SCALE = 0, PVOC_SHIFT = 1, PVOC_READ = 2 };
 struct PvocOpsArgs {

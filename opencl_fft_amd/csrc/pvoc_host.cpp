@@ -26,16 +26,27 @@ struct clfa_pvoc {
   DevBuf half, w2;
   int ops_grid_max = 0;
   DevBuf sop_out, sop_par;
+  // the oscillator bank (pvoc_adsyn.hip): 1 / sr, its state per channel and bin (P uint64, W int32, A float32), the ramp
+  // w_j, its own workspace (the 64-bit chunk sums of one sub-batch, then the endpoints a sub-batch starts from), the
+  // chunks per sub-batch, the cap on its workgroups (CLFA_PVOC_ADSYN_GRID_MAX, 0 = none), staging of the host form
+  float ks = 0.f;
+  DevBuf aphase, aw, aamp, ramp, aws;
+  long acap = 1;
+  int adsyn_grid_max = 0;
+  DevBuf sfmod, ssig;
   StreamOrder order;
 };
 
 static size_t pvoc_bins(const clfa_pvoc *p) { return (size_t)p->channels * (p->M + 1); }
 
-// both states as at creation: prev = (1, 0), theta = 0 (on p->stream, blocking)
+// the states as at creation: prev = (1, 0), theta = 0, the oscillator bank's P = W = A = 0 (on p->stream, blocking)
 static int pvoc_init_state(clfa_pvoc *p) {
   std::vector<cpx> one(pvoc_bins(p), mk(1.f, 0.f));
   HIP_TRY(hipMemcpyAsync(p->prev.p, one.data(), sizeof(cpx) * one.size(), hipMemcpyHostToDevice, p->stream));
   HIP_TRY(hipMemsetAsync(p->theta.p, 0, sizeof(unsigned) * pvoc_bins(p), p->stream));
+  HIP_TRY(hipMemsetAsync(p->aphase.p, 0, sizeof(unsigned long long) * pvoc_bins(p), p->stream));
+  HIP_TRY(hipMemsetAsync(p->aw.p, 0, sizeof(int) * pvoc_bins(p), p->stream));
+  HIP_TRY(hipMemsetAsync(p->aamp.p, 0, sizeof(float) * pvoc_bins(p), p->stream));
   HIP_TRY(hipStreamSynchronize(p->stream));
   return CLFA_SUCCESS;
 }
@@ -67,14 +78,24 @@ static int pvoc_setup(clfa_pvoc *p, int device, int size, int hop, double sr, in
   p->srs = (float)(sr / size);
   p->kf = (float)(hop / sr);
   p->bpf = (float)(size / sr);
+  p->ks = (float)(1.0 / sr);
   // sub-batches bound the scan's workspace (4 bytes per channel, chunk and bin) to about 64 MiB
   p->cap = (64L << 20) / ((long)sizeof(unsigned) * (long)pvoc_bins(p));
   p->cap = p->cap < 1 ? 1 : (p->cap > 4096 ? 4096 : p->cap);
   if (const char *env = getenv("CLFA_PVOC_CHUNKS_MAX")) {
     if (atol(env) > 0 && atol(env) < p->cap) p->cap = atol(env);
   }
+  // the oscillator bank's chunk sums are 8 bytes each: its sub-batches are bounded the same way, by the same switch
+  p->acap = (64L << 20) / ((long)sizeof(unsigned long long) * (long)pvoc_bins(p));
+  p->acap = p->acap < 1 ? 1 : (p->acap > 4096 ? 4096 : p->acap);
+  if (const char *env = getenv("CLFA_PVOC_CHUNKS_MAX")) {
+    if (atol(env) > 0 && atol(env) < p->acap) p->acap = atol(env);
+  }
   if (const char *env = getenv("CLFA_PVOC_OPS_GRID_MAX")) {
     if (atol(env) > 0 && atol(env) < 0x7fffffffL) p->ops_grid_max = (int)atol(env);
+  }
+  if (const char *env = getenv("CLFA_PVOC_ADSYN_GRID_MAX")) {
+    if (atol(env) > 0 && atol(env) < 0x7fffffffL) p->adsyn_grid_max = (int)atol(env);
   }
   int e = device_info(device, p->di);
   if (e) return e;
@@ -88,6 +109,12 @@ static int pvoc_setup(clfa_pvoc *p, int device, int size, int hop, double sr, in
   }
   if ((e = upload(p->etab, tab.data(), sizeof(cpx) * tab.size()))) return e;
   if ((e = p->prev.ensure(sizeof(cpx) * pvoc_bins(p))) || (e = p->theta.ensure(sizeof(unsigned) * pvoc_bins(p)))) return e;
+  std::vector<float> ramp(hop);
+  for (int j = 1; j <= hop; j++) ramp[j - 1] = (float)((double)j / hop);
+  if ((e = upload(p->ramp, ramp.data(), sizeof(float) * ramp.size()))) return e;
+  if ((e = p->aphase.ensure(sizeof(unsigned long long) * pvoc_bins(p))) || (e = p->aw.ensure(sizeof(int) * pvoc_bins(p))) ||
+      (e = p->aamp.ensure(sizeof(float) * pvoc_bins(p))))
+    return e;
   return pvoc_init_state(p);
 }
 
@@ -343,5 +370,116 @@ int clfa_pvoc_synthesize(clfa_pvoc *p, const float *frames, float *spectra_out, 
   HIP_TRY(hipStreamSynchronize(p->stream));
   return CLFA_SUCCESS;
 }
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------
+// frames -> samples: the oscillator bank (pvoc_adsyn.hip)
+// ---------------------------------------------------------------------------------
+
+// The checks that need no device, before the object's own error (as pvoc_ops_check).  0 = go on, 1 = a successful no-op,
+// < 0 = the error.
+static int pvoc_adsyn_check(const clfa_pvoc *p, const void *frames, long F, const void *fmod, int first_bin, int nbins,
+                            int step, const void *signal, long signal_stride, bool device_ptrs) {
+  if (!p) return CLFA_INVALID_VALUE;
+  if (!p->M) return p->err ? p->err : CLFA_INVALID_VALUE;
+  if (F < 0 || F > 0x7fffffffL) return CLFA_INVALID_VALUE;
+  if (step < 1 || nbins < 1 || first_bin < 0 || (long)first_bin + ((long)nbins - 1) * step > p->M) return CLFA_INVALID_VALUE;
+  if (signal_stride < F * p->hop) return CLFA_INVALID_VALUE;
+  if (F == 0) return 1;
+  if (!frames || !signal) return CLFA_INVALID_VALUE;
+  if (device_ptrs && (((uintptr_t)frames & 7) || ((uintptr_t)signal & 3) || ((uintptr_t)fmod & 3))) return CLFA_INVALID_VALUE;
+  // the output's rows and the gaps between them, as one span
+  const size_t fbytes = 2 * sizeof(float) * pvoc_bins(p) * (size_t)F;
+  const size_t obytes = sizeof(float) * ((size_t)(p->channels - 1) * (size_t)signal_stride + (size_t)F * p->hop);
+  if (spans_overlap(frames, fbytes, signal, obytes)) return CLFA_INVALID_VALUE;
+  if (fmod && spans_overlap(fmod, sizeof(float) * (size_t)F, signal, obytes)) return CLFA_INVALID_VALUE;
+  return CLFA_SUCCESS;
+}
+
+static size_t pvoc_adsyn_ws_bytes(const clfa_pvoc *p) {
+  return sizeof(unsigned long long) * pvoc_bins(p) * (size_t)p->acap + (sizeof(int) + sizeof(float)) * pvoc_bins(p);
+}
+
+extern "C" {
+
+int clfa_pvoc_adsyn_dev(clfa_pvoc *p, const void *frames, long F, const void *fmod, int first_bin, int nbins, int step,
+                        float gain, void *signal, long signal_stride, void *stream) {
+  const int chk = pvoc_adsyn_check(p, frames, F, fmod, first_bin, nbins, step, signal, signal_stride, true);
+  if (chk < 0) return chk;
+  if (p->err) return p->err;
+  if (chk == 1) return CLFA_SUCCESS;
+  ENTER_DEVICE(p->di.device);
+  hipStream_t s = (hipStream_t)stream;
+  const long held = p->acap;   // the whole workspace at the first need: its address never changes afterwards
+  HIP_TRY(p->order.use(s));
+  if (int e = ensure_workspaces({{&p->aws, pvoc_adsyn_ws_bytes(p)}}, s)) return e;
+  PvocAdsynArgs a;
+  a.M = p->M;
+  a.channels = p->channels;
+  a.hop = p->hop;
+  a.F = F;
+  a.frames = (const float *)frames;
+  a.fmod = (const float *)fmod;
+  a.first = first_bin;
+  a.nbins = nbins;
+  a.step = step;
+  a.gain = gain;
+  a.ks = p->ks;
+  a.phase = (unsigned long long *)p->aphase.p;
+  a.w = (int *)p->aw.p;
+  a.amp = (float *)p->aamp.p;
+  a.sums = (unsigned long long *)p->aws.p;
+  a.w0 = (int *)(a.sums + pvoc_bins(p) * (size_t)held);
+  a.a0 = (float *)(a.w0 + pvoc_bins(p));
+  a.ramp = (const float *)p->ramp.p;
+  a.signal = (float *)signal;
+  a.sstride = signal_stride;
+  a.grid_max = p->adsyn_grid_max;
+  // sub-batches of at most `held` chunks: each advances the state by its frames, the next one starts from there
+  for (long f0 = 0; f0 < F; f0 += held * kPvocChunk) {
+    const long nf = F - f0 < held * kPvocChunk ? F - f0 : held * kPvocChunk;
+    HIP_TRY(launch_pvoc_adsyn(a, f0, nf, p->di, s));
+  }
+  return CLFA_SUCCESS;
+}
+
+int clfa_pvoc_adsyn(clfa_pvoc *p, const float *frames, long F, const float *fmod, int first_bin, int nbins, int step,
+                    float gain, float *signal, long signal_stride) {
+  const int chk = pvoc_adsyn_check(p, frames, F, fmod, first_bin, nbins, step, signal, signal_stride, false);
+  if (chk < 0) return chk;
+  if (p->err) return p->err;
+  if (chk == 1) return CLFA_SUCCESS;
+  const size_t fbytes = 2 * sizeof(float) * pvoc_bins(p) * (size_t)F, row = sizeof(float) * (size_t)F * p->hop;
+  ENTER_DEVICE(p->di.device);
+  int e = p->sframes.ensure(fbytes);
+  if (!e) e = p->ssig.ensure(row * p->channels);
+  if (!e && fmod) e = p->sfmod.ensure(sizeof(float) * (size_t)F);
+  if (e) return e;
+  HIP_TRY(hipMemcpyAsync(p->sframes.p, frames, fbytes, hipMemcpyHostToDevice, p->stream));
+  if (fmod) HIP_TRY(hipMemcpyAsync(p->sfmod.p, fmod, sizeof(float) * (size_t)F, hipMemcpyHostToDevice, p->stream));
+  if ((e = clfa_pvoc_adsyn_dev(p, p->sframes.p, F, fmod ? p->sfmod.p : nullptr, first_bin, nbins, step, gain, p->ssig.p,
+                               F * p->hop, p->stream)))
+    return e;
+  HIP_TRY(hipMemcpy2DAsync(signal, sizeof(float) * (size_t)signal_stride, p->ssig.p, row, row, p->channels,
+                           hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return CLFA_SUCCESS;
+}
+
+int clfa_pvoc_adsyn_read_state(clfa_pvoc *p, unsigned long long *phase, int *w, float *amp) {
+  if (int e = obj_error(p)) return e;
+  if (!phase || !w || !amp) return CLFA_INVALID_VALUE;
+  ENTER_DEVICE(p->di.device);
+  if (int e = pvoc_quiesce(p)) return e;
+  HIP_TRY(hipMemcpy(phase, p->aphase.p, sizeof(unsigned long long) * pvoc_bins(p), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(w, p->aw.p, sizeof(int) * pvoc_bins(p), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(amp, p->aamp.p, sizeof(float) * pvoc_bins(p), hipMemcpyDeviceToHost));
+  return CLFA_SUCCESS;
+}
+
+size_t clfa_pvoc_adsyn_workspace_bytes(const clfa_pvoc *p) { return p ? p->aws.bytes : 0; }
+int clfa_pvoc_adsyn_tile_bins(void) { return kAdsynTile; }
+const char *clfa_pvoc_adsyn_kernel_name(const clfa_pvoc *p) { return !p || p->err ? "" : "k_adsyn_osc"; }
 
 }  // extern "C"
