@@ -355,14 +355,10 @@ class Pvoc(_Handle):
 
     def _shapes(self, spectra, frames):
         """F if `spectra` is (channels, F, M) (or (F, M) for one channel) and `frames` the matching (.., F, M + 1, 2), else None"""
-        s, f = tuple(spectra.shape), tuple(frames.shape)
+        s, F = tuple(spectra.shape), self._frames_shape(frames.shape)
         if len(s) == 2 and self.channels == 1:
             s = (1,) + s
-        if len(f) == 3 and self.channels == 1:
-            f = (1,) + f
-        if len(s) != 3 or s[0] != self.channels or s[2] != self.M or f != (self.channels, s[1], self.M + 1, 2):
-            return None
-        return s[1]
+        return F if F is not None and s == (self.channels, F, self.M) else None
 
     def _device_call(self, fn, spectra, frames, src, dst, stream):
         import torch
@@ -393,11 +389,8 @@ class Pvoc(_Handle):
 
     def synthesize(self, frames):
         """host: float32 (channels, F, size/2 + 1, 2) (or (F, size/2 + 1, 2)) -> complex64 (.., F, size/2)"""
-        frames = np.ascontiguousarray(frames, dtype=np.float32)
+        frames, F = self._host_frames(frames)
         out = np.zeros(frames.shape[:-2] + (self.M,), np.complex64)
-        F = self._shapes(out, frames)
-        if F is None:
-            raise ValueError("frames must be (%d, F, %d, 2)" % (self.channels, self.M + 1))
         check(lib().clfa_pvoc_synthesize(self._h, frames.ctypes.data, out.ctypes.data, F), "Pvoc.synthesize")
         return out
 
@@ -417,6 +410,28 @@ class Pvoc(_Handle):
             return None
         return f[1]
 
+    def _host_frames(self, frames):
+        """(the frames as a contiguous float32 array, F); ValueError for another shape"""
+        frames = np.ascontiguousarray(frames, dtype=np.float32)
+        F = self._frames_shape(frames.shape)
+        if F is None:
+            raise ValueError("frames must be (%d, F, %d, 2)" % (self.channels, self.M + 1))
+        return frames, F
+
+    def _per_frame(self, par, F, device):
+        """a per-frame value of a device call as a float32 (F,) tensor: a plain number becomes F copies on `device`;
+        None for a tensor of another kind"""
+        import torch
+        if not hasattr(par, "data_ptr"):
+            par = torch.full((F,), float(par), dtype=torch.float32, device=device)
+        if par.dtype != torch.float32 or tuple(par.shape) != (F,) or not par.is_contiguous():
+            return None
+        return par
+
+    def _per_frame_host(self, par, F):
+        """a per-frame value of a host call (a number or an array of F) as a contiguous float32 (F,) array"""
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(par, dtype=np.float32), (F,)))
+
     def _ops_device(self, frames_in, frames_out, par, stream):
         """(Fin, Fout, the per-frame tensor, stream) of a device call, None for bad tensors; a plain number becomes a
         tensor of Fout copies"""
@@ -425,11 +440,8 @@ class Pvoc(_Handle):
         if (Fin is None or Fout is None or frames_in.dtype != torch.float32 or frames_out.dtype != torch.float32
                 or not frames_in.is_contiguous() or not frames_out.is_contiguous()):
             return None
-        if not hasattr(par, "data_ptr"):
-            par = torch.full((Fout,), float(par), dtype=torch.float32, device=frames_out.device)
-        if par.dtype != torch.float32 or tuple(par.shape) != (Fout,) or not par.is_contiguous():
-            return None
-        return Fin, Fout, par, _stream_of(frames_out, stream)
+        par = self._per_frame(par, Fout, frames_out.device)
+        return None if par is None else (Fin, Fout, par, _stream_of(frames_out, stream))
 
     def scale_device(self, frames_in, frames_out, scale, keepform=False, gain=1.0, coefs=80, stream=None):
         """pitch scale (Csound's pvscale): torch frames (channels, F, size/2 + 1, 2) float32 -> frames_out of the same
@@ -460,14 +472,9 @@ class Pvoc(_Handle):
                                         a[1], a[3])
 
     def _ops_host(self, frames, par, Fout=None):
-        frames = np.ascontiguousarray(frames, dtype=np.float32)
-        Fin = self._frames_shape(frames.shape)
-        if Fin is None:
-            raise ValueError("frames must be (%d, F, %d, 2)" % (self.channels, self.M + 1))
+        frames, Fin = self._host_frames(frames)
         Fout = Fin if Fout is None else Fout
-        par = np.ascontiguousarray(np.broadcast_to(np.asarray(par, dtype=np.float32), (Fout,)))
-        lead = frames.shape[:-3]
-        return frames, Fin, par, np.zeros(lead + (Fout, self.M + 1, 2), np.float32)
+        return frames, Fin, self._per_frame_host(par, Fout), np.zeros(frames.shape[:-3] + (Fout, self.M + 1, 2), np.float32)
 
     def scale(self, frames, scale, keepform=False, gain=1.0, coefs=80):
         """host form of scale_device, blocking: returns the new frames; a value of `scale` outside [0.25, 4] raises
@@ -530,10 +537,10 @@ class Pvoc(_Handle):
         p, rows, n, stride = _row_view(out, "out")
         if rows != self.channels or n < F * self.hop:
             return CL_INVALID_VALUE
-        if fmod is not None and not hasattr(fmod, "data_ptr"):
-            fmod = torch.full((F,), float(fmod), dtype=torch.float32, device=out.device)
-        if fmod is not None and (fmod.dtype != torch.float32 or tuple(fmod.shape) != (F,) or not fmod.is_contiguous()):
-            return CL_INVALID_VALUE
+        if fmod is not None:
+            fmod = self._per_frame(fmod, F, out.device)
+            if fmod is None:
+                return CL_INVALID_VALUE
         first_bin, nbins, step = self._selection(first_bin, nbins, step)
         return lib().clfa_pvoc_adsyn_dev(self._h, frames.data_ptr(), F, None if fmod is None else fmod.data_ptr(),
                                          first_bin, nbins, step, float(gain), p, stride if rows > 1 else n,
@@ -542,12 +549,9 @@ class Pvoc(_Handle):
     def adsyn(self, frames, fmod=None, first_bin=0, nbins=None, step=1, gain=1.0):
         """host form of adsyn_device, blocking: float32 (channels, F, size/2 + 1, 2) (or (F, size/2 + 1, 2)) -> float32
         (.., F * hop)"""
-        frames = np.ascontiguousarray(frames, dtype=np.float32)
-        F = self._frames_shape(frames.shape)
-        if F is None:
-            raise ValueError("frames must be (%d, F, %d, 2)" % (self.channels, self.M + 1))
+        frames, F = self._host_frames(frames)
         if fmod is not None:
-            fmod = np.ascontiguousarray(np.broadcast_to(np.asarray(fmod, dtype=np.float32), (F,)))
+            fmod = self._per_frame_host(fmod, F)
         out = np.zeros(frames.shape[:-3] + (F * self.hop,), np.float32)
         first_bin, nbins, step = self._selection(first_bin, nbins, step)
         check(lib().clfa_pvoc_adsyn(self._h, frames.ctypes.data, F, None if fmod is None else fmod.ctypes.data, first_bin,

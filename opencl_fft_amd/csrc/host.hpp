@@ -1,7 +1,7 @@
 // host.hpp — plumbing shared by the host side of the C ABI (clfft_amd.cpp: FFT plans, conv_host.cpp: the
-// convolutions, stft_host.cpp: Stft): error mapping, device and stream handling, owned device / pinned buffers, the
-// exact host tables, and the prelude / creation / destruction every object shares.  Everything here is inline and
-// hidden (-fvisibility=hidden): nothing becomes an exported symbol.
+// convolutions, stft_host.cpp: Stft, pvoc_host.cpp: Pvoc): error mapping, device and stream handling, owned device /
+// pinned buffers, numeric switches of the environment, the exact host tables, and the prelude / creation / destruction
+// every object shares.  Everything here is inline and hidden (-fvisibility=hidden): nothing becomes an exported symbol.
 #pragma once
 #include "../../include/clfft_amd.h"
 
@@ -111,6 +111,14 @@ inline int ilog2(int n) {
   return l;
 }
 inline bool is_pow2(int n) { return n > 0 && (n & (n - 1)) == 0; }
+
+// a numeric tuning switch of the environment: atol of its value where that lies strictly between lo and hi, else 0
+// (unset, not a number, out of range).  lo >= 0, so 0 never is a value
+inline long env_long(const char *name, long lo, long hi) {
+  const char *env = getenv(name);
+  const long v = env ? atol(env) : 0;
+  return v > lo && v < hi ? v : 0;
+}
 
 // W_n^k = (cos(2 pi k/n), -sin(2 pi k/n)) rounded from double, the expression of
 // cl_fft.cpp:89-90 (`i * 2 * PI / N`) so the float values are bit-identical.

@@ -1,14 +1,14 @@
 // pvoc_adsyn.hip — oscillator-bank resynthesis of (amp, freq) frames straight to samples (clfa_pvoc_adsyn,
-// include/clfft_amd.h).  The arithmetic is pvoc_adsyn_plan.hpp's; three launches per sub-batch, the shape of the synthesis
-// in pvoc_kernels.hip:
+// include/clfft_amd.h).  The arithmetic is pvoc_adsyn_plan.hpp's: k_adsyn_sums calls adsyn_step (one frame of one
+// oscillator), k_adsyn_osc spells the same sequence out in its pre-walk and its group loop (it measured slower with the
+// call: DESIGN.md 4e).  Three launches per sub-batch, the shape of the synthesis in pvoc_kernels.hip:
 //
 //   k_adsyn_sums  per (channel, chunk of kPvocChunk frames, oscillator) the uint64 sum of the frames' phase advances.  The
 //                 advance of a frame needs the endpoint of the frame before: read from the frames, or — for the
 //                 sub-batch's first chunk — from the state, which these lanes also copy into the workspace (w0, a0): the
 //                 scan replaces the state before the oscillators run.
-//   k_adsyn_scan  k_pvoc_scan's scheme on 64-bit words: per (channel, oscillator) the chunks' sums become their bases in
-//                 place, P takes the total, W and A the endpoint of the sub-batch's last frame.  The old P is read before
-//                 the barrier and written after it.
+//   k_adsyn_scan  the scan of pvoc_device.hpp (k_pvoc_scan's) on 64-bit words: per (channel, oscillator) the chunks' sums
+//                 become their bases in place, P takes the total, W and A the endpoint of the sub-batch's last frame.
 //   k_adsyn_osc   the hot loop.  A workgroup takes one chunk of one channel, or — where that would leave workgroups idle — a
 //                 run of its frames (it then walks the chunk's earlier frames first: integers only, no samples).  Per
 //                 tile of kAdsynTile oscillators (ascending) and group of G frames: lanes act per oscillator — they walk the group's frames from the phase they carry
@@ -20,8 +20,8 @@
 //
 // No atomics, no waiting between workgroups, no scratch.  G = min(kAdsynGroupMax, ceil(256 / hop)) frames share the LDS
 // (at most 64 KiB: two workgroups per CU and more), so that hops below 256 still fill the lanes of the sample stage.
-#include "internal.hpp"
 #include "pvoc_adsyn_plan.hpp"
+#include "pvoc_device.hpp"
 
 namespace clfa {
 
@@ -29,7 +29,6 @@ namespace {
 
 constexpr int kAdsynWG = kAdsynTile;
 constexpr int kAdsynGroupMax = 8;
-constexpr int kAdsynScanBins = 64, kAdsynScanSegs = 16;
 typedef unsigned long long u64;
 
 struct alignas(16) AdsynOsc {
@@ -59,9 +58,9 @@ __global__ __launch_bounds__(kAdsynWG) void k_adsyn_sums(const cpx *__restrict__
                                                          u64 *__restrict__ sums) {
 #pragma unroll 1
   for (long item = blockIdx.x; item < items; item += gridDim.x) {
-    const long rest = item / tiles;
-    const int tile = (int)(item - rest * tiles);
-    const long c = rest / nch, j = rest - c * nch;
+    int tile;
+    long j, c;
+    pvoc_item(item, tiles, nch, tile, j, c);
     const int i = tile * kAdsynWG + (int)threadIdx.x;
     if (i >= nbins) continue;
     const int k = first + i * step;
@@ -79,59 +78,32 @@ __global__ __launch_bounds__(kAdsynWG) void k_adsyn_sums(const cpx *__restrict__
     }
     u64 s = 0;
     for (long f = f0; f < f1; f++, in += M + 1) {
-      int wf;
-      float af;
-      adsyn_end_at(in, fmod ? fmod + f : nullptr, ks, wf, af);
-      const int ws = adsyn_start(ap, wp, wf);
-      s += adsyn_advance(ws, adsyn_slope(ws, wf, hop), hop);
-      wp = wf;
-      ap = af;
+      const cpx af = *in;
+      int ws;
+      uint64_t d;
+      s += adsyn_step(wp, ap, af.x, af.y, fmod ? fmod[f] : 1.f, fmod != nullptr, ks, hop, ws, d);
     }
     sums[(c * nch + j) * nbins + i] = s;
   }
 }
 
-// one workgroup per (channel, tile of kAdsynScanBins oscillators), a wave per segment of the chunk axis; last: the
-// sub-batch's last frame of channel 0, fm_last its entry of fmod (or NULL)
-__global__ __launch_bounds__(kAdsynScanBins *kAdsynScanSegs) void k_adsyn_scan(u64 *__restrict__ sums, u64 *P, int *W, float *A,
-                                                                               const cpx *__restrict__ last, long cstride,
-                                                                               const float *__restrict__ fm_last, int M,
-                                                                               long nch, int first, int nbins, int step,
-                                                                               float ks, int tiles) {
-  __shared__ u64 s_tot[kAdsynScanSegs][kAdsynScanBins];
-  const int lane = threadIdx.x & (kAdsynScanBins - 1), seg = threadIdx.x / kAdsynScanBins;
+// one workgroup per (channel, tile of kScanBins oscillators); last: the sub-batch's last frame of channel 0, fm_last its
+// entry of fmod (or NULL)
+__global__ __launch_bounds__(kScanBins *kScanSegs) void k_adsyn_scan(u64 *__restrict__ sums, u64 *P, int *W, float *A,
+                                                                     const cpx *__restrict__ last, long cstride,
+                                                                     const float *__restrict__ fm_last, int M, long nch,
+                                                                     int first, int nbins, int step, float ks, int tiles) {
   const long c = blockIdx.x / tiles;
-  const int i = (int)(blockIdx.x - c * tiles) * kAdsynScanBins + lane;
+  const int i = (int)(blockIdx.x - c * tiles) * kScanBins + (int)(threadIdx.x & (kScanBins - 1));
   const bool live = i < nbins;
   const int k = live ? first + i * step : 0;
-  const long len = (nch + kAdsynScanSegs - 1) / kAdsynScanSegs;
-  const long j0 = seg * len < nch ? seg * len : nch, j1 = j0 + len < nch ? j0 + len : nch;
-  u64 *col = sums + c * nch * nbins + i;
-  u64 tot = 0, old = 0;
-  if (live) {
-    old = P[c * (M + 1) + k];
-    for (long j = j0; j < j1; j++) tot += col[j * nbins];
-  }
-  s_tot[seg][lane] = tot;
-  __syncthreads();   // every read of the old phase is behind this barrier, its one write after it
-  if (!live) return;
-  u64 run = old;
-  for (int s = 0; s < seg; s++) run += s_tot[s][lane];
-  if (seg == 0) {
-    u64 all = old;
-    for (int s = 0; s < kAdsynScanSegs; s++) all += s_tot[s][lane];
+  pvoc_scan(sums + c * nch * nbins + i, (long)nbins, nch, live, P + c * (M + 1) + k, [&] {
     int wf;
     float af;
     adsyn_end_at(last + c * cstride + k, fm_last, ks, wf, af);
-    P[c * (M + 1) + k] = all;
     W[c * (M + 1) + k] = wf;
     A[c * (M + 1) + k] = af;
-  }
-  for (long j = j0; j < j1; j++) {
-    const u64 v = col[j * nbins];
-    col[j * nbins] = run;
-    run += v;
-  }
+  });
 }
 
 // signal: the sub-batch's first sample of channel 0 (channel c at c * sstride floats); G frames per group, G * kAdsynTile
@@ -238,17 +210,15 @@ hipError_t launch_pvoc_adsyn(const PvocAdsynArgs &a, long f0, long nf, const Dev
   const long nch = (nf + kPvocChunk - 1) / kPvocChunk, cstride = a.F * (a.M + 1);
   const cpx *frames = reinterpret_cast<const cpx *>(a.frames) + f0 * (a.M + 1);
   const float *fmod = a.fmod ? a.fmod + f0 : nullptr;
-  long cap = (long)di.num_cus * 16;
-  if (a.grid_max > 0 && a.grid_max < cap) cap = a.grid_max;
   const int tiles = (a.nbins + kAdsynWG - 1) / kAdsynWG;
   const long sitems = (long)a.channels * nch * tiles;
-  hipLaunchKernelGGL(k_adsyn_sums, dim3((unsigned)(sitems < cap ? sitems : cap)), dim3(kAdsynWG), 0, s, frames, cstride,
-                     fmod, nf, a.M, nch, a.first, a.nbins, a.step, a.hop, a.ks, tiles, sitems, a.w, a.amp, a.w0, a.a0,
-                     a.sums);
+  hipLaunchKernelGGL(k_adsyn_sums, dim3(pvoc_grid(sitems, (long)di.num_cus * 16, a.grid_max)), dim3(kAdsynWG), 0, s, frames,
+                     cstride, fmod, nf, a.M, nch, a.first, a.nbins, a.step, a.hop, a.ks, tiles, sitems, a.w, a.amp, a.w0,
+                     a.a0, a.sums);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  const int stiles = (a.nbins + kAdsynScanBins - 1) / kAdsynScanBins;
-  hipLaunchKernelGGL(k_adsyn_scan, dim3((unsigned)(stiles * a.channels)), dim3(kAdsynScanBins * kAdsynScanSegs), 0, s,
+  const int stiles = (a.nbins + kScanBins - 1) / kScanBins;
+  hipLaunchKernelGGL(k_adsyn_scan, dim3((unsigned)(stiles * a.channels)), dim3(kScanBins * kScanSegs), 0, s,
                      a.sums, a.phase, a.w, a.amp, frames + (nf - 1) * (a.M + 1), cstride,
                      fmod ? fmod + (nf - 1) : nullptr, a.M, nch, a.first, a.nbins, a.step, a.ks, stiles);
   if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -263,7 +233,7 @@ hipError_t launch_pvoc_adsyn(const PvocAdsynArgs &a, long f0, long nf, const Dev
   while ((long)a.channels * nch * (kPvocChunk / run) < ocap && run / 2 >= G) run /= 2;
   const int nruns = kPvocChunk / run;
   const long oitems = (long)a.channels * nch * nruns;
-  hipLaunchKernelGGL(k_adsyn_osc, dim3((unsigned)(oitems < ocap ? oitems : ocap)), dim3(kAdsynWG),
+  hipLaunchKernelGGL(k_adsyn_osc, dim3(pvoc_grid(oitems, ocap, 0)), dim3(kAdsynWG),
                      sizeof(AdsynOsc) * (size_t)G * kAdsynTile, s, frames, cstride, fmod, nf, a.M, nch, a.first, a.nbins,
                      a.step, a.hop, G, a.ks, a.gain, a.sums, a.w0, a.a0, a.ramp, a.signal + f0 * a.hop, a.sstride, run, nruns, oitems);
   return hipGetLastError();

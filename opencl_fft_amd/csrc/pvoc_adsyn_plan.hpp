@@ -1,8 +1,9 @@
 // pvoc_adsyn_plan.hpp — the arithmetic of the oscillator-bank resynthesis (clfa_pvoc_adsyn, include/clfft_amd.h;
-// kernels: pvoc_adsyn.hip): the endpoint word of a frame, the start rule, the phase slope D, phase(j) and the advance of
-// a frame.  Plain functions of plain arguments, for the host and the device alike: tests/test_pvoc_adsyn_cpu.py builds
-// them with g++ and checks them against Python integers.  Phases are uint64 in 2^-64 turn, frequencies int32 in 2^-32
-// turn per sample; every sum is taken mod 2^64, so any grouping of the frames' advances gives the bits of the serial sum.
+// kernels: pvoc_adsyn.hip): the endpoint word of a frame, the start rule, the phase slope D, phase(j), the advance of a
+// frame, and adsyn_step, which puts them together for one frame of one oscillator.  Plain functions of plain arguments,
+// for the host and the device alike: tests/test_pvoc_adsyn_cpu.py builds them with g++ and checks them against Python
+// integers.  Phases are uint64 in 2^-64 turn, frequencies int32 in 2^-32 turn per sample; every sum is taken mod 2^64,
+// so any grouping of the frames' advances gives the bits of the serial sum.
 #pragma once
 
 #include <cmath>
@@ -70,5 +71,19 @@ CLFA_PLAN_HD inline uint32_t adsyn_phase_hi(uint64_t p, int32_t w0, uint64_t d, 
 
 // the advance of a frame: phase(hop) - P.  It depends on the frame's endpoint and the one before only
 CLFA_PLAN_HD inline uint64_t adsyn_advance(int32_t w0, uint64_t d, int hop) { return adsyn_phase(0, w0, d, (uint32_t)hop); }
+
+// one frame of one oscillator: (w, a) comes in as the endpoint of the frame before and goes out as this frame's; ws = W0
+// after the start rule, d = D; returns the frame's advance
+CLFA_PLAN_HD inline uint64_t adsyn_step(int32_t &w, float &a, float amp, float freq, float fmod, bool has_fmod, float ks,
+                                        int hop, int32_t &ws, uint64_t &d) {
+  int32_t wf;
+  float af;
+  adsyn_endpoint(amp, freq, fmod, has_fmod, ks, wf, af);
+  ws = adsyn_start(a, w, wf);
+  d = adsyn_slope(ws, wf, hop);
+  w = wf;
+  a = af;
+  return adsyn_advance(ws, d, hop);
+}
 
 }  // namespace clfa

@@ -1,0 +1,60 @@
+// pvoc_device.hpp — what the Pvoc kernel files share (pvoc_kernels.hip, pvoc_ops.hip, pvoc_adsyn.hip): the decoding of a
+// grid-stride item, the cap on a launch's workgroups, and the chunked scan that turns the per-chunk sums of phase
+// increments into the bases the chunks start from (k_pvoc_scan on uint32 words, k_adsyn_scan on uint64 ones).
+#pragma once
+#include "internal.hpp"
+
+namespace clfa {
+
+constexpr int kScanBins = 64, kScanSegs = 16;   // the scan's workgroup: a wave per segment of the chunk axis
+
+// item -> (outer index c, inner index j < inner, tile), the tile fastest: neighbouring workgroups hold neighbouring rows
+__device__ __forceinline__ void pvoc_item(long item, int tiles, long inner, int &tile, long &j, long &c) {
+  const long rest = item / tiles;
+  tile = (int)(item - rest * tiles);
+  c = rest / inner;
+  j = rest - c * inner;
+}
+
+// workgroups of a grid-stride launch: one per item, at most cap, at most grid_max where that is set (> 0)
+static inline int pvoc_grid(long items, long cap, int grid_max) {
+  if (grid_max > 0 && cap > grid_max) cap = grid_max;
+  return (int)(items < cap ? items : cap);
+}
+
+// The scan of one column (one bin of one channel) by the kScanSegs lanes that share `lane`: wave `seg` takes the chunks
+// [seg len, (seg + 1) len).  col: the column's entry of chunk 0, the chunks `stride` words apart, nch of them: their sums
+// become their bases in place (the state plus the sums of the chunks before).  *state takes the total, and the one lane
+// that stores it then runs store() (what else belongs to the new state).  Every lane of the workgroup calls this; a lane
+// that is not live touches no memory.
+// The barrier rule: every read of the old state is before the barrier, its one write after it.
+template <class Word, class Store>
+__device__ __forceinline__ void pvoc_scan(Word *col, long stride, long nch, bool live, Word *state, Store store) {
+  __shared__ Word s_tot[kScanSegs][kScanBins];
+  const int lane = threadIdx.x & (kScanBins - 1), seg = threadIdx.x / kScanBins;
+  const long len = (nch + kScanSegs - 1) / kScanSegs;
+  const long j0 = seg * len < nch ? seg * len : nch, j1 = j0 + len < nch ? j0 + len : nch;
+  Word tot = 0, old = 0;
+  if (live) {
+    old = *state;
+    for (long j = j0; j < j1; j++) tot += col[j * stride];
+  }
+  s_tot[seg][lane] = tot;
+  __syncthreads();
+  if (!live) return;
+  Word run = old;
+  for (int s = 0; s < seg; s++) run += s_tot[s][lane];
+  if (seg == 0) {
+    Word all = old;
+    for (int s = 0; s < kScanSegs; s++) all += s_tot[s][lane];
+    *state = all;
+    store();
+  }
+  for (long j = j0; j < j1; j++) {
+    const Word v = col[j * stride];
+    col[j * stride] = run;
+    run += v;
+  }
+}
+
+}  // namespace clfa

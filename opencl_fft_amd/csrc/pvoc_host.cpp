@@ -38,6 +38,29 @@ struct clfa_pvoc {
 };
 
 static size_t pvoc_bins(const clfa_pvoc *p) { return (size_t)p->channels * (p->M + 1); }
+static size_t pvoc_frame_bytes(const clfa_pvoc *p, long F) { return 2 * sizeof(float) * pvoc_bins(p) * (size_t)F; }
+static size_t pvoc_spec_bytes(const clfa_pvoc *p, long F) { return sizeof(cpx) * (size_t)p->channels * (size_t)F * p->M; }
+static bool pvoc_count_ok(long F) { return F >= 0 && F <= 0x7fffffffL; }   // a frame count
+
+// chunks per sub-batch: sub-batches bound a scan's workspace (`word` bytes per channel, chunk and bin) to about 64 MiB;
+// CLFA_PVOC_CHUNKS_MAX (tuning switch, read at creation) lowers it
+static long pvoc_chunks_cap(const clfa_pvoc *p, size_t word) {
+  long cap = (64L << 20) / ((long)word * (long)pvoc_bins(p));
+  cap = cap < 1 ? 1 : (cap > 4096 ? 4096 : cap);
+  if (const long v = env_long("CLFA_PVOC_CHUNKS_MAX", 0, cap)) cap = v;
+  return cap;
+}
+
+// launch(f0, nf) over the call's F frames in sub-batches of at most `held` chunks: each advances the state by its frames,
+// the next one starts from there
+template <class Launch>
+static int pvoc_subbatches(long F, long held, Launch launch) {
+  for (long f0 = 0; f0 < F; f0 += held * kPvocChunk) {
+    const long nf = F - f0 < held * kPvocChunk ? F - f0 : held * kPvocChunk;
+    HIP_TRY(launch(f0, nf));
+  }
+  return CLFA_SUCCESS;
+}
 
 // the states as at creation: prev = (1, 0), theta = 0, the oscillator bank's P = W = A = 0 (on p->stream, blocking)
 static int pvoc_init_state(clfa_pvoc *p) {
@@ -79,24 +102,10 @@ static int pvoc_setup(clfa_pvoc *p, int device, int size, int hop, double sr, in
   p->kf = (float)(hop / sr);
   p->bpf = (float)(size / sr);
   p->ks = (float)(1.0 / sr);
-  // sub-batches bound the scan's workspace (4 bytes per channel, chunk and bin) to about 64 MiB
-  p->cap = (64L << 20) / ((long)sizeof(unsigned) * (long)pvoc_bins(p));
-  p->cap = p->cap < 1 ? 1 : (p->cap > 4096 ? 4096 : p->cap);
-  if (const char *env = getenv("CLFA_PVOC_CHUNKS_MAX")) {
-    if (atol(env) > 0 && atol(env) < p->cap) p->cap = atol(env);
-  }
-  // the oscillator bank's chunk sums are 8 bytes each: its sub-batches are bounded the same way, by the same switch
-  p->acap = (64L << 20) / ((long)sizeof(unsigned long long) * (long)pvoc_bins(p));
-  p->acap = p->acap < 1 ? 1 : (p->acap > 4096 ? 4096 : p->acap);
-  if (const char *env = getenv("CLFA_PVOC_CHUNKS_MAX")) {
-    if (atol(env) > 0 && atol(env) < p->acap) p->acap = atol(env);
-  }
-  if (const char *env = getenv("CLFA_PVOC_OPS_GRID_MAX")) {
-    if (atol(env) > 0 && atol(env) < 0x7fffffffL) p->ops_grid_max = (int)atol(env);
-  }
-  if (const char *env = getenv("CLFA_PVOC_ADSYN_GRID_MAX")) {
-    if (atol(env) > 0 && atol(env) < 0x7fffffffL) p->adsyn_grid_max = (int)atol(env);
-  }
+  p->cap = pvoc_chunks_cap(p, sizeof(unsigned));              // the synthesis' chunk sums are 4 bytes each,
+  p->acap = pvoc_chunks_cap(p, sizeof(unsigned long long));   // the oscillator bank's 8
+  p->ops_grid_max = (int)env_long("CLFA_PVOC_OPS_GRID_MAX", 0, 0x7fffffffL);
+  p->adsyn_grid_max = (int)env_long("CLFA_PVOC_ADSYN_GRID_MAX", 0, 0x7fffffffL);
   int e = device_info(device, p->di);
   if (e) return e;
   ENTER_DEVICE(device);
@@ -129,14 +138,63 @@ static int pvoc_quiesce(clfa_pvoc *p) {
   return CLFA_SUCCESS;
 }
 
+// the blocking read of states: NULL arguments are invalid values, the object's earlier work is waited for
+struct PvocState {
+  void *host;
+  DevBuf clfa_pvoc::*buf;
+  size_t word;   // bytes per channel and bin
+};
+static int pvoc_read_state(clfa_pvoc *p, std::initializer_list<PvocState> states) {
+  if (int e = obj_error(p)) return e;
+  for (const PvocState &st : states)
+    if (!st.host) return CLFA_INVALID_VALUE;
+  ENTER_DEVICE(p->di.device);
+  if (int e = pvoc_quiesce(p)) return e;
+  for (const PvocState &st : states) HIP_TRY(hipMemcpy(st.host, (p->*st.buf).p, st.word * pvoc_bins(p), hipMemcpyDeviceToHost));
+  return CLFA_SUCCESS;
+}
+
+// The blocking host forms: every array has a staging buffer on the device, ensured in the order of the list; the inputs
+// are copied in, dev() runs the device form on the staging buffers and the object's stream, the outputs are copied out,
+// and the stream is waited for.  An array is `rows` rows of `bytes` each, packed in the staging buffer and `pitch` bytes
+// apart on the host (0: packed there too, one plain copy); an input whose host pointer is NULL is left out.
+struct PvocStaged {
+  bool out;
+  const void *host;
+  DevBuf *buf;
+  size_t bytes, rows = 1, pitch = 0;
+};
+template <class Dev>
+static int pvoc_staged(clfa_pvoc *p, std::initializer_list<PvocStaged> arrays, Dev dev) {
+  ENTER_DEVICE(p->di.device);
+  for (const PvocStaged &a : arrays)
+    if (int e = a.host ? a.buf->ensure(a.bytes * a.rows) : 0) return e;
+  for (const PvocStaged &a : arrays)
+    if (!a.out && a.host) HIP_TRY(hipMemcpyAsync(a.buf->p, a.host, a.bytes * a.rows, hipMemcpyHostToDevice, p->stream));
+  if (int e = dev()) return e;
+  for (const PvocStaged &a : arrays) {
+    void *host = const_cast<void *>(a.host);
+    if (a.out && a.pitch)
+      HIP_TRY(hipMemcpy2DAsync(host, a.pitch, a.buf->p, a.bytes, a.bytes, a.rows, hipMemcpyDeviceToHost, p->stream));
+    else if (a.out)
+      HIP_TRY(hipMemcpyAsync(host, a.buf->p, a.bytes * a.rows, hipMemcpyDeviceToHost, p->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return CLFA_SUCCESS;
+}
+
+// The results of the argument checks: 0 = go on, 1 = a successful no-op, < 0 = the error.  An operation or the oscillator
+// bank goes on after its device-free checks with the error, else the object's own error, else chk:
+//   if (int e = pvoc_gate(p, chk)) return pvoc_done(e);
+static int pvoc_gate(const clfa_pvoc *p, int chk) { return chk < 0 ? chk : (p->err ? p->err : chk); }
+static int pvoc_done(int e) { return e == 1 ? CLFA_SUCCESS : e; }
+
 // the argument rules both directions share; 1 = a successful no-op
-static int pvoc_check(const clfa_pvoc *p, const void *spectra, const void *frames, long F, size_t *sbytes, size_t *fbytes) {
-  if (F < 0 || F > 0x7fffffffL) return CLFA_INVALID_VALUE;
+static int pvoc_check(const clfa_pvoc *p, const void *spectra, const void *frames, long F) {
+  if (!pvoc_count_ok(F)) return CLFA_INVALID_VALUE;
   if (F == 0) return 1;
   if (!spectra || !frames || ((uintptr_t)spectra & 7) || ((uintptr_t)frames & 7)) return CLFA_INVALID_VALUE;
-  *sbytes = sizeof(cpx) * (size_t)p->channels * F * p->M;
-  *fbytes = 2 * sizeof(float) * pvoc_bins(p) * F;
-  if (spans_overlap(spectra, *sbytes, frames, *fbytes)) return CLFA_INVALID_VALUE;
+  if (spans_overlap(spectra, pvoc_spec_bytes(p, F), frames, pvoc_frame_bytes(p, F))) return CLFA_INVALID_VALUE;
   return CLFA_SUCCESS;
 }
 
@@ -179,27 +237,16 @@ int clfa_pvoc_reset(clfa_pvoc *p) {
 }
 
 int clfa_pvoc_read_phase(clfa_pvoc *p, unsigned *host) {
-  if (int e = obj_error(p)) return e;
-  if (!host) return CLFA_INVALID_VALUE;
-  ENTER_DEVICE(p->di.device);
-  if (int e = pvoc_quiesce(p)) return e;
-  HIP_TRY(hipMemcpy(host, p->theta.p, sizeof(unsigned) * pvoc_bins(p), hipMemcpyDeviceToHost));
-  return CLFA_SUCCESS;
+  return pvoc_read_state(p, {{host, &clfa_pvoc::theta, sizeof(unsigned)}});
 }
 
 int clfa_pvoc_read_prev(clfa_pvoc *p, float *host) {
-  if (int e = obj_error(p)) return e;
-  if (!host) return CLFA_INVALID_VALUE;
-  ENTER_DEVICE(p->di.device);
-  if (int e = pvoc_quiesce(p)) return e;
-  HIP_TRY(hipMemcpy(host, p->prev.p, sizeof(cpx) * pvoc_bins(p), hipMemcpyDeviceToHost));
-  return CLFA_SUCCESS;
+  return pvoc_read_state(p, {{host, &clfa_pvoc::prev, sizeof(cpx)}});
 }
 
 int clfa_pvoc_analyze_dev(clfa_pvoc *p, const void *spectra, void *frames_out, long F, void *stream) {
   if (int e = obj_error(p)) return e;
-  size_t sbytes, fbytes;
-  if (int e = pvoc_check(p, spectra, frames_out, F, &sbytes, &fbytes)) return e == 1 ? CLFA_SUCCESS : e;
+  if (int e = pvoc_check(p, spectra, frames_out, F)) return pvoc_done(e);
   ENTER_DEVICE(p->di.device);
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(p->order.use(s));
@@ -212,8 +259,7 @@ int clfa_pvoc_analyze_dev(clfa_pvoc *p, const void *spectra, void *frames_out, l
 
 int clfa_pvoc_synthesize_dev(clfa_pvoc *p, const void *frames, void *spectra_out, long F, void *stream) {
   if (int e = obj_error(p)) return e;
-  size_t sbytes, fbytes;
-  if (int e = pvoc_check(p, spectra_out, frames, F, &sbytes, &fbytes)) return e == 1 ? CLFA_SUCCESS : e;
+  if (int e = pvoc_check(p, spectra_out, frames, F)) return pvoc_done(e);
   ENTER_DEVICE(p->di.device);
   hipStream_t s = (hipStream_t)stream;
   const long held = p->cap;   // the whole sub-batch workspace at the first need: its address never changes afterwards
@@ -222,12 +268,7 @@ int clfa_pvoc_synthesize_dev(clfa_pvoc *p, const void *frames, void *spectra_out
   PvocArgs a = pvoc_args(p, F);
   a.frames_in = (const float *)frames;
   a.spec_out = (cpx *)spectra_out;
-  // sub-batches of at most `held` chunks: each advances the state by its frames, the next one starts from there
-  for (long f0 = 0; f0 < F; f0 += held * kPvocChunk) {
-    const long nf = F - f0 < held * kPvocChunk ? F - f0 : held * kPvocChunk;
-    HIP_TRY(launch_pvoc_synth(a, f0, nf, p->di, s));
-  }
-  return CLFA_SUCCESS;
+  return pvoc_subbatches(F, held, [&](long f0, long nf) { return launch_pvoc_synth(a, f0, nf, p->di, s); });
 }
 
 // ---------------------------------------------------------------------------------
@@ -241,14 +282,14 @@ static int pvoc_ops_check(const clfa_pvoc *p, int op, const void *in, long Fin, 
                           int lowest, int keepform, int coefs, bool device_ptrs) {
   if (!p) return CLFA_INVALID_VALUE;
   if (!p->M) return p->err ? p->err : CLFA_INVALID_VALUE;
-  if (F < 0 || F > 0x7fffffffL) return CLFA_INVALID_VALUE;
+  if (!pvoc_count_ok(F)) return CLFA_INVALID_VALUE;
   if (op == PVOC_READ && (Fin < 1 || Fin > (1L << 24))) return CLFA_INVALID_VALUE;
   if (op == PVOC_SHIFT && (lowest < 1 || lowest > p->M - 1)) return CLFA_INVALID_VALUE;
   if (op != PVOC_READ && keepform && (coefs < 1 || coefs >= p->M)) return CLFA_INVALID_VALUE;
   if (F == 0) return 1;
   if (!in || !out || !par) return CLFA_INVALID_VALUE;
   if (device_ptrs && (((uintptr_t)in & 7) || ((uintptr_t)out & 7) || ((uintptr_t)par & 3))) return CLFA_INVALID_VALUE;
-  const size_t ibytes = 2 * sizeof(float) * pvoc_bins(p) * (size_t)Fin, obytes = 2 * sizeof(float) * pvoc_bins(p) * (size_t)F;
+  const size_t ibytes = pvoc_frame_bytes(p, Fin), obytes = pvoc_frame_bytes(p, F);
   if (spans_overlap(in, ibytes, out, obytes) || spans_overlap(par, sizeof(float) * (size_t)F, out, obytes))
     return CLFA_INVALID_VALUE;
   return CLFA_SUCCESS;
@@ -256,10 +297,7 @@ static int pvoc_ops_check(const clfa_pvoc *p, int op, const void *in, long Fin, 
 
 static int pvoc_ops_dev(clfa_pvoc *p, int op, const void *in, long Fin, const void *par, void *out, long F, int lowest,
                         int keepform, float gain, int coefs, void *stream) {
-  const int chk = pvoc_ops_check(p, op, in, Fin, par, out, F, lowest, keepform, coefs, true);
-  if (chk < 0) return chk;
-  if (p->err) return p->err;
-  if (chk == 1) return CLFA_SUCCESS;
+  if (int e = pvoc_gate(p, pvoc_ops_check(p, op, in, Fin, par, out, F, lowest, keepform, coefs, true))) return pvoc_done(e);
   ENTER_DEVICE(p->di.device);
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(p->order.use(s));
@@ -294,21 +332,12 @@ static int pvoc_ops_host(clfa_pvoc *p, int op, const float *in, long Fin, const 
   for (long f = 0; f < F && op != PVOC_READ; f++) {
     if (!std::isfinite(par[f]) || (op == PVOC_SCALE && !(par[f] >= 0.25f && par[f] <= 4.f))) return CLFA_INVALID_VALUE;
   }
-  if (p->err) return p->err;
-  if (chk == 1) return CLFA_SUCCESS;
-  const size_t ibytes = 2 * sizeof(float) * pvoc_bins(p) * (size_t)Fin, obytes = 2 * sizeof(float) * pvoc_bins(p) * (size_t)F;
-  ENTER_DEVICE(p->di.device);
-  int e = p->sframes.ensure(ibytes);
-  if (!e) e = p->sop_out.ensure(obytes);
-  if (!e) e = p->sop_par.ensure(sizeof(float) * (size_t)F);
-  if (e) return e;
-  HIP_TRY(hipMemcpyAsync(p->sframes.p, in, ibytes, hipMemcpyHostToDevice, p->stream));
-  HIP_TRY(hipMemcpyAsync(p->sop_par.p, par, sizeof(float) * (size_t)F, hipMemcpyHostToDevice, p->stream));
-  if ((e = pvoc_ops_dev(p, op, p->sframes.p, Fin, p->sop_par.p, p->sop_out.p, F, lowest, keepform, gain, coefs, p->stream)))
-    return e;
-  HIP_TRY(hipMemcpyAsync(out, p->sop_out.p, obytes, hipMemcpyDeviceToHost, p->stream));
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  return CLFA_SUCCESS;
+  if (int e = pvoc_gate(p, chk)) return pvoc_done(e);
+  return pvoc_staged(p, {{false, in, &p->sframes, pvoc_frame_bytes(p, Fin)}, {true, out, &p->sop_out, pvoc_frame_bytes(p, F)},
+                         {false, par, &p->sop_par, sizeof(float) * (size_t)F}}, [&] {
+                       return pvoc_ops_dev(p, op, p->sframes.p, Fin, p->sop_par.p, p->sop_out.p, F, lowest, keepform, gain,
+                                           coefs, p->stream);
+                     });
 }
 
 int clfa_pvoc_scale_dev(clfa_pvoc *p, const void *frames_in, void *frames_out, long F, const void *scale, int keepform,
@@ -341,34 +370,18 @@ const char *clfa_pvoc_ops_kernel_name(const clfa_pvoc *p, int op, int keepform) 
 
 int clfa_pvoc_analyze(clfa_pvoc *p, const float *spectra, float *frames_out, long F) {
   if (int e = obj_error(p)) return e;
-  if (F < 0 || F > 0x7fffffffL || (F > 0 && (!spectra || !frames_out))) return CLFA_INVALID_VALUE;
+  if (!pvoc_count_ok(F) || (F > 0 && (!spectra || !frames_out))) return CLFA_INVALID_VALUE;
   if (F == 0) return CLFA_SUCCESS;
-  const size_t sbytes = sizeof(cpx) * (size_t)p->channels * F * p->M, fbytes = 2 * sizeof(float) * pvoc_bins(p) * F;
-  ENTER_DEVICE(p->di.device);
-  int e = p->sspec.ensure(sbytes);
-  if (!e) e = p->sframes.ensure(fbytes);
-  if (e) return e;
-  HIP_TRY(hipMemcpyAsync(p->sspec.p, spectra, sbytes, hipMemcpyHostToDevice, p->stream));
-  if ((e = clfa_pvoc_analyze_dev(p, p->sspec.p, p->sframes.p, F, p->stream))) return e;
-  HIP_TRY(hipMemcpyAsync(frames_out, p->sframes.p, fbytes, hipMemcpyDeviceToHost, p->stream));
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  return CLFA_SUCCESS;
+  return pvoc_staged(p, {{false, spectra, &p->sspec, pvoc_spec_bytes(p, F)}, {true, frames_out, &p->sframes, pvoc_frame_bytes(p, F)}},
+                     [&] { return clfa_pvoc_analyze_dev(p, p->sspec.p, p->sframes.p, F, p->stream); });
 }
 
 int clfa_pvoc_synthesize(clfa_pvoc *p, const float *frames, float *spectra_out, long F) {
   if (int e = obj_error(p)) return e;
-  if (F < 0 || F > 0x7fffffffL || (F > 0 && (!frames || !spectra_out))) return CLFA_INVALID_VALUE;
+  if (!pvoc_count_ok(F) || (F > 0 && (!frames || !spectra_out))) return CLFA_INVALID_VALUE;
   if (F == 0) return CLFA_SUCCESS;
-  const size_t sbytes = sizeof(cpx) * (size_t)p->channels * F * p->M, fbytes = 2 * sizeof(float) * pvoc_bins(p) * F;
-  ENTER_DEVICE(p->di.device);
-  int e = p->sspec.ensure(sbytes);
-  if (!e) e = p->sframes.ensure(fbytes);
-  if (e) return e;
-  HIP_TRY(hipMemcpyAsync(p->sframes.p, frames, fbytes, hipMemcpyHostToDevice, p->stream));
-  if ((e = clfa_pvoc_synthesize_dev(p, p->sframes.p, p->sspec.p, F, p->stream))) return e;
-  HIP_TRY(hipMemcpyAsync(spectra_out, p->sspec.p, sbytes, hipMemcpyDeviceToHost, p->stream));
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  return CLFA_SUCCESS;
+  return pvoc_staged(p, {{true, spectra_out, &p->sspec, pvoc_spec_bytes(p, F)}, {false, frames, &p->sframes, pvoc_frame_bytes(p, F)}},
+                     [&] { return clfa_pvoc_synthesize_dev(p, p->sframes.p, p->sspec.p, F, p->stream); });
 }
 
 }  // extern "C"
@@ -383,14 +396,14 @@ static int pvoc_adsyn_check(const clfa_pvoc *p, const void *frames, long F, cons
                             int step, const void *signal, long signal_stride, bool device_ptrs) {
   if (!p) return CLFA_INVALID_VALUE;
   if (!p->M) return p->err ? p->err : CLFA_INVALID_VALUE;
-  if (F < 0 || F > 0x7fffffffL) return CLFA_INVALID_VALUE;
+  if (!pvoc_count_ok(F)) return CLFA_INVALID_VALUE;
   if (step < 1 || nbins < 1 || first_bin < 0 || (long)first_bin + ((long)nbins - 1) * step > p->M) return CLFA_INVALID_VALUE;
   if (signal_stride < F * p->hop) return CLFA_INVALID_VALUE;
   if (F == 0) return 1;
   if (!frames || !signal) return CLFA_INVALID_VALUE;
   if (device_ptrs && (((uintptr_t)frames & 7) || ((uintptr_t)signal & 3) || ((uintptr_t)fmod & 3))) return CLFA_INVALID_VALUE;
   // the output's rows and the gaps between them, as one span
-  const size_t fbytes = 2 * sizeof(float) * pvoc_bins(p) * (size_t)F;
+  const size_t fbytes = pvoc_frame_bytes(p, F);
   const size_t obytes = sizeof(float) * ((size_t)(p->channels - 1) * (size_t)signal_stride + (size_t)F * p->hop);
   if (spans_overlap(frames, fbytes, signal, obytes)) return CLFA_INVALID_VALUE;
   if (fmod && spans_overlap(fmod, sizeof(float) * (size_t)F, signal, obytes)) return CLFA_INVALID_VALUE;
@@ -405,10 +418,8 @@ extern "C" {
 
 int clfa_pvoc_adsyn_dev(clfa_pvoc *p, const void *frames, long F, const void *fmod, int first_bin, int nbins, int step,
                         float gain, void *signal, long signal_stride, void *stream) {
-  const int chk = pvoc_adsyn_check(p, frames, F, fmod, first_bin, nbins, step, signal, signal_stride, true);
-  if (chk < 0) return chk;
-  if (p->err) return p->err;
-  if (chk == 1) return CLFA_SUCCESS;
+  if (int e = pvoc_gate(p, pvoc_adsyn_check(p, frames, F, fmod, first_bin, nbins, step, signal, signal_stride, true)))
+    return pvoc_done(e);
   ENTER_DEVICE(p->di.device);
   hipStream_t s = (hipStream_t)stream;
   const long held = p->acap;   // the whole workspace at the first need: its address never changes afterwards
@@ -436,46 +447,28 @@ int clfa_pvoc_adsyn_dev(clfa_pvoc *p, const void *frames, long F, const void *fm
   a.signal = (float *)signal;
   a.sstride = signal_stride;
   a.grid_max = p->adsyn_grid_max;
-  // sub-batches of at most `held` chunks: each advances the state by its frames, the next one starts from there
-  for (long f0 = 0; f0 < F; f0 += held * kPvocChunk) {
-    const long nf = F - f0 < held * kPvocChunk ? F - f0 : held * kPvocChunk;
-    HIP_TRY(launch_pvoc_adsyn(a, f0, nf, p->di, s));
-  }
-  return CLFA_SUCCESS;
+  return pvoc_subbatches(F, held, [&](long f0, long nf) { return launch_pvoc_adsyn(a, f0, nf, p->di, s); });
 }
 
 int clfa_pvoc_adsyn(clfa_pvoc *p, const float *frames, long F, const float *fmod, int first_bin, int nbins, int step,
                     float gain, float *signal, long signal_stride) {
-  const int chk = pvoc_adsyn_check(p, frames, F, fmod, first_bin, nbins, step, signal, signal_stride, false);
-  if (chk < 0) return chk;
-  if (p->err) return p->err;
-  if (chk == 1) return CLFA_SUCCESS;
-  const size_t fbytes = 2 * sizeof(float) * pvoc_bins(p) * (size_t)F, row = sizeof(float) * (size_t)F * p->hop;
-  ENTER_DEVICE(p->di.device);
-  int e = p->sframes.ensure(fbytes);
-  if (!e) e = p->ssig.ensure(row * p->channels);
-  if (!e && fmod) e = p->sfmod.ensure(sizeof(float) * (size_t)F);
-  if (e) return e;
-  HIP_TRY(hipMemcpyAsync(p->sframes.p, frames, fbytes, hipMemcpyHostToDevice, p->stream));
-  if (fmod) HIP_TRY(hipMemcpyAsync(p->sfmod.p, fmod, sizeof(float) * (size_t)F, hipMemcpyHostToDevice, p->stream));
-  if ((e = clfa_pvoc_adsyn_dev(p, p->sframes.p, F, fmod ? p->sfmod.p : nullptr, first_bin, nbins, step, gain, p->ssig.p,
-                               F * p->hop, p->stream)))
-    return e;
-  HIP_TRY(hipMemcpy2DAsync(signal, sizeof(float) * (size_t)signal_stride, p->ssig.p, row, row, p->channels,
-                           hipMemcpyDeviceToHost, p->stream));
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  return CLFA_SUCCESS;
+  if (int e = pvoc_gate(p, pvoc_adsyn_check(p, frames, F, fmod, first_bin, nbins, step, signal, signal_stride, false)))
+    return pvoc_done(e);
+  // the staged output's rows are packed, the caller's signal_stride floats apart
+  return pvoc_staged(p, {{false, frames, &p->sframes, pvoc_frame_bytes(p, F)},
+                         {true, signal, &p->ssig, sizeof(float) * (size_t)F * p->hop, (size_t)p->channels,
+                          sizeof(float) * (size_t)signal_stride},
+                         {false, fmod, &p->sfmod, sizeof(float) * (size_t)F}},
+                     [&] {
+                       return clfa_pvoc_adsyn_dev(p, p->sframes.p, F, fmod ? p->sfmod.p : nullptr, first_bin, nbins, step,
+                                                  gain, p->ssig.p, F * p->hop, p->stream);
+                     });
 }
 
 int clfa_pvoc_adsyn_read_state(clfa_pvoc *p, unsigned long long *phase, int *w, float *amp) {
-  if (int e = obj_error(p)) return e;
-  if (!phase || !w || !amp) return CLFA_INVALID_VALUE;
-  ENTER_DEVICE(p->di.device);
-  if (int e = pvoc_quiesce(p)) return e;
-  HIP_TRY(hipMemcpy(phase, p->aphase.p, sizeof(unsigned long long) * pvoc_bins(p), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(w, p->aw.p, sizeof(int) * pvoc_bins(p), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(amp, p->aamp.p, sizeof(float) * pvoc_bins(p), hipMemcpyDeviceToHost));
-  return CLFA_SUCCESS;
+  return pvoc_read_state(p, {{phase, &clfa_pvoc::aphase, sizeof(unsigned long long)},
+                             {w, &clfa_pvoc::aw, sizeof(int)},
+                             {amp, &clfa_pvoc::aamp, sizeof(float)}});
 }
 
 size_t clfa_pvoc_adsyn_workspace_bytes(const clfa_pvoc *p) { return p ? p->aws.bytes : 0; }

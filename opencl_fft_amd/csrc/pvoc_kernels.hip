@@ -7,8 +7,8 @@
 //   k_pvoc_sums     synthesis, launch 1: per (channel, chunk of kPvocChunk frames, bin) the sum of the frames' phase
 //                   increments (uint32, units of 2^-32 turn);
 //   k_pvoc_scan     launch 2, small: per (channel, bin) the chunks' sums become their bases in place (the state plus the
-//                   sums of the chunks before), and the state takes the call's total — one workgroup reads the old state
-//                   before a barrier and one of its lanes writes the new one after it;
+//                   sums of the chunks before), and the state takes the call's total: the scan of pvoc_device.hpp, which
+//                   the oscillator bank shares (k_adsyn_scan, pvoc_adsyn.hip);
 //   k_pvoc_walk     launch 3: every chunk starts from its base and walks its frames, writing spectra.
 //
 // The phases are integers, and integer addition is associative: the chunked sums are the bits of the serial sum, for every
@@ -16,7 +16,7 @@
 //
 // Every global access is a row of consecutive bins: 8 bytes per lane (a complex bin, or an (amp, freq) pair), 4 in the
 // sums and bases.
-#include "internal.hpp"
+#include "pvoc_device.hpp"
 
 namespace clfa {
 
@@ -24,7 +24,6 @@ namespace {
 
 constexpr int kPvocWG = 256;    // lanes = bins per workgroup tile
 constexpr int kPvocRun = 4;     // consecutive frames per lane of the analysis
-constexpr int kScanBins = 64, kScanSegs = 16;   // k_pvoc_scan: a wave per segment of the chunk axis
 
 // z[k] of a packed row: bin 0 = (Re P[0], 0), bin M = (Im P[0], 0), bin M/2 conjugated
 __device__ __forceinline__ cpx pvoc_bin(const cpx *__restrict__ row, int k, int M) {
@@ -45,14 +44,6 @@ __device__ __forceinline__ unsigned pvoc_inc(float freq, float kf) {
   const float r = t - rintf(t);
   if (!(fabsf(r) <= 0.5f)) return 0u;   // a non-finite freq (or freq * kf): the phase stays
   return (unsigned)(long long)rint((double)r * 4294967296.0);
-}
-
-// item -> (channel, second index, bin tile), the tile fastest: neighbouring workgroups hold neighbouring rows
-__device__ __forceinline__ void pvoc_item(long item, int tiles, long inner, int &tile, long &j, long &c) {
-  const long rest = item / tiles;
-  tile = (int)(item - rest * tiles);
-  c = rest / inner;
-  j = rest - c * inner;
 }
 
 }  // namespace
@@ -105,37 +96,12 @@ __global__ __launch_bounds__(kPvocWG) void k_pvoc_sums(const cpx *__restrict__ f
   }
 }
 
-// one workgroup per (channel, tile of kScanBins bins), kScanBins x kScanSegs lanes: wave s takes the chunks [s len, (s + 1) len)
+// one workgroup per (channel, tile of kScanBins bins), kScanBins x kScanSegs lanes
 __global__ __launch_bounds__(kScanBins *kScanSegs) void k_pvoc_scan(unsigned *__restrict__ sums, unsigned *theta, int M,
                                                                     long nch, int tiles) {
-  __shared__ unsigned s_tot[kScanSegs][kScanBins];
-  const int lane = threadIdx.x & (kScanBins - 1), seg = threadIdx.x / kScanBins;
   const long c = blockIdx.x / tiles;
-  const int k = (int)(blockIdx.x - c * tiles) * kScanBins + lane;
-  const bool live = k <= M;
-  const long len = (nch + kScanSegs - 1) / kScanSegs;
-  const long j0 = seg * len < nch ? seg * len : nch, j1 = j0 + len < nch ? j0 + len : nch;
-  unsigned *col = sums + c * nch * (M + 1) + k;
-  unsigned tot = 0, th = 0;
-  if (live) {
-    th = theta[c * (M + 1) + k];
-    for (long j = j0; j < j1; j++) tot += col[j * (M + 1)];
-  }
-  s_tot[seg][lane] = tot;
-  __syncthreads();   // every read of the old state is behind this barrier, its one write after it
-  if (!live) return;
-  unsigned run = th;
-  for (int s = 0; s < seg; s++) run += s_tot[s][lane];
-  if (seg == 0) {
-    unsigned all = th;
-    for (int s = 0; s < kScanSegs; s++) all += s_tot[s][lane];
-    theta[c * (M + 1) + k] = all;
-  }
-  for (long j = j0; j < j1; j++) {
-    const unsigned v = col[j * (M + 1)];
-    col[j * (M + 1)] = run;
-    run += v;
-  }
+  const int k = (int)(blockIdx.x - c * tiles) * kScanBins + (int)(threadIdx.x & (kScanBins - 1));
+  pvoc_scan(sums + c * nch * (M + 1) + k, (long)(M + 1), nch, k <= M, theta + c * (M + 1) + k, [] {});
 }
 
 __global__ __launch_bounds__(kPvocWG) void k_pvoc_walk(const cpx *__restrict__ frames, long cstride, long nf, int M,
@@ -167,16 +133,11 @@ __global__ __launch_bounds__(kPvocWG) void k_pvoc_walk(const cpx *__restrict__ f
   }
 }
 
-static int pvoc_grid(long items, const DeviceInfo &di) {
-  const long cap = (long)di.num_cus * 16;
-  return (int)(items < cap ? items : cap);
-}
-
 hipError_t launch_pvoc_analyze(const PvocArgs &a, const DeviceInfo &di, hipStream_t s) {
   if (a.F <= 0 || a.channels <= 0) return hipSuccess;
   const int tiles = (a.M + 1 + kPvocWG - 1) / kPvocWG;
   const long groups = (a.F + kPvocRun - 1) / kPvocRun, items = (long)a.channels * groups * tiles;
-  hipLaunchKernelGGL(k_pvoc_analyze, dim3(pvoc_grid(items, di)), dim3(kPvocWG), 0, s, a.spec_in, a.frames_out, a.prev,
+  hipLaunchKernelGGL(k_pvoc_analyze, dim3(pvoc_grid(items, (long)di.num_cus * 16, 0)), dim3(kPvocWG), 0, s, a.spec_in, a.frames_out, a.prev,
                      a.etab, a.F, a.M, groups, tiles, items, a.sh, a.srs);
   return hipGetLastError();
 }
@@ -187,7 +148,7 @@ hipError_t launch_pvoc_synth(const PvocArgs &a, long f0, long nf, const DeviceIn
   const long nch = (nf + kPvocChunk - 1) / kPvocChunk, items = (long)a.channels * nch * tiles;
   const long cstride = a.F * (a.M + 1), sstride = a.F * a.M;
   const cpx *frames = reinterpret_cast<const cpx *>(a.frames_in) + f0 * (a.M + 1);
-  const int grid = pvoc_grid(items, di);
+  const int grid = pvoc_grid(items, (long)di.num_cus * 16, 0);
   hipLaunchKernelGGL(k_pvoc_sums, dim3(grid), dim3(kPvocWG), 0, s, frames, cstride, nf, a.M, nch, tiles, items, a.kf,
                      a.sums);
   hipError_t e = hipGetLastError();

@@ -1,5 +1,6 @@
 // pvoc_ops.hip — operations on the (amp, freq) frames of clfa_pvoc (include/clfft_amd.h): pitch scale, frequency shift
-// and timed read.  All three are stateless, one launch per call, deterministic (gathers: no atomics).
+// and timed read.  All three are stateless, one launch per call, deterministic (gathers: no atomics).  The decoding of a
+// grid-stride item and the cap on a launch's workgroups are pvoc_device.hpp's, as in the other Pvoc kernel files.
 //
 //   k_pvoc_map      scale and shift without keepform: a lane takes output bin j of one frame, finds its source bin and
 //                   writes the pair; rows of consecutive bins, 8 bytes per lane, no LDS.
@@ -17,6 +18,7 @@
 // Every float32 step of the definitions is rounded on its own: the device functions below switch contraction off, as
 // pvoc_inc does (pvoc_kernels.hip).  tests/pvoc_ops_model.py restates them.
 #include "fft_wg.hpp"
+#include "pvoc_device.hpp"
 
 namespace clfa {
 
@@ -85,16 +87,19 @@ __device__ __forceinline__ cpx pvoc_lerp(cpx x0, cpx x1, float a) {
 
 }  // namespace
 
-// item -> (frame b = c * F + f, bin tile), the tile fastest
+// item -> (channel, frame f, bin tile), the tile fastest
 __global__ __launch_bounds__(kOpsWG) void k_pvoc_map(const cpx *__restrict__ in, cpx *__restrict__ out,
                                                      const float *__restrict__ par, long F, int M, int tiles, long items,
                                                      int op, int lowest, float gain, float cf, float bpf) {
 #pragma unroll 1
   for (long item = blockIdx.x; item < items; item += gridDim.x) {
-    const long b = item / tiles;
-    const int j = (int)(item - b * tiles) * kOpsWG + (int)threadIdx.x;
+    int tile;
+    long f, c;
+    pvoc_item(item, tiles, F, tile, f, c);
+    const int j = tile * kOpsWG + (int)threadIdx.x;
     if (j > M) continue;
-    const float s = par[b % F];
+    const long b = c * F + f;
+    const float s = par[f];
     const cpx *row = in + b * (M + 1);
     const int src = pvoc_source(op, j, M, lowest, s, bpf);
     cpx o;
@@ -114,10 +119,12 @@ __global__ __launch_bounds__(kOpsWG) void k_pvoc_read(const cpx *__restrict__ in
                                                       int tiles, long items) {
 #pragma unroll 1
   for (long item = blockIdx.x; item < items; item += gridDim.x) {
-    const long b = item / tiles;
-    const int j = (int)(item - b * tiles) * kOpsWG + (int)threadIdx.x;
+    int tile;
+    long g, c;
+    pvoc_item(item, tiles, Fout, tile, g, c);
+    const int j = tile * kOpsWG + (int)threadIdx.x;
     if (j > M) continue;
-    const long c = b / Fout, g = b - c * Fout;
+    const long b = c * Fout + g;
     const float p = fminf(fmaxf(pos[g], 0.f), (float)(Fin - 1));   // fmaxf(NaN, 0) = 0
     const long i = (long)floorf(p);
     const float a = p - (float)i;
@@ -233,11 +240,6 @@ __global__ __launch_bounds__(LdsGeom<LOGN>::WG) void k_pvoc_formant(const cpx *_
   }
 }
 
-static int ops_grid(long items, long cap, int grid_max) {
-  if (grid_max > 0 && cap > grid_max) cap = grid_max;
-  return (int)(items < cap ? items : cap);
-}
-
 template <int LOGN>
 static hipError_t launch_pvoc_formant_n(const PvocOpsArgs &a, const DeviceInfo &di, hipStream_t s) {
   using G = LdsGeom<LOGN>;
@@ -251,7 +253,7 @@ static hipError_t launch_pvoc_formant_n(const PvocOpsArgs &a, const DeviceInfo &
     occ = nb;
   }
   const long nframes = (long)a.channels * a.F, groups = (nframes + G::FPW - 1) / G::FPW;
-  const int grid = ops_grid(groups, (long)di.num_cus * occ, a.grid_max);
+  const int grid = pvoc_grid(groups, (long)di.num_cus * occ, a.grid_max);
   hipLaunchKernelGGL((k_pvoc_formant<LOGN>), dim3(grid), dim3(G::WG), 0, s, a.in, a.out, a.par, a.F, nframes, a.op,
                      a.lowest, a.coefs, a.gain, a.cf, a.bpf, a.half, a.w2);
   return hipGetLastError();
@@ -271,7 +273,7 @@ hipError_t launch_pvoc_ops(const PvocOpsArgs &a, const DeviceInfo &di, hipStream
   }
   const int tiles = (a.M + 1 + kOpsWG - 1) / kOpsWG;
   const long items = (long)a.channels * a.F * tiles;
-  const int grid = ops_grid(items, (long)di.num_cus * 16, a.grid_max);
+  const int grid = pvoc_grid(items, (long)di.num_cus * 16, a.grid_max);
   if (a.op == PVOC_READ)
     hipLaunchKernelGGL(k_pvoc_read, dim3(grid), dim3(kOpsWG), 0, s, a.in, a.out, a.par, a.Fin, a.F, a.M, tiles, items);
   else

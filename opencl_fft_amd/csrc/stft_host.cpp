@@ -36,9 +36,7 @@ static int stft_setup(clfa_stft *p, int device, int size, int hop, const float *
   }
   const int m = size / 2;
   p->logn = ilog2(m);
-  if (const char *env = getenv("CLFA_STFT_GRID_MAX")) {
-    if (atol(env) > 0 && atol(env) < 0x7fffffffL) p->grid_max = (int)atol(env);
-  }
+  p->grid_max = (int)env_long("CLFA_STFT_GRID_MAX", 0, 0x7fffffffL);
   int e = device_info(device, p->di);
   if (e) return e;
   ENTER_DEVICE(device);

@@ -169,6 +169,26 @@ def test_split_invariance(size, hop, channels, monkeypatch):
     assert small.workspace_bytes() == 4 * channels * (size // 2 + 1) < pv.workspace_bytes()
 
 
+def test_scan_with_several_chunks_per_segment(monkeypatch):
+    """34 chunks (33 whole ones and one of 5 frames) in one call: k_pvoc_scan's waves take 3 chunks each, the last occupied
+    segment is short and the segments after it are empty.  The phase state is the model's serial sum; the spectra and the
+    states are the bits of the same frames cut into two calls and of sub-batches of 5 chunks (other segment lengths)"""
+    size, hop, channels = 64, 16, 2
+    pv = make(size, hop, channels)
+    ch = pv.scan_chunk()
+    F = 33 * ch + 5
+    spec = stft_spectra(size, hop, channels, F, 61) + 0.05 * random_spectra(size, channels, F, 62)
+    whole = run_cut(pv, spec, [])
+    _, new_theta = pm.phases(whole[0].cpu().numpy()[..., 1], pm.initial_phase(channels, size), hop, SR)
+    assert np.array_equal(whole[3], new_theta), "phase state after one call of 34 chunks"
+    assert same(whole, run_cut(pv, spec, [ch * 17 + 1])), "cut at 17 chunks + 1"
+    monkeypatch.setenv("CLFA_PVOC_CHUNKS_MAX", "5")
+    small = make(size, hop, channels)
+    monkeypatch.delenv("CLFA_PVOC_CHUNKS_MAX")
+    assert same(whole, run_cut(small, spec, [])), "sub-batches of 5 chunks"
+    assert small.workspace_bytes() == 5 * 4 * channels * (size // 2 + 1) < pv.workspace_bytes()
+
+
 @pytest.mark.parametrize("size,hop,channels", [(64, 16, 3), (1024, 256, 1)])
 def test_side_stream_and_graph_replay(size, hop, channels):
     pv = make(size, hop, channels)

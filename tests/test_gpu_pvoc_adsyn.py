@@ -183,6 +183,32 @@ def test_sub_batches_of_one_chunk(monkeypatch):
     assert 0 < small.adsyn_workspace_bytes() < pv.adsyn_workspace_bytes()
 
 
+def test_scan_with_several_chunks_per_segment(monkeypatch):
+    """34 chunks (33 whole ones and one of 5 frames) in one call: k_adsyn_scan's waves take 3 chunks each, the last occupied
+    segment is short and the segments after it are empty.  The state is the integer model's; samples and state are the bits
+    of the same frames cut into two calls and of sub-batches of 5 chunks (other segment lengths)"""
+    size, hop, C, sel = 64, 3, 2, (1, None, 2)
+    pv = make(size, hop, C)
+    ch = pv.scan_chunk()
+    F = 33 * ch + 5
+    fr = random_frames(size, C, F, 81)
+    fm = np.random.default_rng(82).uniform(0.5, 2, F).astype(f32)
+    fr_t, fmod = torch.from_numpy(fr).to(DEV), torch.from_numpy(fm).to(DEV)
+    want = run(pv, fr_t, fmod=fmod, sel=sel)
+    torch.cuda.synchronize()
+    _, state = am.segments(fr, am.initial_state(C, size), hop, SR, fm, am.selection(size // 2, *sel))
+    assert state_equal(pv.adsyn_state(), state), "state after one call of 34 chunks"
+    cut = ch * 17 + 1
+    assert pv.reset() == 0
+    parts = [run(pv, fr_t[:, a:b].contiguous(), fmod=fmod[a:b].contiguous(), sel=sel) for a, b in ((0, cut), (cut, F))]
+    assert torch.equal(torch.cat(parts, dim=1), want) and state_equal(pv.adsyn_state(), state), "cut at 17 chunks + 1"
+    monkeypatch.setenv("CLFA_PVOC_CHUNKS_MAX", "5")
+    small = make(size, hop, C)
+    monkeypatch.delenv("CLFA_PVOC_CHUNKS_MAX")
+    assert torch.equal(run(small, fr_t, fmod=fmod, sel=sel), want) and state_equal(small.adsyn_state(), state), "sub-batches of 5 chunks"
+    assert 0 < small.adsyn_workspace_bytes() < pv.adsyn_workspace_bytes()
+
+
 # ---- exact per-sample probes ------------------------------------------------------------------------------------------
 
 PSR = 32768.0

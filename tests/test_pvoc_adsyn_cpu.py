@@ -29,6 +29,14 @@ void t_endpoint(float amp, float freq, float fmod, int has, float ks, int *w, fl
 int t_start(float a0, int w0, int wf) { return adsyn_start(a0, w0, wf); }
 unsigned long long t_slope(int w0, int wf, int hop) { return adsyn_slope(w0, wf, hop); }
 unsigned long long t_advance(int w0, unsigned long long d, int hop) { return adsyn_advance(w0, d, hop); }
+// one frame step: (*w, *a) moves on to the frame's endpoint
+unsigned long long t_step(int *w, float *a, float amp, float freq, float fmod, int has, float ks, int hop, int *ws,
+                          unsigned long long *d) {
+  int32_t w1 = *w, s; uint64_t dd;
+  const uint64_t adv = adsyn_step(w1, *a, amp, freq, fmod, has != 0, ks, hop, s, dd);
+  *w = w1; *ws = s; *d = dd;
+  return adv;
+}
 // phase(j) and the hot loop's top word, j = 1..hop
 void t_phases(unsigned long long p, int w0, unsigned long long d, int hop, unsigned long long *out, unsigned *hi) {
   for (int j = 1; j <= hop; j++) {
@@ -59,6 +67,8 @@ def plan(tmp_path_factory):
     L.t_slope.restype, L.t_slope.argtypes = u64, [i32, i32, i32]
     L.t_advance.restype, L.t_advance.argtypes = u64, [i32, u64, i32]
     L.t_phases.restype, L.t_phases.argtypes = None, [u64, i32, u64, i32, ctypes.c_void_p, ctypes.c_void_p]
+    L.t_step.restype = u64
+    L.t_step.argtypes = [ctypes.POINTER(i32), ctypes.POINTER(fl), fl, fl, fl, i32, fl, i32, ctypes.POINTER(i32), ctypes.POINTER(u64)]
     return L
 
 
@@ -121,6 +131,58 @@ def test_header_slope_phase_and_advance_against_python_integers(plan):
             assert hi.tolist() == [v >> 32 for v in want], (hop, w0, wf)
             assert want[-1] == (p + am.advance(w0, d, hop)) & am.MASK64
     assert negative_inexact > 1000      # the floor towards minus infinity was exercised
+
+
+def _same_float(a, b):
+    return np.array_equal(f32(a).view(np.uint32), f32(b).view(np.uint32)) or (np.isnan(a) and np.isnan(b))
+
+
+def test_header_step_is_the_composition_of_its_parts(plan):
+    """adsyn_step, which k_adsyn_sums calls, against endpoint, start rule, slope and advance called one by one: over the
+    frequencies and multipliers of the endpoint test (silent endpoints among them), the words of the slope test as the
+    endpoint before and previous amps that do and do not restart the oscillator (0, -0, a denormal, 1, NaN), each with a
+    frame amp of 3, 0, -0 or NaN and a hop of 1 .. 16384 drawn independently (the whole product: tests/cpp/adsyn_step_check.cpp)"""
+    ks = f32(1.0 / 48000.0)
+    rng = np.random.default_rng(6)
+    freqs = np.concatenate([[0.0, -0.0, 1e-30, 23999.9, 24000.0, -24000.0, 23999.998, -23999.998, 1e9, np.inf, -np.inf, np.nan],
+                            rng.uniform(-30000, 30000, 12)]).astype(f32)
+    words = _words(rng, 2)
+    amps = [f32(3.0), f32(0.0), f32(-0.0), f32(np.nan)]
+    hops = [1, 2, 3, 7, 16, 63, 64, 255, 256, 16384]
+    i32, fl, u64 = ctypes.c_int, ctypes.c_float, ctypes.c_ulonglong
+    wf, af, w, a, ws, d = i32(), fl(), i32(), fl(), i32(), u64()
+    silent = restarted = negative_inexact = 0
+    for fr in freqs:
+        for fm in (None, f32(0.5), f32(2.0), f32(np.nan)):
+            has, fmv = int(fm is not None), 1.0 if fm is None else fm
+            for w0 in words:
+                for a0 in (0.0, -0.0, 1e-45, 1.0, np.nan):
+                    amp, hop = amps[rng.integers(len(amps))], hops[rng.integers(len(hops))]
+                    plan.t_endpoint(amp, fr, fmv, has, ks, ctypes.byref(wf), ctypes.byref(af))
+                    ws_want = plan.t_start(a0, w0, wf.value)
+                    d_want = plan.t_slope(ws_want, wf.value, hop)
+                    w.value, a.value = w0, a0
+                    adv = plan.t_step(ctypes.byref(w), ctypes.byref(a), amp, fr, fmv, has, ks, hop, ctypes.byref(ws), ctypes.byref(d))
+                    what = (fr, fm, w0, a0, amp, hop)
+                    assert (w.value, ws.value, d.value) == (wf.value, ws_want, d_want), what
+                    assert _same_float(a.value, af.value), what
+                    assert adv == plan.t_advance(ws_want, d_want, hop) == am.advance(ws_want, d_want, hop), what
+                    silent += not am.word(f32(plan.t_turns(fr, fmv, has, ks)))[1]
+                    restarted += ws_want != w0
+                    negative_inexact += wf.value < ws_want and ((wf.value - ws_want) << 30) % hop != 0
+    assert silent > 100 and restarted > 100 and negative_inexact > 100, (silent, restarted, negative_inexact)
+
+
+def test_step_under_address_and_undefined_behaviour_sanitizers(tmp_path):
+    """tests/cpp/adsyn_step_check.cpp, a program of its own: adsyn_step against the composition over the full grid (every
+    hop), built with -fsanitize=address,undefined; any report ends it with a non-zero status"""
+    exe = str(tmp_path / "adsyn_step_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-static-libasan", "-static-libubsan",     # (the runtimes inside the program: nothing to preload)
+                           "-I", os.path.join(ROOT, "opencl_fft_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "cpp", "adsyn_step_check.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0 and "adsyn_step ok" in r.stdout, (r.returncode, r.stdout[-500:], r.stderr[-2000:])
 
 
 def _random_frames(rng, C, F, size, sr):
