@@ -10,38 +10,13 @@
 
 using namespace clfa;
 
-namespace {
-
-// host tables of the resident n = 65536 kernel (internal.hpp, kRes16TabSize), each value rounded from
-// double like the reference's table (cl_fft.cpp:89-90)
-void fill_res16_tables(std::vector<cpx> &all) {
-  all.clear();
-  std::vector<cpx> part;
-  for (int t = 0; t < 16; t++)
-    for (int j = 0; j < 16; j++) all.push_back(mk((float)cos((t * j) * 2 * kPI / 256), -(float)sin((t * j) * 2 * kPI / 256)));
-  fill_twiddle(part, 256, 65536, 1, -1.f);
-  all.insert(all.end(), part.begin(), part.begin() + 256);
-  fill_twiddle(part, 256, 256, 1, -1.f);
-  all.insert(all.end(), part.begin(), part.begin() + 256);
-  for (int m = 1; m <= 8; m *= 2)
-    for (int k = 0; k < 256; k++) {
-      const int idx = (m * k) & 4095;
-      all.push_back(mk((float)cos(idx * 2 * kPI / 4096), -(float)sin(idx * 2 * kPI / 4096)));
-    }
-}
-
-}  // namespace
-
 // ---------------------------------------------------------------------------------
 // plan objects
 // ---------------------------------------------------------------------------------
 
 struct clfa_fft {
   DeviceInfo di;
-  bool real = false;     // Clrfft
-  bool fwd = true;
-  int n = 0;             // complex length (Clrfft: M = size/2, cl_fft.cpp:210)
-  int logn = 0;
+  FftShape sh;           // what fft_route() decides by (fft_route.hpp); sh.n = complex length (Clrfft: M = size/2, cl_fft.cpp:210)
   int size = 0;          // user-visible size (n, or real points for Clrfft)
   int err = 0;           // Clcfft::cl_err
   char log[2048];
@@ -62,14 +37,7 @@ struct clfa_fft {
   // n > 65536 (extension): n = N1 x N2; `tabs` then belongs to the N2-point row transform
   BigGeom big{};
   DevBuf bigtabs, scratch2;
-  bool rlds15 = false;   // packed real size 65536: k_rfft_2x<14> (two 16384-point runs per transform, one HBM pass)
-  bool c2x13 = false;    // complex n = 16384: k_cfft_2x<13> (two 8192-point runs per transform, two workgroups per CU)
-  bool r2x13 = false;    // packed real size 32768: k_rfft_2x<13> (the same, with the pair maps in registers)
-  bool r16 = false;      // packed real size 131072: k_fft_res16 with the pair map inside (one HBM pass), either direction
-  DevBuf half2;          // ... the tables of the last two: the n = 8192 lane tables + W_16384^t, t < 512
-  long spread_below = 0; // real sizes 32768 / 65536: batches up to this run the four-step pair + pack kernel instead
-  // any other length (extension): Bluestein around two power-of-two plans of length blue_m
-  int blue_m = 0;
+  // any other length (extension): Bluestein around two power-of-two plans of length sh.blue_m
   clfa_fft *blue_f = nullptr, *blue_i = nullptr;
   DevBuf blue_w, blue_b, blue_work;
 };
@@ -201,19 +169,9 @@ static void host_fft(std::vector<double> &re, std::vector<double> &im) {
 
 // any length that is not a power of two (extension): chirp w[j] = exp(-+ i pi j^2 / n) (j^2 reduced mod 2 n
 // in integers, then double), filter B = DFT_m(conj(w) wrapped round m) in double, two m-point sub-plans
-static int blue_setup(clfa_fft *p, int device, int n, bool real, bool fwd) {
-  if (real && (n & 1)) {
-    snprintf(p->log, sizeof(p->log), "real sizes that are not powers of two must be multiples of 4 (got %d)", 2 * n);
-    return CLFA_INVALID_VALUE;
-  }
-  int e = device_info(device, p->di);
-  if (e) return e;
-  ENTER_DEVICE(device);
-  HIP_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-  p->logn = -1;
-  int m = 1;
-  while (m < 2 * n - 1) m <<= 1;
-  p->blue_m = m;
+static int blue_setup(clfa_fft *p, int n, bool fwd) {
+  const int device = p->di.device, m = p->sh.blue_m;
+  int e;
   const double sgn = fwd ? -1.0 : 1.0;
   std::vector<cpx> w(n), bt(m);
   std::vector<double> br(m, 0.0), bi(m, 0.0);
@@ -234,20 +192,17 @@ static int blue_setup(clfa_fft *p, int device, int n, bool real, bool fwd) {
   if ((e = upload(p->blue_b, bt.data(), sizeof(cpx) * m))) return e;
   if ((e = clfa_cfft_create(&p->blue_f, device, m, 1))) return e;
   if ((e = clfa_cfft_create(&p->blue_i, device, m, 0))) return e;
-  // workspace: as many m-point rows as fit 256 MiB (at least one); exec walks the batch in such chunks
-  const size_t per = sizeof(cpx) * (size_t)m, cap = (size_t)256 << 20;
-  if (!blue_lds_ok(m) && (e = p->blue_work.ensure(per * (cap / per > 0 ? cap / per : 1)))) return e;   // (m <= 8192: one launch, no workspace)
-  if (real) {
-    if ((e = upload_w2(p->w2, n, fwd ? -1.f : 1.f))) return e;
-    p->tabs.w2 = (const cpx *)p->w2.p;
-  }
+  // workspace: as many m-point rows as fit 256 MiB; exec walks the batch in such chunks (k_blue_lds: one launch, none)
+  if (fft_route_many(p->sh) == FftRoute::Bluestein) return p->blue_work.ensure(sizeof(cpx) * (size_t)m * chunk_items(sizeof(cpx) * (size_t)m, (size_t)256 << 20));
   return CLFA_SUCCESS;
 }
 
+// Whatever the routes the shape can ever take need (fft_needs): a plan carries the tables of all of them and exec picks by
+// batch.  n > 65536: the big-N tables and chunk workspace here, the rest for the row transform, its workspace in scratch2.
 static int fft_setup(clfa_fft *p, int device, int n, bool real, int size, bool fwd) {
-  p->real = real;
-  p->fwd = fwd;
-  p->n = n;
+  p->sh.real = real;
+  p->sh.fwd = fwd;
+  p->sh.n = n;
   p->size = size;
   p->log[0] = 0;
   if (n < 2 || (is_pow2(n) && n > (1 << kBigMaxLog)) || (!is_pow2(n) && n > kBlueMaxN)) {
@@ -255,100 +210,50 @@ static int fft_setup(clfa_fft *p, int device, int n, bool real, int size, bool f
              1 << kBigMaxLog, kBlueMaxN, n);
     return CLFA_INVALID_VALUE;
   }
-  if (!is_pow2(n)) return blue_setup(p, device, n, real, fwd);
-  p->logn = ilog2(n);
+  if (!is_pow2(n) && real && (n & 1)) {
+    snprintf(p->log, sizeof(p->log), "real sizes that are not powers of two must be multiples of 4 (got %d)", 2 * n);
+    return CLFA_INVALID_VALUE;
+  }
   int e = device_info(device, p->di);
   if (e) return e;
+  p->sh = fft_shape(real, fwd, n, p->di.num_cus);
   ENTER_DEVICE(device);
   HIP_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-  std::vector<cpx> h;
-  int rown = n, rowlog = p->logn;   // the transform the LDS / four-step tables are for
-  if (p->logn > kMaxLog) {
-    big_split(p->logn, &p->big);
-    rowlog = p->big.logn2;
-    rown = 1 << rowlog;
-    const int n1 = 1 << p->big.logn1;
-    std::vector<cpx> all, part;
-    fill_twiddle(part, n1 / 2, n1, 1, -1.f);
-    all.insert(all.end(), part.begin(), part.begin() + n1 / 2);
-    fill_twiddle(part, 128, n, 1, -1.f);              // W_n^e, e = e0 + 128 e1 + 16384 e2 (big_tw(), fft_big.inc)
-    all.insert(all.end(), part.begin(), part.begin() + 128);
-    fill_twiddle(part, 128, n, 128, -1.f);
-    all.insert(all.end(), part.begin(), part.begin() + 128);
-    fill_twiddle(part, n / 16384, n, 16384, -1.f);
-    all.insert(all.end(), part.begin(), part.begin() + n / 16384);
-    if ((e = upload(p->bigtabs, all.data(), sizeof(cpx) * all.size()))) return e;
-    // workspace: as many whole transforms as fit 256 MiB (at least one); exec walks the batch in such chunks
-    size_t per = sizeof(cpx) * (size_t)n, cap = (size_t)256 << 20;
-    if (const char *mb = getenv("CLFA_BIG_CHUNK_MB")) cap = (size_t)(atoi(mb) > 0 ? atoi(mb) : 256) << 20;   // tuning switch, read once
-    if ((e = p->scratch.ensure(per * (cap / per > 0 ? cap / per : 1)))) return e;
-  }
-  p->rlds15 = real && p->logn == 15;
-  p->r2x13 = real && p->logn == 14;
-  p->c2x13 = !real && p->logn == 14;
-  p->r16 = real && p->logn == 16;
-  // The fused real kernels put one workgroup on a transform (13-23 us for a single one); a few transforms are
-  // faster spread over the column / row blocks of the four-step pair plus the pack kernel (11 us): real plans of
-  // these two sizes carry both sets of tables and exec picks by batch (p->spread_below).
-  const bool lane14 = p->rlds15;     // k_rfft_2x<14> runs on the 16384-point lane tables
-  const bool both = p->rlds15 || p->r2x13;
-  const int fourlog = rowlog;
-  if (lane14) rowlog = kLds14Log;
-  if (both) p->spread_below = p->di.num_cus / 8;   // measured crossover: between 32 and 64 transforms
-  if (rowlog <= kLdsMaxLog || lane14) {
-    if (kLdsTwoLevel(rowlog)) {
-      // n = 8192 / 16384: lane-addressed tables (internal.hpp, kLane13Size / kLane14Size), every value rounded from double
-      h.clear();
-      auto w = [&](long k, long n) { h.push_back(mk((float)cos(k * 2 * kPI / n), -(float)sin(k * 2 * kPI / n))); };
-      for (int j = 0; j < 16; j++)
-        for (int t = 0; t < 16; t++) w(j * t, 256);
-      for (int k = 0; k < 4; k++)
-        for (int j = 0; j < 256; j++) w(((1 << k) * j) & 4095, 4096);
-      if (rowlog == kLds14Log) {
-        for (int m = 1; m <= 3; m++)
-          for (int t = 0; t < 1024; t++) w(m * t, 16384);
-      } else {
-        for (int t = 0; t < 512; t++) w(t, 8192);
-      }
-    } else {
-      fill_twiddle(h, rown / 2, rown, 1, -1.f);
-    }
-    if ((e = upload(p->half, h.data(), sizeof(cpx) * h.size()))) return e;
-    p->tabs.half = (const cpx *)p->half.p;
-  }
-  if (!(rowlog <= kLdsMaxLog || lane14) || both) {
-    rowlog = fourlog;
-    rown = 1 << rowlog;
-    std::vector<cpx> all;
-    fill_fourstep_tables(all, rowlog);
-    if ((e = upload(p->four, all.data(), sizeof(cpx) * all.size()))) return e;
-    p->tabs.four = (const cpx *)p->four.p;
-    if (rowlog == 16) {
-      fill_res16_tables(all);
-      if ((e = upload(p->res16, all.data(), sizeof(cpx) * all.size()))) return e;
-      p->tabs.res16 = (const cpx *)p->res16.p;
-    }
-    size_t sbytes = (size_t)fourstep_grid(p->di) * rown * sizeof(cpx);
-    DevBuf &ws = p->logn > kMaxLog ? p->scratch2 : p->scratch;
-    if ((e = ws.ensure(sbytes))) return e;
-  }
   if (real) {
     if ((e = upload_w2(p->w2, n, fwd ? -1.f : 1.f))) return e;
     p->tabs.w2 = (const cpx *)p->w2.p;
   }
-  if (p->c2x13 || p->r2x13) {
-    // the n = 8192 lane tables (as above) + the radix-2 step's lane constants W_16384^t
-    h.clear();
-    auto w = [&](long k, long nn) { h.push_back(mk((float)cos(k * 2 * kPI / nn), -(float)sin(k * 2 * kPI / nn))); };
-    for (int j = 0; j < 16; j++)
-      for (int t = 0; t < 16; t++) w(j * t, 256);
-    for (int k = 0; k < 4; k++)
-      for (int j = 0; j < 256; j++) w(((1 << k) * j) & 4095, 4096);
-    for (int t = 0; t < 512; t++) w(t, 8192);
-    for (int t = 0; t < 512; t++) w(t, 16384);
-    if ((e = upload(p->half2, h.data(), sizeof(cpx) * h.size()))) return e;
+  if (p->sh.blue_m) return blue_setup(p, n, fwd);
+  std::vector<cpx> h;
+  FftShape rows = p->sh;   // the transform the LDS / four-step tables are for
+  if (fft_needs(p->sh) & kNeedBig) {
+    big_split(p->sh.logn, &p->big);
+    rows = fft_shape(false, fwd, 1 << p->big.logn2, p->sh.num_cus);
+    fill_big_tables(h, n, 1 << p->big.logn1);
+    if ((e = upload(p->bigtabs, h.data(), sizeof(cpx) * h.size()))) return e;
+    // workspace: as many whole transforms as fit 256 MiB (at least one); exec walks the batch in such chunks
+    const long mb = env_long("CLFA_BIG_CHUNK_MB", 0, 1L << 31);   // tuning switch, read once
+    const size_t per = sizeof(cpx) * (size_t)n;
+    if ((e = p->scratch.ensure(per * chunk_items(per, (size_t)(mb ? mb : 256) << 20)))) return e;
   }
-  return CLFA_SUCCESS;
+  const unsigned needs = fft_needs(rows);
+  auto put = [&](DevBuf &b, const cpx *&tab) {
+    const int err = upload(b, h.data(), sizeof(cpx) * h.size());
+    tab = (const cpx *)b.p;
+    return err;
+  };
+  if (needs & (kNeedHalf | kNeedHalf2x)) {
+    if (needs & kNeedHalf2x) fill_lane_tables(h, rows.logn - 1, rows.logn == 14);
+    else if (kLdsTwoLevel(rows.logn)) fill_lane_tables(h, rows.logn, false);
+    else fill_twiddle(h, rows.n / 2, rows.n, 1, -1.f);
+    if ((e = put(p->half, p->tabs.half))) return e;
+  }
+  if (needs & kNeedFour) fill_fourstep_tables(h, rows.logn);
+  if ((needs & kNeedFour) && (e = put(p->four, p->tabs.four))) return e;
+  if (needs & kNeedRes16) fill_res16_tables(h);
+  if ((needs & kNeedRes16) && (e = put(p->res16, p->tabs.res16))) return e;
+  DevBuf &ws = rows.logn == p->sh.logn ? p->scratch : p->scratch2;
+  return needs & kNeedFourWs ? ws.ensure((size_t)fourstep_grid(p->di) * rows.n * sizeof(cpx)) : CLFA_SUCCESS;
 }
 
 int clfa_cfft_create(clfa_fft **plan, int device, int n, int forward) {
@@ -383,95 +288,72 @@ size_t clfa_fft_workspace_bytes(const clfa_fft *p) {
   return p->scratch.bytes + p->scratch2.bytes + p->blue_work.bytes + sub;
 }
 
-const char *clfa_fft_kernel_name(const clfa_fft *p) {
-  if (!p) return "";
-  if (p->logn > kMaxLog) return p->big.logn2 <= 11 ? "k_big2_cols" : "k_big_cols";   // two passes (to 2^22) / three
-  if (p->blue_m) return blue_lds_ok(p->blue_m) ? "k_blue_lds" : "bluestein";
-  if (p->rlds15 || p->r2x13) return "k_rfft_2x";
-  if (p->c2x13) return "k_cfft_2x";
-  return p->logn <= kLdsMaxLog ? name_fft_lds(p->logn, p->fwd, !p->real ? MODE_C2C : (p->fwd ? MODE_R2C : MODE_C2R)) : name_fft_4step(p->logn);
+// the kernel of a batch above every threshold
+const char *clfa_fft_kernel_name(const clfa_fft *p) { return p ? route_kernel_name(fft_route_many(p->sh), p->sh) : ""; }
+
+static int fft_exec(clfa_fft *p, cpx *d, long off, long batch, hipStream_t s);
+
+// FftRoute::Bluestein: src -> dst, the batch in chunks of the workspace's rows
+static int blue_exec(clfa_fft *p, const cpx *src, cpx *dst, long batch, hipStream_t s) {
+  const int n = p->sh.n, m = p->sh.blue_m;
+  cpx *work = (cpx *)p->blue_work.p;
+  const cpx *w = (const cpx *)p->blue_w.p, *bt = (const cpx *)p->blue_b.p;
+  return for_chunks(batch, (long)(p->blue_work.bytes / (sizeof(cpx) * (size_t)m)), [&](long b0, long nb) -> int {
+    HIP_TRY(launch_blue_pre(src + b0 * (long)n, w, work, n, m, nb, s));
+    int e = fft_exec(p->blue_f, work, 0, nb, s);
+    if (e) return e;
+    HIP_TRY(launch_blue_mul(work, bt, m, nb, s));
+    if ((e = fft_exec(p->blue_i, work, 0, nb, s))) return e;
+    HIP_TRY(launch_blue_post(work, w, dst + b0 * (long)n, n, m, p->sh.fwd ? 1.0f / (float)n : 1.0f, nb, s));
+    return CLFA_SUCCESS;
+  });
 }
 
 // The body of every device-resident transform: `d` is read, the results go to d + off complex elements (off = 0: in
 // place; otherwise a destination that does not overlap the source, which is then left untouched).  Two-pass routes run
 // their FIRST pass from the source to the destination and the rest in place there.
 static int fft_exec(clfa_fft *p, cpx *d, long off, long batch, hipStream_t s) {
-  const bool scale = p->fwd;  // cl_fft.cpp:39-40: forward plans divide by N, inverse plans do not
-  cpx *o = d + off;
-  if (p->blue_m) {
-    const int n = p->n, m = p->blue_m;
-    cpx *work = (cpx *)p->blue_work.p;
-    const cpx *w = (const cpx *)p->blue_w.p, *bt = (const cpx *)p->blue_b.p;
-    cpx *src = d;
-    if (p->real && !p->fwd) {
-      HIP_TRY(launch_c2r_unpack(d, p->tabs.w2, n, batch, s, off));   // -> the destination
-      src = o;
-    }
-    if (blue_lds_ok(m)) {   // one launch, one read and one write of the data (fft_aux.inc, k_blue_lds)
-      HIP_TRY(launch_blue_lds(m, src, o, w, bt, p->blue_f->tabs.half, n, (scale ? 1.0f / (float)n : 1.0f) / (float)m, batch, p->di, s));
-      if (p->real && p->fwd) HIP_TRY(launch_r2c_pack(o, p->tabs.w2, n, batch, s));
-      return CLFA_SUCCESS;
-    }
-    const long cb = (long)(p->blue_work.bytes / (sizeof(cpx) * (size_t)m));
-    for (long b0 = 0; b0 < batch; b0 += cb) {
-      const long nb = batch - b0 < cb ? batch - b0 : cb;
-      HIP_TRY(launch_blue_pre(src + b0 * (long)n, w, work, n, m, nb, s));
-      int e = fft_exec(p->blue_f, work, 0, nb, s);
+  const FftShape &sh = p->sh;
+  const bool fwd = sh.fwd, scale = sh.fwd;  // cl_fft.cpp:39-40: forward plans divide by N, inverse plans do not
+  const FftRoute route = fft_route(sh, batch);
+  // real plans on a route of the complex transform: the reference's pack / unpack as a pass of its own; the unpack lands
+  // in the destination, where the transform then runs in place
+  const bool apart = sh.real && route_pack_apart(route);
+  cpx *o = d + off, *scratch = (cpx *)p->scratch.p;
+  if (apart && !fwd) {
+    HIP_TRY(launch_c2r_unpack(d, p->tabs.w2, sh.n, batch, s, off));
+    d = o;
+  }
+  switch (route) {
+    case FftRoute::Lds: HIP_TRY(launch_fft_lds(sh.logn, fwd, fft_mode(sh), scale, d, p->tabs, batch, p->di, s, off)); break;
+    case FftRoute::Cfft2x13: HIP_TRY(launch_cfft_2x13(fwd, scale, d, p->tabs, batch, p->di, s, off)); break;
+    case FftRoute::Rfft2x13: HIP_TRY(launch_rfft_2x13(fwd, d, p->tabs, batch, p->di, s, off)); break;
+    case FftRoute::Rfft2x14: HIP_TRY(launch_rfft_lds15(fwd, d, p->tabs, batch, p->di, s, off)); break;
+    case FftRoute::RealRes16:
+      if (fwd) HIP_TRY(launch_rfft_res16(d, o, scratch, p->tabs.res16, p->tabs.w2, batch, p->di, s));
+      else HIP_TRY(launch_crfft_res16(d, o, scratch, p->tabs.res16, p->tabs.w2, batch, p->di, s));
+      break;
+    case FftRoute::FourStepSpread:
+    case FftRoute::FourStep:
+    case FftRoute::Res16: HIP_TRY(launch_fft_4step(sh.logn, fwd, scale, d, scratch, p->tabs, batch, p->di, s, o - d)); break;
+    case FftRoute::Big: {
+      const int e = for_chunks(batch, (long)(p->scratch.bytes / (sizeof(cpx) * (size_t)sh.n)), [&](long b0, long nb) -> int {
+        HIP_TRY(launch_fft_big(p->big, fwd, scale, d + b0 * (long)sh.n, o + b0 * (long)sh.n, scratch, (cpx *)p->scratch2.p,
+                               (const cpx *)p->bigtabs.p, p->tabs, nb, p->di, s));
+        return CLFA_SUCCESS;
+      });
       if (e) return e;
-      HIP_TRY(launch_blue_mul(work, bt, m, nb, s));
-      if ((e = fft_exec(p->blue_i, work, 0, nb, s))) return e;
-      HIP_TRY(launch_blue_post(work, w, o + b0 * (long)n, n, m, scale ? 1.0f / (float)n : 1.0f, nb, s));
+      break;
     }
-    if (p->real && p->fwd) HIP_TRY(launch_r2c_pack(o, p->tabs.w2, n, batch, s));
-    return CLFA_SUCCESS;
+    case FftRoute::BlueLds:   // one launch, one read and one write of the data (fft_aux.inc, k_blue_lds)
+      HIP_TRY(launch_blue_lds(sh.blue_m, d, o, (const cpx *)p->blue_w.p, (const cpx *)p->blue_b.p, p->blue_f->tabs.half, sh.n,
+                              (scale ? 1.0f / (float)sh.n : 1.0f) / (float)sh.blue_m, batch, p->di, s));
+      break;
+    case FftRoute::Bluestein:
+      if (int e = blue_exec(p, d, o, batch, s)) return e;
+      break;
   }
-  const bool spread = p->real && batch <= p->spread_below;   // a few transforms: one workgroup each would be slower
-  if (p->rlds15 && !spread) {
-    HIP_TRY(launch_rfft_lds15(p->fwd, d, p->tabs, batch, p->di, s, off));
-    return CLFA_SUCCESS;
-  }
-  if (p->r2x13 && !spread) {
-    FftTables t2 = p->tabs;
-    t2.half = (const cpx *)p->half2.p;
-    HIP_TRY(launch_rfft_2x13(p->fwd, d, t2, batch, p->di, s, off));
-    return CLFA_SUCCESS;
-  }
-  if (p->c2x13 && batch * 4 > p->di.num_cus) {   // (fewer transforms: spread over the four-step column / row kernels)
-    FftTables t2 = p->tabs;
-    t2.half = (const cpx *)p->half2.p;
-    HIP_TRY(launch_cfft_2x13(p->fwd, scale, d, t2, batch, p->di, s, off));
-    return CLFA_SUCCESS;
-  }
-  if (p->logn <= kLdsMaxLog) {
-    int mode = !p->real ? MODE_C2C : (p->fwd ? MODE_R2C : MODE_C2R);
-    HIP_TRY(launch_fft_lds(p->logn, p->fwd, mode, scale, d, p->tabs, batch, p->di, s, off));
-    return CLFA_SUCCESS;
-  }
-  if (p->r16 && batch * 4 > fourstep_grid(p->di)) {   // (fewer transforms: spread over the column / row kernels + pack)
-    if (p->fwd) HIP_TRY(launch_rfft_res16(d, o, (cpx *)p->scratch.p, p->tabs.res16, p->tabs.w2, batch, p->di, s));
-    else HIP_TRY(launch_crfft_res16(d, o, (cpx *)p->scratch.p, p->tabs.res16, p->tabs.w2, batch, p->di, s));
-    return CLFA_SUCCESS;
-  }
-  // a complex transform, with the reference's pack / unpack as a pass of its own for the packed real sizes that have no
-  // fused kernel (and for a few transforms of those that have one)
-  cpx *src = d;
-  long toff = off;   // the transform's own offset: the inverse real route is at the destination already
-  if (p->real && !p->fwd) {
-    HIP_TRY(launch_c2r_unpack(d, p->tabs.w2, p->n, batch, s, off));
-    src = o;
-    toff = 0;
-  }
-  if (p->logn > kMaxLog) {
-    const long cb = (long)(p->scratch.bytes / (sizeof(cpx) * (size_t)p->n));
-    for (long b0 = 0; b0 < batch; b0 += cb) {
-      const long nb = batch - b0 < cb ? batch - b0 : cb;
-      HIP_TRY(launch_fft_big(p->big, p->fwd, scale, src + b0 * (long)p->n, src + toff + b0 * (long)p->n, (cpx *)p->scratch.p,
-                             (cpx *)p->scratch2.p, (const cpx *)p->bigtabs.p, p->tabs, nb, p->di, s));
-    }
-  } else {
-    HIP_TRY(launch_fft_4step(p->logn, p->fwd, scale, src, (cpx *)p->scratch.p, p->tabs, batch, p->di, s, toff));
-  }
-  if (p->real && p->fwd) HIP_TRY(launch_r2c_pack(o, p->tabs.w2, p->n, batch, s));
+  if (apart && fwd) HIP_TRY(launch_r2c_pack(o, p->tabs.w2, sh.n, batch, s));
   return CLFA_SUCCESS;
 }
 
@@ -490,7 +372,7 @@ int clfa_fft_exec_dev_oop(clfa_fft *p, const void *src, void *dst, long batch, v
   if (!src || !dst || batch < 0) return CLFA_INVALID_VALUE;
   if (src == dst) return clfa_fft_exec_dev(p, dst, batch, stream);
   if (batch == 0) return CLFA_SUCCESS;
-  const size_t bytes = sizeof(cpx) * (size_t)p->n * (size_t)batch;   // real plans: n = size / 2 packed bins = size floats
+  const size_t bytes = sizeof(cpx) * (size_t)p->sh.n * (size_t)batch;   // real plans: n = size / 2 packed bins = size floats
   const char *a = (const char *)src, *b = (const char *)dst;
   if (spans_overlap(a, bytes, b, bytes)) return CLFA_INVALID_VALUE;  // partly overlapping
   if ((b - a) % (long)sizeof(cpx)) return CLFA_INVALID_VALUE;         // the two buffers a whole number of complex values apart
@@ -505,7 +387,7 @@ int clfa_fft_exec_dev_oop(clfa_fft *p, const void *src, void *dst, long batch, v
 int clfa_fft_device_buffers(clfa_fft *p, void **data1, void **data2, void **commands) {
   if (int e = obj_error(p)) return e;
   ENTER_DEVICE(p->di.device);
-  const size_t bytes = sizeof(cpx) * (size_t)p->n;
+  const size_t bytes = sizeof(cpx) * (size_t)p->sh.n;
   int e = p->own1.ensure(bytes);
   if (!e) e = p->own2.ensure(bytes);
   if (e) return e;
@@ -517,12 +399,12 @@ int clfa_fft_device_buffers(clfa_fft *p, void **data1, void **data2, void **comm
 
 int clfa_fft_device_tables(clfa_fft *p, void **w, void **b) {
   if (int e = obj_error(p)) return e;
-  if (p->blue_m || p->logn < 1 || p->logn > kMaxLog) return CLFA_INVALID_OPERATION;
+  if (p->sh.blue_m || p->sh.logn < 1 || p->sh.logn > kMaxLog) return CLFA_INVALID_OPERATION;
   ENTER_DEVICE(p->di.device);
-  const int n = p->n;
+  const int n = p->sh.n;
   if (!p->own_tables_ready) {
     std::vector<cpx> tw;
-    fill_twiddle(tw, n, n, 1, p->fwd ? -1.f : 1.f);                 // cl_fft.cpp:86-91
+    fill_twiddle(tw, n, n, 1, p->sh.fwd ? -1.f : 1.f);                 // cl_fft.cpp:86-91
     std::vector<int> br((size_t)n);
     int e = clfa_bitrev_table(n, br.data());                        // cl_fft.cpp:96-101
     if (!e) e = p->own_w.ensure(sizeof(cpx) * (size_t)n);
@@ -562,11 +444,11 @@ int clfa_stream_synchronize(void *stream) {
 int clfa_fft_run_buffers(clfa_fft *p) {
   if (int e = obj_error(p)) return e;
   if (!p->own1.p || !p->own2.p) return CLFA_INVALID_MEM_OBJECT;
-  if (!p->real) return clfa_fft_exec_dev_oop(p, p->own1.p, p->own2.p, 1, p->stream);
+  if (!p->sh.real) return clfa_fft_exec_dev_oop(p, p->own1.p, p->own2.p, 1, p->stream);
   // a Clrfft's fft() is the complex transform of its N = size / 2 points and nothing else: the reference's conv / iconv
   // are kernels of their own, enqueued by Clrfft::transform (cl_fft.cpp:267-296), not by fft()
   if (!p->own_cplx) {
-    const int e = clfa_cfft_create(&p->own_cplx, p->di.device, p->n, p->fwd ? 1 : 0);
+    const int e = clfa_cfft_create(&p->own_cplx, p->di.device, p->sh.n, p->sh.fwd ? 1 : 0);
     if (e) {
       if (p->own_cplx) clfa_fft_destroy(p->own_cplx);
       p->own_cplx = nullptr;
@@ -583,15 +465,6 @@ int clfa_fft_run_buffers(clfa_fft *p) {
 #define CLFA_ZEROCOPY_MAX_KIB 512   // (profiles/host_path_r05.txt: one N = 65536 transform, 512 KiB: 59.5 us this way, 73.5 by copies)
 #endif
 constexpr size_t kZeroCopyMax = (size_t)CLFA_ZEROCOPY_MAX_KIB << 10;   // (the convolutions': conv_host.cpp)
-
-// host staging in chunks of at most ~256 MiB so huge host batches do not need a
-// device buffer of their full size
-static long chunk_batches(size_t bytes_per_batch, long batch) {
-  size_t cap = (size_t)256 << 20;
-  long c = (long)(cap / bytes_per_batch);
-  if (c < 1) c = 1;
-  return c < batch ? c : batch;
-}
 
 // ---- pinned arrays for the caller (extension) --------------------------------------------------------------------
 // The reference's transform() copies the caller's array to the device and back with two blocking transfers
@@ -639,92 +512,59 @@ static void *pinned_dev(const clfa_fft *p, const void *h, size_t bytes) {
     if ((const char *)h >= r.h && (const char *)h + bytes <= r.h + r.bytes) return r.d + ((const char *)h - r.h);
   return nullptr;
 }
-// Pinned arrays up to this size run zero-copy when the plan's route touches its source and its destination once each
-// (every route of the reference's range except the launch chains with a pack / unpack pass of their own); beyond it, and
-// on the other routes, they are copied by DMA like pageable arrays, only faster.
+// Pinned arrays up to this size run zero-copy when the batch's route touches its source and its destination once each
+// (route_one_touch, fft_route.hpp); beyond it, and on the other routes, they are copied by DMA like pageable arrays, only
+// faster.
 constexpr size_t kPinnedZeroCopyMax = (size_t)8 << 20;
-static bool one_touch_route(const clfa_fft *p, long batch) {
-  if (p->blue_m || p->logn > kMaxLog) return false;
-  if (!p->real) return true;
-  if (p->logn <= kLdsMaxLog) return true;
-  return batch > p->spread_below && (p->rlds15 || p->r2x13 || (p->r16 && batch * 4 > fourstep_grid(p->di)));
-}
 
-int clfa_cfft_transform(clfa_fft *p, float *c, long batch) {
-  if (int e = obj_error(p)) return e;
-  if (!c || batch < 0 || p->real) return CLFA_INVALID_VALUE;
+// The blocking host-pointer transforms: src -> dst, which are equal (Clcfft, in place) or the caller's two arrays (Clrfft).
+static int fft_host_transform(clfa_fft *p, char *src, char *dst, long batch) {
   ENTER_DEVICE(p->di.device);
-  const size_t per = sizeof(cpx) * (size_t)p->n;
-  if (batch > 0 && per * (size_t)batch <= kPinnedZeroCopyMax && one_touch_route(p, batch)) {
-    if (void *dv = pinned_dev(p, c, per * (size_t)batch)) {   // an array of clfa_fft_host_alloc: in place over PCIe
-      // (profiles/host_path_r05.txt: N = 65536 42.2 us; with the copy engine bringing the array in first 46.4)
-      const int e = clfa_fft_exec_dev(p, dv, batch, p->stream);
-      if (e) return e;
-      HIP_TRY(hipStreamSynchronize(p->stream));
-      return CLFA_SUCCESS;
-    }
-  }
-  if (batch > 0 && per * (size_t)batch <= kZeroCopyMax) {
-    int e = p->zstage.ensure(per * batch);
-    if (e) return e;
-    memcpy(p->zstage.h, c, per * batch);
-    if ((e = clfa_fft_exec_dev(p, p->zstage.d, batch, p->stream))) return e;
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    memcpy(c, p->zstage.h, per * batch);
-    return CLFA_SUCCESS;
-  }
-  const long cb = chunk_batches(per, batch);
-  for (long b0 = 0; b0 < batch; b0 += cb) {
-    long nb = batch - b0 < cb ? batch - b0 : cb;
-    int e = p->stage.ensure(per * nb);
-    if (e) return e;
-    char *h = (char *)c + per * b0;
-    HIP_TRY(hipMemcpyAsync(p->stage.p, h, per * nb, hipMemcpyHostToDevice, p->stream));   // cl_fft.cpp:155
-    if ((e = clfa_fft_exec_dev(p, p->stage.p, nb, p->stream))) return e;                   // cl_fft.cpp:157
-    HIP_TRY(hipMemcpyAsync(h, p->stage.p, per * nb, hipMemcpyDeviceToHost, p->stream));   // cl_fft.cpp:158
-    HIP_TRY(hipStreamSynchronize(p->stream));
-  }
-  return CLFA_SUCCESS;
-}
-
-int clfa_rfft_transform(clfa_fft *p, float *c, float *r, long batch) {
-  if (int e = obj_error(p)) return e;
-  if (!c || !r || batch < 0 || !p->real) return CLFA_INVALID_VALUE;
-  ENTER_DEVICE(p->di.device);
-  const size_t per = sizeof(cpx) * (size_t)p->n;  // size floats == M complex
-  if (batch > 0 && per * (size_t)batch <= kPinnedZeroCopyMax && one_touch_route(p, batch)) {
-    void *src = p->fwd ? (void *)r : (void *)c, *dst = p->fwd ? (void *)c : (void *)r;
-    void *ds = pinned_dev(p, src, per * (size_t)batch), *dd = src == dst ? ds : pinned_dev(p, dst, per * (size_t)batch);
-    if (ds && dd) {   // both arrays (or the one, in place) come from clfa_fft_host_alloc
+  const size_t per = sizeof(cpx) * (size_t)p->sh.n, bytes = per * (size_t)batch;   // real plans: size floats == M complex
+  if (batch > 0 && bytes <= kPinnedZeroCopyMax && route_one_touch(fft_route(p->sh, batch), p->sh.real)) {
+    // arrays of clfa_fft_host_alloc, both (or the one, in place): the kernels run on them over PCIe
+    // (profiles/host_path_r05.txt: N = 65536 42.2 us; with the copy engine bringing the array in first 46.4).  Two arrays
+    // that overlap, or lie no whole number of complex values apart, go the ways below like pageable ones.
+    char *ds = (char *)pinned_dev(p, src, bytes), *dd = src == dst ? ds : (char *)pinned_dev(p, dst, bytes);
+    if (ds && dd && (ds == dd || (!spans_overlap(ds, bytes, dd, bytes) && (dd - ds) % (long)sizeof(cpx) == 0))) {
       const int e = clfa_fft_exec_dev_oop(p, ds, dd, batch, p->stream);
       if (e) return e;
       HIP_TRY(hipStreamSynchronize(p->stream));
       return CLFA_SUCCESS;
     }
   }
-  if (batch > 0 && per * (size_t)batch <= kZeroCopyMax) {
-    int e = p->zstage.ensure(per * batch);
+  if (batch > 0 && bytes <= kZeroCopyMax) {
+    int e = p->zstage.ensure(bytes);
     if (e) return e;
-    memcpy(p->zstage.h, p->fwd ? (void *)r : (void *)c, per * batch);
+    memcpy(p->zstage.h, src, bytes);
     if ((e = clfa_fft_exec_dev(p, p->zstage.d, batch, p->stream))) return e;
     HIP_TRY(hipStreamSynchronize(p->stream));
-    memcpy(p->fwd ? (void *)c : (void *)r, p->zstage.h, per * batch);
+    memcpy(dst, p->zstage.h, bytes);
     return CLFA_SUCCESS;
   }
-  const long cb = chunk_batches(per, batch);
-  // forward reads r and writes c; inverse reads c and writes r (cl_fft.cpp:272-294)
-  char *src = (char *)(p->fwd ? (void *)r : (void *)c);
-  char *dst = (char *)(p->fwd ? (void *)c : (void *)r);
-  for (long b0 = 0; b0 < batch; b0 += cb) {
-    long nb = batch - b0 < cb ? batch - b0 : cb;
+  // staging in chunks of at most 256 MiB, so that huge host batches do not need a device buffer of their full size
+  return for_chunks(batch, chunk_items(per, (size_t)256 << 20), [&](long b0, long nb) -> int {
     int e = p->stage.ensure(per * nb);
     if (e) return e;
-    HIP_TRY(hipMemcpyAsync(p->stage.p, src + per * b0, per * nb, hipMemcpyHostToDevice, p->stream));
-    if ((e = clfa_fft_exec_dev(p, p->stage.p, nb, p->stream))) return e;
-    HIP_TRY(hipMemcpyAsync(dst + per * b0, p->stage.p, per * nb, hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipMemcpyAsync(p->stage.p, src + per * b0, per * nb, hipMemcpyHostToDevice, p->stream));   // cl_fft.cpp:155
+    if ((e = clfa_fft_exec_dev(p, p->stage.p, nb, p->stream))) return e;                               // cl_fft.cpp:157
+    HIP_TRY(hipMemcpyAsync(dst + per * b0, p->stage.p, per * nb, hipMemcpyDeviceToHost, p->stream));   // cl_fft.cpp:158
     HIP_TRY(hipStreamSynchronize(p->stream));
-  }
-  return CLFA_SUCCESS;
+    return CLFA_SUCCESS;
+  });
+}
+
+int clfa_cfft_transform(clfa_fft *p, float *c, long batch) {
+  if (int e = obj_error(p)) return e;
+  if (!c || batch < 0 || p->sh.real) return CLFA_INVALID_VALUE;
+  return fft_host_transform(p, (char *)c, (char *)c, batch);
+}
+
+// forward reads r and writes c; inverse reads c and writes r (cl_fft.cpp:272-294)
+int clfa_rfft_transform(clfa_fft *p, float *c, float *r, long batch) {
+  if (int e = obj_error(p)) return e;
+  if (!c || !r || batch < 0 || !p->sh.real) return CLFA_INVALID_VALUE;
+  return fft_host_transform(p, (char *)(p->sh.fwd ? r : c), (char *)(p->sh.fwd ? c : r), batch);
 }
 
 int clfa_reorder_dev(int device, void *out, const void *in, int n, long batch, void *stream) {

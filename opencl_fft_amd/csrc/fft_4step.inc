@@ -402,7 +402,7 @@ template <int LOGN, bool FWD, bool SCALE>
 static hipError_t launch_4step_v(cpx *data, cpx *scratch, const FftTables &t, long batch, const DeviceInfo &di,
                                  hipStream_t s, long out_off) {
   int grid = fourstep_grid(di);
-  if (batch * 4 <= grid && batch <= 65535) {
+  if (fourstep_spread(batch, grid)) {
     // few transforms: spread each over its column / row blocks (scratch holds `grid` transforms)
     using G = FourGeom<LOGN>;
     hipLaunchKernelGGL((k_fft_4step_cols<LOGN, FWD>), dim3(G::NCB, (unsigned)batch), dim3(256), 0, s, data, scratch, t.four);
@@ -439,7 +439,5 @@ hipError_t launch_fft_4step(int logn, bool fwd, bool scale, cpx *data, cpx *scra
     default: return hipErrorInvalidValue;
   }
 }
-
-const char *name_fft_4step(int logn) { return logn == 16 ? "k_fft_res16" : "k_fft_4step"; }
 
 }  // namespace clfa

@@ -171,7 +171,6 @@ static hipError_t launch_blue_lds_m(const cpx *x, cpx *y, const cpx *w, const cp
   hipLaunchKernelGGL((k_blue_lds<LOGM>), dim3(grid < 1 ? 1 : grid), dim3(G::WG), 0, s, x, y, w, bt, tab, n, scale, batch);
   return hipGetLastError();
 }
-bool blue_lds_ok(int m) { return m >= 256 && m <= 8192; }
 // x -> y (may be equal), batch transforms of n points; w = chirp (n), bt = its padded spectrum (m), tab = the m-point plan's
 // LDS table (FftTables::half); scale = the plan's output factor times 1 / m
 hipError_t launch_blue_lds(int m, const cpx *x, cpx *y, const cpx *w, const cpx *bt, const cpx *tab, int n, float scale,

@@ -19,8 +19,6 @@ namespace clfa {
 //      plans                                                                     (16 B/sample)
 // Twiddles W_n^e: big_tw() below.
 
-constexpr int kBig2MaxLog = 22;   // the largest two-pass size
-
 int big_split(int logn, BigGeom *g) {
   if (logn <= kMaxLog || logn > kBigMaxLog) return -1;
   g->logn = logn;

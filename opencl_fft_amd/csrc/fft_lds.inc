@@ -611,11 +611,9 @@ static hipError_t launch_lds_n(bool fwd, int mode, bool scale, cpx *data, const 
                                const DeviceInfo &di, hipStream_t s, long out_off) {
 #define CLFA_CASE(F, M, S)                                                                                     \
   if (fwd == F && mode == M && scale == S) {                                                                   \
-    if constexpr (LOGN <= 2 && M == MODE_C2C) return launch_tiny_one<LOGN, F, S>(data, batch, di, s, out_off); \
-    /* sub-64-byte rows per transform (and the packed real transforms up to 256 bins, whose pair maps  */     \
-    /* store 8-byte pieces): coalesced staging through LDS                                              */     \
-    if constexpr (LOGN >= 2 && (LOGN <= 6 || (M != MODE_C2C && LOGN <= 8)))                                     \
-      return launch_small_one<LOGN, F, M, S>(data, t, batch, di, s, out_off);                                  \
+    /* tiny, else small, else lds: the predicates the kernel's name is chosen by (fft_route.hpp) */           \
+    if constexpr (lds_tiny(LOGN, M)) return launch_tiny_one<LOGN, F, S>(data, batch, di, s, out_off);          \
+    if constexpr (lds_small(LOGN, M)) return launch_small_one<LOGN, F, M, S>(data, t, batch, di, s, out_off);  \
     else return launch_lds_one<LOGN, F, M, S>(data, t, batch, di, s, out_off);                                 \
   }
   CLFA_CASE(true, MODE_C2C, true)
@@ -640,12 +638,6 @@ hipError_t launch_fft_lds(int logn, bool fwd, int mode, bool scale, cpx *data, c
     default:
       return hipErrorInvalidValue;
   }
-}
-
-const char *name_fft_lds(int logn, bool, int mode) {
-  if (logn <= 2 && mode == MODE_C2C) return "k_fft_tiny";
-  if (logn >= 2 && (logn <= 6 || (mode != MODE_C2C && logn <= 8))) return "k_fft_small";
-  return "k_fft_lds";
 }
 
 }  // namespace clfa

@@ -3,14 +3,10 @@
 #include <hip/hip_runtime.h>
 
 #include "fft_device.hpp"
+#include "fft_route.hpp"   // FftMode, kLdsMaxLog, kMaxLog and which kernels a plan runs for a batch
 
 namespace clfa {
 
-enum FftMode { MODE_C2C = 0, MODE_R2C = 1, MODE_C2R = 2 };
-
-// Largest complex length the single-workgroup LDS kernel handles; above it the four-step kernel
-// (two phases, the intermediate in LDS + registers + a small global scratch) takes over.
-constexpr int kLdsMaxLog = 13;
 // n = 8192 uses lane-addressed twiddle tables instead of the half table (fft_device.hpp, LaneTab13):
 // [W_256^(j t), j, t < 16 | W_4096^(2^k j mod 4096), k < 4, j < 256 | W_8192^t, t < 512]; the first
 // kLane13Lds entries live in LDS
@@ -29,7 +25,6 @@ __host__ __device__ constexpr int lane_lds_index(int i) { return i < 256 ? (i >>
 // the 16384-point chains of k_rfft_2x<14> (packed real size 65536: 1024 lanes, passes 16 x 16 x 16 x 4, fft_device.hpp
 // LaneTab14): the same LDS part, then [W_16384^t | W_16384^(2 t) | W_16384^(3 t)], t < 1024
 constexpr int kLds14Log = 14, kLane14Size = kLane13Lds + 3 * 1024;
-constexpr int kMaxLog = 16;  // reference int32 index bound, cl_fft.cpp:32
 
 struct FftTables {      // all device pointers, owned by the plan
   const cpx *half = nullptr;   // W_n^k, k < n/2, forward sign (LDS path; n = complex length)
@@ -49,7 +44,6 @@ struct DeviceInfo {
 // that does not overlap the source (clfa_fft_exec_dev_oop); the source is only read
 hipError_t launch_fft_lds(int logn, bool fwd, int mode, bool scale, cpx *data, const FftTables &t,
                           long batch, const DeviceInfo &di, hipStream_t s, long out_off = 0);
-const char *name_fft_lds(int logn, bool fwd, int mode);
 // packed real size 65536 (n = 32768): two runs of the 16384-point machinery per transform, radix-2 step and pair
 // map in registers; t.half = the n = 16384 lane tables (kLane14Size), t.w2 = the plan's r2c table (n entries)
 hipError_t launch_rfft_lds15(bool fwd, cpx *data, const FftTables &t, long batch, const DeviceInfo &di, hipStream_t s,
@@ -63,13 +57,12 @@ hipError_t launch_rfft_2x13(bool fwd, cpx *data, const FftTables &t, long batch,
 hipError_t launch_cfft_2x13(bool fwd, bool scale, cpx *data, const FftTables &t, long batch, const DeviceInfo &di,
                             hipStream_t s, long out_off = 0);
 
-// four-step FFT, n = 2^logn in (2^kLdsMaxLog, 2^kMaxLog]; scratch = fourstep_grid() * n complex
-// (n = 65536 with more than a few transforms runs the resident kernel below and uses the first
-// kRes16SlotBytes * grid bytes of the scratch as its slots)
+// four-step FFT, n = 2^logn in (2^kLdsMaxLog, 2^kMaxLog]; scratch = fourstep_grid() * n complex.  Which of its kernels
+// a batch runs (the cols + rows pair, k_fft_4step, or for n = 65536 the resident kernel below, whose slots are the first
+// kRes16SlotBytes * grid bytes of the scratch) is fft_route.hpp's decision: fourstep_spread()
 int fourstep_grid(const DeviceInfo &di);
 hipError_t launch_fft_4step(int logn, bool fwd, bool scale, cpx *data, cpx *scratch, const FftTables &t, long batch,
                             const DeviceInfo &di, hipStream_t s, long out_off = 0);
-const char *name_fft_4step(int logn);
 int fourstep_split(int logn, int *logn1, int *logn2, int *loglo);
 // n = 65536, the whole intermediate resident on the CU (fft_resident.hip): one HBM pass, no scratch.
 // tabs: kRes16TabSize entries, forward sign: [W_256^(t j), t, j < 16 | W_n^k, k < 256 | W_256^k, k < 256 |
@@ -107,7 +100,6 @@ hipError_t launch_c2r_unpack(cpx *data, const cpx *w2, int m, long batch, hipStr
 // arbitrary (non power-of-two) complex lengths, an extension: Bluestein's algorithm around two m-point
 // power-of-two transforms, m >= 2 n - 1 (fft_aux.inc); n up to kBlueMaxN
 constexpr int kBlueMaxN = 1 << 22;
-bool blue_lds_ok(int m);
 hipError_t launch_blue_lds(int m, const cpx *x, cpx *y, const cpx *w, const cpx *bt, const cpx *tab, int n, float scale,
                            long batch, const DeviceInfo &di, hipStream_t s);
 hipError_t launch_blue_pre(const cpx *x, const cpx *w, cpx *a, int n, int m, long batch, hipStream_t s);

@@ -338,6 +338,23 @@ def test_plan_host_arrays_bit_identical():
     assert p.free_host(np.zeros(4, np.complex64)) == -30
 
 
+def test_plan_host_arrays_overlapping_views():
+    """packed real plan, c and r views of ONE array of the plan half a transform apart (they overlap, and neither is the
+    other): the call goes the way of pageable arrays instead of being refused, and gives the bits the same call gives on
+    pageable copies laid out the same way"""
+    size, batch, shift = 1024, 2, 512
+    x = np.random.default_rng(11).uniform(-1, 1, batch * size + shift).astype(np.float32)
+    for fwd in (True, False):
+        p = fa.Clrfft(0, size, fwd)
+        got, want = p.alloc_host(x.shape, np.float32), x.copy()
+        got[:] = x
+        for a in (got, want):
+            r, c = a[:batch * size].reshape(batch, size), a[shift:].view(np.complex64).reshape(batch, size // 2)
+            assert p.transform(c, r) == 0
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), fwd
+        assert not np.array_equal(want, x)
+
+
 def test_plan_host_arrays_randomised():
     """tools/stress_pinned.py with a fixed seed: arrays of random sizes taken from the plans and given back in a churning heap,
     complex and packed real, in place and out of place, every result bit for bit what the device-resident call gives (the
