@@ -34,7 +34,7 @@ namespace clfa {
 // chip is in; here XCD x takes the x-th CONTIGUOUS eighth of that window (workgroup i = x + 8 c starts at
 // x * (G / 8) + c), so that the workgroups behind one L2 stream through one compact address range.  Same windows,
 // same step, any batch; measured on the resident n = 65536 kernel: 0.871 -> 0.831 ms per 4096 transforms
-// (profiles/r04_assignment.txt; tools/res16_probe.hip PROBE_PERM sweeps the other assignments).
+// (profiles/assignment_r04.txt: 90 other assignments, measured with a sweep that has since left tools/res16_probe.hip).
 CLFA_HD long xcd_first(unsigned i, unsigned grid) {
   if (grid & 7) return i;
   return (long)(i & 7) * (grid >> 3) + (i >> 3);

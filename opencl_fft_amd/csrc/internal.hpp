@@ -70,7 +70,7 @@ int fourstep_split(int logn, int *logn1, int *logn2, int *loglo);
 constexpr int kRes16TabSize = 1792;
 // slots: 32 KiB per workgroup, grid = min(batch, CUs) workgroups (kRes16SlotBytes each)
 constexpr size_t kRes16SlotBytes = 32768;
-// out == data: in place (what every plan does); out != data: out of place (measured in tools/res16_probe.hip)
+// out == data: in place (what every plan does); out != data: out of place (tools/res16_probe.hip times both; profiles/oop_r04.txt)
 hipError_t launch_fft_res16(bool fwd, bool scale, const cpx *data, cpx *out, cpx *slots, const cpx *tabs, long batch,
                             const DeviceInfo &di, hipStream_t s);
 // packed real transforms of size 131072, forward: the same kernel with the reference's pair map inside its second

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Guards on the resident FFT kernel's code object (run on CPU; tests/test_abi_cpu.py calls it).
 
-The kernel (opencl_fft_amd/csrc/fft_resident.hip) does two things hipcc cannot check:
+The kernel (opencl_fft_amd/csrc/fft_resident.hip, one translation unit with its fft_res_*.inc) does two things hipcc cannot check:
   * it manages the accumulation register file by hand (literal a[N] in inline asm), so the compiler
     must not place anything of its own there: no v_accvgpr_* outside the asm blocks, no scratch;
   * it issues global loads from inline asm (hipcc neither counts nor waits for them) into AGPRs and
