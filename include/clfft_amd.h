@@ -494,6 +494,50 @@ CLFA_API int clfa_pvoc_read(clfa_pvoc *pv, const float *frames_in, long Fin, con
 /* op: 0 = scale, 1 = shift, 2 = read; the kernel's name as above ("" for a failed object or an unknown op) */
 CLFA_API const char *clfa_pvoc_ops_kernel_name(const clfa_pvoc *pv, int op, int keepform);
 
+/* ---- operations on two streams of (amp, freq) frames: cross, morph, filter, mix, vocode ---- */
+/* Csound's pvscross, pvsmorph, pvsfilter, pvsmix and pvsvoc.  frames_a, frames_b and frames_out: channels x F x (M + 1) x 2
+ * float32 in the layout above, 8-byte aligned; p and q: F float32 each, one value per frame, shared by the channels,
+ * 4-byte aligned.  MIX reads neither p nor q, and they may be NULL; every other op needs both.  coefs is used by VOCODE
+ * only, and there 1 <= coefs < M.
+ *
+ * The rules of the frame operations above hold: stateless (prev, theta and the oscillator bank's state are never
+ * touched), no allocation in a device call (every call can be captured), asynchronous on `stream`, one stream at a time,
+ * the current device left as found; F == 0 succeeds and does nothing.  Argument checks that need no device come first: on
+ * an object whose creation found no device a bad argument is still CLFA_INVALID_VALUE, a good one the object's error.
+ * An output that overlaps either input, p or q, even partly, is CLFA_INVALID_VALUE and writes nothing; the two inputs
+ * may overlap or be the same buffer, and p and q may be the same array.  The blocking form also checks the per-frame
+ * values (the device form cannot): every value of p and q finite, weights and depths in [0, 1] — both arrays for MORPH,
+ * p for FILTER and VOCODE; anything else is CLFA_INVALID_VALUE.
+ *
+ * Every float32 operation is rounded on its own (no fused multiply-add); fl() marks a rounding.
+ * clamp(x) = fminf(fmaxf(x, 0), 1), so a NaN gives 0.  Per channel, frame f and bin k = 0..M, every bin alike, with
+ * a = frames_a, b = frames_b, P = p[f], Q = q[f]:
+ *   CROSS   amp = fl(fl(a.amp P) + fl(b.amp Q)); freq = a.freq, a copy of the bits.
+ *   MORPH   wa = clamp(P), wf = clamp(Q); amp = a.amp (bits) where wa == 0, b.amp (bits) where wa == 1, otherwise
+ *           fl(a.amp + fl(wa fl(b.amp - a.amp))); freq follows the same rule with wf.  A value with weight 0 is not
+ *           used, so a NaN there stays out.
+ *   FILTER  d = clamp(P); m = 1 where d == 0, otherwise fl(fl(1 - d) + fl(d b.amp)); amp = fl(Q fl(a.amp m));
+ *           freq = a.freq (bits).
+ *   MIX     the whole pair of b (bits) where b.amp > a.amp, otherwise the pair of a.  Any comparison with a NaN is
+ *           false, so a wins.
+ *   VOCODE  (a gives the formants, b the excitation) envA, envB = env of the respective input frame, the cepstral
+ *           envelope defined above for keepform, with coefs; both are always computed.  d = clamp(P);
+ *           r = fl(envA[k] / envB[k]); m = fl(fl(1 - d) + fl(d r)); amp = fl(Q fl(b.amp m)); freq = b.freq (bits).
+ * tests/pvoc_pair_model.py restates all of it in numpy.
+ *
+ * Kernels: "k_pvoc_pair" (ops 0..3: a lane per output bin, 16 bytes in and 8 out, no LDS), "k_pvoc_vocode" (a workgroup
+ * holds whole frames in LDS and runs the envelope stages of k_pvoc_formant on the a-frames and then on the b-frames; each
+ * input frame is read once, the output written once, no workspace).  One launch per call.  CLFA_PVOC_OPS_GRID_MAX caps
+ * the workgroups of both. */
+enum { CLFA_PVOC_CROSS = 0, CLFA_PVOC_MORPH = 1, CLFA_PVOC_FILTER = 2, CLFA_PVOC_MIX = 3, CLFA_PVOC_VOCODE = 4 };
+CLFA_API int clfa_pvoc_pair_dev(clfa_pvoc *pv, int op, const void *frames_a, const void *frames_b, void *frames_out, long F,
+                                const void *p, const void *q, int coefs, void *stream);
+/* host arrays, copied in and out, blocking */
+CLFA_API int clfa_pvoc_pair(clfa_pvoc *pv, int op, const float *frames_a, const float *frames_b, float *frames_out, long F,
+                            const float *p, const float *q, int coefs);
+/* "k_pvoc_pair", "k_pvoc_vocode" for op 4 ("" for a failed object or an unknown op) */
+CLFA_API const char *clfa_pvoc_pair_kernel_name(const clfa_pvoc *pv, int op);
+
 /* ---- convolution matrix (extension: nothing of the reference's) ------------- */
 /* Uniformly partitioned overlap-add convolution of `inputs` signals with an outputs x inputs matrix of static responses:
  * y_o = sum over i of x_i * h_{o,i}.

@@ -498,6 +498,89 @@ class Pvoc(_Handle):
         check(lib().clfa_pvoc_read(self._h, frames.ctypes.data, Fin, par.ctypes.data, out.ctypes.data, pos.size), "Pvoc.read")
         return out
 
+    # ---- two streams of frames -> frames: cross, morph, filter, mix, vocode (stateless; clfft_amd.h) ----
+
+    _PAIR_OPS = {"cross": 0, "morph": 1, "filter": 2, "mix": 3, "vocode": 4}
+
+    def pair_kernel_name(self, op):
+        """op "cross", "morph", "filter", "mix" (or 0..3) -> "k_pvoc_pair", "vocode" (4) -> "k_pvoc_vocode" ("" for a failed
+        object or an unknown op)"""
+        code = self._PAIR_OPS.get(op, -1) if isinstance(op, str) else int(op)
+        return lib().clfa_pvoc_pair_kernel_name(self._h, code).decode()
+
+    def _pair_device(self, op, a, b, out, p, q, coefs, stream):
+        """one two-input device call; p, q: numbers or float32 device tensors (F,), None for mix"""
+        import torch
+        F = self._frames_shape(out.shape)
+        if F is None or any(self._frames_shape(t.shape) != F or t.dtype != torch.float32 or not t.is_contiguous()
+                            for t in (a, b, out)):
+            return CL_INVALID_VALUE
+        ptrs = []
+        for par in (p, q):
+            if par is not None:
+                par = self._per_frame(par, F, out.device)
+                if par is None:
+                    return CL_INVALID_VALUE
+            ptrs.append(par)
+        return lib().clfa_pvoc_pair_dev(self._h, op, a.data_ptr(), b.data_ptr(), out.data_ptr(), F,
+                                        None if ptrs[0] is None else ptrs[0].data_ptr(),
+                                        None if ptrs[1] is None else ptrs[1].data_ptr(), int(coefs), _stream_of(out, stream))
+
+    def cross_device(self, a, b, out, amp_a=1.0, amp_b=1.0, stream=None):
+        """cross-synthesis (Csound's pvscross): torch frames a, b (channels, F, size/2 + 1, 2) float32 -> out of the same
+        shape with amp = a.amp amp_a + b.amp amp_b and the freqs of a; amp_a, amp_b: numbers or float32 device tensors
+        (F,).  out may overlap neither input; a and b may be the same tensor.  Asynchronous on `stream`."""
+        return self._pair_device(0, a, b, out, amp_a, amp_b, 1, stream)
+
+    def morph_device(self, a, b, out, amp=0.5, freq=0.5, stream=None):
+        """morph (Csound's pvsmorph): amps and freqs interpolated from a (weight 0) to b (weight 1); amp, freq: the two
+        weights, numbers or float32 device tensors (F,), clamped to [0, 1]"""
+        return self._pair_device(1, a, b, out, amp, freq, 1, stream)
+
+    def filter_device(self, a, b, out, depth=1.0, gain=1.0, stream=None):
+        """spectral filter (Csound's pvsfilter): the amps of a times (1 - depth) + depth b.amp, times gain; the freqs of a"""
+        return self._pair_device(2, a, b, out, depth, gain, 1, stream)
+
+    def mix_device(self, a, b, out, stream=None):
+        """spectral maximum (Csound's pvsmix): per bin the (amp, freq) pair of the input with the larger amp"""
+        return self._pair_device(3, a, b, out, None, None, 1, stream)
+
+    def vocode_device(self, a, b, out, depth=1.0, gain=1.0, coefs=80, stream=None):
+        """channel vocoder (Csound's pvsvoc): the excitation b takes the formants of a — its amps are multiplied by
+        (1 - depth) + depth envA / envB, the cepstral envelopes of `coefs` coefficients, and by gain; the freqs of b"""
+        return self._pair_device(4, a, b, out, depth, gain, coefs, stream)
+
+    def _pair_host(self, op, a, b, p, q, coefs, what):
+        a, F = self._host_frames(a)
+        b, Fb = self._host_frames(b)
+        if Fb != F or a.shape != b.shape:
+            raise ValueError("a and b must have the same shape")
+        out = np.zeros(a.shape, np.float32)
+        p, q = (None if x is None else self._per_frame_host(x, F) for x in (p, q))
+        check(lib().clfa_pvoc_pair(self._h, op, a.ctypes.data, b.ctypes.data, out.ctypes.data, F,
+                                   None if p is None else p.ctypes.data, None if q is None else q.ctypes.data, int(coefs)), what)
+        return out
+
+    def cross(self, a, b, amp_a=1.0, amp_b=1.0):
+        """host form of cross_device, blocking: returns the new frames"""
+        return self._pair_host(0, a, b, amp_a, amp_b, 1, "Pvoc.cross")
+
+    def morph(self, a, b, amp=0.5, freq=0.5):
+        """host form of morph_device, blocking; a weight outside [0, 1] raises ClError(CL_INVALID_VALUE)"""
+        return self._pair_host(1, a, b, amp, freq, 1, "Pvoc.morph")
+
+    def filter(self, a, b, depth=1.0, gain=1.0):
+        """host form of filter_device, blocking; a depth outside [0, 1] raises ClError(CL_INVALID_VALUE)"""
+        return self._pair_host(2, a, b, depth, gain, 1, "Pvoc.filter")
+
+    def mix(self, a, b):
+        """host form of mix_device, blocking"""
+        return self._pair_host(3, a, b, None, None, 1, "Pvoc.mix")
+
+    def vocode(self, a, b, depth=1.0, gain=1.0, coefs=80):
+        """host form of vocode_device, blocking; a depth outside [0, 1] raises ClError(CL_INVALID_VALUE)"""
+        return self._pair_host(4, a, b, depth, gain, coefs, "Pvoc.vocode")
+
     # ---- frames -> samples: the oscillator bank (Csound's pvsadsyn; a state of its own; clfft_amd.h) ----
 
     def adsyn_kernel_name(self):

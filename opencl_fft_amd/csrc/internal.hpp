@@ -309,6 +309,23 @@ struct PvocOpsArgs {
 // one launch: k_pvoc_map, k_pvoc_formant<logn> (keepform) or k_pvoc_read
 hipError_t launch_pvoc_ops(const PvocOpsArgs &a, const DeviceInfo &di, hipStream_t s);
 
+// ---- operations on two streams of (amp, freq) frames (pvoc_pair.hip) ------------------
+enum PvocPairOp { PVOC_CROSS = 0, PVOC_MORPH = 1, PVOC_FILTER = 2, PVOC_MIX = 3, PVOC_VOCODE = 4 };   // CLFA_PVOC_*
+struct PvocPairArgs {
+  int op = PVOC_CROSS;
+  int logn = 0;                    // log2(M): the vocoder's transform length (complex)
+  int M = 0, channels = 0;
+  long F = 0;                      // frames per channel of a, b and out
+  const cpx *a = nullptr, *b = nullptr;   // frames as (amp, freq) pairs; they may overlap
+  cpx *out = nullptr;
+  const float *p = nullptr, *q = nullptr;   // F values each (mix: not read)
+  int coefs = 1;                   // vocode
+  const cpx *half = nullptr, *w2 = nullptr;   // vocode: the Clrfft tables of size (forward sign)
+  int grid_max = 0;                // > 0: at most this many workgroups
+};
+// one launch: k_pvoc_pair, or k_pvoc_vocode<logn> for PVOC_VOCODE
+hipError_t launch_pvoc_pair(const PvocPairArgs &a, const DeviceInfo &di, hipStream_t s);
+
 // ---- direct convolution ----------------------------------------------------------
 struct DconvPlan {
   int C;    // taps per workgroup

@@ -26,6 +26,7 @@ struct clfa_pvoc {
   DevBuf half, w2;
   int ops_grid_max = 0;
   DevBuf sop_out, sop_par;
+  DevBuf spair_b, spair_q;   // the two-input operations (pvoc_pair.hip): staging of the second input and per-frame array
   // the oscillator bank (pvoc_adsyn.hip): 1 / sr, its state per channel and bin (P uint64, W int32, A float32), the ramp
   // w_j, its own workspace (the 64-bit chunk sums of one sub-batch, then the endpoints a sub-batch starts from), the
   // chunks per sub-batch, the cap on its workgroups (CLFA_PVOC_ADSYN_GRID_MAX, 0 = none), staging of the host form
@@ -382,6 +383,93 @@ int clfa_pvoc_synthesize(clfa_pvoc *p, const float *frames, float *spectra_out, 
   if (F == 0) return CLFA_SUCCESS;
   return pvoc_staged(p, {{true, spectra_out, &p->sspec, pvoc_spec_bytes(p, F)}, {false, frames, &p->sframes, pvoc_frame_bytes(p, F)}},
                      [&] { return clfa_pvoc_synthesize_dev(p, p->sframes.p, p->sspec.p, F, p->stream); });
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------
+// two streams of frames -> frames: cross, morph, filter, mix, vocode (pvoc_pair.hip)
+// ---------------------------------------------------------------------------------
+
+// The checks that need no device, before the object's own error (as pvoc_ops_check).  0 = go on, 1 = a successful no-op,
+// < 0 = the error.  MIX reads neither per-frame array: they are not looked at.
+static int pvoc_pair_check(const clfa_pvoc *p, int op, const void *a, const void *b, const void *out, long F,
+                           const void *pp, const void *qq, int coefs, bool device_ptrs) {
+  if (!p) return CLFA_INVALID_VALUE;
+  if (!p->M) return p->err ? p->err : CLFA_INVALID_VALUE;
+  if (op < PVOC_CROSS || op > PVOC_VOCODE) return CLFA_INVALID_VALUE;
+  if (!pvoc_count_ok(F)) return CLFA_INVALID_VALUE;
+  if (op == PVOC_VOCODE && (coefs < 1 || coefs >= p->M)) return CLFA_INVALID_VALUE;
+  if (F == 0) return 1;
+  if (!a || !b || !out) return CLFA_INVALID_VALUE;
+  if (device_ptrs && (((uintptr_t)a & 7) || ((uintptr_t)b & 7) || ((uintptr_t)out & 7))) return CLFA_INVALID_VALUE;
+  const size_t fbytes = pvoc_frame_bytes(p, F), pbytes = sizeof(float) * (size_t)F;
+  if (spans_overlap(a, fbytes, out, fbytes) || spans_overlap(b, fbytes, out, fbytes)) return CLFA_INVALID_VALUE;
+  if (op == PVOC_MIX) return CLFA_SUCCESS;
+  if (!pp || !qq) return CLFA_INVALID_VALUE;
+  if (device_ptrs && (((uintptr_t)pp & 3) || ((uintptr_t)qq & 3))) return CLFA_INVALID_VALUE;
+  if (spans_overlap(pp, pbytes, out, fbytes) || spans_overlap(qq, pbytes, out, fbytes)) return CLFA_INVALID_VALUE;
+  return CLFA_SUCCESS;
+}
+
+static int pvoc_pair_dev(clfa_pvoc *p, int op, const void *a, const void *b, void *out, long F, const void *pp,
+                         const void *qq, int coefs, void *stream) {
+  if (int e = pvoc_gate(p, pvoc_pair_check(p, op, a, b, out, F, pp, qq, coefs, true))) return pvoc_done(e);
+  ENTER_DEVICE(p->di.device);
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(p->order.use(s));
+  PvocPairArgs g;
+  g.op = op;
+  g.logn = ilog2(p->M);
+  g.M = p->M;
+  g.channels = p->channels;
+  g.F = F;
+  g.a = (const cpx *)a;
+  g.b = (const cpx *)b;
+  g.out = (cpx *)out;
+  g.p = op == PVOC_MIX ? nullptr : (const float *)pp;
+  g.q = op == PVOC_MIX ? nullptr : (const float *)qq;
+  g.coefs = coefs;
+  g.half = (const cpx *)p->half.p;
+  g.w2 = (const cpx *)p->w2.p;
+  g.grid_max = p->ops_grid_max;
+  HIP_TRY(launch_pvoc_pair(g, p->di, s));
+  return CLFA_SUCCESS;
+}
+
+// the blocking form: the same checks on the host arrays, then the per-frame values, then copies around the device form
+static int pvoc_pair_host(clfa_pvoc *p, int op, const float *a, const float *b, float *out, long F, const float *pp,
+                          const float *qq, int coefs) {
+  const int chk = pvoc_pair_check(p, op, a, b, out, F, pp, qq, coefs, false);
+  if (chk < 0) return chk;
+  const bool unit_p = op == PVOC_MORPH || op == PVOC_FILTER || op == PVOC_VOCODE, unit_q = op == PVOC_MORPH;
+  for (long f = 0; f < F && op != PVOC_MIX; f++) {
+    if (!std::isfinite(pp[f]) || !std::isfinite(qq[f])) return CLFA_INVALID_VALUE;
+    if ((unit_p && !(pp[f] >= 0.f && pp[f] <= 1.f)) || (unit_q && !(qq[f] >= 0.f && qq[f] <= 1.f))) return CLFA_INVALID_VALUE;
+  }
+  if (int e = pvoc_gate(p, chk)) return pvoc_done(e);
+  const bool mix = op == PVOC_MIX;
+  const size_t fbytes = pvoc_frame_bytes(p, F), pbytes = sizeof(float) * (size_t)F;
+  return pvoc_staged(p, {{false, a, &p->sframes, fbytes}, {false, b, &p->spair_b, fbytes}, {true, out, &p->sop_out, fbytes},
+                         {false, mix ? nullptr : pp, &p->sop_par, pbytes}, {false, mix ? nullptr : qq, &p->spair_q, pbytes}}, [&] {
+                       return pvoc_pair_dev(p, op, p->sframes.p, p->spair_b.p, p->sop_out.p, F, p->sop_par.p, p->spair_q.p,
+                                            coefs, p->stream);
+                     });
+}
+
+extern "C" {
+
+int clfa_pvoc_pair_dev(clfa_pvoc *p, int op, const void *frames_a, const void *frames_b, void *frames_out, long F,
+                       const void *pp, const void *qq, int coefs, void *stream) {
+  return pvoc_pair_dev(p, op, frames_a, frames_b, frames_out, F, pp, qq, coefs, stream);
+}
+int clfa_pvoc_pair(clfa_pvoc *p, int op, const float *frames_a, const float *frames_b, float *frames_out, long F,
+                   const float *pp, const float *qq, int coefs) {
+  return pvoc_pair_host(p, op, frames_a, frames_b, frames_out, F, pp, qq, coefs);
+}
+const char *clfa_pvoc_pair_kernel_name(const clfa_pvoc *p, int op) {
+  if (!p || p->err || op < PVOC_CROSS || op > PVOC_VOCODE) return "";
+  return op == PVOC_VOCODE ? "k_pvoc_vocode" : "k_pvoc_pair";
 }
 
 }  // extern "C"

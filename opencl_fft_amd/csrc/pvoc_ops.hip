@@ -10,15 +10,16 @@
 //                   into LDS (the pairs, and the logs of its amps as the even extension Lext), the packed forward real
 //                   transform of Lext runs on the pass chain of k_stft_analyze, the pair step lifters (forward pair map,
 //                   zeros above coefs, inverse pair map in one visit of the pair), the inverse runs on the chain of
-//                   k_stft_synth, expf turns the first M + 1 samples into env in place, and the map gathers amp, freq
+//                   k_stft_synth, expf turns the first M + 1 samples into env in place (these stages are
+//                   pvoc_envelope of pvoc_env.hpp, which k_pvoc_vocode shares), and the map gathers amp, freq
 //                   and the two envelope values from LDS.  One read and one write of the frame, no workspace.  n = 8192
 //                   reads its twiddle tables from L1/L2 (k_stft_synth's LDS budget: here 70 KiB of exchange buffer and
 //                   64 KiB of frame leave no room for 48 KiB of tables).
 //
 // Every float32 step of the definitions is rounded on its own: the device functions below switch contraction off, as
 // pvoc_inc does (pvoc_kernels.hip).  tests/pvoc_ops_model.py restates them.
-#include "fft_wg.hpp"
 #include "pvoc_device.hpp"
+#include "pvoc_env.hpp"
 
 namespace clfa {
 
@@ -136,8 +137,6 @@ __global__ __launch_bounds__(kOpsWG) void k_pvoc_read(const cpx *__restrict__ in
   }
 }
 
-template <int LOGN> constexpr bool pvoc_formant_tab_lds() { return LOGN <= 12; }
-
 // grid-stride over groups of FPW consecutive frames (frame index b = c * F + f; the frames are contiguous)
 template <int LOGN>
 __global__ __launch_bounds__(LdsGeom<LOGN>::WG) void k_pvoc_formant(const cpx *__restrict__ in, cpx *__restrict__ out,
@@ -146,14 +145,14 @@ __global__ __launch_bounds__(LdsGeom<LOGN>::WG) void k_pvoc_formant(const cpx *_
                                                                     float bpf, const cpx *__restrict__ tab_g,
                                                                     const cpx *__restrict__ w2_g) {
   using G = LdsGeom<LOGN>;
-  constexpr int N = G::N, E = G::E, T = G::T, WG = G::WG, FPW = G::FPW, B = N + 1;   // M = N, B bins per frame
-  constexpr bool TL = pvoc_formant_tab_lds<LOGN>();
+  using P = PvocEnv<LOGN>;
+  constexpr int N = G::N, WG = G::WG, FPW = G::FPW, B = N + 1;   // M = N, B bins per frame
+  constexpr bool TL = pvoc_env_tab_lds<LOGN>();
   __shared__ cpx s_tab[TL ? G::HALF : 1];
   __shared__ cpx s_w2[TL ? N / 2 : 1];
   __shared__ cpx s_x[FPW * G::PADN];   // the exchange buffer: Lext, its spectrum, logE, env
   __shared__ cpx s_fr[FPW * B];        // the group's frames as read
   const int tid = threadIdx.x;
-  const int f = tid / T, t = tid % T;
   if constexpr (TL) {
     for (int i = tid; i < N / 2; i += WG) {
       s_tab[i] = tab_g[i];
@@ -161,68 +160,19 @@ __global__ __launch_bounds__(LdsGeom<LOGN>::WG) void k_pvoc_formant(const cpx *_
     }
   }
   const cpx *tab = TL ? s_tab : tab_g, *w2 = TL ? s_w2 : w2_g;
-  cpx *xb = s_x + f * G::PADN;
-  float *xf = reinterpret_cast<float *>(s_x);
-  // sample n of frame fi's real sequence (floats 2p, 2p + 1 of complex element p, padded)
-  auto sample = [&](int fi, int n) -> float & { return xf[2 * (fi * G::PADN + lds_pad(n >> 1)) + (n & 1)]; };
+  auto sample = [&](int fi, int n) -> float & { return P::sample(s_x, fi, n); };
   const long groups = (nframes + FPW - 1) / FPW;
 #pragma unroll 1
   for (long g = blockIdx.x; g < groups; g += gridDim.x) {
     const long b0 = g * FPW;
     const int nv = nframes - b0 < FPW ? (int)(nframes - b0) : FPW;   // frames of a ragged last group; the other slots
     const int live = nv * B;                                         // run the chain on stale LDS and write nothing
-    // the frames in: element idx = frame idx / B, bin idx % B; L[k] lands at samples k and size - k
-    for (int idx = tid; idx < live; idx += WG) {
-      const int fi = idx / B, k = idx - fi * B;
+    // the frames in, once: the pairs stay in s_fr, the envelope of their amps lands in s_x (pvoc_env.hpp)
+    pvoc_envelope<LOGN>(s_x, tab, w2, coefs, live, [&](int idx) {
       const cpx af = in[b0 * B + idx];
       s_fr[idx] = af;
-      const float L = logf(fmaxf(af.x, 1e-20f));   // fmaxf(NaN, floor) = floor
-      sample(fi, k) = L;
-      if (k > 0 && k < N) sample(fi, 2 * N - k) = L;
-    }
-    __syncthreads();
-    cpx v[E];
-    pass_gather_padded<LOGN, G::LOGE>(v, t, xb);
-    wg_passes<LOGN, G::LOGE, 0, true>(v, t, tab, xb);
-#pragma unroll
-    for (int e = 0; e < E; e++) v[e] = cscale(v[e], 1.0f / (float)N);   // forward real plans scale by 1/M
-    __syncthreads();
-    dif_scatter_padded<LOGN, G::LOGE>(v, t, xb);
-    __syncthreads();
-    // one visit of every pair (i, N - i): the forward pair map (k_stft_analyze), the lifter on the packed bins, the
-    // inverse pair map (k_stft_synth; its table is the forward one conjugated)
-#pragma unroll
-    for (int k = 0; k < E / 2; k++) {
-      const int i = t + T * k, j = i == 0 ? N / 2 : N - i;
-      const cpx ci = xb[lds_pad(i)], cj = xb[lds_pad(j)];
-      const cpx w = w2[i];
-      const bool z = i == 0;
-      cpx oi, oj;
-      r2c_pair(ci, cj, w, oi, oj);
-      oi = mk(z ? (ci.x + ci.y) * .5f : oi.x, z ? 0.f : oi.y);   // bin 0 = (DC, Nyquist): the Nyquist half goes
-      oj = mk(z ? cj.x : oj.x, z ? cj.y : oj.y);
-      if (i > coefs) oi = mk(0.f, 0.f);
-      if (j > coefs) oj = mk(0.f, 0.f);
-      cpx ni, nj;
-      c2r_pair(oi, oj, mk(w.x, -w.y), ni, nj);
-      ni = mk(z ? oi.x + oi.y : ni.x, z ? oi.x - oi.y : ni.y);
-      nj = mk(z ? oj.x : nj.x, z ? oj.y : nj.y);
-      xb[lds_pad(i)] = ni;
-      xb[lds_pad(j)] = nj;
-    }
-    __syncthreads();
-    pass_gather_padded<LOGN, G::LOGE>(v, t, xb);
-    wg_passes<LOGN, G::LOGE, 0, false>(v, t, tab, xb);
-    __syncthreads();
-    dif_scatter_padded<LOGN, G::LOGE>(v, t, xb);
-    __syncthreads();
-    // env[k] = expf(logE[k]), k = 0..M, in place
-    for (int idx = tid; idx < live; idx += WG) {
-      const int fi = idx / B, k = idx - fi * B;
-      float &e = sample(fi, k);
-      e = expf(e);
-    }
-    __syncthreads();
+      return af.x;
+    });
     for (int idx = tid; idx < live; idx += WG) {
       const int fi = idx / B, j = idx - fi * B;
       const float s = par[(b0 + fi) % F];

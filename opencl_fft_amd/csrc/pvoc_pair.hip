@@ -1,0 +1,184 @@
+// pvoc_pair.hip — operations on two streams of (amp, freq) frames of clfa_pvoc (include/clfft_amd.h): cross-synthesis,
+// morph, spectral filter, spectral maximum and the channel vocoder.  Stateless, one launch per call, no atomics; the
+// decoding of a grid-stride item and the cap on a launch's workgroups are pvoc_device.hpp's.
+//
+//   k_pvoc_pair    cross, morph, filter, mix: a lane takes bin k of one frame, reads the pair of a and the pair of b and
+//                  writes one pair; rows of consecutive bins, 8 bytes per lane and stream (16 in, 8 out), no LDS.  The
+//                  op is a kernel argument: every lane of a launch takes the same branch.
+//   k_pvoc_vocode  a workgroup holds FPW = LdsGeom::FPW frames.  The a-frames go through the envelope stages of
+//                  k_pvoc_formant (pvoc_envelope, pvoc_env.hpp) and every lane picks up envA of its own bins (element
+//                  tid + i WG, i < 17: 17 floats in registers); the b-frames then go through the same stages in the same
+//                  slots, their pairs staying in LDS as k_pvoc_formant's do; the rule is applied bin by bin, each lane
+//                  on the bins whose envA it holds.  Each input frame is read once, the output written once, no
+//                  workspace.  LDS is k_pvoc_formant's (exchange buffer + one frame copy, 132 KiB at n = 8192, where the
+//                  twiddle tables come from L1/L2).
+//
+// Every float32 step of the definitions is rounded on its own: the device functions below switch contraction off.
+// tests/pvoc_pair_model.py restates them.
+#include "pvoc_device.hpp"
+#include "pvoc_env.hpp"
+
+namespace clfa {
+
+namespace {
+
+constexpr int kPairWG = 256;   // lanes = bins per workgroup tile (k_pvoc_pair)
+
+__device__ __forceinline__ float pvoc_clamp01(float x) { return fminf(fmaxf(x, 0.f), 1.f); }   // fmaxf(NaN, 0) = 0
+
+// x0 where w == 0, x1 where w == 1 (the bits; the other side is not used), else fl(x0 + fl(w fl(x1 - x0)))
+__device__ __forceinline__ float pvoc_morph(float x0, float x1, float w) {
+#pragma clang fp contract(off)
+  const float d = x1 - x0;
+  const float s = w * d;
+  const float m = x0 + s;
+  return w == 0.f ? x0 : (w == 1.f ? x1 : m);
+}
+
+// one bin of ops 0..3
+__device__ __forceinline__ cpx pvoc_pair_bin(int op, cpx a, cpx b, float P, float Q) {
+#pragma clang fp contract(off)
+  if (op == PVOC_CROSS) {
+    const float x = a.x * P, y = b.x * Q;
+    return mk(x + y, a.y);
+  }
+  if (op == PVOC_MORPH) return mk(pvoc_morph(a.x, b.x, pvoc_clamp01(P)), pvoc_morph(a.y, b.y, pvoc_clamp01(Q)));
+  if (op == PVOC_FILTER) {
+    const float d = pvoc_clamp01(P);
+    const float u = 1.f - d, w = d * b.x;
+    const float m = d == 0.f ? 1.f : u + w;
+    const float x = a.x * m;
+    return mk(Q * x, a.y);
+  }
+  return b.x > a.x ? b : a;   // PVOC_MIX: a comparison with a NaN is false
+}
+
+// one bin of the vocoder: b = the excitation's pair
+__device__ __forceinline__ cpx pvoc_vocode_bin(cpx b, float envA, float envB, float P, float Q) {
+#pragma clang fp contract(off)
+  const float d = pvoc_clamp01(P);
+  const float r = envA / envB;
+  const float u = 1.f - d, w = d * r;
+  const float m = u + w;
+  const float x = b.x * m;
+  return mk(Q * x, b.y);
+}
+
+}  // namespace
+
+// item -> (channel, frame f, bin tile), the tile fastest.  p, q: NULL for PVOC_MIX, which reads neither
+__global__ __launch_bounds__(kPairWG) void k_pvoc_pair(const cpx *a, const cpx *b, cpx *__restrict__ out,
+                                                       const float *p, const float *q, long F, int M, int tiles,
+                                                       long items, int op) {
+#pragma unroll 1
+  for (long item = blockIdx.x; item < items; item += gridDim.x) {
+    int tile;
+    long f, c;
+    pvoc_item(item, tiles, F, tile, f, c);
+    const int k = tile * kPairWG + (int)threadIdx.x;
+    if (k > M) continue;
+    const long e = (c * F + f) * (M + 1) + k;
+    float P = 0.f, Q = 0.f;
+    if (op != PVOC_MIX) {
+      P = p[f];
+      Q = q[f];
+    }
+    out[e] = pvoc_pair_bin(op, a[e], b[e], P, Q);
+  }
+}
+
+// grid-stride over groups of FPW consecutive frames (frame index c * F + f; the frames are contiguous)
+template <int LOGN>
+__global__ __launch_bounds__(LdsGeom<LOGN>::WG) void k_pvoc_vocode(const cpx *a, const cpx *b, cpx *__restrict__ out,
+                                                                   const float *p, const float *q, long F, long nframes,
+                                                                   int coefs, const cpx *__restrict__ tab_g,
+                                                                   const cpx *__restrict__ w2_g) {
+  using G = LdsGeom<LOGN>;
+  using P = PvocEnv<LOGN>;
+  constexpr int N = G::N, WG = G::WG, FPW = G::FPW, B = P::B, ITERS = P::ITERS;
+  constexpr bool TL = pvoc_env_tab_lds<LOGN>();
+  __shared__ cpx s_tab[TL ? G::HALF : 1];
+  __shared__ cpx s_w2[TL ? N / 2 : 1];
+  __shared__ cpx s_x[FPW * G::PADN];   // the exchange buffer, first of the a-frames, then of the b-frames
+  __shared__ cpx s_fr[FPW * B];        // the group's b-frames as read
+  __shared__ cpx s_pq[FPW];            // (p, q) of the group's frames
+  const int tid = threadIdx.x;
+  if constexpr (TL) {
+    for (int i = tid; i < N / 2; i += WG) {
+      s_tab[i] = tab_g[i];
+      s_w2[i] = w2_g[i];
+    }
+  }
+  const cpx *tab = TL ? s_tab : tab_g, *w2 = TL ? s_w2 : w2_g;
+  const long groups = (nframes + FPW - 1) / FPW;
+#pragma unroll 1
+  for (long g = blockIdx.x; g < groups; g += gridDim.x) {
+    const long b0 = g * FPW;
+    const int nv = nframes - b0 < FPW ? (int)(nframes - b0) : FPW;   // frames of a ragged last group; the other slots
+    const int live = nv * B;                                         // run the chains on stale LDS and write nothing
+    if (tid < nv) {   // the frames' (p, q); the barriers of the envelope stages stand between this and their use
+      const long f = (b0 + tid) % F;
+      s_pq[tid] = mk(p[f], q[f]);
+    }
+    pvoc_envelope<LOGN>(s_x, tab, w2, coefs, live, [&](int idx) { return a[b0 * B + idx].x; });
+    float ea[ITERS];   // envA of the lane's own bins: element idx = tid + i WG
+#pragma unroll
+    for (int i = 0; i < ITERS; i++) {
+      const int idx = tid + i * WG, fi = idx / B;
+      if (idx < live) ea[i] = P::sample(s_x, fi, idx - fi * B);
+    }
+    __syncthreads();   // envA is out of s_x before the b-frames land there
+    pvoc_envelope<LOGN>(s_x, tab, w2, coefs, live, [&](int idx) {
+      const cpx bf = b[b0 * B + idx];
+      s_fr[idx] = bf;
+      return bf.x;
+    });
+#pragma unroll
+    for (int i = 0; i < ITERS; i++) {
+      const int idx = tid + i * WG, fi = idx / B;
+      if (idx < live)
+        out[b0 * B + idx] = pvoc_vocode_bin(s_fr[idx], ea[i], P::sample(s_x, fi, idx - fi * B), s_pq[fi].x, s_pq[fi].y);
+    }
+    __syncthreads();   // the group is out before the next one lands in s_x, s_fr and s_pq
+  }
+}
+
+template <int LOGN>
+static hipError_t launch_pvoc_vocode_n(const PvocPairArgs &a, const DeviceInfo &di, hipStream_t s) {
+  using G = LdsGeom<LOGN>;
+  static int occ = 0;
+  if (!occ) {
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)k_pvoc_vocode<LOGN>, G::WG, 0) != hipSuccess || nb < 1) {
+      (void)hipGetLastError();
+      nb = 1;
+    }
+    occ = nb;
+  }
+  const long nframes = (long)a.channels * a.F, groups = (nframes + G::FPW - 1) / G::FPW;
+  const int grid = pvoc_grid(groups, (long)di.num_cus * occ, a.grid_max);
+  hipLaunchKernelGGL((k_pvoc_vocode<LOGN>), dim3(grid), dim3(G::WG), 0, s, a.a, a.b, a.out, a.p, a.q, a.F, nframes,
+                     a.coefs, a.half, a.w2);
+  return hipGetLastError();
+}
+
+hipError_t launch_pvoc_pair(const PvocPairArgs &a, const DeviceInfo &di, hipStream_t s) {
+  if (a.F <= 0 || a.channels <= 0) return hipSuccess;
+  if (a.op == PVOC_VOCODE) {
+    switch (a.logn) {
+#define CLFA_N(L) \
+  case L: return launch_pvoc_vocode_n<L>(a, di, s);
+      CLFA_N(5) CLFA_N(6) CLFA_N(7) CLFA_N(8) CLFA_N(9) CLFA_N(10) CLFA_N(11) CLFA_N(12) CLFA_N(13)
+#undef CLFA_N
+      default:
+        return hipErrorInvalidValue;
+    }
+  }
+  const int tiles = (a.M + 1 + kPairWG - 1) / kPairWG;
+  const long items = (long)a.channels * a.F * tiles;
+  const int grid = pvoc_grid(items, (long)di.num_cus * 16, a.grid_max);
+  hipLaunchKernelGGL(k_pvoc_pair, dim3(grid), dim3(kPairWG), 0, s, a.a, a.b, a.out, a.p, a.q, a.F, a.M, tiles, items, a.op);
+  return hipGetLastError();
+}
+
+}  // namespace clfa

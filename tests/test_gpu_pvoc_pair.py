@@ -1,0 +1,466 @@
+"""The two-input frame operations of clfa_pvoc on the device (pvoc_pair.hip: k_pvoc_pair, k_pvoc_vocode) against the numpy
+restatement of their definitions (tests/pvoc_pair_model.py).
+
+Cross, morph, filter and mix are bit-equal with the float32 model: every operation of theirs is a single correctly
+rounded float32 step (where the model gives a NaN the device gives a NaN; payloads are not compared).  The vocoder's freq
+column is bit-equal with b's; its amps go through logf, two LDS transforms and expf per input, which are not numpy's, so
+the contract is the one of tests/test_gpu_pvoc_ops.py: the relative L2 error of the amps against the float64 model is at
+most MARGIN times the float32 model's own error on the same inputs.
+
+MARGIN.  The rule: the smallest of 2, 4, 8 that clears the largest ratio measured over every case of this file by a factor
+1.5.  Every case prints its ratio (`PVOCPAIR ...` lines, pytest -s).
+MEASURED over every case of this file on an MI355X: the ratios lie between 0.46 and 3.45.  On analysed frames the device's
+error is 2.3e-7 .. 1.5e-6 against the model's 2.0e-7 .. 8.8e-7 (ratios 0.93 .. 2.74, the largest at size 1024 with all 511
+coefficients); on the tilted raw frames 6.8e-7 .. 4.2e-6 against 7.0e-7 .. 3.4e-6 (ratios 0.46 .. 3.45).  The largest,
+3.45, is size 64, one channel, five tilted frames, coefs 31: 2.40e-6 against a model error of 6.95e-7 that is itself at
+the low end of what the model shows on such frames.  3.45 x 1.5 = 5.2 rules out 4, so MARGIN is 8.
+"""
+import numpy as np
+import pytest
+import torch
+
+import opencl_fft_amd as fa
+from tests import pvoc_model as pm
+from tests import pvoc_ops_model as om
+from tests import pvoc_pair_model as pp
+from tests import stft_model
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+SR = 48000.0
+MARGIN = 8.0            # see the docstring: the largest ratio measured is 3.45
+CL_INVALID_VALUE = -30
+CANARY = 0x7FC0BEEF     # guard bands: a quiet NaN with a payload no kernel produces (tests/test_gpu_fft_impulses.py)
+f32 = np.float32
+RATIO = {"max": 0.0}
+OPS = ("cross", "morph", "filter", "mix")
+
+
+def fpw(size):
+    """frames per workgroup of k_pvoc_vocode (LdsGeom: 16 points per lane, at least 256 lanes)"""
+    t = max(size // 2 // 16, 1)
+    return max(t, 256) // t
+
+
+def make(size, channels=1, hop=None, grid_max=None, monkeypatch=None):
+    if grid_max is not None:
+        monkeypatch.setenv("CLFA_PVOC_OPS_GRID_MAX", str(grid_max))
+    pv = fa.Pvoc(0, size, hop or size // 4, SR, channels)
+    if grid_max is not None:
+        monkeypatch.delenv("CLFA_PVOC_OPS_GRID_MAX")
+    assert pv.get_error() == 0, pv.get_log()
+    assert [pv.pair_kernel_name(op) for op in OPS + ("vocode",)] == ["k_pvoc_pair"] * 4 + ["k_pvoc_vocode"]
+    return pv
+
+
+def hann(size):
+    return (0.5 - 0.5 * np.cos(2 * np.pi * np.arange(size) / size)).astype(f32)
+
+
+_FRAMES = {}
+
+
+def analysed(size, C, F, seed):
+    """frames of Stft + Pvoc.analyze_device on noise plus two sinusoids that depend on the seed (numpy, cached, read-only)"""
+    key = ("a", size, C, F, seed)
+    if key not in _FRAMES:
+        hop = size // 4
+        rng = np.random.default_rng(seed)
+        n = size + (F - 1) * hop
+        t = np.arange(n)
+        k1, k2 = rng.uniform(5, 20), rng.uniform(size / 4, size / 2 - 2)
+        x = 0.1 * rng.standard_normal((C, n)) + 0.7 * np.cos(2 * np.pi * k1 / size * t + 0.2) \
+            + 0.4 * np.cos(2 * np.pi * k2 / size * t)
+        st = fa.Stft(0, size, hop, window=hann(size))
+        spec = torch.zeros((C, F, size // 2), dtype=torch.complex64, device=DEV)
+        assert st.analyze_device(torch.from_numpy(x.astype(f32)).to(DEV), spec) == 0
+        fr = torch.zeros((C, F, size // 2 + 1, 2), device=DEV)
+        assert fa.Pvoc(0, size, hop, SR, C).analyze_device(spec, fr) == 0
+        torch.cuda.synchronize()
+        a = fr.cpu().numpy()
+        a.setflags(write=False)
+        _FRAMES[key] = a
+    return _FRAMES[key]
+
+
+def raw(size, C, F, seed, tilt=False):
+    """raw random frames, any freq: amps log-uniform over 1e-30 .. 1e30 and a few zeros; tilt (the vocoder's cases): a
+    slope of 15 decades over the bins, up or down by frame, times a random factor 0.1 .. 10, and one zero amp — twice
+    that slope and envA / envB would leave float32"""
+    key = ("r", size, C, F, seed, tilt)
+    if key not in _FRAMES:
+        rng = np.random.default_rng(seed)
+        B = size // 2 + 1
+        if tilt:
+            ramp = np.linspace(-7.5, 7.5, B) * rng.choice([-1.0, 1.0], (C, F, 1))
+            amp = (10.0 ** (ramp + rng.uniform(-1, 1, (C, F, B)))).astype(f32)
+            amp[C - 1, F - 1, B // 3] = 0
+        else:
+            amp = (10.0 ** rng.uniform(-30, 30, (C, F, B))).astype(f32)
+            amp[rng.random((C, F, B)) < 0.02] = 0
+        freq = rng.uniform(-SR, SR, (C, F, B)).astype(f32)
+        a = np.stack([amp, freq], axis=-1)
+        a.setflags(write=False)
+        _FRAMES[key] = a
+    return _FRAMES[key]
+
+
+def guarded(shape):
+    """(int32 buffer of CANARY, float32 view of `shape` in its middle, 8-byte aligned and not 16, offset, floats)"""
+    n = int(np.prod(shape))
+    off = 1024 + 2
+    buf = torch.full((off + n + 1024 + 4,), CANARY, dtype=torch.int32, device=DEV)
+    data = buf[off:off + n].view(torch.float32).view(*shape)
+    assert data.data_ptr() % 16 == 8
+    return buf, data, off, n
+
+
+def intact(g):
+    buf, _, off, n = g
+    return bool((buf[:off] == CANARY).all()) and bool((buf[off + n:] == CANARY).all())
+
+
+def untouched(g):
+    return bool((g[0] == CANARY).all())
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def run(call, shape):
+    """a device call into a guarded output: the result as numpy, the guard bands checked, every element written"""
+    g = guarded(shape)
+    assert call(g[1]) == 0
+    torch.cuda.synchronize()
+    assert intact(g), "wrote outside the output"
+    out = g[1].cpu().numpy()
+    assert not (bits(out) == CANARY).any(), "an output element was not written"
+    return out
+
+
+def same(got, want, what):
+    """bit-equal where the model is a number, a NaN where it is a NaN"""
+    nan = np.isnan(want)
+    assert np.array_equal(np.isnan(got), nan), what + ": where the NaNs are"
+    assert np.array_equal(bits(got)[~nan], bits(want)[~nan]), what
+
+
+def frame_counts(size):
+    return [1, 5, fpw(size) + 1]
+
+
+POOL_P = np.array([0.6, 0.0, 1.0, -0.5, np.nan, 1.5, 0.25, 1.0, 0.0, 2.0 ** -20], f32)
+POOL_Q = np.array([-1.25, 1.0, 0.0, 0.4, 1.0, np.nan, -3.0, 0.0, 7.0, 1.0], f32)
+
+
+def per_frame(F, pool, seed=0):
+    """F per-frame values for the device form: 0, 1, negative, outside [0, 1] and a NaN among them as soon as F allows"""
+    v = np.random.default_rng(F + seed).uniform(-0.5, 1.5, F).astype(f32)
+    n = min(F, pool.size)
+    v[:n] = pool[:n]
+    return v
+
+
+def call_of(pv, op):
+    return {"cross": lambda a, b, o, p, q, **kw: pv.cross_device(a, b, o, p, q, **kw),
+            "morph": lambda a, b, o, p, q, **kw: pv.morph_device(a, b, o, p, q, **kw),
+            "filter": lambda a, b, o, p, q, **kw: pv.filter_device(a, b, o, p, q, **kw),
+            "mix": lambda a, b, o, p, q, **kw: pv.mix_device(a, b, o, **kw)}[op]
+
+
+def check_bits(pv, a, b, what):
+    """ops 0..3 on (a, b): bit-equal with the float32 model, with per-frame arrays and with plain numbers"""
+    size, F = pv.size, a.shape[1]
+    da, db = dev(a), dev(b)
+    p, q = per_frame(F, POOL_P), per_frame(F, POOL_Q)
+    for code, op in enumerate(OPS):
+        fn = call_of(pv, op)
+        got = run(lambda o: fn(da, db, o, dev(p), dev(q)), a.shape)
+        same(got, pp.pair32(code, a, b, p, q, size, SR), "%s: %s" % (what, op))
+        got = run(lambda o: fn(da, db, o, 0.7, 0.4), a.shape)
+        same(got, pp.pair32(code, a, b, 0.7, 0.4, size, SR), "%s: %s by numbers" % (what, op))
+        got = run(lambda o: fn(db, db, o, 1.0, 0.0), a.shape)       # the same tensor twice
+        same(got, pp.pair32(code, b, b, 1.0, 0.0, size, SR), "%s: %s of b with b" % (what, op))
+
+
+@pytest.mark.parametrize("channels", [1, 3])
+@pytest.mark.parametrize("size", [64, 1024])
+def test_cross_morph_filter_mix_are_the_models_bits(size, channels, monkeypatch):
+    pv = make(size, channels)
+    for F in frame_counts(size):
+        check_bits(pv, analysed(size, channels, F, 3), analysed(size, channels, F, 11), "size %d ch %d F %d analysed" % (size, channels, F))
+        check_bits(pv, raw(size, channels, F, 4), raw(size, channels, F, 12), "size %d ch %d F %d raw" % (size, channels, F))
+        check_bits(pv, analysed(size, channels, F, 3), raw(size, channels, F, 12), "size %d ch %d F %d mixed" % (size, channels, F))
+    # more items than the launched grid takes in one stride: launches of at most 2 workgroups
+    small = make(size, channels, grid_max=2, monkeypatch=monkeypatch)
+    check_bits(small, raw(size, channels, 7, 4), raw(size, channels, 7, 12), "size %d ch %d grid of 2" % (size, channels))
+
+
+def check_vocode(pv, a, b, coefs, what, call=None):
+    """freq bit-equal with b's, amps within MARGIN of the float32 model's error against float64; depths 1 and 0.6"""
+    size, F = pv.size, a.shape[1]
+    da, db = dev(a), dev(b)
+    depth = np.where(np.arange(F) % 2 == 0, f32(1), f32(0.6)).astype(f32)
+    gain = np.where(np.arange(F) % 3 == 1, f32(-0.8), f32(1.1)).astype(f32)
+    got = run(lambda o: pv.vocode_device(da, db, o, dev(depth), dev(gain), coefs=coefs), a.shape)
+    m32 = pp.pair32(pp.VOCODE, a, b, depth, gain, size, SR, coefs)
+    m64 = pp.vocode64_amps(a, b, depth, gain, size, SR, coefs)
+    assert np.isfinite(m32).all() and np.isfinite(m64).all(), "the inputs overflow the model"
+    assert np.array_equal(bits(got[..., 1]), bits(b[..., 1])), what + ": freq"
+    e_dev, e_f32 = om.rel_l2(got[..., 0], m64), om.rel_l2(m32[..., 0], m64)
+    ratio = e_dev / max(e_f32, 1e-300)
+    RATIO["max"] = max(RATIO["max"], ratio)
+    print("PVOCPAIR %s coefs %d: amps relL2 %.3g (float32 model %.3g, ratio %.2f; largest so far %.2f)"
+          % (what, coefs, e_dev, e_f32, ratio, RATIO["max"]))
+    assert e_dev <= MARGIN * e_f32, "%s: %.3g against %.3g" % (what, e_dev, e_f32)
+    return got
+
+
+@pytest.mark.parametrize("channels", [1, 3])
+@pytest.mark.parametrize("size", [64, 1024])
+def test_vocode_accuracy(size, channels, monkeypatch):
+    M = size // 2
+    pv = make(size, channels)
+    for F in frame_counts(size):
+        a, b = analysed(size, channels, F, 3), analysed(size, channels, F, 11)
+        for coefs in (1, min(24, M - 1), M - 1):
+            check_vocode(pv, a, b, coefs, "size %d ch %d F %d analysed" % (size, channels, F))
+        ta, tb = raw(size, channels, F, 5, tilt=True), raw(size, channels, F, 13, tilt=True)
+        for coefs in (1, min(24, M - 1), M - 1):
+            check_vocode(pv, ta, tb, coefs, "size %d ch %d F %d tilted" % (size, channels, F))
+    small = make(size, channels, grid_max=2, monkeypatch=monkeypatch)
+    F = (2 * fpw(size)) // channels + 3         # more than two groups of frames
+    a, b = analysed(size, channels, F, 3), analysed(size, channels, F, 11)
+    whole = check_vocode(pv, a, b, min(24, M - 1), "size %d ch %d F %d" % (size, channels, F))
+    capped = check_vocode(small, a, b, min(24, M - 1), "size %d ch %d F %d grid of 2" % (size, channels, F))
+    assert np.array_equal(bits(whole), bits(capped)), "the grid cap changed the result"
+
+
+def test_size_16384_once():
+    """the tables-from-cache route of k_pvoc_vocode, and the widest rows of k_pvoc_pair"""
+    size, C, F = 16384, 2, 3
+    pv = make(size, C)
+    a, b = analysed(size, C, F, 3), analysed(size, C, F, 11)
+    check_bits(pv, a, b, "size 16384")
+    check_vocode(pv, a, b, 80, "size 16384 analysed")
+    check_vocode(pv, raw(size, C, F, 5, tilt=True), raw(size, C, F, 13, tilt=True), 40, "size 16384 tilted")
+
+
+@pytest.mark.parametrize("size", [64, 1024])
+def test_confinement(size):
+    C, F = 2, fpw(size) + 1
+    M = size // 2
+    pv = make(size, C)
+    a, b = np.array(analysed(size, C, F, 3)), np.array(analysed(size, C, F, 11))
+    c0, f0, k0 = 1, F // 2, M // 3
+    # per-frame values that keep every op off its no-touch shortcuts: gains nonzero, weights and depths inside (0, 1)
+    p, q = np.full(F, 0.6, f32), np.full(F, 0.3, f32)
+    calls = [(code, lambda x, y, o, fn=call_of(pv, op): fn(dev(x), dev(y), o, dev(p), dev(q))) for code, op in enumerate(OPS)]
+    calls.append((pp.VOCODE, lambda x, y, o: pv.vocode_device(dev(x), dev(y), o, dev(p), dev(q), coefs=10)))
+    clean = {code: run(lambda o: call(a, b, o), a.shape) for code, call in calls}
+    for code in clean:
+        assert np.isfinite(clean[code]).all()
+    for side in ("a", "b"):
+        for bad_value in (np.nan, np.inf):
+            na, nb = a.copy(), b.copy()
+            (na if side == "a" else nb)[c0, f0, k0, 0] = bad_value
+            for code, call in calls:
+                got, ref = run(lambda o: call(na, nb, o), a.shape), clean[code].copy()
+                what = "op %d, %r in %s" % (code, bad_value, side)
+                assert not np.isnan(got[..., 1]).any(), what
+                hit = np.zeros((C, F, M + 1), bool)
+                hit[c0, f0, k0] = True
+                if np.isnan(bad_value):
+                    if code == pp.MIX:
+                        # the bin takes the pair of a: the clean pair for a NaN in b, the NaN and its freq for one in a
+                        want = hit if side == "a" else np.zeros_like(hit)
+                        assert np.array_equal(bits(got[c0, f0, k0, 1]), bits(a[c0, f0, k0, 1])), what
+                        assert side == "a" or np.array_equal(bits(got[c0, f0, k0]), bits(a[c0, f0, k0])), what
+                    elif code == pp.VOCODE and side == "a":
+                        # a's amps enter through envA alone, where a NaN takes the floor: no NaN comes out at all
+                        want = np.zeros_like(hit)
+                    else:
+                        want = hit
+                    assert np.array_equal(np.isnan(got[..., 0]), want), what + ": where the NaN went"
+                if code == pp.VOCODE:
+                    # the envelope belongs to the frame: a NaN takes its floor, so the frame's other bins stay finite; an
+                    # Inf may spoil its own frame; every other frame keeps its bits
+                    if np.isnan(bad_value):
+                        assert np.isfinite(got[c0, f0, np.arange(M + 1) != k0]).all(), what + ": the frame's other bins"
+                    got[c0, f0], ref[c0, f0] = 0, 0
+                else:
+                    got[c0, f0, k0], ref[c0, f0, k0] = 0, 0
+                assert np.array_equal(bits(got), bits(ref)), what + ": something else changed"
+
+
+def test_the_calls_are_stateless_and_repeatable():
+    size, C, F = 1024, 2, 11
+    M = size // 2
+    pv = make(size, C)
+    # states away from their initial values
+    spec = torch.view_as_complex(torch.randn((C, F, M, 2), device=DEV, generator=torch.Generator(device=DEV).manual_seed(1)))
+    fr = torch.zeros((C, F, M + 1, 2), device=DEV)
+    sp = torch.zeros_like(spec)
+    sig = torch.zeros((C, F * pv.hop), device=DEV)
+    assert pv.analyze_device(spec, fr) == 0 and pv.synthesize_device(fr, sp) == 0 and pv.adsyn_device(fr, sig) == 0
+    torch.cuda.synchronize()
+    state = (pv.read_prev(), pv.read_phase(), pv.adsyn_state())
+
+    def unchanged():
+        now = (pv.read_prev(), pv.read_phase(), pv.adsyn_state())
+        return (np.array_equal(bits(now[0]), bits(state[0])) and np.array_equal(now[1], state[1])
+                and all(np.array_equal(x.view(np.uint8), y.view(np.uint8)) for x, y in zip(now[2], state[2])))
+
+    fb = dev(analysed(size, C, F, 11))
+    hp, hq = per_frame(F, np.array([0.6, 0.0, 1.0, 0.3], f32)).clip(0, 1), per_frame(F, np.array([1.0, 0.0, 0.5], f32), 1).clip(0, 1)
+    p, q = dev(hp), dev(hq)
+    calls = [lambda o, st: pv.cross_device(fr, fb, o, p, q, stream=st), lambda o, st: pv.morph_device(fr, fb, o, p, q, stream=st),
+             lambda o, st: pv.filter_device(fr, fb, o, p, q, stream=st), lambda o, st: pv.mix_device(fr, fb, o, stream=st),
+             lambda o, st: pv.vocode_device(fr, fb, o, p, q, coefs=30, stream=st)]
+    first = []
+    for call in calls:
+        x, y = torch.zeros_like(fr), torch.zeros_like(fr)
+        assert call(x, None) == 0 and call(y, None) == 0
+        torch.cuda.synchronize()
+        assert torch.equal(x.view(torch.int32), y.view(torch.int32)), "the same call twice"
+        first.append(x)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    outs = [torch.zeros_like(fr) for _ in calls]
+    with torch.cuda.stream(side):
+        for call, o in zip(calls, outs):
+            assert call(o, None) == 0
+    torch.cuda.synchronize()
+    for x, o in zip(first, outs):
+        assert torch.equal(x.view(torch.int32), o.view(torch.int32)), "side stream"
+    # all five calls captured into one graph on one stream (none allocates), replayed twice
+    outs = [torch.zeros_like(fr) for _ in calls]
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for call, o in zip(calls, outs):
+            assert call(o, None) == 0
+    for _ in range(2):
+        for o in outs:
+            o.zero_()
+        g.replay()
+        torch.cuda.synchronize()
+        for x, o in zip(first, outs):
+            assert torch.equal(x.view(torch.int32), o.view(torch.int32)), "graph replay"
+    assert unchanged()
+    # the blocking forms are the device forms
+    ha, hb = fr.cpu().numpy(), fb.cpu().numpy()
+    host = [pv.cross(ha, hb, hp, hq), pv.morph(ha, hb, hp, hq), pv.filter(ha, hb, hp, hq), pv.mix(ha, hb),
+            pv.vocode(ha, hb, hp, hq, coefs=30)]
+    for i, (h, x) in enumerate(zip(host, first)):
+        assert np.array_equal(bits(h), bits(x.cpu().numpy())), "host form %d" % i
+    assert unchanged()
+
+
+def test_errors_write_nothing():
+    size, C, F = 64, 2, 5
+    M = size // 2
+    pv = make(size, C)
+    a, b = dev(analysed(size, C, F, 3)), dev(analysed(size, C, F, 11))
+    s = dev(np.full(F, 0.5, f32))
+    g = guarded((C, F, M + 1, 2))
+    out = g[1]
+    pair = [lambda x, y, o, p, q: pv.cross_device(x, y, o, p, q), lambda x, y, o, p, q: pv.morph_device(x, y, o, p, q),
+            lambda x, y, o, p, q: pv.filter_device(x, y, o, p, q), lambda x, y, o, p, q: pv.vocode_device(x, y, o, p, q, coefs=5)]
+    for coefs in (0, M, -3):
+        assert pv.vocode_device(a, b, out, s, s, coefs=coefs) == CL_INVALID_VALUE
+    # shapes, dtypes, strides
+    for call in pair:
+        assert call(a[:, :4].contiguous(), b, out, s, s) == CL_INVALID_VALUE
+        assert call(a, b[:, :4].contiguous(), out, s, s) == CL_INVALID_VALUE
+        assert call(a, b, out, s[:4].contiguous(), s) == CL_INVALID_VALUE
+        assert call(a, b, out, s, s.double()) == CL_INVALID_VALUE
+        assert call(a.double(), b, out, s, s) == CL_INVALID_VALUE
+        assert call(a, b.transpose(0, 1), out, s, s) == CL_INVALID_VALUE
+    assert pv.mix_device(a, b[:1], out) == CL_INVALID_VALUE and pv.mix_device(a.double(), b, out) == CL_INVALID_VALUE
+    torch.cuda.synchronize()
+    assert untouched(g)
+    # an output overlapping a, b, p or q, shifted by one pair
+    n = C * F * (M + 1) * 2
+    buf = torch.full((2 * n + F,), CANARY, dtype=torch.int32, device=DEV).view(torch.float32)
+    lo, hi = buf[:n].view(C, F, M + 1, 2), buf[n - 2:2 * n - 2].view(C, F, M + 1, 2)
+    par = buf[2 * n - 4:2 * n - 4 + F]
+    for call in pair:
+        assert call(lo, b, hi, s, s) == CL_INVALID_VALUE and call(a, hi, lo, s, s) == CL_INVALID_VALUE
+        assert call(lo, b, lo, s, s) == CL_INVALID_VALUE and call(a, lo, lo, s, s) == CL_INVALID_VALUE
+        assert call(a, b, hi, par, s) == CL_INVALID_VALUE and call(a, b, hi, s, par) == CL_INVALID_VALUE
+    assert pv.mix_device(lo, b, hi) == CL_INVALID_VALUE and pv.mix_device(a, hi, lo) == CL_INVALID_VALUE
+    torch.cuda.synchronize()
+    assert bool((buf.view(torch.int32) == CANARY).all())
+    # a and b being the same tensor, and p and q the same tensor, are accepted
+    for call in pair:
+        assert call(a, a, out, s, s) == 0
+    assert pv.mix_device(a, a, out) == 0
+    torch.cuda.synchronize()
+    assert intact(g) and np.array_equal(bits(out.cpu().numpy()), bits(a.cpu().numpy()))    # mix of a with itself
+    # F == 0: success, nothing happens
+    e = torch.zeros((C, 0, M + 1, 2), device=DEV)
+    for call in pair:
+        assert call(e, e.clone(), e.clone(), s[:0].contiguous(), s[:0].contiguous()) == 0
+    assert pv.mix_device(e, e.clone(), e.clone()) == 0
+
+
+def _band_db(y, lo, nfft, band):
+    """energy inside the band over the energy outside it, in dB, of the steady part of y"""
+    X = np.abs(np.fft.rfft(np.asarray(y[lo:lo + nfft], np.float64))) ** 2
+    hz = np.arange(X.size) * SR / nfft
+    inside = (hz >= band[0]) & (hz <= band[1])
+    return 10 * np.log10(X[inside].sum() / X[~inside].sum()), X
+
+
+def _model_chain(xa, xb, size, hop, coefs):
+    """Stft.analyze -> Pvoc.analyze of both -> vocode -> Pvoc.synthesize -> Stft.synthesize(normalize) on the numpy models"""
+    w = hann(size)
+    frames = []
+    for x in (xa, xb):
+        fr = stft_model.windowed_frames_f32(x[None], size, hop, w)
+        P = fa.onesided_to_packed(np.fft.rfft(fr.astype(np.float64), axis=-1)).astype(np.complex64)
+        frames.append(pm.analyze32(P, pm.initial_prev(1, size), size, hop, SR))
+    out = pp.pair32(pp.VOCODE, frames[0], frames[1], 1.0, 1.0, size, SR, coefs)
+    th, _ = pm.phases(out[..., 1], pm.initial_phase(1, size), hop, SR)
+    Q = pm.synth32(out, th)
+    r = np.fft.irfft(fa.packed_to_onesided(Q.astype(np.complex128)), n=size, axis=-1)
+    return stft_model.overlap_add(r, w, hop, normalize=True)[0][0]
+
+
+def test_end_to_end_the_vocoder_puts_a_band_on_a_harmonic_tone():
+    """a: noise filtered to 3 .. 6 kHz; b: 40 harmonics of 375 Hz (bin 64 of an 8192-point rfft), equal amplitudes.  The
+    vocoded tone keeps b's harmonics and takes a's band: the energy inside the band over the energy outside it is the
+    numpy model chain's, within 1 dB"""
+    size, hop, F, nfft, coefs = 1024, 256, 64, 8192, 30
+    n = size + (F - 1) * hop
+    band, h0 = (3000.0, 6000.0), 64
+    rng = np.random.default_rng(21)
+    N = np.fft.rfft(rng.standard_normal(n))
+    hz = np.arange(N.size) * SR / n
+    N[(hz < band[0]) | (hz > band[1])] = 0
+    xa = np.fft.irfft(N, n)
+    xa = (0.5 * xa / np.abs(xa).max()).astype(f32)
+    t = np.arange(n)
+    xb = (sum(np.cos(2 * np.pi * h * h0 / nfft * t + 0.3 * h) for h in range(1, 41)) / 40).astype(f32)
+    lo = 4 * size
+    want_db, _ = _band_db(_model_chain(xa, xb, size, hop, coefs), lo, nfft, band)
+    assert want_db > 10, "the models' chain puts the band on the tone"
+    an, sy, pv = fa.Stft(0, size, hop, window=hann(size)), fa.Stft(0, size, hop, window=hann(size), fwd=False), make(size, 1, hop)
+    fa_, fb_ = pv.analyze(an.analyze(xa[None])), None
+    pv.reset()
+    fb_ = pv.analyze(an.analyze(xb[None]))
+    y = sy.synthesize(pv.synthesize(pv.vocode(fa_, fb_, 1.0, 1.0, coefs=coefs)), normalize=True)[0]
+    got_db, X = _band_db(y, lo, nfft, band)
+    print("PVOCPAIR end to end: band over rest %.2f dB (model chain %.2f dB)" % (got_db, want_db))
+    assert abs(got_db - want_db) <= 1.0
+    # the harmonics inside the band sit where b's are: the largest bin around each multiple of 64 is that multiple
+    for h in range(9, 16):
+        k = h * h0
+        assert abs(int(np.argmax(X[k - 32:k + 32])) - 32) <= 1, h
+    peak = int(np.argmax(X))
+    assert min(peak % h0, h0 - peak % h0) <= 1 and band[0] <= peak * SR / nfft <= band[1]
