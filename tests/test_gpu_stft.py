@@ -34,7 +34,7 @@ def check_analysis(x, size, hop, w, spec):
     util.assert_parity(spec, want, what="stft size %d hop %d" % (size, hop))
 
 
-@pytest.mark.parametrize("size", [64, 256, 1024, 2048, 8192, 16384])
+@pytest.mark.parametrize("size", [64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384])
 @pytest.mark.parametrize("hopk", ["1", "3", "q", "h", "s"])
 def test_analysis_matches_rfft_of_windowed_frames(size, hopk):
     hop = {"1": 1, "3": 3, "q": size // 4, "h": size // 2, "s": size}[hopk]
