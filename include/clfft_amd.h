@@ -538,6 +538,66 @@ CLFA_API int clfa_pvoc_pair(clfa_pvoc *pv, int op, const float *frames_a, const 
 /* "k_pvoc_pair", "k_pvoc_vocode" for op 4 ("" for a failed object or an unknown op) */
 CLFA_API const char *clfa_pvoc_pair_kernel_name(const clfa_pvoc *pv, int op);
 
+/* ---- operations along a stream of (amp, freq) frames, with carried state: blur, smooth, freeze ---- */
+/* Csound's pvsblur, pvsmooth and pvsfreeze.  frames_in and frames_out: channels x F x (M + 1) x 2 float32 in the layout
+ * above, 8-byte aligned; p and q: F float32 each, one value per frame, shared by the channels, 4-byte aligned.  BLUR reads
+ * p only, and q may be NULL; SMOOTH and FREEZE need both, and they may be the same array.
+ *
+ * Each operation carries a state of its own from call to call, so that the results are the same bits however a stream is
+ * cut into calls; a captured call advances the state at every replay.  Each state is EMPTY (the frame operations' EMPTY
+ * bin, (0, fl(k cf))) in every bin at creation, after clfa_pvoc_reset, and (blur only) after clfa_pvoc_blur_setup.  prev,
+ * theta and the oscillator bank's state are never touched.  The rules of the frame operations above hold: no allocation
+ * in a device call, asynchronous on `stream`, one stream at a time, the current device left as found; F == 0 succeeds and
+ * does nothing.  Argument checks that need no device come first: on an object whose creation found no device a bad
+ * argument is still CLFA_INVALID_VALUE, a BLUR call before clfa_pvoc_blur_setup CLFA_INVALID_OPERATION, a good call the
+ * object's error.  An output that overlaps the input, p or q, even partly, is CLFA_INVALID_VALUE.  A failed call writes
+ * nothing and leaves every state bit for bit as it was.  The blocking form also checks the per-frame values.
+ *
+ * Every float32 operation is rounded on its own (no fused multiply-add); fl() marks a rounding.  An output value is a
+ * fixed sequence of such roundings of the stream's values: no parallel float sum or scan is used anywhere.
+ *
+ * BLUR    a moving average over the last n frames.  clfa_pvoc_blur_setup(pv, max_frames), 1 <= max_frames <= 4096, is
+ *         blocking, refused with CLFA_INVALID_OPERATION while the object's stream is being captured, allocates the history
+ *         of L = max_frames - 1 frames per channel and a spare of the same size, and may be called again (the history is
+ *         resized and reset).  The stream seen by frame f of a call is s = history ++ frames_in: s[L + f] is the call's
+ *         frame f.  n = 1 where p[f] >= 1 does not hold (a NaN included), otherwise
+ *         n = (int)floorf(fminf(p[f], (float)max_frames)); the blocking form demands p finite and 1 <= p[f] <= max_frames.
+ *         rn = (float)(1.0 / n), divided in double.  Per bin, for amp and for freq alike: S starts as the value of frame
+ *         L + f - n + 1 (the oldest), the later frames are added in ascending order, one rounded float32 addition each,
+ *         and out = fl(S rn); n = 1 returns the input's bits.  After the call the history is the last L frames of s.
+ * SMOOTH  a one-pole low-pass along the frames.  State y, one pair per channel and bin.  ca = clamp(p[f]),
+ *         cf = clamp(q[f]) (clamp as above: a NaN gives 0); amp = y.amp (bits) where ca == 0, x.amp (bits) where ca == 1,
+ *         otherwise fl(y.amp + fl(ca fl(x.amp - y.amp))); freq follows the same rule with cf (MORPH's rule); y := out.
+ *         The blocking form demands both arrays finite and in [0, 1].
+ * FREEZE  State held, one pair per channel and bin.  The amp column is frozen in frame f where p[f] != 0 (a NaN
+ *         freezes), the freq column where q[f] != 0.  out.amp = held.amp (bits) where frozen, else in.amp (bits); freq
+ *         follows the same rule; held := out.  Equivalently out.amp[f] = in.amp[g], g the last frame <= f of the stream
+ *         with p[g] == 0, or the EMPTY value if there is none since the reset.  The blocking form demands finite values.
+ * tests/pvoc_time_model.py restates all of it in numpy.
+ *
+ * clfa_pvoc_time_read_state (blocking): for BLUR the history, channels x L x (M + 1) x 2, oldest first (nothing is written
+ * for L = 0; CLFA_INVALID_OPERATION before the setup); for SMOOTH and FREEZE channels x (M + 1) x 2.
+ * clfa_pvoc_time_state_bytes: the device memory of the three states, the blur's spare included.
+ *
+ * Kernels: "k_pvoc_blur" (a lane per bin walks a run of consecutive frames and forms each sum in the defined order, O(n)
+ * additions per output; then the last L frames of s go into the spare, which is copied over the history),
+ * "k_pvoc_smooth" (a lane per channel and bin walks the call's frames, the loads of a group of frames in flight ahead of
+ * the recurrence), "k_pvoc_freeze" (a workgroup finds g of its run's first frame by searching p and q backwards, then walks
+ * forward; held is then taken from the output's last frame).  CLFA_PVOC_OPS_GRID_MAX caps the workgroups of all. */
+enum { CLFA_PVOC_BLUR = 0, CLFA_PVOC_SMOOTH = 1, CLFA_PVOC_FREEZE = 2 };
+CLFA_API int clfa_pvoc_blur_setup(clfa_pvoc *pv, int max_frames);
+CLFA_API int clfa_pvoc_time_dev(clfa_pvoc *pv, int op, const void *frames_in, void *frames_out, long F, const void *p,
+                                const void *q, void *stream);
+/* host arrays, copied in and out, blocking */
+CLFA_API int clfa_pvoc_time(clfa_pvoc *pv, int op, const float *frames_in, float *frames_out, long F, const float *p,
+                            const float *q);
+CLFA_API int clfa_pvoc_time_read_state(clfa_pvoc *pv, int op, float *host);
+CLFA_API size_t clfa_pvoc_time_state_bytes(const clfa_pvoc *pv);
+/* max_frames of the last successful setup, 0 before */
+CLFA_API int clfa_pvoc_blur_max_frames(const clfa_pvoc *pv);
+/* "k_pvoc_blur", "k_pvoc_smooth", "k_pvoc_freeze" ("" for a failed object or an unknown op) */
+CLFA_API const char *clfa_pvoc_time_kernel_name(const clfa_pvoc *pv, int op);
+
 /* ---- convolution matrix (extension: nothing of the reference's) ------------- */
 /* Uniformly partitioned overlap-add convolution of `inputs` signals with an outputs x inputs matrix of static responses:
  * y_o = sum over i of x_i * h_{o,i}.

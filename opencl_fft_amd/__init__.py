@@ -581,6 +581,102 @@ class Pvoc(_Handle):
         """host form of vocode_device, blocking; a depth outside [0, 1] raises ClError(CL_INVALID_VALUE)"""
         return self._pair_host(4, a, b, depth, gain, coefs, "Pvoc.vocode")
 
+    # ---- frames -> frames along the stream: blur, smooth, freeze (a carried state each; clfft_amd.h) ----
+
+    _TIME_OPS = {"blur": 0, "smooth": 1, "freeze": 2}
+
+    def _time_op(self, op):
+        return self._TIME_OPS.get(op, -1) if isinstance(op, str) else int(op)
+
+    def time_kernel_name(self, op):
+        """op "blur", "smooth", "freeze" (or 0..2) -> "k_pvoc_blur", "k_pvoc_smooth", "k_pvoc_freeze" ("" for a failed
+        object or an unknown op)"""
+        return lib().clfa_pvoc_time_kernel_name(self._h, self._time_op(op)).decode()
+
+    def time_state_bytes(self):
+        """device memory of the three carried states, the blur's spare included"""
+        return lib().clfa_pvoc_time_state_bytes(self._h)
+
+    def blur_setup(self, max_frames):
+        """allocates and resets the blur's history for windows of up to max_frames (1..4096) frames (blocking)"""
+        return lib().clfa_pvoc_blur_setup(self._h, int(max_frames))
+
+    def blur_max_frames(self):
+        """max_frames of the last blur_setup, 0 before"""
+        return lib().clfa_pvoc_blur_max_frames(self._h)
+
+    def time_state(self, op):
+        """the carried state of op "blur", "smooth" or "freeze" (blocking), float32: the blur's history (channels,
+        max_frames - 1, size/2 + 1, 2), oldest frame first; the smoothing's y and the freeze's held (channels, size/2 + 1, 2)"""
+        code = self._time_op(op)
+        shape = (self.channels, max(self.blur_max_frames() - 1, 0)) if code == 0 else (self.channels,)
+        out = np.zeros(shape + (self.M + 1, 2), np.float32)
+        check(lib().clfa_pvoc_time_read_state(self._h, code, out.ctypes.data), "Pvoc.time_state")
+        return out
+
+    def _time_device(self, op, frames_in, frames_out, p, q, stream):
+        """one device call along the frames; p, q: numbers or float32 device tensors (F,), q None for blur"""
+        import torch
+        F = self._frames_shape(frames_out.shape)
+        if F is None or any(self._frames_shape(t.shape) != F or t.dtype != torch.float32 or not t.is_contiguous()
+                            for t in (frames_in, frames_out)):
+            return CL_INVALID_VALUE
+        ptrs = []
+        for par in (p, q):
+            if par is not None:
+                par = self._per_frame(par, F, frames_out.device)
+                if par is None:
+                    return CL_INVALID_VALUE
+            ptrs.append(par)
+        return lib().clfa_pvoc_time_dev(self._h, op, frames_in.data_ptr(), frames_out.data_ptr(), F, ptrs[0].data_ptr(),
+                                        None if ptrs[1] is None else ptrs[1].data_ptr(), _stream_of(frames_out, stream))
+
+    def blur_device(self, frames_in, frames_out, length, stream=None):
+        """moving average along the frames (Csound's pvsblur): torch frames (channels, F, size/2 + 1, 2) float32 ->
+        frames_out of the same shape, each frame the mean of the stream's last n frames, n = length (a number or a
+        float32 device tensor (F,)) cut to whole frames, 1..max_frames of blur_setup.  The frames of earlier calls are
+        the object's history.  Asynchronous on `stream`."""
+        return self._time_device(0, frames_in, frames_out, length, None, stream)
+
+    def smooth_device(self, frames_in, frames_out, amp=0.5, freq=0.5, stream=None):
+        """one-pole low-pass along the frames (Csound's pvsmooth): y += w (x - y) per bin, for the amps with the weight
+        `amp`, for the freqs with `freq` (numbers or float32 device tensors (F,), clamped to [0, 1]; smooth_weight maps
+        Csound's cutoff to a weight).  y is carried from call to call."""
+        return self._time_device(1, frames_in, frames_out, amp, freq, stream)
+
+    def freeze_device(self, frames_in, frames_out, amp=0.0, freq=0.0, stream=None):
+        """freeze (Csound's pvsfreeze): where amp (freq) is not 0 in a frame, the amps (freqs) of the last frame of the
+        stream where it was 0 are held; numbers or float32 device tensors (F,)"""
+        return self._time_device(2, frames_in, frames_out, amp, freq, stream)
+
+    def _time_host(self, op, frames, p, q, what):
+        frames, F = self._host_frames(frames)
+        out = np.zeros(frames.shape, np.float32)
+        p, q = (None if x is None else self._per_frame_host(x, F) for x in (p, q))
+        check(lib().clfa_pvoc_time(self._h, op, frames.ctypes.data, out.ctypes.data, F, p.ctypes.data,
+                                   None if q is None else q.ctypes.data), what)
+        return out
+
+    def blur(self, frames, length):
+        """host form of blur_device, blocking: returns the new frames; a length outside 1..max_frames raises
+        ClError(CL_INVALID_VALUE)"""
+        return self._time_host(0, frames, length, None, "Pvoc.blur")
+
+    def smooth(self, frames, amp=0.5, freq=0.5):
+        """host form of smooth_device, blocking; a weight outside [0, 1] raises ClError(CL_INVALID_VALUE)"""
+        return self._time_host(1, frames, amp, freq, "Pvoc.smooth")
+
+    def freeze(self, frames, amp=0.0, freq=0.0):
+        """host form of freeze_device, blocking"""
+        return self._time_host(2, frames, amp, freq, "Pvoc.freeze")
+
+    @staticmethod
+    def smooth_weight(cutoff):
+        """Csound's pvsmooth cutoff (a fraction of half the frame rate) as the weight of smooth, in float64:
+        g = 2 - cos(pi cutoff), c = 1 + sqrt(g g - 1) - g"""
+        g = 2.0 - np.cos(np.pi * float(cutoff))
+        return float(1.0 + np.sqrt(g * g - 1.0) - g)
+
     # ---- frames -> samples: the oscillator bank (Csound's pvsadsyn; a state of its own; clfft_amd.h) ----
 
     def adsyn_kernel_name(self):

@@ -326,6 +326,26 @@ struct PvocPairArgs {
 // one launch: k_pvoc_pair, or k_pvoc_vocode<logn> for PVOC_VOCODE
 hipError_t launch_pvoc_pair(const PvocPairArgs &a, const DeviceInfo &di, hipStream_t s);
 
+// ---- operations along a stream of (amp, freq) frames, with carried state (pvoc_time.hip) ----
+enum PvocTimeOp { PVOC_BLUR = 0, PVOC_SMOOTH = 1, PVOC_FREEZE = 2 };   // CLFA_PVOC_*
+struct PvocTimeArgs {
+  int op = PVOC_BLUR;
+  int M = 0, channels = 0;
+  long F = 0;                      // frames per channel of in and out
+  const cpx *in = nullptr;         // frames as (amp, freq) pairs
+  cpx *out = nullptr;
+  const float *p = nullptr, *q = nullptr;   // F values each (blur: q is not read)
+  cpx *state = nullptr;            // blur: the history, channels x L frames, oldest first; smooth: y; freeze: held
+  cpx *spare = nullptr;            // blur: as the history
+  int max_frames = 1;              // blur: L = max_frames - 1
+  int grid_max = 0;                // > 0: at most this many workgroups
+};
+// the main launch, then what commits the state on the same stream: blur k_pvoc_tail into the spare and a copy of the
+// spare over the history, freeze k_pvoc_tail of the output's last frame into held; smooth commits in its own launch
+hipError_t launch_pvoc_time(const PvocTimeArgs &a, const DeviceInfo &di, hipStream_t s);
+// `frames` frames of EMPTY bins (cf = sr / size): what the three states start from
+hipError_t launch_pvoc_time_fill(cpx *dst, long frames, int M, float cf, hipStream_t s);
+
 // ---- direct convolution ----------------------------------------------------------
 struct DconvPlan {
   int C;    // taps per workgroup

@@ -1,6 +1,7 @@
-// pvoc_device.hpp — what the Pvoc kernel files share (pvoc_kernels.hip, pvoc_ops.hip, pvoc_adsyn.hip): the decoding of a
-// grid-stride item, the cap on a launch's workgroups, and the chunked scan that turns the per-chunk sums of phase
-// increments into the bases the chunks start from (k_pvoc_scan on uint32 words, k_adsyn_scan on uint64 ones).
+// pvoc_device.hpp — what the Pvoc kernel files share (pvoc_kernels.hip, pvoc_ops.hip, pvoc_pair.hip, pvoc_time.hip,
+// pvoc_adsyn.hip): the decoding of a grid-stride item, the cap on a launch's workgroups, the frame operations' EMPTY bin,
+// clamp and interpolation rule, and the chunked scan that turns the per-chunk sums of phase increments into the bases the
+// chunks start from (k_pvoc_scan on uint32 words, k_adsyn_scan on uint64 ones).
 #pragma once
 #include "internal.hpp"
 
@@ -20,6 +21,24 @@ __device__ __forceinline__ void pvoc_item(long item, int tiles, long inner, int 
 static inline int pvoc_grid(long items, long cap, int grid_max) {
   if (grid_max > 0 && cap > grid_max) cap = grid_max;
   return (int)(items < cap ? items : cap);
+}
+
+// an EMPTY bin of the frame operations: silent, at its bin centre (cf = sr / size)
+__device__ __forceinline__ cpx pvoc_empty(int j, float cf) {
+#pragma clang fp contract(off)
+  return mk(0.f, (float)j * cf);
+}
+
+__device__ __forceinline__ float pvoc_clamp01(float x) { return fminf(fmaxf(x, 0.f), 1.f); }   // fmaxf(NaN, 0) = 0
+
+// x0 where w == 0, x1 where w == 1 (the bits; the other side is not used), else fl(x0 + fl(w fl(x1 - x0))): the rule of
+// the morph (pvoc_pair.hip) and of the smoothing along the frames (pvoc_time.hip)
+__device__ __forceinline__ float pvoc_morph(float x0, float x1, float w) {
+#pragma clang fp contract(off)
+  const float d = x1 - x0;
+  const float s = w * d;
+  const float m = x0 + s;
+  return w == 0.f ? x0 : (w == 1.f ? x1 : m);
 }
 
 // The scan of one column (one bin of one channel) by the kScanSegs lanes that share `lane`: wave `seg` takes the chunks

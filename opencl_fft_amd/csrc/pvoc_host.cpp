@@ -35,6 +35,10 @@ struct clfa_pvoc {
   long acap = 1;
   int adsyn_grid_max = 0;
   DevBuf sfmod, ssig;
+  // the operations along the frames (pvoc_time.hip): the smoothing's y and the freeze's held, channels x (M + 1) pairs
+  // each; the blur's history of max_frames - 1 frames per channel and its spare (clfa_pvoc_blur_setup; blur_max 0 before)
+  DevBuf tsmooth, theld, bhist, bspare;
+  int blur_max = 0;
   StreamOrder order;
 };
 
@@ -63,7 +67,8 @@ static int pvoc_subbatches(long F, long held, Launch launch) {
   return CLFA_SUCCESS;
 }
 
-// the states as at creation: prev = (1, 0), theta = 0, the oscillator bank's P = W = A = 0 (on p->stream, blocking)
+// the states as at creation: prev = (1, 0), theta = 0, the oscillator bank's P = W = A = 0, EMPTY bins in the smoothing's
+// y, the freeze's held and the blur's history (on p->stream, blocking)
 static int pvoc_init_state(clfa_pvoc *p) {
   std::vector<cpx> one(pvoc_bins(p), mk(1.f, 0.f));
   HIP_TRY(hipMemcpyAsync(p->prev.p, one.data(), sizeof(cpx) * one.size(), hipMemcpyHostToDevice, p->stream));
@@ -71,6 +76,9 @@ static int pvoc_init_state(clfa_pvoc *p) {
   HIP_TRY(hipMemsetAsync(p->aphase.p, 0, sizeof(unsigned long long) * pvoc_bins(p), p->stream));
   HIP_TRY(hipMemsetAsync(p->aw.p, 0, sizeof(int) * pvoc_bins(p), p->stream));
   HIP_TRY(hipMemsetAsync(p->aamp.p, 0, sizeof(float) * pvoc_bins(p), p->stream));
+  HIP_TRY(launch_pvoc_time_fill((cpx *)p->tsmooth.p, p->channels, p->M, p->srs, p->stream));
+  HIP_TRY(launch_pvoc_time_fill((cpx *)p->theld.p, p->channels, p->M, p->srs, p->stream));
+  HIP_TRY(launch_pvoc_time_fill((cpx *)p->bhist.p, (long)p->channels * (p->blur_max > 0 ? p->blur_max - 1 : 0), p->M, p->srs, p->stream));
   HIP_TRY(hipStreamSynchronize(p->stream));
   return CLFA_SUCCESS;
 }
@@ -125,6 +133,7 @@ static int pvoc_setup(clfa_pvoc *p, int device, int size, int hop, double sr, in
   if ((e = p->aphase.ensure(sizeof(unsigned long long) * pvoc_bins(p))) || (e = p->aw.ensure(sizeof(int) * pvoc_bins(p))) ||
       (e = p->aamp.ensure(sizeof(float) * pvoc_bins(p))))
     return e;
+  if ((e = p->tsmooth.ensure(sizeof(cpx) * pvoc_bins(p))) || (e = p->theld.ensure(sizeof(cpx) * pvoc_bins(p)))) return e;
   return pvoc_init_state(p);
 }
 
@@ -470,6 +479,137 @@ int clfa_pvoc_pair(clfa_pvoc *p, int op, const float *frames_a, const float *fra
 const char *clfa_pvoc_pair_kernel_name(const clfa_pvoc *p, int op) {
   if (!p || p->err || op < PVOC_CROSS || op > PVOC_VOCODE) return "";
   return op == PVOC_VOCODE ? "k_pvoc_vocode" : "k_pvoc_pair";
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------
+// frames -> frames along the stream, with carried state: blur, smooth, freeze (pvoc_time.hip)
+// ---------------------------------------------------------------------------------
+
+// The checks that need no device, before the object's own error (as pvoc_ops_check).  0 = go on, 1 = a successful no-op,
+// < 0 = the error.  BLUR does not look at q.  Whether the blur has been set up is pvoc_time_ready's, after these (and, in
+// the blocking form, after the per-frame values).
+static int pvoc_time_check(const clfa_pvoc *p, int op, const void *in, const void *out, long F, const void *pp,
+                           const void *qq, bool device_ptrs) {
+  if (!p) return CLFA_INVALID_VALUE;
+  if (!p->M) return p->err ? p->err : CLFA_INVALID_VALUE;
+  if (op < PVOC_BLUR || op > PVOC_FREEZE) return CLFA_INVALID_VALUE;
+  if (!pvoc_count_ok(F)) return CLFA_INVALID_VALUE;
+  if (F == 0) return 1;
+  if (!in || !out || !pp || (op != PVOC_BLUR && !qq)) return CLFA_INVALID_VALUE;
+  if (op == PVOC_BLUR) qq = nullptr;
+  if (device_ptrs && (((uintptr_t)in & 7) || ((uintptr_t)out & 7) || ((uintptr_t)pp & 3) || ((uintptr_t)qq & 3)))
+    return CLFA_INVALID_VALUE;
+  const size_t fbytes = pvoc_frame_bytes(p, F), pbytes = sizeof(float) * (size_t)F;
+  if (spans_overlap(in, fbytes, out, fbytes) || spans_overlap(pp, pbytes, out, fbytes)) return CLFA_INVALID_VALUE;
+  if (qq && spans_overlap(qq, pbytes, out, fbytes)) return CLFA_INVALID_VALUE;
+  return CLFA_SUCCESS;
+}
+static int pvoc_time_ready(const clfa_pvoc *p, int op) {
+  return op == PVOC_BLUR && !p->blur_max ? CLFA_INVALID_OPERATION : CLFA_SUCCESS;
+}
+
+static DevBuf clfa_pvoc::*pvoc_time_state(int op) {
+  return op == PVOC_BLUR ? &clfa_pvoc::bhist : (op == PVOC_SMOOTH ? &clfa_pvoc::tsmooth : &clfa_pvoc::theld);
+}
+
+static int pvoc_time_dev(clfa_pvoc *p, int op, const void *in, void *out, long F, const void *pp, const void *qq,
+                         void *stream) {
+  int chk = pvoc_time_check(p, op, in, out, F, pp, qq, true);
+  if (chk == 0) chk = pvoc_time_ready(p, op);
+  if (int e = pvoc_gate(p, chk)) return pvoc_done(e);
+  ENTER_DEVICE(p->di.device);
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(p->order.use(s));
+  PvocTimeArgs a;
+  a.op = op;
+  a.M = p->M;
+  a.channels = p->channels;
+  a.F = F;
+  a.in = (const cpx *)in;
+  a.out = (cpx *)out;
+  a.p = (const float *)pp;
+  a.q = op == PVOC_BLUR ? nullptr : (const float *)qq;
+  a.state = (cpx *)(p->*pvoc_time_state(op)).p;
+  a.spare = (cpx *)p->bspare.p;
+  a.max_frames = p->blur_max;
+  a.grid_max = p->ops_grid_max;
+  HIP_TRY(launch_pvoc_time(a, p->di, s));
+  return CLFA_SUCCESS;
+}
+
+// the blocking form: the same checks on the host arrays, then the per-frame values, then copies around the device form
+static int pvoc_time_host(clfa_pvoc *p, int op, const float *in, float *out, long F, const float *pp, const float *qq) {
+  int chk = pvoc_time_check(p, op, in, out, F, pp, qq, false);
+  if (chk < 0) return chk;
+  for (long f = 0; f < F; f++) {
+    if (!std::isfinite(pp[f]) || (op != PVOC_BLUR && !std::isfinite(qq[f]))) return CLFA_INVALID_VALUE;
+    if (op == PVOC_BLUR && (!(pp[f] >= 1.f) || (p->blur_max && !(pp[f] <= (float)p->blur_max)))) return CLFA_INVALID_VALUE;
+    if (op == PVOC_SMOOTH && !(pp[f] >= 0.f && pp[f] <= 1.f && qq[f] >= 0.f && qq[f] <= 1.f)) return CLFA_INVALID_VALUE;
+  }
+  if (chk == 0) chk = pvoc_time_ready(p, op);
+  if (int e = pvoc_gate(p, chk)) return pvoc_done(e);
+  const bool blur = op == PVOC_BLUR;
+  const size_t fbytes = pvoc_frame_bytes(p, F), pbytes = sizeof(float) * (size_t)F;
+  return pvoc_staged(p, {{false, in, &p->sframes, fbytes}, {true, out, &p->sop_out, fbytes}, {false, pp, &p->sop_par, pbytes},
+                         {false, blur ? nullptr : qq, &p->spair_q, pbytes}}, [&] {
+                       return pvoc_time_dev(p, op, p->sframes.p, p->sop_out.p, F, p->sop_par.p, blur ? nullptr : p->spair_q.p,
+                                            p->stream);
+                     });
+}
+
+extern "C" {
+
+int clfa_pvoc_blur_setup(clfa_pvoc *p, int max_frames) {
+  if (!p) return CLFA_INVALID_VALUE;
+  if (!p->M) return p->err ? p->err : CLFA_INVALID_VALUE;
+  if (max_frames < 1 || max_frames > 4096) return CLFA_INVALID_VALUE;
+  if (p->err) return p->err;
+  ENTER_DEVICE(p->di.device);
+  if (int e = pvoc_quiesce(p)) return e;
+  // both buffers first, so that a failed allocation leaves the object as it was
+  const size_t bytes = pvoc_frame_bytes(p, max_frames - 1);
+  DevBuf hist, spare;
+  if (int e = hist.ensure(bytes)) return e;
+  if (int e = spare.ensure(bytes)) return e;
+  HIP_TRY(launch_pvoc_time_fill((cpx *)hist.p, (long)p->channels * (max_frames - 1), p->M, p->srs, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  std::swap(p->bhist.p, hist.p);
+  std::swap(p->bhist.bytes, hist.bytes);
+  std::swap(p->bspare.p, spare.p);
+  std::swap(p->bspare.bytes, spare.bytes);
+  p->blur_max = max_frames;
+  return CLFA_SUCCESS;
+}
+
+int clfa_pvoc_time_dev(clfa_pvoc *p, int op, const void *frames_in, void *frames_out, long F, const void *pp,
+                       const void *qq, void *stream) {
+  return pvoc_time_dev(p, op, frames_in, frames_out, F, pp, qq, stream);
+}
+int clfa_pvoc_time(clfa_pvoc *p, int op, const float *frames_in, float *frames_out, long F, const float *pp,
+                   const float *qq) {
+  return pvoc_time_host(p, op, frames_in, frames_out, F, pp, qq);
+}
+
+int clfa_pvoc_time_read_state(clfa_pvoc *p, int op, float *host) {
+  if (!p || op < PVOC_BLUR || op > PVOC_FREEZE || !host) return CLFA_INVALID_VALUE;
+  if (int e = obj_error(p)) return e;
+  if (int e = pvoc_time_ready(p, op)) return e;
+  ENTER_DEVICE(p->di.device);
+  if (int e = pvoc_quiesce(p)) return e;
+  const size_t bytes = pvoc_frame_bytes(p, op == PVOC_BLUR ? p->blur_max - 1 : 1);
+  if (bytes) HIP_TRY(hipMemcpy(host, (p->*pvoc_time_state(op)).p, bytes, hipMemcpyDeviceToHost));
+  return CLFA_SUCCESS;
+}
+
+size_t clfa_pvoc_time_state_bytes(const clfa_pvoc *p) {
+  return p ? p->tsmooth.bytes + p->theld.bytes + p->bhist.bytes + p->bspare.bytes : 0;
+}
+int clfa_pvoc_blur_max_frames(const clfa_pvoc *p) { return p ? p->blur_max : 0; }
+const char *clfa_pvoc_time_kernel_name(const clfa_pvoc *p, int op) {
+  if (!p || p->err || op < PVOC_BLUR || op > PVOC_FREEZE) return "";
+  return op == PVOC_BLUR ? "k_pvoc_blur" : (op == PVOC_SMOOTH ? "k_pvoc_smooth" : "k_pvoc_freeze");
 }
 
 }  // extern "C"

@@ -56,11 +56,6 @@ __device__ __forceinline__ int pvoc_source(int op, int j, int M, int lowest, flo
   return (k >= lowest && k <= M - 1) ? k : kSrcEmpty;
 }
 
-__device__ __forceinline__ cpx pvoc_empty(int j, float cf) {
-#pragma clang fp contract(off)
-  return mk(0.f, (float)j * cf);
-}
-
 // (amp, freq) of a bin that takes source sv; amp is the finished amplitude
 __device__ __forceinline__ cpx pvoc_moved(int op, cpx sv, float par, float amp) {
 #pragma clang fp contract(off)

@@ -24,17 +24,6 @@ namespace {
 
 constexpr int kPairWG = 256;   // lanes = bins per workgroup tile (k_pvoc_pair)
 
-__device__ __forceinline__ float pvoc_clamp01(float x) { return fminf(fmaxf(x, 0.f), 1.f); }   // fmaxf(NaN, 0) = 0
-
-// x0 where w == 0, x1 where w == 1 (the bits; the other side is not used), else fl(x0 + fl(w fl(x1 - x0)))
-__device__ __forceinline__ float pvoc_morph(float x0, float x1, float w) {
-#pragma clang fp contract(off)
-  const float d = x1 - x0;
-  const float s = w * d;
-  const float m = x0 + s;
-  return w == 0.f ? x0 : (w == 1.f ? x1 : m);
-}
-
 // one bin of ops 0..3
 __device__ __forceinline__ cpx pvoc_pair_bin(int op, cpx a, cpx b, float P, float Q) {
 #pragma clang fp contract(off)
