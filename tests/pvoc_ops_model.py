@@ -115,6 +115,17 @@ def env64(amp, coefs):
         return np.exp(logE).reshape(amp.shape)
 
 
+def env64_fft(amp, coefs):
+    """float64, by numpy's transforms: the same sums as env64 at any size (env64 builds (size x coefs) cosine matrices,
+    1 GB at size 16384 with every coefficient).  env64 stays the definition; this is the truth of the per-bin tests"""
+    amp = _in64(amp)
+    M = amp.shape[-1] - 1
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        P = np.fft.rfft(_ext(np.log(np.fmax(amp, FLOOR).astype(np.float64))), axis=-1)
+        P[..., coefs + 1:] = 0
+        return np.exp(np.fft.irfft(P, n=2 * M, axis=-1)[..., :M + 1])
+
+
 def _apply(frames, srcs, par, op, gain, cf, env, dtype):
     """srcs: (F, M + 1) source maps; par (F,); env: None or (C, F, M + 1) in `dtype`; amps in `dtype`, freqs in float32"""
     fr = _in64(frames) if dtype == np.float64 else np.asarray(frames, f32)

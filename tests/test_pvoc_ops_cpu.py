@@ -8,6 +8,7 @@ import pytest
 
 import opencl_fft_amd as fa
 from opencl_fft_amd import _lib
+from tests import pvoc_env_probe as ep
 from tests import pvoc_ops_model as om
 
 CL_INVALID_VALUE = -30
@@ -181,3 +182,80 @@ def test_argument_errors_come_before_the_device_lookup():
     with pytest.raises(fa.ClError) as e:
         pv.scale(fr, 5.0)
     assert e.value.code == CL_INVALID_VALUE
+
+
+# ---- the probe frames of the per-bin envelope tests (tests/pvoc_env_probe.py, tests/test_gpu_pvoc_env.py) ----
+
+def _log_env(env):
+    with np.errstate(divide="ignore"):
+        return np.log(np.asarray(env, np.float64))
+
+
+@pytest.mark.parametrize("size", [64, 256, 1024])
+def test_env64_fft_is_env64_on_the_probes(size):
+    """env64 (the cosine sums of the definition) stays the definition; env64_fft is what reaches size 16384"""
+    amp = ep.probe_for(size)[..., 0]
+    for coefs in ep.coefs_for(size):
+        d = np.abs(_log_env(om.env64_fft(amp, coefs)) - _log_env(om.env64(amp, coefs))).max()
+        assert d < 1e-11, (size, coefs, d)
+
+
+@pytest.mark.parametrize("size", ep.SIZES)
+def test_the_probes_are_as_specified(size):
+    M, T, w = size // 2, ep.lanes(size), ep.fpw(size)
+    C = ep.channels_for(size)
+    F = ep.frames_for(size, C)
+    fr = ep.probe(size, C, F)
+    assert fr.shape == (C, F, M + 1, 2) and fr.dtype == f32 and not fr.flags.writeable
+    assert F >= 40 and C * F >= 3 * w and (w == 1 or (C * F) % w != 0), "three full groups and a ragged one"
+    assert w == 1 or F % w != 0, "a group straddles the channel boundary"
+    assert ep.frames_for(64, 2) == 193 and ep.frames_for(16384, 2) == 40
+    assert np.isfinite(fr).all()
+    flat = fr.reshape(C * F, M + 1, 2)[..., 0]
+    # odd frames: the two constants alternately
+    assert all((flat[b] == (ep.HI if (b // 2) % 2 == 0 else ep.LO)).all() for b in range(1, C * F, 2))
+    # even frames: ones and one bin of 256, 1 / 256 or 0; every k0 of the list occurs, and every A
+    seen, amps = [], set()
+    for b in range(0, C * F, 2):
+        k = np.flatnonzero(flat[b] != 1)
+        assert k.size == 1
+        seen.append(int(k[0]))
+        amps.add(float(flat[b, k[0]]))
+    want = [0, 1, 2, 3, T - 1, T, T + 1, 15, 16, 17, M // 2 - 1, M // 2, M // 2 + 1, M - 3, M - 2, M - 1, M]
+    assert set(min(max(k, 0), M) for k in want) <= set(seen[:len(ep.k0_list(size))])
+    assert amps == {256.0, 1 / 256, 0.0}
+    cs = ep.coefs_for(size)
+    assert set(cs) == set(min(max(c, 1), M - 1) for c in [1, 2, T - 1, T, T + 1, M // 2 - 1, M // 2, M // 2 + 1, M - 2, M - 1])
+    assert len(cs) == len(set(cs))
+    for coefs in cs:
+        assert np.isfinite(om.env64_fft(flat, coefs)).all() and np.isfinite(om.env32(flat, coefs)).all(), coefs
+
+
+@pytest.mark.parametrize("size", ep.SIZES)
+def test_env32_of_an_all_ones_frame_is_exactly_one(size):
+    """log 1 = 0, the transforms of zeros are zeros, exp 0 = 1: what lets the device tests ask for 1.0 bits"""
+    ones = np.ones((2, size // 2 + 1), f32)
+    for coefs in ep.coefs_for(size):
+        assert np.array_equal(om.env32(ones, coefs).view(np.uint32), ones.view(np.uint32)), coefs
+
+
+@pytest.mark.parametrize("size", ep.SIZES)
+def test_the_probes_localise_a_misplaced_bin(size):
+    """An impulse of 256 moved by one bin changes log E by more than 1 somewhere as soon as coefs >= M / 2 - 1 (measured
+    on the float32 model: 1.7 .. 1.8 at M / 2 - 1, 5.2 .. 5.5 at M - 1, at every size), five orders above the per-bin
+    tolerance of the device tests.  The LOW coefs do not localise: at coefs 1 a move between inner bins changes log E by 6e-7 at size 16384, so
+    they pin the smooth part of the envelope only.  The high values of coefs_for are therefore the ones that find a bin
+    handled as its neighbour: do not trim them to save time."""
+    M = size // 2
+    ks = ep.k0_list(size)
+    here, moved = np.ones((len(ks), M + 1), f32), np.ones((len(ks), M + 1), f32)
+    for i, k in enumerate(ks):
+        here[i, k] = 256
+        moved[i, k + 1 if k < M else k - 1] = 256
+    for coefs in sorted(c for c in ep.coefs_for(size) if c >= M // 2 - 1):
+        d = np.abs(_log_env(om.env32(here, coefs)) - _log_env(om.env32(moved, coefs))).max(axis=-1)
+        assert d.min() > 1, (size, coefs, d.min())
+    if size == 16384:
+        inner = [i for i, k in enumerate(ks) if 1 <= k < M - 1]      # (a move across bin 0 or M changes the mean: 1e-3)
+        d = np.abs(_log_env(om.env32(here[inner], 1)) - _log_env(om.env32(moved[inner], 1))).max()
+        assert d < 1e-5, d
