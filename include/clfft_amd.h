@@ -538,6 +538,68 @@ CLFA_API int clfa_pvoc_pair(clfa_pvoc *pv, int op, const float *frames_a, const 
 /* "k_pvoc_pair", "k_pvoc_vocode" for op 4 ("" for a failed object or an unknown op) */
 CLFA_API const char *clfa_pvoc_pair_kernel_name(const clfa_pvoc *pv, int op);
 
+/* ---- operations that reshape one stream of (amp, freq) frames along the bins: band, mask, stencil, arp, lock, warp ---- */
+/* Csound's pvsbandp / pvsbandr, pvsmaska, pvstencil, pvsarp, pvslock and pvswarp.  frames_in and frames_out: channels x F x
+ * (M + 1) x 2 float32 in the layout above, 8-byte aligned.  par: F rows of 4 float32, one row per frame, shared by the
+ * channels, 4-byte aligned, required for every op; the columns an op does not name are not read.  table: M + 1 float32,
+ * one per bin, shared by channels and frames, 4-byte aligned; required for MASK and STENCIL, not read by the other ops
+ * (it may be NULL for them, and is not looked at).  flags: bit 0 = reject, BAND only; any other bit, or bit 0 on another
+ * op, is CLFA_INVALID_VALUE.  lowest_bin (1..M-1) and coefs (1..M-1) are used and checked for WARP only.
+ *
+ * The rules of the frame operations above hold: stateless (prev, theta, the oscillator bank's state and the states of the
+ * operations along the frames are never touched), no allocation in a device call (every call can be captured),
+ * asynchronous on `stream`, one stream at a time, the current device left as found; F == 0 succeeds and does nothing.
+ * Argument checks that need no device come first: on an object whose creation found no device a bad argument is still
+ * CLFA_INVALID_VALUE, a good one the object's error.  An output that overlaps the input, par or (MASK, STENCIL) table, even
+ * partly, is CLFA_INVALID_VALUE and writes nothing.  The blocking form also checks the per-frame values (the device form
+ * cannot): every value the op names finite; BAND 0 <= lc <= lf <= hf <= hc; depths and pos in [0, 1]; tol >= 0; s in
+ * [0.25, 4]; anything else is CLFA_INVALID_VALUE.
+ *
+ * Every float32 operation is rounded on its own (no fused multiply-add); fl() marks a rounding; a division is the correctly
+ * rounded one, denormals kept.  clamp(x) = fminf(fmaxf(x, 0), 1), so a NaN gives 0.  "bits" is the input's value copied
+ * unchanged.  Per channel, frame f and bin k = 0..M, with (amp, freq) the input's pair; every op copies the freq column as
+ * bits, except LOCK:
+ *   BAND     (pvsbandp; with reject, pvsbandr)  row (lc, lf, hf, hc) in Hz; x = fabsf(freq[k]); every bin alike.  The gain:
+ *            g = 0 where lc <= lf && lf <= hf && hf <= hc does not hold (NaNs included), and where x >= lc && x <= hc does
+ *            not hold; g = fl(fl(x - lc) / fl(lf - lc)) where x < lf; g = 1 where x <= hf; otherwise
+ *            g = fl(fl(hc - x) / fl(hc - hf)).  With reject g := fl(1 - g).  amp = bits where g == 1, +0 where g == 0 (the
+ *            input is not used, so a NaN stays out), otherwise fl(amp g).  Csound's exponential ramp is not offered.
+ *   MASK     (pvsmaska)  row (depth); d = clamp(depth); amp = bits where d == 0, otherwise fl(amp m),
+ *            m = fl(fl(1 - d) + fl(d table[k])).
+ *   STENCIL  (pvstencil)  row (gain, level); thr = fl(table[k] level); amp = fl(amp gain) where amp < thr, otherwise bits
+ *            (any comparison with a NaN is false).
+ *   ARP      (pvsarp)  row (pos, depth, gain); t = (int)floorf(fl(clamp(pos) (float)M)), m = fl(1 - clamp(depth));
+ *            amp = fl(amp gain) at k == t; elsewhere bits where m == 1, otherwise fl(amp m).
+ *   LOCK     (pvslock)  row (lock, tol) (Csound's tol is 0.01).  Where lock != 0 does not hold the frame is copied as bits
+ *            (a NaN locks, as in FREEZE).  Otherwise bin c is a PEAK iff 2 <= c <= M-2 and amp[c] is strictly greater than
+ *            amp[c-2], amp[c-1], amp[c+1] and amp[c+2] (a NaN makes a comparison false).  For output bin j in 1..M-1 the
+ *            candidate c is j+1 if that is a peak, else j-1 if that is a peak; with a candidate, Fc = freq[c],
+ *            d = fl(tol fabsf(Fc)), and freq = Fc (bits) where fabsf(fl(freq[j] - Fc)) < d, otherwise the bits of freq[j].
+ *            Amps are always bits; bins 0, M and every bin without a candidate are copied.  Two peaks are at least 3 bins
+ *            apart, so no bin neighbours two: the gather equals the serial loop over the peaks, in any order.
+ *   WARP     (pvswarp: the spectral envelope moves, the partials stay)  row (s, shift in Hz, gain).  env is the cepstral
+ *            envelope of the INPUT frame, exactly as defined above for keepform, with coefs.  t = fl(shift bpf),
+ *            d = (int)rintf(t); the frame is WARPED iff s is in [0.25, 4] and |t| <= M (a NaN fails either test).  Bins
+ *            0, M and j < lowest_bin are copied as bits.  For j in lowest_bin..M-1 of a warped frame with 1 <= j - d <= M-1
+ *            (the bins of the pitch scale's map that take a source), k is the pitch scale's source of bin j - d: the
+ *            largest k in 1..M-1 with floorf(fl(k s) + 0.5f) == j - d.  If there is such a k,
+ *            amp = fl(fl(fl(gain amp[j]) / env[j]) env[k]).  Every other such bin, and every such bin of a frame that is
+ *            not warped, has amp = fl(gain amp[j]).
+ * tests/pvoc_shape_model.py restates all of it in numpy.
+ *
+ * Kernels: "k_pvoc_shape" (ops 0..3: a lane per output bin, 8 bytes in and 8 out, no LDS), "k_pvoc_lock" (the same items;
+ * a locked frame's tile goes through LDS with a halo of 3 bins, a frame with lock == 0 is copied bin by bin),
+ * "k_pvoc_warp" (a workgroup holds whole frames in LDS and runs the envelope stages of k_pvoc_formant; one read and one
+ * write of the frame, no workspace).  One launch per call.  CLFA_PVOC_OPS_GRID_MAX caps the workgroups of all three. */
+enum { CLFA_PVOC_BAND = 0, CLFA_PVOC_MASK = 1, CLFA_PVOC_STENCIL = 2, CLFA_PVOC_ARP = 3, CLFA_PVOC_LOCK = 4, CLFA_PVOC_WARP = 5 };
+CLFA_API int clfa_pvoc_shape_dev(clfa_pvoc *pv, int op, const void *frames_in, void *frames_out, long F, const void *par,
+                                 const void *table, int flags, int lowest_bin, int coefs, void *stream);
+/* host arrays, copied in and out, blocking */
+CLFA_API int clfa_pvoc_shape(clfa_pvoc *pv, int op, const float *frames_in, float *frames_out, long F, const float *par,
+                             const float *table, int flags, int lowest_bin, int coefs);
+/* "k_pvoc_shape" for ops 0..3, "k_pvoc_lock", "k_pvoc_warp" ("" for a failed object or an unknown op) */
+CLFA_API const char *clfa_pvoc_shape_kernel_name(const clfa_pvoc *pv, int op);
+
 /* ---- operations along a stream of (amp, freq) frames, with carried state: blur, smooth, freeze ---- */
 /* Csound's pvsblur, pvsmooth and pvsfreeze.  frames_in and frames_out: channels x F x (M + 1) x 2 float32 in the layout
  * above, 8-byte aligned; p and q: F float32 each, one value per frame, shared by the channels, 4-byte aligned.  BLUR reads

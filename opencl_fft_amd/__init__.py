@@ -581,6 +581,112 @@ class Pvoc(_Handle):
         """host form of vocode_device, blocking; a depth outside [0, 1] raises ClError(CL_INVALID_VALUE)"""
         return self._pair_host(4, a, b, depth, gain, coefs, "Pvoc.vocode")
 
+    # ---- one stream of frames -> frames, along the bins: band, mask, stencil, arp, lock, warp (stateless; clfft_amd.h) ----
+
+    _SHAPE_OPS = {"band": 0, "mask": 1, "stencil": 2, "arp": 3, "lock": 4, "warp": 5}
+
+    def shape_kernel_name(self, op):
+        """op "band", "mask", "stencil", "arp" (or 0..3) -> "k_pvoc_shape", "lock" (4) -> "k_pvoc_lock", "warp" (5) ->
+        "k_pvoc_warp" ("" for a failed object or an unknown op)"""
+        code = self._SHAPE_OPS.get(op, -1) if isinstance(op, str) else int(op)
+        return lib().clfa_pvoc_shape_kernel_name(self._h, code).decode()
+
+    def _shape_device(self, op, frames_in, frames_out, cols, table, flags, lowest_bin, coefs, stream):
+        """one shaping device call; cols: the op's per-frame values (numbers or float32 device tensors (F,)), stacked
+        into the (F, 4) rows the library reads; table: None or a float32 device tensor (size/2 + 1,)"""
+        import torch
+        F = self._frames_shape(frames_out.shape)
+        if F is None or any(self._frames_shape(t.shape) != F or t.dtype != torch.float32 or not t.is_contiguous()
+                            for t in (frames_in, frames_out)):
+            return CL_INVALID_VALUE
+        rows = torch.zeros((F, 4), dtype=torch.float32, device=frames_out.device)
+        for i, par in enumerate(cols):
+            if hasattr(par, "data_ptr"):
+                par = self._per_frame(par, F, frames_out.device)
+                if par is None:
+                    return CL_INVALID_VALUE
+                rows[:, i] = par
+            else:
+                rows[:, i] = float(par)
+        if table is not None and (not hasattr(table, "data_ptr") or table.dtype != torch.float32
+                                  or tuple(table.shape) != (self.M + 1,) or not table.is_contiguous()):
+            return CL_INVALID_VALUE
+        return lib().clfa_pvoc_shape_dev(self._h, op, frames_in.data_ptr(), frames_out.data_ptr(), F, rows.data_ptr(),
+                                         None if table is None else table.data_ptr(), int(flags), int(lowest_bin),
+                                         int(coefs), _stream_of(frames_out, stream))
+
+    def band_device(self, frames_in, frames_out, lowcut, lowfull, highfull, highcut, reject=False, stream=None):
+        """band pass (Csound's pvsbandp; reject: the band reject pvsbandr): torch frames (channels, F, size/2 + 1, 2)
+        float32 -> frames_out of the same shape, the amps times a gain that rises from 0 at lowcut to 1 at lowfull, stays
+        1 up to highfull and falls to 0 at highcut (Hz, against each bin's |freq|; numbers or float32 device tensors
+        (F,)).  frames_out may not overlap frames_in.  Asynchronous on `stream`."""
+        return self._shape_device(0, frames_in, frames_out, (lowcut, lowfull, highfull, highcut), None,
+                                  int(bool(reject)), 1, 1, stream)
+
+    def mask_device(self, frames_in, frames_out, table, depth=1.0, stream=None):
+        """table mask (Csound's pvsmaska): the amps times (1 - depth) + depth table[k]; table: float32 device tensor
+        (size/2 + 1,), depth clamped to [0, 1]"""
+        return self._shape_device(1, frames_in, frames_out, (depth,), table, 0, 1, 1, stream)
+
+    def stencil_device(self, frames_in, frames_out, table, gain=0.0, level=1.0, stream=None):
+        """stencil (Csound's pvstencil): the amps below table[k] level are multiplied by gain, the others kept"""
+        return self._shape_device(2, frames_in, frames_out, (gain, level), table, 0, 1, 1, stream)
+
+    def arp_device(self, frames_in, frames_out, pos, depth=1.0, gain=1.0, stream=None):
+        """spectral arpeggiator (Csound's pvsarp): the bin at pos (0..1 of the bins 0..size/2) is multiplied by gain,
+        every other bin by 1 - depth"""
+        return self._shape_device(3, frames_in, frames_out, (pos, depth, gain), None, 0, 1, 1, stream)
+
+    def lock_device(self, frames_in, frames_out, lock=1.0, tol=0.01, stream=None):
+        """peak frequency lock (Csound's pvslock): in a frame with lock != 0, the bins next to a spectral peak take the
+        peak's freq where theirs lies within tol |freq| of it"""
+        return self._shape_device(4, frames_in, frames_out, (lock, tol), None, 0, 1, 1, stream)
+
+    def warp_device(self, frames_in, frames_out, scale, shift=0.0, lowest_bin=1, gain=1.0, coefs=80, stream=None):
+        """envelope warp (Csound's pvswarp): the spectral envelope (cepstral, `coefs` coefficients) of the bins from
+        lowest_bin up is scaled by `scale` (in [0.25, 4]) and shifted by `shift` Hz, the partials stay where they are"""
+        return self._shape_device(5, frames_in, frames_out, (scale, shift, gain), None, 0, lowest_bin, coefs, stream)
+
+    def _shape_host(self, op, frames, cols, table, flags, lowest_bin, coefs, what):
+        frames, F = self._host_frames(frames)
+        out = np.zeros(frames.shape, np.float32)
+        rows = np.zeros((F, 4), np.float32)
+        for i, par in enumerate(cols):
+            rows[:, i] = self._per_frame_host(par, F)
+        if table is not None:
+            table = np.ascontiguousarray(table, dtype=np.float32)
+            if table.shape != (self.M + 1,):
+                raise ValueError("table must be (%d,)" % (self.M + 1))
+        check(lib().clfa_pvoc_shape(self._h, op, frames.ctypes.data, out.ctypes.data, F, rows.ctypes.data,
+                                    None if table is None else table.ctypes.data, int(flags), int(lowest_bin),
+                                    int(coefs)), what)
+        return out
+
+    def band(self, frames, lowcut, lowfull, highfull, highcut, reject=False):
+        """host form of band_device, blocking: returns the new frames; edges that are not finite or not in the order
+        0 <= lowcut <= lowfull <= highfull <= highcut raise ClError(CL_INVALID_VALUE)"""
+        return self._shape_host(0, frames, (lowcut, lowfull, highfull, highcut), None, int(bool(reject)), 1, 1, "Pvoc.band")
+
+    def mask(self, frames, table, depth=1.0):
+        """host form of mask_device, blocking; a depth outside [0, 1] raises ClError(CL_INVALID_VALUE)"""
+        return self._shape_host(1, frames, (depth,), table, 0, 1, 1, "Pvoc.mask")
+
+    def stencil(self, frames, table, gain=0.0, level=1.0):
+        """host form of stencil_device, blocking"""
+        return self._shape_host(2, frames, (gain, level), table, 0, 1, 1, "Pvoc.stencil")
+
+    def arp(self, frames, pos, depth=1.0, gain=1.0):
+        """host form of arp_device, blocking; a pos or depth outside [0, 1] raises ClError(CL_INVALID_VALUE)"""
+        return self._shape_host(3, frames, (pos, depth, gain), None, 0, 1, 1, "Pvoc.arp")
+
+    def lock(self, frames, lock=1.0, tol=0.01):
+        """host form of lock_device, blocking; a negative tol raises ClError(CL_INVALID_VALUE)"""
+        return self._shape_host(4, frames, (lock, tol), None, 0, 1, 1, "Pvoc.lock")
+
+    def warp(self, frames, scale, shift=0.0, lowest_bin=1, gain=1.0, coefs=80):
+        """host form of warp_device, blocking; a scale outside [0.25, 4] raises ClError(CL_INVALID_VALUE)"""
+        return self._shape_host(5, frames, (scale, shift, gain), None, 0, lowest_bin, coefs, "Pvoc.warp")
+
     # ---- frames -> frames along the stream: blur, smooth, freeze (a carried state each; clfft_amd.h) ----
 
     _TIME_OPS = {"blur": 0, "smooth": 1, "freeze": 2}

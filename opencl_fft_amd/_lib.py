@@ -129,6 +129,9 @@ SYMBOLS = [
     ("clfa_pvoc_pair_dev", C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_long, _vp, _vp, C.c_int, _vp]),
     ("clfa_pvoc_pair", C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_long, _vp, _vp, C.c_int]),
     ("clfa_pvoc_pair_kernel_name", C.c_char_p, [_vp, C.c_int]),
+    ("clfa_pvoc_shape_dev", C.c_int, [_vp, C.c_int, _vp, _vp, C.c_long, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
+    ("clfa_pvoc_shape", C.c_int, [_vp, C.c_int, _vp, _vp, C.c_long, _vp, _vp, C.c_int, C.c_int, C.c_int]),
+    ("clfa_pvoc_shape_kernel_name", C.c_char_p, [_vp, C.c_int]),
     ("clfa_pvoc_blur_setup", C.c_int, [_vp, C.c_int]),
     ("clfa_pvoc_time_dev", C.c_int, [_vp, C.c_int, _vp, _vp, C.c_long, _vp, _vp, _vp]),
     ("clfa_pvoc_time", C.c_int, [_vp, C.c_int, _vp, _vp, C.c_long, _vp, _vp]),

@@ -326,6 +326,26 @@ struct PvocPairArgs {
 // one launch: k_pvoc_pair, or k_pvoc_vocode<logn> for PVOC_VOCODE
 hipError_t launch_pvoc_pair(const PvocPairArgs &a, const DeviceInfo &di, hipStream_t s);
 
+// ---- operations that reshape one stream of (amp, freq) frames along the bins (pvoc_shape.hip) ----
+enum PvocShapeOp { PVOC_BAND = 0, PVOC_MASK = 1, PVOC_STENCIL = 2, PVOC_ARP = 3, PVOC_LOCK = 4, PVOC_WARP = 5 };   // CLFA_PVOC_*
+struct PvocShapeArgs {
+  int op = PVOC_BAND;
+  int logn = 0;                    // log2(M): the warp's transform length (complex)
+  int M = 0, channels = 0;
+  long F = 0;                      // frames per channel of in and out
+  const cpx *in = nullptr;         // frames as (amp, freq) pairs
+  cpx *out = nullptr;
+  const float *par = nullptr;      // F rows of 4 values
+  const float *table = nullptr;    // M + 1 values (mask, stencil; the others do not read it)
+  int reject = 0;                  // band
+  int lowest = 1, coefs = 1;       // warp
+  float bpf = 0.f;                 // size / sr
+  const cpx *half = nullptr, *w2 = nullptr;   // warp: the Clrfft tables of size (forward sign)
+  int grid_max = 0;                // > 0: at most this many workgroups
+};
+// one launch: k_pvoc_shape (ops 0..3), k_pvoc_lock or k_pvoc_warp<logn>
+hipError_t launch_pvoc_shape(const PvocShapeArgs &a, const DeviceInfo &di, hipStream_t s);
+
 // ---- operations along a stream of (amp, freq) frames, with carried state (pvoc_time.hip) ----
 enum PvocTimeOp { PVOC_BLUR = 0, PVOC_SMOOTH = 1, PVOC_FREEZE = 2 };   // CLFA_PVOC_*
 struct PvocTimeArgs {

@@ -1,7 +1,8 @@
 // pvoc_device.hpp — what the Pvoc kernel files share (pvoc_kernels.hip, pvoc_ops.hip, pvoc_pair.hip, pvoc_time.hip,
-// pvoc_adsyn.hip): the decoding of a grid-stride item, the cap on a launch's workgroups, the frame operations' EMPTY bin,
-// clamp and interpolation rule, and the chunked scan that turns the per-chunk sums of phase increments into the bases the
-// chunks start from (k_pvoc_scan on uint32 words, k_adsyn_scan on uint64 ones).
+// pvoc_shape.hip, pvoc_adsyn.hip): the decoding of a grid-stride item, the cap on a launch's workgroups, the frame
+// operations' EMPTY bin, clamp and interpolation rule, the pitch scale's source map (pvoc_ops.hip's k_pvoc_map and
+// k_pvoc_formant, pvoc_shape.hip's k_pvoc_warp), and the chunked scan that turns the per-chunk sums of phase
+// increments into the bases the chunks start from (k_pvoc_scan on uint32 words, k_adsyn_scan on uint64 ones).
 #pragma once
 #include "internal.hpp"
 
@@ -30,6 +31,29 @@ __device__ __forceinline__ cpx pvoc_empty(int j, float cf) {
 }
 
 __device__ __forceinline__ float pvoc_clamp01(float x) { return fminf(fmaxf(x, 0.f), 1.f); }   // fmaxf(NaN, 0) = 0
+
+constexpr int kSrcEmpty = -1, kSrcCopy = -2;   // what a frame operation's source map answers besides a bin
+
+// the pitch scale's map k -> j
+__device__ __forceinline__ int pvoc_scale_j(int k, float s) {
+#pragma clang fp contract(off)
+  const float t = (float)k * s;
+  return (int)floorf(t + 0.5f);
+}
+
+// The pitch scale's source of bin j, 1 <= j <= M-1: k in 1..M-1, or kSrcEmpty (also for s outside [1/4, 4] or a NaN).
+// k -> j is monotone, so the source — the last k of the serial definition — is the largest k with j(k) <= j if that k
+// lands on j; it lies next to (j + 1/2) / s, and the two loops move the estimate there (a few steps: s >= 1/4).
+// Shared by the scale map (pvoc_ops.hip) and the envelope warp (pvoc_shape.hip).
+__device__ __forceinline__ int pvoc_scale_source(int j, int M, float s) {
+#pragma clang fp contract(off)
+  if (!(s >= 0.25f && s <= 4.f)) return kSrcEmpty;
+  int k = (int)(((float)j + 0.5f) / s);
+  k = k < 1 ? 1 : (k > M - 1 ? M - 1 : k);
+  while (k < M - 1 && pvoc_scale_j(k + 1, s) <= j) k++;
+  while (k >= 1 && pvoc_scale_j(k, s) > j) k--;
+  return (k >= 1 && pvoc_scale_j(k, s) == j) ? k : kSrcEmpty;
+}
 
 // x0 where w == 0, x1 where w == 1 (the bits; the other side is not used), else fl(x0 + fl(w fl(x1 - x0))): the rule of
 // the morph (pvoc_pair.hip) and of the smoothing along the frames (pvoc_time.hip)

@@ -1,6 +1,7 @@
 // pvoc_env.hpp — the cepstral envelope of (amp, freq) frames held in LDS (env of include/clfft_amd.h), shared by
-// k_pvoc_formant (pvoc_ops.hip) and k_pvoc_vocode (pvoc_pair.hip).  A workgroup of LdsGeom<LOGN>::WG lanes works
-// FPW = LdsGeom::FPW frames of B = N + 1 bins at once (N = M = size / 2), frame fi in slot fi of the exchange buffer:
+// k_pvoc_formant (pvoc_ops.hip), k_pvoc_vocode (pvoc_pair.hip) and k_pvoc_warp (pvoc_shape.hip).  A workgroup of
+// LdsGeom<LOGN>::WG lanes works FPW = LdsGeom::FPW frames of B = N + 1 bins at once (N = M = size / 2), frame fi in
+// slot fi of the exchange buffer:
 //   (1) L[k] = logf(fmaxf(amp[k], 1e-20f)) lands at samples k and size - k of the slot: the even extension Lext;
 //   (2) the packed forward real transform of Lext on the pass chain of k_stft_analyze, scaled by 1 / N;
 //   (3) the pair step: forward pair map, zeros above coefs and in the Nyquist half of bin 0, inverse pair map, in one

@@ -27,6 +27,7 @@ struct clfa_pvoc {
   int ops_grid_max = 0;
   DevBuf sop_out, sop_par;
   DevBuf spair_b, spair_q;   // the two-input operations (pvoc_pair.hip): staging of the second input and per-frame array
+  DevBuf sshape_tab;         // the shaping operations (pvoc_shape.hip): staging of the table (their rows go to sop_par)
   // the oscillator bank (pvoc_adsyn.hip): 1 / sr, its state per channel and bin (P uint64, W int32, A float32), the ramp
   // w_j, its own workspace (the 64-bit chunk sums of one sub-batch, then the endpoints a sub-batch starts from), the
   // chunks per sub-batch, the cap on its workgroups (CLFA_PVOC_ADSYN_GRID_MAX, 0 = none), staging of the host form
@@ -479,6 +480,112 @@ int clfa_pvoc_pair(clfa_pvoc *p, int op, const float *frames_a, const float *fra
 const char *clfa_pvoc_pair_kernel_name(const clfa_pvoc *p, int op) {
   if (!p || p->err || op < PVOC_CROSS || op > PVOC_VOCODE) return "";
   return op == PVOC_VOCODE ? "k_pvoc_vocode" : "k_pvoc_pair";
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------
+// one stream of frames -> frames, along the bins: band, mask, stencil, arp, lock, warp (pvoc_shape.hip)
+// ---------------------------------------------------------------------------------
+
+static bool pvoc_shape_table(int op) { return op == PVOC_MASK || op == PVOC_STENCIL; }
+
+// The checks that need no device, before the object's own error (as pvoc_ops_check).  0 = go on, 1 = a successful no-op,
+// < 0 = the error.  The table is looked at for MASK and STENCIL only.
+static int pvoc_shape_check(const clfa_pvoc *p, int op, const void *in, const void *out, long F, const void *par,
+                            const void *table, int flags, int lowest, int coefs, bool device_ptrs) {
+  if (!p) return CLFA_INVALID_VALUE;
+  if (!p->M) return p->err ? p->err : CLFA_INVALID_VALUE;
+  if (op < PVOC_BAND || op > PVOC_WARP) return CLFA_INVALID_VALUE;
+  if (!pvoc_count_ok(F)) return CLFA_INVALID_VALUE;
+  if (flags & ~(op == PVOC_BAND ? 1 : 0)) return CLFA_INVALID_VALUE;
+  if (op == PVOC_WARP && (lowest < 1 || lowest > p->M - 1 || coefs < 1 || coefs >= p->M)) return CLFA_INVALID_VALUE;
+  if (F == 0) return 1;
+  if (!in || !out || !par) return CLFA_INVALID_VALUE;
+  if (!pvoc_shape_table(op)) table = nullptr;
+  else if (!table) return CLFA_INVALID_VALUE;
+  if (device_ptrs && (((uintptr_t)in & 7) || ((uintptr_t)out & 7) || ((uintptr_t)par & 3) || ((uintptr_t)table & 3)))
+    return CLFA_INVALID_VALUE;
+  const size_t fbytes = pvoc_frame_bytes(p, F), pbytes = 4 * sizeof(float) * (size_t)F;
+  if (spans_overlap(in, fbytes, out, fbytes) || spans_overlap(par, pbytes, out, fbytes)) return CLFA_INVALID_VALUE;
+  if (table && spans_overlap(table, sizeof(float) * (size_t)(p->M + 1), out, fbytes)) return CLFA_INVALID_VALUE;
+  return CLFA_SUCCESS;
+}
+
+static int pvoc_shape_dev(clfa_pvoc *p, int op, const void *in, void *out, long F, const void *par, const void *table,
+                          int flags, int lowest, int coefs, void *stream) {
+  if (int e = pvoc_gate(p, pvoc_shape_check(p, op, in, out, F, par, table, flags, lowest, coefs, true))) return pvoc_done(e);
+  ENTER_DEVICE(p->di.device);
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(p->order.use(s));
+  PvocShapeArgs a;
+  a.op = op;
+  a.logn = ilog2(p->M);
+  a.M = p->M;
+  a.channels = p->channels;
+  a.F = F;
+  a.in = (const cpx *)in;
+  a.out = (cpx *)out;
+  a.par = (const float *)par;
+  a.table = pvoc_shape_table(op) ? (const float *)table : nullptr;
+  a.reject = flags & 1;
+  a.lowest = lowest;
+  a.coefs = coefs;
+  a.bpf = p->bpf;
+  a.half = (const cpx *)p->half.p;
+  a.w2 = (const cpx *)p->w2.p;
+  a.grid_max = p->ops_grid_max;
+  HIP_TRY(launch_pvoc_shape(a, p->di, s));
+  return CLFA_SUCCESS;
+}
+
+// the values of one row the blocking form accepts: those the op names finite, and the op's ranges
+static bool pvoc_shape_row_ok(int op, const float *r) {
+  static const int cols[] = {4, 1, 2, 3, 2, 3};
+  for (int i = 0; i < cols[op]; i++)
+    if (!std::isfinite(r[i])) return false;
+  const auto unit = [](float x) { return x >= 0.f && x <= 1.f; };
+  switch (op) {
+    case PVOC_BAND: return 0.f <= r[0] && r[0] <= r[1] && r[1] <= r[2] && r[2] <= r[3];
+    case PVOC_MASK: return unit(r[0]);
+    case PVOC_ARP: return unit(r[0]) && unit(r[1]);
+    case PVOC_LOCK: return r[1] >= 0.f;
+    case PVOC_WARP: return r[0] >= 0.25f && r[0] <= 4.f;
+    default: return true;   // STENCIL: gain and level are free
+  }
+}
+
+// the blocking form: the same checks on the host arrays, then the per-frame values, then copies around the device form
+static int pvoc_shape_host(clfa_pvoc *p, int op, const float *in, float *out, long F, const float *par, const float *table,
+                           int flags, int lowest, int coefs) {
+  const int chk = pvoc_shape_check(p, op, in, out, F, par, table, flags, lowest, coefs, false);
+  if (chk < 0) return chk;
+  for (long f = 0; f < F; f++)
+    if (!pvoc_shape_row_ok(op, par + 4 * f)) return CLFA_INVALID_VALUE;
+  if (int e = pvoc_gate(p, chk)) return pvoc_done(e);
+  const bool tab = pvoc_shape_table(op);
+  const size_t fbytes = pvoc_frame_bytes(p, F);
+  return pvoc_staged(p, {{false, in, &p->sframes, fbytes}, {true, out, &p->sop_out, fbytes},
+                         {false, par, &p->sop_par, 4 * sizeof(float) * (size_t)F},
+                         {false, tab ? table : nullptr, &p->sshape_tab, sizeof(float) * (size_t)(p->M + 1)}}, [&] {
+                       return pvoc_shape_dev(p, op, p->sframes.p, p->sop_out.p, F, p->sop_par.p, tab ? p->sshape_tab.p : nullptr,
+                                             flags, lowest, coefs, p->stream);
+                     });
+}
+
+extern "C" {
+
+int clfa_pvoc_shape_dev(clfa_pvoc *p, int op, const void *frames_in, void *frames_out, long F, const void *par,
+                        const void *table, int flags, int lowest_bin, int coefs, void *stream) {
+  return pvoc_shape_dev(p, op, frames_in, frames_out, F, par, table, flags, lowest_bin, coefs, stream);
+}
+int clfa_pvoc_shape(clfa_pvoc *p, int op, const float *frames_in, float *frames_out, long F, const float *par,
+                    const float *table, int flags, int lowest_bin, int coefs) {
+  return pvoc_shape_host(p, op, frames_in, frames_out, F, par, table, flags, lowest_bin, coefs);
+}
+const char *clfa_pvoc_shape_kernel_name(const clfa_pvoc *p, int op) {
+  if (!p || p->err || op < PVOC_BAND || op > PVOC_WARP) return "";
+  return op == PVOC_WARP ? "k_pvoc_warp" : (op == PVOC_LOCK ? "k_pvoc_lock" : "k_pvoc_shape");
 }
 
 }  // extern "C"

@@ -26,29 +26,13 @@ namespace clfa {
 namespace {
 
 constexpr int kOpsWG = 256;            // lanes = bins per workgroup tile (k_pvoc_map, k_pvoc_read)
-constexpr int kSrcEmpty = -1, kSrcCopy = -2;
 
-// the pitch scale's map k -> j
-__device__ __forceinline__ int pvoc_scale_j(int k, float s) {
-#pragma clang fp contract(off)
-  const float t = (float)k * s;
-  return (int)floorf(t + 0.5f);
-}
-
-// source bin of output bin j: k in 1..M-1, kSrcEmpty, or kSrcCopy (the bin is handed over unchanged).
-// Scale: k -> j is monotone, so the source — the last k of the serial definition — is the largest k with j(k) <= j if
-// that k lands on j; it lies next to (j + 1/2) / s, and the two loops move the estimate there (a few steps: s >= 1/4).
+// source bin of output bin j: k in 1..M-1, kSrcEmpty, or kSrcCopy (the bin is handed over unchanged).  The scale map's
+// gather is pvoc_scale_source (pvoc_device.hpp).
 __device__ __forceinline__ int pvoc_source(int op, int j, int M, int lowest, float par, float bpf) {
 #pragma clang fp contract(off)
   if (j == 0 || j == M) return kSrcCopy;
-  if (op == PVOC_SCALE) {
-    if (!(par >= 0.25f && par <= 4.f)) return kSrcEmpty;
-    int k = (int)(((float)j + 0.5f) / par);
-    k = k < 1 ? 1 : (k > M - 1 ? M - 1 : k);
-    while (k < M - 1 && pvoc_scale_j(k + 1, par) <= j) k++;
-    while (k >= 1 && pvoc_scale_j(k, par) > j) k--;
-    return (k >= 1 && pvoc_scale_j(k, par) == j) ? k : kSrcEmpty;
-  }
+  if (op == PVOC_SCALE) return pvoc_scale_source(j, M, par);
   if (j < lowest) return kSrcCopy;
   const float t = par * bpf;
   if (!(fabsf(t) <= (float)M)) return kSrcEmpty;   // past every bin, or not a number
