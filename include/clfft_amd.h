@@ -660,6 +660,70 @@ CLFA_API int clfa_pvoc_blur_max_frames(const clfa_pvoc *pv);
 /* "k_pvoc_blur", "k_pvoc_smooth", "k_pvoc_freeze" ("" for a failed object or an unknown op) */
 CLFA_API const char *clfa_pvoc_time_kernel_name(const clfa_pvoc *pv, int op);
 
+/* ---- per-frame descriptors of a stream of (amp, freq) frames: magnitude, centroid, flux, peak ---- */
+/* Frames to control values: Csound's pvscent, the level and onset detectors built from pvsbin, peak followers.
+ * frames_in: channels x F x (M + 1) x 2 float32 in the layout above, 8-byte aligned; only the amp column and, for the
+ * peak, the freq column are read.  desc: channels x F x 8 float32, 4-byte aligned, one row per frame, the columns below.
+ * first_bin and nbins select the bins lo = first_bin .. hi = first_bin + nbins - 1, 0 <= lo <= hi <= M; rectify is 0 or 1;
+ * anything else is CLFA_INVALID_VALUE.
+ *
+ * Every float32 operation is rounded on its own (no fused multiply-add); fl() marks a rounding.
+ *
+ * THE TREE SUM T(t) of the terms t[0..M], a term outside lo..hi being +0 (M is a power of two, 32..8192):
+ *   1. W = min(M, 256).  For j < W, p[j] starts as t[j]; then t[j + W], t[j + 2W], ... (indices < M) are added in
+ *      ascending order, one rounded addition each.
+ *   2. While more than one value is left, s[i] = fl(s[2i] + s[2i+1]): adjacent pairs first, a balanced tree.
+ *   3. T = fl(s[0] + t[M]): the Nyquist bin last.
+ * The pairing is what is fixed; float addition is commutative, so a butterfly in which every lane of a group ends up with
+ * the group's sum gives these bits whichever lane of the sibling group a value is fetched from.
+ *
+ * The columns of the row of frame f of a channel, with a = amp[k], w[k] = fl((float)k cf) (the EMPTY bin's freq,
+ * cf = (float)(sr / size)) and prev = the amp of the same bin in the stream's previous frame:
+ *   0  MAG        T(a)
+ *   1  POW        T(fl(a a))
+ *   2  MOM        T(fl(a w[k]))
+ *   3  CENT       +0 where MAG == 0, otherwise fl(MOM / MAG), the correctly rounded division (pvscent's rule)
+ *   4  FLUX       T(fl(d d)), d = fl(a - prev); with rectify d = +0 wherever d > 0 does not hold, so a NaN is dropped
+ *   5  PEAK_AMP   the amp bits of bin kp
+ *   6  PEAK_FREQ  the freq bits of bin kp
+ *   7  PEAK_BIN   (float)kp
+ * kp is the lowest bin in lo..hi whose amp is not a NaN and is >= every amp of the range that is not a NaN (-0 == +0, so
+ * the lower bin wins a tie).  If there is no such bin, columns 5..7 are +0, +0, -1.
+ *
+ * State `last`, channels x (M + 1) amps: the previous frame of a call's frame 0.  0 (the EMPTY amp) at creation and after
+ * clfa_pvoc_reset; after a call the amps of the call's last frame, of all bins and not only lo..hi.  So the rows are the
+ * same bits however a stream is cut into calls, on any stream and for any grid cap, and a captured call advances the
+ * state at every replay.  prev, theta, the oscillator bank's state and the states of the operations along the frames are
+ * never touched.  The state is allocated at creation: a device call allocates nothing.  The rules of the frame operations
+ * above hold: asynchronous on `stream`, one stream at a time, the current device left as found; F == 0 succeeds and does
+ * nothing.  Argument checks that need no device come first: on an object whose creation found no device a bad argument is
+ * still CLFA_INVALID_VALUE, a good one the object's error.  A desc that overlaps the frames, even partly, is
+ * CLFA_INVALID_VALUE.  A failed call writes nothing and leaves `last` as it was.
+ * tests/pvoc_desc_model.py restates all of it in numpy.
+ *
+ * Kernels: "k_pvoc_desc" (a group of W lanes takes a run of 4 consecutive frames of a channel and walks the bins
+ * outermost, lane j holding p[j] of each frame's four sums and a peak in registers: the input is read 5/4 times, bins
+ * outside the range not at all; then the tree, inside a wave with DPP and swizzle moves — at the first four levels a lane
+ * and its partner split the 16 sums they hold, each adding the other's partial sum to the half it keeps: the tree's
+ * additions, half as many a level — and across the waves of a group through LDS; it only reads the state), then
+ * "k_pvoc_tail" on the same stream (the freeze's commit: the call's last frame into the state, which the device keeps as
+ * pairs).  No atomics, no waiting between workgroups.  CLFA_PVOC_OPS_GRID_MAX caps the workgroups of both. */
+enum {
+  CLFA_PVOC_DESC_MAG = 0, CLFA_PVOC_DESC_POW = 1, CLFA_PVOC_DESC_MOM = 2, CLFA_PVOC_DESC_CENT = 3, CLFA_PVOC_DESC_FLUX = 4,
+  CLFA_PVOC_DESC_PEAK_AMP = 5, CLFA_PVOC_DESC_PEAK_FREQ = 6, CLFA_PVOC_DESC_PEAK_BIN = 7
+};
+CLFA_API int clfa_pvoc_desc_dev(clfa_pvoc *pv, const void *frames_in, void *desc, long F, int first_bin, int nbins,
+                                int rectify, void *stream);
+/* host arrays, copied in and out, blocking */
+CLFA_API int clfa_pvoc_desc(clfa_pvoc *pv, const float *frames_in, float *desc, long F, int first_bin, int nbins,
+                            int rectify);
+/* state diagnostics, blocking: channels x (M + 1) float32, the amps of the stream's previous frame */
+CLFA_API int clfa_pvoc_desc_read_state(clfa_pvoc *pv, float *host);
+/* the device memory of the state */
+CLFA_API size_t clfa_pvoc_desc_state_bytes(const clfa_pvoc *pv);
+/* "k_pvoc_desc" ("" for a failed object) */
+CLFA_API const char *clfa_pvoc_desc_kernel_name(const clfa_pvoc *pv);
+
 /* ---- convolution matrix (extension: nothing of the reference's) ------------- */
 /* Uniformly partitioned overlap-add convolution of `inputs` signals with an outputs x inputs matrix of static responses:
  * y_o = sum over i of x_i * h_{o,i}.

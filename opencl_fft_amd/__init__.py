@@ -312,6 +312,7 @@ class Pvoc(_Handle):
     frames back into spectra.  The object carries the last spectrum (analysis) and an integer phase per bin (synthesis)
     from call to call, so a stream may be cut into calls anywhere; reset() returns both to their start.
     adsyn() is the second way back to sound: an oscillator per bin, summed straight into samples (a state of its own).
+    describe() turns frames into control values: eight descriptors per frame (the previous frame's amps carried along).
     Like the other objects the constructor does not raise, and every call returns its status."""
     _destroy = "clfa_pvoc_destroy"
 
@@ -782,6 +783,54 @@ class Pvoc(_Handle):
         g = 2 - cos(pi cutoff), c = 1 + sqrt(g g - 1) - g"""
         g = 2.0 - np.cos(np.pi * float(cutoff))
         return float(1.0 + np.sqrt(g * g - 1.0) - g)
+
+    # ---- frames -> eight descriptors per frame (Csound's pvscent and kin; a state of its own; clfft_amd.h) ----
+
+    DESC_MAG, DESC_POW, DESC_MOM, DESC_CENT, DESC_FLUX, DESC_PEAK_AMP, DESC_PEAK_FREQ, DESC_PEAK_BIN = range(8)
+
+    def desc_kernel_name(self):
+        """ "k_pvoc_desc" ("" for a failed object)"""
+        return lib().clfa_pvoc_desc_kernel_name(self._h).decode()
+
+    def desc_state_bytes(self):
+        """device memory of the descriptors' carried state"""
+        return lib().clfa_pvoc_desc_state_bytes(self._h)
+
+    def desc_state(self):
+        """the descriptors' carried state (blocking): float32 (channels, size/2 + 1), the amps of the stream's last frame"""
+        out = np.zeros((self.channels, self.M + 1), np.float32)
+        check(lib().clfa_pvoc_desc_read_state(self._h, out.ctypes.data), "Pvoc.desc_state")
+        return out
+
+    def describe_device(self, frames_in, out, first_bin=0, nbins=None, rectify=False, stream=None):
+        """torch: frames (channels, F, size/2 + 1, 2) float32, contiguous -> out (channels, F, 8) float32, contiguous
+        ((F, 8) for one channel): per frame the columns DESC_MAG (sum of the amps), DESC_POW (of their squares), DESC_MOM
+        (of amp times bin centre), DESC_CENT (MOM / MAG, Csound's pvscent), DESC_FLUX (the sum of the squared amp
+        differences to the stream's previous frame; rectify: rises only), DESC_PEAK_AMP, DESC_PEAK_FREQ and DESC_PEAK_BIN,
+        over the bins first_bin .. first_bin + nbins - 1 (default: up to size/2).  The sums are a fixed tree of float32
+        additions: the same bits on every call.  The last frame's amps are carried to the next call.  Asynchronous on
+        `stream`."""
+        import torch
+        F = self._frames_shape(frames_in.shape)
+        o = tuple(out.shape)
+        if len(o) == 2 and self.channels == 1:
+            o = (1,) + o
+        if (F is None or o != (self.channels, F, 8) or frames_in.dtype != torch.float32 or out.dtype != torch.float32
+                or not frames_in.is_contiguous() or not out.is_contiguous()):
+            return CL_INVALID_VALUE
+        first_bin, nbins, _ = self._selection(first_bin, nbins, 1)
+        return lib().clfa_pvoc_desc_dev(self._h, frames_in.data_ptr(), out.data_ptr(), F, first_bin, nbins,
+                                        int(bool(rectify)), _stream_of(out, stream))
+
+    def describe(self, frames, first_bin=0, nbins=None, rectify=False):
+        """host form of describe_device, blocking: float32 (channels, F, size/2 + 1, 2) (or (F, size/2 + 1, 2)) -> float32
+        (.., F, 8)"""
+        frames, F = self._host_frames(frames)
+        out = np.zeros(frames.shape[:-2] + (8,), np.float32)
+        first_bin, nbins, _ = self._selection(first_bin, nbins, 1)
+        check(lib().clfa_pvoc_desc(self._h, frames.ctypes.data, out.ctypes.data, F, first_bin, nbins, int(bool(rectify))),
+              "Pvoc.describe")
+        return out
 
     # ---- frames -> samples: the oscillator bank (Csound's pvsadsyn; a state of its own; clfft_amd.h) ----
 

@@ -365,6 +365,24 @@ struct PvocTimeArgs {
 hipError_t launch_pvoc_time(const PvocTimeArgs &a, const DeviceInfo &di, hipStream_t s);
 // `frames` frames of EMPTY bins (cf = sr / size): what the three states start from
 hipError_t launch_pvoc_time_fill(cpx *dst, long frames, int M, float cf, hipStream_t s);
+// dst (channels x (M + 1) pairs) = frame F - 1 of src (channels x F frames), F >= 1: k_pvoc_tail, the freeze's commit
+hipError_t launch_pvoc_time_last(const cpx *src, long F, cpx *dst, int channels, int M, int grid_max, const DeviceInfo &di,
+                                 hipStream_t s);
+
+// ---- per-frame descriptors of a stream of (amp, freq) frames, with carried state (pvoc_desc.hip) ----
+struct PvocDescArgs {
+  int M = 0, channels = 0;
+  long F = 0;                      // frames per channel of in, rows per channel of desc
+  const cpx *in = nullptr;         // frames as (amp, freq) pairs
+  float *desc = nullptr;           // channels x F x 8
+  cpx *last = nullptr;             // the state: channels x (M + 1) pairs, the stream's previous frame (the amps are read)
+  int lo = 0, hi = 0;              // the range of bins, 0 <= lo <= hi <= M
+  int rectify = 0;
+  float cf = 0.f;                  // sr / size
+  int grid_max = 0;                // > 0: at most this many workgroups
+};
+// k_pvoc_desc<min(M, 256)>, which only reads the state, then its commit on the same stream (k_pvoc_tail)
+hipError_t launch_pvoc_desc(const PvocDescArgs &a, const DeviceInfo &di, hipStream_t s);
 
 // ---- direct convolution ----------------------------------------------------------
 struct DconvPlan {

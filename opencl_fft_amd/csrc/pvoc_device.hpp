@@ -1,5 +1,5 @@
 // pvoc_device.hpp — what the Pvoc kernel files share (pvoc_kernels.hip, pvoc_ops.hip, pvoc_pair.hip, pvoc_time.hip,
-// pvoc_shape.hip, pvoc_adsyn.hip): the decoding of a grid-stride item, the cap on a launch's workgroups, the frame
+// pvoc_shape.hip, pvoc_desc.hip, pvoc_adsyn.hip): the decoding of a grid-stride item, the cap on a launch's workgroups, the frame
 // operations' EMPTY bin, clamp and interpolation rule, the pitch scale's source map (pvoc_ops.hip's k_pvoc_map and
 // k_pvoc_formant, pvoc_shape.hip's k_pvoc_warp), and the chunked scan that turns the per-chunk sums of phase
 // increments into the bases the chunks start from (k_pvoc_scan on uint32 words, k_adsyn_scan on uint64 ones).

@@ -40,6 +40,9 @@ struct clfa_pvoc {
   // each; the blur's history of max_frames - 1 frames per channel and its spare (clfa_pvoc_blur_setup; blur_max 0 before)
   DevBuf tsmooth, theld, bhist, bspare;
   int blur_max = 0;
+  // the descriptors (pvoc_desc.hip): the stream's previous frame, channels x (M + 1) pairs of which the amps are the
+  // state `last`; staging of the host form's rows
+  DevBuf dlast, sdesc;
   StreamOrder order;
 };
 
@@ -69,7 +72,7 @@ static int pvoc_subbatches(long F, long held, Launch launch) {
 }
 
 // the states as at creation: prev = (1, 0), theta = 0, the oscillator bank's P = W = A = 0, EMPTY bins in the smoothing's
-// y, the freeze's held and the blur's history (on p->stream, blocking)
+// y, the freeze's held, the blur's history and the descriptors' previous frame (on p->stream, blocking)
 static int pvoc_init_state(clfa_pvoc *p) {
   std::vector<cpx> one(pvoc_bins(p), mk(1.f, 0.f));
   HIP_TRY(hipMemcpyAsync(p->prev.p, one.data(), sizeof(cpx) * one.size(), hipMemcpyHostToDevice, p->stream));
@@ -79,6 +82,7 @@ static int pvoc_init_state(clfa_pvoc *p) {
   HIP_TRY(hipMemsetAsync(p->aamp.p, 0, sizeof(float) * pvoc_bins(p), p->stream));
   HIP_TRY(launch_pvoc_time_fill((cpx *)p->tsmooth.p, p->channels, p->M, p->srs, p->stream));
   HIP_TRY(launch_pvoc_time_fill((cpx *)p->theld.p, p->channels, p->M, p->srs, p->stream));
+  HIP_TRY(launch_pvoc_time_fill((cpx *)p->dlast.p, p->channels, p->M, p->srs, p->stream));
   HIP_TRY(launch_pvoc_time_fill((cpx *)p->bhist.p, (long)p->channels * (p->blur_max > 0 ? p->blur_max - 1 : 0), p->M, p->srs, p->stream));
   HIP_TRY(hipStreamSynchronize(p->stream));
   return CLFA_SUCCESS;
@@ -135,6 +139,7 @@ static int pvoc_setup(clfa_pvoc *p, int device, int size, int hop, double sr, in
       (e = p->aamp.ensure(sizeof(float) * pvoc_bins(p))))
     return e;
   if ((e = p->tsmooth.ensure(sizeof(cpx) * pvoc_bins(p))) || (e = p->theld.ensure(sizeof(cpx) * pvoc_bins(p)))) return e;
+  if ((e = p->dlast.ensure(sizeof(cpx) * pvoc_bins(p)))) return e;
   return pvoc_init_state(p);
 }
 
@@ -718,6 +723,73 @@ const char *clfa_pvoc_time_kernel_name(const clfa_pvoc *p, int op) {
   if (!p || p->err || op < PVOC_BLUR || op > PVOC_FREEZE) return "";
   return op == PVOC_BLUR ? "k_pvoc_blur" : (op == PVOC_SMOOTH ? "k_pvoc_smooth" : "k_pvoc_freeze");
 }
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------
+// frames -> eight descriptors per frame, with carried state (pvoc_desc.hip)
+// ---------------------------------------------------------------------------------
+
+static size_t pvoc_desc_bytes(const clfa_pvoc *p, long F) { return 8 * sizeof(float) * (size_t)p->channels * (size_t)F; }
+
+// The checks that need no device, before the object's own error (as pvoc_ops_check).  0 = go on, 1 = a successful no-op,
+// < 0 = the error.
+static int pvoc_desc_check(const clfa_pvoc *p, const void *in, const void *desc, long F, int first_bin, int nbins,
+                           int rectify, bool device_ptrs) {
+  if (!p) return CLFA_INVALID_VALUE;
+  if (!p->M) return p->err ? p->err : CLFA_INVALID_VALUE;
+  if (!pvoc_count_ok(F)) return CLFA_INVALID_VALUE;
+  if (first_bin < 0 || nbins < 1 || (long)first_bin + nbins - 1 > p->M) return CLFA_INVALID_VALUE;
+  if (rectify != 0 && rectify != 1) return CLFA_INVALID_VALUE;
+  if (F == 0) return 1;
+  if (!in || !desc) return CLFA_INVALID_VALUE;
+  if (device_ptrs && (((uintptr_t)in & 7) || ((uintptr_t)desc & 3))) return CLFA_INVALID_VALUE;
+  if (spans_overlap(in, pvoc_frame_bytes(p, F), desc, pvoc_desc_bytes(p, F))) return CLFA_INVALID_VALUE;
+  return CLFA_SUCCESS;
+}
+
+extern "C" {
+
+int clfa_pvoc_desc_dev(clfa_pvoc *p, const void *frames_in, void *desc, long F, int first_bin, int nbins, int rectify,
+                       void *stream) {
+  if (int e = pvoc_gate(p, pvoc_desc_check(p, frames_in, desc, F, first_bin, nbins, rectify, true))) return pvoc_done(e);
+  ENTER_DEVICE(p->di.device);
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(p->order.use(s));
+  PvocDescArgs a;
+  a.M = p->M;
+  a.channels = p->channels;
+  a.F = F;
+  a.in = (const cpx *)frames_in;
+  a.desc = (float *)desc;
+  a.last = (cpx *)p->dlast.p;
+  a.lo = first_bin;
+  a.hi = first_bin + nbins - 1;
+  a.rectify = rectify;
+  a.cf = p->srs;
+  a.grid_max = p->ops_grid_max;
+  HIP_TRY(launch_pvoc_desc(a, p->di, s));
+  return CLFA_SUCCESS;
+}
+
+int clfa_pvoc_desc(clfa_pvoc *p, const float *frames_in, float *desc, long F, int first_bin, int nbins, int rectify) {
+  if (int e = pvoc_gate(p, pvoc_desc_check(p, frames_in, desc, F, first_bin, nbins, rectify, false))) return pvoc_done(e);
+  return pvoc_staged(p, {{false, frames_in, &p->sframes, pvoc_frame_bytes(p, F)}, {true, desc, &p->sdesc, pvoc_desc_bytes(p, F)}},
+                     [&] { return clfa_pvoc_desc_dev(p, p->sframes.p, p->sdesc.p, F, first_bin, nbins, rectify, p->stream); });
+}
+
+// the amps of the previous frame: the first of every pair the device holds
+int clfa_pvoc_desc_read_state(clfa_pvoc *p, float *host) {
+  if (int e = obj_error(p)) return e;
+  if (!host) return CLFA_INVALID_VALUE;
+  std::vector<cpx> pairs(pvoc_bins(p));
+  if (int e = pvoc_read_state(p, {{pairs.data(), &clfa_pvoc::dlast, sizeof(cpx)}})) return e;
+  for (size_t i = 0; i < pairs.size(); i++) host[i] = pairs[i].x;
+  return CLFA_SUCCESS;
+}
+
+size_t clfa_pvoc_desc_state_bytes(const clfa_pvoc *p) { return p ? p->dlast.bytes : 0; }
+const char *clfa_pvoc_desc_kernel_name(const clfa_pvoc *p) { return !p || p->err ? "" : "k_pvoc_desc"; }
 
 }  // extern "C"
 

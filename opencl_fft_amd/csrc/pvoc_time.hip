@@ -14,7 +14,7 @@
 //                  which a device copy on the same stream then puts over the history, so that no launch both reads and
 //                  writes the history and no ring position exists (on the host it would not advance under graph replay,
 //                  on the device its update would race with its readers).  The freeze's commit: the output's last frame
-//                  into held.
+//                  into held.  The descriptors' commit (pvoc_desc.hip, launch_pvoc_time_last): the input's last frame.
 //   k_pvoc_smooth  the recurrence is serial along the frames: a lane owns one (channel, bin), reads its state first, walks
 //                  the call's frames and writes the state last.  The loads do not depend on the recurrence: a group of
 //                  kSmoothGroup frames is in flight in registers ahead of the arithmetic.  Workgroups of 64 lanes spread
@@ -221,6 +221,17 @@ static hipError_t launch_pvoc_tail(const PvocTimeArgs &a, const cpx *hist, int L
   const int grid = pvoc_grid(items, (long)di.num_cus * 16, a.grid_max);
   hipLaunchKernelGGL(k_pvoc_tail, dim3(grid), dim3(kTimeWG), 0, s, hist, L, src, a.F, dst, rows, a.M, tiles, items);
   return hipGetLastError();
+}
+
+hipError_t launch_pvoc_time_last(const cpx *src, long F, cpx *dst, int channels, int M, int grid_max, const DeviceInfo &di,
+                                 hipStream_t s) {
+  if (F <= 0 || channels <= 0) return hipSuccess;
+  PvocTimeArgs a;
+  a.M = M;
+  a.channels = channels;
+  a.F = F;
+  a.grid_max = grid_max;
+  return launch_pvoc_tail(a, nullptr, 0, src, dst, 1, di, s);
 }
 
 hipError_t launch_pvoc_time(const PvocTimeArgs &a, const DeviceInfo &di, hipStream_t s) {
