@@ -419,30 +419,52 @@ class Pvoc(_Handle):
             raise ValueError("frames must be (%d, F, %d, 2)" % (self.channels, self.M + 1))
         return frames, F
 
+    @staticmethod
+    def _is_f32(t, shape):
+        """a device call's tensor: float32, contiguous, of this shape"""
+        import torch
+        return t.dtype == torch.float32 and tuple(t.shape) == tuple(shape) and t.is_contiguous()
+
+    def _device_frames(self, *tensors):
+        """F if every tensor holds F frames for a device call ((channels, F, M + 1, 2), or (F, M + 1, 2) for one channel,
+        float32, contiguous), else None"""
+        F = self._frames_shape(tensors[0].shape)
+        ok = F is not None and all(self._frames_shape(t.shape) == F and self._is_f32(t, t.shape) for t in tensors)
+        return F if ok else None
+
     def _per_frame(self, par, F, device):
         """a per-frame value of a device call as a float32 (F,) tensor: a plain number becomes F copies on `device`;
         None for a tensor of another kind"""
         import torch
         if not hasattr(par, "data_ptr"):
             par = torch.full((F,), float(par), dtype=torch.float32, device=device)
-        if par.dtype != torch.float32 or tuple(par.shape) != (F,) or not par.is_contiguous():
-            return None
-        return par
+        return par if self._is_f32(par, (F,)) else None
+
+    def _per_frame_ptrs(self, pars, F, device):
+        """the per-frame parameters of a device call as (their pointers, the tensors to keep until the call is made): a
+        number becomes a tensor of F copies, None a NULL; (None, None) if one is a tensor of another kind"""
+        keep = [None if par is None else self._per_frame(par, F, device) for par in pars]
+        if any(t is None and par is not None for t, par in zip(keep, pars)):
+            return None, None
+        return [None if t is None else t.data_ptr() for t in keep], keep
 
     def _per_frame_host(self, par, F):
         """a per-frame value of a host call (a number or an array of F) as a contiguous float32 (F,) array"""
         return np.ascontiguousarray(np.broadcast_to(np.asarray(par, dtype=np.float32), (F,)))
 
+    @staticmethod
+    def _op_code(ops, op):
+        """an op given by its name or its code, as the code (-1 for an unknown name)"""
+        return ops.get(op, -1) if isinstance(op, str) else int(op)
+
     def _ops_device(self, frames_in, frames_out, par, stream):
-        """(Fin, Fout, the per-frame tensor, stream) of a device call, None for bad tensors; a plain number becomes a
-        tensor of Fout copies"""
-        import torch
-        Fin, Fout = self._frames_shape(frames_in.shape), self._frames_shape(frames_out.shape)
-        if (Fin is None or Fout is None or frames_in.dtype != torch.float32 or frames_out.dtype != torch.float32
-                or not frames_in.is_contiguous() or not frames_out.is_contiguous()):
+        """(Fin, Fout, the per-frame pointer, stream, what to keep) of a device call, None for bad tensors; a plain number
+        becomes a tensor of Fout copies"""
+        Fin, Fout = self._device_frames(frames_in), self._device_frames(frames_out)
+        if Fin is None or Fout is None:
             return None
-        par = self._per_frame(par, Fout, frames_out.device)
-        return None if par is None else (Fin, Fout, par, _stream_of(frames_out, stream))
+        ptrs, keep = self._per_frame_ptrs((par,), Fout, frames_out.device)
+        return None if ptrs is None else (Fin, Fout, ptrs[0], _stream_of(frames_out, stream), keep)
 
     def scale_device(self, frames_in, frames_out, scale, keepform=False, gain=1.0, coefs=80, stream=None):
         """pitch scale (Csound's pvscale): torch frames (channels, F, size/2 + 1, 2) float32 -> frames_out of the same
@@ -451,7 +473,7 @@ class Pvoc(_Handle):
         a = self._ops_device(frames_in, frames_out, scale, stream)
         if a is None or a[0] != a[1]:
             return CL_INVALID_VALUE
-        return lib().clfa_pvoc_scale_dev(self._h, frames_in.data_ptr(), frames_out.data_ptr(), a[1], a[2].data_ptr(),
+        return lib().clfa_pvoc_scale_dev(self._h, frames_in.data_ptr(), frames_out.data_ptr(), a[1], a[2],
                                          int(bool(keepform)), float(gain), int(coefs), a[3])
 
     def shift_device(self, frames_in, frames_out, shift, lowest_bin=1, keepform=False, gain=1.0, coefs=80, stream=None):
@@ -460,7 +482,7 @@ class Pvoc(_Handle):
         a = self._ops_device(frames_in, frames_out, shift, stream)
         if a is None or a[0] != a[1]:
             return CL_INVALID_VALUE
-        return lib().clfa_pvoc_shift_dev(self._h, frames_in.data_ptr(), frames_out.data_ptr(), a[1], a[2].data_ptr(),
+        return lib().clfa_pvoc_shift_dev(self._h, frames_in.data_ptr(), frames_out.data_ptr(), a[1], a[2],
                                          int(lowest_bin), int(bool(keepform)), float(gain), int(coefs), a[3])
 
     def read_device(self, frames_in, pos, frames_out, stream=None):
@@ -469,7 +491,7 @@ class Pvoc(_Handle):
         a = self._ops_device(frames_in, frames_out, pos, stream)
         if a is None or not hasattr(pos, "data_ptr"):
             return CL_INVALID_VALUE
-        return lib().clfa_pvoc_read_dev(self._h, frames_in.data_ptr(), a[0], a[2].data_ptr(), frames_out.data_ptr(),
+        return lib().clfa_pvoc_read_dev(self._h, frames_in.data_ptr(), a[0], a[2], frames_out.data_ptr(),
                                         a[1], a[3])
 
     def _ops_host(self, frames, par, Fout=None):
@@ -506,26 +528,16 @@ class Pvoc(_Handle):
     def pair_kernel_name(self, op):
         """op "cross", "morph", "filter", "mix" (or 0..3) -> "k_pvoc_pair", "vocode" (4) -> "k_pvoc_vocode" ("" for a failed
         object or an unknown op)"""
-        code = self._PAIR_OPS.get(op, -1) if isinstance(op, str) else int(op)
-        return lib().clfa_pvoc_pair_kernel_name(self._h, code).decode()
+        return lib().clfa_pvoc_pair_kernel_name(self._h, self._op_code(self._PAIR_OPS, op)).decode()
 
     def _pair_device(self, op, a, b, out, p, q, coefs, stream):
         """one two-input device call; p, q: numbers or float32 device tensors (F,), None for mix"""
-        import torch
-        F = self._frames_shape(out.shape)
-        if F is None or any(self._frames_shape(t.shape) != F or t.dtype != torch.float32 or not t.is_contiguous()
-                            for t in (a, b, out)):
+        F = self._device_frames(out, a, b)
+        ptrs, keep = (None, None) if F is None else self._per_frame_ptrs((p, q), F, out.device)
+        if ptrs is None:
             return CL_INVALID_VALUE
-        ptrs = []
-        for par in (p, q):
-            if par is not None:
-                par = self._per_frame(par, F, out.device)
-                if par is None:
-                    return CL_INVALID_VALUE
-            ptrs.append(par)
-        return lib().clfa_pvoc_pair_dev(self._h, op, a.data_ptr(), b.data_ptr(), out.data_ptr(), F,
-                                        None if ptrs[0] is None else ptrs[0].data_ptr(),
-                                        None if ptrs[1] is None else ptrs[1].data_ptr(), int(coefs), _stream_of(out, stream))
+        return lib().clfa_pvoc_pair_dev(self._h, op, a.data_ptr(), b.data_ptr(), out.data_ptr(), F, ptrs[0], ptrs[1],
+                                        int(coefs), _stream_of(out, stream))
 
     def cross_device(self, a, b, out, amp_a=1.0, amp_b=1.0, stream=None):
         """cross-synthesis (Csound's pvscross): torch frames a, b (channels, F, size/2 + 1, 2) float32 -> out of the same
@@ -589,16 +601,14 @@ class Pvoc(_Handle):
     def shape_kernel_name(self, op):
         """op "band", "mask", "stencil", "arp" (or 0..3) -> "k_pvoc_shape", "lock" (4) -> "k_pvoc_lock", "warp" (5) ->
         "k_pvoc_warp" ("" for a failed object or an unknown op)"""
-        code = self._SHAPE_OPS.get(op, -1) if isinstance(op, str) else int(op)
-        return lib().clfa_pvoc_shape_kernel_name(self._h, code).decode()
+        return lib().clfa_pvoc_shape_kernel_name(self._h, self._op_code(self._SHAPE_OPS, op)).decode()
 
     def _shape_device(self, op, frames_in, frames_out, cols, table, flags, lowest_bin, coefs, stream):
         """one shaping device call; cols: the op's per-frame values (numbers or float32 device tensors (F,)), stacked
         into the (F, 4) rows the library reads; table: None or a float32 device tensor (size/2 + 1,)"""
         import torch
-        F = self._frames_shape(frames_out.shape)
-        if F is None or any(self._frames_shape(t.shape) != F or t.dtype != torch.float32 or not t.is_contiguous()
-                            for t in (frames_in, frames_out)):
+        F = self._device_frames(frames_out, frames_in)
+        if F is None:
             return CL_INVALID_VALUE
         rows = torch.zeros((F, 4), dtype=torch.float32, device=frames_out.device)
         for i, par in enumerate(cols):
@@ -609,8 +619,7 @@ class Pvoc(_Handle):
                 rows[:, i] = par
             else:
                 rows[:, i] = float(par)
-        if table is not None and (not hasattr(table, "data_ptr") or table.dtype != torch.float32
-                                  or tuple(table.shape) != (self.M + 1,) or not table.is_contiguous()):
+        if table is not None and not (hasattr(table, "data_ptr") and self._is_f32(table, (self.M + 1,))):
             return CL_INVALID_VALUE
         return lib().clfa_pvoc_shape_dev(self._h, op, frames_in.data_ptr(), frames_out.data_ptr(), F, rows.data_ptr(),
                                          None if table is None else table.data_ptr(), int(flags), int(lowest_bin),
@@ -692,13 +701,10 @@ class Pvoc(_Handle):
 
     _TIME_OPS = {"blur": 0, "smooth": 1, "freeze": 2}
 
-    def _time_op(self, op):
-        return self._TIME_OPS.get(op, -1) if isinstance(op, str) else int(op)
-
     def time_kernel_name(self, op):
         """op "blur", "smooth", "freeze" (or 0..2) -> "k_pvoc_blur", "k_pvoc_smooth", "k_pvoc_freeze" ("" for a failed
         object or an unknown op)"""
-        return lib().clfa_pvoc_time_kernel_name(self._h, self._time_op(op)).decode()
+        return lib().clfa_pvoc_time_kernel_name(self._h, self._op_code(self._TIME_OPS, op)).decode()
 
     def time_state_bytes(self):
         """device memory of the three carried states, the blur's spare included"""
@@ -715,7 +721,7 @@ class Pvoc(_Handle):
     def time_state(self, op):
         """the carried state of op "blur", "smooth" or "freeze" (blocking), float32: the blur's history (channels,
         max_frames - 1, size/2 + 1, 2), oldest frame first; the smoothing's y and the freeze's held (channels, size/2 + 1, 2)"""
-        code = self._time_op(op)
+        code = self._op_code(self._TIME_OPS, op)
         shape = (self.channels, max(self.blur_max_frames() - 1, 0)) if code == 0 else (self.channels,)
         out = np.zeros(shape + (self.M + 1, 2), np.float32)
         check(lib().clfa_pvoc_time_read_state(self._h, code, out.ctypes.data), "Pvoc.time_state")
@@ -723,20 +729,12 @@ class Pvoc(_Handle):
 
     def _time_device(self, op, frames_in, frames_out, p, q, stream):
         """one device call along the frames; p, q: numbers or float32 device tensors (F,), q None for blur"""
-        import torch
-        F = self._frames_shape(frames_out.shape)
-        if F is None or any(self._frames_shape(t.shape) != F or t.dtype != torch.float32 or not t.is_contiguous()
-                            for t in (frames_in, frames_out)):
+        F = self._device_frames(frames_out, frames_in)
+        ptrs, keep = (None, None) if F is None else self._per_frame_ptrs((p, q), F, frames_out.device)
+        if ptrs is None:
             return CL_INVALID_VALUE
-        ptrs = []
-        for par in (p, q):
-            if par is not None:
-                par = self._per_frame(par, F, frames_out.device)
-                if par is None:
-                    return CL_INVALID_VALUE
-            ptrs.append(par)
-        return lib().clfa_pvoc_time_dev(self._h, op, frames_in.data_ptr(), frames_out.data_ptr(), F, ptrs[0].data_ptr(),
-                                        None if ptrs[1] is None else ptrs[1].data_ptr(), _stream_of(frames_out, stream))
+        return lib().clfa_pvoc_time_dev(self._h, op, frames_in.data_ptr(), frames_out.data_ptr(), F, ptrs[0], ptrs[1],
+                                        _stream_of(frames_out, stream))
 
     def blur_device(self, frames_in, frames_out, length, stream=None):
         """moving average along the frames (Csound's pvsblur): torch frames (channels, F, size/2 + 1, 2) float32 ->
@@ -810,13 +808,11 @@ class Pvoc(_Handle):
         over the bins first_bin .. first_bin + nbins - 1 (default: up to size/2).  The sums are a fixed tree of float32
         additions: the same bits on every call.  The last frame's amps are carried to the next call.  Asynchronous on
         `stream`."""
-        import torch
-        F = self._frames_shape(frames_in.shape)
+        F = self._device_frames(frames_in)
         o = tuple(out.shape)
         if len(o) == 2 and self.channels == 1:
             o = (1,) + o
-        if (F is None or o != (self.channels, F, 8) or frames_in.dtype != torch.float32 or out.dtype != torch.float32
-                or not frames_in.is_contiguous() or not out.is_contiguous()):
+        if F is None or o != (self.channels, F, 8) or not self._is_f32(out, out.shape):
             return CL_INVALID_VALUE
         first_bin, nbins, _ = self._selection(first_bin, nbins, 1)
         return lib().clfa_pvoc_desc_dev(self._h, frames_in.data_ptr(), out.data_ptr(), F, first_bin, nbins,
@@ -865,20 +861,18 @@ class Pvoc(_Handle):
         oscillators of the bins first_bin + i * step, i < nbins (default: all that fit), times gain.  fmod: a frequency
         multiplier, a number or a float32 device tensor (F,); None: none.  Asynchronous on `stream`."""
         import torch
-        F = self._frames_shape(frames.shape)
-        if F is None or frames.dtype != torch.float32 or out.dtype != torch.float32 or not frames.is_contiguous():
+        F = self._device_frames(frames)
+        if F is None or out.dtype != torch.float32:
             return CL_INVALID_VALUE
         p, rows, n, stride = _row_view(out, "out")
         if rows != self.channels or n < F * self.hop:
             return CL_INVALID_VALUE
-        if fmod is not None:
-            fmod = self._per_frame(fmod, F, out.device)
-            if fmod is None:
-                return CL_INVALID_VALUE
+        ptrs, keep = self._per_frame_ptrs((fmod,), F, out.device)
+        if ptrs is None:
+            return CL_INVALID_VALUE
         first_bin, nbins, step = self._selection(first_bin, nbins, step)
-        return lib().clfa_pvoc_adsyn_dev(self._h, frames.data_ptr(), F, None if fmod is None else fmod.data_ptr(),
-                                         first_bin, nbins, step, float(gain), p, stride if rows > 1 else n,
-                                         _stream_of(out, stream))
+        return lib().clfa_pvoc_adsyn_dev(self._h, frames.data_ptr(), F, ptrs[0], first_bin, nbins, step, float(gain), p,
+                                         stride if rows > 1 else n, _stream_of(out, stream))
 
     def adsyn(self, frames, fmod=None, first_bin=0, nbins=None, step=1, gain=1.0):
         """host form of adsyn_device, blocking: float32 (channels, F, size/2 + 1, 2) (or (F, size/2 + 1, 2)) -> float32

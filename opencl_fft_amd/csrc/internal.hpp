@@ -290,49 +290,45 @@ struct PvocAdsynArgs {
 // frames [f0, f0 + nf) of every channel, nf <= the workspace's chunks x kPvocChunk: k_adsyn_sums, k_adsyn_scan, k_adsyn_osc
 hipError_t launch_pvoc_adsyn(const PvocAdsynArgs &a, long f0, long nf, const DeviceInfo &di, hipStream_t s);
 
+// ---- what the launches of the frame operations below share (filled by pvoc_host.cpp's pvoc_frames_args) ----
+struct PvocFramesArgs {
+  int M = 0, channels = 0;
+  long F = 0;                      // frames per channel of the output (and of every input but the read's)
+  int logn = 0;                    // log2(M): the envelope kernels' transform length (complex)
+  const cpx *half = nullptr, *w2 = nullptr;   // the envelope kernels: the Clrfft tables of size (forward sign)
+  int grid_max = 0;                // > 0: at most this many workgroups
+};
+
 // ---- operations on (amp, freq) frames (pvoc_ops.hip): pitch scale, frequency shift, timed read ----
 enum PvocOp { PVOC_SCALE = 0, PVOC_SHIFT = 1, PVOC_READ = 2 };
-struct PvocOpsArgs {
+struct PvocOpsArgs : PvocFramesArgs {
   int op = PVOC_SCALE;
-  int logn = 0;                    // log2(M): the formant kernel's transform length (complex)
-  int M = 0, channels = 0;
-  long F = 0;                      // output frames per channel (scale, shift: also the input's)
   long Fin = 0;                    // read: input frames per channel
   const cpx *in = nullptr;         // frames as (amp, freq) pairs
   cpx *out = nullptr;
   const float *par = nullptr;      // F values: scale, shift in Hz, or positions
   int lowest = 1, keepform = 0, coefs = 1;
   float gain = 1.f, cf = 0.f, bpf = 0.f;   // sr / size, size / sr
-  const cpx *half = nullptr, *w2 = nullptr;   // formant: the Clrfft tables of size (forward sign)
-  int grid_max = 0;                // > 0: at most this many workgroups
 };
 // one launch: k_pvoc_map, k_pvoc_formant<logn> (keepform) or k_pvoc_read
 hipError_t launch_pvoc_ops(const PvocOpsArgs &a, const DeviceInfo &di, hipStream_t s);
 
 // ---- operations on two streams of (amp, freq) frames (pvoc_pair.hip) ------------------
 enum PvocPairOp { PVOC_CROSS = 0, PVOC_MORPH = 1, PVOC_FILTER = 2, PVOC_MIX = 3, PVOC_VOCODE = 4 };   // CLFA_PVOC_*
-struct PvocPairArgs {
+struct PvocPairArgs : PvocFramesArgs {
   int op = PVOC_CROSS;
-  int logn = 0;                    // log2(M): the vocoder's transform length (complex)
-  int M = 0, channels = 0;
-  long F = 0;                      // frames per channel of a, b and out
   const cpx *a = nullptr, *b = nullptr;   // frames as (amp, freq) pairs; they may overlap
   cpx *out = nullptr;
   const float *p = nullptr, *q = nullptr;   // F values each (mix: not read)
   int coefs = 1;                   // vocode
-  const cpx *half = nullptr, *w2 = nullptr;   // vocode: the Clrfft tables of size (forward sign)
-  int grid_max = 0;                // > 0: at most this many workgroups
 };
 // one launch: k_pvoc_pair, or k_pvoc_vocode<logn> for PVOC_VOCODE
 hipError_t launch_pvoc_pair(const PvocPairArgs &a, const DeviceInfo &di, hipStream_t s);
 
 // ---- operations that reshape one stream of (amp, freq) frames along the bins (pvoc_shape.hip) ----
 enum PvocShapeOp { PVOC_BAND = 0, PVOC_MASK = 1, PVOC_STENCIL = 2, PVOC_ARP = 3, PVOC_LOCK = 4, PVOC_WARP = 5 };   // CLFA_PVOC_*
-struct PvocShapeArgs {
+struct PvocShapeArgs : PvocFramesArgs {
   int op = PVOC_BAND;
-  int logn = 0;                    // log2(M): the warp's transform length (complex)
-  int M = 0, channels = 0;
-  long F = 0;                      // frames per channel of in and out
   const cpx *in = nullptr;         // frames as (amp, freq) pairs
   cpx *out = nullptr;
   const float *par = nullptr;      // F rows of 4 values
@@ -340,25 +336,20 @@ struct PvocShapeArgs {
   int reject = 0;                  // band
   int lowest = 1, coefs = 1;       // warp
   float bpf = 0.f;                 // size / sr
-  const cpx *half = nullptr, *w2 = nullptr;   // warp: the Clrfft tables of size (forward sign)
-  int grid_max = 0;                // > 0: at most this many workgroups
 };
 // one launch: k_pvoc_shape (ops 0..3), k_pvoc_lock or k_pvoc_warp<logn>
 hipError_t launch_pvoc_shape(const PvocShapeArgs &a, const DeviceInfo &di, hipStream_t s);
 
 // ---- operations along a stream of (amp, freq) frames, with carried state (pvoc_time.hip) ----
 enum PvocTimeOp { PVOC_BLUR = 0, PVOC_SMOOTH = 1, PVOC_FREEZE = 2 };   // CLFA_PVOC_*
-struct PvocTimeArgs {
+struct PvocTimeArgs : PvocFramesArgs {
   int op = PVOC_BLUR;
-  int M = 0, channels = 0;
-  long F = 0;                      // frames per channel of in and out
   const cpx *in = nullptr;         // frames as (amp, freq) pairs
   cpx *out = nullptr;
   const float *p = nullptr, *q = nullptr;   // F values each (blur: q is not read)
   cpx *state = nullptr;            // blur: the history, channels x L frames, oldest first; smooth: y; freeze: held
   cpx *spare = nullptr;            // blur: as the history
   int max_frames = 1;              // blur: L = max_frames - 1
-  int grid_max = 0;                // > 0: at most this many workgroups
 };
 // the main launch, then what commits the state on the same stream: blur k_pvoc_tail into the spare and a copy of the
 // spare over the history, freeze k_pvoc_tail of the output's last frame into held; smooth commits in its own launch
@@ -370,16 +361,13 @@ hipError_t launch_pvoc_time_last(const cpx *src, long F, cpx *dst, int channels,
                                  hipStream_t s);
 
 // ---- per-frame descriptors of a stream of (amp, freq) frames, with carried state (pvoc_desc.hip) ----
-struct PvocDescArgs {
-  int M = 0, channels = 0;
-  long F = 0;                      // frames per channel of in, rows per channel of desc
+struct PvocDescArgs : PvocFramesArgs {   // F: also the rows per channel of desc
   const cpx *in = nullptr;         // frames as (amp, freq) pairs
   float *desc = nullptr;           // channels x F x 8
   cpx *last = nullptr;             // the state: channels x (M + 1) pairs, the stream's previous frame (the amps are read)
   int lo = 0, hi = 0;              // the range of bins, 0 <= lo <= hi <= M
   int rectify = 0;
   float cf = 0.f;                  // sr / size
-  int grid_max = 0;                // > 0: at most this many workgroups
 };
 // k_pvoc_desc<min(M, 256)>, which only reads the state, then its commit on the same stream (k_pvoc_tail)
 hipError_t launch_pvoc_desc(const PvocDescArgs &a, const DeviceInfo &di, hipStream_t s);

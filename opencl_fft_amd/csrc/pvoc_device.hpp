@@ -1,8 +1,11 @@
 // pvoc_device.hpp — what the Pvoc kernel files share (pvoc_kernels.hip, pvoc_ops.hip, pvoc_pair.hip, pvoc_time.hip,
-// pvoc_shape.hip, pvoc_desc.hip, pvoc_adsyn.hip): the decoding of a grid-stride item, the cap on a launch's workgroups, the frame
-// operations' EMPTY bin, clamp and interpolation rule, the pitch scale's source map (pvoc_ops.hip's k_pvoc_map and
-// k_pvoc_formant, pvoc_shape.hip's k_pvoc_warp), and the chunked scan that turns the per-chunk sums of phase
-// increments into the bases the chunks start from (k_pvoc_scan on uint32 words, k_adsyn_scan on uint64 ones).
+// pvoc_shape.hip, pvoc_desc.hip, pvoc_adsyn.hip):
+//   pvoc_item, pvoc_bin    the decoding of a grid-stride item, and the bin a lane of a tile kernel takes of it
+//   pvoc_grid, pvoc_tiles  the cap on a launch's workgroups, and the tiles, items and grid of a tile launch
+//   pvoc_empty, pvoc_clamp01, pvoc_morph   the frame operations' EMPTY bin, clamp and interpolation rule
+//   pvoc_scale_source      the pitch scale's source map (k_pvoc_map, k_pvoc_formant, k_pvoc_warp)
+//   pvoc_scan              the chunked scan that turns the per-chunk sums of phase increments into the bases the
+//                          chunks start from (k_pvoc_scan on uint32 words, k_adsyn_scan on uint64 ones)
 #pragma once
 #include "internal.hpp"
 
@@ -18,10 +21,34 @@ __device__ __forceinline__ void pvoc_item(long item, int tiles, long inner, int 
   j = rest - c * inner;
 }
 
+// The prologue of a tile kernel (a lane per bin, WG bins per tile): the item's (c, j) and the lane's bin k; false where
+// the last tile reaches past bin M
+template <int WG>
+__device__ __forceinline__ bool pvoc_bin(long item, int tiles, long inner, int M, int &k, long &j, long &c) {
+  int tile;
+  pvoc_item(item, tiles, inner, tile, j, c);
+  k = tile * WG + (int)threadIdx.x;
+  return k <= M;
+}
+
 // workgroups of a grid-stride launch: one per item, at most cap, at most grid_max where that is set (> 0)
 static inline int pvoc_grid(long items, long cap, int grid_max) {
   if (grid_max > 0 && cap > grid_max) cap = grid_max;
   return (int)(items < cap ? items : cap);
+}
+
+// A tile launch: tiles of `lanes` bins per row of M + 1, `outer` rows (channels x frames, runs, ...), an item per tile,
+// at most per_cu workgroups per CU
+struct PvocTiles {
+  int tiles, grid;
+  long items;
+};
+static inline PvocTiles pvoc_tiles(int M, int lanes, long outer, const DeviceInfo &di, int per_cu, int grid_max) {
+  PvocTiles t;
+  t.tiles = (M + 1 + lanes - 1) / lanes;
+  t.items = outer * t.tiles;
+  t.grid = pvoc_grid(t.items, (long)di.num_cus * per_cu, grid_max);
+  return t;
 }
 
 // an EMPTY bin of the frame operations: silent, at its bin centre (cf = sr / size)

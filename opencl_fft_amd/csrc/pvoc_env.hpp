@@ -8,13 +8,66 @@
 //       visit of every pair (i, N - i);
 //   (4) the unscaled inverse on the chain of k_stft_synth;
 //   (5) expf turns the first B samples of the slot into env, in place.
+// What the three kernels share besides the stages: the bounds of a group of frames (PvocEnvGroup) and, on the host, their
+// launch (launch_pvoc_env under pvoc_env_dispatch).  The __shared__ arrays, the staging of the twiddle tables into them
+// and the loop over the groups stay in each kernel: a shared function changes the LDS layout or the staging's
+// instructions (at n = 1024..4096 its two ds_write_b64 become one ds_write2st64_b64).
 #pragma once
+#include <type_traits>
+
 #include "fft_wg.hpp"
+#include "pvoc_device.hpp"
 
 namespace clfa {
 
 // n = 8192 reads its twiddle tables from L1/L2 (pvoc_ops.hip)
 template <int LOGN> constexpr bool pvoc_env_tab_lds() { return LOGN <= 12; }
+
+// Group g of FPW consecutive frames out of nframes: its first frame, its frames (fewer in a ragged last group, whose other
+// slots run the chain on stale LDS and write nothing) and its bins
+template <int LOGN> struct PvocEnvGroup {
+  long b0;
+  int nv, live;
+  __device__ __forceinline__ PvocEnvGroup(long g, long nframes) {
+    constexpr int FPW = LdsGeom<LOGN>::FPW;
+    b0 = g * FPW;
+    nv = nframes - b0 < FPW ? (int)(nframes - b0) : FPW;
+    live = nv * (LdsGeom<LOGN>::N + 1);
+  }
+};
+
+// One launch of an envelope kernel over the groups of nframes frames, as many workgroups as stay resident (asked once per
+// kernel); args: the kernel's own
+template <int LOGN, auto Kernel, class... Args>
+static hipError_t launch_pvoc_env(long nframes, int grid_max, const DeviceInfo &di, hipStream_t s, Args... args) {
+  using G = LdsGeom<LOGN>;
+  static int occ = 0;
+  if (!occ) {
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)Kernel, G::WG, 0) != hipSuccess || nb < 1) {
+      (void)hipGetLastError();
+      nb = 1;
+    }
+    occ = nb;
+  }
+  const long groups = (nframes + G::FPW - 1) / G::FPW;
+  const int grid = pvoc_grid(groups, (long)di.num_cus * occ, grid_max);
+  hipLaunchKernelGGL(Kernel, dim3(grid), dim3(G::WG), 0, s, args...);
+  return hipGetLastError();
+}
+
+// launch(std::integral_constant<int, LOGN>()) for logn = log2(size / 2) of the nine sizes
+template <class Launch>
+static hipError_t pvoc_env_dispatch(int logn, Launch launch) {
+  switch (logn) {
+#define CLFA_N(L) \
+  case L: return launch(std::integral_constant<int, L>());
+    CLFA_N(5) CLFA_N(6) CLFA_N(7) CLFA_N(8) CLFA_N(9) CLFA_N(10) CLFA_N(11) CLFA_N(12) CLFA_N(13)
+#undef CLFA_N
+    default:
+      return hipErrorInvalidValue;
+  }
+}
 
 template <int LOGN> struct PvocEnv {
   using G = LdsGeom<LOGN>;

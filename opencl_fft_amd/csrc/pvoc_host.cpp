@@ -1,10 +1,13 @@
 // pvoc_host.cpp — C ABI of the phase vocoder on the Stft spectra (see include/clfft_amd.h): Pvoc.  Shared plumbing: host.hpp.
+// The object and its states come first; then what every call shares — the description of its arrays (PvocArray), their
+// check, the device form, the staged blocking form, and pvoc_call, which puts a call's results in the header's order —
+// then one function per family of calls with what is its own: scalar rules, array list, per-frame value rule, launch.
 #include "host.hpp"
 
 using namespace clfa;
 
 // ---------------------------------------------------------------------------------
-// spectra <-> (amp, freq) frames (pvoc_kernels.hip)
+// The object, its setup and its states
 // ---------------------------------------------------------------------------------
 
 struct clfa_pvoc {
@@ -170,48 +173,164 @@ static int pvoc_read_state(clfa_pvoc *p, std::initializer_list<PvocState> states
   return CLFA_SUCCESS;
 }
 
-// The blocking host forms: every array has a staging buffer on the device, ensured in the order of the list; the inputs
-// are copied in, dev() runs the device form on the staging buffers and the object's stream, the outputs are copied out,
-// and the stream is waited for.  An array is `rows` rows of `bytes` each, packed in the staging buffer and `pitch` bytes
-// apart on the host (0: packed there too, one plain copy); an input whose host pointer is NULL is left out.
-struct PvocStaged {
-  bool out;
-  const void *host;
-  DevBuf *buf;
-  size_t bytes, rows = 1, pitch = 0;
+// The results of the argument checks: 0 = go on, 1 = a successful no-op, < 0 = the error.  A call goes on after its
+// device-free checks with the error, else the object's own error, else chk:
+//   if (int e = pvoc_gate(p, chk)) return pvoc_done(e);
+static int pvoc_gate(const clfa_pvoc *p, int chk) { return chk < 0 ? chk : (p->err ? p->err : chk); }
+static int pvoc_done(int e) { return e == 1 ? CLFA_SUCCESS : e; }
+
+// what a launch answers, as a status
+static int pvoc_code(int e) { return e; }
+static int pvoc_code(hipError_t e) {
+  HIP_TRY(e);
+  return CLFA_SUCCESS;
+}
+
+// ---------------------------------------------------------------------------------
+// One description of a call, checked, staged and handed to the launch from one place
+// ---------------------------------------------------------------------------------
+
+// One array of a call, as the caller passed it: device memory in a device form, host memory in a blocking form.  It is
+// `rows` rows of `bytes` each, `pitch` bytes apart (0: packed).  An array the op does not look at (`used` false: MIX's p
+// and q, BLUR's q, the table of most shaping ops, a NULL fmod) is not examined, not staged, and reaches the launch as NULL.
+struct PvocArray {
+  const void *ptr;
+  size_t bytes;
+  int align;                  // what a device form asks of ptr: 8 (frames, spectra, pairs) or 4 (floats)
+  bool out;                   // the call's one output; the others are inputs
+  DevBuf clfa_pvoc::*stage;   // where a blocking form stages it, its rows packed
+  bool used = true;
+  size_t rows = 1, pitch = 0;
+  size_t span() const { return pitch ? (rows - 1) * pitch + bytes : rows * bytes; }   // first byte to last, gaps included
 };
-template <class Dev>
-static int pvoc_staged(clfa_pvoc *p, std::initializer_list<PvocStaged> arrays, Dev dev) {
+constexpr size_t kPvocArrays = 5;   // at most so many per call
+
+// The arrays' rules: a NULL is an invalid value, so is with device_ptrs a misaligned one, so is an input that overlaps
+// the output even partly (the inputs may overlap each other)
+template <size_t N>
+static int pvoc_arrays_check(const PvocArray (&arrays)[N], bool device_ptrs) {
+  const PvocArray *out = nullptr;
+  for (const PvocArray &a : arrays) {
+    if (!a.used) continue;
+    if (!a.ptr || (device_ptrs && ((uintptr_t)a.ptr & (uintptr_t)(a.align - 1)))) return CLFA_INVALID_VALUE;
+    if (a.out) out = &a;
+  }
+  for (const PvocArray &a : arrays)
+    if (a.used && !a.out && out && spans_overlap(a.ptr, a.span(), out->ptr, out->span())) return CLFA_INVALID_VALUE;
+  return CLFA_SUCCESS;
+}
+
+// The device forms after their checks (chk): the error, else the object's own, else a no-op's success, ahead of any device
+// work; then launch(stream) on the object's device, ordered behind the object's earlier work
+template <class Launch>
+static int pvoc_dev_form(clfa_pvoc *p, int chk, void *stream, Launch launch) {
+  if (int e = pvoc_gate(p, chk)) return pvoc_done(e);
   ENTER_DEVICE(p->di.device);
-  for (const PvocStaged &a : arrays)
-    if (int e = a.host ? a.buf->ensure(a.bytes * a.rows) : 0) return e;
-  for (const PvocStaged &a : arrays)
-    if (!a.out && a.host) HIP_TRY(hipMemcpyAsync(a.buf->p, a.host, a.bytes * a.rows, hipMemcpyHostToDevice, p->stream));
-  if (int e = dev()) return e;
-  for (const PvocStaged &a : arrays) {
-    void *host = const_cast<void *>(a.host);
-    if (a.out && a.pitch)
-      HIP_TRY(hipMemcpy2DAsync(host, a.pitch, a.buf->p, a.bytes, a.bytes, a.rows, hipMemcpyDeviceToHost, p->stream));
-    else if (a.out)
-      HIP_TRY(hipMemcpyAsync(host, a.buf->p, a.bytes * a.rows, hipMemcpyDeviceToHost, p->stream));
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(p->order.use(s));
+  return pvoc_code(launch(s));
+}
+
+// The blocking forms after their checks: every array the op looks at has a staging buffer on the device, ensured in the
+// order of the list; the inputs are copied in, dev(d) runs the device work on the staged arrays d[i] (NULL where the op
+// does not look) and the object's stream, the output is copied out, and the stream is waited for.
+template <size_t N, class Dev>
+static int pvoc_staged(clfa_pvoc *p, const PvocArray (&arrays)[N], Dev dev) {
+  static_assert(N <= kPvocArrays, "kPvocArrays");
+  ENTER_DEVICE(p->di.device);
+  const void *d[kPvocArrays] = {};
+  for (size_t i = 0; i < N; i++) {
+    const PvocArray &a = arrays[i];
+    if (int e = a.used ? (p->*a.stage).ensure(a.bytes * a.rows) : 0) return e;
+    if (a.used) d[i] = (p->*a.stage).p;
+  }
+  for (size_t i = 0; i < N; i++) {
+    const PvocArray &a = arrays[i];
+    if (d[i] && !a.out) HIP_TRY(hipMemcpyAsync(const_cast<void *>(d[i]), a.ptr, a.bytes * a.rows, hipMemcpyHostToDevice, p->stream));
+  }
+  if (int e = dev(d)) return e;
+  for (size_t i = 0; i < N; i++) {
+    const PvocArray &a = arrays[i];
+    void *host = const_cast<void *>(a.ptr);
+    if (d[i] && a.out && a.pitch)
+      HIP_TRY(hipMemcpy2DAsync(host, a.pitch, d[i], a.bytes, a.bytes, a.rows, hipMemcpyDeviceToHost, p->stream));
+    else if (d[i] && a.out)
+      HIP_TRY(hipMemcpyAsync(host, d[i], a.bytes * a.rows, hipMemcpyDeviceToHost, p->stream));
   }
   HIP_TRY(hipStreamSynchronize(p->stream));
   return CLFA_SUCCESS;
 }
 
-// The results of the argument checks: 0 = go on, 1 = a successful no-op, < 0 = the error.  An operation or the oscillator
-// bank goes on after its device-free checks with the error, else the object's own error, else chk:
-//   if (int e = pvoc_gate(p, chk)) return pvoc_done(e);
-static int pvoc_gate(const clfa_pvoc *p, int chk) { return chk < 0 ? chk : (p->err ? p->err : chk); }
-static int pvoc_done(int e) { return e == 1 ? CLFA_SUCCESS : e; }
+// The object can take a call's arguments at all: a NULL object is an invalid value, one whose creation arguments were bad
+// (M == 0) answers with that error.  One that only found no device goes on: a bad argument is still an invalid value there,
+// which is why a call's checks come before the object's own error.
+static int pvoc_usable(const clfa_pvoc *p) {
+  if (!p) return CLFA_INVALID_VALUE;
+  return p->M ? CLFA_SUCCESS : (p->err ? p->err : CLFA_INVALID_VALUE);
+}
 
-// the argument rules both directions share; 1 = a successful no-op
-static int pvoc_check(const clfa_pvoc *p, const void *spectra, const void *frames, long F) {
+// Either form of a call of F frames on a usable object, the results in the order of the header: the op code and the
+// scalar ranges (scalars_ok: the family's), F == 0 as a successful no-op, the arrays, in a blocking form the per-frame
+// values (values_ok(): the family's rule on the host arrays), `ready` (the blur's setup), the object's own error; then
+// launch(d, stream) with the arrays the device reads and writes: the caller's in a device form, the staged ones in a
+// blocking form.
+template <size_t N, class Values, class Launch>
+static int pvoc_call(clfa_pvoc *p, bool blocking, void *stream, bool scalars_ok, long F, const PvocArray (&arrays)[N], int ready,
+                     Values values_ok, Launch launch) {
+  static_assert(N <= kPvocArrays, "kPvocArrays");
+  int chk = !scalars_ok || !pvoc_count_ok(F) ? CLFA_INVALID_VALUE : (F == 0 ? 1 : pvoc_arrays_check(arrays, !blocking));
+  if (chk == 0 && blocking && !values_ok()) chk = CLFA_INVALID_VALUE;
+  if (chk == 0) chk = ready;
+  if (!blocking) {
+    const void *d[kPvocArrays] = {};
+    for (size_t i = 0; i < N; i++) d[i] = arrays[i].used ? arrays[i].ptr : nullptr;
+    return pvoc_dev_form(p, chk, stream, [&](hipStream_t s) { return launch(d, s); });
+  }
+  if (int e = pvoc_gate(p, chk)) return pvoc_done(e);
+  return pvoc_staged(p, arrays, [&](const void *const *d) {
+    return pvoc_dev_form(p, CLFA_SUCCESS, p->stream, [&](hipStream_t s) { return launch(d, s); });
+  });
+}
+static bool pvoc_no_values() { return true; }
+
+// the fields every launch of a frame operation takes
+static void pvoc_frames_args(const clfa_pvoc *p, long F, PvocFramesArgs &a) {
+  a.M = p->M;
+  a.channels = p->channels;
+  a.F = F;
+  a.logn = ilog2(p->M);
+  a.half = (const cpx *)p->half.p;
+  a.w2 = (const cpx *)p->w2.p;
+  a.grid_max = p->ops_grid_max;
+}
+
+// ---------------------------------------------------------------------------------
+// spectra <-> (amp, freq) frames (pvoc_kernels.hip).  Unlike the frame operations, both directions answer with the
+// object's own error before they look at an argument.
+// ---------------------------------------------------------------------------------
+
+struct PvocConvert {
+  PvocArray arrays[2];   // the spectra, the frames
+};
+static PvocConvert pvoc_convert(const clfa_pvoc *p, const void *spectra, const void *frames, long F, bool synthesis) {
+  return {{{spectra, pvoc_spec_bytes(p, F), 8, synthesis, &clfa_pvoc::sspec},
+           {frames, pvoc_frame_bytes(p, F), 8, !synthesis, &clfa_pvoc::sframes}}};
+}
+
+// the argument rules of the two device forms; 1 = a successful no-op
+static int pvoc_check(const PvocConvert &c, long F) {
   if (!pvoc_count_ok(F)) return CLFA_INVALID_VALUE;
-  if (F == 0) return 1;
-  if (!spectra || !frames || ((uintptr_t)spectra & 7) || ((uintptr_t)frames & 7)) return CLFA_INVALID_VALUE;
-  if (spans_overlap(spectra, pvoc_spec_bytes(p, F), frames, pvoc_frame_bytes(p, F))) return CLFA_INVALID_VALUE;
-  return CLFA_SUCCESS;
+  return F == 0 ? 1 : pvoc_arrays_check(c.arrays, true);
+}
+
+// the blocking forms: NULL arrays are invalid values, then copies around dev(spectra, frames) on the staged arrays
+template <class Dev>
+static int pvoc_convert_host(clfa_pvoc *p, const void *spectra, const void *frames, long F, bool synthesis, Dev dev) {
+  if (int e = obj_error(p)) return e;
+  const PvocConvert c = pvoc_convert(p, spectra, frames, F, synthesis);
+  if (!pvoc_count_ok(F) || (F > 0 && (!c.arrays[0].ptr || !c.arrays[1].ptr))) return CLFA_INVALID_VALUE;
+  if (F == 0) return CLFA_SUCCESS;
+  return pvoc_staged(p, c.arrays, [&](const void *const *d) { return dev(const_cast<void *>(d[0]), const_cast<void *>(d[1])); });
 }
 
 static PvocArgs pvoc_args(clfa_pvoc *p, long F) {
@@ -262,142 +381,107 @@ int clfa_pvoc_read_prev(clfa_pvoc *p, float *host) {
 
 int clfa_pvoc_analyze_dev(clfa_pvoc *p, const void *spectra, void *frames_out, long F, void *stream) {
   if (int e = obj_error(p)) return e;
-  if (int e = pvoc_check(p, spectra, frames_out, F)) return pvoc_done(e);
-  ENTER_DEVICE(p->di.device);
-  hipStream_t s = (hipStream_t)stream;
-  HIP_TRY(p->order.use(s));
-  PvocArgs a = pvoc_args(p, F);
-  a.spec_in = (const cpx *)spectra;
-  a.frames_out = (float *)frames_out;
-  HIP_TRY(launch_pvoc_analyze(a, p->di, s));
-  return CLFA_SUCCESS;
+  return pvoc_dev_form(p, pvoc_check(pvoc_convert(p, spectra, frames_out, F, false), F), stream, [&](hipStream_t s) {
+    PvocArgs a = pvoc_args(p, F);
+    a.spec_in = (const cpx *)spectra;
+    a.frames_out = (float *)frames_out;
+    return launch_pvoc_analyze(a, p->di, s);
+  });
 }
 
 int clfa_pvoc_synthesize_dev(clfa_pvoc *p, const void *frames, void *spectra_out, long F, void *stream) {
   if (int e = obj_error(p)) return e;
-  if (int e = pvoc_check(p, spectra_out, frames, F)) return pvoc_done(e);
-  ENTER_DEVICE(p->di.device);
-  hipStream_t s = (hipStream_t)stream;
-  const long held = p->cap;   // the whole sub-batch workspace at the first need: its address never changes afterwards
-  HIP_TRY(p->order.use(s));
-  if (int e = ensure_workspaces({{&p->ws, sizeof(unsigned) * pvoc_bins(p) * (size_t)held}}, s)) return e;
-  PvocArgs a = pvoc_args(p, F);
-  a.frames_in = (const float *)frames;
-  a.spec_out = (cpx *)spectra_out;
-  return pvoc_subbatches(F, held, [&](long f0, long nf) { return launch_pvoc_synth(a, f0, nf, p->di, s); });
+  return pvoc_dev_form(p, pvoc_check(pvoc_convert(p, spectra_out, frames, F, true), F), stream, [&](hipStream_t s) {
+    const long held = p->cap;   // the whole sub-batch workspace at the first need: its address never changes afterwards
+    if (int e = ensure_workspaces({{&p->ws, sizeof(unsigned) * pvoc_bins(p) * (size_t)held}}, s)) return e;
+    PvocArgs a = pvoc_args(p, F);
+    a.frames_in = (const float *)frames;
+    a.spec_out = (cpx *)spectra_out;
+    return pvoc_subbatches(F, held, [&](long f0, long nf) { return launch_pvoc_synth(a, f0, nf, p->di, s); });
+  });
 }
+
+int clfa_pvoc_analyze(clfa_pvoc *p, const float *spectra, float *frames_out, long F) {
+  return pvoc_convert_host(p, spectra, frames_out, F, false, [&](void *dspectra, void *dframes) {
+    return clfa_pvoc_analyze_dev(p, dspectra, dframes, F, p->stream);
+  });
+}
+
+int clfa_pvoc_synthesize(clfa_pvoc *p, const float *frames, float *spectra_out, long F) {
+  return pvoc_convert_host(p, spectra_out, frames, F, true, [&](void *dspectra, void *dframes) {
+    return clfa_pvoc_synthesize_dev(p, dframes, dspectra, F, p->stream);
+  });
+}
+
+}  // extern "C"
 
 // ---------------------------------------------------------------------------------
 // frames -> frames: pitch scale, frequency shift, timed read (pvoc_ops.hip)
 // ---------------------------------------------------------------------------------
 
-// The checks that need no device, in the order of the header: they come before the object's own error, so that on an
-// object whose creation found no device a bad argument is still an invalid value (M != 0: the creation arguments were
-// good).  0 = go on, 1 = a successful no-op, < 0 = the error.  F: output frames, Fin: input frames (== F for scale and shift).
-static int pvoc_ops_check(const clfa_pvoc *p, int op, const void *in, long Fin, const void *par, const void *out, long F,
-                          int lowest, int keepform, int coefs, bool device_ptrs) {
-  if (!p) return CLFA_INVALID_VALUE;
-  if (!p->M) return p->err ? p->err : CLFA_INVALID_VALUE;
-  if (!pvoc_count_ok(F)) return CLFA_INVALID_VALUE;
-  if (op == PVOC_READ && (Fin < 1 || Fin > (1L << 24))) return CLFA_INVALID_VALUE;
-  if (op == PVOC_SHIFT && (lowest < 1 || lowest > p->M - 1)) return CLFA_INVALID_VALUE;
-  if (op != PVOC_READ && keepform && (coefs < 1 || coefs >= p->M)) return CLFA_INVALID_VALUE;
-  if (F == 0) return 1;
-  if (!in || !out || !par) return CLFA_INVALID_VALUE;
-  if (device_ptrs && (((uintptr_t)in & 7) || ((uintptr_t)out & 7) || ((uintptr_t)par & 3))) return CLFA_INVALID_VALUE;
-  const size_t ibytes = pvoc_frame_bytes(p, Fin), obytes = pvoc_frame_bytes(p, F);
-  if (spans_overlap(in, ibytes, out, obytes) || spans_overlap(par, sizeof(float) * (size_t)F, out, obytes))
-    return CLFA_INVALID_VALUE;
-  return CLFA_SUCCESS;
+// F: output frames, Fin: input frames (== F for scale and shift).  The blocking forms ask finite values of scale and
+// shift, and scales in [1/4, 4]; the read's positions are clamped, whatever they are.
+static int pvoc_ops_call(clfa_pvoc *p, bool blocking, int op, const void *in, long Fin, const void *par, void *out, long F,
+                         int lowest, int keepform, float gain, int coefs, void *stream) {
+  if (int e = pvoc_usable(p)) return e;
+  const bool scalars_ok = !(op == PVOC_READ && (Fin < 1 || Fin > (1L << 24))) &&
+                          !(op == PVOC_SHIFT && (lowest < 1 || lowest > p->M - 1)) &&
+                          !(op != PVOC_READ && keepform && (coefs < 1 || coefs >= p->M));
+  const PvocArray arrays[] = {{in, pvoc_frame_bytes(p, Fin), 8, false, &clfa_pvoc::sframes},
+                              {out, pvoc_frame_bytes(p, F), 8, true, &clfa_pvoc::sop_out},
+                              {par, sizeof(float) * (size_t)F, 4, false, &clfa_pvoc::sop_par}};
+  const auto values_ok = [&] {
+    const float *v = (const float *)par;
+    for (long f = 0; f < F && op != PVOC_READ; f++)
+      if (!std::isfinite(v[f]) || (op == PVOC_SCALE && !(v[f] >= 0.25f && v[f] <= 4.f))) return false;
+    return true;
+  };
+  return pvoc_call(p, blocking, stream, scalars_ok, F, arrays, CLFA_SUCCESS, values_ok, [&](const void *const *d, hipStream_t s) {
+    PvocOpsArgs a;
+    pvoc_frames_args(p, F, a);
+    a.op = op;
+    a.Fin = Fin;
+    a.in = (const cpx *)d[0];
+    a.out = (cpx *)d[1];
+    a.par = (const float *)d[2];
+    a.lowest = lowest;
+    a.keepform = keepform != 0;
+    a.coefs = coefs;
+    a.gain = gain;
+    a.cf = p->srs;
+    a.bpf = p->bpf;
+    return launch_pvoc_ops(a, p->di, s);
+  });
 }
 
-static int pvoc_ops_dev(clfa_pvoc *p, int op, const void *in, long Fin, const void *par, void *out, long F, int lowest,
-                        int keepform, float gain, int coefs, void *stream) {
-  if (int e = pvoc_gate(p, pvoc_ops_check(p, op, in, Fin, par, out, F, lowest, keepform, coefs, true))) return pvoc_done(e);
-  ENTER_DEVICE(p->di.device);
-  hipStream_t s = (hipStream_t)stream;
-  HIP_TRY(p->order.use(s));
-  PvocOpsArgs a;
-  a.op = op;
-  a.logn = ilog2(p->M);
-  a.M = p->M;
-  a.channels = p->channels;
-  a.F = F;
-  a.Fin = Fin;
-  a.in = (const cpx *)in;
-  a.out = (cpx *)out;
-  a.par = (const float *)par;
-  a.lowest = lowest;
-  a.keepform = keepform != 0;
-  a.coefs = coefs;
-  a.gain = gain;
-  a.cf = p->srs;
-  a.bpf = p->bpf;
-  a.half = (const cpx *)p->half.p;
-  a.w2 = (const cpx *)p->w2.p;
-  a.grid_max = p->ops_grid_max;
-  HIP_TRY(launch_pvoc_ops(a, p->di, s));
-  return CLFA_SUCCESS;
-}
-
-// the blocking forms: the same checks on the host arrays, then the per-frame values, then copies around the device form
-static int pvoc_ops_host(clfa_pvoc *p, int op, const float *in, long Fin, const float *par, float *out, long F, int lowest,
-                         int keepform, float gain, int coefs) {
-  const int chk = pvoc_ops_check(p, op, in, Fin, par, out, F, lowest, keepform, coefs, false);
-  if (chk < 0) return chk;
-  for (long f = 0; f < F && op != PVOC_READ; f++) {
-    if (!std::isfinite(par[f]) || (op == PVOC_SCALE && !(par[f] >= 0.25f && par[f] <= 4.f))) return CLFA_INVALID_VALUE;
-  }
-  if (int e = pvoc_gate(p, chk)) return pvoc_done(e);
-  return pvoc_staged(p, {{false, in, &p->sframes, pvoc_frame_bytes(p, Fin)}, {true, out, &p->sop_out, pvoc_frame_bytes(p, F)},
-                         {false, par, &p->sop_par, sizeof(float) * (size_t)F}}, [&] {
-                       return pvoc_ops_dev(p, op, p->sframes.p, Fin, p->sop_par.p, p->sop_out.p, F, lowest, keepform, gain,
-                                           coefs, p->stream);
-                     });
-}
+extern "C" {
 
 int clfa_pvoc_scale_dev(clfa_pvoc *p, const void *frames_in, void *frames_out, long F, const void *scale, int keepform,
                         float gain, int coefs, void *stream) {
-  return pvoc_ops_dev(p, PVOC_SCALE, frames_in, F, scale, frames_out, F, 1, keepform, gain, coefs, stream);
+  return pvoc_ops_call(p, false, PVOC_SCALE, frames_in, F, scale, frames_out, F, 1, keepform, gain, coefs, stream);
 }
 int clfa_pvoc_shift_dev(clfa_pvoc *p, const void *frames_in, void *frames_out, long F, const void *shift, int lowest_bin,
                         int keepform, float gain, int coefs, void *stream) {
-  return pvoc_ops_dev(p, PVOC_SHIFT, frames_in, F, shift, frames_out, F, lowest_bin, keepform, gain, coefs, stream);
+  return pvoc_ops_call(p, false, PVOC_SHIFT, frames_in, F, shift, frames_out, F, lowest_bin, keepform, gain, coefs, stream);
 }
 int clfa_pvoc_read_dev(clfa_pvoc *p, const void *frames_in, long Fin, const void *pos, void *frames_out, long Fout,
                        void *stream) {
-  return pvoc_ops_dev(p, PVOC_READ, frames_in, Fin, pos, frames_out, Fout, 1, 0, 1.f, 1, stream);
+  return pvoc_ops_call(p, false, PVOC_READ, frames_in, Fin, pos, frames_out, Fout, 1, 0, 1.f, 1, stream);
 }
 int clfa_pvoc_scale(clfa_pvoc *p, const float *frames_in, float *frames_out, long F, const float *scale, int keepform,
                     float gain, int coefs) {
-  return pvoc_ops_host(p, PVOC_SCALE, frames_in, F, scale, frames_out, F, 1, keepform, gain, coefs);
+  return pvoc_ops_call(p, true, PVOC_SCALE, frames_in, F, scale, frames_out, F, 1, keepform, gain, coefs, nullptr);
 }
 int clfa_pvoc_shift(clfa_pvoc *p, const float *frames_in, float *frames_out, long F, const float *shift, int lowest_bin,
                     int keepform, float gain, int coefs) {
-  return pvoc_ops_host(p, PVOC_SHIFT, frames_in, F, shift, frames_out, F, lowest_bin, keepform, gain, coefs);
+  return pvoc_ops_call(p, true, PVOC_SHIFT, frames_in, F, shift, frames_out, F, lowest_bin, keepform, gain, coefs, nullptr);
 }
 int clfa_pvoc_read(clfa_pvoc *p, const float *frames_in, long Fin, const float *pos, float *frames_out, long Fout) {
-  return pvoc_ops_host(p, PVOC_READ, frames_in, Fin, pos, frames_out, Fout, 1, 0, 1.f, 1);
+  return pvoc_ops_call(p, true, PVOC_READ, frames_in, Fin, pos, frames_out, Fout, 1, 0, 1.f, 1, nullptr);
 }
 const char *clfa_pvoc_ops_kernel_name(const clfa_pvoc *p, int op, int keepform) {
   if (!p || p->err || op < PVOC_SCALE || op > PVOC_READ) return "";
   return op == PVOC_READ ? "k_pvoc_read" : (keepform ? "k_pvoc_formant" : "k_pvoc_map");
-}
-
-int clfa_pvoc_analyze(clfa_pvoc *p, const float *spectra, float *frames_out, long F) {
-  if (int e = obj_error(p)) return e;
-  if (!pvoc_count_ok(F) || (F > 0 && (!spectra || !frames_out))) return CLFA_INVALID_VALUE;
-  if (F == 0) return CLFA_SUCCESS;
-  return pvoc_staged(p, {{false, spectra, &p->sspec, pvoc_spec_bytes(p, F)}, {true, frames_out, &p->sframes, pvoc_frame_bytes(p, F)}},
-                     [&] { return clfa_pvoc_analyze_dev(p, p->sspec.p, p->sframes.p, F, p->stream); });
-}
-
-int clfa_pvoc_synthesize(clfa_pvoc *p, const float *frames, float *spectra_out, long F) {
-  if (int e = obj_error(p)) return e;
-  if (!pvoc_count_ok(F) || (F > 0 && (!frames || !spectra_out))) return CLFA_INVALID_VALUE;
-  if (F == 0) return CLFA_SUCCESS;
-  return pvoc_staged(p, {{true, spectra_out, &p->sspec, pvoc_spec_bytes(p, F)}, {false, frames, &p->sframes, pvoc_frame_bytes(p, F)}},
-                     [&] { return clfa_pvoc_synthesize_dev(p, p->sframes.p, p->sspec.p, F, p->stream); });
 }
 
 }  // extern "C"
@@ -406,81 +490,48 @@ int clfa_pvoc_synthesize(clfa_pvoc *p, const float *frames, float *spectra_out, 
 // two streams of frames -> frames: cross, morph, filter, mix, vocode (pvoc_pair.hip)
 // ---------------------------------------------------------------------------------
 
-// The checks that need no device, before the object's own error (as pvoc_ops_check).  0 = go on, 1 = a successful no-op,
-// < 0 = the error.  MIX reads neither per-frame array: they are not looked at.
-static int pvoc_pair_check(const clfa_pvoc *p, int op, const void *a, const void *b, const void *out, long F,
-                           const void *pp, const void *qq, int coefs, bool device_ptrs) {
-  if (!p) return CLFA_INVALID_VALUE;
-  if (!p->M) return p->err ? p->err : CLFA_INVALID_VALUE;
-  if (op < PVOC_CROSS || op > PVOC_VOCODE) return CLFA_INVALID_VALUE;
-  if (!pvoc_count_ok(F)) return CLFA_INVALID_VALUE;
-  if (op == PVOC_VOCODE && (coefs < 1 || coefs >= p->M)) return CLFA_INVALID_VALUE;
-  if (F == 0) return 1;
-  if (!a || !b || !out) return CLFA_INVALID_VALUE;
-  if (device_ptrs && (((uintptr_t)a & 7) || ((uintptr_t)b & 7) || ((uintptr_t)out & 7))) return CLFA_INVALID_VALUE;
-  const size_t fbytes = pvoc_frame_bytes(p, F), pbytes = sizeof(float) * (size_t)F;
-  if (spans_overlap(a, fbytes, out, fbytes) || spans_overlap(b, fbytes, out, fbytes)) return CLFA_INVALID_VALUE;
-  if (op == PVOC_MIX) return CLFA_SUCCESS;
-  if (!pp || !qq) return CLFA_INVALID_VALUE;
-  if (device_ptrs && (((uintptr_t)pp & 3) || ((uintptr_t)qq & 3))) return CLFA_INVALID_VALUE;
-  if (spans_overlap(pp, pbytes, out, fbytes) || spans_overlap(qq, pbytes, out, fbytes)) return CLFA_INVALID_VALUE;
-  return CLFA_SUCCESS;
-}
-
-static int pvoc_pair_dev(clfa_pvoc *p, int op, const void *a, const void *b, void *out, long F, const void *pp,
-                         const void *qq, int coefs, void *stream) {
-  if (int e = pvoc_gate(p, pvoc_pair_check(p, op, a, b, out, F, pp, qq, coefs, true))) return pvoc_done(e);
-  ENTER_DEVICE(p->di.device);
-  hipStream_t s = (hipStream_t)stream;
-  HIP_TRY(p->order.use(s));
-  PvocPairArgs g;
-  g.op = op;
-  g.logn = ilog2(p->M);
-  g.M = p->M;
-  g.channels = p->channels;
-  g.F = F;
-  g.a = (const cpx *)a;
-  g.b = (const cpx *)b;
-  g.out = (cpx *)out;
-  g.p = op == PVOC_MIX ? nullptr : (const float *)pp;
-  g.q = op == PVOC_MIX ? nullptr : (const float *)qq;
-  g.coefs = coefs;
-  g.half = (const cpx *)p->half.p;
-  g.w2 = (const cpx *)p->w2.p;
-  g.grid_max = p->ops_grid_max;
-  HIP_TRY(launch_pvoc_pair(g, p->di, s));
-  return CLFA_SUCCESS;
-}
-
-// the blocking form: the same checks on the host arrays, then the per-frame values, then copies around the device form
-static int pvoc_pair_host(clfa_pvoc *p, int op, const float *a, const float *b, float *out, long F, const float *pp,
-                          const float *qq, int coefs) {
-  const int chk = pvoc_pair_check(p, op, a, b, out, F, pp, qq, coefs, false);
-  if (chk < 0) return chk;
-  const bool unit_p = op == PVOC_MORPH || op == PVOC_FILTER || op == PVOC_VOCODE, unit_q = op == PVOC_MORPH;
-  for (long f = 0; f < F && op != PVOC_MIX; f++) {
-    if (!std::isfinite(pp[f]) || !std::isfinite(qq[f])) return CLFA_INVALID_VALUE;
-    if ((unit_p && !(pp[f] >= 0.f && pp[f] <= 1.f)) || (unit_q && !(qq[f] >= 0.f && qq[f] <= 1.f))) return CLFA_INVALID_VALUE;
-  }
-  if (int e = pvoc_gate(p, chk)) return pvoc_done(e);
+// MIX reads neither per-frame array.  The blocking form asks finite values, and the depths and weights in [0, 1].
+static int pvoc_pair_call(clfa_pvoc *p, bool blocking, int op, const void *a, const void *b, void *out, long F,
+                          const void *pp, const void *qq, int coefs, void *stream) {
+  if (int e = pvoc_usable(p)) return e;
+  const bool scalars_ok = op >= PVOC_CROSS && op <= PVOC_VOCODE && !(op == PVOC_VOCODE && (coefs < 1 || coefs >= p->M));
   const bool mix = op == PVOC_MIX;
   const size_t fbytes = pvoc_frame_bytes(p, F), pbytes = sizeof(float) * (size_t)F;
-  return pvoc_staged(p, {{false, a, &p->sframes, fbytes}, {false, b, &p->spair_b, fbytes}, {true, out, &p->sop_out, fbytes},
-                         {false, mix ? nullptr : pp, &p->sop_par, pbytes}, {false, mix ? nullptr : qq, &p->spair_q, pbytes}}, [&] {
-                       return pvoc_pair_dev(p, op, p->sframes.p, p->spair_b.p, p->sop_out.p, F, p->sop_par.p, p->spair_q.p,
-                                            coefs, p->stream);
-                     });
+  const PvocArray arrays[] = {{a, fbytes, 8, false, &clfa_pvoc::sframes},    {b, fbytes, 8, false, &clfa_pvoc::spair_b},
+                              {out, fbytes, 8, true, &clfa_pvoc::sop_out},   {pp, pbytes, 4, false, &clfa_pvoc::sop_par, !mix},
+                              {qq, pbytes, 4, false, &clfa_pvoc::spair_q, !mix}};
+  const auto values_ok = [&] {
+    const float *P = (const float *)pp, *Q = (const float *)qq;
+    const bool unit_p = op == PVOC_MORPH || op == PVOC_FILTER || op == PVOC_VOCODE, unit_q = op == PVOC_MORPH;
+    for (long f = 0; f < F && !mix; f++) {
+      if (!std::isfinite(P[f]) || !std::isfinite(Q[f])) return false;
+      if ((unit_p && !(P[f] >= 0.f && P[f] <= 1.f)) || (unit_q && !(Q[f] >= 0.f && Q[f] <= 1.f))) return false;
+    }
+    return true;
+  };
+  return pvoc_call(p, blocking, stream, scalars_ok, F, arrays, CLFA_SUCCESS, values_ok, [&](const void *const *d, hipStream_t s) {
+    PvocPairArgs g;
+    pvoc_frames_args(p, F, g);
+    g.op = op;
+    g.a = (const cpx *)d[0];
+    g.b = (const cpx *)d[1];
+    g.out = (cpx *)d[2];
+    g.p = (const float *)d[3];
+    g.q = (const float *)d[4];
+    g.coefs = coefs;
+    return launch_pvoc_pair(g, p->di, s);
+  });
 }
 
 extern "C" {
 
 int clfa_pvoc_pair_dev(clfa_pvoc *p, int op, const void *frames_a, const void *frames_b, void *frames_out, long F,
                        const void *pp, const void *qq, int coefs, void *stream) {
-  return pvoc_pair_dev(p, op, frames_a, frames_b, frames_out, F, pp, qq, coefs, stream);
+  return pvoc_pair_call(p, false, op, frames_a, frames_b, frames_out, F, pp, qq, coefs, stream);
 }
 int clfa_pvoc_pair(clfa_pvoc *p, int op, const float *frames_a, const float *frames_b, float *frames_out, long F,
                    const float *pp, const float *qq, int coefs) {
-  return pvoc_pair_host(p, op, frames_a, frames_b, frames_out, F, pp, qq, coefs);
+  return pvoc_pair_call(p, true, op, frames_a, frames_b, frames_out, F, pp, qq, coefs, nullptr);
 }
 const char *clfa_pvoc_pair_kernel_name(const clfa_pvoc *p, int op) {
   if (!p || p->err || op < PVOC_CROSS || op > PVOC_VOCODE) return "";
@@ -492,57 +543,6 @@ const char *clfa_pvoc_pair_kernel_name(const clfa_pvoc *p, int op) {
 // ---------------------------------------------------------------------------------
 // one stream of frames -> frames, along the bins: band, mask, stencil, arp, lock, warp (pvoc_shape.hip)
 // ---------------------------------------------------------------------------------
-
-static bool pvoc_shape_table(int op) { return op == PVOC_MASK || op == PVOC_STENCIL; }
-
-// The checks that need no device, before the object's own error (as pvoc_ops_check).  0 = go on, 1 = a successful no-op,
-// < 0 = the error.  The table is looked at for MASK and STENCIL only.
-static int pvoc_shape_check(const clfa_pvoc *p, int op, const void *in, const void *out, long F, const void *par,
-                            const void *table, int flags, int lowest, int coefs, bool device_ptrs) {
-  if (!p) return CLFA_INVALID_VALUE;
-  if (!p->M) return p->err ? p->err : CLFA_INVALID_VALUE;
-  if (op < PVOC_BAND || op > PVOC_WARP) return CLFA_INVALID_VALUE;
-  if (!pvoc_count_ok(F)) return CLFA_INVALID_VALUE;
-  if (flags & ~(op == PVOC_BAND ? 1 : 0)) return CLFA_INVALID_VALUE;
-  if (op == PVOC_WARP && (lowest < 1 || lowest > p->M - 1 || coefs < 1 || coefs >= p->M)) return CLFA_INVALID_VALUE;
-  if (F == 0) return 1;
-  if (!in || !out || !par) return CLFA_INVALID_VALUE;
-  if (!pvoc_shape_table(op)) table = nullptr;
-  else if (!table) return CLFA_INVALID_VALUE;
-  if (device_ptrs && (((uintptr_t)in & 7) || ((uintptr_t)out & 7) || ((uintptr_t)par & 3) || ((uintptr_t)table & 3)))
-    return CLFA_INVALID_VALUE;
-  const size_t fbytes = pvoc_frame_bytes(p, F), pbytes = 4 * sizeof(float) * (size_t)F;
-  if (spans_overlap(in, fbytes, out, fbytes) || spans_overlap(par, pbytes, out, fbytes)) return CLFA_INVALID_VALUE;
-  if (table && spans_overlap(table, sizeof(float) * (size_t)(p->M + 1), out, fbytes)) return CLFA_INVALID_VALUE;
-  return CLFA_SUCCESS;
-}
-
-static int pvoc_shape_dev(clfa_pvoc *p, int op, const void *in, void *out, long F, const void *par, const void *table,
-                          int flags, int lowest, int coefs, void *stream) {
-  if (int e = pvoc_gate(p, pvoc_shape_check(p, op, in, out, F, par, table, flags, lowest, coefs, true))) return pvoc_done(e);
-  ENTER_DEVICE(p->di.device);
-  hipStream_t s = (hipStream_t)stream;
-  HIP_TRY(p->order.use(s));
-  PvocShapeArgs a;
-  a.op = op;
-  a.logn = ilog2(p->M);
-  a.M = p->M;
-  a.channels = p->channels;
-  a.F = F;
-  a.in = (const cpx *)in;
-  a.out = (cpx *)out;
-  a.par = (const float *)par;
-  a.table = pvoc_shape_table(op) ? (const float *)table : nullptr;
-  a.reject = flags & 1;
-  a.lowest = lowest;
-  a.coefs = coefs;
-  a.bpf = p->bpf;
-  a.half = (const cpx *)p->half.p;
-  a.w2 = (const cpx *)p->w2.p;
-  a.grid_max = p->ops_grid_max;
-  HIP_TRY(launch_pvoc_shape(a, p->di, s));
-  return CLFA_SUCCESS;
-}
 
 // the values of one row the blocking form accepts: those the op names finite, and the op's ranges
 static bool pvoc_shape_row_ok(int op, const float *r) {
@@ -560,33 +560,48 @@ static bool pvoc_shape_row_ok(int op, const float *r) {
   }
 }
 
-// the blocking form: the same checks on the host arrays, then the per-frame values, then copies around the device form
-static int pvoc_shape_host(clfa_pvoc *p, int op, const float *in, float *out, long F, const float *par, const float *table,
-                           int flags, int lowest, int coefs) {
-  const int chk = pvoc_shape_check(p, op, in, out, F, par, table, flags, lowest, coefs, false);
-  if (chk < 0) return chk;
-  for (long f = 0; f < F; f++)
-    if (!pvoc_shape_row_ok(op, par + 4 * f)) return CLFA_INVALID_VALUE;
-  if (int e = pvoc_gate(p, chk)) return pvoc_done(e);
-  const bool tab = pvoc_shape_table(op);
+// The table is looked at for MASK and STENCIL only; flags: bit 0, for BAND alone; lowest and coefs: WARP's.
+static int pvoc_shape_call(clfa_pvoc *p, bool blocking, int op, const void *in, void *out, long F, const void *par,
+                           const void *table, int flags, int lowest, int coefs, void *stream) {
+  if (int e = pvoc_usable(p)) return e;
+  const bool scalars_ok = op >= PVOC_BAND && op <= PVOC_WARP && !(flags & ~(op == PVOC_BAND ? 1 : 0)) &&
+                          !(op == PVOC_WARP && (lowest < 1 || lowest > p->M - 1 || coefs < 1 || coefs >= p->M));
   const size_t fbytes = pvoc_frame_bytes(p, F);
-  return pvoc_staged(p, {{false, in, &p->sframes, fbytes}, {true, out, &p->sop_out, fbytes},
-                         {false, par, &p->sop_par, 4 * sizeof(float) * (size_t)F},
-                         {false, tab ? table : nullptr, &p->sshape_tab, sizeof(float) * (size_t)(p->M + 1)}}, [&] {
-                       return pvoc_shape_dev(p, op, p->sframes.p, p->sop_out.p, F, p->sop_par.p, tab ? p->sshape_tab.p : nullptr,
-                                             flags, lowest, coefs, p->stream);
-                     });
+  const PvocArray arrays[] = {{in, fbytes, 8, false, &clfa_pvoc::sframes},
+                              {out, fbytes, 8, true, &clfa_pvoc::sop_out},
+                              {par, 4 * sizeof(float) * (size_t)F, 4, false, &clfa_pvoc::sop_par},
+                              {table, sizeof(float) * (size_t)(p->M + 1), 4, false, &clfa_pvoc::sshape_tab,
+                               op == PVOC_MASK || op == PVOC_STENCIL}};
+  const auto values_ok = [&] {
+    for (long f = 0; f < F; f++)
+      if (!pvoc_shape_row_ok(op, (const float *)par + 4 * f)) return false;
+    return true;
+  };
+  return pvoc_call(p, blocking, stream, scalars_ok, F, arrays, CLFA_SUCCESS, values_ok, [&](const void *const *d, hipStream_t s) {
+    PvocShapeArgs a;
+    pvoc_frames_args(p, F, a);
+    a.op = op;
+    a.in = (const cpx *)d[0];
+    a.out = (cpx *)d[1];
+    a.par = (const float *)d[2];
+    a.table = (const float *)d[3];
+    a.reject = flags & 1;
+    a.lowest = lowest;
+    a.coefs = coefs;
+    a.bpf = p->bpf;
+    return launch_pvoc_shape(a, p->di, s);
+  });
 }
 
 extern "C" {
 
 int clfa_pvoc_shape_dev(clfa_pvoc *p, int op, const void *frames_in, void *frames_out, long F, const void *par,
                         const void *table, int flags, int lowest_bin, int coefs, void *stream) {
-  return pvoc_shape_dev(p, op, frames_in, frames_out, F, par, table, flags, lowest_bin, coefs, stream);
+  return pvoc_shape_call(p, false, op, frames_in, frames_out, F, par, table, flags, lowest_bin, coefs, stream);
 }
 int clfa_pvoc_shape(clfa_pvoc *p, int op, const float *frames_in, float *frames_out, long F, const float *par,
                     const float *table, int flags, int lowest_bin, int coefs) {
-  return pvoc_shape_host(p, op, frames_in, frames_out, F, par, table, flags, lowest_bin, coefs);
+  return pvoc_shape_call(p, true, op, frames_in, frames_out, F, par, table, flags, lowest_bin, coefs, nullptr);
 }
 const char *clfa_pvoc_shape_kernel_name(const clfa_pvoc *p, int op) {
   if (!p || p->err || op < PVOC_BAND || op > PVOC_WARP) return "";
@@ -599,25 +614,7 @@ const char *clfa_pvoc_shape_kernel_name(const clfa_pvoc *p, int op) {
 // frames -> frames along the stream, with carried state: blur, smooth, freeze (pvoc_time.hip)
 // ---------------------------------------------------------------------------------
 
-// The checks that need no device, before the object's own error (as pvoc_ops_check).  0 = go on, 1 = a successful no-op,
-// < 0 = the error.  BLUR does not look at q.  Whether the blur has been set up is pvoc_time_ready's, after these (and, in
-// the blocking form, after the per-frame values).
-static int pvoc_time_check(const clfa_pvoc *p, int op, const void *in, const void *out, long F, const void *pp,
-                           const void *qq, bool device_ptrs) {
-  if (!p) return CLFA_INVALID_VALUE;
-  if (!p->M) return p->err ? p->err : CLFA_INVALID_VALUE;
-  if (op < PVOC_BLUR || op > PVOC_FREEZE) return CLFA_INVALID_VALUE;
-  if (!pvoc_count_ok(F)) return CLFA_INVALID_VALUE;
-  if (F == 0) return 1;
-  if (!in || !out || !pp || (op != PVOC_BLUR && !qq)) return CLFA_INVALID_VALUE;
-  if (op == PVOC_BLUR) qq = nullptr;
-  if (device_ptrs && (((uintptr_t)in & 7) || ((uintptr_t)out & 7) || ((uintptr_t)pp & 3) || ((uintptr_t)qq & 3)))
-    return CLFA_INVALID_VALUE;
-  const size_t fbytes = pvoc_frame_bytes(p, F), pbytes = sizeof(float) * (size_t)F;
-  if (spans_overlap(in, fbytes, out, fbytes) || spans_overlap(pp, pbytes, out, fbytes)) return CLFA_INVALID_VALUE;
-  if (qq && spans_overlap(qq, pbytes, out, fbytes)) return CLFA_INVALID_VALUE;
-  return CLFA_SUCCESS;
-}
+// whether the blur has been set up: asked after the arguments (and, in the blocking form, after the per-frame values)
 static int pvoc_time_ready(const clfa_pvoc *p, int op) {
   return op == PVOC_BLUR && !p->blur_max ? CLFA_INVALID_OPERATION : CLFA_SUCCESS;
 }
@@ -626,56 +623,46 @@ static DevBuf clfa_pvoc::*pvoc_time_state(int op) {
   return op == PVOC_BLUR ? &clfa_pvoc::bhist : (op == PVOC_SMOOTH ? &clfa_pvoc::tsmooth : &clfa_pvoc::theld);
 }
 
-static int pvoc_time_dev(clfa_pvoc *p, int op, const void *in, void *out, long F, const void *pp, const void *qq,
-                         void *stream) {
-  int chk = pvoc_time_check(p, op, in, out, F, pp, qq, true);
-  if (chk == 0) chk = pvoc_time_ready(p, op);
-  if (int e = pvoc_gate(p, chk)) return pvoc_done(e);
-  ENTER_DEVICE(p->di.device);
-  hipStream_t s = (hipStream_t)stream;
-  HIP_TRY(p->order.use(s));
-  PvocTimeArgs a;
-  a.op = op;
-  a.M = p->M;
-  a.channels = p->channels;
-  a.F = F;
-  a.in = (const cpx *)in;
-  a.out = (cpx *)out;
-  a.p = (const float *)pp;
-  a.q = op == PVOC_BLUR ? nullptr : (const float *)qq;
-  a.state = (cpx *)(p->*pvoc_time_state(op)).p;
-  a.spare = (cpx *)p->bspare.p;
-  a.max_frames = p->blur_max;
-  a.grid_max = p->ops_grid_max;
-  HIP_TRY(launch_pvoc_time(a, p->di, s));
-  return CLFA_SUCCESS;
-}
-
-// the blocking form: the same checks on the host arrays, then the per-frame values, then copies around the device form
-static int pvoc_time_host(clfa_pvoc *p, int op, const float *in, float *out, long F, const float *pp, const float *qq) {
-  int chk = pvoc_time_check(p, op, in, out, F, pp, qq, false);
-  if (chk < 0) return chk;
-  for (long f = 0; f < F; f++) {
-    if (!std::isfinite(pp[f]) || (op != PVOC_BLUR && !std::isfinite(qq[f]))) return CLFA_INVALID_VALUE;
-    if (op == PVOC_BLUR && (!(pp[f] >= 1.f) || (p->blur_max && !(pp[f] <= (float)p->blur_max)))) return CLFA_INVALID_VALUE;
-    if (op == PVOC_SMOOTH && !(pp[f] >= 0.f && pp[f] <= 1.f && qq[f] >= 0.f && qq[f] <= 1.f)) return CLFA_INVALID_VALUE;
-  }
-  if (chk == 0) chk = pvoc_time_ready(p, op);
-  if (int e = pvoc_gate(p, chk)) return pvoc_done(e);
-  const bool blur = op == PVOC_BLUR;
+// BLUR does not look at q.  The blocking form asks finite values, the blur's lengths in 1..max_frames (where it is set
+// up) and the smoothing's weights in [0, 1].
+static int pvoc_time_call(clfa_pvoc *p, bool blocking, int op, const void *in, void *out, long F, const void *pp,
+                          const void *qq, void *stream) {
+  if (int e = pvoc_usable(p)) return e;
+  const bool scalars_ok = op >= PVOC_BLUR && op <= PVOC_FREEZE;
   const size_t fbytes = pvoc_frame_bytes(p, F), pbytes = sizeof(float) * (size_t)F;
-  return pvoc_staged(p, {{false, in, &p->sframes, fbytes}, {true, out, &p->sop_out, fbytes}, {false, pp, &p->sop_par, pbytes},
-                         {false, blur ? nullptr : qq, &p->spair_q, pbytes}}, [&] {
-                       return pvoc_time_dev(p, op, p->sframes.p, p->sop_out.p, F, p->sop_par.p, blur ? nullptr : p->spair_q.p,
-                                            p->stream);
-                     });
+  const PvocArray arrays[] = {{in, fbytes, 8, false, &clfa_pvoc::sframes},
+                              {out, fbytes, 8, true, &clfa_pvoc::sop_out},
+                              {pp, pbytes, 4, false, &clfa_pvoc::sop_par},
+                              {qq, pbytes, 4, false, &clfa_pvoc::spair_q, op != PVOC_BLUR}};
+  const auto values_ok = [&] {
+    const float *P = (const float *)pp, *Q = (const float *)qq;
+    for (long f = 0; f < F; f++) {
+      if (!std::isfinite(P[f]) || (op != PVOC_BLUR && !std::isfinite(Q[f]))) return false;
+      if (op == PVOC_BLUR && (!(P[f] >= 1.f) || (p->blur_max && !(P[f] <= (float)p->blur_max)))) return false;
+      if (op == PVOC_SMOOTH && !(P[f] >= 0.f && P[f] <= 1.f && Q[f] >= 0.f && Q[f] <= 1.f)) return false;
+    }
+    return true;
+  };
+  return pvoc_call(p, blocking, stream, scalars_ok, F, arrays, pvoc_time_ready(p, op), values_ok,
+                   [&](const void *const *d, hipStream_t s) {
+                     PvocTimeArgs a;
+                     pvoc_frames_args(p, F, a);
+                     a.op = op;
+                     a.in = (const cpx *)d[0];
+                     a.out = (cpx *)d[1];
+                     a.p = (const float *)d[2];
+                     a.q = (const float *)d[3];
+                     a.state = (cpx *)(p->*pvoc_time_state(op)).p;
+                     a.spare = (cpx *)p->bspare.p;
+                     a.max_frames = p->blur_max;
+                     return launch_pvoc_time(a, p->di, s);
+                   });
 }
 
 extern "C" {
 
 int clfa_pvoc_blur_setup(clfa_pvoc *p, int max_frames) {
-  if (!p) return CLFA_INVALID_VALUE;
-  if (!p->M) return p->err ? p->err : CLFA_INVALID_VALUE;
+  if (int e = pvoc_usable(p)) return e;
   if (max_frames < 1 || max_frames > 4096) return CLFA_INVALID_VALUE;
   if (p->err) return p->err;
   ENTER_DEVICE(p->di.device);
@@ -697,11 +684,11 @@ int clfa_pvoc_blur_setup(clfa_pvoc *p, int max_frames) {
 
 int clfa_pvoc_time_dev(clfa_pvoc *p, int op, const void *frames_in, void *frames_out, long F, const void *pp,
                        const void *qq, void *stream) {
-  return pvoc_time_dev(p, op, frames_in, frames_out, F, pp, qq, stream);
+  return pvoc_time_call(p, false, op, frames_in, frames_out, F, pp, qq, stream);
 }
 int clfa_pvoc_time(clfa_pvoc *p, int op, const float *frames_in, float *frames_out, long F, const float *pp,
                    const float *qq) {
-  return pvoc_time_host(p, op, frames_in, frames_out, F, pp, qq);
+  return pvoc_time_call(p, true, op, frames_in, frames_out, F, pp, qq, nullptr);
 }
 
 int clfa_pvoc_time_read_state(clfa_pvoc *p, int op, float *host) {
@@ -730,52 +717,36 @@ const char *clfa_pvoc_time_kernel_name(const clfa_pvoc *p, int op) {
 // frames -> eight descriptors per frame, with carried state (pvoc_desc.hip)
 // ---------------------------------------------------------------------------------
 
-static size_t pvoc_desc_bytes(const clfa_pvoc *p, long F) { return 8 * sizeof(float) * (size_t)p->channels * (size_t)F; }
-
-// The checks that need no device, before the object's own error (as pvoc_ops_check).  0 = go on, 1 = a successful no-op,
-// < 0 = the error.
-static int pvoc_desc_check(const clfa_pvoc *p, const void *in, const void *desc, long F, int first_bin, int nbins,
-                           int rectify, bool device_ptrs) {
-  if (!p) return CLFA_INVALID_VALUE;
-  if (!p->M) return p->err ? p->err : CLFA_INVALID_VALUE;
-  if (!pvoc_count_ok(F)) return CLFA_INVALID_VALUE;
-  if (first_bin < 0 || nbins < 1 || (long)first_bin + nbins - 1 > p->M) return CLFA_INVALID_VALUE;
-  if (rectify != 0 && rectify != 1) return CLFA_INVALID_VALUE;
-  if (F == 0) return 1;
-  if (!in || !desc) return CLFA_INVALID_VALUE;
-  if (device_ptrs && (((uintptr_t)in & 7) || ((uintptr_t)desc & 3))) return CLFA_INVALID_VALUE;
-  if (spans_overlap(in, pvoc_frame_bytes(p, F), desc, pvoc_desc_bytes(p, F))) return CLFA_INVALID_VALUE;
-  return CLFA_SUCCESS;
+static int pvoc_desc_call(clfa_pvoc *p, bool blocking, const void *in, void *desc, long F, int first_bin, int nbins,
+                          int rectify, void *stream) {
+  if (int e = pvoc_usable(p)) return e;
+  const bool scalars_ok = first_bin >= 0 && nbins >= 1 && (long)first_bin + nbins - 1 <= p->M && (rectify == 0 || rectify == 1);
+  const PvocArray arrays[] = {{in, pvoc_frame_bytes(p, F), 8, false, &clfa_pvoc::sframes},
+                              {desc, 8 * sizeof(float) * (size_t)p->channels * (size_t)F, 4, true, &clfa_pvoc::sdesc}};
+  const auto launch = [&](const void *const *d, hipStream_t s) {
+    PvocDescArgs a;
+    pvoc_frames_args(p, F, a);
+    a.in = (const cpx *)d[0];
+    a.desc = (float *)d[1];
+    a.last = (cpx *)p->dlast.p;
+    a.lo = first_bin;
+    a.hi = first_bin + nbins - 1;
+    a.rectify = rectify;
+    a.cf = p->srs;
+    return launch_pvoc_desc(a, p->di, s);
+  };
+  return pvoc_call(p, blocking, stream, scalars_ok, F, arrays, CLFA_SUCCESS, pvoc_no_values, launch);
 }
 
 extern "C" {
 
 int clfa_pvoc_desc_dev(clfa_pvoc *p, const void *frames_in, void *desc, long F, int first_bin, int nbins, int rectify,
                        void *stream) {
-  if (int e = pvoc_gate(p, pvoc_desc_check(p, frames_in, desc, F, first_bin, nbins, rectify, true))) return pvoc_done(e);
-  ENTER_DEVICE(p->di.device);
-  hipStream_t s = (hipStream_t)stream;
-  HIP_TRY(p->order.use(s));
-  PvocDescArgs a;
-  a.M = p->M;
-  a.channels = p->channels;
-  a.F = F;
-  a.in = (const cpx *)frames_in;
-  a.desc = (float *)desc;
-  a.last = (cpx *)p->dlast.p;
-  a.lo = first_bin;
-  a.hi = first_bin + nbins - 1;
-  a.rectify = rectify;
-  a.cf = p->srs;
-  a.grid_max = p->ops_grid_max;
-  HIP_TRY(launch_pvoc_desc(a, p->di, s));
-  return CLFA_SUCCESS;
+  return pvoc_desc_call(p, false, frames_in, desc, F, first_bin, nbins, rectify, stream);
 }
 
 int clfa_pvoc_desc(clfa_pvoc *p, const float *frames_in, float *desc, long F, int first_bin, int nbins, int rectify) {
-  if (int e = pvoc_gate(p, pvoc_desc_check(p, frames_in, desc, F, first_bin, nbins, rectify, false))) return pvoc_done(e);
-  return pvoc_staged(p, {{false, frames_in, &p->sframes, pvoc_frame_bytes(p, F)}, {true, desc, &p->sdesc, pvoc_desc_bytes(p, F)}},
-                     [&] { return clfa_pvoc_desc_dev(p, p->sframes.p, p->sdesc.p, F, first_bin, nbins, rectify, p->stream); });
+  return pvoc_desc_call(p, true, frames_in, desc, F, first_bin, nbins, rectify, nullptr);
 }
 
 // the amps of the previous frame: the first of every pair the device holds
@@ -797,79 +768,61 @@ const char *clfa_pvoc_desc_kernel_name(const clfa_pvoc *p) { return !p || p->err
 // frames -> samples: the oscillator bank (pvoc_adsyn.hip)
 // ---------------------------------------------------------------------------------
 
-// The checks that need no device, before the object's own error (as pvoc_ops_check).  0 = go on, 1 = a successful no-op,
-// < 0 = the error.
-static int pvoc_adsyn_check(const clfa_pvoc *p, const void *frames, long F, const void *fmod, int first_bin, int nbins,
-                            int step, const void *signal, long signal_stride, bool device_ptrs) {
-  if (!p) return CLFA_INVALID_VALUE;
-  if (!p->M) return p->err ? p->err : CLFA_INVALID_VALUE;
-  if (!pvoc_count_ok(F)) return CLFA_INVALID_VALUE;
-  if (step < 1 || nbins < 1 || first_bin < 0 || (long)first_bin + ((long)nbins - 1) * step > p->M) return CLFA_INVALID_VALUE;
-  if (signal_stride < F * p->hop) return CLFA_INVALID_VALUE;
-  if (F == 0) return 1;
-  if (!frames || !signal) return CLFA_INVALID_VALUE;
-  if (device_ptrs && (((uintptr_t)frames & 7) || ((uintptr_t)signal & 3) || ((uintptr_t)fmod & 3))) return CLFA_INVALID_VALUE;
-  // the output's rows and the gaps between them, as one span
-  const size_t fbytes = pvoc_frame_bytes(p, F);
-  const size_t obytes = sizeof(float) * ((size_t)(p->channels - 1) * (size_t)signal_stride + (size_t)F * p->hop);
-  if (spans_overlap(frames, fbytes, signal, obytes)) return CLFA_INVALID_VALUE;
-  if (fmod && spans_overlap(fmod, sizeof(float) * (size_t)F, signal, obytes)) return CLFA_INVALID_VALUE;
-  return CLFA_SUCCESS;
-}
-
 static size_t pvoc_adsyn_ws_bytes(const clfa_pvoc *p) {
   return sizeof(unsigned long long) * pvoc_bins(p) * (size_t)p->acap + (sizeof(int) + sizeof(float)) * pvoc_bins(p);
+}
+
+// signal: channels rows of F hop floats, signal_stride floats apart at the caller's (the overlap rule takes the rows and
+// the gaps between them as one span), packed where the blocking form stages them.  A NULL fmod is none.
+static int pvoc_adsyn_call(clfa_pvoc *p, bool blocking, const void *frames, long F, const void *fmod, int first_bin, int nbins,
+                           int step, float gain, void *signal, long signal_stride, void *stream) {
+  if (int e = pvoc_usable(p)) return e;
+  const bool scalars_ok = step >= 1 && nbins >= 1 && first_bin >= 0 && (long)first_bin + ((long)nbins - 1) * step <= p->M &&
+                          pvoc_count_ok(F) && signal_stride >= F * p->hop;
+  const size_t row = sizeof(float) * (size_t)F * p->hop, pitch = sizeof(float) * (size_t)signal_stride;
+  const PvocArray arrays[] = {{frames, pvoc_frame_bytes(p, F), 8, false, &clfa_pvoc::sframes},
+                              {signal, row, 4, true, &clfa_pvoc::ssig, true, (size_t)p->channels, pitch},
+                              {fmod, sizeof(float) * (size_t)F, 4, false, &clfa_pvoc::sfmod, fmod != nullptr}};
+  const auto launch = [&](const void *const *d, hipStream_t s) {
+    const long held = p->acap;   // the whole workspace at the first need: its address never changes afterwards
+    if (int e = ensure_workspaces({{&p->aws, pvoc_adsyn_ws_bytes(p)}}, s)) return e;
+    PvocAdsynArgs a;
+    a.M = p->M;
+    a.channels = p->channels;
+    a.hop = p->hop;
+    a.F = F;
+    a.frames = (const float *)d[0];
+    a.fmod = (const float *)d[2];
+    a.first = first_bin;
+    a.nbins = nbins;
+    a.step = step;
+    a.gain = gain;
+    a.ks = p->ks;
+    a.phase = (unsigned long long *)p->aphase.p;
+    a.w = (int *)p->aw.p;
+    a.amp = (float *)p->aamp.p;
+    a.sums = (unsigned long long *)p->aws.p;
+    a.w0 = (int *)(a.sums + pvoc_bins(p) * (size_t)held);
+    a.a0 = (float *)(a.w0 + pvoc_bins(p));
+    a.ramp = (const float *)p->ramp.p;
+    a.signal = (float *)d[1];
+    a.sstride = blocking ? F * p->hop : signal_stride;
+    a.grid_max = p->adsyn_grid_max;
+    return pvoc_subbatches(F, held, [&](long f0, long nf) { return launch_pvoc_adsyn(a, f0, nf, p->di, s); });
+  };
+  return pvoc_call(p, blocking, stream, scalars_ok, F, arrays, CLFA_SUCCESS, pvoc_no_values, launch);
 }
 
 extern "C" {
 
 int clfa_pvoc_adsyn_dev(clfa_pvoc *p, const void *frames, long F, const void *fmod, int first_bin, int nbins, int step,
                         float gain, void *signal, long signal_stride, void *stream) {
-  if (int e = pvoc_gate(p, pvoc_adsyn_check(p, frames, F, fmod, first_bin, nbins, step, signal, signal_stride, true)))
-    return pvoc_done(e);
-  ENTER_DEVICE(p->di.device);
-  hipStream_t s = (hipStream_t)stream;
-  const long held = p->acap;   // the whole workspace at the first need: its address never changes afterwards
-  HIP_TRY(p->order.use(s));
-  if (int e = ensure_workspaces({{&p->aws, pvoc_adsyn_ws_bytes(p)}}, s)) return e;
-  PvocAdsynArgs a;
-  a.M = p->M;
-  a.channels = p->channels;
-  a.hop = p->hop;
-  a.F = F;
-  a.frames = (const float *)frames;
-  a.fmod = (const float *)fmod;
-  a.first = first_bin;
-  a.nbins = nbins;
-  a.step = step;
-  a.gain = gain;
-  a.ks = p->ks;
-  a.phase = (unsigned long long *)p->aphase.p;
-  a.w = (int *)p->aw.p;
-  a.amp = (float *)p->aamp.p;
-  a.sums = (unsigned long long *)p->aws.p;
-  a.w0 = (int *)(a.sums + pvoc_bins(p) * (size_t)held);
-  a.a0 = (float *)(a.w0 + pvoc_bins(p));
-  a.ramp = (const float *)p->ramp.p;
-  a.signal = (float *)signal;
-  a.sstride = signal_stride;
-  a.grid_max = p->adsyn_grid_max;
-  return pvoc_subbatches(F, held, [&](long f0, long nf) { return launch_pvoc_adsyn(a, f0, nf, p->di, s); });
+  return pvoc_adsyn_call(p, false, frames, F, fmod, first_bin, nbins, step, gain, signal, signal_stride, stream);
 }
 
 int clfa_pvoc_adsyn(clfa_pvoc *p, const float *frames, long F, const float *fmod, int first_bin, int nbins, int step,
                     float gain, float *signal, long signal_stride) {
-  if (int e = pvoc_gate(p, pvoc_adsyn_check(p, frames, F, fmod, first_bin, nbins, step, signal, signal_stride, false)))
-    return pvoc_done(e);
-  // the staged output's rows are packed, the caller's signal_stride floats apart
-  return pvoc_staged(p, {{false, frames, &p->sframes, pvoc_frame_bytes(p, F)},
-                         {true, signal, &p->ssig, sizeof(float) * (size_t)F * p->hop, (size_t)p->channels,
-                          sizeof(float) * (size_t)signal_stride},
-                         {false, fmod, &p->sfmod, sizeof(float) * (size_t)F}},
-                     [&] {
-                       return clfa_pvoc_adsyn_dev(p, p->sframes.p, F, fmod ? p->sfmod.p : nullptr, first_bin, nbins, step,
-                                                  gain, p->ssig.p, F * p->hop, p->stream);
-                     });
+  return pvoc_adsyn_call(p, true, frames, F, fmod, first_bin, nbins, step, gain, signal, signal_stride, nullptr);
 }
 
 int clfa_pvoc_adsyn_read_state(clfa_pvoc *p, unsigned long long *phase, int *w, float *amp) {

@@ -1,6 +1,7 @@
 // pvoc_ops.hip — operations on the (amp, freq) frames of clfa_pvoc (include/clfft_amd.h): pitch scale, frequency shift
-// and timed read.  All three are stateless, one launch per call, deterministic (gathers: no atomics).  The decoding of a
-// grid-stride item and the cap on a launch's workgroups are pvoc_device.hpp's, as in the other Pvoc kernel files.
+// and timed read.  All three are stateless, one launch per call, deterministic (gathers: no atomics).  The tile kernels'
+// prologue and launch (pvoc_bin, pvoc_tiles) are pvoc_device.hpp's, as in the other Pvoc kernel files; the envelope
+// kernel's launch and size dispatch (launch_pvoc_env, pvoc_env_dispatch) are pvoc_env.hpp's.
 //
 //   k_pvoc_map      scale and shift without keepform: a lane takes output bin j of one frame, finds its source bin and
 //                   writes the pair; rows of consecutive bins, 8 bytes per lane, no LDS.
@@ -73,11 +74,9 @@ __global__ __launch_bounds__(kOpsWG) void k_pvoc_map(const cpx *__restrict__ in,
                                                      int op, int lowest, float gain, float cf, float bpf) {
 #pragma unroll 1
   for (long item = blockIdx.x; item < items; item += gridDim.x) {
-    int tile;
+    int j;
     long f, c;
-    pvoc_item(item, tiles, F, tile, f, c);
-    const int j = tile * kOpsWG + (int)threadIdx.x;
-    if (j > M) continue;
+    if (!pvoc_bin<kOpsWG>(item, tiles, F, M, j, f, c)) continue;
     const long b = c * F + f;
     const float s = par[f];
     const cpx *row = in + b * (M + 1);
@@ -99,11 +98,9 @@ __global__ __launch_bounds__(kOpsWG) void k_pvoc_read(const cpx *__restrict__ in
                                                       int tiles, long items) {
 #pragma unroll 1
   for (long item = blockIdx.x; item < items; item += gridDim.x) {
-    int tile;
+    int j;
     long g, c;
-    pvoc_item(item, tiles, Fout, tile, g, c);
-    const int j = tile * kOpsWG + (int)threadIdx.x;
-    if (j > M) continue;
+    if (!pvoc_bin<kOpsWG>(item, tiles, Fout, M, j, g, c)) continue;
     const long b = c * Fout + g;
     const float p = fminf(fmaxf(pos[g], 0.f), (float)(Fin - 1));   // fmaxf(NaN, 0) = 0
     const long i = (long)floorf(p);
@@ -143,9 +140,9 @@ __global__ __launch_bounds__(LdsGeom<LOGN>::WG) void k_pvoc_formant(const cpx *_
   const long groups = (nframes + FPW - 1) / FPW;
 #pragma unroll 1
   for (long g = blockIdx.x; g < groups; g += gridDim.x) {
-    const long b0 = g * FPW;
-    const int nv = nframes - b0 < FPW ? (int)(nframes - b0) : FPW;   // frames of a ragged last group; the other slots
-    const int live = nv * B;                                         // run the chain on stale LDS and write nothing
+    const PvocEnvGroup<LOGN> grp(g, nframes);
+    const long b0 = grp.b0;
+    const int live = grp.live;
     // the frames in, once: the pairs stay in s_fr, the envelope of their amps lands in s_x (pvoc_env.hpp)
     pvoc_envelope<LOGN>(s_x, tab, w2, coefs, live, [&](int idx) {
       const cpx af = in[b0 * B + idx];
@@ -169,44 +166,21 @@ __global__ __launch_bounds__(LdsGeom<LOGN>::WG) void k_pvoc_formant(const cpx *_
   }
 }
 
-template <int LOGN>
-static hipError_t launch_pvoc_formant_n(const PvocOpsArgs &a, const DeviceInfo &di, hipStream_t s) {
-  using G = LdsGeom<LOGN>;
-  static int occ = 0;
-  if (!occ) {
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)k_pvoc_formant<LOGN>, G::WG, 0) != hipSuccess || nb < 1) {
-      (void)hipGetLastError();
-      nb = 1;
-    }
-    occ = nb;
-  }
-  const long nframes = (long)a.channels * a.F, groups = (nframes + G::FPW - 1) / G::FPW;
-  const int grid = pvoc_grid(groups, (long)di.num_cus * occ, a.grid_max);
-  hipLaunchKernelGGL((k_pvoc_formant<LOGN>), dim3(grid), dim3(G::WG), 0, s, a.in, a.out, a.par, a.F, nframes, a.op,
-                     a.lowest, a.coefs, a.gain, a.cf, a.bpf, a.half, a.w2);
-  return hipGetLastError();
-}
-
 hipError_t launch_pvoc_ops(const PvocOpsArgs &a, const DeviceInfo &di, hipStream_t s) {
   if (a.F <= 0 || a.channels <= 0) return hipSuccess;
   if (a.op != PVOC_READ && a.keepform) {
-    switch (a.logn) {
-#define CLFA_N(L) \
-  case L: return launch_pvoc_formant_n<L>(a, di, s);
-      CLFA_N(5) CLFA_N(6) CLFA_N(7) CLFA_N(8) CLFA_N(9) CLFA_N(10) CLFA_N(11) CLFA_N(12) CLFA_N(13)
-#undef CLFA_N
-      default:
-        return hipErrorInvalidValue;
-    }
+    const long nframes = (long)a.channels * a.F;
+    return pvoc_env_dispatch(a.logn, [&](auto L) {
+      constexpr int LOGN = decltype(L)::value;
+      return launch_pvoc_env<LOGN, k_pvoc_formant<LOGN>>(nframes, a.grid_max, di, s, a.in, a.out, a.par, a.F, nframes, a.op,
+                                                         a.lowest, a.coefs, a.gain, a.cf, a.bpf, a.half, a.w2);
+    });
   }
-  const int tiles = (a.M + 1 + kOpsWG - 1) / kOpsWG;
-  const long items = (long)a.channels * a.F * tiles;
-  const int grid = pvoc_grid(items, (long)di.num_cus * 16, a.grid_max);
+  const PvocTiles t = pvoc_tiles(a.M, kOpsWG, (long)a.channels * a.F, di, 16, a.grid_max);
   if (a.op == PVOC_READ)
-    hipLaunchKernelGGL(k_pvoc_read, dim3(grid), dim3(kOpsWG), 0, s, a.in, a.out, a.par, a.Fin, a.F, a.M, tiles, items);
+    hipLaunchKernelGGL(k_pvoc_read, dim3(t.grid), dim3(kOpsWG), 0, s, a.in, a.out, a.par, a.Fin, a.F, a.M, t.tiles, t.items);
   else
-    hipLaunchKernelGGL(k_pvoc_map, dim3(grid), dim3(kOpsWG), 0, s, a.in, a.out, a.par, a.F, a.M, tiles, items, a.op,
+    hipLaunchKernelGGL(k_pvoc_map, dim3(t.grid), dim3(kOpsWG), 0, s, a.in, a.out, a.par, a.F, a.M, t.tiles, t.items, a.op,
                        a.lowest, a.gain, a.cf, a.bpf);
   return hipGetLastError();
 }

@@ -1,6 +1,7 @@
 // pvoc_pair.hip — operations on two streams of (amp, freq) frames of clfa_pvoc (include/clfft_amd.h): cross-synthesis,
-// morph, spectral filter, spectral maximum and the channel vocoder.  Stateless, one launch per call, no atomics; the
-// decoding of a grid-stride item and the cap on a launch's workgroups are pvoc_device.hpp's.
+// morph, spectral filter, spectral maximum and the channel vocoder.  Stateless, one launch per call, no atomics; the tile
+// kernel's prologue and launch (pvoc_bin, pvoc_tiles) are pvoc_device.hpp's, the vocoder's launch and size dispatch
+// (launch_pvoc_env, pvoc_env_dispatch) pvoc_env.hpp's.
 //
 //   k_pvoc_pair    cross, morph, filter, mix: a lane takes bin k of one frame, reads the pair of a and the pair of b and
 //                  writes one pair; rows of consecutive bins, 8 bytes per lane and stream (16 in, 8 out), no LDS.  The
@@ -61,11 +62,9 @@ __global__ __launch_bounds__(kPairWG) void k_pvoc_pair(const cpx *a, const cpx *
                                                        long items, int op) {
 #pragma unroll 1
   for (long item = blockIdx.x; item < items; item += gridDim.x) {
-    int tile;
+    int k;
     long f, c;
-    pvoc_item(item, tiles, F, tile, f, c);
-    const int k = tile * kPairWG + (int)threadIdx.x;
-    if (k > M) continue;
+    if (!pvoc_bin<kPairWG>(item, tiles, F, M, k, f, c)) continue;
     const long e = (c * F + f) * (M + 1) + k;
     float P = 0.f, Q = 0.f;
     if (op != PVOC_MIX) {
@@ -102,10 +101,10 @@ __global__ __launch_bounds__(LdsGeom<LOGN>::WG) void k_pvoc_vocode(const cpx *a,
   const long groups = (nframes + FPW - 1) / FPW;
 #pragma unroll 1
   for (long g = blockIdx.x; g < groups; g += gridDim.x) {
-    const long b0 = g * FPW;
-    const int nv = nframes - b0 < FPW ? (int)(nframes - b0) : FPW;   // frames of a ragged last group; the other slots
-    const int live = nv * B;                                         // run the chains on stale LDS and write nothing
-    if (tid < nv) {   // the frames' (p, q); the barriers of the envelope stages stand between this and their use
+    const PvocEnvGroup<LOGN> grp(g, nframes);
+    const long b0 = grp.b0;
+    const int live = grp.live;
+    if (tid < grp.nv) {   // the frames' (p, q); the barriers of the envelope stages stand between this and their use
       const long f = (b0 + tid) % F;
       s_pq[tid] = mk(p[f], q[f]);
     }
@@ -132,41 +131,19 @@ __global__ __launch_bounds__(LdsGeom<LOGN>::WG) void k_pvoc_vocode(const cpx *a,
   }
 }
 
-template <int LOGN>
-static hipError_t launch_pvoc_vocode_n(const PvocPairArgs &a, const DeviceInfo &di, hipStream_t s) {
-  using G = LdsGeom<LOGN>;
-  static int occ = 0;
-  if (!occ) {
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)k_pvoc_vocode<LOGN>, G::WG, 0) != hipSuccess || nb < 1) {
-      (void)hipGetLastError();
-      nb = 1;
-    }
-    occ = nb;
-  }
-  const long nframes = (long)a.channels * a.F, groups = (nframes + G::FPW - 1) / G::FPW;
-  const int grid = pvoc_grid(groups, (long)di.num_cus * occ, a.grid_max);
-  hipLaunchKernelGGL((k_pvoc_vocode<LOGN>), dim3(grid), dim3(G::WG), 0, s, a.a, a.b, a.out, a.p, a.q, a.F, nframes,
-                     a.coefs, a.half, a.w2);
-  return hipGetLastError();
-}
-
 hipError_t launch_pvoc_pair(const PvocPairArgs &a, const DeviceInfo &di, hipStream_t s) {
   if (a.F <= 0 || a.channels <= 0) return hipSuccess;
   if (a.op == PVOC_VOCODE) {
-    switch (a.logn) {
-#define CLFA_N(L) \
-  case L: return launch_pvoc_vocode_n<L>(a, di, s);
-      CLFA_N(5) CLFA_N(6) CLFA_N(7) CLFA_N(8) CLFA_N(9) CLFA_N(10) CLFA_N(11) CLFA_N(12) CLFA_N(13)
-#undef CLFA_N
-      default:
-        return hipErrorInvalidValue;
-    }
+    const long nframes = (long)a.channels * a.F;
+    return pvoc_env_dispatch(a.logn, [&](auto L) {
+      constexpr int LOGN = decltype(L)::value;
+      return launch_pvoc_env<LOGN, k_pvoc_vocode<LOGN>>(nframes, a.grid_max, di, s, a.a, a.b, a.out, a.p, a.q, a.F, nframes,
+                                                        a.coefs, a.half, a.w2);
+    });
   }
-  const int tiles = (a.M + 1 + kPairWG - 1) / kPairWG;
-  const long items = (long)a.channels * a.F * tiles;
-  const int grid = pvoc_grid(items, (long)di.num_cus * 16, a.grid_max);
-  hipLaunchKernelGGL(k_pvoc_pair, dim3(grid), dim3(kPairWG), 0, s, a.a, a.b, a.out, a.p, a.q, a.F, a.M, tiles, items, a.op);
+  const PvocTiles t = pvoc_tiles(a.M, kPairWG, (long)a.channels * a.F, di, 16, a.grid_max);
+  hipLaunchKernelGGL(k_pvoc_pair, dim3(t.grid), dim3(kPairWG), 0, s, a.a, a.b, a.out, a.p, a.q, a.F, a.M, t.tiles, t.items,
+                     a.op);
   return hipGetLastError();
 }
 

@@ -1,7 +1,8 @@
 // pvoc_shape.hip — operations that reshape ONE stream of (amp, freq) frames of clfa_pvoc along the bins
 // (include/clfft_amd.h): band pass / reject, table mask, stencil, arpeggiator, peak frequency lock and the warp of the
-// spectral envelope.  Stateless, one launch per call, no atomics; the decoding of a grid-stride item, the cap on a
-// launch's workgroups and the pitch scale's source map are pvoc_device.hpp's.  par: F rows of 4 floats, one per frame.
+// spectral envelope.  Stateless, one launch per call, no atomics; the tile kernels' prologue and launch (pvoc_bin,
+// pvoc_tiles) and the pitch scale's source map are pvoc_device.hpp's, the warp's launch and size dispatch
+// (launch_pvoc_env, pvoc_env_dispatch) pvoc_env.hpp's.  par: F rows of 4 floats, one per frame.
 //
 //   k_pvoc_shape  band, mask, stencil, arp: a lane takes bin k of one frame, reads its pair and writes one pair; rows of
 //                 consecutive bins, 8 bytes in and 8 out per lane, no LDS.  The op is a kernel argument: every lane of a
@@ -109,11 +110,9 @@ __global__ __launch_bounds__(kShapeWG) void k_pvoc_shape(const cpx *__restrict__
                                                          long F, int M, int tiles, long items, int op, int reject) {
 #pragma unroll 1
   for (long item = blockIdx.x; item < items; item += gridDim.x) {
-    int tile;
+    int k;
     long f, c;
-    pvoc_item(item, tiles, F, tile, f, c);
-    const int k = tile * kShapeWG + (int)threadIdx.x;
-    if (k > M) continue;
+    if (!pvoc_bin<kShapeWG>(item, tiles, F, M, k, f, c)) continue;
     const long e = (c * F + f) * (M + 1) + k;
     float r[4] = {0.f, 0.f, 0.f, 0.f};   // the columns the op names
     const int cols = op == PVOC_BAND ? 4 : (op == PVOC_MASK ? 1 : (op == PVOC_STENCIL ? 2 : 3));
@@ -135,7 +134,7 @@ __global__ __launch_bounds__(kShapeWG) void k_pvoc_lock(const cpx *__restrict__ 
   for (long item = blockIdx.x; item < items; item += gridDim.x) {
     int tile;
     long f, c;
-    pvoc_item(item, tiles, F, tile, f, c);
+    pvoc_item(item, tiles, F, tile, f, c);   // not pvoc_bin: the lanes past bin M fetch the halo and keep the barriers
     const int k0 = tile * kShapeWG, j = k0 + tid;
     const cpx *row = in + (c * F + f) * (M + 1);
     cpx *orow = out + (c * F + f) * (M + 1);
@@ -197,9 +196,9 @@ __global__ __launch_bounds__(LdsGeom<LOGN>::WG) void k_pvoc_warp(const cpx *__re
   const long groups = (nframes + FPW - 1) / FPW;
 #pragma unroll 1
   for (long g = blockIdx.x; g < groups; g += gridDim.x) {
-    const long b0 = g * FPW;
-    const int nv = nframes - b0 < FPW ? (int)(nframes - b0) : FPW;   // frames of a ragged last group; the other slots
-    const int live = nv * B;                                         // run the chain on stale LDS and write nothing
+    const PvocEnvGroup<LOGN> grp(g, nframes);
+    const long b0 = grp.b0;
+    const int live = grp.live;
     pvoc_envelope<LOGN>(s_x, tab, w2, coefs, live, [&](int idx) {
       const cpx af = in[b0 * B + idx];
       s_fr[idx] = af;
@@ -220,46 +219,23 @@ __global__ __launch_bounds__(LdsGeom<LOGN>::WG) void k_pvoc_warp(const cpx *__re
   }
 }
 
-template <int LOGN>
-static hipError_t launch_pvoc_warp_n(const PvocShapeArgs &a, const DeviceInfo &di, hipStream_t s) {
-  using G = LdsGeom<LOGN>;
-  static int occ = 0;
-  if (!occ) {
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)k_pvoc_warp<LOGN>, G::WG, 0) != hipSuccess || nb < 1) {
-      (void)hipGetLastError();
-      nb = 1;
-    }
-    occ = nb;
-  }
-  const long nframes = (long)a.channels * a.F, groups = (nframes + G::FPW - 1) / G::FPW;
-  const int grid = pvoc_grid(groups, (long)di.num_cus * occ, a.grid_max);
-  hipLaunchKernelGGL((k_pvoc_warp<LOGN>), dim3(grid), dim3(G::WG), 0, s, a.in, a.out, a.par, a.F, nframes, a.lowest,
-                     a.coefs, a.bpf, a.half, a.w2);
-  return hipGetLastError();
-}
-
 hipError_t launch_pvoc_shape(const PvocShapeArgs &a, const DeviceInfo &di, hipStream_t s) {
   if (a.F <= 0 || a.channels <= 0) return hipSuccess;
   if (a.op == PVOC_WARP) {
-    switch (a.logn) {
-#define CLFA_N(L) \
-  case L: return launch_pvoc_warp_n<L>(a, di, s);
-      CLFA_N(5) CLFA_N(6) CLFA_N(7) CLFA_N(8) CLFA_N(9) CLFA_N(10) CLFA_N(11) CLFA_N(12) CLFA_N(13)
-#undef CLFA_N
-      default:
-        return hipErrorInvalidValue;
-    }
+    const long nframes = (long)a.channels * a.F;
+    return pvoc_env_dispatch(a.logn, [&](auto L) {
+      constexpr int LOGN = decltype(L)::value;
+      return launch_pvoc_env<LOGN, k_pvoc_warp<LOGN>>(nframes, a.grid_max, di, s, a.in, a.out, a.par, a.F, nframes, a.lowest,
+                                                      a.coefs, a.bpf, a.half, a.w2);
+    });
   }
   if (a.op < PVOC_BAND || a.op > PVOC_LOCK) return hipErrorInvalidValue;
-  const int tiles = (a.M + 1 + kShapeWG - 1) / kShapeWG;
-  const long items = (long)a.channels * a.F * tiles;
-  const int grid = pvoc_grid(items, (long)di.num_cus * 16, a.grid_max);
+  const PvocTiles t = pvoc_tiles(a.M, kShapeWG, (long)a.channels * a.F, di, 16, a.grid_max);
   if (a.op == PVOC_LOCK)
-    hipLaunchKernelGGL(k_pvoc_lock, dim3(grid), dim3(kShapeWG), 0, s, a.in, a.out, a.par, a.F, a.M, tiles, items);
+    hipLaunchKernelGGL(k_pvoc_lock, dim3(t.grid), dim3(kShapeWG), 0, s, a.in, a.out, a.par, a.F, a.M, t.tiles, t.items);
   else
-    hipLaunchKernelGGL(k_pvoc_shape, dim3(grid), dim3(kShapeWG), 0, s, a.in, a.out, a.par, a.table, a.F, a.M, tiles,
-                       items, a.op, a.reject);
+    hipLaunchKernelGGL(k_pvoc_shape, dim3(t.grid), dim3(kShapeWG), 0, s, a.in, a.out, a.par, a.table, a.F, a.M, t.tiles,
+                       t.items, a.op, a.reject);
   return hipGetLastError();
 }
 

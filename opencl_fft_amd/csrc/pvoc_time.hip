@@ -2,7 +2,7 @@
 // (blur), one-pole low-pass (smooth) and freeze.  Each carries a state from call to call.  An output value is a fixed
 // sequence of single float32 roundings of the stream's values, so the bits do not depend on how the stream is cut into
 // calls, on the grid or on the run length: there is no parallel float sum or scan here, no atomics and no waiting between
-// workgroups.  The decoding of a grid-stride item and the cap on a launch's workgroups are pvoc_device.hpp's.
+// workgroups.  The tile kernels' prologue and launch (pvoc_bin, pvoc_tiles) are pvoc_device.hpp's.
 //
 //   k_pvoc_blur    an item is (channel, run of kTimeRun consecutive frames, tile of 256 bins), a lane per bin.  The lane
 //                  forms each output's sum in the defined order, oldest frame first: O(n) additions per output by
@@ -56,11 +56,9 @@ __global__ __launch_bounds__(kTimeWG) void k_pvoc_blur(const cpx *in, cpx *__res
 #pragma clang fp contract(off)
 #pragma unroll 1
   for (long item = blockIdx.x; item < items; item += gridDim.x) {
-    int tile;
+    int k;
     long r, c;
-    pvoc_item(item, tiles, runs, tile, r, c);
-    const int k = tile * kTimeWG + (int)threadIdx.x;
-    if (k > M) continue;
+    if (!pvoc_bin<kTimeWG>(item, tiles, runs, M, k, r, c)) continue;
     const long f0 = r * kTimeRun, f1 = f0 + kTimeRun < F ? f0 + kTimeRun : F;
     const cpx *ic = in + c * F * (M + 1) + k;          // frame t >= 0 of the stream
     const cpx *hc = hist + (c * L + L) * (M + 1) + k;  // frame t < 0 (t >= -L: n <= max_frames)
@@ -102,11 +100,9 @@ __global__ __launch_bounds__(kTimeWG) void k_pvoc_tail(const cpx *hist, int L, c
                                                        int rows, int M, int tiles, long items) {
 #pragma unroll 1
   for (long item = blockIdx.x; item < items; item += gridDim.x) {
-    int tile;
+    int k;
     long j, c;
-    pvoc_item(item, tiles, rows, tile, j, c);
-    const int k = tile * kTimeWG + (int)threadIdx.x;
-    if (k > M) continue;
+    if (!pvoc_bin<kTimeWG>(item, tiles, rows, M, k, j, c)) continue;
     const long t = F - rows + j;
     dst[(c * rows + j) * (M + 1) + k] = t < 0 ? hist[(c * L + L + t) * (M + 1) + k] : src[(c * F + t) * (M + 1) + k];
   }
@@ -119,11 +115,9 @@ __global__ __launch_bounds__(kSmoothWG) void k_pvoc_smooth(const cpx *__restrict
   constexpr int G = kSmoothGroup;
 #pragma unroll 1
   for (long item = blockIdx.x; item < items; item += gridDim.x) {
-    int tile;
+    int k;
     long j, c;
-    pvoc_item(item, tiles, 1, tile, j, c);
-    const int k = tile * kSmoothWG + (int)threadIdx.x;
-    if (k > M) continue;
+    if (!pvoc_bin<kSmoothWG>(item, tiles, 1, M, k, j, c)) continue;
     const long row = M + 1;
     const cpx *x = in + c * F * row + k;
     cpx *o = out + c * F * row + k;
@@ -162,9 +156,9 @@ __global__ __launch_bounds__(kTimeWG) void k_pvoc_freeze(const cpx *__restrict__
   int buf = 0;
 #pragma unroll 1
   for (long item = blockIdx.x; item < items; item += gridDim.x) {
-    int tile;
+    int k;
     long r, c;
-    pvoc_item(item, tiles, runs, tile, r, c);
+    const bool in_row = pvoc_bin<kTimeWG>(item, tiles, runs, M, k, r, c);
     const long f0 = r * kTimeRun, f1 = f0 + kTimeRun < F ? f0 + kTimeRun : F;
     // g of frame f0, per column: every lane of the workgroup takes part and ends with the same answers
     long ga = -1, gf = -1;
@@ -188,8 +182,7 @@ __global__ __launch_bounds__(kTimeWG) void k_pvoc_freeze(const cpx *__restrict__
         if (v >= 0) gf = v, df = true;
       }
     }
-    const int k = tile * kTimeWG + tid;
-    if (k > M) continue;
+    if (!in_row) continue;   // only now: every lane took part in the search
     const cpx *ic = in + c * F * (M + 1) + k;
     const cpx h = held[c * (M + 1) + k];
 #pragma unroll 1
@@ -216,10 +209,8 @@ __global__ __launch_bounds__(kTimeWG) void k_pvoc_fill(cpx *__restrict__ dst, in
 
 static hipError_t launch_pvoc_tail(const PvocTimeArgs &a, const cpx *hist, int L, const cpx *src, cpx *dst, int rows,
                                    const DeviceInfo &di, hipStream_t s) {
-  const int tiles = (a.M + 1 + kTimeWG - 1) / kTimeWG;
-  const long items = (long)a.channels * rows * tiles;
-  const int grid = pvoc_grid(items, (long)di.num_cus * 16, a.grid_max);
-  hipLaunchKernelGGL(k_pvoc_tail, dim3(grid), dim3(kTimeWG), 0, s, hist, L, src, a.F, dst, rows, a.M, tiles, items);
+  const PvocTiles t = pvoc_tiles(a.M, kTimeWG, (long)a.channels * rows, di, 16, a.grid_max);
+  hipLaunchKernelGGL(k_pvoc_tail, dim3(t.grid), dim3(kTimeWG), 0, s, hist, L, src, a.F, dst, rows, a.M, t.tiles, t.items);
   return hipGetLastError();
 }
 
@@ -237,23 +228,23 @@ hipError_t launch_pvoc_time_last(const cpx *src, long F, cpx *dst, int channels,
 hipError_t launch_pvoc_time(const PvocTimeArgs &a, const DeviceInfo &di, hipStream_t s) {
   if (a.F <= 0 || a.channels <= 0) return hipSuccess;
   if (a.op == PVOC_SMOOTH) {
-    const int tiles = (a.M + 1 + kSmoothWG - 1) / kSmoothWG;
-    const long items = (long)a.channels * tiles;
-    const int grid = pvoc_grid(items, (long)di.num_cus * 32, a.grid_max);
-    hipLaunchKernelGGL(k_pvoc_smooth, dim3(grid), dim3(kSmoothWG), 0, s, a.in, a.out, a.p, a.q, a.state, a.F, a.M, tiles, items);
+    const PvocTiles t = pvoc_tiles(a.M, kSmoothWG, a.channels, di, 32, a.grid_max);
+    hipLaunchKernelGGL(k_pvoc_smooth, dim3(t.grid), dim3(kSmoothWG), 0, s, a.in, a.out, a.p, a.q, a.state, a.F, a.M, t.tiles,
+                       t.items);
     return hipGetLastError();
   }
-  const int tiles = (a.M + 1 + kTimeWG - 1) / kTimeWG;
-  const long runs = (a.F + kTimeRun - 1) / kTimeRun, items = (long)a.channels * runs * tiles;
-  const int grid = pvoc_grid(items, (long)di.num_cus * 16, a.grid_max);
+  const long runs = (a.F + kTimeRun - 1) / kTimeRun;
+  const PvocTiles t = pvoc_tiles(a.M, kTimeWG, a.channels * runs, di, 16, a.grid_max);
   if (a.op == PVOC_FREEZE) {
-    hipLaunchKernelGGL(k_pvoc_freeze, dim3(grid), dim3(kTimeWG), 0, s, a.in, a.out, a.p, a.q, a.state, a.F, a.M, tiles, runs, items);
+    hipLaunchKernelGGL(k_pvoc_freeze, dim3(t.grid), dim3(kTimeWG), 0, s, a.in, a.out, a.p, a.q, a.state, a.F, a.M, t.tiles, runs,
+                       t.items);
     if (hipError_t e = hipGetLastError()) return e;
     return launch_pvoc_tail(a, nullptr, 0, a.out, a.state, 1, di, s);
   }
   if (a.op != PVOC_BLUR) return hipErrorInvalidValue;
   const int L = a.max_frames - 1;
-  hipLaunchKernelGGL(k_pvoc_blur, dim3(grid), dim3(kTimeWG), 0, s, a.in, a.out, a.p, a.state, a.F, a.M, L, a.max_frames, tiles, runs, items);
+  hipLaunchKernelGGL(k_pvoc_blur, dim3(t.grid), dim3(kTimeWG), 0, s, a.in, a.out, a.p, a.state, a.F, a.M, L, a.max_frames, t.tiles,
+                     runs, t.items);
   if (hipError_t e = hipGetLastError()) return e;
   if (L == 0) return hipSuccess;
   if (hipError_t e = launch_pvoc_tail(a, a.state, L, a.in, a.spare, L, di, s)) return e;
