@@ -3,10 +3,11 @@ model, tests/test_pvoc_desc_cpu.py runs the model's mutants on the same ones (a 
 A case is (name, frames (C, F, M + 1, 2) float32, first_bin, nbins, rectify); nbins None = up to M."""
 import numpy as np
 
+from tests import pvoc_inputs
 from tests.pvoc_desc_model import lanes
+from tests.pvoc_inputs import SR
 
 f32 = np.float32
-SR = 48000.0
 SIZES = (64, 128, 256, 512, 1024, 16384)      # W below a wave, one wave, two waves, 256 with one row, two rows, 32 rows
 MORE_SIZES = (2048, 4096, 8192)
 FRAME_COUNTS = (1, 5, 37, 200)
@@ -22,10 +23,9 @@ def plain(size, C, F, seed):
 
 
 def raw(size, C, F, seed):
-    """tests/test_gpu_pvoc_pair.py's raw(): amps log-uniform over 1e-30 .. 1e30 with a few zeros, any freq; pow and flux
+    """tests/pvoc_inputs.py's raw(): amps log-uniform over 1e-30 .. 1e30 with a few zeros, any freq; pow and flux
     overflow to inf on purpose"""
-    from tests.test_gpu_pvoc_pair import raw as pair_raw
-    return pair_raw(size, C, F, seed)
+    return pvoc_inputs.raw(size, C, F, seed)
 
 
 def ranges(M):

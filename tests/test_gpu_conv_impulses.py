@@ -19,12 +19,12 @@ import pytest
 import opencl_fft_amd as fa
 from oracle import oracle
 from tests import conv_exact as cx
+from tests import gpu_guard
 from tests.test_gpu_pconv_fade import SWEEP
 from tests.util import TOL
 
 pytestmark = pytest.mark.gpu
 
-CANARY = 0x7FC0BEEF     # guard bands: a quiet NaN with a payload no kernel produces
 # Guard rows start off 16-byte alignment.  Cldconv's single-block kernel reads and writes single floats: 4 bytes off.
 # Clpconv's single-block kernels move real samples in pairs, as 8-byte words (include/clfft_amd.h states 8 bytes for
 # clfa_pconv_process_dev): 8 bytes off.
@@ -36,39 +36,12 @@ def _torch():
     return torch
 
 
-class _Guarded:
+def _rows(nrows, rowlen, misalign):
     """nrows rows of rowlen floats inside a buffer of canaries: at least 4 canaries between rows, 64 at both ends; every
     row starts `misalign` floats past a 16-byte boundary"""
-
-    def __init__(self, nrows, rowlen, misalign):
-        torch = _torch()
-        stride = (rowlen + 4 + 3) // 4 * 4
-        off = 64 + misalign
-        self.buf = torch.full((off + nrows * stride + 64,), CANARY, dtype=torch.int32, device="cuda")
-        assert self.buf.data_ptr() % 16 == 0
-        self.words = self.buf[off:off + nrows * stride].view(nrows, stride)[:, :rowlen]
-        self.rows = list(self.words.view(torch.float32).unbind(0))
-        assert all(r.data_ptr() % 16 == 4 * misalign for r in self.rows[:2])
-        self.inside = torch.zeros(self.buf.shape, dtype=torch.bool, device="cuda")
-        self.inside[off:off + nrows * stride].view(nrows, stride)[:, :rowlen] = True
-
-    def fill(self, host):
-        torch = _torch()
-        self.words.view(torch.float32).copy_(torch.from_numpy(np.ascontiguousarray(host, dtype=np.float32)).cuda())
-        self.kept = self.buf.clone()
-        return self
-
-    def guards_intact(self):
-        return bool((self.buf[~self.inside] == CANARY).all())
-
-    def unchanged(self):
-        return bool(_torch().equal(self.buf, self.kept))
-
-    def written(self):
-        return not bool((self.words == CANARY).any())
-
-    def host(self):
-        return self.words.view(_torch().float32).contiguous().cpu().numpy()
+    g = gpu_guard.rows(nrows, rowlen, (rowlen + 4 + 3) // 4 * 4, misalign=misalign, before=64, after=64)
+    assert all(r.data_ptr() % 16 == 4 * misalign for r in g.data[:2])
+    return g
 
 
 # ---- (a) per bin, per partition, every Clpconv route --------------------------------------------------------------------------------
@@ -113,14 +86,14 @@ def _single_block_run(p, x1, x2):
     """every block through process_device, inputs and outputs as guarded rows -> (channels, nblocks * pts) on the host"""
     ch, pts = p.channels, p.pts
     nblocks = x1.shape[1] // pts
-    a = _Guarded(nblocks, ch * pts, PCONV_MISALIGN).fill(_by_block(x1, ch, pts))
-    b = _Guarded(nblocks, ch * pts, PCONV_MISALIGN).fill(_by_block(x2, ch, pts)) if x2 is not None else None
-    o = _Guarded(nblocks, ch * pts, PCONV_MISALIGN)
+    a = _rows(nblocks, ch * pts, PCONV_MISALIGN).fill(_by_block(x1, ch, pts))
+    b = _rows(nblocks, ch * pts, PCONV_MISALIGN).fill(_by_block(x2, ch, pts)) if x2 is not None else None
+    o = _rows(nblocks, ch * pts, PCONV_MISALIGN)
     for j in range(nblocks):
-        assert p.process_device(o.rows[j], a.rows[j], b.rows[j] if b is not None else None) == 0
+        assert p.process_device(o.data[j], a.data[j], b.data[j] if b is not None else None) == 0
     _torch().cuda.synchronize()
-    assert o.guards_intact(), "wrote outside the output blocks"
-    assert o.written(), "an output block was not written completely"
+    assert o.intact(), "wrote outside the output blocks"
+    assert not o.unwritten(), "an output block was not written completely"
     assert a.unchanged() and (b is None or b.unchanged()), "an input buffer changed"
     return np.ascontiguousarray(o.host().reshape(nblocks, ch, pts).transpose(1, 0, 2)).reshape(ch, nblocks * pts)
 
@@ -277,14 +250,14 @@ def test_dconv_single_block_kernel_exact_delay(irsize, vsize):
     """k_dconv_block: one-channel objects, block by block through process_device on guarded rows 4 bytes off alignment"""
     nblocks = cx.dconv_blocks_needed(irsize, vsize)
     x = cx.nonzero_noise([irsize, vsize], nblocks * vsize)
-    a = _Guarded(nblocks, vsize, DCONV_MISALIGN).fill(x.reshape(nblocks, vsize))
+    a = _rows(nblocks, vsize, DCONV_MISALIGN).fill(x.reshape(nblocks, vsize))
     for k in cx.dconv_taps(irsize):
         d = _dconv(irsize, vsize, 1, cx.unit_tap(irsize, k))
-        o = _Guarded(nblocks, vsize, DCONV_MISALIGN)
+        o = _rows(nblocks, vsize, DCONV_MISALIGN)
         for j in range(nblocks):
-            assert d.process_device(o.rows[j], a.rows[j]) == 0
+            assert d.process_device(o.data[j], a.data[j]) == 0
         _torch().cuda.synchronize()
-        assert o.guards_intact() and o.written() and a.unchanged(), "tap %d: guard bands" % k
+        assert o.intact() and not o.unwritten() and a.unchanged(), "tap %d: guard bands" % k
         _same_values(o.host().reshape(-1), cx.dconv_delayed(x, k), "irsize %d vsize %d tap %d" % (irsize, vsize, k))
 
 

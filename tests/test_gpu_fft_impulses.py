@@ -13,13 +13,13 @@ import pytest
 
 import opencl_fft_amd as fa
 from tests import fft_exact as fx
+from tests.gpu_guard import flat
 from tests.util import TOL, rel_err
 
 pytestmark = pytest.mark.gpu
 
 AMP = 1 - 0.5j          # both components of a complex delta / bin
 RAMP = 0.75             # real deltas
-CANARY = 0x7FC0BEEF     # guard bands: a quiet NaN with a payload no kernel produces
 
 
 def _plan(real, n, fwd):
@@ -226,21 +226,6 @@ def test_poisoned_neighbour(real, n, batch, kernel):
             assert torch.equal(y.view(torch.int32), base.view(torch.int32)), "NaN of transform %d reached a neighbour (fwd=%s)" % (bs, fwd)
 
 
-def _guarded(nfloats, misalign):
-    """(whole buffer as int32 filled with CANARY, float32 view of nfloats in its middle, offset): at least 4096 bytes of
-    guard on both sides; the view starts 16-byte aligned (misalign 0) or 8 bytes past that (misalign 2 floats)"""
-    import torch
-    off = 1024 + misalign
-    buf = torch.full((off + nfloats + 1024 + 4,), CANARY, dtype=torch.int32, device="cuda")
-    data = buf[off:off + nfloats].view(torch.float32)
-    assert data.data_ptr() % 16 == 4 * misalign
-    return buf, data, off
-
-
-def _guards_intact(buf, off, nfloats):
-    return bool((buf[:off] == CANARY).all()) and bool((buf[off + nfloats:] == CANARY).all())
-
-
 @pytest.mark.parametrize("misalign", [2, 0], ids=["align8", "align16"])
 @pytest.mark.parametrize("real,n,batch,kernel", ROUTES, ids=ROUTE_IDS)
 def test_guard_bands(real, n, batch, kernel, misalign):
@@ -254,19 +239,20 @@ def test_guard_bands(real, n, batch, kernel, misalign):
         x = _noise(real, n, batch, 7 * n + batch).reshape(-1)
         plain = x.clone()
         assert plan.exec_device(plain, batch) == 0
-        buf, data, off = _guarded(nf, misalign)
+        g = flat((nf,), misalign=misalign)
+        data = g.data
         data.copy_(x)
         assert plan.exec_device(data, batch) == 0
         _sync()
-        assert _guards_intact(buf, off, nf), "in place: wrote outside the batch (fwd=%s)" % fwd
+        assert g.intact(), "in place: wrote outside the batch (fwd=%s)" % fwd
         scale = float(plain.abs().max())
         assert float((data - plain).abs().max()) <= 1e-6 * scale, "in place: result differs from the aligned call"
-        sbuf, src, _ = _guarded(nf, misalign)
-        dbuf, dst, _ = _guarded(nf, misalign)
+        sg, dg = flat((nf,), misalign=misalign), flat((nf,), misalign=misalign)
+        src, dst = sg.data, dg.data
         src.copy_(x)
         assert plan.exec_device_oop(src, dst, batch) == 0
         _sync()
-        assert _guards_intact(sbuf, off, nf) and _guards_intact(dbuf, off, nf), "out of place: wrote outside the batch (fwd=%s)" % fwd
+        assert sg.intact() and dg.intact(), "out of place: wrote outside the batch (fwd=%s)" % fwd
         assert torch.equal(src.view(torch.int32), x.view(torch.int32)), "source modified (fwd=%s)" % fwd
-        assert not bool((dst.view(torch.int32) == CANARY).any()), "destination not written completely (fwd=%s)" % fwd
+        assert not dg.unwritten(), "destination not written completely (fwd=%s)" % fwd
         assert torch.equal(dst.view(torch.int32), data.view(torch.int32)), "out of place differs from in place (fwd=%s)" % fwd

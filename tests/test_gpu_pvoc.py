@@ -21,35 +21,25 @@ import torch
 
 import opencl_fft_amd as fa
 from tests import pvoc_model as pm
+from tests.gpu_guard import CANARY, DEV, flat
+from tests.pvoc_inputs import SR, hann, make_pvoc, two_tones
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-SR = 48000.0
 MARGIN = 2.0
 CL_INVALID_VALUE, CL_INVALID_OPERATION = -30, -59
-CANARY = 0x7FC0BEEF     # guard bands: a quiet NaN with a payload no kernel produces (tests/test_gpu_fft_impulses.py)
-
-
-def hann(size):
-    return (0.5 - 0.5 * np.cos(2 * np.pi * np.arange(size) / size)).astype(np.float32)
 
 
 def make(size, hop, channels=1):
-    pv = fa.Pvoc(0, size, hop, SR, channels)
-    assert pv.get_error() == 0, pv.get_log()
+    pv = make_pvoc(size, hop, channels)
     assert pv.kernel_name() == "k_pvoc_analyze" and pv.kernel_name(True) == "k_pvoc_walk"
     return pv
 
 
 def stft_spectra(size, hop, C, F, seed):
     """Stft.analyze_device on noise plus two sinusoids (one between bins, one near Nyquist): (C, F, M) complex64 on the device"""
-    rng = np.random.default_rng(seed)
-    n = size + (F - 1) * hop
-    t = np.arange(n)
-    x = 0.1 * rng.standard_normal((C, n)) + 0.7 * np.cos(2 * np.pi * 10.37 / size * t + 0.2) \
-        + 0.4 * np.cos(2 * np.pi * (size / 2 - 3.21) / size * t)
+    x = two_tones(size, hop, C, F, seed)
     st = fa.Stft(0, size, hop, window=hann(size))
-    assert st.get_error() == 0 and st.frames(n) == F
+    assert st.get_error() == 0 and st.frames(x.shape[1]) == F
     out = torch.zeros((C, F, size // 2), dtype=torch.complex64, device=DEV)
     assert st.analyze_device(torch.from_numpy(x.astype(np.float32)).to(DEV), out) == 0
     torch.cuda.synchronize()
@@ -297,19 +287,6 @@ def test_special_bins_and_zero_spectrum():
     assert np.all(np.sign(sp[0, :, 0].real) == np.sign(P[0, :, 0].real)) and np.all(sp[0, :, 0].imag < 0)
 
 
-def _guarded(nfloats):
-    """(int32 buffer of CANARY, float32 view of nfloats in its middle, 8-byte aligned and not 16, offset)"""
-    off = 1024 + 2
-    buf = torch.full((off + nfloats + 1024 + 4,), CANARY, dtype=torch.int32, device=DEV)
-    data = buf[off:off + nfloats].view(torch.float32)
-    assert data.data_ptr() % 16 == 8
-    return buf, data, off
-
-
-def _guards_intact(buf, off, nfloats):
-    return bool((buf[:off] == CANARY).all()) and bool((buf[off + nfloats:] == CANARY).all())
-
-
 @pytest.mark.parametrize("size,hop,channels", [(64, 16, 3), (1024, 3, 2)])
 def test_guard_bands_and_a_nan_frequency(size, hop, channels):
     pv = make(size, hop, channels)
@@ -319,15 +296,13 @@ def test_guard_bands_and_a_nan_frequency(size, hop, channels):
     plain_sp = synthesize(pv, plain_fr)
     state = (pv.read_prev(), pv.read_phase())
     assert pv.reset() == 0
-    nfr, nsp = channels * F * (M + 1) * 2, channels * F * M * 2
-    fbuf, fdata, foff = _guarded(nfr)
-    sbuf, sdata, soff = _guarded(nsp)
-    fr = fdata.view(channels, F, M + 1, 2)
-    sp = torch.view_as_complex(sdata.view(channels, F, M, 2))
+    fg, sg = flat((channels, F, M + 1, 2)), flat((channels, F, M, 2))
+    fr = fg.data
+    sp = torch.view_as_complex(sg.data)
     assert pv.analyze_device(spec, fr) == 0 and pv.synthesize_device(fr, sp) == 0
     torch.cuda.synchronize()
-    assert _guards_intact(fbuf, foff, nfr) and _guards_intact(sbuf, soff, nsp), "wrote outside an output"
-    assert not bool((fdata.view(torch.int32) == CANARY).any()) and not bool((sdata.view(torch.int32) == CANARY).any())
+    assert fg.intact() and sg.intact(), "wrote outside an output"
+    assert not fg.unwritten() and not sg.unwritten()
     assert torch.equal(fr, plain_fr) and torch.equal(torch.view_as_real(sp), torch.view_as_real(plain_sp))
     assert np.array_equal(pv.read_prev().view(np.uint32), state[0].view(np.uint32)) and np.array_equal(pv.read_phase(), state[1])
     # a NaN in one frame's freq: that bin's phase does not move in that frame, nothing else changes
@@ -335,10 +310,10 @@ def test_guard_bands_and_a_nan_frequency(size, hop, channels):
     bad = plain_fr.clone()
     bad[c0, f0, k0, 1] = float("nan")
     assert pv.reset() == 0
-    sbuf.fill_(CANARY)
+    sg.buf.fill_(CANARY)
     assert pv.synthesize_device(bad, sp) == 0
     torch.cuda.synchronize()
-    assert _guards_intact(sbuf, soff, nsp)
+    assert sg.intact()
     th, new_theta = pm.phases(bad.cpu().numpy()[..., 1], pm.initial_phase(channels, size), hop, SR)
     assert np.array_equal(pv.read_phase(), new_theta)
     assert th[c0, f0, k0] == th[c0, f0 - 1, k0] and new_theta[c0, k0] != state[1][c0, k0]

@@ -19,24 +19,19 @@ import torch
 
 import opencl_fft_amd as fa
 from tests import pvoc_adsyn_model as am
+from tests import gpu_guard
+from tests.gpu_guard import DEV
+from tests.pvoc_inputs import SR, analyse_device, make_pvoc, two_tones
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-SR = 48000.0
 MARGIN = 2.0
 CL_INVALID_VALUE, CL_INVALID_OPERATION = -30, -59
-CANARY = 0x7FC0BEEF     # guard bands: a quiet NaN with a payload no kernel produces (tests/test_gpu_pvoc.py)
 f32 = np.float32
 RATIO = {"max": 0.0}
 
 
-def hann(size):
-    return (0.5 - 0.5 * np.cos(2 * np.pi * np.arange(size) / size)).astype(f32)
-
-
 def make(size, hop, channels=1, sr=SR):
-    pv = fa.Pvoc(0, size, hop, sr, channels)
-    assert pv.get_error() == 0, pv.get_log()
+    pv = make_pvoc(size, hop, channels, sr)
     assert pv.adsyn_kernel_name() == "k_adsyn_osc"
     return pv
 
@@ -65,18 +60,9 @@ def random_frames(size, C, F, seed, sr=SR):
 def analysed_frames(size, hop, C, F, seed):
     """Stft and Pvoc.analyze on the device, of noise plus two sinusoids (one between bins, one near Nyquist)"""
     rng = np.random.default_rng(seed)
-    n = size + (F - 1) * hop
-    t = np.arange(n)
-    x = 0.1 * rng.standard_normal((C, n)) + 0.7 * np.cos(2 * np.pi * 10.37 / size * t + 0.2) \
-        + 0.4 * np.cos(2 * np.pi * (size / 2 - 3.21) / size * t)
-    st = fa.Stft(0, size, hop, window=hann(size))
-    assert st.get_error() == 0 and st.frames(n) == F
-    spec = torch.zeros((C, F, size // 2), dtype=torch.complex64, device=DEV)
-    assert st.analyze_device(torch.from_numpy(x.astype(f32)).to(DEV), spec) == 0
-    fr = torch.zeros((C, F, size // 2 + 1, 2), device=DEV)
-    assert fa.Pvoc(0, size, hop, SR, C).analyze_device(spec, fr) == 0
-    torch.cuda.synchronize()
-    return spoil(fr.cpu().numpy(), rng)
+    fr = analyse_device(two_tones(size, hop, C, F, rng), size, hop)
+    assert fr.shape[1] == F
+    return spoil(fr, rng)
 
 
 def run(pv, fr_t, fmod=None, sel=(0, None, 1), gain=1.0, stream=None):
@@ -232,18 +218,6 @@ def probe_expected(seg, gain):
     return y.astype(f32)
 
 
-def guarded_rows(C, n, stride):
-    """(int32 buffer of CANARY, float32 (C, n) view of rows `stride` apart in its middle, mask of the floats a call may write)"""
-    off = 1024 + 1
-    total = off + C * stride + 1024
-    buf = torch.full((total,), CANARY, dtype=torch.int32, device=DEV)
-    rows = buf[off:off + C * stride].view(torch.float32).view(C, stride)[:, :n]
-    mask = torch.zeros(total, dtype=torch.bool, device=DEV)
-    for c in range(C):
-        mask[off + c * stride:off + c * stride + n] = True
-    return buf, rows, mask
-
-
 def probe_sizes():
     tile = fa.Pvoc(0, 64, 16, PSR).adsyn_tile_bins()
     big = 64
@@ -288,11 +262,12 @@ def test_exact_probe(case, pattern):
     for F in [1, ch + 2, 3]:
         fr = frames(F, True)
         n, stride = F * hop, F * hop + 5
-        buf, rows, mask = guarded_rows(C, n, stride)
+        g = gpu_guard.rows(C, n, stride, misalign=1)
+        rows = g.data
         assert pv.adsyn_device(torch.from_numpy(fr).to(DEV), rows, first_bin=sel[0], nbins=sel[1], step=sel[2], gain=gain) == 0
         torch.cuda.synchronize()
-        assert bool((buf[~mask] == CANARY).all()), "wrote outside the output rows"
-        assert not bool((buf[mask] == CANARY).any()), "left an output sample unwritten"
+        assert g.intact(), "wrote outside the output rows"
+        assert not g.unwritten(), "left an output sample unwritten"
         seg, new = am.segments(fr, state, hop, PSR, None, bins)
         want = probe_expected(seg, gain)
         got = rows.cpu().numpy()

@@ -44,55 +44,30 @@ import numpy as np
 import pytest
 import torch
 
-import opencl_fft_amd as fa
 from tests import pvoc_model as pm
 from tests import pvoc_probe as pp
+from tests.gpu_guard import bits, dev, flat
+from tests.pvoc_inputs import make_pvoc
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 SR = pp.SR
 MARGIN_BIN = pp.MARGIN_BIN
-CANARY = 0x7FC0BEEF     # guard bands: a quiet NaN with a payload no kernel produces (tests/test_gpu_pvoc.py)
 C = 2
 RATIO = {"max": 0.0, "case": ""}
 
 
 def make(size, hop, sr=SR, chunks_max=None, monkeypatch=None):
-    if chunks_max is not None:
-        monkeypatch.setenv("CLFA_PVOC_CHUNKS_MAX", str(chunks_max))
-    pv = fa.Pvoc(0, size, hop, sr, C)
-    if chunks_max is not None:
-        monkeypatch.delenv("CLFA_PVOC_CHUNKS_MAX")
-    assert pv.get_error() == 0, pv.get_log()
+    pv = make_pvoc(size, hop, C, sr, env={"CLFA_PVOC_CHUNKS_MAX": chunks_max}, monkeypatch=monkeypatch)
     assert pv.kernel_name() == "k_pvoc_analyze" and pv.kernel_name(True) == "k_pvoc_walk"
     return pv
 
 
-def guarded(shape):
-    """(int32 buffer of CANARY, float32 view of `shape` in its middle, 8-byte aligned and not 16, offset, floats)"""
-    n = int(np.prod(shape))
-    off = 1024 + 2
-    buf = torch.full((off + n + 1024 + 4,), CANARY, dtype=torch.int32, device=DEV)
-    data = buf[off:off + n].view(torch.float32).view(*shape)
-    assert data.data_ptr() % 16 == 8
-    return buf, data, off, n
-
-
 def finish(g, what):
     """after the launches into g: the guard bands intact, every element written"""
-    buf, data, off, n = g
     torch.cuda.synchronize()
-    assert bool((buf[:off] == CANARY).all()) and bool((buf[off + n:] == CANARY).all()), what + ": wrote outside the output"
-    assert not bool((buf[off:off + n] == CANARY).any()), what + ": an output element was not written"
-    return data
-
-
-def dev(a):
-    return torch.from_numpy(np.array(a, order="C")).to(DEV)      # (a copy: the probes are read-only)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
+    assert g.intact(), what + ": wrote outside the output"
+    assert not g.unwritten(), what + ": an output element was not written"
+    return g.data
 
 
 def analyze(pv, spec, cuts, what):
@@ -101,8 +76,8 @@ def analyze(pv, spec, cuts, what):
     F, M = spec.shape[1:]
     parts = []
     for a, b in zip([0] + cuts, cuts + [F]):
-        g = guarded((C, b - a, M + 1, 2))
-        assert pv.analyze_device(spec[:, a:b].contiguous(), g[1]) == 0
+        g = flat((C, b - a, M + 1, 2))
+        assert pv.analyze_device(spec[:, a:b].contiguous(), g.data) == 0
         parts.append(finish(g, what))
     return parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
 
@@ -112,8 +87,8 @@ def synthesize(pv, fr, cuts, what):
     F, B = fr.shape[1:3]
     parts = []
     for a, b in zip([0] + cuts, cuts + [F]):
-        g = guarded((C, b - a, B - 1, 2))
-        assert pv.synthesize_device(fr[:, a:b].contiguous(), torch.view_as_complex(g[1])) == 0
+        g = flat((C, b - a, B - 1, 2))
+        assert pv.synthesize_device(fr[:, a:b].contiguous(), torch.view_as_complex(g.data)) == 0
         parts.append(finish(g, what).cpu().numpy().view(np.complex64)[..., 0])
     return np.concatenate(parts, axis=1)
 

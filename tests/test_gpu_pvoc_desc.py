@@ -4,8 +4,8 @@ the numpy restatement of their definition (tests/pvoc_desc_model.py).
 Everything is compared bit for bit with the float32 model: the sums are the header's tree of single correctly rounded
 float32 additions, so there is no tolerance to choose.  Where the model gives a NaN the device gives a NaN; payloads are
 not compared.  The inputs are tests/pvoc_desc_cases.py's (tests/test_pvoc_desc_cpu.py shows that they notice seven mutants
-of the model) and tests/test_gpu_pvoc_pair.py's analysed() frames; the outputs have its guard bands, 8-byte and not 16-byte
-aligned."""
+of the model) and tests/pvoc_inputs.py's analysed() frames; the outputs have the guard bands of tests/gpu_guard.py, 8-byte
+and not 16-byte aligned."""
 import numpy as np
 import pytest
 import torch
@@ -13,7 +13,8 @@ import torch
 import opencl_fft_amd as fa
 from tests import pvoc_desc_cases as dc
 from tests import pvoc_desc_model as dm
-from tests.test_gpu_pvoc_pair import CANARY, DEV, SR, analysed, bits, dev, guarded, intact, same
+from tests.gpu_guard import CANARY, DEV, bits, dev, run, same
+from tests.pvoc_inputs import SR, analysed, make_pvoc
 
 pytestmark = pytest.mark.gpu
 CL_INVALID_VALUE = -30
@@ -22,25 +23,15 @@ assert SR == dc.SR
 
 
 def make(size, channels=1, grid_max=None, monkeypatch=None):
-    if grid_max is not None:
-        monkeypatch.setenv("CLFA_PVOC_OPS_GRID_MAX", str(grid_max))
-    pv = fa.Pvoc(0, size, size // 4, SR, channels)
-    if grid_max is not None:
-        monkeypatch.delenv("CLFA_PVOC_OPS_GRID_MAX")
-    assert pv.get_error() == 0, pv.get_log()
+    pv = make_pvoc(size, size // 4, channels, env={"CLFA_PVOC_OPS_GRID_MAX": grid_max}, monkeypatch=monkeypatch)
     assert pv.desc_kernel_name() == "k_pvoc_desc"
     return pv
 
 
 def run_guarded(pv, x, first_bin=0, nbins=None, rectify=False, stream=None):
     """one device call into a guarded output: the rows as numpy, the guard bands checked, every element written"""
-    g = guarded(x.shape[:2] + (8,))
-    assert pv.describe_device(dev(x), g[1], first_bin, nbins, rectify, stream=stream) == 0
-    torch.cuda.synchronize()
-    assert intact(g), "wrote outside the output"
-    out = g[1].cpu().numpy()
-    assert not (bits(out) == CANARY).any(), "an output element was not written"
-    return out
+    dx = dev(x)
+    return run(lambda o: pv.describe_device(dx, o, first_bin, nbins, rectify, stream=stream), x.shape[:2] + (8,))
 
 
 def run_cut(pv, x, cut, first_bin=0, nbins=None, rectify=False, stream=None):

@@ -33,71 +33,28 @@ value in every call like the other sizes.
 """
 import numpy as np
 import pytest
-import torch
 
-import opencl_fft_amd as fa
 from tests import pvoc_env_probe as ep
 from tests import pvoc_ops_model as om
 from tests import pvoc_pair_model as pp
+from tests.gpu_guard import bits, dev, run
+from tests.pvoc_inputs import SR, make_pvoc
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-SR = 48000.0
 MARGIN_BIN = 4.0        # see the docstring: the largest ratio measured is 1.61
-CANARY = 0x7FC0BEEF     # guard bands: a quiet NaN with a payload no kernel produces (tests/test_gpu_fft_impulses.py)
 GAIN = 0.7
 f32 = np.float32
 RATIO = {"max": 0.0, "case": ""}
 
 
 def make(size, channels, grid_max=None, monkeypatch=None):
-    if grid_max is not None:
-        monkeypatch.setenv("CLFA_PVOC_OPS_GRID_MAX", str(grid_max))
-    pv = fa.Pvoc(0, size, size // 4, SR, channels)
-    if grid_max is not None:
-        monkeypatch.delenv("CLFA_PVOC_OPS_GRID_MAX")
-    assert pv.get_error() == 0, pv.get_log()
-    return pv
+    return make_pvoc(size, size // 4, channels, env={"CLFA_PVOC_OPS_GRID_MAX": grid_max}, monkeypatch=monkeypatch)
 
 
 def both(size, monkeypatch):
     """(the probe, a free object, one whose launches have at most 2 workgroups)"""
     fr = ep.probe_for(size)
     return fr, make(size, fr.shape[0]), make(size, fr.shape[0], grid_max=2, monkeypatch=monkeypatch)
-
-
-def guarded(shape):
-    """(int32 buffer of CANARY, float32 view of `shape` in its middle, 8-byte aligned and not 16, offset, floats)"""
-    n = int(np.prod(shape))
-    off = 1024 + 2
-    buf = torch.full((off + n + 1024 + 4,), CANARY, dtype=torch.int32, device=DEV)
-    data = buf[off:off + n].view(torch.float32).view(*shape)
-    assert data.data_ptr() % 16 == 8
-    return buf, data, off, n
-
-
-def intact(g):
-    buf, _, off, n = g
-    return bool((buf[:off] == CANARY).all()) and bool((buf[off + n:] == CANARY).all())
-
-
-def dev(a):
-    return torch.from_numpy(np.array(a, order="C")).to(DEV)      # (a copy: the probes are read-only)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def run(call, shape):
-    """a device call into a guarded output: the result as numpy, the guard bands checked, every element written"""
-    g = guarded(shape)
-    assert call(g[1]) == 0
-    torch.cuda.synchronize()
-    assert intact(g), "wrote outside the output"
-    out = g[1].cpu().numpy()
-    assert not (bits(out) == CANARY).any(), "an output element was not written"
-    return out
 
 
 def run_both(pvs, call, shape, what):

@@ -23,14 +23,13 @@ import opencl_fft_amd as fa
 from opencl_fft_amd import _lib
 from tests import pvoc_model as pm
 from tests import pvoc_ops_model as om
-from tests import stft_model
+from tests import pvoc_inputs, stft_model
+from tests.gpu_guard import CANARY, DEV, bits, dev, flat, run
+from tests.pvoc_inputs import SR, hann, make_pvoc
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-SR = 48000.0
 MARGIN = 4.0            # see the docstring: the largest ratio measured so far is 2.15
 CL_INVALID_VALUE = -30
-CANARY = 0x7FC0BEEF     # guard bands: a quiet NaN with a payload no kernel produces (tests/test_gpu_fft_impulses.py)
 f32 = np.float32
 RATIO = {"max": 0.0}
 
@@ -42,103 +41,20 @@ def fpw(size):
 
 
 def make(size, channels=1, hop=None, grid_max=None, monkeypatch=None):
-    if grid_max is not None:
-        monkeypatch.setenv("CLFA_PVOC_OPS_GRID_MAX", str(grid_max))
-    pv = fa.Pvoc(0, size, hop or size // 4, SR, channels)
-    if grid_max is not None:
-        monkeypatch.delenv("CLFA_PVOC_OPS_GRID_MAX")
-    assert pv.get_error() == 0, pv.get_log()
+    pv = make_pvoc(size, hop or size // 4, channels, env={"CLFA_PVOC_OPS_GRID_MAX": grid_max}, monkeypatch=monkeypatch)
     assert (pv.ops_kernel_name("scale"), pv.ops_kernel_name("shift", True), pv.ops_kernel_name("read")) == \
         ("k_pvoc_map", "k_pvoc_formant", "k_pvoc_read")
     return pv
 
 
-def hann(size):
-    return (0.5 - 0.5 * np.cos(2 * np.pi * np.arange(size) / size)).astype(f32)
-
-
-_FRAMES = {}
-
-
 def analysed(size, C, F, seed=3):
-    """frames of Stft + Pvoc.analyze_device on noise plus two sinusoids, as in test_gpu_pvoc.py (numpy, cached, read-only)"""
-    key = ("a", size, C, F, seed)
-    if key not in _FRAMES:
-        hop = size // 4
-        rng = np.random.default_rng(seed)
-        n = size + (F - 1) * hop
-        t = np.arange(n)
-        x = 0.1 * rng.standard_normal((C, n)) + 0.7 * np.cos(2 * np.pi * 10.37 / size * t + 0.2) \
-            + 0.4 * np.cos(2 * np.pi * (size / 2 - 3.21) / size * t)
-        st = fa.Stft(0, size, hop, window=hann(size))
-        spec = torch.zeros((C, F, size // 2), dtype=torch.complex64, device=DEV)
-        assert st.analyze_device(torch.from_numpy(x.astype(f32)).to(DEV), spec) == 0
-        fr = torch.zeros((C, F, size // 2 + 1, 2), device=DEV)
-        assert fa.Pvoc(0, size, hop, SR, C).analyze_device(spec, fr) == 0
-        torch.cuda.synchronize()
-        a = fr.cpu().numpy()
-        a.setflags(write=False)
-        _FRAMES[key] = a
-    return _FRAMES[key]
+    """the shared frames with the tones of test_gpu_pvoc.py: bins 10.37 and size / 2 - 3.21"""
+    return pvoc_inputs.analysed(size, C, F, seed, seeded_tones=False)
 
 
 def raw(size, C, F, seed=4, tilt=False):
-    """raw random frames, any freq: amps log-uniform over 1e-30 .. 1e30 and a few zeros; tilt (the formant cases): the
-    same span as a slope over the bins, up or down by frame, times a random factor 0.1 .. 10 — with independent bins
-    amp / env * env of the definition leaves float32's range (1e52 in float64), which no model could be compared on"""
-    key = ("r", size, C, F, seed, tilt)
-    if key not in _FRAMES:
-        rng = np.random.default_rng(seed)
-        B = size // 2 + 1
-        if tilt:
-            ramp = np.linspace(-30, 30, B) * rng.choice([-1.0, 1.0], (C, F, 1))
-            amp = (10.0 ** (ramp + rng.uniform(-1, 1, (C, F, B)))).astype(f32)
-        else:
-            amp = (10.0 ** rng.uniform(-30, 30, (C, F, B))).astype(f32)
-            amp[rng.random((C, F, B)) < 0.02] = 0
-        freq = rng.uniform(-SR, SR, (C, F, B)).astype(f32)
-        a = np.stack([amp, freq], axis=-1)
-        a.setflags(write=False)
-        _FRAMES[key] = a
-    return _FRAMES[key]
-
-
-def guarded(shape):
-    """(int32 buffer of CANARY, float32 view of `shape` in its middle, 8-byte aligned and not 16, offset, floats)"""
-    n = int(np.prod(shape))
-    off = 1024 + 2
-    buf = torch.full((off + n + 1024 + 4,), CANARY, dtype=torch.int32, device=DEV)
-    data = buf[off:off + n].view(torch.float32).view(*shape)
-    assert data.data_ptr() % 16 == 8
-    return buf, data, off, n
-
-
-def intact(g):
-    buf, _, off, n = g
-    return bool((buf[:off] == CANARY).all()) and bool((buf[off + n:] == CANARY).all())
-
-
-def untouched(g):
-    return bool((g[0] == CANARY).all())
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def run(call, shape):
-    """a device call into a guarded output: the result as numpy, the guard bands checked, every element written"""
-    g = guarded(shape)
-    assert call(g[1]) == 0
-    torch.cuda.synchronize()
-    assert intact(g), "wrote outside the output"
-    out = g[1].cpu().numpy()
-    assert not (bits(out) == CANARY).any(), "an output element was not written"
-    return out
+    """the shared raw frames; tilt (the formant cases): the whole span of 60 decades as the slope, no forced zero"""
+    return pvoc_inputs.raw(size, C, F, seed, tilt, decades=30, zero=False)
 
 
 def frame_counts(size):
@@ -347,8 +263,8 @@ def test_errors_write_nothing():
     pv = make(size, C)
     fr = dev(analysed(size, C, F))
     s = dev(per_frame(F, "scale", size))
-    g = guarded((C, F, M + 1, 2))
-    out = g[1]
+    g = flat((C, F, M + 1, 2))
+    out = g.data
     for coefs in (0, M, -3):
         assert pv.scale_device(fr, out, s, keepform=True, coefs=coefs) == CL_INVALID_VALUE
         assert pv.shift_device(fr, out, s, keepform=True, coefs=coefs) == CL_INVALID_VALUE
@@ -364,7 +280,7 @@ def test_errors_write_nothing():
     assert pv.scale_device(fr.double(), out, s) == CL_INVALID_VALUE
     assert pv.read_device(fr, 1.0, out) == CL_INVALID_VALUE
     torch.cuda.synchronize()
-    assert untouched(g)
+    assert g.untouched()
     # an output overlapping the frames, or the per-frame array, even partly
     n = C * F * (M + 1) * 2
     buf = torch.full((2 * n + F,), CANARY, dtype=torch.int32, device=DEV).view(torch.float32)

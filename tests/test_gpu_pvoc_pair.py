@@ -24,13 +24,12 @@ from tests import pvoc_model as pm
 from tests import pvoc_ops_model as om
 from tests import pvoc_pair_model as pp
 from tests import stft_model
+from tests.gpu_guard import CANARY, DEV, bits, dev, flat, run, same
+from tests.pvoc_inputs import SR, analysed, hann, make_pvoc, raw
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-SR = 48000.0
 MARGIN = 8.0            # see the docstring: the largest ratio measured is 3.45
 CL_INVALID_VALUE = -30
-CANARY = 0x7FC0BEEF     # guard bands: a quiet NaN with a payload no kernel produces (tests/test_gpu_fft_impulses.py)
 f32 = np.float32
 RATIO = {"max": 0.0}
 OPS = ("cross", "morph", "filter", "mix")
@@ -43,111 +42,9 @@ def fpw(size):
 
 
 def make(size, channels=1, hop=None, grid_max=None, monkeypatch=None):
-    if grid_max is not None:
-        monkeypatch.setenv("CLFA_PVOC_OPS_GRID_MAX", str(grid_max))
-    pv = fa.Pvoc(0, size, hop or size // 4, SR, channels)
-    if grid_max is not None:
-        monkeypatch.delenv("CLFA_PVOC_OPS_GRID_MAX")
-    assert pv.get_error() == 0, pv.get_log()
+    pv = make_pvoc(size, hop or size // 4, channels, env={"CLFA_PVOC_OPS_GRID_MAX": grid_max}, monkeypatch=monkeypatch)
     assert [pv.pair_kernel_name(op) for op in OPS + ("vocode",)] == ["k_pvoc_pair"] * 4 + ["k_pvoc_vocode"]
     return pv
-
-
-def hann(size):
-    return (0.5 - 0.5 * np.cos(2 * np.pi * np.arange(size) / size)).astype(f32)
-
-
-_FRAMES = {}
-
-
-def analysed(size, C, F, seed):
-    """frames of Stft + Pvoc.analyze_device on noise plus two sinusoids that depend on the seed (numpy, cached, read-only)"""
-    key = ("a", size, C, F, seed)
-    if key not in _FRAMES:
-        hop = size // 4
-        rng = np.random.default_rng(seed)
-        n = size + (F - 1) * hop
-        t = np.arange(n)
-        k1, k2 = rng.uniform(5, 20), rng.uniform(size / 4, size / 2 - 2)
-        x = 0.1 * rng.standard_normal((C, n)) + 0.7 * np.cos(2 * np.pi * k1 / size * t + 0.2) \
-            + 0.4 * np.cos(2 * np.pi * k2 / size * t)
-        st = fa.Stft(0, size, hop, window=hann(size))
-        spec = torch.zeros((C, F, size // 2), dtype=torch.complex64, device=DEV)
-        assert st.analyze_device(torch.from_numpy(x.astype(f32)).to(DEV), spec) == 0
-        fr = torch.zeros((C, F, size // 2 + 1, 2), device=DEV)
-        assert fa.Pvoc(0, size, hop, SR, C).analyze_device(spec, fr) == 0
-        torch.cuda.synchronize()
-        a = fr.cpu().numpy()
-        a.setflags(write=False)
-        _FRAMES[key] = a
-    return _FRAMES[key]
-
-
-def raw(size, C, F, seed, tilt=False):
-    """raw random frames, any freq: amps log-uniform over 1e-30 .. 1e30 and a few zeros; tilt (the vocoder's cases): a
-    slope of 15 decades over the bins, up or down by frame, times a random factor 0.1 .. 10, and one zero amp — twice
-    that slope and envA / envB would leave float32"""
-    key = ("r", size, C, F, seed, tilt)
-    if key not in _FRAMES:
-        rng = np.random.default_rng(seed)
-        B = size // 2 + 1
-        if tilt:
-            ramp = np.linspace(-7.5, 7.5, B) * rng.choice([-1.0, 1.0], (C, F, 1))
-            amp = (10.0 ** (ramp + rng.uniform(-1, 1, (C, F, B)))).astype(f32)
-            amp[C - 1, F - 1, B // 3] = 0
-        else:
-            amp = (10.0 ** rng.uniform(-30, 30, (C, F, B))).astype(f32)
-            amp[rng.random((C, F, B)) < 0.02] = 0
-        freq = rng.uniform(-SR, SR, (C, F, B)).astype(f32)
-        a = np.stack([amp, freq], axis=-1)
-        a.setflags(write=False)
-        _FRAMES[key] = a
-    return _FRAMES[key]
-
-
-def guarded(shape):
-    """(int32 buffer of CANARY, float32 view of `shape` in its middle, 8-byte aligned and not 16, offset, floats)"""
-    n = int(np.prod(shape))
-    off = 1024 + 2
-    buf = torch.full((off + n + 1024 + 4,), CANARY, dtype=torch.int32, device=DEV)
-    data = buf[off:off + n].view(torch.float32).view(*shape)
-    assert data.data_ptr() % 16 == 8
-    return buf, data, off, n
-
-
-def intact(g):
-    buf, _, off, n = g
-    return bool((buf[:off] == CANARY).all()) and bool((buf[off + n:] == CANARY).all())
-
-
-def untouched(g):
-    return bool((g[0] == CANARY).all())
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def run(call, shape):
-    """a device call into a guarded output: the result as numpy, the guard bands checked, every element written"""
-    g = guarded(shape)
-    assert call(g[1]) == 0
-    torch.cuda.synchronize()
-    assert intact(g), "wrote outside the output"
-    out = g[1].cpu().numpy()
-    assert not (bits(out) == CANARY).any(), "an output element was not written"
-    return out
-
-
-def same(got, want, what):
-    """bit-equal where the model is a number, a NaN where it is a NaN"""
-    nan = np.isnan(want)
-    assert np.array_equal(np.isnan(got), nan), what + ": where the NaNs are"
-    assert np.array_equal(bits(got)[~nan], bits(want)[~nan]), what
 
 
 def frame_counts(size):
@@ -367,8 +264,8 @@ def test_errors_write_nothing():
     pv = make(size, C)
     a, b = dev(analysed(size, C, F, 3)), dev(analysed(size, C, F, 11))
     s = dev(np.full(F, 0.5, f32))
-    g = guarded((C, F, M + 1, 2))
-    out = g[1]
+    g = flat((C, F, M + 1, 2))
+    out = g.data
     pair = [lambda x, y, o, p, q: pv.cross_device(x, y, o, p, q), lambda x, y, o, p, q: pv.morph_device(x, y, o, p, q),
             lambda x, y, o, p, q: pv.filter_device(x, y, o, p, q), lambda x, y, o, p, q: pv.vocode_device(x, y, o, p, q, coefs=5)]
     for coefs in (0, M, -3):
@@ -383,7 +280,7 @@ def test_errors_write_nothing():
         assert call(a, b.transpose(0, 1), out, s, s) == CL_INVALID_VALUE
     assert pv.mix_device(a, b[:1], out) == CL_INVALID_VALUE and pv.mix_device(a.double(), b, out) == CL_INVALID_VALUE
     torch.cuda.synchronize()
-    assert untouched(g)
+    assert g.untouched()
     # an output overlapping a, b, p or q, shifted by one pair
     n = C * F * (M + 1) * 2
     buf = torch.full((2 * n + F,), CANARY, dtype=torch.int32, device=DEV).view(torch.float32)
@@ -401,7 +298,7 @@ def test_errors_write_nothing():
         assert call(a, a, out, s, s) == 0
     assert pv.mix_device(a, a, out) == 0
     torch.cuda.synchronize()
-    assert intact(g) and np.array_equal(bits(out.cpu().numpy()), bits(a.cpu().numpy()))    # mix of a with itself
+    assert g.intact() and np.array_equal(bits(out.cpu().numpy()), bits(a.cpu().numpy()))    # mix of a with itself
     # F == 0: success, nothing happens
     e = torch.zeros((C, 0, M + 1, 2), device=DEV)
     for call in pair:

@@ -28,17 +28,16 @@ import numpy as np
 import pytest
 import torch
 
-import opencl_fft_amd as fa
 from opencl_fft_amd import _lib
 from tests import pvoc_ops_model as om
 from tests import pvoc_shape_model as sm
+from tests.gpu_guard import CANARY, DEV, bits, dev, flat, run, same
+from tests.pvoc_inputs import SR, analysed, make_pvoc
+from tests.pvoc_inputs import raw_freq_first as raw     # freqs drawn first, NaN amps and freqs among the plain frames
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-SR = 48000.0
 MARGIN = 4.0            # see the docstring: the largest ratio measured is 1.84
 CL_INVALID_VALUE = -30
-CANARY = 0x7FC0BEEF     # guard bands: a quiet NaN with a payload no kernel produces (tests/test_gpu_fft_impulses.py)
 f32 = np.float32
 RATIO = {"max": 0.0}
 NAMES = ("band", "mask", "stencil", "arp", "lock", "warp")
@@ -51,114 +50,9 @@ def fpw(size):
 
 
 def make(size, channels=1, hop=None, grid_max=None, monkeypatch=None):
-    if grid_max is not None:
-        monkeypatch.setenv("CLFA_PVOC_OPS_GRID_MAX", str(grid_max))
-    pv = fa.Pvoc(0, size, hop or size // 4, SR, channels)
-    if grid_max is not None:
-        monkeypatch.delenv("CLFA_PVOC_OPS_GRID_MAX")
-    assert pv.get_error() == 0, pv.get_log()
+    pv = make_pvoc(size, hop or size // 4, channels, env={"CLFA_PVOC_OPS_GRID_MAX": grid_max}, monkeypatch=monkeypatch)
     assert [pv.shape_kernel_name(op) for op in NAMES] == ["k_pvoc_shape"] * 4 + ["k_pvoc_lock", "k_pvoc_warp"]
     return pv
-
-
-def hann(size):
-    return (0.5 - 0.5 * np.cos(2 * np.pi * np.arange(size) / size)).astype(f32)
-
-
-_FRAMES = {}
-
-
-def analysed(size, C, F, seed):
-    """frames of Stft + Pvoc.analyze_device on noise plus two sinusoids that depend on the seed (numpy, cached, read-only)"""
-    key = ("a", size, C, F, seed)
-    if key not in _FRAMES:
-        hop = size // 4
-        rng = np.random.default_rng(seed)
-        n = size + (F - 1) * hop
-        t = np.arange(n)
-        k1, k2 = rng.uniform(5, 20), rng.uniform(size / 4, size / 2 - 2)
-        x = 0.1 * rng.standard_normal((C, n)) + 0.7 * np.cos(2 * np.pi * k1 / size * t + 0.2) \
-            + 0.4 * np.cos(2 * np.pi * k2 / size * t)
-        st = fa.Stft(0, size, hop, window=hann(size))
-        spec = torch.zeros((C, F, size // 2), dtype=torch.complex64, device=DEV)
-        assert st.analyze_device(torch.from_numpy(x.astype(f32)).to(DEV), spec) == 0
-        fr = torch.zeros((C, F, size // 2 + 1, 2), device=DEV)
-        assert fa.Pvoc(0, size, hop, SR, C).analyze_device(spec, fr) == 0
-        torch.cuda.synchronize()
-        a = fr.cpu().numpy()
-        a.setflags(write=False)
-        _FRAMES[key] = a
-    return _FRAMES[key]
-
-
-def raw(size, C, F, seed, tilt=False):
-    """raw random frames, any freq of either sign: amps log-uniform over 1e-30 .. 1e30 and a few zeros, some bins with a
-    NaN amp and some with a NaN freq; tilt (the warp's cases, as in tests/test_gpu_pvoc_pair.py): a slope of 15 decades
-    over the bins, up or down by frame, times a random factor 0.1 .. 10, and one zero amp, no NaN — twice that slope and
-    a ratio of two envelope values would leave float32"""
-    key = ("r", size, C, F, seed, tilt)
-    if key not in _FRAMES:
-        rng = np.random.default_rng(seed)
-        B = size // 2 + 1
-        freq = rng.uniform(-SR, SR, (C, F, B)).astype(f32)
-        if tilt:
-            ramp = np.linspace(-7.5, 7.5, B) * rng.choice([-1.0, 1.0], (C, F, 1))
-            amp = (10.0 ** (ramp + rng.uniform(-1, 1, (C, F, B)))).astype(f32)
-            amp[C - 1, F - 1, B // 3] = 0
-        else:
-            amp = (10.0 ** rng.uniform(-30, 30, (C, F, B))).astype(f32)
-            amp[rng.random((C, F, B)) < 0.02] = 0
-            amp[rng.random((C, F, B)) < 0.02] = np.nan
-            freq[rng.random((C, F, B)) < 0.02] = np.nan
-        a = np.stack([amp, freq], axis=-1)
-        a.setflags(write=False)
-        _FRAMES[key] = a
-    return _FRAMES[key]
-
-
-def guarded(shape):
-    """(int32 buffer of CANARY, float32 view of `shape` in its middle, 8-byte aligned and not 16, offset, floats)"""
-    n = int(np.prod(shape))
-    off = 1024 + 2
-    buf = torch.full((off + n + 1024 + 4,), CANARY, dtype=torch.int32, device=DEV)
-    data = buf[off:off + n].view(torch.float32).view(*shape)
-    assert data.data_ptr() % 16 == 8
-    return buf, data, off, n
-
-
-def intact(g):
-    buf, _, off, n = g
-    return bool((buf[:off] == CANARY).all()) and bool((buf[off + n:] == CANARY).all())
-
-
-def untouched(g):
-    return bool((g[0] == CANARY).all())
-
-
-def dev(a):
-    return torch.from_numpy(np.array(a, order="C")).to(DEV)       # a copy: the cached frames are read-only
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def run(call, shape):
-    """a device call into a guarded output: the result as numpy, the guard bands checked, every element written"""
-    g = guarded(shape)
-    assert call(g[1]) == 0
-    torch.cuda.synchronize()
-    assert intact(g), "wrote outside the output"
-    out = g[1].cpu().numpy()
-    assert not (bits(out) == CANARY).any(), "an output element was not written"
-    return out
-
-
-def same(got, want, what):
-    """bit-equal where the model is a number, a NaN where it is a NaN"""
-    nan = np.isnan(want)
-    assert np.array_equal(np.isnan(got), nan), what + ": where the NaNs are"
-    assert np.array_equal(bits(got)[~nan], bits(want)[~nan]), what
 
 
 def chunks(pool, F):
@@ -504,8 +398,8 @@ def test_errors_write_nothing():
     a = dev(analysed(size, C, F, 3))
     s = dev(np.full(F, 0.5, f32))
     tab = dev(np.full(M + 1, 0.5, f32))
-    g = guarded((C, F, M + 1, 2))
-    out = g[1]
+    g = flat((C, F, M + 1, 2))
+    out = g.data
     calls = [lambda x, o, p, t=tab: pv.band_device(x, o, p, p, p, p), lambda x, o, p, t=tab: pv.mask_device(x, o, t, p),
              lambda x, o, p, t=tab: pv.stencil_device(x, o, t, p, p), lambda x, o, p, t=tab: pv.arp_device(x, o, p, p, p),
              lambda x, o, p, t=tab: pv.lock_device(x, o, p, p), lambda x, o, p, t=tab: pv.warp_device(x, o, p, p, coefs=5)]
@@ -533,7 +427,7 @@ def test_errors_write_nothing():
     assert pv.mask_device(a, out, tab[:-1].contiguous(), s) == CL_INVALID_VALUE
     assert pv.stencil_device(a, out, tab.double(), s, s) == CL_INVALID_VALUE
     torch.cuda.synchronize()
-    assert untouched(g)
+    assert g.untouched()
     # an output overlapping the input or the table, shifted by one pair
     n = C * F * (M + 1) * 2
     buf = torch.full((2 * n + M + 1,), CANARY, dtype=torch.int32, device=DEV).view(torch.float32)
@@ -557,4 +451,4 @@ def test_errors_write_nothing():
     # and a good call still works: the lock of a frame with lock 0 is a copy
     assert pv.lock_device(a, out, 0.0) == 0
     torch.cuda.synchronize()
-    assert intact(g) and np.array_equal(bits(out.cpu().numpy()), bits(a.cpu().numpy()))
+    assert g.intact() and np.array_equal(bits(out.cpu().numpy()), bits(a.cpu().numpy()))

@@ -3,8 +3,8 @@ against the numpy restatement of their definitions (tests/pvoc_time_model.py).
 
 Everything is compared bit for bit with the float32 model: an output value is a fixed sequence of single correctly rounded
 float32 operations on the stream's values, so there is no tolerance to choose.  Where the model gives a NaN the device gives
-a NaN; payloads are not compared.  The frames are those of tests/test_gpu_pvoc_pair.py (its analysed() and raw() recipes,
-and its guard bands)."""
+a NaN; payloads are not compared.  The frames are tests/pvoc_inputs.py's analysed() and raw(), the guard bands those of
+tests/gpu_guard.py."""
 import numpy as np
 import pytest
 import torch
@@ -13,7 +13,8 @@ import opencl_fft_amd as fa
 from tests import pvoc_model as pm
 from tests import pvoc_time_model as tm
 from tests import stft_model
-from tests.test_gpu_pvoc_pair import CANARY, DEV, SR, analysed, bits, dev, guarded, hann, intact, raw, same
+from tests.gpu_guard import CANARY, DEV, bits, dev, flat, run, same
+from tests.pvoc_inputs import SR, analysed, hann, make_pvoc, raw
 
 pytestmark = pytest.mark.gpu
 CL_INVALID_VALUE = -30
@@ -24,12 +25,7 @@ MAX_FRAMES = (1, 2, 7, 40)
 
 
 def make(size, channels=1, max_frames=None, grid_max=None, monkeypatch=None):
-    if grid_max is not None:
-        monkeypatch.setenv("CLFA_PVOC_OPS_GRID_MAX", str(grid_max))
-    pv = fa.Pvoc(0, size, size // 4, SR, channels)
-    if grid_max is not None:
-        monkeypatch.delenv("CLFA_PVOC_OPS_GRID_MAX")
-    assert pv.get_error() == 0, pv.get_log()
+    pv = make_pvoc(size, size // 4, channels, env={"CLFA_PVOC_OPS_GRID_MAX": grid_max}, monkeypatch=monkeypatch)
     assert [pv.time_kernel_name(op) for op in OPS] == ["k_pvoc_blur", "k_pvoc_smooth", "k_pvoc_freeze"]
     if max_frames is not None:
         assert pv.blur_setup(max_frames) == 0 and pv.blur_max_frames() == max_frames
@@ -78,14 +74,8 @@ def dev_pq(p, q):
 
 def run_guarded(pv, op, x, p, q):
     """one device call into a guarded output: the result as numpy, the guard bands checked, every element written"""
-    g = guarded(x.shape)
-    dp, dq = dev_pq(p, q)
-    assert call(pv, op, dev(x), g[1], dp, dq) == 0
-    torch.cuda.synchronize()
-    assert intact(g), "wrote outside the output"
-    out = g[1].cpu().numpy()
-    assert not (bits(out) == CANARY).any(), "an output element was not written"
-    return out
+    dx, (dp, dq) = dev(x), dev_pq(p, q)
+    return run(lambda o: call(pv, op, dx, o, dp, dq), x.shape)
 
 
 def run_cut(pv, op, x, p, q, cut, stream=None):
@@ -128,11 +118,11 @@ def test_one_call_is_the_models_bits(size, channels):
                 same(pv.time_state(op), model.state(op), what + ": state")
                 # a second call goes on from the first one's state; plain numbers as per-frame values
                 num = (3.0, None) if op == tm.BLUR else ((0.3, 0.6) if op == tm.SMOOTH else (1.0, 0.0))
-                g = guarded(x.shape)
-                assert call(pv, op, dev(x), g[1], num[0], num[1]) == 0
+                g = flat(x.shape)
+                assert call(pv, op, dev(x), g.data, num[0], num[1]) == 0
                 torch.cuda.synchronize()
-                assert intact(g)
-                same(g[1].cpu().numpy(), model.run(op, x, num[0], num[1]), what + ": second call")
+                assert g.intact()
+                same(g.data.cpu().numpy(), model.run(op, x, num[0], num[1]), what + ": second call")
                 same(pv.time_state(op), model.state(op), what + ": state after the second call")
     assert pv.time_state_bytes() == 2 * channels * (size // 2 + 1) * 8 * (1 + 39)
 

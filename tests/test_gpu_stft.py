@@ -8,14 +8,10 @@ import torch
 import opencl_fft_amd as fa
 from oracle import oracle
 from tests import stft_model, util
+from tests.pvoc_inputs import hann
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-def hann(size):
-    n = np.arange(size)
-    return (0.5 - 0.5 * np.cos(2 * np.pi * n / size)).astype(np.float32)   # periodic
 
 
 def analyze_dev(size, hop, x_t, w=None):

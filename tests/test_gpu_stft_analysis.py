@@ -35,11 +35,12 @@ import opencl_fft_amd as fa
 from opencl_fft_amd import _lib
 from oracle import oracle
 from tests import fft_exact, util
+from tests import gpu_guard
 from tests import stft_model as sm
-from tests.test_gpu_stft_synth import CANARY, int_window
+from tests.gpu_guard import DEV
+from tests.test_gpu_stft_synth import int_window
 
 gpu = pytest.mark.gpu
-DEV = "cuda:0"
 GUARD = 1024            # complex canaries around the spectra; NaN floats around the signal
 TOL = util.TOL
 SIZES = [64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384]
@@ -183,17 +184,12 @@ def analyze_guarded(size, hop, x, w, route, grid_max=None, monkeypatch=None):
     # the predicate of clfa_stft_analyze_dev: the route takes the load form it is named after
     assert (rows.data_ptr() % 8 == 0 and hop % 2 == 0 and rows.stride(0) % 2 == 0) == a8
     C_, F, M = x.shape[0], st.frames(x.shape[1]), size // 2
-    n = C_ * F * M
-    buf = torch.full((2 * (GUARD + n + GUARD),), CANARY, dtype=torch.int32, device=DEV).view(torch.complex64)
-    out = buf[GUARD:GUARD + n].view(C_, F, M)
-    assert st.analyze_device(rows, out) == 0
+    g = gpu_guard.flat((C_, F, M), torch.complex64, misalign=0, before=2 * GUARD, after=2 * GUARD)
+    assert st.analyze_device(rows, g.data) == 0
     torch.cuda.synchronize()
-    raw = buf.cpu().numpy().view(np.uint32)
-    assert np.all(raw[:2 * GUARD] == CANARY), "wrote before the spectra"
-    assert np.all(raw[2 * (GUARD + n):] == CANARY), "wrote after the spectra"
-    body = raw[2 * GUARD:2 * (GUARD + n)]
-    assert not np.any(body == CANARY), "%d floats of the spectra were not written" % np.count_nonzero(body == CANARY)
-    return body.view(np.complex64).reshape(C_, F, M).copy()
+    g.check_sides("the spectra")
+    assert not g.unwritten(), "%d floats of the spectra were not written" % g.unwritten()
+    return g.data.cpu().numpy()
 
 
 def assert_isolated(spec):

@@ -25,12 +25,12 @@ import torch
 
 import opencl_fft_amd as fa
 from oracle import oracle
+from tests import gpu_guard
 from tests import stft_model as sm
+from tests.gpu_guard import DEV
 from tests.test_gpu_stft import analyze_dev, check_analysis
 
 gpu = pytest.mark.gpu
-DEV = "cuda:0"
-CANARY = 0x7FC0BEEF     # guard bands: a quiet NaN with a payload no kernel produces (tests/test_gpu_fft_impulses.py)
 GUARD, PAD = 1024, 5    # floats before and after the buffer; floats between a row's end and the next row
 NORM_TOL = 2.0 ** -23 * (1 + 1e-6)   # one rounding of the envelope + one division
 SIZES = sorted({s for s, _ in sm.SYNTH_PAIRS})
@@ -87,18 +87,11 @@ def synth_guarded(size, hop, spec, w, normalize, grid_max=None, monkeypatch=None
     C, F, _ = spec.shape
     L = st.samples(F)
     assert L == (F - 1) * hop + size
-    stride = L + PAD
-    buf = torch.full((GUARD + C * stride + GUARD,), CANARY, dtype=torch.int32, device=DEV).view(torch.float32)
-    rows = buf[GUARD:GUARD + C * stride].view(C, stride)[:, :L]
-    s_t = torch.from_numpy(np.array(spec)).to(DEV)   # (a writable copy: the shared case is read-only)
-    assert st.synthesize_device(s_t, rows, normalize=normalize) == 0
+    g = gpu_guard.rows(C, L, L + PAD, before=GUARD, after=GUARD)
+    assert st.synthesize_device(gpu_guard.dev(spec), g.data, normalize=normalize) == 0
     torch.cuda.synchronize()
-    raw = buf.cpu().numpy().view(np.uint32)
-    assert np.all(raw[:GUARD] == CANARY), "wrote before the buffer"
-    assert np.all(raw[GUARD + C * stride:] == CANARY), "wrote after the buffer"
-    body = raw[GUARD:GUARD + C * stride].reshape(C, stride)
-    assert np.all(body[:, L:] == CANARY), "wrote between the rows"
-    return body[:, :L].view(np.float32).copy()
+    g.check_sides("the buffer")
+    return g.host()
 
 
 def split_of(size, hop, C, F):

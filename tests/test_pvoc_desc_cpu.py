@@ -23,7 +23,7 @@ def bits(a):
 
 
 def differs(a, b):
-    """some compared value differs: the test of tests/test_gpu_pvoc_pair.py's same(), negated"""
+    """some compared value differs: the test of tests/gpu_guard.py's same(), negated"""
     na, nb = np.isnan(a), np.isnan(b)
     return not np.array_equal(na, nb) or not np.array_equal(bits(a)[~na], bits(b)[~na])
 

@@ -8,6 +8,7 @@ import pytest
 
 from tests import pvoc_model as pm
 from tests import pvoc_probe as pp
+from tests.pvoc_inputs import two_tones
 
 f32 = np.float32
 SR = pp.SR
@@ -131,11 +132,7 @@ def plant_dev(fr, c, f, k, turns, size, hop):
 
 def stft_style_spectra(size, hop, F, seed):
     """the input of tests/test_gpu_pvoc.py's stft_spectra, in numpy: Hann-windowed frames of noise plus two sinusoids"""
-    rng = np.random.default_rng(seed)
-    n = size + (F - 1) * hop
-    t = np.arange(n)
-    x = 0.1 * rng.standard_normal(n) + 0.7 * np.cos(2 * np.pi * 10.37 / size * t + 0.2) \
-        + 0.4 * np.cos(2 * np.pi * (size / 2 - 3.21) / size * t)
+    x = two_tones(size, hop, 1, F, seed)[0]
     w = 0.5 - 0.5 * np.cos(2 * np.pi * np.arange(size) / size)
     X = np.fft.rfft(np.stack([x[f * hop:f * hop + size] * w for f in range(F)]), axis=-1)
     return pm.unbins(X).astype(np.complex64)[None]
