@@ -724,6 +724,55 @@ CLFA_API size_t clfa_pvoc_desc_state_bytes(const clfa_pvoc *pv);
 /* "k_pvoc_desc" ("" for a failed object) */
 CLFA_API const char *clfa_pvoc_desc_kernel_name(const clfa_pvoc *pv);
 
+/* ---- the N loudest bins of every frame: trace, residual, bin list ---- */
+/* Csound's pvstrace with an exact count: the N loudest bins of a range of every frame are kept and the rest of the range
+ * is silenced; with CLFA_PVOC_TRACE_RESIDUAL it is the other way round (the noise part of a sines-plus-noise split); and
+ * the bins kept can be had as a list.
+ * frames_in, frames_out: channels x F x (M + 1) x 2 float32 in the layout above, 8-byte aligned.  n: F float32, one per
+ * frame, shared by the channels, 4-byte aligned, required.  bins: NULL, or channels x F x list_n int32, 4-byte aligned;
+ * list_n >= 1 where bins is given, not looked at where it is NULL.  first_bin and nbins select the bins first_bin ..
+ * first_bin + nbins - 1 as for clfa_pvoc_desc_dev (0 <= first_bin, 1 <= nbins, first_bin + nbins <= M + 1); flags: bit 0
+ * is CLFA_PVOC_TRACE_RESIDUAL, any other bit is CLFA_INVALID_VALUE.
+ *
+ * Per channel and frame f, on the bins of the range:
+ *   COUNT      N = 0 where n[f] >= 0 does not hold (a NaN, a negative), else N = (int)floorf(fminf(n[f], (float)nbins)).
+ *   ORDER      bin j is LOUDER than bin k iff amp[j] > amp[k] as float32 (so -0 == +0), or the amps are equal and j < k:
+ *              the tie rule of the descriptors' peak, the lower bin wins.  The amp is compared as it stands, not its
+ *              absolute value.  A bin whose amp is a NaN is never a candidate; every other bin of the range is one.
+ *   SELECTION  a bin of the range is SELECTED iff it is a candidate and fewer than N candidates of the range are louder
+ *              than it: exactly min(N, number of candidates) bins.  Ties at the cut are broken, not all kept (Csound's
+ *              pvstrace keeps every bin >= the N-th loudest amp, a varying number).
+ *   FRAMES     the freq column is always the input's bits; a bin outside the range is copied as bits.  Inside the range,
+ *              without RESIDUAL a selected bin's amp is the input's bits and every other amp is +0 (the input is not
+ *              used: a NaN stays out); with RESIDUAL a selected bin's amp is +0 and every other amp is the input's bits
+ *              (a NaN amp passes through).
+ *   BIN LIST   (bins != NULL) the frame's selected bins in ascending bin order, the first list_n of them; the remaining
+ *              entries of the row are -1.  The same list with and without RESIDUAL.
+ * There is no arithmetic and so no rounding in any of it, and the selection is a function of one frame: the outputs are
+ * the same bits however a stream is cut into calls, on any stream and for any grid cap.
+ *
+ * Stateless: no state of the object is read or written, and a device call allocates nothing.  The rules of the frame
+ * operations above hold: asynchronous on `stream`, capturable, one launch per call, one stream at a time, the current
+ * device left as found; F == 0 succeeds and does nothing.  Argument checks that need no device come first: on an object
+ * whose creation found no device a bad argument is still CLFA_INVALID_VALUE, a good one the object's error.  This is the
+ * one call with two outputs: frames_out or bins overlapping frames_in, n or each other, even partly, is
+ * CLFA_INVALID_VALUE and nothing is written.  The blocking form takes any values of n (each is defined above).
+ * tests/pvoc_trace_model.py restates all of it in numpy.
+ *
+ * Kernel: "k_pvoc_trace" (a group of W = min(M, 256) lanes owns a frame and holds its pairs in registers, so the frame is
+ * read once; the cut is found by a radix select on the monotone uint32 image of the amps, four passes of 8 bits over 256
+ * integer counters in LDS; the tie rule and the list are one prefix count in bin order, by ballots inside a wave and the
+ * per-row counts of the waves through LDS).  No atomics on global memory, no waiting between workgroups.
+ * CLFA_PVOC_OPS_GRID_MAX caps its workgroups. */
+enum { CLFA_PVOC_TRACE_RESIDUAL = 1 };
+CLFA_API int clfa_pvoc_trace_dev(clfa_pvoc *pv, const void *frames_in, void *frames_out, const void *n, void *bins,
+                                 int list_n, long F, int first_bin, int nbins, int flags, void *stream);
+/* host arrays, copied in and out, blocking */
+CLFA_API int clfa_pvoc_trace(clfa_pvoc *pv, const float *frames_in, float *frames_out, const float *n, int *bins,
+                             int list_n, long F, int first_bin, int nbins, int flags);
+/* "k_pvoc_trace" ("" for a failed object) */
+CLFA_API const char *clfa_pvoc_trace_kernel_name(const clfa_pvoc *pv);
+
 /* ---- convolution matrix (extension: nothing of the reference's) ------------- */
 /* Uniformly partitioned overlap-add convolution of `inputs` signals with an outputs x inputs matrix of static responses:
  * y_o = sum over i of x_i * h_{o,i}.

@@ -828,6 +828,55 @@ class Pvoc(_Handle):
               "Pvoc.describe")
         return out
 
+    # ---- frames -> frames: the N loudest bins of every frame (Csound's pvstrace; stateless; clfft_amd.h) ----
+
+    TRACE_RESIDUAL = 1
+
+    def trace_kernel_name(self):
+        """ "k_pvoc_trace" ("" for a failed object)"""
+        return lib().clfa_pvoc_trace_kernel_name(self._h).decode()
+
+    def trace_device(self, frames_in, frames_out, n, first_bin=0, nbins=None, residual=False, bins_out=None, stream=None):
+        """torch: frames (channels, F, size/2 + 1, 2) float32, contiguous -> frames_out of the same shape: of the bins
+        first_bin .. first_bin + nbins - 1 (default: up to size/2) of every frame the floor(n) loudest keep their amp and the
+        others get +0; residual: the other way round.  Equal amps: the lower bin is the louder one, so exactly floor(n) bins
+        are selected (Csound's pvstrace keeps all ties); a NaN amp is never selected.  n: a number or a float32 device tensor
+        (F,), shared by the channels.  bins_out: an int32 device tensor (channels, F, L), contiguous ((F, L) for one
+        channel), that takes the selected bins in ascending order, the first L of them, then -1.  Asynchronous on `stream`."""
+        import torch
+        F = self._device_frames(frames_in, frames_out)
+        if F is None:
+            return CL_INVALID_VALUE
+        ptrs, keep = self._per_frame_ptrs((n,), F, frames_out.device)
+        if ptrs is None:
+            return CL_INVALID_VALUE
+        bins, L = None, 0
+        if bins_out is not None:
+            b = tuple(bins_out.shape)
+            if len(b) == 2 and self.channels == 1:
+                b = (1,) + b
+            if (len(b) != 3 or b[:2] != (self.channels, F) or b[2] < 1 or bins_out.dtype != torch.int32
+                    or not bins_out.is_contiguous() or bins_out.device != frames_out.device):
+                return CL_INVALID_VALUE
+            bins, L = bins_out.data_ptr(), b[2]
+        first_bin, nbins, _ = self._selection(first_bin, nbins, 1)
+        return lib().clfa_pvoc_trace_dev(self._h, frames_in.data_ptr(), frames_out.data_ptr(), ptrs[0], bins, L, F, first_bin,
+                                         nbins, self.TRACE_RESIDUAL if residual else 0, _stream_of(frames_out, stream))
+
+    def trace(self, frames, n, first_bin=0, nbins=None, residual=False, list_n=0):
+        """host form of trace_device, blocking: float32 (channels, F, size/2 + 1, 2) (or (F, size/2 + 1, 2)) -> the new
+        frames, or (frames, bins) with bins int32 (.., F, list_n) when list_n > 0"""
+        frames, F = self._host_frames(frames)
+        n = self._per_frame_host(n, F)
+        out = np.zeros_like(frames)
+        list_n = int(list_n)
+        bins = np.full(frames.shape[:-2] + (list_n,), -1, np.int32) if list_n > 0 else None
+        first_bin, nbins, _ = self._selection(first_bin, nbins, 1)
+        check(lib().clfa_pvoc_trace(self._h, frames.ctypes.data, out.ctypes.data, n.ctypes.data,
+                                    None if bins is None else bins.ctypes.data, list_n, F, first_bin, nbins,
+                                    self.TRACE_RESIDUAL if residual else 0), "Pvoc.trace")
+        return out if bins is None else (out, bins)
+
     # ---- frames -> samples: the oscillator bank (Csound's pvsadsyn; a state of its own; clfft_amd.h) ----
 
     def adsyn_kernel_name(self):

@@ -372,6 +372,19 @@ struct PvocDescArgs : PvocFramesArgs {   // F: also the rows per channel of desc
 // k_pvoc_desc<min(M, 256)>, which only reads the state, then its commit on the same stream (k_pvoc_tail)
 hipError_t launch_pvoc_desc(const PvocDescArgs &a, const DeviceInfo &di, hipStream_t s);
 
+// ---- the N loudest bins of every frame of a stream of (amp, freq) frames (pvoc_trace.hip) ----
+struct PvocTraceArgs : PvocFramesArgs {
+  const cpx *in = nullptr;         // frames as (amp, freq) pairs
+  cpx *out = nullptr;
+  const float *n = nullptr;        // F values, shared by the channels
+  int *bins = nullptr;             // NULL, or channels x F x list_n: the bins kept, ascending, then -1
+  int list_n = 0;
+  int lo = 0, hi = 0;              // the range of bins, 0 <= lo <= hi <= M
+  int residual = 0;                // the complement: the selected bins silenced, the others kept
+};
+// one launch: k_pvoc_trace<min(M, 256)>
+hipError_t launch_pvoc_trace(const PvocTraceArgs &a, const DeviceInfo &di, hipStream_t s);
+
 // ---- direct convolution ----------------------------------------------------------
 struct DconvPlan {
   int C;    // taps per workgroup

@@ -2,8 +2,8 @@
 // power, moment, centroid, flux and peak of a range of bins, eight float32 per frame.  The first parallel float sums of
 // the Pvoc code: the header fixes their TREE SUM (which lanes' values meet in which addition), and the kernel is written
 // to it, so the bits do not depend on the grid, on how the stream is cut into calls or on the run length.  No atomics, no
-// waiting between workgroups.  The decoding of a grid-stride item and the cap on a launch's workgroups are
-// pvoc_device.hpp's; the state's commit is pvoc_time.hip's k_pvoc_tail.
+// waiting between workgroups.  The group kernels' item (which run a group of W lanes takes) and launch are
+// pvoc_device.hpp's, shared with pvoc_trace.hip; the state's commit is pvoc_time.hip's k_pvoc_tail.
 //
 //   k_pvoc_desc<W>  W = min(M, 256) lanes form a group, lane j holding the tree's p[j]; 256 / W groups share a workgroup.
 //                   A group takes a run of kDescRun = 4 consecutive frames of one channel and walks the bins outermost,
@@ -32,7 +32,7 @@ namespace clfa {
 
 namespace {
 
-constexpr int kDescWG = 256;    // lanes of a workgroup = the largest W
+constexpr int kDescWG = kGroupWG;   // lanes of a workgroup = the largest W
 constexpr int kDescRun = 4;     // consecutive frames per run
 constexpr int kDescSums = 4;    // mag, pow, mom, flux
 constexpr int kDescVals = kDescRun * kDescSums;
@@ -114,17 +114,16 @@ __global__ __launch_bounds__(kDescWG) void k_pvoc_desc(const cpx *__restrict__ i
                                                        float *__restrict__ desc, long F, int M, int lo, int hi, int rectify,
                                                        float cf, long runs, long rgroups, long items) {
 #pragma clang fp contract(off)
-  constexpr int R = kDescRun, G = kDescWG / W, WAVES = W > 64 ? W / 64 : 1;
+  constexpr int R = kDescRun, WAVES = W > 64 ? W / 64 : 1;
   __shared__ float s_sum[kDescWG / 64][kDescVals];
   __shared__ DescPeak s_peak[kDescWG / 64][R];
-  const int tid = threadIdx.x, g = tid / W, j = tid & (W - 1);
+  const int tid = threadIdx.x;
   const long row = M + 1;
 #pragma unroll 1
   for (long item = blockIdx.x; item < items; item += gridDim.x) {
-    int tile;
-    long rg, c;
-    pvoc_item(item, 1, rgroups, tile, rg, c);
-    const long r = rg * G + g;
+    int g, j;
+    long r, c;
+    pvoc_group_row<W>(item, rgroups, g, j, r, c);
     const long f0 = r * R;
     const int nf = r < runs ? (int)(F - f0 < R ? F - f0 : R) : 0;   // frames of the run; 0: the group idles along
     const float *ic = (const float *)(in + c * F * row);              // the channel's amps, 2 floats apart
@@ -238,11 +237,10 @@ __global__ __launch_bounds__(kDescWG) void k_pvoc_desc(const cpx *__restrict__ i
 
 template <int W>
 static hipError_t launch_pvoc_desc_w(const PvocDescArgs &a, const DeviceInfo &di, hipStream_t s) {
-  constexpr int G = kDescWG / W;
-  const long runs = (a.F + kDescRun - 1) / kDescRun, rgroups = (runs + G - 1) / G, items = (long)a.channels * rgroups;
-  const int grid = pvoc_grid(items, (long)di.num_cus * 8, a.grid_max);
-  hipLaunchKernelGGL((k_pvoc_desc<W>), dim3(grid), dim3(kDescWG), 0, s, a.in, a.last, a.desc, a.F, a.M, a.lo, a.hi,
-                     a.rectify, a.cf, runs, rgroups, items);
+  const long runs = (a.F + kDescRun - 1) / kDescRun;
+  const PvocGroups q = pvoc_groups<W>(runs, a.channels, di, a.grid_max);
+  hipLaunchKernelGGL((k_pvoc_desc<W>), dim3(q.grid), dim3(kDescWG), 0, s, a.in, a.last, a.desc, a.F, a.M, a.lo, a.hi,
+                     a.rectify, a.cf, runs, q.rgroups, q.items);
   return hipGetLastError();
 }
 
@@ -250,7 +248,7 @@ hipError_t launch_pvoc_desc(const PvocDescArgs &a, const DeviceInfo &di, hipStre
   if (a.F <= 0 || a.channels <= 0) return hipSuccess;
   if (a.lo < 0 || a.lo > a.hi || a.hi > a.M) return hipErrorInvalidValue;
   hipError_t e;
-  switch (a.M < kDescWG ? a.M : kDescWG) {
+  switch (pvoc_group_lanes(a.M)) {
     case 32: e = launch_pvoc_desc_w<32>(a, di, s); break;
     case 64: e = launch_pvoc_desc_w<64>(a, di, s); break;
     case 128: e = launch_pvoc_desc_w<128>(a, di, s); break;

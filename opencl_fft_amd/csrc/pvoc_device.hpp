@@ -1,7 +1,9 @@
 // pvoc_device.hpp — what the Pvoc kernel files share (pvoc_kernels.hip, pvoc_ops.hip, pvoc_pair.hip, pvoc_time.hip,
-// pvoc_shape.hip, pvoc_desc.hip, pvoc_adsyn.hip):
+// pvoc_shape.hip, pvoc_desc.hip, pvoc_trace.hip, pvoc_adsyn.hip):
 //   pvoc_item, pvoc_bin    the decoding of a grid-stride item, and the bin a lane of a tile kernel takes of it
 //   pvoc_grid, pvoc_tiles  the cap on a launch's workgroups, and the tiles, items and grid of a tile launch
+//   pvoc_group_row, pvoc_groups   the group kernels (k_pvoc_desc<W>, k_pvoc_trace<W>): which row of a channel a group of W
+//                          lanes takes of an item, and the items and grid of such a launch
 //   pvoc_empty, pvoc_clamp01, pvoc_morph   the frame operations' EMPTY bin, clamp and interpolation rule
 //   pvoc_scale_source      the pitch scale's source map (k_pvoc_map, k_pvoc_formant, k_pvoc_warp)
 //   pvoc_scan              the chunked scan that turns the per-chunk sums of phase increments into the bases the
@@ -49,6 +51,37 @@ static inline PvocTiles pvoc_tiles(int M, int lanes, long outer, const DeviceInf
   t.items = outer * t.tiles;
   t.grid = pvoc_grid(t.items, (long)di.num_cus * per_cu, grid_max);
   return t;
+}
+
+// The group kernels: W = min(M, 256) lanes form a group that owns one row of a channel (a frame, a run of frames),
+// kGroupWG / W groups share a workgroup, and an item is a (channel, kGroupWG / W consecutive rows).
+constexpr int kGroupWG = 256;   // lanes of a workgroup = the largest W
+static inline int pvoc_group_lanes(int M) { return M < kGroupWG ? M : kGroupWG; }
+
+// The prologue of a group kernel: the lane's group g of the workgroup and its place j in it, the item's channel c and
+// the group's row r of that channel (r may lie past the last row: the group then idles along)
+template <int W>
+__device__ __forceinline__ void pvoc_group_row(long item, long rgroups, int &g, int &j, long &r, long &c) {
+  int tile;
+  long rg;
+  g = (int)threadIdx.x / W;
+  j = (int)threadIdx.x & (W - 1);
+  pvoc_item(item, 1, rgroups, tile, rg, c);
+  r = rg * (kGroupWG / W) + g;
+}
+
+// A group launch over `rows` rows per channel: the groups of rows per channel, the items, the grid
+struct PvocGroups {
+  long rgroups, items;
+  int grid;
+};
+template <int W>
+static inline PvocGroups pvoc_groups(long rows, int channels, const DeviceInfo &di, int grid_max) {
+  PvocGroups q;
+  q.rgroups = (rows + kGroupWG / W - 1) / (kGroupWG / W);
+  q.items = (long)channels * q.rgroups;
+  q.grid = pvoc_grid(q.items, (long)di.num_cus * 8, grid_max);
+  return q;
 }
 
 // an EMPTY bin of the frame operations: silent, at its bin centre (cf = sr / size)

@@ -46,6 +46,7 @@ struct clfa_pvoc {
   // the descriptors (pvoc_desc.hip): the stream's previous frame, channels x (M + 1) pairs of which the amps are the
   // state `last`; staging of the host form's rows
   DevBuf dlast, sdesc;
+  DevBuf strace_bins;   // the N loudest bins (pvoc_trace.hip): staging of the host form's bin list
   StreamOrder order;
 };
 
@@ -197,7 +198,7 @@ struct PvocArray {
   const void *ptr;
   size_t bytes;
   int align;                  // what a device form asks of ptr: 8 (frames, spectra, pairs) or 4 (floats)
-  bool out;                   // the call's one output; the others are inputs
+  bool out;                   // an output of the call (one, or trace's two: the frames and the bin list); else an input
   DevBuf clfa_pvoc::*stage;   // where a blocking form stages it, its rows packed
   bool used = true;
   size_t rows = 1, pitch = 0;
@@ -205,18 +206,16 @@ struct PvocArray {
 };
 constexpr size_t kPvocArrays = 5;   // at most so many per call
 
-// The arrays' rules: a NULL is an invalid value, so is with device_ptrs a misaligned one, so is an input that overlaps
-// the output even partly (the inputs may overlap each other)
+// The arrays' rules: a NULL is an invalid value, so is with device_ptrs a misaligned one, so is an output that overlaps
+// any other array of the call even partly, an input or another output (the inputs may overlap each other)
 template <size_t N>
 static int pvoc_arrays_check(const PvocArray (&arrays)[N], bool device_ptrs) {
-  const PvocArray *out = nullptr;
-  for (const PvocArray &a : arrays) {
-    if (!a.used) continue;
-    if (!a.ptr || (device_ptrs && ((uintptr_t)a.ptr & (uintptr_t)(a.align - 1)))) return CLFA_INVALID_VALUE;
-    if (a.out) out = &a;
-  }
   for (const PvocArray &a : arrays)
-    if (a.used && !a.out && out && spans_overlap(a.ptr, a.span(), out->ptr, out->span())) return CLFA_INVALID_VALUE;
+    if (a.used && (!a.ptr || (device_ptrs && ((uintptr_t)a.ptr & (uintptr_t)(a.align - 1))))) return CLFA_INVALID_VALUE;
+  for (const PvocArray &out : arrays)
+    for (const PvocArray &a : arrays)
+      if (out.used && out.out && a.used && &a != &out && spans_overlap(a.ptr, a.span(), out.ptr, out.span()))
+        return CLFA_INVALID_VALUE;
   return CLFA_SUCCESS;
 }
 
@@ -233,7 +232,7 @@ static int pvoc_dev_form(clfa_pvoc *p, int chk, void *stream, Launch launch) {
 
 // The blocking forms after their checks: every array the op looks at has a staging buffer on the device, ensured in the
 // order of the list; the inputs are copied in, dev(d) runs the device work on the staged arrays d[i] (NULL where the op
-// does not look) and the object's stream, the output is copied out, and the stream is waited for.
+// does not look) and the object's stream, every output is copied out, and the stream is waited for.
 template <size_t N, class Dev>
 static int pvoc_staged(clfa_pvoc *p, const PvocArray (&arrays)[N], Dev dev) {
   static_assert(N <= kPvocArrays, "kPvocArrays");
@@ -761,6 +760,55 @@ int clfa_pvoc_desc_read_state(clfa_pvoc *p, float *host) {
 
 size_t clfa_pvoc_desc_state_bytes(const clfa_pvoc *p) { return p ? p->dlast.bytes : 0; }
 const char *clfa_pvoc_desc_kernel_name(const clfa_pvoc *p) { return !p || p->err ? "" : "k_pvoc_desc"; }
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------
+// frames -> frames: the N loudest bins of every frame, or all but those, and the list of the bins (pvoc_trace.hip)
+// ---------------------------------------------------------------------------------
+
+// The one call with two outputs: the frames, and the bin list where `bins` is given (list_n is looked at only then).
+// Every n has a meaning (a NaN or a negative keeps nothing), so the blocking form has no values to refuse.
+static int pvoc_trace_call(clfa_pvoc *p, bool blocking, const void *in, void *out, const void *n, void *bins, int list_n,
+                           long F, int first_bin, int nbins, int flags, void *stream) {
+  if (int e = pvoc_usable(p)) return e;
+  const bool scalars_ok = first_bin >= 0 && nbins >= 1 && (long)first_bin + nbins - 1 <= p->M &&
+                          !(flags & ~CLFA_PVOC_TRACE_RESIDUAL) && !(bins && list_n < 1);
+  const size_t fbytes = pvoc_frame_bytes(p, F);
+  const size_t lbytes = bins && list_n >= 1 ? sizeof(int) * (size_t)p->channels * (size_t)(F > 0 ? F : 0) * (size_t)list_n : 0;
+  const PvocArray arrays[] = {{in, fbytes, 8, false, &clfa_pvoc::sframes},
+                              {out, fbytes, 8, true, &clfa_pvoc::sop_out},
+                              {n, sizeof(float) * (size_t)F, 4, false, &clfa_pvoc::sop_par},
+                              {bins, lbytes, 4, true, &clfa_pvoc::strace_bins, bins != nullptr}};
+  const auto launch = [&](const void *const *d, hipStream_t s) {
+    PvocTraceArgs a;
+    pvoc_frames_args(p, F, a);
+    a.in = (const cpx *)d[0];
+    a.out = (cpx *)d[1];
+    a.n = (const float *)d[2];
+    a.bins = (int *)d[3];
+    a.list_n = list_n;
+    a.lo = first_bin;
+    a.hi = first_bin + nbins - 1;
+    a.residual = flags & CLFA_PVOC_TRACE_RESIDUAL;
+    return launch_pvoc_trace(a, p->di, s);
+  };
+  return pvoc_call(p, blocking, stream, scalars_ok, F, arrays, CLFA_SUCCESS, pvoc_no_values, launch);
+}
+
+extern "C" {
+
+int clfa_pvoc_trace_dev(clfa_pvoc *p, const void *frames_in, void *frames_out, const void *n, void *bins, int list_n, long F,
+                        int first_bin, int nbins, int flags, void *stream) {
+  return pvoc_trace_call(p, false, frames_in, frames_out, n, bins, list_n, F, first_bin, nbins, flags, stream);
+}
+
+int clfa_pvoc_trace(clfa_pvoc *p, const float *frames_in, float *frames_out, const float *n, int *bins, int list_n, long F,
+                    int first_bin, int nbins, int flags) {
+  return pvoc_trace_call(p, true, frames_in, frames_out, n, bins, list_n, F, first_bin, nbins, flags, nullptr);
+}
+
+const char *clfa_pvoc_trace_kernel_name(const clfa_pvoc *p) { return !p || p->err ? "" : "k_pvoc_trace"; }
 
 }  // extern "C"
 
