@@ -1,0 +1,590 @@
+"""Pvoc: the phase vocoder on Stft's spectra — (amp, freq) frames both ways, and the operations on such frames."""
+import numpy as np
+
+from ._base import CL_INVALID_VALUE, _Object, _data, _is_f32, _row_view, _stream_of
+from ._lib import check
+
+
+def _dense_f32(t, shape):
+    """a device call's tensor: float32, contiguous, of this shape"""
+    return _is_f32(t) and tuple(t.shape) == tuple(shape) and t.is_contiguous()
+
+
+class Pvoc(_Object):
+    """Phase vocoder on the spectra of Stft (extension, clfa_pvoc in clfft_amd.h): analyze() reads (channels, F, size/2)
+    complex64 spectra as (channels, F, size/2 + 1, 2) float32 frames of (amp, freq in Hz) per bin, synthesize() turns such
+    frames back into spectra.  The object carries the last spectrum (analysis) and an integer phase per bin (synthesis)
+    from call to call, so a stream may be cut into calls anywhere; reset() returns both to their start.
+    adsyn() is the second way back to sound: an oscillator per bin, summed straight into samples (a state of its own).
+    describe() turns frames into control values: eight descriptors per frame (the previous frame's amps carried along).
+    Like the other objects the constructor does not raise, and every call returns its status."""
+    _abi = "clfa_pvoc_"
+
+    def __init__(self, device_id, size, hop, sr, channels=1):
+        self.size, self.hop, self.sr, self.channels = int(size), int(hop), float(sr), int(channels)
+        self.M = self.size // 2
+        self._create(self._fn("create"), int(device_id), self.size, self.hop, self.sr, self.channels)
+
+    def kernel_name(self, synthesis=False):
+        return self._text("kernel_name", int(bool(synthesis)))
+
+    def scan_chunk(self):
+        """frames per chunk of the synthesis' phase scan (fixed)"""
+        return self._fn("scan_chunk")()
+
+    def reset(self):
+        return self._get("reset")
+
+    def read_phase(self):
+        """the synthesis state: uint32 (channels, size/2 + 1), units of 2^-32 turn (blocking)"""
+        out = np.zeros((self.channels, self.M + 1), np.uint32)
+        check(self._get("read_phase", out.ctypes.data), "Pvoc.read_phase")
+        return out
+
+    def read_prev(self):
+        """the analysis state: complex64 (channels, size/2 + 1), z of the last frame analysed (blocking)"""
+        out = np.zeros((self.channels, self.M + 1), np.complex64)
+        check(self._get("read_prev", out.ctypes.data), "Pvoc.read_prev")
+        return out
+
+    # ---- what the calls share: shapes, then the preparation of a host call and of a device call ----
+
+    def _full(self, shape, rank):
+        """`shape` as a tuple of `rank` axes, the channel axis first: for one channel it may be left out"""
+        s = tuple(shape)
+        return (1,) + s if len(s) == rank - 1 and self.channels == 1 else s
+
+    def _frames_shape(self, shape):
+        """F of a (channels, F, M + 1, 2) shape (or (F, M + 1, 2) for one channel), else None"""
+        f = self._full(shape, 4)
+        return f[1] if len(f) == 4 and f[0] == self.channels and f[2:] == (self.M + 1, 2) else None
+
+    def _shapes(self, spectra, frames):
+        """F if `spectra` is (channels, F, M) (or (F, M) for one channel) and `frames` the matching (.., F, M + 1, 2), else None"""
+        F = self._frames_shape(frames.shape)
+        return F if F is not None and self._full(spectra.shape, 3) == (self.channels, F, self.M) else None
+
+    def _host_frames(self, frames):
+        """(the frames as a contiguous float32 array, F); ValueError for another shape"""
+        frames = np.ascontiguousarray(frames, dtype=np.float32)
+        F = self._frames_shape(frames.shape)
+        if F is None:
+            raise ValueError("frames must be (%d, F, %d, 2)" % (self.channels, self.M + 1))
+        return frames, F
+
+    def _host_prep(self, frames, pars=(), rows=None, tail=None, dtype=np.float32):
+        """A host call's preparation: (the frames as a contiguous float32 array, F, the per-frame values `pars` — numbers
+        or arrays, None stays None — as contiguous float32 (rows,) arrays, the zeroed output (.., rows) + tail).  rows: F
+        unless given; tail: (M + 1, 2), the output being frames, unless given.  ValueError for frames of another shape."""
+        frames, F = self._host_frames(frames)
+        rows = F if rows is None else rows
+        pars = [None if par is None else np.ascontiguousarray(np.broadcast_to(np.asarray(par, dtype=np.float32), (rows,)))
+                for par in pars]
+        return frames, F, pars, np.zeros(frames.shape[:-3] + (rows,) + ((self.M + 1, 2) if tail is None else tail), dtype)
+
+    def _device_frames(self, *tensors):
+        """F if every tensor holds F frames for a device call ((channels, F, M + 1, 2), or (F, M + 1, 2) for one channel,
+        float32, contiguous), else None"""
+        F = self._frames_shape(tensors[0].shape)
+        ok = F is not None and all(self._frames_shape(t.shape) == F and _dense_f32(t, t.shape) for t in tensors)
+        return F if ok else None
+
+    def _device_prep(self, F, device, pars, columns=0):
+        """The rest of a device call's preparation, F being _device_frames() of its frame tensors: (F, the pointers of the
+        per-frame values `pars`, the tensors to keep until the call is made), or None for a call to refuse: F is None,
+        or a value is a tensor that is not float32 (F,), contiguous.  A plain number becomes a tensor of F copies on
+        `device`, None a NULL.  columns: the values become the columns of the one (F, columns) tensor of rows that the
+        shaping ops read instead."""
+        if F is None:
+            return None
+        pars = [par if par is None or hasattr(par, "data_ptr") else float(par) for par in pars]
+        if any(hasattr(par, "data_ptr") and not _dense_f32(par, (F,)) for par in pars):
+            return None
+        # Known ordering problem, left as it was: the tensors made here are filled on torch's current stream, while the
+        # library call that reads them runs on the caller's `stream`.  When the two differ nothing orders the fill before
+        # the kernel, and the tensors are released when the caller returns.  A fix belongs here and nowhere else.
+        import torch
+        made = dict(dtype=torch.float32, device=device)
+        if columns:
+            rows = torch.zeros((F, columns), **made)
+            for i, par in enumerate(pars):
+                rows[:, i] = par
+            pars = [rows]
+        else:
+            pars = [torch.full((F,), par, **made) if isinstance(par, float) else par for par in pars]
+        return F, [None if t is None else t.data_ptr() for t in pars], pars
+
+    @staticmethod
+    def _op_code(ops, op):
+        """an op given by its name or its code, as the code (-1 for an unknown name)"""
+        return ops.get(op, -1) if isinstance(op, str) else int(op)
+
+    def _selection(self, first_bin, nbins, step):
+        first_bin, step = int(first_bin), int(step)
+        if nbins is None:      # every bin from first_bin up that the step reaches
+            nbins = (self.M - first_bin) // step + 1 if step >= 1 and 0 <= first_bin <= self.M else 0
+        return first_bin, int(nbins), step
+
+    # ---- spectra <-> frames ----
+
+    def _device_call(self, name, spectra, frames, src, dst, stream):
+        F = self._shapes(spectra, frames)
+        if (F is None or str(spectra.dtype) != "torch.complex64" or not _is_f32(frames)
+                or not spectra.is_contiguous() or not frames.is_contiguous()):
+            return CL_INVALID_VALUE
+        return self._get(name, src.data_ptr(), dst.data_ptr(), F, _stream_of(dst, stream))
+
+    def analyze_device(self, spectra, frames_out, stream=None):
+        """torch: spectra (channels, F, size/2) complex64 -> frames_out (channels, F, size/2 + 1, 2) float32, both
+        contiguous (anything else: CL_INVALID_VALUE); asynchronous on `stream` (default: the current stream)"""
+        return self._device_call("analyze_dev", spectra, frames_out, spectra, frames_out, stream)
+
+    def synthesize_device(self, frames, spectra_out, stream=None):
+        """torch: frames (channels, F, size/2 + 1, 2) float32 -> spectra_out (channels, F, size/2) complex64"""
+        return self._device_call("synthesize_dev", spectra_out, frames, frames, spectra_out, stream)
+
+    def analyze(self, spectra):
+        """host: complex64 (channels, F, size/2) (or (F, size/2) for one channel) -> float32 (.., F, size/2 + 1, 2)"""
+        spectra = np.ascontiguousarray(spectra, dtype=np.complex64)
+        out = np.zeros(spectra.shape[:-1] + (self.M + 1, 2), np.float32)
+        F = self._shapes(spectra, out)
+        if F is None:
+            raise ValueError("spectra must be (%d, F, %d)" % (self.channels, self.M))
+        check(self._get("analyze", spectra.ctypes.data, out.ctypes.data, F), "Pvoc.analyze")
+        return out
+
+    def synthesize(self, frames):
+        """host: float32 (channels, F, size/2 + 1, 2) (or (F, size/2 + 1, 2)) -> complex64 (.., F, size/2)"""
+        frames, F, _, out = self._host_prep(frames, tail=(self.M,), dtype=np.complex64)
+        check(self._get("synthesize", frames.ctypes.data, out.ctypes.data, F), "Pvoc.synthesize")
+        return out
+
+    # ---- frames -> frames: pitch scale, frequency shift, timed read (stateless; clfft_amd.h) ----
+
+    def ops_kernel_name(self, op, keepform=False):
+        """op "scale", "shift" or "read" -> "k_pvoc_map" / "k_pvoc_formant" (keepform) / "k_pvoc_read" ("" for a failed object)"""
+        return self._text("ops_kernel_name", {"scale": 0, "shift": 1, "read": 2}.get(op, -1), int(bool(keepform)))
+
+    def scale_device(self, frames_in, frames_out, scale, keepform=False, gain=1.0, coefs=80, stream=None):
+        """pitch scale (Csound's pvscale): torch frames (channels, F, size/2 + 1, 2) float32 -> frames_out of the same
+        shape; scale: a number or a float32 device tensor (F,), each in [0.25, 4]; keepform: the formants (the
+        cepstral envelope of `coefs` coefficients) stay where they are.  Asynchronous on `stream`."""
+        prep = self._device_prep(self._device_frames(frames_in, frames_out), frames_out.device, (scale,))
+        if prep is None:
+            return CL_INVALID_VALUE
+        F, (par,), _ = prep
+        return self._get("scale_dev", frames_in.data_ptr(), frames_out.data_ptr(), F, par, int(bool(keepform)),
+                         float(gain), int(coefs), _stream_of(frames_out, stream))
+
+    def shift_device(self, frames_in, frames_out, shift, lowest_bin=1, keepform=False, gain=1.0, coefs=80, stream=None):
+        """frequency shift (Csound's pvshift): the bins from lowest_bin up move by shift Hz (a number or a float32
+        device tensor (F,)), rounded to whole bins; the bins below are copied"""
+        prep = self._device_prep(self._device_frames(frames_in, frames_out), frames_out.device, (shift,))
+        if prep is None:
+            return CL_INVALID_VALUE
+        F, (par,), _ = prep
+        return self._get("shift_dev", frames_in.data_ptr(), frames_out.data_ptr(), F, par, int(lowest_bin),
+                         int(bool(keepform)), float(gain), int(coefs), _stream_of(frames_out, stream))
+
+    def read_device(self, frames_in, pos, frames_out, stream=None):
+        """timed read (Csound's pvsbufread): frames_out[:, g] = frames_in read at the position pos[g] in frames (float32
+        device tensor (Fout,)), clamped to the ends and interpolated linearly between neighbouring frames"""
+        Fin = self._device_frames(frames_in)
+        prep = None if Fin is None else self._device_prep(self._device_frames(frames_out), frames_out.device, (pos,))
+        if prep is None or not hasattr(pos, "data_ptr"):
+            return CL_INVALID_VALUE
+        Fout, (par,), _ = prep
+        return self._get("read_dev", frames_in.data_ptr(), Fin, par, frames_out.data_ptr(), Fout,
+                         _stream_of(frames_out, stream))
+
+    def scale(self, frames, scale, keepform=False, gain=1.0, coefs=80):
+        """host form of scale_device, blocking: returns the new frames; a value of `scale` outside [0.25, 4] raises
+        ClError(CL_INVALID_VALUE)"""
+        frames, F, (par,), out = self._host_prep(frames, (scale,))
+        check(self._get("scale", frames.ctypes.data, out.ctypes.data, F, par.ctypes.data, int(bool(keepform)), float(gain),
+                        int(coefs)), "Pvoc.scale")
+        return out
+
+    def shift(self, frames, shift, lowest_bin=1, keepform=False, gain=1.0, coefs=80):
+        """host form of shift_device, blocking"""
+        frames, F, (par,), out = self._host_prep(frames, (shift,))
+        check(self._get("shift", frames.ctypes.data, out.ctypes.data, F, par.ctypes.data, int(lowest_bin),
+                        int(bool(keepform)), float(gain), int(coefs)), "Pvoc.shift")
+        return out
+
+    def read(self, frames, pos):
+        """host form of read_device, blocking: pos float32 (Fout,) -> frames (.., Fout, size/2 + 1, 2)"""
+        pos = np.ascontiguousarray(pos, dtype=np.float32).reshape(-1)
+        frames, Fin, (par,), out = self._host_prep(frames, (pos,), rows=pos.size)
+        check(self._get("read", frames.ctypes.data, Fin, par.ctypes.data, out.ctypes.data, pos.size), "Pvoc.read")
+        return out
+
+    # ---- two streams of frames -> frames: cross, morph, filter, mix, vocode (stateless; clfft_amd.h) ----
+
+    _PAIR_OPS = {"cross": 0, "morph": 1, "filter": 2, "mix": 3, "vocode": 4}
+
+    def pair_kernel_name(self, op):
+        """op "cross", "morph", "filter", "mix" (or 0..3) -> "k_pvoc_pair", "vocode" (4) -> "k_pvoc_vocode" ("" for a failed
+        object or an unknown op)"""
+        return self._text("pair_kernel_name", self._op_code(self._PAIR_OPS, op))
+
+    def _pair_device(self, op, a, b, out, p, q, coefs, stream):
+        """one two-input device call; p, q: numbers or float32 device tensors (F,), None for mix"""
+        prep = self._device_prep(self._device_frames(out, a, b), out.device, (p, q))
+        if prep is None:
+            return CL_INVALID_VALUE
+        F, (p, q), _ = prep
+        return self._get("pair_dev", op, a.data_ptr(), b.data_ptr(), out.data_ptr(), F, p, q, int(coefs),
+                         _stream_of(out, stream))
+
+    def cross_device(self, a, b, out, amp_a=1.0, amp_b=1.0, stream=None):
+        """cross-synthesis (Csound's pvscross): torch frames a, b (channels, F, size/2 + 1, 2) float32 -> out of the same
+        shape with amp = a.amp amp_a + b.amp amp_b and the freqs of a; amp_a, amp_b: numbers or float32 device tensors
+        (F,).  out may overlap neither input; a and b may be the same tensor.  Asynchronous on `stream`."""
+        return self._pair_device(0, a, b, out, amp_a, amp_b, 1, stream)
+
+    def morph_device(self, a, b, out, amp=0.5, freq=0.5, stream=None):
+        """morph (Csound's pvsmorph): amps and freqs interpolated from a (weight 0) to b (weight 1); amp, freq: the two
+        weights, numbers or float32 device tensors (F,), clamped to [0, 1]"""
+        return self._pair_device(1, a, b, out, amp, freq, 1, stream)
+
+    def filter_device(self, a, b, out, depth=1.0, gain=1.0, stream=None):
+        """spectral filter (Csound's pvsfilter): the amps of a times (1 - depth) + depth b.amp, times gain; the freqs of a"""
+        return self._pair_device(2, a, b, out, depth, gain, 1, stream)
+
+    def mix_device(self, a, b, out, stream=None):
+        """spectral maximum (Csound's pvsmix): per bin the (amp, freq) pair of the input with the larger amp"""
+        return self._pair_device(3, a, b, out, None, None, 1, stream)
+
+    def vocode_device(self, a, b, out, depth=1.0, gain=1.0, coefs=80, stream=None):
+        """channel vocoder (Csound's pvsvoc): the excitation b takes the formants of a — its amps are multiplied by
+        (1 - depth) + depth envA / envB, the cepstral envelopes of `coefs` coefficients, and by gain; the freqs of b"""
+        return self._pair_device(4, a, b, out, depth, gain, coefs, stream)
+
+    def _pair_host(self, op, a, b, p, q, coefs, what):
+        (a, F), (b, Fb) = self._host_frames(a), self._host_frames(b)
+        if Fb != F or a.shape != b.shape:
+            raise ValueError("a and b must have the same shape")
+        a, F, (p, q), out = self._host_prep(a, (p, q))
+        check(self._get("pair", op, a.ctypes.data, b.ctypes.data, out.ctypes.data, F, _data(p), _data(q), int(coefs)), what)
+        return out
+
+    def cross(self, a, b, amp_a=1.0, amp_b=1.0):
+        """host form of cross_device, blocking: returns the new frames"""
+        return self._pair_host(0, a, b, amp_a, amp_b, 1, "Pvoc.cross")
+
+    def morph(self, a, b, amp=0.5, freq=0.5):
+        """host form of morph_device, blocking; a weight outside [0, 1] raises ClError(CL_INVALID_VALUE)"""
+        return self._pair_host(1, a, b, amp, freq, 1, "Pvoc.morph")
+
+    def filter(self, a, b, depth=1.0, gain=1.0):
+        """host form of filter_device, blocking; a depth outside [0, 1] raises ClError(CL_INVALID_VALUE)"""
+        return self._pair_host(2, a, b, depth, gain, 1, "Pvoc.filter")
+
+    def mix(self, a, b):
+        """host form of mix_device, blocking"""
+        return self._pair_host(3, a, b, None, None, 1, "Pvoc.mix")
+
+    def vocode(self, a, b, depth=1.0, gain=1.0, coefs=80):
+        """host form of vocode_device, blocking; a depth outside [0, 1] raises ClError(CL_INVALID_VALUE)"""
+        return self._pair_host(4, a, b, depth, gain, coefs, "Pvoc.vocode")
+
+    # ---- one stream of frames -> frames, along the bins: band, mask, stencil, arp, lock, warp (stateless; clfft_amd.h) ----
+
+    _SHAPE_OPS = {"band": 0, "mask": 1, "stencil": 2, "arp": 3, "lock": 4, "warp": 5}
+
+    def shape_kernel_name(self, op):
+        """op "band", "mask", "stencil", "arp" (or 0..3) -> "k_pvoc_shape", "lock" (4) -> "k_pvoc_lock", "warp" (5) ->
+        "k_pvoc_warp" ("" for a failed object or an unknown op)"""
+        return self._text("shape_kernel_name", self._op_code(self._SHAPE_OPS, op))
+
+    def _shape_device(self, op, frames_in, frames_out, cols, table, flags, lowest_bin, coefs, stream):
+        """one shaping device call; cols: the op's per-frame values (numbers or float32 device tensors (F,)), stacked
+        into the (F, 4) rows the library reads; table: None or a float32 device tensor (size/2 + 1,)"""
+        prep = self._device_prep(self._device_frames(frames_out, frames_in), frames_out.device, cols, columns=4)
+        if prep is None or (table is not None and not (hasattr(table, "data_ptr") and _dense_f32(table, (self.M + 1,)))):
+            return CL_INVALID_VALUE
+        F, (rows,), _ = prep
+        return self._get("shape_dev", op, frames_in.data_ptr(), frames_out.data_ptr(), F, rows,
+                         None if table is None else table.data_ptr(), int(flags), int(lowest_bin), int(coefs),
+                         _stream_of(frames_out, stream))
+
+    def band_device(self, frames_in, frames_out, lowcut, lowfull, highfull, highcut, reject=False, stream=None):
+        """band pass (Csound's pvsbandp; reject: the band reject pvsbandr): torch frames (channels, F, size/2 + 1, 2)
+        float32 -> frames_out of the same shape, the amps times a gain that rises from 0 at lowcut to 1 at lowfull, stays
+        1 up to highfull and falls to 0 at highcut (Hz, against each bin's |freq|; numbers or float32 device tensors
+        (F,)).  frames_out may not overlap frames_in.  Asynchronous on `stream`."""
+        return self._shape_device(0, frames_in, frames_out, (lowcut, lowfull, highfull, highcut), None,
+                                  int(bool(reject)), 1, 1, stream)
+
+    def mask_device(self, frames_in, frames_out, table, depth=1.0, stream=None):
+        """table mask (Csound's pvsmaska): the amps times (1 - depth) + depth table[k]; table: float32 device tensor
+        (size/2 + 1,), depth clamped to [0, 1]"""
+        return self._shape_device(1, frames_in, frames_out, (depth,), table, 0, 1, 1, stream)
+
+    def stencil_device(self, frames_in, frames_out, table, gain=0.0, level=1.0, stream=None):
+        """stencil (Csound's pvstencil): the amps below table[k] level are multiplied by gain, the others kept"""
+        return self._shape_device(2, frames_in, frames_out, (gain, level), table, 0, 1, 1, stream)
+
+    def arp_device(self, frames_in, frames_out, pos, depth=1.0, gain=1.0, stream=None):
+        """spectral arpeggiator (Csound's pvsarp): the bin at pos (0..1 of the bins 0..size/2) is multiplied by gain,
+        every other bin by 1 - depth"""
+        return self._shape_device(3, frames_in, frames_out, (pos, depth, gain), None, 0, 1, 1, stream)
+
+    def lock_device(self, frames_in, frames_out, lock=1.0, tol=0.01, stream=None):
+        """peak frequency lock (Csound's pvslock): in a frame with lock != 0, the bins next to a spectral peak take the
+        peak's freq where theirs lies within tol |freq| of it"""
+        return self._shape_device(4, frames_in, frames_out, (lock, tol), None, 0, 1, 1, stream)
+
+    def warp_device(self, frames_in, frames_out, scale, shift=0.0, lowest_bin=1, gain=1.0, coefs=80, stream=None):
+        """envelope warp (Csound's pvswarp): the spectral envelope (cepstral, `coefs` coefficients) of the bins from
+        lowest_bin up is scaled by `scale` (in [0.25, 4]) and shifted by `shift` Hz, the partials stay where they are"""
+        return self._shape_device(5, frames_in, frames_out, (scale, shift, gain), None, 0, lowest_bin, coefs, stream)
+
+    def _shape_host(self, op, frames, cols, table, flags, lowest_bin, coefs, what):
+        frames, F, cols, out = self._host_prep(frames, cols)
+        rows = np.zeros((F, 4), np.float32)
+        rows[:, :len(cols)] = np.stack(cols, axis=1)
+        if table is not None:
+            table = np.ascontiguousarray(table, dtype=np.float32)
+            if table.shape != (self.M + 1,):
+                raise ValueError("table must be (%d,)" % (self.M + 1))
+        check(self._get("shape", op, frames.ctypes.data, out.ctypes.data, F, rows.ctypes.data, _data(table), int(flags),
+                        int(lowest_bin), int(coefs)), what)
+        return out
+
+    def band(self, frames, lowcut, lowfull, highfull, highcut, reject=False):
+        """host form of band_device, blocking: returns the new frames; edges that are not finite or not in the order
+        0 <= lowcut <= lowfull <= highfull <= highcut raise ClError(CL_INVALID_VALUE)"""
+        return self._shape_host(0, frames, (lowcut, lowfull, highfull, highcut), None, int(bool(reject)), 1, 1, "Pvoc.band")
+
+    def mask(self, frames, table, depth=1.0):
+        """host form of mask_device, blocking; a depth outside [0, 1] raises ClError(CL_INVALID_VALUE)"""
+        return self._shape_host(1, frames, (depth,), table, 0, 1, 1, "Pvoc.mask")
+
+    def stencil(self, frames, table, gain=0.0, level=1.0):
+        """host form of stencil_device, blocking"""
+        return self._shape_host(2, frames, (gain, level), table, 0, 1, 1, "Pvoc.stencil")
+
+    def arp(self, frames, pos, depth=1.0, gain=1.0):
+        """host form of arp_device, blocking; a pos or depth outside [0, 1] raises ClError(CL_INVALID_VALUE)"""
+        return self._shape_host(3, frames, (pos, depth, gain), None, 0, 1, 1, "Pvoc.arp")
+
+    def lock(self, frames, lock=1.0, tol=0.01):
+        """host form of lock_device, blocking; a negative tol raises ClError(CL_INVALID_VALUE)"""
+        return self._shape_host(4, frames, (lock, tol), None, 0, 1, 1, "Pvoc.lock")
+
+    def warp(self, frames, scale, shift=0.0, lowest_bin=1, gain=1.0, coefs=80):
+        """host form of warp_device, blocking; a scale outside [0.25, 4] raises ClError(CL_INVALID_VALUE)"""
+        return self._shape_host(5, frames, (scale, shift, gain), None, 0, lowest_bin, coefs, "Pvoc.warp")
+
+    # ---- frames -> frames along the stream: blur, smooth, freeze (a carried state each; clfft_amd.h) ----
+
+    _TIME_OPS = {"blur": 0, "smooth": 1, "freeze": 2}
+
+    def time_kernel_name(self, op):
+        """op "blur", "smooth", "freeze" (or 0..2) -> "k_pvoc_blur", "k_pvoc_smooth", "k_pvoc_freeze" ("" for a failed
+        object or an unknown op)"""
+        return self._text("time_kernel_name", self._op_code(self._TIME_OPS, op))
+
+    def time_state_bytes(self):
+        """device memory of the three carried states, the blur's spare included"""
+        return self._get("time_state_bytes")
+
+    def blur_setup(self, max_frames):
+        """allocates and resets the blur's history for windows of up to max_frames (1..4096) frames (blocking)"""
+        return self._get("blur_setup", int(max_frames))
+
+    def blur_max_frames(self):
+        """max_frames of the last blur_setup, 0 before"""
+        return self._get("blur_max_frames")
+
+    def time_state(self, op):
+        """the carried state of op "blur", "smooth" or "freeze" (blocking), float32: the blur's history (channels,
+        max_frames - 1, size/2 + 1, 2), oldest frame first; the smoothing's y and the freeze's held (channels, size/2 + 1, 2)"""
+        code = self._op_code(self._TIME_OPS, op)
+        shape = (self.channels, max(self.blur_max_frames() - 1, 0)) if code == 0 else (self.channels,)
+        out = np.zeros(shape + (self.M + 1, 2), np.float32)
+        check(self._get("time_read_state", code, out.ctypes.data), "Pvoc.time_state")
+        return out
+
+    def _time_device(self, op, frames_in, frames_out, p, q, stream):
+        """one device call along the frames; p, q: numbers or float32 device tensors (F,), q None for blur"""
+        prep = self._device_prep(self._device_frames(frames_out, frames_in), frames_out.device, (p, q))
+        if prep is None:
+            return CL_INVALID_VALUE
+        F, (p, q), _ = prep
+        return self._get("time_dev", op, frames_in.data_ptr(), frames_out.data_ptr(), F, p, q,
+                         _stream_of(frames_out, stream))
+
+    def blur_device(self, frames_in, frames_out, length, stream=None):
+        """moving average along the frames (Csound's pvsblur): torch frames (channels, F, size/2 + 1, 2) float32 ->
+        frames_out of the same shape, each frame the mean of the stream's last n frames, n = length (a number or a
+        float32 device tensor (F,)) cut to whole frames, 1..max_frames of blur_setup.  The frames of earlier calls are
+        the object's history.  Asynchronous on `stream`."""
+        return self._time_device(0, frames_in, frames_out, length, None, stream)
+
+    def smooth_device(self, frames_in, frames_out, amp=0.5, freq=0.5, stream=None):
+        """one-pole low-pass along the frames (Csound's pvsmooth): y += w (x - y) per bin, for the amps with the weight
+        `amp`, for the freqs with `freq` (numbers or float32 device tensors (F,), clamped to [0, 1]; smooth_weight maps
+        Csound's cutoff to a weight).  y is carried from call to call."""
+        return self._time_device(1, frames_in, frames_out, amp, freq, stream)
+
+    def freeze_device(self, frames_in, frames_out, amp=0.0, freq=0.0, stream=None):
+        """freeze (Csound's pvsfreeze): where amp (freq) is not 0 in a frame, the amps (freqs) of the last frame of the
+        stream where it was 0 are held; numbers or float32 device tensors (F,)"""
+        return self._time_device(2, frames_in, frames_out, amp, freq, stream)
+
+    def _time_host(self, op, frames, p, q, what):
+        frames, F, (p, q), out = self._host_prep(frames, (p, q))
+        check(self._get("time", op, frames.ctypes.data, out.ctypes.data, F, p.ctypes.data, _data(q)), what)
+        return out
+
+    def blur(self, frames, length):
+        """host form of blur_device, blocking: returns the new frames; a length outside 1..max_frames raises
+        ClError(CL_INVALID_VALUE)"""
+        return self._time_host(0, frames, length, None, "Pvoc.blur")
+
+    def smooth(self, frames, amp=0.5, freq=0.5):
+        """host form of smooth_device, blocking; a weight outside [0, 1] raises ClError(CL_INVALID_VALUE)"""
+        return self._time_host(1, frames, amp, freq, "Pvoc.smooth")
+
+    def freeze(self, frames, amp=0.0, freq=0.0):
+        """host form of freeze_device, blocking"""
+        return self._time_host(2, frames, amp, freq, "Pvoc.freeze")
+
+    @staticmethod
+    def smooth_weight(cutoff):
+        """Csound's pvsmooth cutoff (a fraction of half the frame rate) as the weight of smooth, in float64:
+        g = 2 - cos(pi cutoff), c = 1 + sqrt(g g - 1) - g"""
+        g = 2.0 - np.cos(np.pi * float(cutoff))
+        return float(1.0 + np.sqrt(g * g - 1.0) - g)
+
+    # ---- frames -> eight descriptors per frame (Csound's pvscent and kin; a state of its own; clfft_amd.h) ----
+
+    DESC_MAG, DESC_POW, DESC_MOM, DESC_CENT, DESC_FLUX, DESC_PEAK_AMP, DESC_PEAK_FREQ, DESC_PEAK_BIN = range(8)
+
+    def desc_kernel_name(self):
+        """ "k_pvoc_desc" ("" for a failed object)"""
+        return self._text("desc_kernel_name")
+
+    def desc_state_bytes(self):
+        """device memory of the descriptors' carried state"""
+        return self._get("desc_state_bytes")
+
+    def desc_state(self):
+        """the descriptors' carried state (blocking): float32 (channels, size/2 + 1), the amps of the stream's last frame"""
+        out = np.zeros((self.channels, self.M + 1), np.float32)
+        check(self._get("desc_read_state", out.ctypes.data), "Pvoc.desc_state")
+        return out
+
+    def describe_device(self, frames_in, out, first_bin=0, nbins=None, rectify=False, stream=None):
+        """torch: frames (channels, F, size/2 + 1, 2) float32, contiguous -> out (channels, F, 8) float32, contiguous
+        ((F, 8) for one channel): per frame the columns DESC_MAG (sum of the amps), DESC_POW (of their squares), DESC_MOM
+        (of amp times bin centre), DESC_CENT (MOM / MAG, Csound's pvscent), DESC_FLUX (the sum of the squared amp
+        differences to the stream's previous frame; rectify: rises only), DESC_PEAK_AMP, DESC_PEAK_FREQ and DESC_PEAK_BIN,
+        over the bins first_bin .. first_bin + nbins - 1 (default: up to size/2).  The sums are a fixed tree of float32
+        additions: the same bits on every call.  The last frame's amps are carried to the next call.  Asynchronous on
+        `stream`."""
+        F = self._device_frames(frames_in)
+        if F is None or self._full(out.shape, 3) != (self.channels, F, 8) or not _dense_f32(out, out.shape):
+            return CL_INVALID_VALUE
+        first_bin, nbins, _ = self._selection(first_bin, nbins, 1)
+        return self._get("desc_dev", frames_in.data_ptr(), out.data_ptr(), F, first_bin, nbins, int(bool(rectify)),
+                         _stream_of(out, stream))
+
+    def describe(self, frames, first_bin=0, nbins=None, rectify=False):
+        """host form of describe_device, blocking: float32 (channels, F, size/2 + 1, 2) (or (F, size/2 + 1, 2)) -> float32
+        (.., F, 8)"""
+        frames, F, _, out = self._host_prep(frames, tail=(8,))
+        first_bin, nbins, _ = self._selection(first_bin, nbins, 1)
+        check(self._get("desc", frames.ctypes.data, out.ctypes.data, F, first_bin, nbins, int(bool(rectify))), "Pvoc.describe")
+        return out
+
+    # ---- frames -> frames: the N loudest bins of every frame (Csound's pvstrace; stateless; clfft_amd.h) ----
+
+    TRACE_RESIDUAL = 1
+
+    def trace_kernel_name(self):
+        """ "k_pvoc_trace" ("" for a failed object)"""
+        return self._text("trace_kernel_name")
+
+    def trace_device(self, frames_in, frames_out, n, first_bin=0, nbins=None, residual=False, bins_out=None, stream=None):
+        """torch: frames (channels, F, size/2 + 1, 2) float32, contiguous -> frames_out of the same shape: of the bins
+        first_bin .. first_bin + nbins - 1 (default: up to size/2) of every frame the floor(n) loudest keep their amp and the
+        others get +0; residual: the other way round.  Equal amps: the lower bin is the louder one, so exactly floor(n) bins
+        are selected (Csound's pvstrace keeps all ties); a NaN amp is never selected.  n: a number or a float32 device tensor
+        (F,), shared by the channels.  bins_out: an int32 device tensor (channels, F, L), contiguous ((F, L) for one
+        channel), that takes the selected bins in ascending order, the first L of them, then -1.  Asynchronous on `stream`."""
+        prep = self._device_prep(self._device_frames(frames_in, frames_out), frames_out.device, (n,))
+        if prep is None:
+            return CL_INVALID_VALUE
+        (F, (n,), _), bins, L = prep, None, 0
+        if bins_out is not None:
+            b = self._full(bins_out.shape, 3)
+            if (len(b) != 3 or b[:2] != (self.channels, F) or b[2] < 1 or str(bins_out.dtype) != "torch.int32"
+                    or not bins_out.is_contiguous() or bins_out.device != frames_out.device):
+                return CL_INVALID_VALUE
+            bins, L = bins_out.data_ptr(), b[2]
+        first_bin, nbins, _ = self._selection(first_bin, nbins, 1)
+        return self._get("trace_dev", frames_in.data_ptr(), frames_out.data_ptr(), n, bins, L, F, first_bin, nbins,
+                         self.TRACE_RESIDUAL if residual else 0, _stream_of(frames_out, stream))
+
+    def trace(self, frames, n, first_bin=0, nbins=None, residual=False, list_n=0):
+        """host form of trace_device, blocking: float32 (channels, F, size/2 + 1, 2) (or (F, size/2 + 1, 2)) -> the new
+        frames, or (frames, bins) with bins int32 (.., F, list_n) when list_n > 0"""
+        frames, F, (n,), out = self._host_prep(frames, (n,))
+        list_n = int(list_n)
+        bins = np.full(frames.shape[:-2] + (list_n,), -1, np.int32) if list_n > 0 else None
+        first_bin, nbins, _ = self._selection(first_bin, nbins, 1)
+        check(self._get("trace", frames.ctypes.data, out.ctypes.data, n.ctypes.data, _data(bins), list_n, F, first_bin, nbins,
+                        self.TRACE_RESIDUAL if residual else 0), "Pvoc.trace")
+        return out if bins is None else (out, bins)
+
+    # ---- frames -> samples: the oscillator bank (Csound's pvsadsyn; a state of its own; clfft_amd.h) ----
+
+    def adsyn_kernel_name(self):
+        """ "k_adsyn_osc" ("" for a failed object)"""
+        return self._text("adsyn_kernel_name")
+
+    def adsyn_workspace_bytes(self):
+        return self._get("adsyn_workspace_bytes")
+
+    def adsyn_tile_bins(self):
+        """oscillators per LDS tile of k_adsyn_osc (fixed)"""
+        return self._fn("adsyn_tile_bins")()
+
+    def adsyn_state(self):
+        """the oscillator bank's state (blocking): (P uint64 in 2^-64 turn, W int32 in 2^-32 turn per sample, A float32),
+        each (channels, size/2 + 1)"""
+        shape = (self.channels, self.M + 1)
+        P, W, A = np.zeros(shape, np.uint64), np.zeros(shape, np.int32), np.zeros(shape, np.float32)
+        check(self._get("adsyn_read_state", P.ctypes.data, W.ctypes.data, A.ctypes.data), "Pvoc.adsyn_state")
+        return P, W, A
+
+    def adsyn_device(self, frames, out, fmod=None, first_bin=0, nbins=None, step=1, gain=1.0, stream=None):
+        """torch: frames (channels, F, size/2 + 1, 2) float32, contiguous -> out (channels, n >= F * hop) float32 with
+        contiguous rows (one row for one channel): frame f yields the samples [f hop, (f + 1) hop), summed over the
+        oscillators of the bins first_bin + i * step, i < nbins (default: all that fit), times gain.  fmod: a frequency
+        multiplier, a number or a float32 device tensor (F,); None: none.  Asynchronous on `stream`."""
+        F = self._device_frames(frames)
+        if F is None or not _is_f32(out):
+            return CL_INVALID_VALUE
+        p, rows, n, stride = _row_view(out, "out")
+        prep = None if rows != self.channels or n < F * self.hop else self._device_prep(F, out.device, (fmod,))
+        if prep is None:
+            return CL_INVALID_VALUE
+        (fmod,) = prep[1]
+        first_bin, nbins, step = self._selection(first_bin, nbins, step)
+        return self._get("adsyn_dev", frames.data_ptr(), F, fmod, first_bin, nbins, step, float(gain), p,
+                         stride if rows > 1 else n, _stream_of(out, stream))
+
+    def adsyn(self, frames, fmod=None, first_bin=0, nbins=None, step=1, gain=1.0):
+        """host form of adsyn_device, blocking: float32 (channels, F, size/2 + 1, 2) (or (F, size/2 + 1, 2)) -> float32
+        (.., F * hop)"""
+        frames, F, (fmod,), out = self._host_prep(frames, (fmod,), tail=(self.hop,))
+        out = out.reshape(out.shape[:-2] + (F * self.hop,))
+        first_bin, nbins, step = self._selection(first_bin, nbins, step)
+        check(self._get("adsyn", frames.ctypes.data, F, _data(fmod), first_bin, nbins, step, float(gain), out.ctypes.data,
+                        F * self.hop), "Pvoc.adsyn")
+        return out

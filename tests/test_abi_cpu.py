@@ -32,6 +32,70 @@ def test_header_symbols_all_exported():
     assert bound == set(names), (bound ^ set(names))
 
 
+def _prototypes():
+    """{name: (return kind, [argument kinds])} of every CLFA_API prototype, comments stripped, over any number of lines"""
+    src = open(os.path.join(ROOT, "include", "clfft_amd.h")).read()
+    src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
+    src = re.sub(r"//[^\n]*", " ", src)
+
+    def kind(decl, named):
+        if "*" in decl:
+            return "pointer"
+        words = [w for w in decl.split() if w != "const"]
+        return " ".join(words[:-1] if named and len(words) > 1 else words)
+
+    out = {}
+    for ret, name, args in re.findall(r"CLFA_API\s+([^;()]*?)\b(clfa_\w+)\s*\(([^;()]*)\)\s*;", src):
+        assert name not in out, "%s is declared twice" % name
+        args = [] if args.strip() in ("", "void") else args.split(",")
+        out[name] = (kind(ret, False), [kind(a, True) for a in args])
+    return out
+
+
+_KINDS = {ctypes.c_int: "int", ctypes.c_long: "long", ctypes.c_size_t: "size_t", ctypes.c_float: "float",
+          ctypes.c_double: "double", None: "void"}
+
+
+def _ctype_kind(t):
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or (isinstance(t, type) and issubclass(t, ctypes._Pointer)):
+        return "pointer"
+    return _KINDS.get(t, repr(t))
+
+
+def _type_mismatches(protos, symbols):
+    """what the rows (name, restype, argtypes) bind differently from the prototypes, one line each"""
+    bad = []
+    for name, res, args in symbols:
+        ret, kinds = protos[name]
+        if _ctype_kind(res) != ret:
+            bad.append("%s returns %s, bound as %s" % (name, ret, _ctype_kind(res)))
+        if len(args) != len(kinds):
+            bad.append("%s takes %d arguments, bound with %d" % (name, len(kinds), len(args)))
+            continue
+        bad += ["%s argument %d is %s, bound as %s" % (name, i, k, _ctype_kind(a))
+                for i, (k, a) in enumerate(zip(kinds, args)) if _ctype_kind(a) != k]
+    return bad
+
+
+def test_bound_types_match_the_header():
+    """_lib.SYMBOLS against the prototypes: return type, argument count and every argument's kind (int, long, size_t,
+    float, double, or a pointer of any sort) — a long bound as c_int loads and runs and truncates"""
+    protos = _prototypes()
+    assert len(protos) == len(_declared()), set(_declared()) ^ set(protos)
+    known = set(_KINDS.values()) | {"pointer"}
+    for name, (ret, kinds) in protos.items():
+        assert ret in known - {"float", "double"} and set(kinds) <= known - {"void"}, (name, ret, kinds)
+    assert _type_mismatches(protos, _lib.SYMBOLS) == []
+    # the check sees a narrowed argument: one row with its first c_long bound as c_int
+    name, res, args = next(s for s in _lib.SYMBOLS if ctypes.c_long in s[2])
+    i = args.index(ctypes.c_long)
+    mutant = (name, res, args[:i] + [ctypes.c_int] + args[i + 1:])
+    assert _type_mismatches(protos, [mutant]) == ["%s argument %d is long, bound as int" % (name, i)]
+    assert _type_mismatches(protos, [(name, ctypes.c_long, args)]) == ["%s returns int, bound as long" % name]
+    assert _type_mismatches(protos, [(name, res, args[:-1])]) == [
+        "%s takes %d arguments, bound with %d" % (name, len(args), len(args) - 1)]
+
+
 def test_no_oracle_or_cpu_fallback_linked():
     """the product library must not contain the oracle"""
     out = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()

@@ -1,4 +1,4 @@
-"""The argument contracts of the Python layer (opencl_fft_amd/__init__.py) as a table: each row is a call on the smallest
+"""The argument contracts of the Python layer (opencl_fft_amd/conv.py) as a table: each row is a call on the smallest
 object that reaches a branch and its outcome — a status code, ValueError with its message, or success with the output
 compared (with the oracle, or bit for bit with another call).  The table records what the layer does, so that a change
 of its plumbing (shared helpers, base classes) is checked row by row against the behaviour it had.
