@@ -1,16 +1,13 @@
 // conv_host.cpp — C ABI of the convolutions (see include/clfft_amd.h): Clpconv and its multi-block route, Cldconv, and
-// the convolution matrix.  Shared plumbing: host.hpp.
+// the convolution matrix.  Shared plumbing: host.hpp, where the staged blocking form lives (staged_call); the rules of a
+// call's arrays: overlap.hpp.  Every object stages its blocking calls in members in1, in2, out and its responses in ir.
 #include "host.hpp"
 
 using namespace clfa;
 
 namespace {
 
-// device staging of the blocking host entry points
-struct Staging {
-  DevBuf in1, in2, out;
-};
-// ... and for single blocks their zero-copy counterparts (mapped pinned host memory)
+// zero-copy staging of single blocks (mapped pinned host memory)
 struct ZeroCopy {
   HostBuf in1, in2, out;
 };
@@ -22,34 +19,31 @@ constexpr size_t kZeroCopyMaxConv = (size_t)256 << 10;   // the convolutions' bl
 // Cldconv only for blocks of up to 4096 samples: every workgroup whose ring window meets the new block reads it from there
 constexpr size_t kZeroCopyMaxDconv = (size_t)16 << 10;
 
-// A blocking host call through device staging: the inputs (ibytes each; in2 may be NULL) copied in, run(out, in1, in2)
-// enqueued on s, obytes of output copied back, one synchronisation
-template <class Run>
-int staged_call(Staging &st, hipStream_t s, void *out, size_t obytes, const void *in1, const void *in2, size_t ibytes,
-                Run run) {
-  int e;
-  if ((e = st.in1.ensure(ibytes)) || (e = st.out.ensure(obytes)) || (in2 && (e = st.in2.ensure(ibytes)))) return e;
-  HIP_TRY(hipMemcpyAsync(st.in1.p, in1, ibytes, hipMemcpyHostToDevice, s));
-  if (in2) HIP_TRY(hipMemcpyAsync(st.in2.p, in2, ibytes, hipMemcpyHostToDevice, s));
-  if ((e = run(st.out.p, st.in1.p, in2 ? st.in2.p : nullptr))) return e;
-  HIP_TRY(hipMemcpyAsync(out, st.out.p, obytes, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));   // blocking read, cl_conv.cpp:455
-  return CLFA_SUCCESS;
+// The arrays of a blocking call of object T, packed, in the order their staging is ensured: in1, out, in2 (ibytes per
+// input, a NULL in2 is not used; obytes of output) ...
+template <class T>
+HostArrays<T, 3> conv_arrays(void *out, size_t obytes, const void *in1, const void *in2, size_t ibytes) {
+  return {{{in1, ibytes, 4, false, &T::in1}, {out, obytes, 4, true, &T::out}, {in2, ibytes, 4, false, &T::in2, in2 != nullptr}}};
+}
+// ... and the staged form around run(out, in1, in2), its one synchronisation the blocking read of cl_conv.cpp:455
+template <class T, class Run>
+int conv_staged(T *p, const HostArrays<T, 3> &io, Run run) {
+  return staged_call(p, io.a, [&](const void *const *d) { return run(const_cast<void *>(d[1]), d[0], d[2]); });
 }
 
 // A blocking host call of one audio block (blk bytes per input and output): up to zc_max bytes the kernels read the
 // inputs from, and write the output to, mapped pinned host memory — no copy calls, one synchronisation (cl_conv.cpp:399,
-// 455); larger blocks go through staged_call
-template <class Run>
-int block_call(ZeroCopy &z, Staging &st, size_t zc_max, hipStream_t s, float *out, const float *in1, const float *in2,
-               size_t blk, Run run) {
-  if (blk > zc_max) return staged_call(st, s, out, blk, in1, in2, blk, run);
+// 455); larger blocks take the staged form
+template <class T, class Run>
+int block_call(T *p, size_t zc_max, float *out, const float *in1, const float *in2, size_t blk, Run run) {
+  if (blk > zc_max) return conv_staged(p, conv_arrays<T>(out, blk, in1, in2, blk), run);
+  ZeroCopy &z = p->zc;
   int e;
   if ((e = z.in1.ensure(blk)) || (e = z.out.ensure(blk)) || (in2 && (e = z.in2.ensure(blk)))) return e;
   memcpy(z.in1.h, in1, blk);
   if (in2) memcpy(z.in2.h, in2, blk);
   if ((e = run(z.out.d, z.in1.d, in2 ? z.in2.d : nullptr))) return e;
-  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipStreamSynchronize(p->stream));
   memcpy(out, z.out.h, blk);
   return CLFA_SUCCESS;
 }
@@ -70,30 +64,64 @@ int subbatch_cap(long per_block, const char *env_name) {
   return (int)(cap < 1 ? 1 : (cap > 1024 ? 1024 : cap));
 }
 
-// the count checks of a multi-block call: *len = nblocks * pts floats per row, 0 when there is nothing to do
-int blocks_len(long nblocks, long pts, const void *out, const void *in, long *len) {
+// rows of floats in device memory, looked at alone: the shared check's NULL and alignment answers
+bool device_rows_ok(const void *rows) {
+  const CallArray<int> a[] = {{rows, sizeof(float), 4, false, 0}};
+  return arrays_ok(a, true);
+}
+
+// the count check of a multi-block call: *len = nblocks * pts floats per row, 0 when there is nothing to do
+int blocks_len(long nblocks, long pts, long *len) {
   *len = 0;
-  if (nblocks < 0) return CLFA_INVALID_VALUE;
-  if (nblocks == 0) return CLFA_SUCCESS;
-  if (!out || !in || nblocks > 0x7fffffffL / pts) return CLFA_INVALID_VALUE;
+  if (nblocks < 0 || nblocks > 0x7fffffffL / pts) return CLFA_INVALID_VALUE;
   *len = nblocks * pts;
   return CLFA_SUCCESS;
 }
 
-// ... and of a device-resident one: out_rows rows of out and in_rows rows of in1 (and in2), 4-byte aligned, strides of
-// at least *len floats, out overlapping no input row even partly
+// ... and the checks of a device-resident one: out_rows rows of out and in_rows rows of in1 (and in2, where given), there
+// and 4-byte aligned, strides of at least *len floats, out overlapping no input row even partly
 int check_blocks_dev(long nblocks, long pts, const void *out, long out_stride, long out_rows, const void *in1,
                      const void *in2, long in_stride, long in_rows, long *len) {
-  if (int e = blocks_len(nblocks, pts, out, in1, len)) return e;
+  if (int e = blocks_len(nblocks, pts, len)) return e;
   if (!*len) return CLFA_SUCCESS;
+  if (!device_rows_ok(out) || !device_rows_ok(in1) || (in2 && !device_rows_ok(in2))) return CLFA_INVALID_VALUE;
   if (in_stride < *len || out_stride < *len) return CLFA_INVALID_VALUE;
-  auto misaligned = [](const void *q) { return ((uintptr_t)q & 3) != 0; };
-  if (misaligned(out) || misaligned(in1) || (in2 && misaligned(in2))) return CLFA_INVALID_VALUE;
+  // Where the two overlap rules meet: the shared description's rule (arrays_ok) takes a strided array as one span, gaps
+  // included; the multi-block device forms and the matrix promise more — an output row may lie in the gap between two
+  // input rows — so they ask the row-precise rows_overlap instead, and only NULL and alignment of the shared check.
   const long lb = *len * (long)sizeof(float);
   const long osb = out_stride * (long)sizeof(float), isb = in_stride * (long)sizeof(float);
   if (rows_overlap(out, osb, out_rows, in1, isb, in_rows, lb) || (in2 && rows_overlap(out, osb, out_rows, in2, isb, in_rows, lb)))
     return CLFA_INVALID_VALUE;
   return CLFA_SUCCESS;
+}
+
+// what a multi-block call of an object moves: nblocks * pts floats in each row (block_shape(p): behind every object)
+struct BlockShape {
+  long pts, in_rows, out_rows;
+};
+
+// The blocking multi-block forms: the object's error, the count, the arrays (there, and the packed output sharing no byte
+// with a packed input), then the staged form around dev(out, len, in1, in2), the object's device form on packed rows
+template <class T, class Dev>
+int blocks_host(T *p, float *out, const float *in1, const float *in2, long nblocks, Dev dev) {
+  if (int e = obj_error(p)) return e;
+  const BlockShape shape = block_shape(p);
+  long len;
+  if (int e = blocks_len(nblocks, shape.pts, &len)) return e;
+  if (!len) return CLFA_SUCCESS;
+  const HostArrays<T, 3> io = conv_arrays<T>(out, sizeof(float) * len * shape.out_rows, in1, in2, sizeof(float) * len * shape.in_rows);
+  if (!arrays_ok(io.a, false)) return CLFA_INVALID_VALUE;
+  ENTER_DEVICE(p->di.device);
+  return conv_staged(p, io, [&](void *o, const void *i1, const void *i2) { return dev(o, len, i1, i2); });
+}
+
+// The blocking pushes of a response: `bytes` of packed rows staged in the object's ir, then push(rows), the device form on
+// the object's stream, one synchronisation.  The caller has run its refusals and entered the device.
+template <class T, class Push>
+int push_host(T *p, const float *ir, size_t bytes, Push push) {
+  const HostArray<T> rows[] = {{ir, bytes, 4, false, &T::ir}};
+  return staged_call(p, rows, [&](const void *const *d) { return push(d[0]); });
 }
 
 }  // namespace
@@ -111,7 +139,7 @@ struct clfa_pconv {
   hipStream_t stream = nullptr;
   DevBuf half, w2f, w2i;             // tables (cl_conv.cpp:263-287)
   DevBuf ringA, ringB, acc, tail;    // spec1, spec2, in1-as-accumulator, olap tail
-  Staging io;                        // staging for the host entry points
+  DevBuf in1, in2, out;              // staging of the blocking forms (conv_arrays)
   ZeroCopy zc;                       // ... zero-copy staging for small blocks
   DevBuf ir;                         // ... and for push_ir
   DevBuf four, scratch, work;        // partitions above the LDS sizes: large-N tables, scratch, work frames
@@ -126,6 +154,7 @@ struct clfa_pconv {
   DevBuf bX, bXB, bY, btail, bstage; // spectra of the new blocks / second inputs, output spectra, new tail; loop staging
 };
 
+static BlockShape block_shape(const clfa_pconv *p) { return {p->pts, p->g.channels, p->g.channels}; }
 static int pconv_setup(clfa_pconv *p, int device, int cvs, int pts, int channels) {
   p->cvs = cvs;
   p->pts = pts;
@@ -252,13 +281,9 @@ int clfa_pconv_push_ir(clfa_pconv *p, const float *ir) {
   if (int e = obj_error(p)) return e;
   if (!ir) return CLFA_INVALID_VALUE;
   ENTER_DEVICE(p->di.device);
-  const size_t bytes = sizeof(float) * (size_t)p->g.channels * p->g.nparts * p->pts;
-  int e = p->ir.ensure(bytes);
-  if (e) return e;
-  HIP_TRY(hipMemcpyAsync(p->ir.p, ir, bytes, hipMemcpyHostToDevice, p->stream));
-  if ((e = clfa_pconv_push_ir_dev(p, p->ir.p, (long)p->g.nparts * p->pts, p->stream))) return e;
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  return CLFA_SUCCESS;
+  const long len = (long)p->g.nparts * p->pts;
+  return push_host(p, ir, sizeof(float) * (size_t)p->g.channels * len,
+                   [&](const void *rows) { return clfa_pconv_push_ir_dev(p, rows, len, p->stream); });
 }
 
 int clfa_pconv_process_dev(clfa_pconv *p, void *out, const void *in1, const void *in2, void *stream) {
@@ -319,7 +344,7 @@ static int pconv_host(clfa_pconv *p, float *out, const float *in1, const float *
   if (!out || !in1) return CLFA_INVALID_VALUE;
   ENTER_DEVICE(p->di.device);
   // one audio block of a few channels goes zero-copy
-  return block_call(p->zc, p->io, kZeroCopyMaxConv, p->stream, out, in1, in2, sizeof(float) * (size_t)p->g.channels * p->pts,
+  return block_call(p, kZeroCopyMaxConv, out, in1, in2, sizeof(float) * (size_t)p->g.channels * p->pts,
                     [&](void *o, const void *i1, const void *i2) { return clfa_pconv_process_dev(p, o, i1, i2, p->stream); });
 }
 
@@ -407,14 +432,7 @@ int clfa_pconv_process_blocks_dev(clfa_pconv *p, void *out, long out_stride, con
 }
 
 int clfa_pconv_convolution_blocks(clfa_pconv *p, float *out, const float *in1, const float *in2, long nblocks) {
-  if (int e = obj_error(p)) return e;
-  long len;
-  if (int e = blocks_len(nblocks, p->pts, out, in1, &len)) return e;
-  if (!len) return CLFA_SUCCESS;
-  const size_t bytes = sizeof(float) * (size_t)len * p->g.channels;
-  if (spans_overlap(out, bytes, in1, bytes) || (in2 && spans_overlap(out, bytes, in2, bytes))) return CLFA_INVALID_VALUE;
-  ENTER_DEVICE(p->di.device);
-  return staged_call(p->io, p->stream, out, bytes, in1, in2, bytes, [&](void *o, const void *i1, const void *i2) {
+  return blocks_host(p, out, in1, in2, nblocks, [&](void *o, long len, const void *i1, const void *i2) {
     return clfa_pconv_process_blocks_dev(p, o, len, i1, i2, len, nblocks, p->stream);
   });
 }
@@ -431,7 +449,7 @@ struct clfa_dconv {
   int err = 0;
   hipStream_t stream = nullptr;
   DevBuf del, coefs;   // channels rings of irsize + vsize floats each; one wp for all of them
-  Staging io;          // staging of the host entry points' blocks (allocated at creation)
+  DevBuf in1, in2, out;   // staging of the blocking forms (conv_arrays), allocated at creation for one block
   ZeroCopy zc;         // ... zero-copy staging for small blocks (mapped pinned host memory)
   DevBuf part, cnt;    // partial sums per tap chunk and their arrival counter (plan.G > 1)
   DconvPlan plan{64, 1, 1};
@@ -443,6 +461,7 @@ struct clfa_dconv {
   DevBuf ir;               // staging of push_ir (channels > 1)
 };
 
+static BlockShape block_shape(const clfa_dconv *d) { return {d->vsize, d->channels, d->channels}; }
 static int dconv_setup(clfa_dconv *d, int device, int irsize, int vsize, int channels) {
   d->irsize = irsize;
   d->vsize = vsize;
@@ -463,8 +482,8 @@ static int dconv_setup(clfa_dconv *d, int device, int irsize, int vsize, int cha
   if (const char *env = getenv("CLFA_DCONV_BLOCKS_R")) {   // tuning switch, read per object: outputs per lane, 2 or 8
     if (atoi(env) == 2 || atoi(env) == 8) d->bplan.force_r = atoi(env);
   }
-  if ((e = d->del.ensure(ring)) || (e = d->coefs.ensure(ring)) || (e = d->io.out.ensure(blk)) || (e = d->io.in1.ensure(blk)) ||
-      (e = d->io.in2.ensure(blk)) || (e = d->part.ensure(blk * d->plan.G)) ||
+  if ((e = d->del.ensure(ring)) || (e = d->coefs.ensure(ring)) || (e = d->out.ensure(blk)) || (e = d->in1.ensure(blk)) ||
+      (e = d->in2.ensure(blk)) || (e = d->part.ensure(blk * d->plan.G)) ||
       (e = d->cnt.ensure(sizeof(unsigned) * d->plan.VB)))
     return e;
   // the reference leaves these uninitialised (cl_dconv.cpp:87-91); zero is the intent
@@ -492,7 +511,7 @@ static int dconv_host(clfa_dconv *d, float *out, const float *in1, const float *
   ENTER_DEVICE(d->di.device);
   HIP_TRY(d->order.use(d->stream));
   // an audio block goes zero-copy as the partitioned convolution's host path does (kZeroCopyMaxDconv)
-  return block_call(d->zc, d->io, kZeroCopyMaxDconv, d->stream, out, in1, in2, sizeof(float) * (size_t)d->vsize,
+  return block_call(d, kZeroCopyMaxDconv, out, in1, in2, sizeof(float) * (size_t)d->vsize,
                     [&](void *o, const void *i1, const void *i2) {
                       return dconv_block(d, (float *)o, (const float *)i1, (const float *)i2, d->stream);
                     });
@@ -522,7 +541,7 @@ const char *clfa_dconv_blocks_kernel_name(const clfa_dconv *d, int time_varying)
 
 int clfa_dconv_push_ir_dev(clfa_dconv *d, const void *ir, long channel_stride, void *stream) {
   if (int e = obj_error(d)) return e;
-  if (!ir || channel_stride < d->irsize || ((uintptr_t)ir & 3)) return CLFA_INVALID_VALUE;
+  if (!device_rows_ok(ir) || channel_stride < d->irsize) return CLFA_INVALID_VALUE;
   ENTER_DEVICE(d->di.device);
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(d->order.use(s));
@@ -536,17 +555,11 @@ int clfa_dconv_push_ir(clfa_dconv *d, const float *ir) {
   if (int e = obj_error(d)) return e;
   if (!ir) return CLFA_INVALID_VALUE;
   ENTER_DEVICE(d->di.device);
-  if (d->channels > 1) {
-    const size_t bytes = sizeof(float) * (size_t)d->channels * d->irsize;
-    int e = d->ir.ensure(bytes);
-    if (e) return e;
-    HIP_TRY(d->order.use(d->stream));
-    HIP_TRY(hipMemcpyAsync(d->ir.p, ir, bytes, hipMemcpyHostToDevice, d->stream));
-    if ((e = clfa_dconv_push_ir_dev(d, d->ir.p, d->irsize, d->stream))) return e;
-    HIP_TRY(hipStreamSynchronize(d->stream));
-    return CLFA_SUCCESS;
-  }
   HIP_TRY(d->order.use(d->stream));
+  if (d->channels > 1)
+    return push_host(d, ir, sizeof(float) * (size_t)d->channels * d->irsize,
+                     [&](const void *rows) { return clfa_dconv_push_ir_dev(d, rows, d->irsize, d->stream); });
+  // one channel: straight into the coefficient ring
   HIP_TRY(hipMemcpyAsync(d->coefs.p, ir, sizeof(float) * d->irsize, hipMemcpyHostToDevice, d->stream));
   HIP_TRY(hipStreamSynchronize(d->stream));
   return CLFA_SUCCESS;
@@ -605,14 +618,7 @@ int clfa_dconv_process_blocks_dev(clfa_dconv *d, void *out, long out_stride, con
 }
 
 int clfa_dconv_convolution_blocks(clfa_dconv *d, float *out, const float *in1, const float *in2, long nblocks) {
-  if (int e = obj_error(d)) return e;
-  long len;
-  if (int e = blocks_len(nblocks, d->vsize, out, in1, &len)) return e;
-  if (!len) return CLFA_SUCCESS;
-  const size_t bytes = sizeof(float) * (size_t)len * d->channels;
-  if (spans_overlap(out, bytes, in1, bytes) || (in2 && spans_overlap(out, bytes, in2, bytes))) return CLFA_INVALID_VALUE;
-  ENTER_DEVICE(d->di.device);
-  return staged_call(d->io, d->stream, out, bytes, in1, in2, bytes, [&](void *o, const void *i1, const void *i2) {
+  return blocks_host(d, out, in1, in2, nblocks, [&](void *o, long len, const void *i1, const void *i2) {
     return clfa_dconv_process_blocks_dev(d, o, len, i1, i2, len, nblocks, d->stream);
   });
 }
@@ -658,8 +664,8 @@ struct clfa_pconv_matrix {
   DevBuf half, w2f, w2i;         // tables of the pts-bin transforms (as Clpconv)
   DevBuf H, ringA, tail;         // responses, input spectra rings, overlap-add tails
   DevBuf X, Y, P, tail_ws;       // sub-batch workspaces: allocated by the first call that needs them
-  Staging io;                    // staging of the host entry points (one input: io.in2 stays empty)
-  DevBuf hir;                    // ... and of push_ir
+  DevBuf in1, in2, out;          // staging of the blocking forms (conv_arrays; one input: in2 stays empty)
+  DevBuf ir;                     // ... and of the pushes
   PconvMatrixPlan plan;
   int cap = 1;                   // blocks per sub-batch (CLFA_PCONV_MATRIX_BLOCKS_MAX: tuning switch, read at creation)
   StreamOrder order;
@@ -670,6 +676,7 @@ struct clfa_pconv_matrix {
   bool fade_two_mac = false;     // CLFA_PCONV_MATRIX_FADE_MAC=two: two launches of the plain MAC (tuning switch)
 };
 
+static BlockShape block_shape(const clfa_pconv_matrix *p) { return {p->pts, p->inputs, p->outputs}; }
 // the launcher's view of the object (everything but the call's rows, K and w)
 static PconvMatrixArgs mconv_args(const clfa_pconv_matrix *p) {
   PconvMatrixArgs a;
@@ -757,18 +764,12 @@ static int mconv_setup(clfa_pconv_matrix *p, int device, int cvs, int pts, int i
   return CLFA_SUCCESS;
 }
 
-// the blocking host pushes: the rows staged on the object's stream, then the device form `push`
+// the blocking host pushes after their refusals: the outputs x inputs packed rows staged, then the device form `push`
 template <class Push>
 static int mconv_push_host(clfa_pconv_matrix *p, const float *ir, Push push) {
   ENTER_DEVICE(p->di.device);
   const long len = (long)p->nparts * p->pts;
-  const size_t bytes = sizeof(float) * (size_t)len * p->outputs * p->inputs;
-  int e = p->hir.ensure(bytes);
-  if (e) return e;
-  HIP_TRY(hipMemcpyAsync(p->hir.p, ir, bytes, hipMemcpyHostToDevice, p->stream));
-  if ((e = push(p->hir.p, len))) return e;
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  return CLFA_SUCCESS;
+  return push_host(p, ir, sizeof(float) * (size_t)len * p->outputs * p->inputs, [&](const void *rows) { return push(rows, len); });
 }
 
 extern "C" {
@@ -795,7 +796,7 @@ const char *clfa_pconv_matrix_kernel_name(const clfa_pconv_matrix *p) { return !
 int clfa_pconv_matrix_push_ir_dev(clfa_pconv_matrix *p, const void *ir, long row_stride, void *stream) {
   if (int e = obj_error(p)) return e;
   const long len = (long)p->nparts * p->pts;
-  if (!ir || row_stride < len || ((uintptr_t)ir & 3)) return CLFA_INVALID_VALUE;
+  if (!device_rows_ok(ir) || row_stride < len) return CLFA_INVALID_VALUE;
   if (p->fade_len) return CLFA_INVALID_OPERATION;   // a fade is pending: H is one end of it
   ENTER_DEVICE(p->di.device);
   hipStream_t s = (hipStream_t)stream;
@@ -817,7 +818,7 @@ int clfa_pconv_matrix_push_ir(clfa_pconv_matrix *p, const float *ir) {
 int clfa_pconv_matrix_push_ir_fade_dev(clfa_pconv_matrix *p, const void *ir, long row_stride, long fade_blocks, void *stream) {
   if (int e = obj_error(p)) return e;
   const long len = (long)p->nparts * p->pts;
-  if (!ir || row_stride < len || ((uintptr_t)ir & 3) || fade_blocks < 1 || fade_blocks > 0x7fffffffL / p->pts)
+  if (!device_rows_ok(ir) || row_stride < len || fade_blocks < 1 || fade_blocks > 0x7fffffffL / p->pts)
     return CLFA_INVALID_VALUE;
   if (p->fade_len) return CLFA_INVALID_OPERATION;   // one fade at a time
   ENTER_DEVICE(p->di.device);
@@ -900,14 +901,7 @@ int clfa_pconv_matrix_process_dev(clfa_pconv_matrix *p, void *out, long out_stri
 }
 
 int clfa_pconv_matrix_convolution(clfa_pconv_matrix *p, float *out, const float *in, long nblocks) {
-  if (int e = obj_error(p)) return e;
-  long len;
-  if (int e = blocks_len(nblocks, p->pts, out, in, &len)) return e;
-  if (!len) return CLFA_SUCCESS;
-  const size_t ib = sizeof(float) * (size_t)len * p->inputs, ob = sizeof(float) * (size_t)len * p->outputs;
-  if (spans_overlap(out, ob, in, ib)) return CLFA_INVALID_VALUE;
-  ENTER_DEVICE(p->di.device);
-  return staged_call(p->io, p->stream, out, ob, in, nullptr, ib, [&](void *o, const void *i1, const void *) {
+  return blocks_host(p, out, in, nullptr, nblocks, [&](void *o, long len, const void *i1, const void *) {
     return clfa_pconv_matrix_process_dev(p, o, len, i1, len, nblocks, p->stream);
   });
 }

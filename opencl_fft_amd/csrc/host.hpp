@@ -1,7 +1,8 @@
 // host.hpp — plumbing shared by the host side of the C ABI (clfft_amd.cpp: FFT plans, conv_host.cpp: the
 // convolutions, stft_host.cpp: Stft, pvoc_host.cpp: Pvoc): error mapping, device and stream handling, owned device /
-// pinned buffers, numeric switches of the environment, the exact host tables, and the prelude / creation / destruction
-// every object shares.  Everything here is inline and hidden (-fvisibility=hidden): nothing becomes an exported symbol.
+// pinned buffers, numeric switches of the environment, the exact host tables, the prelude / creation / destruction every
+// object shares, and the staged blocking form of a call (staged_call) over the description of its arrays (HostArray; its
+// rules: overlap.hpp).  Everything here is inline and hidden (-fvisibility=hidden): nothing becomes an exported symbol.
 #pragma once
 #include "../../include/clfft_amd.h"
 
@@ -365,6 +366,46 @@ inline int ensure_workspaces(std::initializer_list<Want> want, hipStream_t s) {
     int e = w.b->ensure(w.bytes);
     if (e) return e;
   }
+  return CLFA_SUCCESS;
+}
+
+// One array of a call of the object T (CallArray, overlap.hpp) with where a blocking form stages it: a DevBuf member of
+// T, the rows packed there; HostArrays: the list a function that describes a call's arrays returns
+template <class T>
+using HostArray = CallArray<DevBuf T::*>;
+template <class T, size_t N>
+struct HostArrays {
+  HostArray<T> a[N];
+};
+constexpr size_t kCallArrays = 5;   // at most so many per call
+
+// The blocking form around a device form, on the object's device (the caller has entered it): every array the call looks
+// at has its staging buffer, ensured in the order of the list; the inputs are copied in (strided rows packed), dev(d) runs
+// the device work on the staged arrays d[i] (NULL where the call does not look) and the object's stream, every output is
+// copied out (to the caller's strided rows), and the stream is waited for, once.
+template <class T, size_t N, class Dev>
+inline int staged_call(T *p, const HostArray<T> (&arrays)[N], Dev dev) {
+  static_assert(N <= kCallArrays, "kCallArrays");
+  const void *d[kCallArrays] = {};
+  for (size_t i = 0; i < N; i++) {
+    const HostArray<T> &a = arrays[i];
+    if (int e = a.used ? (p->*a.stage).ensure(a.bytes * a.rows) : 0) return e;
+    if (a.used) d[i] = (p->*a.stage).p;
+  }
+  const auto copy = [&](size_t i) {   // between the caller's rows and the packed staging, the way the array goes
+    const HostArray<T> &a = arrays[i];
+    void *dst = const_cast<void *>(a.out ? a.ptr : d[i]);
+    const void *src = a.out ? d[i] : a.ptr;
+    const hipMemcpyKind kind = a.out ? hipMemcpyDeviceToHost : hipMemcpyHostToDevice;
+    if (!a.pitch) return hipMemcpyAsync(dst, src, a.bytes * a.rows, kind, p->stream);
+    return hipMemcpy2DAsync(dst, a.out ? a.pitch : a.bytes, src, a.out ? a.bytes : a.pitch, a.bytes, a.rows, kind, p->stream);
+  };
+  for (size_t i = 0; i < N; i++)
+    if (d[i] && !arrays[i].out) HIP_TRY(copy(i));
+  if (int e = dev(d)) return e;
+  for (size_t i = 0; i < N; i++)
+    if (d[i] && arrays[i].out) HIP_TRY(copy(i));
+  HIP_TRY(hipStreamSynchronize(p->stream));
   return CLFA_SUCCESS;
 }
 

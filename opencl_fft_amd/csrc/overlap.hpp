@@ -1,9 +1,10 @@
-// overlap.hpp — the aliasing checks of the C ABI's entry points (plain C++: tests/test_overlap_cpu.py builds it with g++).
-//
+// overlap.hpp — the argument rules of the C ABI's arrays (plain C++: tests/test_overlap_cpu.py builds it with g++): the
+// two aliasing predicates, the description of one array of a call, and the check every entry point runs over its arrays.
 // They decide which caller buffers an entry point refuses.  On the one-launch routes that refusal is what keeps the
-// kernels' __restrict__ reads correct, so every entry point uses these two and no copy of its own.
+// kernels' __restrict__ reads correct, so every entry point uses these and no copy of its own.
 #pragma once
 #include <cstddef>
+#include <cstdint>
 
 namespace clfa {
 
@@ -29,6 +30,33 @@ inline bool rows_overlap(const void *a, long sa, long ra, const void *b, long sb
     if (kmin <= kmax) return true;
   }
   return false;
+}
+
+// One array of a call, as the caller passed it: device memory in a device form, host memory in a blocking form.  It is
+// `rows` rows of `bytes` each, `pitch` bytes apart (0: packed).  An array the call does not look at (`used` false) is not
+// examined, not staged, and reaches the launch as NULL.  `stage`: where a blocking form stages it (host.hpp).
+template <class Stage>
+struct CallArray {
+  const void *ptr;
+  size_t bytes;
+  int align;     // what a device form asks of ptr: 8 (frames, spectra, pairs) or 4 (floats)
+  bool out;      // an output of the call; else an input
+  Stage stage;
+  bool used = true;
+  size_t rows = 1, pitch = 0;
+  size_t span() const { return pitch ? (rows - 1) * pitch + bytes : rows * bytes; }   // first byte to last, gaps included
+};
+
+// The arrays' rules: a NULL is refused, so is with device_ptrs a misaligned one, so is an output whose span (a strided
+// array's gaps included) shares a byte with any other array of the call; the inputs may overlap each other.
+template <class A, size_t N>
+inline bool arrays_ok(const A (&arrays)[N], bool device_ptrs) {
+  for (const A &a : arrays)
+    if (a.used && (!a.ptr || (device_ptrs && ((uintptr_t)a.ptr & (uintptr_t)(a.align - 1))))) return false;
+  for (const A &out : arrays)
+    for (const A &a : arrays)
+      if (out.used && out.out && a.used && &a != &out && spans_overlap(a.ptr, a.span(), out.ptr, out.span())) return false;
+  return true;
 }
 
 }  // namespace clfa

@@ -1,7 +1,7 @@
 // pvoc_host.cpp — C ABI of the phase vocoder on the Stft spectra (see include/clfft_amd.h): Pvoc.  Shared plumbing: host.hpp.
-// The object and its states come first; then what every call shares — the description of its arrays (PvocArray), their
-// check, the device form, the staged blocking form, and pvoc_call, which puts a call's results in the header's order —
-// then one function per family of calls with what is its own: scalar rules, array list, per-frame value rule, launch.
+// The object and its states come first; then what every call shares — the description of its arrays (PvocArray: host.hpp's
+// HostArray, checked by arrays_ok, staged by staged_call), the device form, and pvoc_call, which puts a call's results in
+// the header's order — then one function per family of calls: scalar rules, array list, per-frame value rule, launch.
 #include "host.hpp"
 
 using namespace clfa;
@@ -191,33 +191,9 @@ static int pvoc_code(hipError_t e) {
 // One description of a call, checked, staged and handed to the launch from one place
 // ---------------------------------------------------------------------------------
 
-// One array of a call, as the caller passed it: device memory in a device form, host memory in a blocking form.  It is
-// `rows` rows of `bytes` each, `pitch` bytes apart (0: packed).  An array the op does not look at (`used` false: MIX's p
-// and q, BLUR's q, the table of most shaping ops, a NULL fmod) is not examined, not staged, and reaches the launch as NULL.
-struct PvocArray {
-  const void *ptr;
-  size_t bytes;
-  int align;                  // what a device form asks of ptr: 8 (frames, spectra, pairs) or 4 (floats)
-  bool out;                   // an output of the call (one, or trace's two: the frames and the bin list); else an input
-  DevBuf clfa_pvoc::*stage;   // where a blocking form stages it, its rows packed
-  bool used = true;
-  size_t rows = 1, pitch = 0;
-  size_t span() const { return pitch ? (rows - 1) * pitch + bytes : rows * bytes; }   // first byte to last, gaps included
-};
-constexpr size_t kPvocArrays = 5;   // at most so many per call
-
-// The arrays' rules: a NULL is an invalid value, so is with device_ptrs a misaligned one, so is an output that overlaps
-// any other array of the call even partly, an input or another output (the inputs may overlap each other)
-template <size_t N>
-static int pvoc_arrays_check(const PvocArray (&arrays)[N], bool device_ptrs) {
-  for (const PvocArray &a : arrays)
-    if (a.used && (!a.ptr || (device_ptrs && ((uintptr_t)a.ptr & (uintptr_t)(a.align - 1))))) return CLFA_INVALID_VALUE;
-  for (const PvocArray &out : arrays)
-    for (const PvocArray &a : arrays)
-      if (out.used && out.out && a.used && &a != &out && spans_overlap(a.ptr, a.span(), out.ptr, out.span()))
-        return CLFA_INVALID_VALUE;
-  return CLFA_SUCCESS;
-}
+// One array of a call (HostArray, host.hpp; the rules: arrays_ok, overlap.hpp): the outputs are one, or trace's two (the
+// frames and the bin list); what an op does not look at is not `used`: MIX's p and q, BLUR's q, most tables, a NULL fmod
+using PvocArray = HostArray<clfa_pvoc>;
 
 // The device forms after their checks (chk): the error, else the object's own, else a no-op's success, ahead of any device
 // work; then launch(stream) on the object's device, ordered behind the object's earlier work
@@ -228,36 +204,6 @@ static int pvoc_dev_form(clfa_pvoc *p, int chk, void *stream, Launch launch) {
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(p->order.use(s));
   return pvoc_code(launch(s));
-}
-
-// The blocking forms after their checks: every array the op looks at has a staging buffer on the device, ensured in the
-// order of the list; the inputs are copied in, dev(d) runs the device work on the staged arrays d[i] (NULL where the op
-// does not look) and the object's stream, every output is copied out, and the stream is waited for.
-template <size_t N, class Dev>
-static int pvoc_staged(clfa_pvoc *p, const PvocArray (&arrays)[N], Dev dev) {
-  static_assert(N <= kPvocArrays, "kPvocArrays");
-  ENTER_DEVICE(p->di.device);
-  const void *d[kPvocArrays] = {};
-  for (size_t i = 0; i < N; i++) {
-    const PvocArray &a = arrays[i];
-    if (int e = a.used ? (p->*a.stage).ensure(a.bytes * a.rows) : 0) return e;
-    if (a.used) d[i] = (p->*a.stage).p;
-  }
-  for (size_t i = 0; i < N; i++) {
-    const PvocArray &a = arrays[i];
-    if (d[i] && !a.out) HIP_TRY(hipMemcpyAsync(const_cast<void *>(d[i]), a.ptr, a.bytes * a.rows, hipMemcpyHostToDevice, p->stream));
-  }
-  if (int e = dev(d)) return e;
-  for (size_t i = 0; i < N; i++) {
-    const PvocArray &a = arrays[i];
-    void *host = const_cast<void *>(a.ptr);
-    if (d[i] && a.out && a.pitch)
-      HIP_TRY(hipMemcpy2DAsync(host, a.pitch, d[i], a.bytes, a.bytes, a.rows, hipMemcpyDeviceToHost, p->stream));
-    else if (d[i] && a.out)
-      HIP_TRY(hipMemcpyAsync(host, d[i], a.bytes * a.rows, hipMemcpyDeviceToHost, p->stream));
-  }
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  return CLFA_SUCCESS;
 }
 
 // The object can take a call's arguments at all: a NULL object is an invalid value, one whose creation arguments were bad
@@ -276,17 +222,18 @@ static int pvoc_usable(const clfa_pvoc *p) {
 template <size_t N, class Values, class Launch>
 static int pvoc_call(clfa_pvoc *p, bool blocking, void *stream, bool scalars_ok, long F, const PvocArray (&arrays)[N], int ready,
                      Values values_ok, Launch launch) {
-  static_assert(N <= kPvocArrays, "kPvocArrays");
-  int chk = !scalars_ok || !pvoc_count_ok(F) ? CLFA_INVALID_VALUE : (F == 0 ? 1 : pvoc_arrays_check(arrays, !blocking));
+  static_assert(N <= kCallArrays, "kCallArrays");
+  int chk = !scalars_ok || !pvoc_count_ok(F) || (F > 0 && !arrays_ok(arrays, !blocking)) ? CLFA_INVALID_VALUE : F == 0;
   if (chk == 0 && blocking && !values_ok()) chk = CLFA_INVALID_VALUE;
   if (chk == 0) chk = ready;
   if (!blocking) {
-    const void *d[kPvocArrays] = {};
+    const void *d[kCallArrays] = {};
     for (size_t i = 0; i < N; i++) d[i] = arrays[i].used ? arrays[i].ptr : nullptr;
     return pvoc_dev_form(p, chk, stream, [&](hipStream_t s) { return launch(d, s); });
   }
   if (int e = pvoc_gate(p, chk)) return pvoc_done(e);
-  return pvoc_staged(p, arrays, [&](const void *const *d) {
+  ENTER_DEVICE(p->di.device);
+  return staged_call(p, arrays, [&](const void *const *d) {
     return pvoc_dev_form(p, CLFA_SUCCESS, p->stream, [&](hipStream_t s) { return launch(d, s); });
   });
 }
@@ -308,9 +255,7 @@ static void pvoc_frames_args(const clfa_pvoc *p, long F, PvocFramesArgs &a) {
 // object's own error before they look at an argument.
 // ---------------------------------------------------------------------------------
 
-struct PvocConvert {
-  PvocArray arrays[2];   // the spectra, the frames
-};
+using PvocConvert = HostArrays<clfa_pvoc, 2>;   // the spectra, the frames
 static PvocConvert pvoc_convert(const clfa_pvoc *p, const void *spectra, const void *frames, long F, bool synthesis) {
   return {{{spectra, pvoc_spec_bytes(p, F), 8, synthesis, &clfa_pvoc::sspec},
            {frames, pvoc_frame_bytes(p, F), 8, !synthesis, &clfa_pvoc::sframes}}};
@@ -318,8 +263,8 @@ static PvocConvert pvoc_convert(const clfa_pvoc *p, const void *spectra, const v
 
 // the argument rules of the two device forms; 1 = a successful no-op
 static int pvoc_check(const PvocConvert &c, long F) {
-  if (!pvoc_count_ok(F)) return CLFA_INVALID_VALUE;
-  return F == 0 ? 1 : pvoc_arrays_check(c.arrays, true);
+  if (!pvoc_count_ok(F) || (F > 0 && !arrays_ok(c.a, true))) return CLFA_INVALID_VALUE;
+  return F == 0;
 }
 
 // the blocking forms: NULL arrays are invalid values, then copies around dev(spectra, frames) on the staged arrays
@@ -327,9 +272,10 @@ template <class Dev>
 static int pvoc_convert_host(clfa_pvoc *p, const void *spectra, const void *frames, long F, bool synthesis, Dev dev) {
   if (int e = obj_error(p)) return e;
   const PvocConvert c = pvoc_convert(p, spectra, frames, F, synthesis);
-  if (!pvoc_count_ok(F) || (F > 0 && (!c.arrays[0].ptr || !c.arrays[1].ptr))) return CLFA_INVALID_VALUE;
+  if (!pvoc_count_ok(F) || (F > 0 && (!c.a[0].ptr || !c.a[1].ptr))) return CLFA_INVALID_VALUE;
   if (F == 0) return CLFA_SUCCESS;
-  return pvoc_staged(p, c.arrays, [&](const void *const *d) { return dev(const_cast<void *>(d[0]), const_cast<void *>(d[1])); });
+  ENTER_DEVICE(p->di.device);
+  return staged_call(p, c.a, [&](const void *const *d) { return dev(const_cast<void *>(d[0]), const_cast<void *>(d[1])); });
 }
 
 static PvocArgs pvoc_args(clfa_pvoc *p, long F) {

@@ -1,4 +1,5 @@
-// stft_host.cpp — C ABI of the short-time transforms (see include/clfft_amd.h): Stft.  Shared plumbing: host.hpp.
+// stft_host.cpp — C ABI of the short-time transforms (see include/clfft_amd.h): Stft.  Shared plumbing: host.hpp, where
+// the staged blocking form lives; the rules of a call's arrays: overlap.hpp.
 #include "host.hpp"
 #include "stft_plan.hpp"
 
@@ -17,7 +18,7 @@ struct clfa_stft {
   char log[512];
   hipStream_t stream = nullptr;
   DevBuf half, w2, win, cum;   // Clrfft tables of the direction, the window, its running sums of squares (synthesis, double)
-  DevBuf sig, spec;            // staging of the host entry points
+  DevBuf sig, spec;            // staging of the blocking forms (stft_arrays)
   StreamOrder order;
 };
 
@@ -55,6 +56,16 @@ static int stft_setup(clfa_stft *p, int device, int size, int hop, const float *
 }
 
 static long stft_frames_of(int size, int hop, long samples) { return samples < size ? 0 : 1 + (samples - size) / hop; }
+
+// The two arrays of either direction (HostArrays, host.hpp): the signal, `channels` rows of `len` floats — with one
+// channel the caller's stride is not used, the pitch is the row length — and the packed spectra of F frames per channel.
+// The analysis writes the spectra, the synthesis the signal.
+using StftArrays = HostArrays<clfa_stft, 2>;
+static StftArrays stft_arrays(const clfa_stft *p, const void *signal, long stride, long len, const void *spectra, long F, long channels) {
+  const size_t row = sizeof(float) * (size_t)len, pitch = channels > 1 ? sizeof(float) * (size_t)stride : row;
+  return {{{signal, row, 4, !p->fwd, &clfa_stft::sig, true, (size_t)channels, pitch},
+           {spectra, sizeof(cpx) * (size_t)F * channels * (p->size / 2), 8, p->fwd, &clfa_stft::spec}}};
+}
 
 // spectra of `frames` frames per channel; a grid of at most 2^31 - 1 frames (more would not fit a device)
 static int stft_run(clfa_stft *p, StftArgs &a, long frames, long channels, hipStream_t s) {
@@ -100,11 +111,8 @@ int clfa_stft_analyze_dev(clfa_stft *p, const void *signal, long signal_stride, 
   if (!p->fwd || samples < 0 || channels < 0) return CLFA_INVALID_VALUE;
   const long F = stft_frames_of(p->size, p->hop, samples);
   if (F == 0 || channels == 0) return CLFA_SUCCESS;
-  if (!signal || !spectra || (channels > 1 && signal_stride < samples)) return CLFA_INVALID_VALUE;
-  if (((uintptr_t)signal & 3) || ((uintptr_t)spectra & 7)) return CLFA_INVALID_VALUE;
-  const size_t sbytes = sizeof(float) * ((size_t)(channels - 1) * signal_stride + samples);
-  const size_t obytes = sizeof(cpx) * (size_t)F * channels * (p->size / 2);
-  if (spans_overlap(signal, sbytes, spectra, obytes)) return CLFA_INVALID_VALUE;
+  const StftArrays io = stft_arrays(p, signal, signal_stride, samples, spectra, F, channels);
+  if ((channels > 1 && signal_stride < samples) || !arrays_ok(io.a, true)) return CLFA_INVALID_VALUE;
   ENTER_DEVICE(p->di.device);
   StftArgs a;
   a.signal = (const float *)signal;
@@ -119,12 +127,9 @@ int clfa_stft_synthesize_dev(clfa_stft *p, const void *spectra, long frames, lon
   if (int e = obj_error(p)) return e;
   if (p->fwd || frames < 0 || channels < 0) return CLFA_INVALID_VALUE;
   if (frames == 0 || channels == 0) return CLFA_SUCCESS;
-  if (!signal || !spectra || ((uintptr_t)signal & 3) || ((uintptr_t)spectra & 7)) return CLFA_INVALID_VALUE;
   const long L = (frames - 1) * p->hop + p->size;
-  if (channels > 1 && signal_stride < L) return CLFA_INVALID_VALUE;
-  const size_t sbytes = sizeof(float) * ((size_t)(channels - 1) * signal_stride + L);
-  const size_t ibytes = sizeof(cpx) * (size_t)frames * channels * (p->size / 2);
-  if (spans_overlap(signal, sbytes, spectra, ibytes)) return CLFA_INVALID_VALUE;
+  const StftArrays io = stft_arrays(p, signal, signal_stride, L, spectra, frames, channels);
+  if ((channels > 1 && signal_stride < L) || !arrays_ok(io.a, true)) return CLFA_INVALID_VALUE;
   ENTER_DEVICE(p->di.device);
   StftArgs a;
   a.spec_in = (const cpx *)spectra;
@@ -134,24 +139,17 @@ int clfa_stft_synthesize_dev(clfa_stft *p, const void *spectra, long frames, lon
   return stft_run(p, a, frames, channels, (hipStream_t)stream);
 }
 
+// the blocking forms: a NULL array is refused before the no-op; the staged rows are packed (device stride = row length)
 int clfa_stft_analyze(clfa_stft *p, const float *signal, long signal_stride, long samples, long channels, float *spectra) {
   if (int e = obj_error(p)) return e;
   if (!p->fwd || !signal || !spectra || samples < 0 || channels < 0 || (channels > 1 && signal_stride < samples))
     return CLFA_INVALID_VALUE;
   const long F = stft_frames_of(p->size, p->hop, samples);
   if (F == 0 || channels == 0) return CLFA_SUCCESS;
-  // the rows are packed on the way in: the device copy has stride = samples
-  const size_t row = sizeof(float) * (size_t)samples, obytes = sizeof(cpx) * (size_t)F * channels * (p->size / 2);
   ENTER_DEVICE(p->di.device);
-  int e = p->sig.ensure(row * channels);
-  if (!e) e = p->spec.ensure(obytes);
-  if (e) return e;
-  HIP_TRY(hipMemcpy2DAsync(p->sig.p, row, signal, sizeof(float) * (size_t)(channels > 1 ? signal_stride : samples), row,
-                           channels, hipMemcpyHostToDevice, p->stream));
-  if ((e = clfa_stft_analyze_dev(p, p->sig.p, samples, samples, channels, p->spec.p, p->stream))) return e;
-  HIP_TRY(hipMemcpyAsync(spectra, p->spec.p, obytes, hipMemcpyDeviceToHost, p->stream));
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  return CLFA_SUCCESS;
+  return staged_call(p, stft_arrays(p, signal, signal_stride, samples, spectra, F, channels).a, [&](const void *const *d) {
+    return clfa_stft_analyze_dev(p, d[0], samples, samples, channels, const_cast<void *>(d[1]), p->stream);
+  });
 }
 
 int clfa_stft_synthesize(clfa_stft *p, const float *spectra, long frames, long channels, float *signal, long signal_stride,
@@ -161,17 +159,10 @@ int clfa_stft_synthesize(clfa_stft *p, const float *spectra, long frames, long c
   if (frames == 0 || channels == 0) return CLFA_SUCCESS;
   const long L = (frames - 1) * p->hop + p->size;
   if (channels > 1 && signal_stride < L) return CLFA_INVALID_VALUE;
-  const size_t row = sizeof(float) * (size_t)L, ibytes = sizeof(cpx) * (size_t)frames * channels * (p->size / 2);
   ENTER_DEVICE(p->di.device);
-  int e = p->sig.ensure(row * channels);
-  if (!e) e = p->spec.ensure(ibytes);
-  if (e) return e;
-  HIP_TRY(hipMemcpyAsync(p->spec.p, spectra, ibytes, hipMemcpyHostToDevice, p->stream));
-  if ((e = clfa_stft_synthesize_dev(p, p->spec.p, frames, channels, p->sig.p, L, normalize, p->stream))) return e;
-  HIP_TRY(hipMemcpy2DAsync(signal, sizeof(float) * (size_t)(channels > 1 ? signal_stride : L), p->sig.p, row, row, channels,
-                           hipMemcpyDeviceToHost, p->stream));
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  return CLFA_SUCCESS;
+  return staged_call(p, stft_arrays(p, signal, signal_stride, L, spectra, frames, channels).a, [&](const void *const *d) {
+    return clfa_stft_synthesize_dev(p, d[1], frames, channels, const_cast<void *>(d[0]), L, normalize, p->stream);
+  });
 }
 
 }  // extern "C"
