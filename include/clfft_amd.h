@@ -773,6 +773,65 @@ CLFA_API int clfa_pvoc_trace(clfa_pvoc *pv, const float *frames_in, float *frame
 /* "k_pvoc_trace" ("" for a failed object) */
 CLFA_API const char *clfa_pvoc_trace_kernel_name(const clfa_pvoc *pv);
 
+/* ---- stereo demix by azimuth, with an azimuth profile ---- */
+/* The two inputs are the left and the right channel of one recording: every bin is placed on an azimuth axis by the gain
+ * that best cancels it between the channels, the bins inside a window of positions are kept, and the azimuth profile —
+ * where the sources sit — can be had beside them.  Csound's pvsdemix, the ADRess method.
+ * frames_l, frames_r, frames_out: channels x F x (M + 1) x 2 float32 in the layout above, 8-byte aligned.  par: F x 2
+ * float32, 4-byte aligned, required: row f is (pos, width), shared by the channels.  az: NULL, or channels x F x (2P + 1)
+ * float32, 4-byte aligned.  P = points, 1 <= P <= 1024.  first_bin and nbins select the bins lo = first_bin .. hi =
+ * first_bin + nbins - 1 as for clfa_pvoc_desc_dev (0 <= lo <= hi <= M).  Anything else is CLFA_INVALID_VALUE.
+ *
+ * Every float32 operation is rounded on its own (no fused multiply-add); fl() marks a rounding.
+ *
+ * Per channel, frame f and bin k, with L = l.amp and R = r.amp:
+ *   SIDE       the bin is LEFT where L > R holds, otherwise RIGHT (a tie or a NaN is RIGHT).  loud is the larger amp,
+ *              quiet the other.  The freq of the output is the freq bits of the loud side's input, in every bin: kept or
+ *              not, in the range or not.
+ *   SCAN       g[n] = fl((float)n / (float)P), n = 0..P, the correctly rounded division; d[n] = |fl(quiet - fl(g[n] loud))|.
+ *              m is the smallest d, nmin the lowest n that has it, mx the largest d; mag = fl(mx - m).  The bin is PLACED
+ *              where no d[n] is a NaN and mag > 0 holds.
+ *   AZIMUTH    u = nmin - P for LEFT (-P..0, -P is hard left), u = P - nmin for RIGHT (0..P): one axis of 2P + 1 positions,
+ *              on which the centred bins of both sides meet at u = 0.
+ *   WINDOW     of frame f: pc = fminf(fmaxf(pos, -1), 1) (a NaN gives -1), c = (int)rintf(fl(pc (float)P));
+ *              w = fminf(fmaxf(width, 1), (float)(2P + 1)) (a NaN gives 1), H = (int)w / 2, an integer division.  The bin
+ *              is KEPT where it is placed, lies in lo..hi, and |u - c| <= H.
+ *   FRAMES     the output amp is mag where the bin is kept, +0 elsewhere.
+ *   PROFILE    (az != NULL) column j = 0..2P of a frame's row is T(t), THE TREE SUM of the descriptors above (the same W,
+ *              the same pairing, the Nyquist bin last, a term outside lo..hi being +0), with t[k] = mag where bin k is
+ *              placed and u == j - P, else +0.  The window does not enter the profile.  Every term is >= +0, so no column
+ *              is a NaN.
+ * The scan need not be executed literally: fl(quiet - fl(g[n] loud)) is monotone in n, so mx is at an end and m where the
+ * sign changes.  What is defined is the scan's result, for every input — odd amps, negative ones, infinities and NaNs
+ * included; the closed form round(P quiet / loud) alone is not the definition, ties and rounding go to the scan.
+ *
+ * How this differs from Csound's pvsdemix: there is one signed azimuth axis, not a plane per side, which keeps a source of
+ * the other side from piling up at the centre; the side is chosen per bin, by the louder amp; the width is a count of
+ * positions centred on pos; and the profile is an output of its own.
+ *
+ * Stateless: no state of the object is read or written, and a device call allocates nothing.  The rules of the frame
+ * operations above hold: asynchronous on `stream`, capturable, one launch per call, one stream at a time, the current
+ * device left as found; F == 0 succeeds and does nothing.  Argument checks that need no device come first: on an object
+ * whose creation found no device a bad argument is still CLFA_INVALID_VALUE, a good one the object's error.  An output
+ * (frames_out, az) that overlaps any input or the other output, even partly, is CLFA_INVALID_VALUE and nothing is
+ * written; the two inputs may overlap or be one buffer.  The blocking form also refuses per-frame values outside their
+ * meaning: pos must be finite and in [-1, 1], width finite and in [1, 2P + 1]; the device form clamps as above.  The
+ * outputs are the same bits however a stream is cut into calls, for any grid cap, on any stream and under graph replay.
+ * tests/pvoc_demix_model.py restates all of it in numpy, the scan done literally.
+ *
+ * Kernels: "k_pvoc_demix" without the profile (a lane per bin, 16 bytes in and 8 out, no LDS; two bisections over n in
+ * place of the scan), "k_pvoc_demix_az" with it (a workgroup takes whole frames: the same per bin, leaving (u, mag) of
+ * every bin in LDS, 8 bytes a bin; then the 2P + 1 tree sums from LDS, the columns dealt over the waves, four columns a
+ * pass, the tree inside a wave with the descriptors' DPP and swizzle moves).  Each input frame is read once, each output
+ * written once.  No atomics, no waiting between workgroups.  CLFA_PVOC_OPS_GRID_MAX caps the workgroups of both. */
+CLFA_API int clfa_pvoc_demix_dev(clfa_pvoc *pv, const void *frames_l, const void *frames_r, void *frames_out, const void *par,
+                                 void *az, long F, int points, int first_bin, int nbins, void *stream);
+/* host arrays, copied in and out, blocking */
+CLFA_API int clfa_pvoc_demix(clfa_pvoc *pv, const float *frames_l, const float *frames_r, float *frames_out, const float *par,
+                             float *az, long F, int points, int first_bin, int nbins);
+/* "k_pvoc_demix", or "k_pvoc_demix_az" for a call with the profile ("" for a failed object) */
+CLFA_API const char *clfa_pvoc_demix_kernel_name(const clfa_pvoc *pv, int with_az);
+
 /* ---- convolution matrix (extension: nothing of the reference's) ------------- */
 /* Uniformly partitioned overlap-add convolution of `inputs` signals with an outputs x inputs matrix of static responses:
  * y_o = sum over i of x_i * h_{o,i}.

@@ -147,6 +147,9 @@ SYMBOLS = [
     ("clfa_pvoc_trace_dev", C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_long, C.c_int, C.c_int, C.c_int, _vp]),
     ("clfa_pvoc_trace", C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_long, C.c_int, C.c_int, C.c_int]),
     ("clfa_pvoc_trace_kernel_name", C.c_char_p, [_vp]),
+    ("clfa_pvoc_demix_dev", C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_long, C.c_int, C.c_int, C.c_int, _vp]),
+    ("clfa_pvoc_demix", C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_long, C.c_int, C.c_int, C.c_int]),
+    ("clfa_pvoc_demix_kernel_name", C.c_char_p, [_vp, C.c_int]),
     ("clfa_pvoc_adsyn_dev",C.c_int, [_vp, _vp, C.c_long, _vp, C.c_int, C.c_int, C.c_int, C.c_float, _vp, C.c_long, _vp]),
     ("clfa_pvoc_adsyn", C.c_int, [_vp, _vp, C.c_long, _vp, C.c_int, C.c_int, C.c_int, C.c_float, _vp, C.c_long]),
     ("clfa_pvoc_adsyn_read_state", C.c_int, [_vp, _vp, _vp, _vp]),

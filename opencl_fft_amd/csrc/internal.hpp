@@ -385,6 +385,18 @@ struct PvocTraceArgs : PvocFramesArgs {
 // one launch: k_pvoc_trace<min(M, 256)>
 hipError_t launch_pvoc_trace(const PvocTraceArgs &a, const DeviceInfo &di, hipStream_t s);
 
+// ---- stereo demix by azimuth of two streams of (amp, freq) frames, with the azimuth profile (pvoc_demix.hip) ----
+struct PvocDemixArgs : PvocFramesArgs {
+  const cpx *l = nullptr, *r = nullptr;   // the left and the right channel's frames as (amp, freq) pairs; they may overlap
+  cpx *out = nullptr;
+  const float *par = nullptr;      // F rows of (pos, width), shared by the channels
+  float *az = nullptr;             // NULL, or channels x F x (2 points + 1): the azimuth profile
+  int points = 1;                  // P, 1..1024: the gains 0, 1/P, ..., 1 of either side
+  int lo = 0, hi = 0;              // the range of bins, 0 <= lo <= hi <= M
+};
+// one launch: k_pvoc_demix, or k_pvoc_demix_az<log2 M> where az is given
+hipError_t launch_pvoc_demix(const PvocDemixArgs &a, const DeviceInfo &di, hipStream_t s);
+
 // ---- direct convolution ----------------------------------------------------------
 struct DconvPlan {
   int C;    // taps per workgroup

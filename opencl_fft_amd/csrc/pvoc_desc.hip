@@ -3,7 +3,8 @@
 // the Pvoc code: the header fixes their TREE SUM (which lanes' values meet in which addition), and the kernel is written
 // to it, so the bits do not depend on the grid, on how the stream is cut into calls or on the run length.  No atomics, no
 // waiting between workgroups.  The group kernels' item (which run a group of W lanes takes) and launch are
-// pvoc_device.hpp's, shared with pvoc_trace.hip; the state's commit is pvoc_time.hip's k_pvoc_tail.
+// pvoc_device.hpp's, shared with pvoc_trace.hip, and so are the in-wave moves and the fold of the tree (desc_dpp, desc_xor,
+// desc_fold), shared with pvoc_demix.hip; the state's commit is pvoc_time.hip's k_pvoc_tail.
 //
 //   k_pvoc_desc<W>  W = min(M, 256) lanes form a group, lane j holding the tree's p[j]; 256 / W groups share a workgroup.
 //                   A group takes a run of kDescRun = 4 consecutive frames of one channel and walks the bins outermost,
@@ -38,27 +39,6 @@ constexpr int kDescSums = 4;    // mag, pow, mom, flux
 constexpr int kDescVals = kDescRun * kDescSums;
 static_assert(kDescRun == 4 && kDescVals == 16, "the fold below ends with a frame's four sums in a quad");
 
-template <int CTRL>
-__device__ __forceinline__ int desc_dpp(int v) {
-  return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true);
-}
-
-// v of lane ^ STEP
-template <int STEP>
-__device__ __forceinline__ int desc_xor_bits(int v) {
-  static_assert(STEP == 1 || STEP == 2 || STEP == 4 || STEP == 8 || STEP == 16 || STEP == 32, "a level of one wave");
-  if constexpr (STEP == 1) return desc_dpp<0xB1>(v);                            // quad_perm [1,0,3,2]
-  else if constexpr (STEP == 2) return desc_dpp<0x4E>(v);                       // quad_perm [2,3,0,1]
-  else if constexpr (STEP == 4) return __builtin_amdgcn_ds_swizzle(v, 0x101F);  // and 0x1f, xor 0x04
-  else if constexpr (STEP == 8) return desc_dpp<0x128>(v);                      // row_ror:8
-  else if constexpr (STEP == 16) return __builtin_amdgcn_ds_swizzle(v, 0x401F); // and 0x1f, xor 0x10
-  else return __shfl_xor(v, 32);
-}
-template <int STEP>
-__device__ __forceinline__ float desc_xor(float v) {
-  return __builtin_bit_cast(float, desc_xor_bits<STEP>(__builtin_bit_cast(int, v)));
-}
-
 // a peak: bin k (-1: none yet) and its amp, never a NaN.  The better of two: the larger amp, the lower bin on a tie
 struct DescPeak {
   float a;
@@ -68,6 +48,7 @@ __device__ __forceinline__ DescPeak desc_better(DescPeak p, DescPeak o) {
   const bool take = o.k >= 0 && (p.k < 0 || o.a > p.a || (o.a == p.a && o.k < p.k));   // -0 == +0
   return take ? o : p;
 }
+using clfa::desc_xor;   // pvoc_device.hpp's, for a float: the overload below would hide it
 template <int STEP>
 __device__ __forceinline__ DescPeak desc_xor(DescPeak p) {
   DescPeak o;
@@ -76,17 +57,8 @@ __device__ __forceinline__ DescPeak desc_xor(DescPeak p) {
   return o;
 }
 
-// one level of the tree on the N values the lane still holds: the half that bit STEP of the lane names stays and takes
-// the partner's partial sum, the other half goes to the partner; N / 2 values are left, in V[0 .. N/2)
-template <int STEP, int N>
-__device__ __forceinline__ void desc_fold(float (&V)[kDescVals], bool up) {
-#pragma clang fp contract(off)
-#pragma unroll
-  for (int i = 0; i < N / 2; i++) {
-    const float keep = up ? V[i + N / 2] : V[i], send = up ? V[i] : V[i + N / 2];
-    V[i] = keep + desc_xor<STEP>(send);
-  }
-}
+// one level of the fold (pvoc_device.hpp's desc_fold, the sums') on the N peaks the lane still holds
+using clfa::desc_fold;
 template <int STEP, int N>
 __device__ __forceinline__ void desc_fold(DescPeak (&P)[kDescRun], bool up) {
 #pragma unroll
@@ -102,8 +74,6 @@ __device__ __forceinline__ void desc_level(float &v, DescPeak &p) {
   v = v + desc_xor<STEP>(v);
   p = desc_better(p, desc_xor<STEP>(p));
 }
-
-__device__ __forceinline__ int desc_bitrev2(int x) { return ((x & 1) << 1) | ((x >> 1) & 1); }
 
 }  // namespace
 

@@ -47,6 +47,7 @@ struct clfa_pvoc {
   // state `last`; staging of the host form's rows
   DevBuf dlast, sdesc;
   DevBuf strace_bins;   // the N loudest bins (pvoc_trace.hip): staging of the host form's bin list
+  DevBuf sdemix_az;     // the stereo demix (pvoc_demix.hip): staging of the host form's azimuth profile
   StreamOrder order;
 };
 
@@ -191,8 +192,8 @@ static int pvoc_code(hipError_t e) {
 // One description of a call, checked, staged and handed to the launch from one place
 // ---------------------------------------------------------------------------------
 
-// One array of a call (HostArray, host.hpp; the rules: arrays_ok, overlap.hpp): the outputs are one, or trace's two (the
-// frames and the bin list); what an op does not look at is not `used`: MIX's p and q, BLUR's q, most tables, a NULL fmod
+// One array of a call (HostArray, host.hpp; the rules: arrays_ok, overlap.hpp): the outputs are one, or two (trace's
+// frames and bin list, demix's frames and profile); what an op does not look at is not `used`: MIX's p and q, BLUR's q, most tables, a NULL fmod
 using PvocArray = HostArray<clfa_pvoc>;
 
 // The device forms after their checks (chk): the error, else the object's own, else a no-op's success, ahead of any device
@@ -755,6 +756,65 @@ int clfa_pvoc_trace(clfa_pvoc *p, const float *frames_in, float *frames_out, con
 }
 
 const char *clfa_pvoc_trace_kernel_name(const clfa_pvoc *p) { return !p || p->err ? "" : "k_pvoc_trace"; }
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------
+// the left and the right frames of one recording -> frames, by azimuth, and the azimuth profile (pvoc_demix.hip)
+// ---------------------------------------------------------------------------------
+
+// The second call with two outputs: the frames, and the profile where `az` is given.  par: F rows of (pos, width).  The
+// blocking form asks finite values, pos in [-1, 1] and width in [1, 2 points + 1]; the device form clamps.
+static int pvoc_demix_call(clfa_pvoc *p, bool blocking, const void *l, const void *r, void *out, const void *par, void *az,
+                           long F, int points, int first_bin, int nbins, void *stream) {
+  if (int e = pvoc_usable(p)) return e;
+  const bool scalars_ok = points >= 1 && points <= 1024 && first_bin >= 0 && nbins >= 1 && (long)first_bin + nbins - 1 <= p->M;
+  const size_t fbytes = pvoc_frame_bytes(p, F);
+  const size_t abytes = az && scalars_ok ? sizeof(float) * (size_t)p->channels * (size_t)(F > 0 ? F : 0) * (size_t)(2 * points + 1) : 0;
+  const PvocArray arrays[] = {{l, fbytes, 8, false, &clfa_pvoc::sframes},
+                              {r, fbytes, 8, false, &clfa_pvoc::spair_b},
+                              {out, fbytes, 8, true, &clfa_pvoc::sop_out},
+                              {par, 2 * sizeof(float) * (size_t)F, 4, false, &clfa_pvoc::sop_par},
+                              {az, abytes, 4, true, &clfa_pvoc::sdemix_az, az != nullptr}};
+  const auto values_ok = [&] {
+    const float *v = (const float *)par;
+    for (long f = 0; f < F; f++) {
+      const float pos = v[2 * f], width = v[2 * f + 1];
+      if (!std::isfinite(pos) || !std::isfinite(width)) return false;
+      if (!(pos >= -1.f && pos <= 1.f && width >= 1.f && width <= (float)(2 * points + 1))) return false;
+    }
+    return true;
+  };
+  return pvoc_call(p, blocking, stream, scalars_ok, F, arrays, CLFA_SUCCESS, values_ok, [&](const void *const *d, hipStream_t s) {
+    PvocDemixArgs a;
+    pvoc_frames_args(p, F, a);
+    a.l = (const cpx *)d[0];
+    a.r = (const cpx *)d[1];
+    a.out = (cpx *)d[2];
+    a.par = (const float *)d[3];
+    a.az = (float *)d[4];
+    a.points = points;
+    a.lo = first_bin;
+    a.hi = first_bin + nbins - 1;
+    return launch_pvoc_demix(a, p->di, s);
+  });
+}
+
+extern "C" {
+
+int clfa_pvoc_demix_dev(clfa_pvoc *p, const void *frames_l, const void *frames_r, void *frames_out, const void *par, void *az,
+                        long F, int points, int first_bin, int nbins, void *stream) {
+  return pvoc_demix_call(p, false, frames_l, frames_r, frames_out, par, az, F, points, first_bin, nbins, stream);
+}
+
+int clfa_pvoc_demix(clfa_pvoc *p, const float *frames_l, const float *frames_r, float *frames_out, const float *par, float *az,
+                    long F, int points, int first_bin, int nbins) {
+  return pvoc_demix_call(p, true, frames_l, frames_r, frames_out, par, az, F, points, first_bin, nbins, nullptr);
+}
+
+const char *clfa_pvoc_demix_kernel_name(const clfa_pvoc *p, int with_az) {
+  return !p || p->err ? "" : (with_az ? "k_pvoc_demix_az" : "k_pvoc_demix");
+}
 
 }  // extern "C"
 

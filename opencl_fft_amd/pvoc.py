@@ -10,13 +10,74 @@ def _dense_f32(t, shape):
     return _is_f32(t) and tuple(t.shape) == tuple(shape) and t.is_contiguous()
 
 
-class Pvoc(_Object):
+class _PvocStereo:
+    """The operations of Pvoc whose two inputs are the left and the right channel of one recording (clfa_pvoc_demix*
+    in clfft_amd.h).  A base of Pvoc, which supplies the object and the shared preparation of a call: the operations
+    Pvoc itself defines take one stream of frames, or two unrelated ones."""
+
+    # ---- left and right frames -> frames by azimuth, and the azimuth profile (Csound's pvsdemix; stateless; clfft_amd.h) ----
+
+    def demix_kernel_name(self, az=False):
+        """ "k_pvoc_demix", or "k_pvoc_demix_az" for a call with the profile ("" for a failed object)"""
+        return self._text("demix_kernel_name", int(bool(az)))
+
+    def demix_device(self, left, right, out, par, points, first_bin=0, nbins=None, az_out=None, stream=None):
+        """torch: the frames of the left and of the right channel of one recording, (channels, F, size/2 + 1, 2) float32,
+        contiguous -> out of the same shape.  Every bin of first_bin .. first_bin + nbins - 1 (default: up to size/2) is
+        placed on an azimuth axis of 2 points + 1 positions, -points hard left .. +points hard right, by the gain n / points
+        of the louder side that best cancels the quieter one; the bins within width / 2 positions of pos * points keep
+        the magnitude the cancellation uncovers, every other amp is +0; the freqs are the louder side's.  par: a float32
+        device tensor (F, 2) of rows (pos in [-1, 1], width in [1, 2 points + 1]), shared by the channels, or a (pos, width)
+        pair of numbers.  az_out: a float32 device tensor (channels, F, 2 points + 1), contiguous ((F, 2 points + 1) for one
+        channel), that takes the azimuth profile: per position the summed magnitudes of the bins placed there, whatever the
+        window.  out and az_out may overlap nothing; left and right may be one tensor.  Asynchronous on `stream`."""
+        F = self._device_frames(left, right, out)
+        if hasattr(par, "data_ptr"):
+            prep = None if F is None or not _dense_f32(par, (F, 2)) else (F, [par.data_ptr()], [par])
+        else:
+            try:
+                pos, width = par
+            except (TypeError, ValueError):
+                return CL_INVALID_VALUE
+            prep = self._device_prep(F, out.device, (pos, width), columns=2)
+        points = int(points)
+        if prep is None:
+            return CL_INVALID_VALUE
+        (F, (rows,), _), az = prep, None
+        if az_out is not None:
+            if (self._full(az_out.shape, 3) != (self.channels, F, 2 * points + 1) or not _dense_f32(az_out, az_out.shape)
+                    or az_out.device != out.device):
+                return CL_INVALID_VALUE
+            az = az_out.data_ptr()
+        first_bin, nbins, _ = self._selection(first_bin, nbins, 1)
+        return self._get("demix_dev", left.data_ptr(), right.data_ptr(), out.data_ptr(), rows, az, F, points, first_bin,
+                         nbins, _stream_of(out, stream))
+
+    def demix(self, left, right, pos, width, points, first_bin=0, nbins=None, az=False):
+        """host form of demix_device, blocking: float32 (channels, F, size/2 + 1, 2) (or (F, size/2 + 1, 2)) twice -> the
+        new frames, or (frames, profile) with the profile float32 (.., F, 2 points + 1) when az is set.  pos, width:
+        numbers or (F,) arrays; a pos outside [-1, 1] or a width outside [1, 2 points + 1] raises ClError(CL_INVALID_VALUE)"""
+        (left, F), (right, Fr) = self._host_frames(left), self._host_frames(right)
+        if Fr != F or left.shape != right.shape:
+            raise ValueError("left and right must have the same shape")
+        left, F, (pos, width), out = self._host_prep(left, (pos, width))
+        points = int(points)
+        par = np.ascontiguousarray(np.stack([pos, width], axis=1))
+        prof = np.zeros(left.shape[:-2] + (max(2 * points + 1, 0),), np.float32) if az else None
+        first_bin, nbins, _ = self._selection(first_bin, nbins, 1)
+        check(self._get("demix", left.ctypes.data, right.ctypes.data, out.ctypes.data, par.ctypes.data, _data(prof), F, points,
+                        first_bin, nbins), "Pvoc.demix")
+        return out if prof is None else (out, prof)
+
+
+class Pvoc(_Object, _PvocStereo):
     """Phase vocoder on the spectra of Stft (extension, clfa_pvoc in clfft_amd.h): analyze() reads (channels, F, size/2)
     complex64 spectra as (channels, F, size/2 + 1, 2) float32 frames of (amp, freq in Hz) per bin, synthesize() turns such
     frames back into spectra.  The object carries the last spectrum (analysis) and an integer phase per bin (synthesis)
     from call to call, so a stream may be cut into calls anywhere; reset() returns both to their start.
     adsyn() is the second way back to sound: an oscillator per bin, summed straight into samples (a state of its own).
     describe() turns frames into control values: eight descriptors per frame (the previous frame's amps carried along).
+    demix() takes the frames of the left and of the right channel of one recording apart by pan position.
     Like the other objects the constructor does not raise, and every call returns its status."""
     _abi = "clfa_pvoc_"
 
