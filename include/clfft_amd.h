@@ -660,6 +660,71 @@ CLFA_API int clfa_pvoc_blur_max_frames(const clfa_pvoc *pv);
 /* "k_pvoc_blur", "k_pvoc_smooth", "k_pvoc_freeze" ("" for a failed object or an unknown op) */
 CLFA_API const char *clfa_pvoc_time_kernel_name(const clfa_pvoc *pv, int op);
 
+/* ---- per-bin delay with feedback along a stream of (amp, freq) frames, with carried state ---- */
+/* Csound's pvsbuffer + pvsbufread2 with a delay time per bin taken from a table, the "spectral delay", and with feedback:
+ * echoes that decay per bin.  frames_in and frames_out: channels x F x (M + 1) x 2 float32 in the layout above, 8-byte
+ * aligned.  Two tables, shared by the channels, fixed for one call and free to change between calls: delays, M + 1 int32
+ * (whole frames), 4-byte aligned; feedback, M + 1 float32, 4-byte aligned, or NULL for none.
+ *
+ * clfa_pvoc_delay_setup(pv, max_delay), 0 <= max_delay <= 4096 (anything else is CLFA_INVALID_VALUE), sets L = max_delay
+ * frames and allocates two histories, xhist (the stream's past input frames) and yhist (its past output frames), channels x
+ * L x (M + 1) x 2 float32 each, and one spare of the same size that their commits share; every bin of both histories is
+ * EMPTY (the frame operations' EMPTY bin, (0, fl(k cf))) after it, and again after clfa_pvoc_reset.  The setup follows
+ * clfa_pvoc_blur_setup's rules: blocking, refused with CLFA_INVALID_OPERATION while the object's stream is being
+ * captured, the new buffers allocated before the old ones are replaced (a failed allocation leaves the object as it was),
+ * and it may be called again (the histories are resized and reset).  A delay call before the setup is
+ * CLFA_INVALID_OPERATION.  No other state of the object is touched by any of this.
+ *
+ * The device form takes d = min(max(delays[b], 0), L) for bin b and uses feedback[b] as it is, whatever it is.  The
+ * blocking form refuses, with CLFA_INVALID_VALUE, a delay outside [0, L] (before the setup: outside [0, 4096]) and a
+ * feedback that is not finite or has |g| > 1.
+ *
+ * The streams are xs = xhist ++ frames_in and ys = yhist ++ frames_out: frame f of the call is index L + f of both.  For
+ * channel c, bin b and frame f, with j = L + f - d:
+ *   where feedback is NULL or d == 0:  out = xs[j][b], both columns, the bits moved.  (d == 0 is the input's frame itself;
+ *                                      a loop without a delay is not defined, so the feedback is off for that bin.)
+ *   otherwise, every float32 operation rounded on its own (no fused multiply-add; fl() marks a rounding):
+ *     a1 = xs[j][b].amp,  a2 = fl(feedback[b] ys[j][b].amp),  out.amp = fl(a1 + a2),
+ *     out.freq = ys[j][b].freq where fabsf(a2) > fabsf(a1) holds, else xs[j][b].freq (so with a NaN on either side the
+ *     input's freq); the bits are moved.
+ * This is y[t] = x[t - d] + g y[t - d], a comb on the delayed input: the transfer function of a delay line with feedback,
+ * without a workspace for the line; an echo carries the freq of the partial it echoes.
+ *
+ * After the call xhist is the last L frames of xs and yhist the last L frames of ys, whichever kernel ran, so the results
+ * are the same bits however a stream is cut into calls and whatever route earlier calls took.  The commit follows the
+ * blur's spare-buffer rule: no launch both reads and writes a history, and there is no ring position on the host or on
+ * the device.
+ *
+ * The rules of clfa_pvoc_time_dev hold: F == 0 succeeds and does nothing; the checks that need no device come first (on
+ * an object whose creation found no device a bad argument is still CLFA_INVALID_VALUE, a call before the setup
+ * CLFA_INVALID_OPERATION, a good call the object's error); an output that overlaps the input or a table, even partly, is
+ * CLFA_INVALID_VALUE; a failed call writes nothing and leaves both histories bit for bit as they were; no allocation in a
+ * device call; asynchronous on `stream`, one stream at a time; capturable, a replay advancing the state.
+ * tests/pvoc_delay_model.py restates all of it in numpy.
+ *
+ * clfa_pvoc_delay_read_state (blocking): which = 0 xhist, 1 yhist (anything else is CLFA_INVALID_VALUE), channels x L x
+ * (M + 1) x 2, oldest frame first (nothing is written for L = 0; CLFA_INVALID_OPERATION before the setup).
+ * clfa_pvoc_delay_state_bytes: the device memory of the two histories and the spare; clfa_pvoc_time_state_bytes does not
+ * count it.
+ *
+ * Kernels: "k_pvoc_delay" (feedback NULL: a gather, a lane per bin over a run of consecutive frames) and
+ * "k_pvoc_delay_fb" (a lane per channel and bin walks the call's frames in blocks of 8; with d <= 8 the taps of ys are the
+ * lane's last 8 outputs, kept in registers; with d > 8 a block's 8 frames do not depend on each other and their taps are
+ * loaded together, rows of frames_out the lane stored itself among them); then, for each history, the last L frames of its stream go into the spare, which is copied over it.
+ * CLFA_PVOC_OPS_GRID_MAX caps the workgroups of all. */
+CLFA_API int clfa_pvoc_delay_setup(clfa_pvoc *pv, int max_delay);
+CLFA_API int clfa_pvoc_delay_dev(clfa_pvoc *pv, const void *frames_in, void *frames_out, long F, const void *delays,
+                                 const void *feedback, void *stream);
+/* host arrays, copied in and out, blocking */
+CLFA_API int clfa_pvoc_delay(clfa_pvoc *pv, const float *frames_in, float *frames_out, long F, const int *delays,
+                             const float *feedback);
+CLFA_API int clfa_pvoc_delay_read_state(clfa_pvoc *pv, int which, float *host);
+CLFA_API size_t clfa_pvoc_delay_state_bytes(const clfa_pvoc *pv);
+/* max_delay of the last successful setup, -1 before (0 is a setup too) */
+CLFA_API int clfa_pvoc_delay_max_frames(const clfa_pvoc *pv);
+/* "k_pvoc_delay", or "k_pvoc_delay_fb" for a call with feedback ("" for a failed object) */
+CLFA_API const char *clfa_pvoc_delay_kernel_name(const clfa_pvoc *pv, int feedback);
+
 /* ---- per-frame descriptors of a stream of (amp, freq) frames: magnitude, centroid, flux, peak ---- */
 /* Frames to control values: Csound's pvscent, the level and onset detectors built from pvsbin, peak followers.
  * frames_in: channels x F x (M + 1) x 2 float32 in the layout above, 8-byte aligned; only the amp column and, for the

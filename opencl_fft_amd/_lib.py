@@ -139,6 +139,13 @@ SYMBOLS = [
     ("clfa_pvoc_time_state_bytes", C.c_size_t, [_vp]),
     ("clfa_pvoc_blur_max_frames", C.c_int, [_vp]),
     ("clfa_pvoc_time_kernel_name", C.c_char_p, [_vp, C.c_int]),
+    ("clfa_pvoc_delay_setup", C.c_int, [_vp, C.c_int]),
+    ("clfa_pvoc_delay_dev", C.c_int, [_vp, _vp, _vp, C.c_long, _vp, _vp, _vp]),
+    ("clfa_pvoc_delay", C.c_int, [_vp, _vp, _vp, C.c_long, _vp, _vp]),
+    ("clfa_pvoc_delay_read_state", C.c_int, [_vp, C.c_int, _vp]),
+    ("clfa_pvoc_delay_state_bytes", C.c_size_t, [_vp]),
+    ("clfa_pvoc_delay_max_frames", C.c_int, [_vp]),
+    ("clfa_pvoc_delay_kernel_name", C.c_char_p, [_vp, C.c_int]),
     ("clfa_pvoc_desc_dev", C.c_int, [_vp, _vp, _vp, C.c_long, C.c_int, C.c_int, C.c_int, _vp]),
     ("clfa_pvoc_desc", C.c_int, [_vp, _vp, _vp, C.c_long, C.c_int, C.c_int, C.c_int]),
     ("clfa_pvoc_desc_read_state", C.c_int, [_vp, _vp]),

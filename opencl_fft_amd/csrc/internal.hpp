@@ -359,6 +359,24 @@ hipError_t launch_pvoc_time_fill(cpx *dst, long frames, int M, float cf, hipStre
 // dst (channels x (M + 1) pairs) = frame F - 1 of src (channels x F frames), F >= 1: k_pvoc_tail, the freeze's commit
 hipError_t launch_pvoc_time_last(const cpx *src, long F, cpx *dst, int channels, int M, int grid_max, const DeviceInfo &di,
                                  hipStream_t s);
+// dst (channels x rows frames) = the last `rows` frames of the stream hist ++ src per channel (hist: channels x L frames,
+// read only where rows > F, and then rows <= L; src: channels x F frames): k_pvoc_tail, a history's commit into its spare
+hipError_t launch_pvoc_time_tail(const cpx *hist, int L, const cpx *src, long F, cpx *dst, int rows, int channels, int M,
+                                 int grid_max, const DeviceInfo &di, hipStream_t s);
+
+// ---- per-bin delay with feedback along a stream of (amp, freq) frames, with carried state (pvoc_delay.hip) ----
+struct PvocDelayArgs : PvocFramesArgs {
+  const cpx *in = nullptr;         // frames as (amp, freq) pairs
+  cpx *out = nullptr;
+  const int *delays = nullptr;     // M + 1 values, shared by the channels, clamped to 0 .. L
+  const float *feedback = nullptr; // M + 1 values, or NULL: none
+  cpx *xhist = nullptr, *yhist = nullptr;   // the last L input / output frames per channel, oldest first
+  cpx *spare = nullptr;            // as one history
+  int L = 0;
+};
+// k_pvoc_delay (feedback NULL) or k_pvoc_delay_fb, which only read the histories, then their commits on the same stream:
+// for xhist and then for yhist, k_pvoc_tail into the spare and a copy of the spare over the history
+hipError_t launch_pvoc_delay(const PvocDelayArgs &a, const DeviceInfo &di, hipStream_t s);
 
 // ---- per-frame descriptors of a stream of (amp, freq) frames, with carried state (pvoc_desc.hip) ----
 struct PvocDescArgs : PvocFramesArgs {   // F: also the rows per channel of desc

@@ -1,7 +1,8 @@
 // pvoc_device.hpp — what the Pvoc kernel files share (pvoc_kernels.hip, pvoc_ops.hip, pvoc_pair.hip, pvoc_time.hip,
-// pvoc_shape.hip, pvoc_desc.hip, pvoc_trace.hip, pvoc_demix.hip, pvoc_adsyn.hip):
+// pvoc_delay.hip, pvoc_shape.hip, pvoc_desc.hip, pvoc_trace.hip, pvoc_demix.hip, pvoc_adsyn.hip):
 //   pvoc_item, pvoc_bin    the decoding of a grid-stride item, and the bin a lane of a tile kernel takes of it
 //   pvoc_grid, pvoc_tiles  the cap on a launch's workgroups, and the tiles, items and grid of a tile launch
+//   kTimeWG, kTimeRun      the item of the kernels along the frames (pvoc_time.hip, pvoc_delay.hip): a tile of bins, a run of frames
 //   pvoc_group_row, pvoc_groups   the group kernels (k_pvoc_desc<W>, k_pvoc_trace<W>): which row of a channel a group of W
 //                          lanes takes of an item, and the items and grid of such a launch
 //   desc_dpp, desc_xor, desc_fold   the in-wave moves and the fold of the descriptors' TREE SUM (k_pvoc_desc<W>, k_pvoc_demix_az<LOGM>)
@@ -15,6 +16,8 @@
 namespace clfa {
 
 constexpr int kScanBins = 64, kScanSegs = 16;   // the scan's workgroup: a wave per segment of the chunk axis
+constexpr int kTimeWG = 256;   // lanes = bins per workgroup tile (k_pvoc_blur, k_pvoc_freeze, k_pvoc_tail, k_pvoc_fill, k_pvoc_delay)
+constexpr int kTimeRun = 8;    // consecutive frames per item of those
 
 // item -> (outer index c, inner index j < inner, tile), the tile fastest: neighbouring workgroups hold neighbouring rows
 __device__ __forceinline__ void pvoc_item(long item, int tiles, long inner, int &tile, long &j, long &c) {

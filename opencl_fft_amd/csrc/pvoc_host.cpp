@@ -43,6 +43,11 @@ struct clfa_pvoc {
   // each; the blur's history of max_frames - 1 frames per channel and its spare (clfa_pvoc_blur_setup; blur_max 0 before)
   DevBuf tsmooth, theld, bhist, bspare;
   int blur_max = 0;
+  // the per-bin delay (pvoc_delay.hip): the last delay_max input frames and the last delay_max output frames per channel,
+  // the spare their commits share (clfa_pvoc_delay_setup; delay_max -1 before: 0 is a setup too), staging of the delays
+  DevBuf dxhist, dyhist, dspare;
+  int delay_max = -1;
+  DevBuf sdelay_tab;
   // the descriptors (pvoc_desc.hip): the stream's previous frame, channels x (M + 1) pairs of which the amps are the
   // state `last`; staging of the host form's rows
   DevBuf dlast, sdesc;
@@ -77,7 +82,8 @@ static int pvoc_subbatches(long F, long held, Launch launch) {
 }
 
 // the states as at creation: prev = (1, 0), theta = 0, the oscillator bank's P = W = A = 0, EMPTY bins in the smoothing's
-// y, the freeze's held, the blur's history and the descriptors' previous frame (on p->stream, blocking)
+// y, the freeze's held, the blur's history, the delay's two histories and the descriptors' previous frame (on p->stream,
+// blocking)
 static int pvoc_init_state(clfa_pvoc *p) {
   std::vector<cpx> one(pvoc_bins(p), mk(1.f, 0.f));
   HIP_TRY(hipMemcpyAsync(p->prev.p, one.data(), sizeof(cpx) * one.size(), hipMemcpyHostToDevice, p->stream));
@@ -89,6 +95,9 @@ static int pvoc_init_state(clfa_pvoc *p) {
   HIP_TRY(launch_pvoc_time_fill((cpx *)p->theld.p, p->channels, p->M, p->srs, p->stream));
   HIP_TRY(launch_pvoc_time_fill((cpx *)p->dlast.p, p->channels, p->M, p->srs, p->stream));
   HIP_TRY(launch_pvoc_time_fill((cpx *)p->bhist.p, (long)p->channels * (p->blur_max > 0 ? p->blur_max - 1 : 0), p->M, p->srs, p->stream));
+  const long delay_rows = (long)p->channels * (p->delay_max > 0 ? p->delay_max : 0);
+  HIP_TRY(launch_pvoc_time_fill((cpx *)p->dxhist.p, delay_rows, p->M, p->srs, p->stream));
+  HIP_TRY(launch_pvoc_time_fill((cpx *)p->dyhist.p, delay_rows, p->M, p->srs, p->stream));
   HIP_TRY(hipStreamSynchronize(p->stream));
   return CLFA_SUCCESS;
 }
@@ -655,6 +664,100 @@ int clfa_pvoc_blur_max_frames(const clfa_pvoc *p) { return p ? p->blur_max : 0; 
 const char *clfa_pvoc_time_kernel_name(const clfa_pvoc *p, int op) {
   if (!p || p->err || op < PVOC_BLUR || op > PVOC_FREEZE) return "";
   return op == PVOC_BLUR ? "k_pvoc_blur" : (op == PVOC_SMOOTH ? "k_pvoc_smooth" : "k_pvoc_freeze");
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------
+// frames -> frames along the stream: the per-bin delay with feedback, with carried state (pvoc_delay.hip)
+// ---------------------------------------------------------------------------------
+
+constexpr int kPvocDelayMax = 4096;   // the largest max_delay of clfa_pvoc_delay_setup
+
+// whether the delay has been set up: asked after the arguments (and, in the blocking form, after the tables' values)
+static int pvoc_delay_ready(const clfa_pvoc *p) { return p->delay_max < 0 ? CLFA_INVALID_OPERATION : CLFA_SUCCESS; }
+
+// A NULL feedback is none.  The blocking form asks delays in 0..max_delay (before the setup: 0..4096, what a setup can make
+// valid) and finite feedbacks in [-1, 1]; the device form clamps the delays and takes the feedbacks as they are.
+static int pvoc_delay_call(clfa_pvoc *p, bool blocking, const void *in, void *out, long F, const void *delays,
+                           const void *feedback, void *stream) {
+  if (int e = pvoc_usable(p)) return e;
+  const size_t fbytes = pvoc_frame_bytes(p, F);
+  const PvocArray arrays[] = {{in, fbytes, 8, false, &clfa_pvoc::sframes},
+                              {out, fbytes, 8, true, &clfa_pvoc::sop_out},
+                              {delays, sizeof(int) * (size_t)(p->M + 1), 4, false, &clfa_pvoc::sdelay_tab},
+                              {feedback, sizeof(float) * (size_t)(p->M + 1), 4, false, &clfa_pvoc::sshape_tab, feedback != nullptr}};
+  const auto values_ok = [&] {
+    const int *d = (const int *)delays;
+    const float *g = (const float *)feedback;
+    for (int k = 0; k <= p->M; k++) {
+      if (d[k] < 0 || d[k] > (p->delay_max >= 0 ? p->delay_max : kPvocDelayMax)) return false;
+      if (g && !(std::isfinite(g[k]) && g[k] >= -1.f && g[k] <= 1.f)) return false;
+    }
+    return true;
+  };
+  return pvoc_call(p, blocking, stream, true, F, arrays, pvoc_delay_ready(p), values_ok, [&](const void *const *d, hipStream_t s) {
+    PvocDelayArgs a;
+    pvoc_frames_args(p, F, a);
+    a.in = (const cpx *)d[0];
+    a.out = (cpx *)d[1];
+    a.delays = (const int *)d[2];
+    a.feedback = (const float *)d[3];
+    a.xhist = (cpx *)p->dxhist.p;
+    a.yhist = (cpx *)p->dyhist.p;
+    a.spare = (cpx *)p->dspare.p;
+    a.L = p->delay_max;
+    return launch_pvoc_delay(a, p->di, s);
+  });
+}
+
+extern "C" {
+
+int clfa_pvoc_delay_setup(clfa_pvoc *p, int max_delay) {
+  if (int e = pvoc_usable(p)) return e;
+  if (max_delay < 0 || max_delay > kPvocDelayMax) return CLFA_INVALID_VALUE;
+  if (p->err) return p->err;
+  ENTER_DEVICE(p->di.device);
+  if (int e = pvoc_quiesce(p)) return e;
+  // the three buffers first, so that a failed allocation leaves the object as it was
+  const size_t bytes = pvoc_frame_bytes(p, max_delay);
+  DevBuf bufs[3];
+  DevBuf clfa_pvoc::*const mine[3] = {&clfa_pvoc::dxhist, &clfa_pvoc::dyhist, &clfa_pvoc::dspare};
+  for (DevBuf &b : bufs)
+    if (int e = b.ensure(bytes)) return e;
+  for (int i = 0; i < 2; i++) HIP_TRY(launch_pvoc_time_fill((cpx *)bufs[i].p, (long)p->channels * max_delay, p->M, p->srs, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  for (int i = 0; i < 3; i++) {
+    std::swap((p->*mine[i]).p, bufs[i].p);
+    std::swap((p->*mine[i]).bytes, bufs[i].bytes);
+  }
+  p->delay_max = max_delay;
+  return CLFA_SUCCESS;
+}
+
+int clfa_pvoc_delay_dev(clfa_pvoc *p, const void *frames_in, void *frames_out, long F, const void *delays,
+                        const void *feedback, void *stream) {
+  return pvoc_delay_call(p, false, frames_in, frames_out, F, delays, feedback, stream);
+}
+int clfa_pvoc_delay(clfa_pvoc *p, const float *frames_in, float *frames_out, long F, const int *delays, const float *feedback) {
+  return pvoc_delay_call(p, true, frames_in, frames_out, F, delays, feedback, nullptr);
+}
+
+int clfa_pvoc_delay_read_state(clfa_pvoc *p, int which, float *host) {
+  if (!p || which < 0 || which > 1 || !host) return CLFA_INVALID_VALUE;
+  if (int e = obj_error(p)) return e;
+  if (int e = pvoc_delay_ready(p)) return e;
+  ENTER_DEVICE(p->di.device);
+  if (int e = pvoc_quiesce(p)) return e;
+  const size_t bytes = pvoc_frame_bytes(p, p->delay_max);
+  if (bytes) HIP_TRY(hipMemcpy(host, (which ? p->dyhist : p->dxhist).p, bytes, hipMemcpyDeviceToHost));
+  return CLFA_SUCCESS;
+}
+
+size_t clfa_pvoc_delay_state_bytes(const clfa_pvoc *p) { return p ? p->dxhist.bytes + p->dyhist.bytes + p->dspare.bytes : 0; }
+int clfa_pvoc_delay_max_frames(const clfa_pvoc *p) { return p ? p->delay_max : -1; }
+const char *clfa_pvoc_delay_kernel_name(const clfa_pvoc *p, int feedback) {
+  return !p || p->err ? "" : (feedback ? "k_pvoc_delay_fb" : "k_pvoc_delay");
 }
 
 }  // extern "C"

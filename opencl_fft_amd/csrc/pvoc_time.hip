@@ -15,6 +15,7 @@
 //                  writes the history and no ring position exists (on the host it would not advance under graph replay,
 //                  on the device its update would race with its readers).  The freeze's commit: the output's last frame
 //                  into held.  The descriptors' commit (pvoc_desc.hip, launch_pvoc_time_last): the input's last frame.
+//                  The delay's commit (pvoc_delay.hip, launch_pvoc_time_tail): its two histories, as the blur's.
 //   k_pvoc_smooth  the recurrence is serial along the frames: a lane owns one (channel, bin), reads its state first, walks
 //                  the call's frames and writes the state last.  The loads do not depend on the recurrence: a group of
 //                  kSmoothGroup frames is in flight in registers ahead of the arithmetic.  Workgroups of 64 lanes spread
@@ -33,8 +34,6 @@ namespace clfa {
 
 namespace {
 
-constexpr int kTimeWG = 256;       // lanes = bins per workgroup tile (k_pvoc_blur, k_pvoc_freeze, k_pvoc_tail, k_pvoc_fill)
-constexpr int kTimeRun = 8;        // consecutive frames per item
 constexpr int kSmoothWG = 64;      // lanes = bins per workgroup tile of k_pvoc_smooth
 constexpr int kSmoothGroup = 8;    // frames in flight ahead of the recurrence
 
@@ -214,15 +213,21 @@ static hipError_t launch_pvoc_tail(const PvocTimeArgs &a, const cpx *hist, int L
   return hipGetLastError();
 }
 
-hipError_t launch_pvoc_time_last(const cpx *src, long F, cpx *dst, int channels, int M, int grid_max, const DeviceInfo &di,
-                                 hipStream_t s) {
-  if (F <= 0 || channels <= 0) return hipSuccess;
+hipError_t launch_pvoc_time_tail(const cpx *hist, int L, const cpx *src, long F, cpx *dst, int rows, int channels, int M,
+                                 int grid_max, const DeviceInfo &di, hipStream_t s) {
+  if (rows <= 0 || channels <= 0) return hipSuccess;
   PvocTimeArgs a;
   a.M = M;
   a.channels = channels;
   a.F = F;
   a.grid_max = grid_max;
-  return launch_pvoc_tail(a, nullptr, 0, src, dst, 1, di, s);
+  return launch_pvoc_tail(a, hist, L, src, dst, rows, di, s);
+}
+
+hipError_t launch_pvoc_time_last(const cpx *src, long F, cpx *dst, int channels, int M, int grid_max, const DeviceInfo &di,
+                                 hipStream_t s) {
+  if (F <= 0) return hipSuccess;
+  return launch_pvoc_time_tail(nullptr, 0, src, F, dst, 1, channels, M, grid_max, di, s);
 }
 
 hipError_t launch_pvoc_time(const PvocTimeArgs &a, const DeviceInfo &di, hipStream_t s) {

@@ -70,7 +70,83 @@ class _PvocStereo:
         return out if prof is None else (out, prof)
 
 
-class Pvoc(_Object, _PvocStereo):
+class _PvocDelay:
+    """The operation of Pvoc that reads the stream's past through a table over the bins (clfa_pvoc_delay* in clfft_amd.h):
+    the per-bin delay with feedback.  A base of Pvoc, like _PvocStereo: Pvoc supplies the object and the shared
+    preparation of a call, and its own operations take their parameters per frame, not per bin."""
+
+    # ---- frames -> frames along the stream: a delay per bin, with feedback (Csound's pvsbuffer + pvsbufread2 with a
+    # ---- table of delay times; two carried histories; clfft_amd.h)
+
+    def delay_kernel_name(self, feedback=False):
+        """ "k_pvoc_delay", or "k_pvoc_delay_fb" for a call with feedback ("" for a failed object)"""
+        return self._text("delay_kernel_name", int(bool(feedback)))
+
+    def delay_setup(self, max_delay):
+        """allocates and resets the two histories for delays of up to max_delay (0..4096) frames (blocking)"""
+        return self._get("delay_setup", int(max_delay))
+
+    def delay_max_frames(self):
+        """max_delay of the last delay_setup, -1 before"""
+        return self._get("delay_max_frames")
+
+    def delay_state_bytes(self):
+        """device memory of the two histories and the spare their commits share"""
+        return self._get("delay_state_bytes")
+
+    def delay_state(self):
+        """(xhist, yhist): the last max_delay input frames and the last max_delay output frames of the stream (blocking),
+        float32 (channels, max_delay, size/2 + 1, 2) each, oldest frame first"""
+        out = [np.zeros((self.channels, max(self.delay_max_frames(), 0), self.M + 1, 2), np.float32) for _ in range(2)]
+        for which, a in enumerate(out):
+            check(self._get("delay_read_state", which, a.ctypes.data), "Pvoc.delay_state")
+        return tuple(out)
+
+    @staticmethod
+    def delay_frames(seconds, sr, hop):
+        """a delay time in seconds as the nearest whole number of frames of `hop` samples at the sample rate sr"""
+        return int(round(float(seconds) * float(sr) / int(hop)))
+
+    def _delay_table(self, t, dtype, device):
+        """a table over the bins for a device call: a device tensor of `dtype` (size/2 + 1,), contiguous, as it is; a number
+        as a tensor of size/2 + 1 copies on `device` (filled on torch's current stream, as _device_prep's are); else None"""
+        import torch
+        if hasattr(t, "data_ptr"):
+            ok = t.dtype == dtype and tuple(t.shape) == (self.M + 1,) and t.is_contiguous() and t.device == device
+            return t if ok else None
+        try:
+            return torch.full((self.M + 1,), int(t) if dtype == torch.int32 else float(t), dtype=dtype, device=device)
+        except (TypeError, ValueError):
+            return None
+
+    def delay_device(self, frames_in, frames_out, delays, feedback=None, stream=None):
+        """torch: frames (channels, F, size/2 + 1, 2) float32, contiguous -> frames_out of the same shape: bin b of frame t
+        is bin b of the stream's frame t - d, d = delays[b] clamped to 0..max_delay of delay_setup; with feedback,
+        y[t] = x[t - d] + g y[t - d] per bin, g = feedback[b], and an echo louder than the delayed input brings its freq
+        along.  delays: an int32 device tensor (size/2 + 1,) or one int for every bin; feedback: a float32 device tensor
+        (size/2 + 1,), a number, or None for none.  The frames of earlier calls are the object's two histories.
+        frames_out may overlap neither frames_in nor a table.  Asynchronous on `stream`."""
+        import torch
+        F = self._device_frames(frames_in, frames_out)
+        d = self._delay_table(delays, torch.int32, frames_out.device)
+        g = None if feedback is None else self._delay_table(feedback, torch.float32, frames_out.device)
+        if F is None or d is None or (feedback is not None and g is None):
+            return CL_INVALID_VALUE
+        return self._get("delay_dev", frames_in.data_ptr(), frames_out.data_ptr(), F, d.data_ptr(),
+                         None if g is None else g.data_ptr(), _stream_of(frames_out, stream))
+
+    def delay(self, frames, delays, feedback=None):
+        """host form of delay_device, blocking: returns the new frames; delays: an int or an integer (size/2 + 1,) array,
+        feedback: a number, a (size/2 + 1,) array or None.  A delay outside 0..max_delay, or a feedback that is not finite
+        or above 1 in size, raises ClError(CL_INVALID_VALUE)"""
+        frames, F, _, out = self._host_prep(frames)
+        d = np.ascontiguousarray(np.broadcast_to(np.asarray(delays, dtype=np.int32), (self.M + 1,)))
+        g = None if feedback is None else np.ascontiguousarray(np.broadcast_to(np.asarray(feedback, dtype=np.float32), (self.M + 1,)))
+        check(self._get("delay", frames.ctypes.data, out.ctypes.data, F, d.ctypes.data, _data(g)), "Pvoc.delay")
+        return out
+
+
+class Pvoc(_Object, _PvocStereo, _PvocDelay):
     """Phase vocoder on the spectra of Stft (extension, clfa_pvoc in clfft_amd.h): analyze() reads (channels, F, size/2)
     complex64 spectra as (channels, F, size/2 + 1, 2) float32 frames of (amp, freq in Hz) per bin, synthesize() turns such
     frames back into spectra.  The object carries the last spectrum (analysis) and an integer phase per bin (synthesis)
@@ -78,6 +154,7 @@ class Pvoc(_Object, _PvocStereo):
     adsyn() is the second way back to sound: an oscillator per bin, summed straight into samples (a state of its own).
     describe() turns frames into control values: eight descriptors per frame (the previous frame's amps carried along).
     demix() takes the frames of the left and of the right channel of one recording apart by pan position.
+    delay() gives every bin its own delay time and feedback (two histories of the stream carried along, after delay_setup()).
     Like the other objects the constructor does not raise, and every call returns its status."""
     _abi = "clfa_pvoc_"
 
