@@ -145,6 +145,18 @@ CLFA_API int clfa_fft_run_buffers(clfa_fft *plan);
 CLFA_API size_t clfa_fft_workspace_bytes(const clfa_fft *plan);
 /* name of the HIP kernel that does the work for this plan (for profiles) */
 CLFA_API const char *clfa_fft_kernel_name(const clfa_fft *plan);
+/* measurement aid (complex n = 65536 plans, CLFA_INVALID_OPERATION for others): with on != 0 every later launch of the
+ * resident kernel k_fft_res16 leaves one 16-byte record per workgroup — { uint32 transforms it processed, uint32
+ * workgroup index % 8, uint64 wall clock (100 MHz) at its exit } — at the price of one store per
+ * workgroup; on = 0 stops it.  clfa_fft_balance_read waits for the device and copies the last launch's records, in
+ * workgroup order (workgroup i runs on XCD i % 8), up to max_records of them; *count = how many.  Both calls block. */
+CLFA_API int clfa_fft_balance_record(clfa_fft *plan, int on);
+CLFA_API int clfa_fft_balance_read(clfa_fft *plan, void *records, int max_records, int *count);
+/* test aid (the same plans, CLFA_INVALID_OPERATION for others): waits for the device and copies the 352 32-bit words around
+ * the shared assignment's counters in the plan's workspace, up to max_words of them; *count = how many.  Words 0..31 and
+ * 320..351 are the guard lines in front of and behind the counters and always hold 0xA5A5A5A5; words 32..319 are the nine
+ * 128-byte counter lines, all zero whenever no launch is running. */
+CLFA_API int clfa_fft_balance_counters(clfa_fft *plan, unsigned *words, int max_words, int *count);
 
 /* measurement aid (nothing of the reference's): sustained device-memory bandwidth in TB/s over
  * `launches` launches on two buffers of `bytes` each (a multiple of 512 KiB, far beyond the 256 MiB

@@ -43,6 +43,9 @@ SYMBOLS = [
     ("clfa_stream_synchronize", C.c_int, [_vp]),
     ("clfa_fft_workspace_bytes", C.c_size_t, [_vp]),
     ("clfa_fft_kernel_name", C.c_char_p, [_vp]),
+    ("clfa_fft_balance_record", C.c_int, [_vp, C.c_int]),
+    ("clfa_fft_balance_read", C.c_int, [_vp, _vp, C.c_int, _ip]),
+    ("clfa_fft_balance_counters", C.c_int, [_vp, _vp, C.c_int, _ip]),
     ("clfa_reorder_dev", C.c_int, [C.c_int, _vp, _vp, C.c_int, C.c_long, _vp]),
     ("clfa_pconv_create", C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.c_int, C.c_int]),
     ("clfa_pconv_destroy", None, [_vp]),

@@ -37,6 +37,12 @@ struct clfa_fft {
   // n > 65536 (extension): n = N1 x N2; `tabs` then belongs to the N2-point row transform
   BigGeom big{};
   DevBuf bigtabs, scratch2;
+  // complex n = 65536: the resident kernel's counters (kRes16CtrBytes behind the workspace, a guard line on either side:
+  // zeroed once at creation, left zero by every launch) and, on request, its per-workgroup records (clfa_fft_balance_record)
+  unsigned *res16_ctr = nullptr;
+  bool res16_static = false;   // CLFA_RES16_STATIC=1 (a measuring switch, read at creation): the static assignment always
+  DevBuf res16_rec;
+  int rec_grid = 0;        // workgroups of the last recorded launch
   // any other length (extension): Bluestein around two power-of-two plans of length sh.blue_m
   clfa_fft *blue_f = nullptr, *blue_i = nullptr;
   DevBuf blue_w, blue_b, blue_work;
@@ -253,7 +259,22 @@ static int fft_setup(clfa_fft *p, int device, int n, bool real, int size, bool f
   if (needs & kNeedRes16) fill_res16_tables(h);
   if ((needs & kNeedRes16) && (e = put(p->res16, p->tabs.res16))) return e;
   DevBuf &ws = rows.logn == p->sh.logn ? p->scratch : p->scratch2;
-  return needs & kNeedFourWs ? ws.ensure((size_t)fourstep_grid(p->di) * rows.n * sizeof(cpx)) : CLFA_SUCCESS;
+  if (!(needs & kNeedFourWs)) return CLFA_SUCCESS;
+  const size_t wsb = (size_t)fourstep_grid(p->di) * rows.n * sizeof(cpx);
+  // the plan's own complex n = 65536 transform: the shared assignment's counters behind the workspace proper (whose first
+  // part are the slots; the few-transform route writes up to num_cus / 4 transforms there, so the counters follow its
+  // end), between two guard lines.  The packed real size-131072 plans run the static assignment: no counters.
+  const bool ctr = !real && (needs & kNeedRes16) && rows.logn == p->sh.logn;
+  if ((e = ws.ensure(wsb + (ctr ? kRes16CtrBytes + 2 * kRes16GuardBytes : 0)))) return e;
+  if (ctr) {
+    char *g = (char *)ws.p + wsb;
+    p->res16_ctr = (unsigned *)(g + kRes16GuardBytes);
+    HIP_TRY(hipMemsetAsync(g, (int)(kRes16GuardWord & 0xff), kRes16CtrBytes + 2 * kRes16GuardBytes, p->stream));
+    HIP_TRY(hipMemsetAsync(p->res16_ctr, 0, kRes16CtrBytes, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));   // launches may follow on any stream
+    p->res16_static = env_long("CLFA_RES16_STATIC", 0, 2) != 0;
+  }
+  return CLFA_SUCCESS;
 }
 
 int clfa_cfft_create(clfa_fft **plan, int device, int n, int forward) {
@@ -334,8 +355,13 @@ static int fft_exec(clfa_fft *p, cpx *d, long off, long batch, hipStream_t s) {
       else HIP_TRY(launch_crfft_res16(d, o, scratch, p->tabs.res16, p->tabs.w2, batch, p->di, s));
       break;
     case FftRoute::FourStepSpread:
-    case FftRoute::FourStep:
-    case FftRoute::Res16: HIP_TRY(launch_fft_4step(sh.logn, fwd, scale, d, scratch, p->tabs, batch, p->di, s, o - d)); break;
+    case FftRoute::FourStep: HIP_TRY(launch_fft_4step(sh.logn, fwd, scale, d, scratch, p->tabs, batch, p->di, s, o - d)); break;
+    case FftRoute::Res16: {
+      ResRecord *rec = (ResRecord *)p->res16_rec.p;
+      if (rec) p->rec_grid = (int)(batch < p->di.num_cus ? batch : p->di.num_cus);
+      HIP_TRY(launch_fft_res16(fwd, scale, d, o, scratch, p->tabs.res16, batch, p->di, s, p->res16_static ? nullptr : p->res16_ctr, rec));
+      break;
+    }
     case FftRoute::Big: {
       const int e = for_chunks(batch, (long)(p->scratch.bytes / (sizeof(cpx) * (size_t)sh.n)), [&](long b0, long nb) -> int {
         HIP_TRY(launch_fft_big(p->big, fwd, scale, d + b0 * (long)sh.n, o + b0 * (long)sh.n, scratch, (cpx *)p->scratch2.p,
@@ -382,6 +408,48 @@ int clfa_fft_exec_dev_oop(clfa_fft *p, const void *src, void *dst, long batch, v
   // every kernel reads the source and writes the destination (the kernels take the distance between the two); the source
   // is never written — also not by the routes of several passes, whose first pass already lands in the destination
   return fft_exec(p, (cpx *)const_cast<void *>(src), (long)((b - a) / (long)sizeof(cpx)), batch, s);
+}
+
+// ---- measurement aid: what every workgroup of the resident n = 65536 kernel did in the plan's last launch ----
+int clfa_fft_balance_record(clfa_fft *p, int on) {
+  if (int e = obj_error(p)) return e;
+  if (!p->res16_ctr) return CLFA_INVALID_OPERATION;   // no complex n = 65536 plan
+  ENTER_DEVICE(p->di.device);
+  HIP_TRY(hipDeviceSynchronize());
+  p->rec_grid = 0;
+  if (!on) {
+    p->res16_rec.release();
+    return CLFA_SUCCESS;
+  }
+  return p->res16_rec.ensure(sizeof(ResRecord) * (size_t)p->di.num_cus);
+}
+
+int clfa_fft_balance_read(clfa_fft *p, void *records, int max_records, int *count) {
+  if (int e = obj_error(p)) return e;
+  if (!records || !count || max_records < 0) return CLFA_INVALID_VALUE;
+  *count = 0;
+  if (!p->res16_rec.p) return CLFA_INVALID_OPERATION;
+  ENTER_DEVICE(p->di.device);
+  HIP_TRY(hipDeviceSynchronize());   // the launch may be on any stream
+  const int n = p->rec_grid < max_records ? p->rec_grid : max_records;
+  if (n) HIP_TRY(hipMemcpy(records, p->res16_rec.p, sizeof(ResRecord) * (size_t)n, hipMemcpyDeviceToHost));
+  *count = n;
+  return CLFA_SUCCESS;
+}
+
+// ---- test aid: the counters' lines as they stand, with the guard line on either side ----
+int clfa_fft_balance_counters(clfa_fft *p, unsigned *words, int max_words, int *count) {
+  if (int e = obj_error(p)) return e;
+  if (!words || !count || max_words < 0) return CLFA_INVALID_VALUE;
+  *count = 0;
+  if (!p->res16_ctr) return CLFA_INVALID_OPERATION;
+  ENTER_DEVICE(p->di.device);
+  HIP_TRY(hipDeviceSynchronize());   // the launch may be on any stream
+  const int all = (int)((kRes16CtrBytes + 2 * kRes16GuardBytes) / sizeof(unsigned));
+  const int n = all < max_words ? all : max_words;
+  if (n) HIP_TRY(hipMemcpy(words, (const char *)p->res16_ctr - kRes16GuardBytes, sizeof(unsigned) * (size_t)n, hipMemcpyDeviceToHost));
+  *count = n;
+  return CLFA_SUCCESS;
 }
 
 int clfa_fft_device_buffers(clfa_fft *p, void **data1, void **data2, void **commands) {

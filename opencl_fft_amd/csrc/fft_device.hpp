@@ -39,6 +39,21 @@ CLFA_HD long xcd_first(unsigned i, unsigned grid) {
   if (grid & 7) return i;
   return (long)(i & 7) * (grid >> 3) + (i >> 3);
 }
+// The same sequence per XCD, for kernels that deal it out dynamically (the resident n = 65536 kernel's shared
+// assignment, fft_resident.hip): XCD x walks positions p = 0, 1, ... through its eighth of every window, so position p
+// is the transform workgroup x + 8 (p % (G / 8)) reaches in its iteration p / (G / 8) above.  grid: a multiple of 8.
+CLFA_HD unsigned xcd_transform(unsigned x, unsigned grid, unsigned p) {
+  const unsigned w = grid >> 3;
+  return (p / w) * grid + x * w + p % w;
+}
+// ... and XCD x's share of a batch: the positions p < xcd_share() map to transforms < batch, all others lie beyond it
+// (xcd_transform() grows with p).  The eight shares add up to the batch.
+CLFA_HD unsigned xcd_share(unsigned x, unsigned grid, unsigned batch) {
+  const unsigned w = grid >> 3, r = batch % grid, lo = x * w;
+  return (batch / grid) * w + (r <= lo ? 0u : r - lo < w ? r - lo : w);
+}
+// where the shared assignment applies: every workgroup has more than one transform, whole XCD eighths, 32-bit indices
+CLFA_HD bool xcd_shared_ok(long batch, unsigned grid) { return grid >= 8 && !(grid & 7) && batch > (long)grid && batch < (1L << 31); }
 
 
 // A complex value is a native 2-float vector on the device (and wherever clang compiles this

@@ -302,13 +302,15 @@ __device__ __forceinline__ void res_row_block(cpx (&v)[16], const ResLane &L, co
 // phase 1, one column block: wait for its data (N younger asm loads), take it out of its landing zone
 // (ZC >= 0: AGPR columns ZC, ZC + 1; ZC < 0: v[224:255]), transform it with the loads of the block two
 // ahead riding along (-> AGPR columns NZ, NZ + 1, or the landing registers for NZ < 0; none if !LOAD)
-template <bool FWD, int ZC, int NZ, bool LOAD, int N = 16, bool LAST = false>
+// draw: the shared assignment's step (res_draw_step), behind the wait and ahead of the block's hooked loads
+template <bool FWD, int ZC, int NZ, bool LOAD, int N = 16, bool LAST = false, class DS = NoTail>
 __device__ __forceinline__ void res_phase1_block(cpx (&v)[16], const ResLane &L, const cpx *x, int cb,
                                                  const int (&so)[16], f32x32 (&K)[kVgprBlk], __amdgpu_buffer_rsrc_t slot,
-                                                 const cpx *s_tab, cpx *s_x) {
+                                                 const cpx *s_tab, cpx *s_x, const DS &draw = DS()) {
   res_wait_vm<N>();
   if constexpr (ZC >= 0) acc_fetch_raw<ZC>(v, std::make_integer_sequence<int, 8>());
   else res_land_fetch(v);
+  draw();
   if constexpr (LOAD) {
     const __amdgpu_buffer_rsrc_t r = res_rsrc(x + (cb + 2) * 16);
     if constexpr (NZ >= 0) res_col_block<FWD>(v, L, cb, s_tab, s_x, HookAcc<NZ>{r, L.voff, so});

@@ -167,6 +167,74 @@ template <int N> __device__ __forceinline__ void res_wait_vm() {
   if constexpr (N == 32) asm volatile("s_waitcnt vmcnt(32)" ::: "memory");
 }
 
+// ---- the shared assignment's draws (k_fft_res16<..., DYN>) -------------------------------------------------------------
+// One returning add of 1 on a word of the plan's counters (agent scope: the form hipcc emits for a relaxed
+// __hip_atomic_fetch_add, executed at the memory side), issued by ONE lane of wave 0.  Like the loads it must land where
+// hipcc never looks while it is pending: in the first register of an AGPR landing zone that is empty for this and the next
+// column block (REG = a[2 * zone column]: the block that took its data out of the zone issues into the first column, the
+// block after it into the second; the zone's next loads are hooked to the block after that).  It is issued behind the
+// block's wait and ahead of its 16 hooked loads, so the next block's vmcnt(16) covers it and no count changes.
+template <int REG> __device__ __forceinline__ void res_draw_issue(unsigned *ctr, int byte_off) {
+  asm volatile("v_accvgpr_write_b32 a[%c0], 1\n\ts_nop 4\n\tglobal_atomic_add a[%c0], %1, a[%c0], %2 sc0" ::"n"(REG), "v"(byte_off), "s"(ctr) : "memory");
+}
+// the counters: one per XCD and the launch's count of workgroups that have drawn for the last time, 128 bytes apart
+constexpr int kDrawStride = 128, kDrawDone = 8;
+// The steps' state is uniform, but hipcc does not see that: said so (readfirstlane), it stays in scalar registers — as
+// three VGPRs more the keep matrix no longer fits.  Scalar registers are as short: the two small fields share one, and
+// what a step derives from the grid and the batch is worked out again in every step (opaque copies) instead of being
+// carried round the transform's loop.
+__device__ __forceinline__ int res_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+struct ResDraw {   // wave 0's
+  int st;    // kk + 16 (dk + 1): kk = the next draw's place in the rotation (0 = the XCD's own counter, k = that of XCD
+             // x + k, 8 = none left), dk = the pending draw's place (kDrawDone: the arrival at the launch's end, -1: none)
+  int nxt;   // the next transform, -1 = none yet
+};
+// One step of wave 0, behind column block cb's wait: take the draw issued a block ago out of a[RP], issue the next into
+// a[RC].  A draw beyond the XCD's share moves on to the other XCDs' counters, one draw each in a fixed rotation that
+// goes on where the previous transform's steps stopped: at most 8 draws per transform (blocks 0..7), nothing waits for
+// another workgroup.  Block 8 posts the outcome for the other waves (read in phase 2, many barriers later) and, when
+// nothing is left, counts the workgroup as done; the workgroup that arrives last (block 9) returns the nine words to
+// zero for the next launch — no workgroup can draw after every one of them has given up.
+template <int RP, int RC>
+__device__ __forceinline__ void res_draw_step(ResDraw &D, int cb, unsigned *ctr, unsigned grid, unsigned batch, int tid, int *s_next) {
+  asm volatile("" : "+s"(grid), "+s"(batch));
+  const unsigned x = blockIdx.x & 7;
+  int kk = D.st & 15;
+  const int dk = (D.st >> 4) - 1;
+  int pend = -1;
+  if (dk >= 0) {
+    const unsigned d = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(unsigned, acc_read<RP>()));
+    if (dk < kDrawDone) {
+      // the first G / 8 positions of every XCD are the workgroups' first transforms (xcd_first): the counters start behind them
+      const unsigned xs = (x + dk) & 7, p = d + (grid >> 3);
+      const bool hit = p < xcd_share(xs, grid, batch);
+      if (hit) D.nxt = res_uniform((int)xcd_transform(xs, grid, p));
+      // On purpose, not left-over rotation state: only the XCD's own counter is drawn from again after a hit.  A hit on
+      // another XCD's counter moves on as a miss does — at most one draw per other XCD in a workgroup's life, which bounds
+      // every path and keeps the stolen tail to about one transform per workgroup (profiles/res16_balance.txt, section 1).
+      kk = hit && dk == 0 ? 0 : dk + 1;
+    } else if (d == grid - 1 && tid <= kDrawDone) {
+      // (a zero of its own: one shared with the keep matrix's initial zeros hipcc keeps in a[0:31] for the whole kernel)
+      unsigned zero = 0;
+      asm volatile("" : "+v"(zero));
+      __hip_atomic_store(ctr + tid * (kDrawStride / 4), zero, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+  if (cb < 8) {
+    if (D.nxt < 0 && kk < 8) {
+      if (tid == 0) res_draw_issue<RC>(ctr, (int)(((x + kk) & 7) * kDrawStride));
+      pend = kk;
+    }
+  } else if (cb == 8) {
+    if (tid == 0) *s_next = D.nxt;
+    if (D.nxt < 0) {
+      if (tid == 0) res_draw_issue<RC>(ctr, kDrawDone * kDrawStride);
+      pend = kDrawDone;
+    }
+  }
+  D.st = res_uniform(kk + 16 * (pend + 1));
+}
+
 // ---- loads interleaved with the arithmetic ---------------------------------------------------------
 // One wave per SIMD cannot afford to issue a block's 16 loads back to back: with the memory pipeline
 // saturated every load instruction then waits ~80 cycles for a queue slot, and nothing else runs on

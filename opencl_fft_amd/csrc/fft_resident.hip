@@ -215,12 +215,32 @@ __device__ __forceinline__ void res_phase2_r2c(const f32x32 (&K)[kVgprBlk], cons
 #else
 #define CLFA_RES16_TARGET
 #endif
-template <bool FWD, bool SCALE, bool R2C = false, bool C2R = false>
+// DYN (complex transforms, batch > grid, grid a multiple of 8: xcd_shared_ok): the shared assignment.  A workgroup's first
+// transform is today's (xcd_first); every further one is a position drawn from its XCD's counter `ctr` — today's
+// XCD-compact sequence, dealt to whichever of the XCD's workgroups asks next — and once that share is used up, one draw
+// from each other XCD's counter (res_draw_step, fft_res_regs.inc): the XCDs that finish early take over the tail of the
+// ones that run late (profiles/res16_balance.txt), every transform still runs exactly once and its arithmetic does not
+// depend on who runs it.  ctr: nine zeroed words kDrawStride bytes apart, zero again when the launch ends.
+// rec (null in every ordinary call): one ResRecord per workgroup, written as it exits.
+// Both are arguments of the complex instantiations only (X = unsigned *, ResRecord *); the packed real ones (X empty) keep
+// the arguments, and with them the code, they had without either.
+__device__ __forceinline__ unsigned *res_ctr_of() { return nullptr; }
+__device__ __forceinline__ unsigned *res_ctr_of(unsigned *ctr, ResRecord *) { return ctr; }
+__device__ __forceinline__ ResRecord *res_rec_of() { return nullptr; }
+__device__ __forceinline__ ResRecord *res_rec_of(unsigned *, ResRecord *rec) { return rec; }
+template <bool FWD, bool SCALE, bool R2C = false, bool C2R = false, bool DYN = false, class... X>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(224))) CLFA_RES16_TARGET void k_fft_res16(const cpx *data, cpx *out, cpx *__restrict__ slots,
                                                    const cpx *__restrict__ tabs_g, long batch,
-                                                   const cpx *__restrict__ w2_g = nullptr) {
+                                                   const cpx *__restrict__ w2_g, X... extra) {
+  static_assert(sizeof...(X) == ((R2C || C2R) ? 0 : 2), "ctr and rec: the complex transforms'");
+  [[maybe_unused]] unsigned *const ctr = res_ctr_of(extra...);
+  [[maybe_unused]] ResRecord *const rec = res_rec_of(extra...);
   static_assert(!R2C || (FWD && SCALE && !C2R), "the fused forward pair map");
   static_assert(!C2R || (!FWD && !SCALE), "the fused inverse pair map");
+  static_assert(!DYN || (!R2C && !C2R), "the packed real transforms keep the static assignment");
+  constexpr bool REC = !R2C && !C2R;
+  [[maybe_unused]] __shared__ int s_next;
+  [[maybe_unused]] unsigned done = 0;
   __shared__ __attribute__((aligned(16))) cpx s_tab[(R2C || C2R) ? kTabSizeR : kTabSize];
   __shared__ __attribute__((aligned(16))) cpx s_x[kXSize];
   __shared__ __attribute__((aligned(16))) char s_spill[256 * kSpillStride];
@@ -290,6 +310,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(224))) CLFA_RES
   for (int j = 0; j < kVgprBlk; j++) K[j] = 0.f;
   cpx v[16];
   long b = xcd_first(blockIdx.x, gridDim.x);   // XCD-compact assignment (fft_device.hpp)
+  [[maybe_unused]] ResDraw D{0, -1};
+  // (an opaque copy of the lane index, as in lane(): what is derived from it is recomputed where it is used)
+  [[maybe_unused]] auto draw_step = [&](auto RP, auto RC, int cb) {
+    return [&, cb]() {
+      if constexpr (DYN) {
+        int l = tid;
+        asm volatile("" : "+v"(l));
+        if (__builtin_amdgcn_readfirstlane(l) < 64)
+          res_draw_step<decltype(RP)::value, decltype(RC)::value>(D, cb, ctr, gridDim.x, (unsigned)batch, l, &s_next);
+      }
+    };
+  };
+  // the draws' registers: the first words of the landing zones' columns, in the order the zones fall empty (blocks 4 q,
+  // 4 q + 1: Z0; 4 q + 2, 4 q + 3: Z1)
+  constexpr int kD0 = 2 * kZone0, kD1 = 2 * kZone0 + 2, kD2 = 2 * kZone1, kD3 = 2 * kZone1 + 2;
   // blocks 0 and 1 of the first transform
   if constexpr (C2R) {
     // the first pair: block 7 -> Z0, block 8 mirrored -> landing registers, column 128 (lanes c = 0, mirrored rows) -> Z1
@@ -304,7 +339,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(224))) CLFA_RES
     res_load_land(data + b * (long)kN + 16, L0.voff);
   }
 #pragma unroll 1
-  for (; b < batch; b += gridDim.x) {
+  for (; b < batch;) {
+    if constexpr (REC) done++;
+    if constexpr (DYN) D.nxt = -1;
     const cpx *x = data + b * (long)kN;
     cpx *y = out + b * (long)kN;   // out == data: in place
     if constexpr (C2R) {
@@ -378,10 +415,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(224))) CLFA_RES
       // block 0 is in (or on its way to) Z0 and block 1 on its way to the landing registers
 #pragma unroll 1
       for (int cb = 0; cb < 12; cb += 4) {
+        if constexpr (DYN) {
+          res_phase1_block<FWD, kZone0, kZone1, true, 16, false>(v, lane(), x, cb, so, K, slot, s_tab, s_x, draw_step(ic<kD3>(), ic<kD0>(), cb));
+          res_phase1_block<FWD, -1, -1, true, 16, false>(v, lane(), x, cb + 1, so, K, slot, s_tab, s_x, draw_step(ic<kD0>(), ic<kD1>(), cb + 1));
+          res_phase1_block<FWD, kZone1, kZone0, true, 16, false>(v, lane(), x, cb + 2, so, K, slot, s_tab, s_x, draw_step(ic<kD1>(), ic<kD2>(), cb + 2));
+          res_phase1_block<FWD, -1, -1, true, 16, false>(v, lane(), x, cb + 3, so, K, slot, s_tab, s_x, draw_step(ic<kD2>(), ic<kD3>(), cb + 3));
+        } else {
         res_phase1_block<FWD, kZone0, kZone1, true>(v, lane(), x, cb, so, K, slot, s_tab, s_x);
         res_phase1_block<FWD, -1, -1, true>(v, lane(), x, cb + 1, so, K, slot, s_tab, s_x);
         res_phase1_block<FWD, kZone1, kZone0, true>(v, lane(), x, cb + 2, so, K, slot, s_tab, s_x);
         res_phase1_block<FWD, -1, -1, true>(v, lane(), x, cb + 3, so, K, slot, s_tab, s_x);
+        }
       }
       res_phase1_block<FWD, kZone0, kZone1, true>(v, lane(), x, 12, so, K, slot, s_tab, s_x);
       res_phase1_block<FWD, -1, -1, true>(v, lane(), x, 13, so, K, slot, s_tab, s_x);
@@ -390,34 +434,59 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(224))) CLFA_RES
       res_phase1_block<FWD, -1, -1, false, 0, !R2C>(v, lane(), x, 15, so, K, slot, s_tab, s_x);
     }
     // ---- phase 2 (the next transform's first loads ride along: clamped, they are issued unconditionally)
-    long bn = b + gridDim.x;
-    bn = bn < batch ? bn : batch - 1;
-    const cpx *xn = data + bn * (long)kN;
-    if constexpr (R2C) res_phase2_r2c(K, so, slot, lane, lane_m, xn, y, s_tab, s_c0);
-    else res_phase2_c2c<FWD, C2R>(v, K, so, lane, xn, y);
+    long bn;
+    if constexpr (DYN) {
+      // wave 0 posted the draws' outcome in column block 8; without a next transform the loads re-read this one
+      const int nx = __builtin_amdgcn_readfirstlane(s_next);
+      bn = nx < 0 ? b : (long)nx;
+      const cpx *xn = data + bn * (long)kN;
+      res_phase2_c2c<FWD, C2R>(v, K, so, lane, xn, y);
+      b = nx < 0 ? batch : bn;
+    } else {
+      bn = b + gridDim.x;
+      bn = bn < batch ? bn : batch - 1;
+      const cpx *xn = data + bn * (long)kN;
+      if constexpr (R2C) res_phase2_r2c(K, so, slot, lane, lane_m, xn, y, s_tab, s_c0);
+      else res_phase2_c2c<FWD, C2R>(v, K, so, lane, xn, y);
+      b += gridDim.x;
+    }
+  }
+  if constexpr (REC) {
+    if (rec && tid == 0) {
+      rec[blockIdx.x] = ResRecord{done, blockIdx.x & 7, (unsigned long long)wall_clock64()};
+    }
   }
 }
 
 namespace {
 
-// one workgroup per CU (fewer for small batches); every instantiation has the same signature
-using ResKernel = void (*)(const cpx *, cpx *, cpx *, const cpx *, long, const cpx *);
-hipError_t res_launch(ResKernel k, const cpx *data, cpx *out, cpx *slots, const cpx *tabs, const cpx *w2, long batch,
-                      const DeviceInfo &di, hipStream_t s) {
+// one workgroup per CU (fewer for small batches); X: the complex instantiations' counters and records
+int res_grid(long batch, const DeviceInfo &di) { return (int)(batch < di.num_cus ? batch : di.num_cus); }
+template <class... X>
+hipError_t res_launch(void (*k)(const cpx *, cpx *, cpx *, const cpx *, long, const cpx *, X...), const cpx *data, cpx *out,
+                      cpx *slots, const cpx *tabs, const cpx *w2, long batch, const DeviceInfo &di, hipStream_t s, X... extra) {
   if (batch <= 0) return hipSuccess;
-  const int grid = (int)(batch < di.num_cus ? batch : di.num_cus);
-  hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, s, data, out, slots, tabs, batch, w2);
+  hipLaunchKernelGGL(k, dim3(res_grid(batch, di)), dim3(256), 0, s, data, out, slots, tabs, batch, w2, extra...);
   return hipGetLastError();
 }
 
 }  // namespace
 
 hipError_t launch_fft_res16(bool fwd, bool scale, const cpx *data, cpx *out, cpx *slots, const cpx *tabs, long batch,
-                            const DeviceInfo &di, hipStream_t s) {
+                            const DeviceInfo &di, hipStream_t s, unsigned *ctr, ResRecord *rec) {
   if (batch <= 0) return hipSuccess;
   if (!fwd && scale) return hipErrorInvalidValue;
-  const ResKernel k = !fwd ? k_fft_res16<false, false> : scale ? k_fft_res16<true, true> : k_fft_res16<true, false>;
-  return res_launch(k, data, out, slots, tabs, nullptr, batch, di, s);
+  // the shared assignment where it applies (and the caller has counters for it), else the static one
+  if (ctr && xcd_shared_ok(batch, (unsigned)res_grid(batch, di))) {
+    const auto k = !fwd ? k_fft_res16<false, false, false, false, true, unsigned *, ResRecord *>
+                   : scale ? k_fft_res16<true, true, false, false, true, unsigned *, ResRecord *>
+                           : k_fft_res16<true, false, false, false, true, unsigned *, ResRecord *>;
+    return res_launch(k, data, out, slots, tabs, (const cpx *)nullptr, batch, di, s, ctr, rec);
+  }
+  const auto k = !fwd ? k_fft_res16<false, false, false, false, false, unsigned *, ResRecord *>
+                 : scale ? k_fft_res16<true, true, false, false, false, unsigned *, ResRecord *>
+                         : k_fft_res16<true, false, false, false, false, unsigned *, ResRecord *>;
+  return res_launch(k, data, out, slots, tabs, (const cpx *)nullptr, batch, di, s, (unsigned *)nullptr, rec);
 }
 
 hipError_t launch_crfft_res16(const cpx *data, cpx *out, cpx *slots, const cpx *tabs, const cpx *w2, long batch,

@@ -131,7 +131,8 @@ enum FftNeed : unsigned {
   kNeedHalf2x = 2,    // ... of the half-length runs: the n = 8192 lane tables + W_16384^t (logn 14), the n = 16384 ones (logn 15)
   kNeedFour = 4,      // the four-step tables
   kNeedRes16 = 8,     // the resident kernel's tables
-  kNeedFourWs = 16,   // a workspace of num_cus transforms (the resident kernel's slots are its first part)
+  kNeedFourWs = 16,   // a workspace of num_cus transforms (the resident kernel's slots are its first part;
+                      // a complex n = 65536 plan appends kRes16CtrBytes: the shared assignment's counters)
   kNeedBig = 32       // the big-N tables and a workspace of one chunk, and what the routes of the row transform need
 };
 constexpr unsigned route_needs(FftRoute r) {

@@ -71,8 +71,22 @@ constexpr int kRes16TabSize = 1792;
 // slots: 32 KiB per workgroup, grid = min(batch, CUs) workgroups (kRes16SlotBytes each)
 constexpr size_t kRes16SlotBytes = 32768;
 // out == data: in place (what every plan does); out != data: out of place (tools/res16_probe.hip times both; profiles/oop_r04.txt)
+// ctr (optional): the counters of the shared assignment (fft_resident.hip, k_fft_res16<..., DYN>), kRes16CtrBytes that
+// were zero before the first launch; every launch leaves them zero.  Like the slots they serve one launch at a time.
+// Without them, and for batches where xcd_shared_ok() (fft_device.hpp) says no, the static assignment runs.
+// rec (optional, a measurement aid): one ResRecord per workgroup, written as the workgroup exits.
+constexpr size_t kRes16CtrBytes = 9 * 128;
+// a plan keeps one line of kRes16GuardWord in front of its counters and one behind them: a counter access that strays shows
+// there (clfa_fft_balance_counters)
+constexpr size_t kRes16GuardBytes = 128;
+constexpr unsigned kRes16GuardWord = 0xA5A5A5A5u;
+struct alignas(16) ResRecord {
+  unsigned count;              // transforms the workgroup processed
+  unsigned xcd;                // workgroup index % 8
+  unsigned long long stamp;    // wall clock at its exit
+};
 hipError_t launch_fft_res16(bool fwd, bool scale, const cpx *data, cpx *out, cpx *slots, const cpx *tabs, long batch,
-                            const DeviceInfo &di, hipStream_t s);
+                            const DeviceInfo &di, hipStream_t s, unsigned *ctr = nullptr, ResRecord *rec = nullptr);
 // packed real transforms of size 131072, forward: the same kernel with the reference's pair map inside its second
 // phase (w2 = the plan's pair twiddles, 65536 entries) — one HBM pass instead of the transform + k_r2c_pack
 hipError_t launch_rfft_res16(const cpx *data, cpx *out, cpx *slots, const cpx *tabs, const cpx *w2, long batch,

@@ -8,6 +8,8 @@ from ._base import CL_INVALID_VALUE, CL_SUCCESS, _Object, _host, _pkg, _ptr_stre
 from ._lib import check
 
 PI = 3.141592653589793  # cl_fft.h:24
+# one workgroup's record of the resident n = 65536 kernel (clfa_fft_balance_read)
+BALANCE_RECORD = np.dtype([("count", np.uint32), ("xcd", np.uint32), ("stamp", np.uint64)])
 
 
 def cl_error_string(err):
@@ -96,6 +98,31 @@ class _Plan(_Object):
         ps, stream = _ptr_stream(src, stream)
         pd, _ = _ptr_stream(dst, stream)
         return _pkg.lib().clfa_fft_exec_dev_oop(self._h, ps, pd, batch, stream)
+
+    def balance_record(self, on=True):
+        """measurement aid (complex n = 65536 plans): let every later launch of the resident kernel leave one record
+        per workgroup (clfa_fft_balance_record); blocks"""
+        return _pkg.lib().clfa_fft_balance_record(self._h, int(bool(on)))
+
+    def balance_read(self):
+        """the records of the plan's last launch, in workgroup order (workgroup i runs on XCD i % 8): a structured array
+        with the fields count (transforms processed), xcd (workgroup index % 8) and stamp (100 MHz wall clock at
+        exit); waits for the device.  None if nothing is being recorded."""
+        out = np.zeros(4096, dtype=BALANCE_RECORD)
+        n = C.c_int(0)
+        if _pkg.lib().clfa_fft_balance_read(self._h, out.ctypes.data, len(out), C.byref(n)) != CL_SUCCESS:
+            return None
+        return out[:n.value].copy()
+
+    def balance_counters(self):
+        """test aid (complex n = 65536 plans): (guard line before, the nine counter lines as a (9, 32) array, guard line
+        after) of the shared assignment's counters in the plan's workspace, uint32 words (clfa_fft_balance_counters);
+        waits for the device.  None for any other plan."""
+        out = np.zeros(352, dtype=np.uint32)
+        n = C.c_int(0)
+        if _pkg.lib().clfa_fft_balance_counters(self._h, out.ctypes.data, len(out), C.byref(n)) != CL_SUCCESS or n.value != len(out):
+            return None
+        return out[:32].copy(), out[32:320].reshape(9, 32).copy(), out[320:].copy()
 
 
 class Clcfft(_Plan):

@@ -5,6 +5,8 @@
 //   PROBE_DELTA=1  dst = src + delta inside ONE allocation: which address relation of the two streams matters?
 //   PROBE_OOP=1    in place against out of place, then ping-pong A -> B, B -> A (PROBE_PP=1: the ping-pong part only)
 //   (none)         forward, then forward / inverse alternating on random data with real tables, per launch after an idle period
+//   PROBE_STATIC=1 with any of them: the static transform assignment instead of the library's choice (the shared one
+//                  wherever xcd_shared_ok() allows it, as launch_fft_res16 decides)
 // The experiments that needed code INSIDE the kernel (parts left out, phase stamps, grid barrier, time slots, assignment
 // sweeps) ended with the commit named in profiles/HISTORY.md, "The resident kernel's probe"; their results are on record there.
 #include "../opencl_fft_amd/csrc/fft_resident.hip"
@@ -44,8 +46,17 @@ template <class F> static float time_launches(int warm, int reps, F launch) {
   return ms / reps;
 }
 
+// the shared assignment's counters (kRes16CtrBytes, zeroed once: every launch leaves them zero); null = PROBE_STATIC
+static unsigned *g_ctr = nullptr;
+
+// the complex instantiations carry the counters and the record pointer (null here) as arguments
 template <bool FWD, bool SCALE> static void fft(int grid, const cpx *src, cpx *dst, cpx *slots, const cpx *tabs, long batch) {
-  hipLaunchKernelGGL((k_fft_res16<FWD, SCALE>), dim3(grid), dim3(256), 0, 0, src, dst, slots, tabs, batch, (const cpx *)nullptr);
+  if (g_ctr && xcd_shared_ok(batch, (unsigned)grid))
+    hipLaunchKernelGGL((k_fft_res16<FWD, SCALE, false, false, true, unsigned *, ResRecord *>), dim3(grid), dim3(256), 0, 0, src, dst, slots,
+                       tabs, batch, (const cpx *)nullptr, g_ctr, (ResRecord *)nullptr);
+  else
+    hipLaunchKernelGGL((k_fft_res16<FWD, SCALE, false, false, false, unsigned *, ResRecord *>), dim3(grid), dim3(256), 0, 0, src, dst, slots,
+                       tabs, batch, (const cpx *)nullptr, (unsigned *)nullptr, (ResRecord *)nullptr);
 }
 
 static void report(const char *name, float ms, long batch) {
@@ -62,10 +73,15 @@ int main() {
   CK(hipMalloc(&slots, (size_t)cus * 32768));
   CK(hipMalloc(&tabs, 1792 * 8));
   CK(hipMemset(data, 0, batch * 65536 * 8));
+  if (!getenv("PROBE_STATIC")) {
+    CK(hipMalloc(&g_ctr, kRes16CtrBytes));
+    CK(hipMemset(g_ctr, 0, kRes16CtrBytes));
+    CK(hipDeviceSynchronize());
+  }
   std::vector<cpx> t(1792);
   for (int i = 0; i < 1792; i++) t[i] = mk((float)cos(i * 0.001), (float)sin(i * 0.001));   // unit-modulus stand-ins: timing only
   CK(hipMemcpy(tabs, t.data(), 1792 * 8, hipMemcpyHostToDevice));
-  printf("k_fft_res16 probe: %ld transforms, %d workgroups\n", batch, cus);
+  printf("k_fft_res16 probe: %ld transforms, %d workgroups, %s assignment\n", batch, cus, g_ctr ? "shared" : "static");
   if (getenv("PROBE_GRID")) {
     for (int round = 0; round < 3; round++)
       for (int g : {256, 248, 240, 224, 208, 192, 160, 128}) {
