@@ -6,6 +6,9 @@
 // compute fallback exists: without a HIP device every constructor reports CL_DEVICE_NOT_FOUND and every exec call fails.
 #include <utility>
 
+#include "fft_launch.hpp"
+#include "fft_route.hpp"
+#include "fft_tables.hpp"
 #include "host.hpp"
 
 using namespace clfa;

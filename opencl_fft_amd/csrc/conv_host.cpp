@@ -1,7 +1,12 @@
 // conv_host.cpp — C ABI of the convolutions (see include/clfft_amd.h): Clpconv and its multi-block route, Cldconv, and
 // the convolution matrix.  Shared plumbing: host.hpp, where the staged blocking form lives (staged_call); the rules of a
 // call's arrays: overlap.hpp.  Every object stages its blocking calls in members in1, in2, out and its responses in ir.
+#include "dconv_launch.hpp"
+#include "fft_launch.hpp"
+#include "fft_route.hpp"
+#include "fft_tables.hpp"
 #include "host.hpp"
+#include "pconv_launch.hpp"
 
 using namespace clfa;
 

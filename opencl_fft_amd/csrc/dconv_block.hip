@@ -1,7 +1,7 @@
 // dconv_block.hip — direct convolution, one block per launch (k_dconv_block); restates cl_dconv.cpp:32-43 (kernel) and
 // cl_dconv.cpp:109-148 (host side).  Whole signals for many channels: dconv_blocks.hip.
 #include "handover.hpp"
-#include "internal.hpp"
+#include "dconv_launch.hpp"
 
 namespace clfa {
 

@@ -19,7 +19,7 @@
 // the chunks' sums added in ascending order, then the segments' in ascending order.  Nothing in it depends on which tile
 // or lane an output lands in or on R, so results do not depend on nblocks, on the split into calls and sub-batches, or
 // on the R the launcher picks.  No atomics.
-#include "internal.hpp"
+#include "dconv_launch.hpp"
 #include "pconv_device.hpp"
 
 namespace clfa {

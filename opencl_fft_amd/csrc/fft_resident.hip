@@ -63,7 +63,8 @@
 #include <type_traits>
 #include <utility>
 
-#include "internal.hpp"
+#include "fft_device.hpp"
+#include "fft_launch.hpp"
 
 #include "fft_res_regs.inc"
 #include "fft_res_blocks.inc"

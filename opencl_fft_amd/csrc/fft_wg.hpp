@@ -1,7 +1,7 @@
 // fft_wg.hpp — workgroup-level pieces shared by the FFT, STFT and convolution kernels (fft_kernels.hip, stft_kernels.hip,
 // pconv_chain.hip, pconv_fused.inc, pconv_coop.hip, pconv_blocks.hip, pconv_matrix.hip): the LDS-exchanged pass chains and their geometry.
 #pragma once
-#include "internal.hpp"
+#include "fft_device.hpp"
 
 namespace clfa {
 

@@ -3,7 +3,7 @@
 // workgroup ever waits for another one: nothing spins.  (An extension: the reference sums with CAS atomics instead,
 // cl_conv_kernels.h:102-118, cl_dconv.cpp:32-43.)  tools/check_isa.py --handover audits the compiled form of both kernels.
 #pragma once
-#include "internal.hpp"
+#include "cpx.hpp"
 
 namespace clfa {
 

@@ -1,8 +1,10 @@
 // host.hpp — plumbing shared by the host side of the C ABI (clfft_amd.cpp: FFT plans, conv_host.cpp: the
 // convolutions, stft_host.cpp: Stft, pvoc_host.cpp: Pvoc): error mapping, device and stream handling, owned device /
-// pinned buffers, numeric switches of the environment, the exact host tables, the prelude / creation / destruction every
-// object shares, and the staged blocking form of a call (staged_call) over the description of its arrays (HostArray; its
-// rules: overlap.hpp).  Everything here is inline and hidden (-fvisibility=hidden): nothing becomes an exported symbol.
+// pinned buffers, numeric switches of the environment, the exact host tables every object needs (the FFT-only ones:
+// fft_tables.hpp), the prelude / creation / destruction every object shares, and the staged blocking form of a call
+// (staged_call) over the description of its arrays (HostArray; its rules: overlap.hpp).  Each *_host.cpp adds the launch
+// headers of its own kernel families (fft_launch.hpp, pconv_launch.hpp, dconv_launch.hpp, stft_launch.hpp, pvoc_launch.hpp).
+// Everything here is inline and hidden (-fvisibility=hidden): nothing becomes an exported symbol.
 #pragma once
 #include "../../include/clfft_amd.h"
 
@@ -17,7 +19,8 @@
 #include <new>
 #include <vector>
 
-#include "internal.hpp"
+#include "cpx.hpp"
+#include "device_info.hpp"
 #include "overlap.hpp"
 
 namespace clfa {
@@ -139,76 +142,6 @@ inline void fill_w2(std::vector<cpx> &v, int m, float sign) {
     v[i].x = (float)cos(i * kPI / m);
     v[i].y = sign * (float)sin(i * kPI / m);
   }
-}
-
-// host tables of the four-step kernel: [half N1 | half N2 | lo: W_n^k, k < 2^loglo | hi: W_n^(k 2^loglo)]
-inline void fill_fourstep_tables(std::vector<cpx> &all, int logn) {
-  int l1, l2, llo;
-  fourstep_split(logn, &l1, &l2, &llo);
-  const int n = 1 << logn, n1 = 1 << l1, n2 = 1 << l2, lo = 1 << llo, hi = n >> llo;
-  std::vector<cpx> part;
-  all.clear();
-  fill_twiddle(part, n1 / 2, n1, 1, -1.f);
-  all.insert(all.end(), part.begin(), part.begin() + n1 / 2);
-  fill_twiddle(part, n2 / 2, n2, 1, -1.f);
-  all.insert(all.end(), part.begin(), part.begin() + n2 / 2);
-  fill_twiddle(part, lo, n, 1, -1.f);
-  all.insert(all.end(), part.begin(), part.begin() + lo);
-  fill_twiddle(part, hi, n, lo, -1.f);
-  all.insert(all.end(), part.begin(), part.begin() + hi);
-}
-
-// lane-addressed tables of the two-level LDS transforms (internal.hpp, kLane13Size / kLane14Size), every value rounded
-// from double: [W_256^(j t), j, t < 16 | W_4096^(2^k j mod 4096), k < 4, j < 256 | tail].  The tail: logn 13 W_8192^t,
-// t < 512 — with tail2x followed by W_16384^t, t < 512, the radix-2 step's lane constants of k_cfft_2x / k_rfft_2x<13>;
-// logn 14 W_16384^(m t), m = 1, 2, 3, t < 1024
-inline void fill_lane_tables(std::vector<cpx> &h, int logn, bool tail2x) {
-  h.clear();
-  auto w = [&](long k, long n) { h.push_back(mk((float)cos(k * 2 * kPI / n), -(float)sin(k * 2 * kPI / n))); };
-  for (int j = 0; j < 16; j++)
-    for (int t = 0; t < 16; t++) w(j * t, 256);
-  for (int k = 0; k < 4; k++)
-    for (int j = 0; j < 256; j++) w(((1 << k) * j) & 4095, 4096);
-  if (logn == kLds14Log) {
-    for (int m = 1; m <= 3; m++)
-      for (int t = 0; t < 1024; t++) w(m * t, 16384);
-    return;
-  }
-  for (int t = 0; t < 512; t++) w(t, 8192);
-  for (int t = 0; tail2x && t < 512; t++) w(t, 16384);
-}
-
-// host tables of the resident n = 65536 kernel (internal.hpp, kRes16TabSize), each value rounded from
-// double like the reference's table (cl_fft.cpp:89-90)
-inline void fill_res16_tables(std::vector<cpx> &all) {
-  all.clear();
-  std::vector<cpx> part;
-  for (int t = 0; t < 16; t++)
-    for (int j = 0; j < 16; j++) all.push_back(mk((float)cos((t * j) * 2 * kPI / 256), -(float)sin((t * j) * 2 * kPI / 256)));
-  fill_twiddle(part, 256, 65536, 1, -1.f);
-  all.insert(all.end(), part.begin(), part.begin() + 256);
-  fill_twiddle(part, 256, 256, 1, -1.f);
-  all.insert(all.end(), part.begin(), part.begin() + 256);
-  for (int m = 1; m <= 8; m *= 2)
-    for (int k = 0; k < 256; k++) {
-      const int idx = (m * k) & 4095;
-      all.push_back(mk((float)cos(idx * 2 * kPI / 4096), -(float)sin(idx * 2 * kPI / 4096)));
-    }
-}
-
-// host tables of n = 2^17 .. 2^24 = N1 x N2 (internal.hpp, launch_fft_big): [half N1 | W_n^e0 | W_n^(128 e1) |
-// W_n^(16384 e2)], e = e0 + 128 e1 + 16384 e2 (big_tw(), fft_big.inc)
-inline void fill_big_tables(std::vector<cpx> &all, int n, int n1) {
-  std::vector<cpx> part;
-  all.clear();
-  fill_twiddle(part, n1 / 2, n1, 1, -1.f);
-  all.insert(all.end(), part.begin(), part.begin() + n1 / 2);
-  fill_twiddle(part, 128, n, 1, -1.f);
-  all.insert(all.end(), part.begin(), part.begin() + 128);
-  fill_twiddle(part, 128, n, 128, -1.f);
-  all.insert(all.end(), part.begin(), part.begin() + 128);
-  fill_twiddle(part, n / 16384, n, 16384, -1.f);
-  all.insert(all.end(), part.begin(), part.begin() + n / 16384);
 }
 
 // Batches that do not fit a workspace run in chunks.  chunk_items: as many items of `per` bytes as fit `cap` bytes, at

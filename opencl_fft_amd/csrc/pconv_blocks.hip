@@ -15,6 +15,7 @@
 // Every output bin is one accumulator summed over p = 0, 1, ... nparts - 1 with the products of k_pconv_mac, whatever
 // the tile, the sub-batch or the split of the signal into calls: results are bit-identical across splits.
 #include "pconv_device.hpp"
+#include "pconv_launch.hpp"
 
 namespace clfa {
 

@@ -22,6 +22,7 @@
 #include <cstdlib>
 
 #include "pconv_device.hpp"
+#include "pconv_launch.hpp"
 
 namespace clfa {
 

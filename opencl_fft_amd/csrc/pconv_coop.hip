@@ -5,6 +5,7 @@
 
 #include "handover.hpp"
 #include "pconv_device.hpp"
+#include "pconv_launch.hpp"
 
 namespace clfa {
 

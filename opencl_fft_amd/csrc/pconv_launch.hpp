@@ -1,0 +1,124 @@
+// pconv_launch.hpp — the launchers of the partitioned convolution (pconv_chain.hip, pconv_coop.hip, pconv_blocks.hip,
+// pconv_matrix.hip) as conv_host.cpp sees them: PconvGeom and the per-block launches, the cooperative and the fused block,
+// the many-block sub-batch (PconvBlocks), the convolution matrix (PconvMatrixArgs) and the ends of the composed chain.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "cpx.hpp"
+#include "device_info.hpp"
+
+namespace clfa {
+
+// ---- partitioned convolution --------------------------------------------------
+struct PconvGeom {
+  int logb;      // log2(bins), bins = pts
+  int bins;
+  int nparts;
+  int channels;
+};
+// input block (channels x pts floats) -> zero-padded 2*pts real FFT -> packed
+// spectrum frame `frame` of ring (channels x nparts x bins complex).  Unscaled,
+// reference pack (cl_conv_kernels.h:46-85).
+// in_b / ring_b / frame_b: optional second input of a time-varying block, transformed by the same launch
+hipError_t launch_pconv_forward(const PconvGeom &g, const float *in, long in_stride, cpx *ring, int frame,
+                                const cpx *half, const cpx *w2f, hipStream_t s, const float *in_b = nullptr,
+                                cpx *ring_b = nullptr, int frame_b = 0);
+// acc = sum_p A[(wp+p)%nparts] (.) B[p]  (cl_conv_kernels.h:102-118), acc: channels x bins complex
+int pconv_mac_split(const PconvGeom &g);   // partial accumulators the MAC writes (acc must hold that many)
+// reduce = false leaves the pconv_mac_split() partial sums for launch_pconv_inverse(nsplit) to add up
+hipError_t launch_pconv_mac(const PconvGeom &g, const cpx *ringA, const cpx *ringB, int wp, cpx *acc,
+                            hipStream_t s, bool reduce = true);
+// acc -> c2r -> inverse FFT -> overlap-add (cl_conv_kernels.h:87-100,120-124); out channels x pts,
+// tail channels x pts (unscaled second half kept for the next block)
+hipError_t launch_pconv_inverse(const PconvGeom &g, const cpx *acc, float *tail, float *out,
+                                const cpx *half, const cpx *w2i, hipStream_t s, int nsplit = 1);
+// one launch per block (forward + MAC + inverse in one workgroup per channel); used when
+// one launch per block for a FEW channels (pconv_coop.hip, k_pconv_coop): 2^logs bin slices x sparts segments of
+// the partition axis per channel (logs = -1: the kernel does not apply); xacc: channels x sparts x bins complex
+// (hand-over of the accumulator slices), counters: one zero-initialised unsigned per channel (returned to zero by
+// every launch)
+struct PconvCoop {
+  int logs, sparts;
+};
+PconvCoop pconv_coop_plan(const PconvGeom &g, const DeviceInfo &di);
+hipError_t launch_pconv_coop(const PconvGeom &g, PconvCoop c, const float *in1, const float *in2, cpx *ringA, cpx *ringB,
+                             float *tail, float *out, int frame1, int frame2, int wp, const cpx *half, const cpx *w2f,
+                             const cpx *w2i, cpx *xacc, unsigned *counters, int num_cus, hipStream_t s);
+// pconv_fused_ok(): bins 512..4096 and enough channels to fill the chip
+bool pconv_fused_ok(const PconvGeom &g, const DeviceInfo &di);
+hipError_t launch_pconv_fused(const PconvGeom &g, const float *in1, const float *in2, cpx *ringA, cpx *ringB,
+                              float *tail, float *out, int frame1, int frame2, int wp, const cpx *half,
+                              const cpx *w2f, const cpx *w2i, hipStream_t s, bool deep = false);   // deep: fewer channels than CUs
+// K consecutive blocks of every channel in four launches (pconv_blocks.hip), bins 32..4096: in1 / in2 / out point at
+// block 0 of the sub-batch (row c at c * stride floats); X, Y (and XB, time-varying) are channels x cap x bins complex
+// workspaces, tail_ws channels x bins floats.  w / w2: the object's wp / wp2 before the sub-batch; K <= cap, and
+// K <= nparts when in2 is set.  The rings and the tail are written only by the last launch, after every read.
+struct PconvBlocks {
+  PconvGeom g;
+  int K = 0, cap = 0, w = 0, w2 = 0;
+  int kt = 4;     // outputs per MAC tile: pconv_blocks_tile()
+  int run = 8;    // blocks per inverse run
+  const float *in1 = nullptr, *in2 = nullptr;
+  long in_stride = 0, out_stride = 0;
+  float *out = nullptr;
+  int aligned_in = 1, aligned_out = 1;   // every row start 8-byte aligned
+  cpx *ringA = nullptr, *ringB = nullptr;
+  float *tail = nullptr;
+  cpx *X = nullptr, *XB = nullptr, *Y = nullptr;
+  float *tail_ws = nullptr;
+  const cpx *half = nullptr, *w2f = nullptr, *w2i = nullptr;
+};
+int pconv_blocks_tile(const PconvGeom &g, const DeviceInfo &di);
+hipError_t launch_pconv_blocks(const PconvBlocks &a, hipStream_t s);
+constexpr int kPconvBlocksMinLog = 5, kPconvBlocksMaxLog = 12;
+// the forward / inverse launches of a sub-batch on their own (pconv_blocks.hip), for the convolution matrix
+hipError_t launch_pconvb_forward(int logb, const float *in, long in_stride, cpx *X, int K, int cap, int channels, int aligned,
+                                 const cpx *half, const cpx *w2f, hipStream_t s);
+hipError_t launch_pconvb_inverse(int logb, const cpx *Y, const float *tail, float *tail_out, float *out, long out_stride, int K,
+                                 int cap, int R, int channels, int aligned, const cpx *half, const cpx *w2i, hipStream_t s);
+// Convolution matrix (pconv_matrix.hip): y_o = sum_i x_i * h_{o,i}, K consecutive blocks of every input per sub-batch.
+// Responses H: outputs x inputs x nparts x bins complex, partition q of row (o, i) at ((o * inputs + i) * nparts + q) * bins.
+// The MAC walks the reduction sequence r = i * nparts + p (p = 0 pairs with partition nparts - 1, the oldest input frame)
+// in `segs` fixed segments [r_s, r_{s+1}), r_s = floor(s * inputs * nparts / segs); segment 0 writes Y, segment s > 0 the
+// partial P[s - 1]; with segs > 1 a reduce launch adds them to Y in ascending s.
+struct PconvMatrixPlan {
+  int kt = 4;     // outputs per MAC tile (4 or 16)
+  int segs = 1;   // segments of the reduction over (input, partition)
+};
+struct PconvMatrixArgs {
+  int logb = 0, bins = 0, nparts = 0, inputs = 0, outputs = 0;
+  PconvMatrixPlan plan;
+  int K = 0, cap = 0, w = 0;
+  int run = 8;    // blocks per inverse run
+  const float *in = nullptr;
+  float *out = nullptr;
+  long in_stride = 0, out_stride = 0;
+  int aligned_in = 1, aligned_out = 1;   // every row start 8-byte aligned
+  const cpx *H = nullptr;
+  cpx *ringA = nullptr;                  // inputs x nparts x bins
+  float *tail = nullptr;                 // outputs x bins
+  cpx *X = nullptr, *Y = nullptr, *P = nullptr;   // inputs x cap, outputs x cap, (segs - 1) x outputs x cap frames
+  float *tail_ws = nullptr;              // outputs x bins
+  const cpx *half = nullptr, *w2f = nullptr, *w2i = nullptr;
+  // a timed crossfade to a second response set (launch_pconv_matrix_fade / _prime): the set, its tails and workspaces
+  const cpx *H2 = nullptr;
+  float *tail2 = nullptr;                // outputs x bins
+  cpx *Y2 = nullptr, *P2 = nullptr;      // as Y, P
+  float *tail_ws2 = nullptr;             // outputs x bins
+  float *mix = nullptr;                  // the second path's samples: outputs rows of cap * bins floats
+  long fade_pos = 0, fade_len = 0;       // blocks of the fade before this sub-batch, blocks of the whole fade
+  bool two_mac = false;                  // two launches of the plain MAC instead of the two-response one
+};
+PconvMatrixPlan pconv_matrix_plan(int bins, int nparts, int inputs, int outputs, const DeviceInfo &di);
+hipError_t launch_pconv_matrix(const PconvMatrixArgs &a, hipStream_t s);
+// A sub-batch inside a fade (K <= fade_len - fade_pos): both paths over the shared ring, the second one's samples mixed
+// into `out` with g(n) = (float)n / (float)(fade_len * bins), n counted from the fade's first sample; ring, tail and tail2
+// committed.  _prime: tail2 = the second half of the block before the next one under H2, from ring A alone.
+hipError_t launch_pconv_matrix_fade(const PconvMatrixArgs &a, hipStream_t s);
+hipError_t launch_pconv_matrix_prime(const PconvMatrixArgs &a, hipStream_t s);
+constexpr int kPconvMaxLogBins = 15;   // pts up to 32768 (the reference harness' largest, csound/tests.py:13)
+// ends of the composed chain used when bins exceed the LDS FFT sizes
+hipError_t launch_pconv_pad(const float *in, long in_stride, cpx *work, int bins, int channels, hipStream_t s);
+hipError_t launch_pconv_olap(const float *work, float *tail, float *out, int bins, int channels, hipStream_t s);
+
+}  // namespace clfa

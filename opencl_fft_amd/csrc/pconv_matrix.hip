@@ -21,6 +21,7 @@
 // a + g * (b - a) in place, and the commit also takes the second tails.  launch_pconv_matrix_prime starts the second path's
 // tails at the push: the block before the next one under H2, whose nparts input frames are exactly what ring A holds.
 #include "pconv_device.hpp"
+#include "pconv_launch.hpp"
 
 namespace clfa {
 

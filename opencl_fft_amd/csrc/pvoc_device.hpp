@@ -11,7 +11,7 @@
 //   pvoc_scan              the chunked scan that turns the per-chunk sums of phase increments into the bases the
 //                          chunks start from (k_pvoc_scan on uint32 words, k_adsyn_scan on uint64 ones)
 #pragma once
-#include "internal.hpp"
+#include "pvoc_launch.hpp"
 
 namespace clfa {
 

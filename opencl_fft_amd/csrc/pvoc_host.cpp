@@ -2,7 +2,9 @@
 // The object and its states come first; then what every call shares — the description of its arrays (PvocArray: host.hpp's
 // HostArray, checked by arrays_ok, staged by staged_call), the device form, and pvoc_call, which puts a call's results in
 // the header's order — then one function per family of calls: scalar rules, array list, per-frame value rule, launch.
+#include "fft_route.hpp"
 #include "host.hpp"
+#include "pvoc_launch.hpp"
 
 using namespace clfa;
 

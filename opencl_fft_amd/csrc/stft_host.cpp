@@ -1,6 +1,8 @@
 // stft_host.cpp — C ABI of the short-time transforms (see include/clfft_amd.h): Stft.  Shared plumbing: host.hpp, where
 // the staged blocking form lives; the rules of a call's arrays: overlap.hpp.
+#include "fft_route.hpp"
 #include "host.hpp"
+#include "stft_launch.hpp"
 #include "stft_plan.hpp"
 
 using namespace clfa;

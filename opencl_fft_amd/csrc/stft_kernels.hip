@@ -11,6 +11,7 @@
 // holds FPW = LdsGeom::FPW frames at once; global accesses go in chunk order (element tid + WG e of the FPW * n
 // elements), so a wave reads runs of whole frames.
 #include "fft_wg.hpp"
+#include "stft_launch.hpp"
 #include "stft_plan.hpp"
 
 namespace clfa {

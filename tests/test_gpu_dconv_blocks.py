@@ -2,7 +2,7 @@
 oracle.Dconv per channel, block by block; bit-identity across splits, sub-batches, streams, graph replay and the
 single-block calls; the state a call leaves; the two-input "loop" route; errors; accuracy against float64.
 
-The kernel's own constants (opencl_fft_amd/csrc/internal.hpp, dconv_blocks.hip): the tap chunk kDconvbChunk = 256 (taps
+The kernel's own constants (opencl_fft_amd/csrc/dconv_launch.hpp, dconv_blocks.hip): the tap chunk kDconvbChunk = 256 (taps
 per staged window and per partial accumulator), R = 2 or 8 outputs per lane (CLFA_DCONV_BLOCKS_R forces one; the launcher
 picks by the size of the launch), the tile 256 R = 512 or 2048 outputs per workgroup, and the segment length kDconvbSeg =
 4096 taps (longer responses: partial sums per segment, k_dconvb_reduce)."""
