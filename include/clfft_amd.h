@@ -60,6 +60,7 @@ typedef struct clfa_pconv clfa_pconv; /* Clpconv object, `channels` independent 
 typedef struct clfa_dconv clfa_dconv; /* Cldconv object */
 typedef struct clfa_stft clfa_stft;   /* short-time analysis / overlap-add synthesis plan (extension) */
 typedef struct clfa_pconv_matrix clfa_pconv_matrix; /* convolution matrix: inputs mixed into outputs (extension) */
+typedef struct clfa_nupconv clfa_nupconv;           /* non-uniformly partitioned convolution, two levels (extension) */
 typedef struct clfa_pvoc clfa_pvoc;   /* phase vocoder on the clfa_stft spectra: (amp, freq) frames both ways (extension) */
 
 /* ---- library / devices ---------------------------------------------------- */
@@ -986,6 +987,67 @@ CLFA_API size_t clfa_pconv_matrix_state_bytes(const clfa_pconv_matrix *m);
 CLFA_API size_t clfa_pconv_matrix_workspace_bytes(const clfa_pconv_matrix *m);
 /* "k_pconvm_mac" ("" for a failed object) */
 CLFA_API const char *clfa_pconv_matrix_kernel_name(const clfa_pconv_matrix *m);
+
+/* ---- non-uniformly partitioned convolution (extension): long responses at low latency ---------------------------------
+ * Two levels, static responses, `channels` independent instances.  pts0 and pts1 are powers of two with
+ * 32 <= pts0 < pts1 <= 4096, m = pts1 / pts0, and cvs >= 3 * pts1.  The head covers h[0 : 2*pts1) in 2m partitions of
+ * pts0; the tail covers h[2*pts1 : 2*pts1 + n1*pts1), n1 = floor((cvs - 2*pts1) / pts1), in partitions of pts1; the
+ * remainder of cvs is ignored (the reference's floor).  Anything else: CLFA_INVALID_VALUE from create, the offending
+ * parameter named in the log; the arguments are checked before the device is looked for.
+ *
+ * Definition, bit for bit.  For a channel with input stream x, counted from creation or the last reset: let yh be what
+ * Clpconv(2*pts1, pts0) holding h[:2*pts1] returns for x through clfa_pconv_process_blocks_dev, and yt what
+ * Clpconv(cvs - 2*pts1, pts1) holding h[2*pts1:] returns for x the same way.  Then y[n] = yh[n] + yt[n - 2*pts1], one
+ * float32 addition with the head as its first operand; yt[k] = +0 for k < 0, and the addition is performed there too.
+ * Both levels take the blocks route's arithmetic whatever the call's length (forward transform, one accumulator per bin
+ * over the partitions ascending, inverse transform and overlap-add): the output bits do not depend on how the stream is
+ * cut into calls, and a call of K blocks equals K calls of one block, in output and in the state it leaves.  The packed
+ * DC / Nyquist rule of the library (products at half gain) applies per level at that level's block size, so the result is
+ * NEITHER bit-equal NOR rounding-equal to Clpconv(cvs, pts0): it differs from it in bins 0 and pts of every level's
+ * products, as two Clpconv objects of different pts differ from each other.
+ *
+ * Schedule.  c = head blocks since reset (position()), s = c mod m its phase.  Tail block j (input x[j*pts1 : (j+1)*pts1))
+ * is complete after head block (j+1)*m - 1; its spectrum is taken at c = (j+1)*m; head block c in [(j+1)*m, (j+2)*m)
+ * computes slice s of its bins (16-byte items [s*pts0/2, (s+1)*pts0/2) of two bins) over all n1 partitions; after slice
+ * m - 1 it is inverse-transformed and overlap-added; its pts1 samples are mixed into head blocks [(j+2)*m, (j+3)*m).  Per
+ * head block that is 2m partitions of pts0 head bins plus n1 partitions of pts0 tail bins, one forward transform of pts1
+ * at phase 0 and one inverse at phase m - 1: no phase carries a whole tail block.  In a call of many blocks the head runs
+ * through the blocks route over the whole call and the tail's slices between two period boundaries are one launch: the
+ * number of launches is a constant plus a constant per boundary crossed.
+ *
+ * process_dev: rows as clfa_pconv_process_blocks_dev (row c of `in` at in + c*in_stride floats, nblocks*pts0 floats; any
+ * 4-byte aligned address, strides >= nblocks*pts0); nblocks == 0 succeeds and does nothing.  A bad argument, or an out
+ * that overlaps in even partly: CLFA_INVALID_VALUE, the state untouched.  A call (or a reset) on a capturing stream:
+ * CLFA_INVALID_OPERATION — the phase lives on the host.  One object runs on one stream at a time.  convolution: the same
+ * on packed host rows, blocking.
+ * push_ir / push_ir_dev: rows of at least 2*pts1 + n1*pts1 floats (e.g. cvs), both levels' responses written in stream
+ * order.  At position() % m == 0 a push is exact: at c = P*m it equals pushing the head object of the definition before
+ * its block c and the tail object before its block P - 1 (block 0 for P = 0), the tail block whose multiply-accumulate
+ * begins at c — the new tail response is heard from sample (P + 1)*pts1 on, the new head at once.  At another phase the
+ * tail block in progress sums the bins of its REMAINING slices with the new response and keeps the bins of the slices
+ * already done: push at phase 0.
+ * reset: the input history, the overlap-add tails and the blocks in progress are cleared, position() is 0, the responses
+ * stay: the object then repeats what it returned after its creation and the same pushes. */
+CLFA_API int clfa_nupconv_create(clfa_nupconv **pc, int device, int cvs, int pts0, int pts1, int channels);
+CLFA_API void clfa_nupconv_destroy(clfa_nupconv *pc);
+CLFA_API int clfa_nupconv_get_error(const clfa_nupconv *pc);
+CLFA_API const char *clfa_nupconv_get_log(const clfa_nupconv *pc);
+/* partitions of level 0 (the head: 2m) or 1 (the tail: n1); 0 for another level or a failed object */
+CLFA_API int clfa_nupconv_nparts(const clfa_nupconv *pc, int level);
+/* head blocks since creation or the last reset */
+CLFA_API long clfa_nupconv_position(const clfa_nupconv *pc);
+/* both levels' rings, responses and tails, the stage row and the pending tail output; the tail block's accumulators and
+ * the head's sub-batch workspaces (grown by the call that needs more blocks than any before it) */
+CLFA_API size_t clfa_nupconv_state_bytes(const clfa_nupconv *pc);
+CLFA_API size_t clfa_nupconv_workspace_bytes(const clfa_nupconv *pc);
+/* "k_nupc_mac" ("" for a failed object) */
+CLFA_API const char *clfa_nupconv_kernel_name(const clfa_nupconv *pc);
+CLFA_API int clfa_nupconv_push_ir(clfa_nupconv *pc, const float *ir);
+CLFA_API int clfa_nupconv_push_ir_dev(clfa_nupconv *pc, const void *ir, long channel_stride, void *stream);
+CLFA_API int clfa_nupconv_process_dev(clfa_nupconv *pc, void *out, long out_stride, const void *in, long in_stride,
+                                      long nblocks, void *stream);
+CLFA_API int clfa_nupconv_convolution(clfa_nupconv *pc, float *out, const float *in, long nblocks);
+CLFA_API int clfa_nupconv_reset(clfa_nupconv *pc, void *stream);
 
 #ifdef __cplusplus
 }

@@ -80,6 +80,20 @@ SYMBOLS = [
     ("clfa_pconv_matrix_state_bytes", C.c_size_t, [_vp]),
     ("clfa_pconv_matrix_workspace_bytes", C.c_size_t, [_vp]),
     ("clfa_pconv_matrix_kernel_name", C.c_char_p, [_vp]),
+    ("clfa_nupconv_create", C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    ("clfa_nupconv_destroy", None, [_vp]),
+    ("clfa_nupconv_get_error", C.c_int, [_vp]),
+    ("clfa_nupconv_get_log", C.c_char_p, [_vp]),
+    ("clfa_nupconv_nparts", C.c_int, [_vp, C.c_int]),
+    ("clfa_nupconv_position", C.c_long, [_vp]),
+    ("clfa_nupconv_state_bytes", C.c_size_t, [_vp]),
+    ("clfa_nupconv_workspace_bytes", C.c_size_t, [_vp]),
+    ("clfa_nupconv_kernel_name", C.c_char_p, [_vp]),
+    ("clfa_nupconv_push_ir", C.c_int, [_vp, _vp]),
+    ("clfa_nupconv_push_ir_dev", C.c_int, [_vp, _vp, C.c_long, _vp]),
+    ("clfa_nupconv_process_dev", C.c_int, [_vp, _vp, C.c_long, _vp, C.c_long, C.c_long, _vp]),
+    ("clfa_nupconv_convolution", C.c_int, [_vp, _vp, _vp, C.c_long]),
+    ("clfa_nupconv_reset", C.c_int, [_vp, _vp]),
     ("clfa_dconv_create", C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.c_int]),
     ("clfa_dconv_destroy", None, [_vp]),
     ("clfa_dconv_get_error", C.c_int, [_vp]),

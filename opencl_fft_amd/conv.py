@@ -1,5 +1,5 @@
 """The convolutions: Clpconv and Cldconv of the reference's cl_conv.h / cl_dconv.h with what they share (_BlockConv),
-and the convolution matrix PconvMatrix."""
+the convolution matrix PconvMatrix and the non-uniformly partitioned convolution Nupconv."""
 import numpy as np
 
 from ._base import CL_INVALID_VALUE, CL_SUCCESS, _Handle, _Object, _block_rows, _host, _is_f32, _pkg, _ptr_stream, _stream_of
@@ -236,6 +236,81 @@ class PconvMatrix(_Object):
             return CL_INVALID_VALUE
         return _pkg.lib().clfa_pconv_matrix_process_dev(self._h, out.data_ptr(), so, x.data_ptr(), si, li // self.pts,
                                                    _stream_of(x, stream))
+
+
+class Nupconv(_Object):
+    """Non-uniformly partitioned convolution (extension, clfa_nupconv in clfft_amd.h): long responses at a latency of
+    pts0 samples.  A head of 2 * pts1 / pts0 partitions of pts0 covers h[:2*pts1]; the tail runs in partitions of pts1,
+    each tail block's work spread over the pts1 / pts0 small blocks that pass while it is not yet needed.  The output is,
+    bit for bit, Clpconv(2*pts1, pts0) on h[:2*pts1] plus Clpconv(cvs - 2*pts1, pts1) on h[2*pts1:] delayed by 2*pts1
+    samples, both through process_blocks_device — not the bits of Clpconv(cvs, pts0).  pts0 < pts1 are powers of two,
+    32..4096; cvs >= 3 * pts1.  Like the other objects the constructor does not raise: get_error() / get_log()."""
+    _abi = "clfa_nupconv_"
+
+    def __init__(self, device_id, cvs, pts0, pts1, channels=1):
+        self.cvs, self.pts0, self.pts1, self.channels = int(cvs), int(pts0), int(pts1), int(channels)
+        self._create(_pkg.lib().clfa_nupconv_create, int(device_id), self.cvs, self.pts0, self.pts1, self.channels)
+
+    position = property(lambda s: s._get("position"))
+
+    def nparts(self, level):
+        """partitions of level 0 (the head) or 1 (the tail)"""
+        return self._get("nparts", int(level))
+
+    def state_bytes(self):
+        return self._get("state_bytes")
+
+    def _need(self):
+        return 2 * self.pts1 + self.nparts(1) * self.pts1
+
+    def push_ir(self, ir):
+        """ir: float32 (channels, >= 2*pts1 + nparts(1)*pts1), e.g. rows of cvs samples (1-D for one channel); blocking.
+        Exact at position % (pts1 // pts0) == 0; at another phase the tail block in progress mixes both responses."""
+        ir = np.asarray(ir, dtype=np.float32)
+        if ir.ndim == 1:
+            ir = ir[None, :]
+        need = self._need()
+        if ir.ndim != 2 or ir.shape[0] != self.channels or ir.shape[1] < need:
+            return CL_INVALID_VALUE
+        ir = np.ascontiguousarray(ir[:, :need])
+        return _pkg.lib().clfa_nupconv_push_ir(self._h, ir.ctypes.data)
+
+    def push_ir_device(self, ir, stream=None):
+        """ir: device tensor (channels, >= 2*pts1 + nparts(1)*pts1) of float32 (1-D for one channel), stride(1) == 1; the
+        row stride is its stride(0).  Asynchronous on `stream`."""
+        length, stride = _block_rows(ir, self.channels, "channels", True)
+        if length < self._need():
+            return CL_INVALID_VALUE
+        return _pkg.lib().clfa_nupconv_push_ir_dev(self._h, ir.data_ptr(), stride, _stream_of(ir, stream))
+
+    def convolution(self, output, input):
+        """whole signals on the host: float32 (channels, L) -> (channels, L) (1-D for one channel), L a multiple of
+        pts0; blocking"""
+        output = _host(output, np.float32)
+        a = np.ascontiguousarray(input, dtype=np.float32)
+        if a.ndim == 1:
+            a = a[None, :]
+        if a.ndim != 2 or a.shape[0] != self.channels or a.shape[1] % self.pts0 or output.size != a.size:
+            return CL_INVALID_VALUE
+        return _pkg.lib().clfa_nupconv_convolution(self._h, output.ctypes.data, a.ctypes.data, a.shape[1] // self.pts0)
+
+    def process_device(self, out, x, stream=None):
+        """device tensors (channels, L) of float32 (1-D for one channel), stride(1) == 1, L a multiple of pts0; the row
+        stride of each is its stride(0) (views into longer rows are fine).  Asynchronous on `stream`; not under graph
+        capture (CL_INVALID_OPERATION: the phase of the schedule lives on the host)."""
+        (lo, so), (li, si) = (_block_rows(t, self.channels, "channels", True) for t in (out, x))
+        if lo != li or li % self.pts0:
+            return CL_INVALID_VALUE
+        return _pkg.lib().clfa_nupconv_process_dev(self._h, out.data_ptr(), so, x.data_ptr(), si, li // self.pts0,
+                                                   _stream_of(x, stream))
+
+    def reset(self, stream=None):
+        """forget the input history (position 0); the responses stay.  `stream`: a HIP stream handle, default the
+        current torch stream of the object's device"""
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream().cuda_stream
+        return self._get("reset", stream)
 
 
 class Cldconv(_BlockConv):

@@ -1,5 +1,5 @@
-// conv_host.cpp — C ABI of the convolutions (see include/clfft_amd.h): Clpconv and its multi-block route, Cldconv, and
-// the convolution matrix.  Shared plumbing: host.hpp, where the staged blocking form lives (staged_call); the rules of a
+// conv_host.cpp — C ABI of the convolutions (see include/clfft_amd.h): Clpconv and its multi-block route, Cldconv, the
+// convolution matrix and the non-uniformly partitioned convolution.  Shared plumbing: host.hpp, where the staged blocking form lives (staged_call); the rules of a
 // call's arrays: overlap.hpp.  Every object stages its blocking calls in members in1, in2, out and its responses in ir.
 #include "dconv_launch.hpp"
 #include "fft_launch.hpp"
@@ -909,6 +909,277 @@ int clfa_pconv_matrix_convolution(clfa_pconv_matrix *p, float *out, const float 
   return blocks_host(p, out, in, nullptr, nblocks, [&](void *o, long len, const void *i1, const void *) {
     return clfa_pconv_matrix_process_dev(p, o, len, i1, len, nblocks, p->stream);
   });
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------
+// non-uniformly partitioned convolution (pconv_nup.hip; the head is the blocks route of pconv_blocks.hip)
+// ---------------------------------------------------------------------------------
+
+// one level: its geometry, tables, input-spectra ring, response spectra, ring position
+struct NupLevel {
+  PconvGeom g{};
+  DevBuf half, w2f, w2i;
+  DevBuf ringA, ringB;
+  int w = 0;
+};
+
+struct clfa_nupconv {
+  DeviceInfo di;
+  int cvs = 0, pts0 = 0, pts1 = 0, m = 0, channels = 0;
+  int err = 0;
+  char log[256];
+  hipStream_t stream = nullptr;
+  NupLevel lv[2];                // the head (2m partitions of pts0) and the tail (n1 partitions of pts1)
+  DevBuf tail0[2], tail1[2];     // the levels' overlap-add tails: a single block's inverse reads one and writes the other
+  int hcur = 0, tcur = 0;        // ... the one in force
+  DevBuf stage, pend;            // the tail block being collected; the finished tail block's samples, being mixed in
+  DevBuf Y0, Y1;                 // a single head block's accumulators; the tail block's, filled slice by slice
+                                 // (a single block's X is its ring frame w)
+  DevBuf bX, bY, btail;          // the head's sub-batch workspaces, for hcap blocks (grown by the call that needs more)
+  int hcap = 0, bcap = 1, bkt = 4;
+  DevBuf in1, in2, out;          // staging of the blocking form (conv_arrays; in2 stays empty)
+  DevBuf ir;                     // ... and of push_ir
+  StreamOrder order;
+  long c = 0;                    // head blocks since creation / reset
+};
+
+static BlockShape block_shape(const clfa_nupconv *p) { return {p->pts0, p->channels, p->channels}; }
+static long nup_ir_len(const clfa_nupconv *p) { return 2L * p->pts1 + (long)p->lv[1].g.nparts * p->pts1; }
+
+static int nup_setup(clfa_nupconv *p, int device, int cvs, int pts0, int pts1, int channels) {
+  p->log[0] = 0;
+  p->cvs = cvs;
+  p->pts0 = pts0;
+  p->pts1 = pts1;
+  p->channels = channels;
+  const int lo = 1 << kPconvBlocksMinLog, hi = 1 << kPconvBlocksMaxLog;
+  if (!is_pow2(pts0) || pts0 < lo) {
+    snprintf(p->log, sizeof(p->log), "pts0 must be a power of two, %d..%d (got %d)", lo, hi / 2, pts0);
+    return CLFA_INVALID_VALUE;
+  }
+  if (!is_pow2(pts1) || pts1 > hi || pts1 <= pts0) {
+    snprintf(p->log, sizeof(p->log), "pts1 must be a power of two above pts0, at most %d (got pts0 %d, pts1 %d)", hi, pts0, pts1);
+    return CLFA_INVALID_VALUE;
+  }
+  if (cvs / 3 < pts1) {
+    snprintf(p->log, sizeof(p->log), "cvs must be at least 3 * pts1 = %d (got %d)", 3 * pts1, cvs);
+    return CLFA_INVALID_VALUE;
+  }
+  if (channels < 1) {
+    snprintf(p->log, sizeof(p->log), "channels must be at least 1 (got %d)", channels);
+    return CLFA_INVALID_VALUE;
+  }
+  p->m = pts1 / pts0;
+  p->lv[0].g = {ilog2(pts0), pts0, 2 * p->m, channels};
+  p->lv[1].g = {ilog2(pts1), pts1, (cvs - 2 * pts1) / pts1, channels};   // floor: remainder samples are dropped
+  int e = device_info(device, p->di);
+  if (e) return e;
+  p->bcap = subbatch_cap(3L * channels * pts0 * (long)sizeof(cpx), "CLFA_PCONV_BLOCKS_MAX");   // as Clpconv's blocks route
+  p->bkt = pconv_blocks_tile(p->lv[0].g, p->di);
+  ENTER_DEVICE(device);
+  HIP_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
+  for (NupLevel &l : p->lv) {
+    if ((e = upload_conv_tables(l.g.bins, l.half, l.w2f, l.w2i))) return e;
+    const size_t ring = sizeof(cpx) * (size_t)channels * l.g.nparts * l.g.bins;
+    if ((e = l.ringA.ensure(ring)) || (e = l.ringB.ensure(ring))) return e;
+    HIP_TRY(hipMemsetAsync(l.ringA.p, 0, ring, p->stream));
+    HIP_TRY(hipMemsetAsync(l.ringB.p, 0, ring, p->stream));
+  }
+  const size_t row0 = sizeof(float) * (size_t)channels * pts0, row1 = sizeof(float) * (size_t)channels * pts1;
+  if ((e = p->tail0[0].ensure(row0)) || (e = p->tail0[1].ensure(row0)) || (e = p->tail1[0].ensure(row1)) ||
+      (e = p->tail1[1].ensure(row1)) || (e = p->stage.ensure(row1)) || (e = p->pend.ensure(row1)) ||
+      (e = p->Y0.ensure(sizeof(cpx) * (size_t)channels * pts0)) || (e = p->Y1.ensure(sizeof(cpx) * (size_t)channels * pts1)))
+    return e;
+  for (DevBuf *b : {&p->tail0[0], &p->tail0[1], &p->tail1[0], &p->tail1[1], &p->stage, &p->pend})
+    HIP_TRY(hipMemsetAsync(b->p, 0, b->bytes, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return CLFA_SUCCESS;
+}
+
+// partition i of every row -> response frame nparts - 1 - i of the level (the frame the MAC pairs with the i-th newest
+// input block), with the blocks route's forward transform: the bits Clpconv's push gives
+static int nup_push_level(const NupLevel &l, const float *ir, long stride, hipStream_t s) {
+  const int aligned = ((uintptr_t)ir & 7) == 0 && (stride & 1) == 0;
+  for (int i = 0; i < l.g.nparts; i++)
+    HIP_TRY(launch_pconvb_forward(l.g.logb, ir + (long)i * l.g.bins, stride, (cpx *)l.ringB.p + (long)(l.g.nparts - 1 - i) * l.g.bins,
+                                  1, l.g.nparts, l.g.channels, aligned, (const cpx *)l.half.p, (const cpx *)l.w2f.p, s));
+  return CLFA_SUCCESS;
+}
+
+// the head's K blocks through the blocks route, sub-batch by sub-batch, as clfa_pconv_process_blocks_dev
+static int nup_head(clfa_nupconv *p, float *out, long out_stride, const float *in, long in_stride, long nblocks, hipStream_t s) {
+  NupLevel &l = p->lv[0];
+  PconvBlocks a;
+  a.g = l.g;
+  a.cap = p->hcap;
+  a.kt = p->bkt;
+  a.in_stride = in_stride;
+  a.out_stride = out_stride;
+  a.aligned_in = ((uintptr_t)in & 7) == 0 && (in_stride & 1) == 0;
+  a.aligned_out = ((uintptr_t)out & 7) == 0 && (out_stride & 1) == 0;
+  a.ringA = (cpx *)l.ringA.p;
+  a.ringB = (cpx *)l.ringB.p;
+  a.tail = (float *)p->tail0[p->hcur].p;
+  a.X = (cpx *)p->bX.p;
+  a.Y = (cpx *)p->bY.p;
+  a.tail_ws = (float *)p->btail.p;
+  a.half = (const cpx *)l.half.p;
+  a.w2f = (const cpx *)l.w2f.p;
+  a.w2i = (const cpx *)l.w2i.p;
+  for (long j0 = 0; j0 < nblocks; j0 += a.K) {
+    a.K = (int)(nblocks - j0 < p->hcap ? nblocks - j0 : p->hcap);
+    a.w = l.w;
+    a.in1 = in + j0 * p->pts0;
+    a.out = out + j0 * p->pts0;
+    HIP_TRY(launch_pconv_blocks(a, s));
+    l.w = (int)((l.w + a.K) % l.g.nparts);
+  }
+  return CLFA_SUCCESS;
+}
+
+extern "C" {
+
+int clfa_nupconv_create(clfa_nupconv **pc, int device, int cvs, int pts0, int pts1, int channels) {
+  return create_object(pc, [&](clfa_nupconv *p) { return nup_setup(p, device, cvs, pts0, pts1, channels); });
+}
+
+void clfa_nupconv_destroy(clfa_nupconv *p) { destroy_object(p); }
+
+int clfa_nupconv_get_error(const clfa_nupconv *p) { return p ? p->err : CLFA_INVALID_VALUE; }
+const char *clfa_nupconv_get_log(const clfa_nupconv *p) { return p ? p->log : ""; }
+int clfa_nupconv_nparts(const clfa_nupconv *p, int level) {
+  return p && !p->err && (level == 0 || level == 1) ? p->lv[level].g.nparts : 0;
+}
+long clfa_nupconv_position(const clfa_nupconv *p) { return p ? p->c : 0; }
+size_t clfa_nupconv_state_bytes(const clfa_nupconv *p) {
+  if (!p) return 0;
+  size_t n = p->tail0[0].bytes + p->tail0[1].bytes + p->tail1[0].bytes + p->tail1[1].bytes + p->stage.bytes + p->pend.bytes;
+  for (const NupLevel &l : p->lv) n += l.ringA.bytes + l.ringB.bytes;
+  return n;
+}
+size_t clfa_nupconv_workspace_bytes(const clfa_nupconv *p) {
+  return p ? p->Y0.bytes + p->Y1.bytes + p->bX.bytes + p->bY.bytes + p->btail.bytes : 0;
+}
+const char *clfa_nupconv_kernel_name(const clfa_nupconv *p) { return !p || p->err ? "" : "k_nupc_mac"; }
+
+int clfa_nupconv_push_ir_dev(clfa_nupconv *p, const void *ir, long channel_stride, void *stream) {
+  if (int e = obj_error(p)) return e;
+  if (!device_rows_ok(ir) || channel_stride < nup_ir_len(p)) return CLFA_INVALID_VALUE;
+  ENTER_DEVICE(p->di.device);
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(p->order.use(s));
+  // h[0 : 2*pts1) in the head's partitions, h[2*pts1 : 2*pts1 + n1*pts1) in the tail's, in stream order
+  if (int e = nup_push_level(p->lv[0], (const float *)ir, channel_stride, s)) return e;
+  return nup_push_level(p->lv[1], (const float *)ir + 2L * p->pts1, channel_stride, s);
+}
+
+int clfa_nupconv_push_ir(clfa_nupconv *p, const float *ir) {
+  if (int e = obj_error(p)) return e;
+  if (!ir) return CLFA_INVALID_VALUE;
+  ENTER_DEVICE(p->di.device);
+  const long len = nup_ir_len(p);
+  return push_host(p, ir, sizeof(float) * (size_t)p->channels * len,
+                   [&](const void *rows) { return clfa_nupconv_push_ir_dev(p, rows, len, p->stream); });
+}
+
+int clfa_nupconv_process_dev(clfa_nupconv *p, void *out, long out_stride, const void *in, long in_stride, long nblocks,
+                             void *stream) {
+  if (int e = obj_error(p)) return e;
+  const long pts0 = p->pts0, ch = p->channels, m = p->m;
+  long len;
+  if (int e = check_blocks_dev(nblocks, pts0, out, out_stride, ch, in, nullptr, in_stride, ch, &len)) return e;
+  if (!len) return CLFA_SUCCESS;
+  ENTER_DEVICE(p->di.device);
+  hipStream_t s = (hipStream_t)stream;
+  // the phase of the schedule is host state, which a replay would not advance
+  if (StreamOrder::capturing(s)) return CLFA_INVALID_OPERATION;
+  // One block: the head's forward transform straight into its ring frame, its multiply-accumulate beside the tail's slice
+  // in one launch of k_nupc_mac, its inverse.  Several blocks: the head through the blocks route over the whole call.  The
+  // arithmetic of a bin is the same on both ways, and both leave the same rings, tails and positions.
+  const bool single = nblocks == 1;
+  if (!single && nblocks > p->hcap) {
+    const int cap = (int)(nblocks < p->bcap ? nblocks : p->bcap);
+    if (cap > p->hcap) {
+      const size_t frames = sizeof(cpx) * (size_t)ch * (size_t)cap * (size_t)pts0;
+      if (int e = ensure_workspaces({{&p->bX, frames}, {&p->bY, frames}, {&p->btail, sizeof(float) * (size_t)ch * (size_t)pts0}}, s))
+        return e;
+      p->hcap = cap;
+    }
+  }
+  HIP_TRY(p->order.use(s));
+  const float *x = (const float *)in;
+  float *o = (float *)out;
+  NupLevel &h = p->lv[0], &t = p->lv[1];
+  if (!single)
+    if (int e = nup_head(p, o, out_stride, x, in_stride, nblocks, s)) return e;
+  // the tail, period by period: head blocks [j0, j0 + k) of the call are phases [sa, sb) of period P, in which tail block
+  // P - 1 is multiplied and tail block P - 2 is heard
+  const int hb0 = (int)(pts0 / 2);
+  for (long j0 = 0; j0 < nblocks;) {
+    const long P = p->c / m;
+    const int sa = (int)(p->c % m);
+    const long k = nblocks - j0 < m - sa ? nblocks - j0 : m - sa;
+    const int sb = sa + (int)k, off = sa * (int)pts0, n = (int)(k * pts0);
+    if (single)
+      HIP_TRY(launch_pconvb_forward(h.g.logb, x, in_stride, (cpx *)h.ringA.p + (long)h.w * h.g.bins, 1, h.g.nparts, (int)ch,
+                                    ((uintptr_t)x & 7) == 0 && (in_stride & 1) == 0, (const cpx *)h.half.p, (const cpx *)h.w2f.p, s));
+    // phase 0: the spectrum of the finished block, before this period's samples overwrite the row
+    if (P >= 1 && sa == 0)
+      HIP_TRY(launch_pconvb_forward(t.g.logb, (const float *)p->stage.p, p->pts1, (cpx *)t.ringA.p + (long)t.w * t.g.bins, 1,
+                                    t.g.nparts, (int)ch, 1, (const cpx *)t.half.p, (const cpx *)t.w2f.p, s));
+    HIP_TRY(launch_nupc_stage(x + j0 * pts0, in_stride, (float *)p->stage.p, p->pts1, off, n, (int)ch, s));
+    NupcMacJob jobs[2];
+    int njobs = 0;
+    if (single) jobs[njobs++] = {(const cpx *)h.ringA.p, (const cpx *)h.ringB.p, (cpx *)p->Y0.p, h.w, h.g.bins, h.g.nparts, 0, hb0};
+    if (P >= 1)
+      jobs[njobs++] = {(const cpx *)t.ringA.p, (const cpx *)t.ringB.p, (cpx *)p->Y1.p, t.w, t.g.bins, t.g.nparts, sa * hb0, (sb - sa) * hb0};
+    if (njobs) HIP_TRY(launch_nupc_mac(jobs, njobs, (int)ch, s));
+    if (single) {
+      HIP_TRY(launch_pconvb_inverse(h.g.logb, (const cpx *)p->Y0.p, (const float *)p->tail0[p->hcur].p,
+                                    (float *)p->tail0[p->hcur ^ 1].p, o, out_stride, 1, 1, 1, (int)ch,
+                                    ((uintptr_t)o & 7) == 0 && (out_stride & 1) == 0, (const cpx *)h.half.p, (const cpx *)h.w2i.p, s));
+      p->hcur ^= 1;
+      h.w = (h.w + 1) % h.g.nparts;
+    }
+    HIP_TRY(launch_nupc_mix(o + j0 * pts0, out_stride, (const float *)p->pend.p, p->pts1, off, n, (int)ch, s));
+    // after slice m - 1: the block's samples replace the ones just heard, its spectrum stays in the ring
+    if (P >= 1 && sb == m) {
+      HIP_TRY(launch_pconvb_inverse(t.g.logb, (const cpx *)p->Y1.p, (const float *)p->tail1[p->tcur].p,
+                                    (float *)p->tail1[p->tcur ^ 1].p, (float *)p->pend.p, p->pts1, 1, 1, 1, (int)ch, 1,
+                                    (const cpx *)t.half.p, (const cpx *)t.w2i.p, s));
+      p->tcur ^= 1;
+      t.w = (t.w + 1) % t.g.nparts;
+    }
+    p->c += k;
+    j0 += k;
+  }
+  return CLFA_SUCCESS;
+}
+
+int clfa_nupconv_convolution(clfa_nupconv *p, float *out, const float *in, long nblocks) {
+  return blocks_host(p, out, in, nullptr, nblocks, [&](void *o, long len, const void *i1, const void *) {
+    return clfa_nupconv_process_dev(p, o, len, i1, len, nblocks, p->stream);
+  });
+}
+
+int clfa_nupconv_reset(clfa_nupconv *p, void *stream) {
+  if (int e = obj_error(p)) return e;
+  ENTER_DEVICE(p->di.device);
+  hipStream_t s = (hipStream_t)stream;
+  if (StreamOrder::capturing(s)) return CLFA_INVALID_OPERATION;
+  HIP_TRY(p->order.use(s));
+  // the input history, the tails and the blocks in progress; the responses stay
+  for (NupLevel &l : p->lv) {
+    HIP_TRY(hipMemsetAsync(l.ringA.p, 0, l.ringA.bytes, s));
+    l.w = 0;
+  }
+  for (DevBuf *b : {&p->tail0[0], &p->tail0[1], &p->tail1[0], &p->tail1[1], &p->stage, &p->pend})
+    HIP_TRY(hipMemsetAsync(b->p, 0, b->bytes, s));
+  p->hcur = p->tcur = 0;
+  p->c = 0;
+  return CLFA_SUCCESS;
 }
 
 }  // extern "C"

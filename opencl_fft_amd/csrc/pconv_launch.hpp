@@ -1,6 +1,7 @@
 // pconv_launch.hpp — the launchers of the partitioned convolution (pconv_chain.hip, pconv_coop.hip, pconv_blocks.hip,
-// pconv_matrix.hip) as conv_host.cpp sees them: PconvGeom and the per-block launches, the cooperative and the fused block,
-// the many-block sub-batch (PconvBlocks), the convolution matrix (PconvMatrixArgs) and the ends of the composed chain.
+// pconv_matrix.hip, pconv_nup.hip) as conv_host.cpp sees them: PconvGeom and the per-block launches, the cooperative and the
+// fused block, the many-block sub-batch (PconvBlocks), the convolution matrix (PconvMatrixArgs), the tail level of the
+// non-uniform partitioning (launch_nupc_*) and the ends of the composed chain.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -116,7 +117,25 @@ hipError_t launch_pconv_matrix(const PconvMatrixArgs &a, hipStream_t s);
 // committed.  _prime: tail2 = the second half of the block before the next one under H2, from ring A alone.
 hipError_t launch_pconv_matrix_fade(const PconvMatrixArgs &a, hipStream_t s);
 hipError_t launch_pconv_matrix_prime(const PconvMatrixArgs &a, hipStream_t s);
-constexpr int kPconvMaxLogBins = 15;   // pts up to 32768 (the reference harness' largest, csound/tests.py:13)
+// Non-uniformly partitioned convolution, the tail level (pconv_nup.hip).  stage / pend: channels x pts1 floats; off and n
+// (multiples of 32, off + n <= pts1) are the stream's position in the tail block and the call's samples there; in / out
+// point at the first of them (row c at c * stride floats, any 4-byte aligned address and stride).
+hipError_t launch_nupc_stage(const float *in, long in_stride, float *stage, int pts1, int off, int n, int channels,
+                             hipStream_t s);
+// out = out + pend[off .. off + n): out holds the head's samples
+hipError_t launch_nupc_mix(float *out, long out_stride, const float *pend, int pts1, int off, int n, int channels,
+                           hipStream_t s);
+// Y (channels x bins complex) items [item0, item0 + nitems) of 16 bytes = the sum over the nparts partitions, ascending, of
+// ring A frame (w - (nparts - 1) + p) mod nparts times ring B frame p: w is the frame that holds the new block.  One or two
+// jobs (the head's block, the tail's slice) side by side in one launch
+struct NupcMacJob {
+  const cpx *ringA = nullptr, *ringB = nullptr;   // channels x nparts x bins
+  cpx *Y = nullptr;
+  int w = 0, bins = 0, nparts = 0, item0 = 0, nitems = 0;
+};
+constexpr int kNupcMacDepth = 16;   // partitions whose loads are in flight per lane
+hipError_t launch_nupc_mac(const NupcMacJob *jobs, int njobs, int channels, hipStream_t s);
+constexpr int kPconvMaxLogBins = 15;  // pts up to 32768 (the reference harness' largest, csound/tests.py:13)
 // ends of the composed chain used when bins exceed the LDS FFT sizes
 hipError_t launch_pconv_pad(const float *in, long in_stride, cpx *work, int bins, int channels, hipStream_t s);
 hipError_t launch_pconv_olap(const float *work, float *tail, float *out, int bins, int channels, hipStream_t s);

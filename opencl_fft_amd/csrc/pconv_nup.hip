@@ -1,0 +1,161 @@
+// pconv_nup.hip — the kernels of the non-uniformly partitioned convolution (clfa_nupconv, conv_host.cpp): a head of small
+// partitions (pts0) gives the latency; the long tail runs in large partitions (pts1 = m * pts0), and each tail block's
+// multiply-accumulate is spread in m slices of its bins over the m head blocks that pass while its output is not yet needed.
+//   k_nupc_stage   the call's input rows -> the tail's input row (channels x pts1 floats) at the stream's position
+//   k_nupc_mac     Y = sum_p A[(w - (nparts - 1) + p) mod nparts] (.) B[p] of ONE block of a level over a range of its
+//                  16-byte items: one accumulator per bin over p = 0, 1, ... nparts - 1 with mac_term, the order and the
+//                  products of k_pconvb_mac — the bits of Clpconv's blocks route, however the bins are cut into slices.
+//                  A single-block call runs the head's block and the tail's slice in one launch of it
+//   k_nupc_mix     out = head + pending tail output at the stream's position, one float32 addition, the head first
+// The forward and inverse transforms are launch_pconvb_forward / launch_pconvb_inverse with K = 1; calls of several blocks
+// run the head through launch_pconv_blocks.  A new block's spectrum goes straight into ring frame w, the one frame the
+// multiply-accumulate of the block before it does not read; committing it is the host's w + 1.
+#include "pconv_device.hpp"
+#include "pconv_launch.hpp"
+
+namespace clfa {
+
+namespace {
+
+typedef float v4f __attribute__((ext_vector_type(4)));
+
+// rows of n floats (a multiple of 32) as units of V floats: V = 4 where every row start is 16-byte aligned
+template <int V> struct RowUnit;
+template <> struct RowUnit<1> { typedef float type; };
+template <> struct RowUnit<4> { typedef v4f type; };
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------
+// stage: in[ch][0 .. n) -> stage[ch][off .. off + n)
+// ---------------------------------------------------------------------------------
+template <int V>
+__global__ __launch_bounds__(256) void k_nupc_stage(const float *__restrict__ in, long in_stride, float *__restrict__ stage,
+                                                    int pts1, int off, int n, int channels) {
+  typedef typename RowUnit<V>::type U;
+  const int nu = n / V;
+  const long total = (long)channels * nu;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const int ch = (int)(i / nu), k = (int)(i % nu) * V;
+    *reinterpret_cast<U *>(stage + (long)ch * pts1 + off + k) = *reinterpret_cast<const U *>(in + (long)ch * in_stride + k);
+  }
+}
+
+// ---------------------------------------------------------------------------------
+// mix: out[ch][0 .. n) = out[ch][0 .. n) + pend[ch][off .. off + n)   (out holds the head's samples)
+// ---------------------------------------------------------------------------------
+template <int V>
+__global__ __launch_bounds__(256) void k_nupc_mix(float *out, long out_stride, const float *__restrict__ pend, int pts1, int off,
+                                                  int n, int channels) {
+  typedef typename RowUnit<V>::type U;
+  const int nu = n / V;
+  const long total = (long)channels * nu;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const int ch = (int)(i / nu), k = (int)(i % nu) * V;
+    U *o = reinterpret_cast<U *>(out + (long)ch * out_stride + k);
+    *o = *o + *reinterpret_cast<const U *>(pend + (long)ch * pts1 + off + k);
+  }
+}
+
+// ---------------------------------------------------------------------------------
+// multiply-accumulate of ONE block of a level over items [item0, item0 + nitems) of every channel: one lane = (channel,
+// item), the lanes laid over both together, so that a slice of 16 items still fills its waves.  The partitions are one
+// serial chain per lane (the order is the result's bits), so what hides the memory latency is depth: the loads of D
+// partitions are in flight together.  blockIdx.y picks the job: a single-block call runs the head's block (all its items)
+// and the tail's slice side by side in one launch.
+// ---------------------------------------------------------------------------------
+template <int D>
+__global__ __launch_bounds__(64) void k_nupc_mac(NupcMacJob job0, NupcMacJob job1, int channels) {
+  const NupcMacJob &job = blockIdx.y ? job1 : job0;
+  const cpx *__restrict__ ringA = job.ringA;
+  const cpx *__restrict__ ringB = job.ringB;
+  cpx *__restrict__ Y = job.Y;
+  const int w = job.w, bins = job.bins, nparts = job.nparts, item0 = job.item0, nitems = job.nitems;
+  if (blockIdx.x * 64L >= (long)channels * nitems) return;   // (the grid is the larger job's)
+  const int hb = bins >> 1;
+  const long total = (long)channels * nitems;
+  const long gid = blockIdx.x * 64L + threadIdx.x;
+  const long g = gid < total ? gid : total - 1;   // (clamped: straight-line loads; the store is guarded)
+  const int ch = (int)(g / nitems), item = item0 + (int)(g % nitems);
+  const cpx2 *ra = reinterpret_cast<const cpx2 *>(ringA + (long)ch * nparts * bins) + item;
+  const cpx2 *rb = reinterpret_cast<const cpx2 *>(ringB + (long)ch * nparts * bins) + item;
+  // input frame of partition p: block (p - (nparts - 1)) counted from the new one, ring frame (w + that) mod nparts; the
+  // new block's own spectrum is frame w (p = nparts - 1).  Past the last partition: clamped, never used
+  auto frame = [&](int p) -> const cpx2 * {
+    p = p < nparts ? p : nparts - 1;
+    int f = w - (nparts - 1) + p;
+    f = f < 0 ? f + nparts : f;
+    return ra + (long)f * hb;
+  };
+  auto resp = [&](int p) -> const cpx2 * { return rb + (long)(p < nparts ? p : nparts - 1) * hb; };
+  const bool dc = item == 0;   // packed DC / Nyquist bin: (re*re, im*im)
+  cpx s0 = mk(0.f, 0.f), s1 = mk(0.f, 0.f);
+  cpx2 xq[D], hq[D];
+#pragma unroll
+  for (int d = 0; d < D; d++) {
+    xq[d] = ld_nt(frame(d));
+    hq[d] = ld_nt(resp(d));
+  }
+  for (int p0 = 0; p0 < nparts; p0 += D) {
+#pragma unroll
+    for (int d = 0; d < D; d++) {
+      const cpx2 x = xq[d], h = hq[d];
+      xq[d] = ld_nt(frame(p0 + d + D));
+      hq[d] = ld_nt(resp(p0 + d + D));
+      // past the last partition the term is dropped by a select on the sums, not by a branch: a branch in the body ends
+      // the overlap of the loads with the arithmetic
+      cpx t0 = s0, t1 = s1;
+      mac_term(t0, t1, x, h, dc);
+      const bool live = p0 + d < nparts;
+      s0 = mk(live ? t0.x : s0.x, live ? t0.y : s0.y);
+      s1 = mk(live ? t1.x : s1.x, live ? t1.y : s1.y);
+    }
+  }
+  if (gid < total) {
+    cpx2 o;
+    o.a = s0;
+    o.b = s1;
+    reinterpret_cast<cpx2 *>(Y + (long)ch * bins)[item] = o;
+  }
+}
+
+// ---------------------------------------------------------------------------------
+// launchers
+// ---------------------------------------------------------------------------------
+static bool rows_16(const void *p, long stride) { return ((uintptr_t)p & 15) == 0 && (stride & 3) == 0; }
+
+hipError_t launch_nupc_stage(const float *in, long in_stride, float *stage, int pts1, int off, int n, int channels,
+                             hipStream_t s) {
+  if (n < 1 || (n & 31) || (off & 31) || off + n > pts1) return hipErrorInvalidValue;
+  const bool v4 = rows_16(in, in_stride);   // (the stage row itself: hipMalloc'ed, pts1 and off multiples of 32)
+  const int grid = grid_clamp(((long)channels * (n / (v4 ? 4 : 1)) + 255) / 256, 4096);
+  if (v4) hipLaunchKernelGGL(k_nupc_stage<4>, dim3(grid), dim3(256), 0, s, in, in_stride, stage, pts1, off, n, channels);
+  else hipLaunchKernelGGL(k_nupc_stage<1>, dim3(grid), dim3(256), 0, s, in, in_stride, stage, pts1, off, n, channels);
+  return hipGetLastError();
+}
+
+hipError_t launch_nupc_mix(float *out, long out_stride, const float *pend, int pts1, int off, int n, int channels,
+                           hipStream_t s) {
+  if (n < 1 || (n & 31) || (off & 31) || off + n > pts1) return hipErrorInvalidValue;
+  const bool v4 = rows_16(out, out_stride);
+  const int grid = grid_clamp(((long)channels * (n / (v4 ? 4 : 1)) + 255) / 256, 4096);
+  if (v4) hipLaunchKernelGGL(k_nupc_mix<4>, dim3(grid), dim3(256), 0, s, out, out_stride, pend, pts1, off, n, channels);
+  else hipLaunchKernelGGL(k_nupc_mix<1>, dim3(grid), dim3(256), 0, s, out, out_stride, pend, pts1, off, n, channels);
+  return hipGetLastError();
+}
+
+hipError_t launch_nupc_mac(const NupcMacJob *jobs, int njobs, int channels, hipStream_t s) {
+  if (njobs < 1 || njobs > 2) return hipErrorInvalidValue;
+  long blocks = 0;
+  for (int i = 0; i < njobs; i++) {
+    const NupcMacJob &j = jobs[i];
+    if (j.item0 < 0 || j.nitems < 1 || j.item0 + j.nitems > j.bins / 2 || j.w < 0 || j.w >= j.nparts) return hipErrorInvalidValue;
+    const long b = ((long)channels * j.nitems + 63) / 64;
+    blocks = b > blocks ? b : blocks;
+  }
+  if (blocks > 0x7fffffffL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_nupc_mac<kNupcMacDepth>, dim3((unsigned)blocks, njobs), dim3(64), 0, s, jobs[0], jobs[njobs - 1], channels);
+  return hipGetLastError();
+}
+
+}  // namespace clfa
