@@ -1025,9 +1025,43 @@ CLFA_API const char *clfa_pconv_matrix_kernel_name(const clfa_pconv_matrix *m);
  * its block c and the tail object before its block P - 1 (block 0 for P = 0), the tail block whose multiply-accumulate
  * begins at c — the new tail response is heard from sample (P + 1)*pts1 on, the new head at once.  At another phase the
  * tail block in progress sums the bins of its REMAINING slices with the new response and keeps the bins of the slices
- * already done: push at phase 0.
+ * already done: push at phase 0, or use the timed crossfade below, which is clean at any phase.
  * reset: the input history, the overlap-add tails and the blocks in progress are cleared, position() is 0, the responses
- * stay: the object then repeats what it returned after its creation and the same pushes. */
+ * stay: the object then repeats what it returned after its creation and the same pushes.
+ *
+ * Timed crossfade (push_ir_fade, push_ir_fade_dev): a change of responses without the step of a plain push, at any phase.
+ * ir, channel_stride and the row layout are those of push_ir / push_ir_dev.  Definition: let A be the response set in
+ * force at the push and B the pushed set; c = position() at the push (any phase); block 0 the next head block processed;
+ * N = fade_blocks * pts0; n a sample's index counted from the first sample of block 0; yA what this object would have
+ * produced without the push; yB what a second object of the same geometry would produce if it had held B since its
+ * creation or last reset and had received every input this object has received since then.  Both are complete outputs,
+ * head + pending tail, one float32 addition with the head first.  Then
+ *   for 0 <= n < N the output sample is  yA + g(n) * (yB - yA),  evaluated in float32 in that form (a subtraction, a
+ *     multiplication, an addition, each rounded on its own, no contraction), with  g(n) = (float)n / (float)N  (IEEE
+ *     division, round to nearest): exactly 0 at n = 0, rising linearly to (N-1)/N;
+ *   from sample N on the output is yB, B is in force, fade_remaining() is 0, and the object is in every later bit the
+ *     object that always held B.
+ * The output does not depend on how the stream is cut into calls, during the fade or after it; a fade from A to A gives
+ * the bits of no push at all.
+ * State: the input-spectra rings do not depend on the response; both paths share them and they are written once.  The
+ * second path has its own response spectra of both levels, overlap-add tails of both levels, pending row, tail-block
+ * accumulators and a scratch row of channels x pts0 for its head output.  All of its history is recomputed at the push
+ * from the rings alone with the plain path's kernels, hence with its bits: with P = c div m and s = c mod m, the head's
+ * tail from head block c - 1 (c >= 1); the tail level's tail from tail block P - 3 (P >= 3); the pending row and the
+ * tail level's tail from tail block P - 2 (P >= 2); slices 0 .. s-1 of tail block P - 1 (P >= 1, s > 0).  A block of
+ * negative index is not computed: its contribution is the +0 of a cleared row.  For this the tail's ring keeps n1 + 2
+ * frames (the multiply-accumulate walks the newest n1).  When the last fade block has been issued the second set becomes
+ * the first by an exchange of pointers on the host, nothing is copied.  The second set is allocated by the first fade
+ * push and kept for the next: A FADE DOUBLES THE RESPONSE MEMORY (the tail responses of 256 channels x 2^20 taps are
+ * 2 GB), and state_bytes() and workspace_bytes() count the second set from then on.
+ * Schedule: a head block of a fade runs one forward transform (and the tail's at phase 0), the stage kernel, ONE
+ * k_nupc_mac launch of up to four jobs (head and tail slice under A and under B), the two head inverses, k_nupc_fade_mix
+ * and, after phase m - 1, both tail inverses.  A call of K blocks that meets a fade runs the fade's blocks one at a time
+ * and what follows the fade on the usual route.
+ * Refusals (the state is untouched in each): fade_blocks < 1, fade_blocks * pts0 > 2^31 - 1 or any argument error of
+ * push_ir_dev: CLFA_INVALID_VALUE; a fade push, a plain push_ir / push_ir_dev, or a reset while fade_remaining() > 0:
+ * CLFA_INVALID_OPERATION; a fade push on a capturing stream: CLFA_INVALID_OPERATION.  The argument checks come before
+ * the device is looked at; a failed object answers with its error. */
 CLFA_API int clfa_nupconv_create(clfa_nupconv **pc, int device, int cvs, int pts0, int pts1, int channels);
 CLFA_API void clfa_nupconv_destroy(clfa_nupconv *pc);
 CLFA_API int clfa_nupconv_get_error(const clfa_nupconv *pc);
@@ -1036,14 +1070,20 @@ CLFA_API const char *clfa_nupconv_get_log(const clfa_nupconv *pc);
 CLFA_API int clfa_nupconv_nparts(const clfa_nupconv *pc, int level);
 /* head blocks since creation or the last reset */
 CLFA_API long clfa_nupconv_position(const clfa_nupconv *pc);
-/* both levels' rings, responses and tails, the stage row and the pending tail output; the tail block's accumulators and
- * the head's sub-batch workspaces (grown by the call that needs more blocks than any before it) */
+/* both levels' rings, responses and tails, the stage row and the pending tail output (+ a fade's second responses, tails
+ * and pending row); the tail block's accumulators and the head's sub-batch workspaces (grown by the call that needs more
+ * blocks than any before it; + a fade's second accumulators and head row) */
 CLFA_API size_t clfa_nupconv_state_bytes(const clfa_nupconv *pc);
 CLFA_API size_t clfa_nupconv_workspace_bytes(const clfa_nupconv *pc);
 /* "k_nupc_mac" ("" for a failed object) */
 CLFA_API const char *clfa_nupconv_kernel_name(const clfa_nupconv *pc);
 CLFA_API int clfa_nupconv_push_ir(clfa_nupconv *pc, const float *ir);
 CLFA_API int clfa_nupconv_push_ir_dev(clfa_nupconv *pc, const void *ir, long channel_stride, void *stream);
+CLFA_API int clfa_nupconv_push_ir_fade(clfa_nupconv *pc, const float *ir, long fade_blocks); /* host rows, blocking */
+CLFA_API int clfa_nupconv_push_ir_fade_dev(clfa_nupconv *pc, const void *ir, long channel_stride, long fade_blocks,
+                                           void *stream);
+/* head blocks of the fade not yet processed; 0 = none (and for a NULL handle) */
+CLFA_API long clfa_nupconv_fade_remaining(const clfa_nupconv *pc);
 CLFA_API int clfa_nupconv_process_dev(clfa_nupconv *pc, void *out, long out_stride, const void *in, long in_stride,
                                       long nblocks, void *stream);
 CLFA_API int clfa_nupconv_convolution(clfa_nupconv *pc, float *out, const float *in, long nblocks);

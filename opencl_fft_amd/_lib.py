@@ -91,6 +91,9 @@ SYMBOLS = [
     ("clfa_nupconv_kernel_name", C.c_char_p, [_vp]),
     ("clfa_nupconv_push_ir", C.c_int, [_vp, _vp]),
     ("clfa_nupconv_push_ir_dev", C.c_int, [_vp, _vp, C.c_long, _vp]),
+    ("clfa_nupconv_push_ir_fade", C.c_int, [_vp, _vp, C.c_long]),
+    ("clfa_nupconv_push_ir_fade_dev", C.c_int, [_vp, _vp, C.c_long, C.c_long, _vp]),
+    ("clfa_nupconv_fade_remaining", C.c_long, [_vp]),
     ("clfa_nupconv_process_dev", C.c_int, [_vp, _vp, C.c_long, _vp, C.c_long, C.c_long, _vp]),
     ("clfa_nupconv_convolution", C.c_int, [_vp, _vp, _vp, C.c_long]),
     ("clfa_nupconv_reset", C.c_int, [_vp, _vp]),

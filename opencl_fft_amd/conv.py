@@ -263,16 +263,23 @@ class Nupconv(_Object):
     def _need(self):
         return 2 * self.pts1 + self.nparts(1) * self.pts1
 
-    def push_ir(self, ir):
-        """ir: float32 (channels, >= 2*pts1 + nparts(1)*pts1), e.g. rows of cvs samples (1-D for one channel); blocking.
-        Exact at position % (pts1 // pts0) == 0; at another phase the tail block in progress mixes both responses."""
+    def _host_rows(self, ir):
+        """the packed rows of a host array of responses, None for a bad one"""
         ir = np.asarray(ir, dtype=np.float32)
         if ir.ndim == 1:
             ir = ir[None, :]
         need = self._need()
         if ir.ndim != 2 or ir.shape[0] != self.channels or ir.shape[1] < need:
+            return None
+        return np.ascontiguousarray(ir[:, :need])
+
+    def push_ir(self, ir):
+        """ir: float32 (channels, >= 2*pts1 + nparts(1)*pts1), e.g. rows of cvs samples (1-D for one channel); blocking.
+        Exact at position % (pts1 // pts0) == 0; at another phase the tail block in progress mixes both responses: for a
+        change at any phase, and without the step, use push_ir_fade."""
+        ir = self._host_rows(ir)
+        if ir is None:
             return CL_INVALID_VALUE
-        ir = np.ascontiguousarray(ir[:, :need])
         return _pkg.lib().clfa_nupconv_push_ir(self._h, ir.ctypes.data)
 
     def push_ir_device(self, ir, stream=None):
@@ -282,6 +289,27 @@ class Nupconv(_Object):
         if length < self._need():
             return CL_INVALID_VALUE
         return _pkg.lib().clfa_nupconv_push_ir_dev(self._h, ir.data_ptr(), stride, _stream_of(ir, stream))
+
+    def push_ir_fade(self, ir, fade_blocks):
+        """push_ir as a crossfade, at any phase: over the next fade_blocks head blocks the output moves linearly, sample by
+        sample, from what the responses in force give to what an object that always held `ir` gives on the same input
+        history (clfft_amd.h); blocking.  The first fade allocates a second response set: it doubles the response memory."""
+        ir = self._host_rows(ir)
+        if ir is None:
+            return CL_INVALID_VALUE
+        return _pkg.lib().clfa_nupconv_push_ir_fade(self._h, ir.ctypes.data, int(fade_blocks))
+
+    def push_ir_fade_device(self, ir, fade_blocks, stream=None):
+        """push_ir_device as a crossfade over the next fade_blocks head blocks.  Asynchronous on `stream`; not under graph
+        capture, and no other push and no reset while fade_remaining() > 0 (CL_INVALID_OPERATION)."""
+        length, stride = _block_rows(ir, self.channels, "channels", True)
+        if length < self._need():
+            return CL_INVALID_VALUE
+        return _pkg.lib().clfa_nupconv_push_ir_fade_dev(self._h, ir.data_ptr(), stride, int(fade_blocks), _stream_of(ir, stream))
+
+    def fade_remaining(self):
+        """head blocks of a pending crossfade that have not been processed yet; 0: none"""
+        return self._get("fade_remaining")
 
     def convolution(self, output, input):
         """whole signals on the host: float32 (channels, L) -> (channels, L) (1-D for one channel), L a multiple of

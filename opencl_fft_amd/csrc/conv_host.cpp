@@ -917,12 +917,33 @@ int clfa_pconv_matrix_convolution(clfa_pconv_matrix *p, float *out, const float 
 // non-uniformly partitioned convolution (pconv_nup.hip; the head is the blocks route of pconv_blocks.hip)
 // ---------------------------------------------------------------------------------
 
-// one level: its geometry, tables, input-spectra ring, response spectra, ring position
+// one level: its geometry, tables, input-spectra ring (`ring` frames: the tail keeps two more than its sum walks, the
+// history from which a fade push recomputes the second path), ring position
 struct NupLevel {
   PconvGeom g{};
+  int ring = 0;
   DevBuf half, w2f, w2i;
-  DevBuf ringA, ringB;
+  DevBuf ringA;
   int w = 0;
+};
+
+// what depends on the responses: both levels' spectra of them, the levels' overlap-add tails (a single block's inverse
+// reads one and writes the other; hcur / tcur: the one in force), the finished tail block's samples, being mixed in, and
+// the tail block's accumulators, filled slice by slice.  A fade runs two of these over the shared rings
+struct NupSet {
+  DevBuf ringB[2];
+  DevBuf tail0[2], tail1[2];
+  int hcur = 0, tcur = 0;
+  DevBuf pend, Y1;
+  size_t state_bytes() const {
+    return ringB[0].bytes + ringB[1].bytes + tail0[0].bytes + tail0[1].bytes + tail1[0].bytes + tail1[1].bytes + pend.bytes;
+  }
+  hipError_t clear_history(hipStream_t s) {   // (the responses stay)
+    for (DevBuf *b : {&tail0[0], &tail0[1], &tail1[0], &tail1[1], &pend})
+      if (hipError_t e = hipMemsetAsync(b->p, 0, b->bytes, s)) return e;
+    hcur = tcur = 0;
+    return hipSuccess;
+  }
 };
 
 struct clfa_nupconv {
@@ -932,11 +953,15 @@ struct clfa_nupconv {
   char log[256];
   hipStream_t stream = nullptr;
   NupLevel lv[2];                // the head (2m partitions of pts0) and the tail (n1 partitions of pts1)
-  DevBuf tail0[2], tail1[2];     // the levels' overlap-add tails: a single block's inverse reads one and writes the other
-  int hcur = 0, tcur = 0;        // ... the one in force
-  DevBuf stage, pend;            // the tail block being collected; the finished tail block's samples, being mixed in
-  DevBuf Y0, Y1;                 // a single head block's accumulators; the tail block's, filled slice by slice
-                                 // (a single block's X is its ring frame w)
+  NupSet sets[2];                // sets[cur]: the responses in force and their path.  sets[cur ^ 1]: the second path of a
+  int cur = 0;                   // timed crossfade (push_ir_fade), allocated by the first fade push and kept; it becomes
+                                 // the first, on the host, when the fade's last block is issued
+  NupSet &first() { return sets[cur]; }
+  NupSet &second() { return sets[cur ^ 1]; }
+  DevBuf stage;                  // the tail block being collected
+  DevBuf Y0;                     // a single head block's accumulators (a single block's X is its ring frame w)
+  DevBuf Y0b, headb;             // a fade: the second path's head accumulators and head samples (channels x pts0)
+  long fade_len = 0, fade_done = 0;   // head blocks of the pending fade (0: none) and how many of them have been processed
   DevBuf bX, bY, btail;          // the head's sub-batch workspaces, for hcap blocks (grown by the call that needs more)
   int hcap = 0, bcap = 1, bkt = 4;
   DevBuf in1, in2, out;          // staging of the blocking form (conv_arrays; in2 stays empty)
@@ -947,6 +972,18 @@ struct clfa_nupconv {
 
 static BlockShape block_shape(const clfa_nupconv *p) { return {p->pts0, p->channels, p->channels}; }
 static long nup_ir_len(const clfa_nupconv *p) { return 2L * p->pts1 + (long)p->lv[1].g.nparts * p->pts1; }
+
+// a set's buffers (kept once they exist)
+static int nup_alloc_set(const clfa_nupconv *p, NupSet &b) {
+  const size_t ch = (size_t)p->channels;
+  int e;
+  for (int i = 0; i < 2; i++)
+    if ((e = b.ringB[i].ensure(sizeof(cpx) * ch * p->lv[i].g.nparts * p->lv[i].g.bins)) ||
+        (e = b.tail0[i].ensure(sizeof(float) * ch * p->pts0)) || (e = b.tail1[i].ensure(sizeof(float) * ch * p->pts1)))
+      return e;
+  if ((e = b.pend.ensure(sizeof(float) * ch * p->pts1)) || (e = b.Y1.ensure(sizeof(cpx) * ch * p->pts1))) return e;
+  return CLFA_SUCCESS;
+}
 
 static int nup_setup(clfa_nupconv *p, int device, int cvs, int pts0, int pts1, int channels) {
   p->log[0] = 0;
@@ -974,6 +1011,8 @@ static int nup_setup(clfa_nupconv *p, int device, int cvs, int pts0, int pts1, i
   p->m = pts1 / pts0;
   p->lv[0].g = {ilog2(pts0), pts0, 2 * p->m, channels};
   p->lv[1].g = {ilog2(pts1), pts1, (cvs - 2 * pts1) / pts1, channels};   // floor: remainder samples are dropped
+  p->lv[0].ring = p->lv[0].g.nparts;
+  p->lv[1].ring = p->lv[1].g.nparts + 2;
   int e = device_info(device, p->di);
   if (e) return e;
   p->bcap = subbatch_cap(3L * channels * pts0 * (long)sizeof(cpx), "CLFA_PCONV_BLOCKS_MAX");   // as Clpconv's blocks route
@@ -982,28 +1021,25 @@ static int nup_setup(clfa_nupconv *p, int device, int cvs, int pts0, int pts1, i
   HIP_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
   for (NupLevel &l : p->lv) {
     if ((e = upload_conv_tables(l.g.bins, l.half, l.w2f, l.w2i))) return e;
-    const size_t ring = sizeof(cpx) * (size_t)channels * l.g.nparts * l.g.bins;
-    if ((e = l.ringA.ensure(ring)) || (e = l.ringB.ensure(ring))) return e;
-    HIP_TRY(hipMemsetAsync(l.ringA.p, 0, ring, p->stream));
-    HIP_TRY(hipMemsetAsync(l.ringB.p, 0, ring, p->stream));
+    if ((e = l.ringA.ensure(sizeof(cpx) * (size_t)channels * l.ring * l.g.bins))) return e;
+    HIP_TRY(hipMemsetAsync(l.ringA.p, 0, l.ringA.bytes, p->stream));
   }
-  const size_t row0 = sizeof(float) * (size_t)channels * pts0, row1 = sizeof(float) * (size_t)channels * pts1;
-  if ((e = p->tail0[0].ensure(row0)) || (e = p->tail0[1].ensure(row0)) || (e = p->tail1[0].ensure(row1)) ||
-      (e = p->tail1[1].ensure(row1)) || (e = p->stage.ensure(row1)) || (e = p->pend.ensure(row1)) ||
-      (e = p->Y0.ensure(sizeof(cpx) * (size_t)channels * pts0)) || (e = p->Y1.ensure(sizeof(cpx) * (size_t)channels * pts1)))
+  NupSet &a = p->first();
+  if ((e = nup_alloc_set(p, a)) || (e = p->stage.ensure(sizeof(float) * (size_t)channels * pts1)) ||
+      (e = p->Y0.ensure(sizeof(cpx) * (size_t)channels * pts0)))
     return e;
-  for (DevBuf *b : {&p->tail0[0], &p->tail0[1], &p->tail1[0], &p->tail1[1], &p->stage, &p->pend})
-    HIP_TRY(hipMemsetAsync(b->p, 0, b->bytes, p->stream));
+  for (DevBuf *b : {&a.ringB[0], &a.ringB[1], &p->stage}) HIP_TRY(hipMemsetAsync(b->p, 0, b->bytes, p->stream));
+  HIP_TRY(a.clear_history(p->stream));
   HIP_TRY(hipStreamSynchronize(p->stream));
   return CLFA_SUCCESS;
 }
 
 // partition i of every row -> response frame nparts - 1 - i of the level (the frame the MAC pairs with the i-th newest
 // input block), with the blocks route's forward transform: the bits Clpconv's push gives
-static int nup_push_level(const NupLevel &l, const float *ir, long stride, hipStream_t s) {
+static int nup_push_level(const NupLevel &l, const DevBuf &ringB, const float *ir, long stride, hipStream_t s) {
   const int aligned = ((uintptr_t)ir & 7) == 0 && (stride & 1) == 0;
   for (int i = 0; i < l.g.nparts; i++)
-    HIP_TRY(launch_pconvb_forward(l.g.logb, ir + (long)i * l.g.bins, stride, (cpx *)l.ringB.p + (long)(l.g.nparts - 1 - i) * l.g.bins,
+    HIP_TRY(launch_pconvb_forward(l.g.logb, ir + (long)i * l.g.bins, stride, (cpx *)ringB.p + (long)(l.g.nparts - 1 - i) * l.g.bins,
                                   1, l.g.nparts, l.g.channels, aligned, (const cpx *)l.half.p, (const cpx *)l.w2f.p, s));
   return CLFA_SUCCESS;
 }
@@ -1011,6 +1047,7 @@ static int nup_push_level(const NupLevel &l, const float *ir, long stride, hipSt
 // the head's K blocks through the blocks route, sub-batch by sub-batch, as clfa_pconv_process_blocks_dev
 static int nup_head(clfa_nupconv *p, float *out, long out_stride, const float *in, long in_stride, long nblocks, hipStream_t s) {
   NupLevel &l = p->lv[0];
+  NupSet &set = p->first();
   PconvBlocks a;
   a.g = l.g;
   a.cap = p->hcap;
@@ -1020,8 +1057,8 @@ static int nup_head(clfa_nupconv *p, float *out, long out_stride, const float *i
   a.aligned_in = ((uintptr_t)in & 7) == 0 && (in_stride & 1) == 0;
   a.aligned_out = ((uintptr_t)out & 7) == 0 && (out_stride & 1) == 0;
   a.ringA = (cpx *)l.ringA.p;
-  a.ringB = (cpx *)l.ringB.p;
-  a.tail = (float *)p->tail0[p->hcur].p;
+  a.ringB = (cpx *)set.ringB[0].p;
+  a.tail = (float *)set.tail0[set.hcur].p;
   a.X = (cpx *)p->bX.p;
   a.Y = (cpx *)p->bY.p;
   a.tail_ws = (float *)p->btail.p;
@@ -1035,6 +1072,155 @@ static int nup_head(clfa_nupconv *p, float *out, long out_stride, const float *i
     a.out = out + j0 * p->pts0;
     HIP_TRY(launch_pconv_blocks(a, s));
     l.w = (int)((l.w + a.K) % l.g.nparts);
+  }
+  return CLFA_SUCCESS;
+}
+
+// h[0 : 2*pts1) in the head's partitions, h[2*pts1 : 2*pts1 + n1*pts1) in the tail's, in stream order
+static int nup_push_levels(const clfa_nupconv *p, const DevBuf &ringB0, const DevBuf &ringB1, const float *ir, long stride,
+                           hipStream_t s) {
+  if (int e = nup_push_level(p->lv[0], ringB0, ir, stride, s)) return e;
+  return nup_push_level(p->lv[1], ringB1, ir + 2L * p->pts1, stride, s);
+}
+
+// one block of a level, single-block route.  forward: its samples -> ring frame w (committing it is the caller's w + 1)
+static int nup_forward(const NupLevel &l, const float *in, long in_stride, hipStream_t s) {
+  HIP_TRY(launch_pconvb_forward(l.g.logb, in, in_stride, (cpx *)l.ringA.p + (long)l.w * l.g.bins, 1, l.ring, l.g.channels,
+                                ((uintptr_t)in & 7) == 0 && (in_stride & 1) == 0, (const cpx *)l.half.p, (const cpx *)l.w2f.p, s));
+  return CLFA_SUCCESS;
+}
+// ... the multiply-accumulate of items [item0, item0 + nitems) of the block in frame w under the responses ringB, into Y
+static NupcMacJob nup_job(const NupLevel &l, const DevBuf &ringB, const DevBuf &Y, int w, int item0, int nitems) {
+  return {(const cpx *)l.ringA.p, (const cpx *)ringB.p, (cpx *)Y.p, w, l.g.bins, l.g.nparts, l.ring, item0, nitems};
+}
+// ... inverse transform and overlap-add: Y and the tail in force -> out, the other tail, which comes into force
+static int nup_inverse(const NupLevel &l, const DevBuf &Y, DevBuf (&tails)[2], int &cur, float *out, long out_stride, hipStream_t s) {
+  HIP_TRY(launch_pconvb_inverse(l.g.logb, (const cpx *)Y.p, (const float *)tails[cur].p, (float *)tails[cur ^ 1].p, out, out_stride, 1, 1,
+                                1, l.g.channels, ((uintptr_t)out & 7) == 0 && (out_stride & 1) == 0, (const cpx *)l.half.p,
+                                (const cpx *)l.w2i.p, s));
+  cur ^= 1;
+  return CLFA_SUCCESS;
+}
+
+// nblocks >= 1 blocks outside a fade.  One block: the head's forward transform straight into its ring frame, its
+// multiply-accumulate beside the tail's slice in one launch of k_nupc_mac, its inverse.  Several blocks: the head through
+// the blocks route over the whole call.  The arithmetic of a bin is the same on both ways, and both leave the same rings,
+// tails and positions.
+static int nup_blocks(clfa_nupconv *p, float *o, long out_stride, const float *x, long in_stride, long nblocks, hipStream_t s) {
+  const long pts0 = p->pts0, m = p->m;
+  const int ch = p->channels;
+  const bool single = nblocks == 1;
+  NupLevel &h = p->lv[0], &t = p->lv[1];
+  NupSet &a = p->first();
+  if (!single)
+    if (int e = nup_head(p, o, out_stride, x, in_stride, nblocks, s)) return e;
+  // the tail, period by period: head blocks [j0, j0 + k) of the call are phases [sa, sb) of period P, in which tail block
+  // P - 1 is multiplied and tail block P - 2 is heard
+  const int hb0 = (int)(pts0 / 2);
+  for (long j0 = 0; j0 < nblocks;) {
+    const long P = p->c / m;
+    const int sa = (int)(p->c % m);
+    const long k = nblocks - j0 < m - sa ? nblocks - j0 : m - sa;
+    const int sb = sa + (int)k, off = sa * (int)pts0, n = (int)(k * pts0);
+    if (single)
+      if (int e = nup_forward(h, x, in_stride, s)) return e;
+    // phase 0: the spectrum of the finished block, before this period's samples overwrite the row
+    if (P >= 1 && sa == 0)
+      if (int e = nup_forward(t, (const float *)p->stage.p, p->pts1, s)) return e;
+    HIP_TRY(launch_nupc_stage(x + j0 * pts0, in_stride, (float *)p->stage.p, p->pts1, off, n, ch, s));
+    NupcMacJob jobs[2];
+    int njobs = 0;
+    if (single) jobs[njobs++] = nup_job(h, a.ringB[0], p->Y0, h.w, 0, hb0);
+    if (P >= 1) jobs[njobs++] = nup_job(t, a.ringB[1], a.Y1, t.w, sa * hb0, (sb - sa) * hb0);
+    if (njobs) HIP_TRY(launch_nupc_mac(jobs, njobs, ch, s));
+    if (single) {
+      if (int e = nup_inverse(h, p->Y0, a.tail0, a.hcur, o, out_stride, s)) return e;
+      h.w = (h.w + 1) % h.ring;
+    }
+    HIP_TRY(launch_nupc_mix(o + j0 * pts0, out_stride, (const float *)a.pend.p, p->pts1, off, n, ch, s));
+    // after slice m - 1: the block's samples replace the ones just heard, its spectrum stays in the ring
+    if (P >= 1 && sb == m) {
+      if (int e = nup_inverse(t, a.Y1, a.tail1, a.tcur, (float *)a.pend.p, p->pts1, s)) return e;
+      t.w = (t.w + 1) % t.ring;
+    }
+    p->c += k;
+    j0 += k;
+  }
+  return CLFA_SUCCESS;
+}
+
+// One head block of a fade, on the single-block route with every response-dependent step run for both sets over the
+// shared rings: the four multiply-accumulates are one launch, the first path's head goes to the output rows and the
+// second's to headb, and k_nupc_fade_mix forms both paths' head + pending sums and a + g * (b - a).  After the fade's last
+// block the second set becomes the first (nothing is copied; the object is not capturable, so no address has to stay
+// fixed).
+static int nup_fade_block(clfa_nupconv *p, float *o, long out_stride, const float *x, long in_stride, hipStream_t s) {
+  NupLevel &h = p->lv[0], &t = p->lv[1];
+  NupSet &a = p->first(), &b = p->second();
+  const int ch = p->channels, pts0 = p->pts0, m = p->m, hb0 = pts0 / 2;
+  const long P = p->c / m;
+  const int sa = (int)(p->c % m), off = sa * pts0;
+  if (int e = nup_forward(h, x, in_stride, s)) return e;
+  if (P >= 1 && sa == 0)
+    if (int e = nup_forward(t, (const float *)p->stage.p, p->pts1, s)) return e;
+  HIP_TRY(launch_nupc_stage(x, in_stride, (float *)p->stage.p, p->pts1, off, pts0, ch, s));
+  NupcMacJob jobs[kNupcMacJobs];
+  int njobs = 0;
+  jobs[njobs++] = nup_job(h, a.ringB[0], p->Y0, h.w, 0, hb0);
+  jobs[njobs++] = nup_job(h, b.ringB[0], p->Y0b, h.w, 0, hb0);
+  if (P >= 1) {
+    jobs[njobs++] = nup_job(t, a.ringB[1], a.Y1, t.w, sa * hb0, hb0);
+    jobs[njobs++] = nup_job(t, b.ringB[1], b.Y1, t.w, sa * hb0, hb0);
+  }
+  HIP_TRY(launch_nupc_mac(jobs, njobs, ch, s));
+  int e;
+  if ((e = nup_inverse(h, p->Y0, a.tail0, a.hcur, o, out_stride, s)) ||
+      (e = nup_inverse(h, p->Y0b, b.tail0, b.hcur, (float *)p->headb.p, pts0, s)))
+    return e;
+  h.w = (h.w + 1) % h.ring;
+  HIP_TRY(launch_nupc_fade_mix(o, out_stride, (const float *)p->headb.p, (const float *)a.pend.p, (const float *)b.pend.p, p->pts1,
+                               off, pts0, ch, p->fade_done * pts0, (float)(p->fade_len * pts0), s));
+  if (P >= 1 && sa == m - 1) {
+    if ((e = nup_inverse(t, a.Y1, a.tail1, a.tcur, (float *)a.pend.p, p->pts1, s)) ||
+        (e = nup_inverse(t, b.Y1, b.tail1, b.tcur, (float *)b.pend.p, p->pts1, s)))
+      return e;
+    t.w = (t.w + 1) % t.ring;
+  }
+  p->c++;
+  if (++p->fade_done == p->fade_len) {
+    p->cur ^= 1;
+    p->fade_len = p->fade_done = 0;
+  }
+  return CLFA_SUCCESS;
+}
+
+// The second set's history at position c = P * m + sa, recomputed under its responses from the rings alone with the plain
+// path's kernels, hence with its bits: the head's tail from head block c - 1; the tail level's tail, pending row and tail
+// again from tail blocks P - 3 and P - 2 (whole blocks in one multiply-accumulate: a bin's sum does not depend on how the
+// bins are cut into slices); slices [0, sa) of tail block P - 1, in progress.  A block of negative index is not computed:
+// what it would have left is the +0 the rows are cleared to.  Tail block P - 3 reads back to input block P - 2 - n1, which
+// is why the tail's ring keeps n1 + 2 frames.
+static int nup_prime(clfa_nupconv *p, hipStream_t s) {
+  NupLevel &h = p->lv[0], &t = p->lv[1];
+  NupSet &b = p->second();
+  const int ch = p->channels, hb0 = p->pts0 / 2;
+  const long P = p->c / p->m;
+  const int sa = (int)(p->c % p->m);
+  HIP_TRY(b.clear_history(s));
+  const auto back = [](const NupLevel &l, int k) { return (l.w - k + l.ring) % l.ring; };   // the frame k blocks before frame w
+  // a whole block of level l in frame w: multiply-accumulate, inverse (the samples: to `out`)
+  const auto block = [&](const NupLevel &l, const DevBuf &ringB, const DevBuf &Y, int w, DevBuf (&tails)[2], int &cur, float *out) {
+    const NupcMacJob job = nup_job(l, ringB, Y, w, 0, l.g.bins / 2);
+    HIP_TRY(launch_nupc_mac(&job, 1, ch, s));
+    return nup_inverse(l, Y, tails, cur, out, l.g.bins, s);
+  };
+  int e;
+  if (p->c >= 1 && (e = block(h, b.ringB[0], p->Y0b, back(h, 1), b.tail0, b.hcur, (float *)p->headb.p))) return e;
+  if (P >= 3 && (e = block(t, b.ringB[1], b.Y1, back(t, 2), b.tail1, b.tcur, (float *)b.pend.p))) return e;
+  if (P >= 2 && (e = block(t, b.ringB[1], b.Y1, back(t, 1), b.tail1, b.tcur, (float *)b.pend.p))) return e;
+  if (P >= 1 && sa > 0) {
+    const NupcMacJob job = nup_job(t, b.ringB[1], b.Y1, t.w, 0, sa * hb0);
+    HIP_TRY(launch_nupc_mac(&job, 1, ch, s));
   }
   return CLFA_SUCCESS;
 }
@@ -1055,52 +1241,82 @@ int clfa_nupconv_nparts(const clfa_nupconv *p, int level) {
 long clfa_nupconv_position(const clfa_nupconv *p) { return p ? p->c : 0; }
 size_t clfa_nupconv_state_bytes(const clfa_nupconv *p) {
   if (!p) return 0;
-  size_t n = p->tail0[0].bytes + p->tail0[1].bytes + p->tail1[0].bytes + p->tail1[1].bytes + p->stage.bytes + p->pend.bytes;
-  for (const NupLevel &l : p->lv) n += l.ringA.bytes + l.ringB.bytes;
-  return n;
+  return p->lv[0].ringA.bytes + p->lv[1].ringA.bytes + p->stage.bytes + p->sets[0].state_bytes() + p->sets[1].state_bytes();
 }
 size_t clfa_nupconv_workspace_bytes(const clfa_nupconv *p) {
-  return p ? p->Y0.bytes + p->Y1.bytes + p->bX.bytes + p->bY.bytes + p->btail.bytes : 0;
+  return p ? p->Y0.bytes + p->sets[0].Y1.bytes + p->sets[1].Y1.bytes + p->Y0b.bytes + p->headb.bytes + p->bX.bytes + p->bY.bytes +
+                 p->btail.bytes
+           : 0;
 }
+long clfa_nupconv_fade_remaining(const clfa_nupconv *p) { return p ? p->fade_len - p->fade_done : 0; }
 const char *clfa_nupconv_kernel_name(const clfa_nupconv *p) { return !p || p->err ? "" : "k_nupc_mac"; }
 
 int clfa_nupconv_push_ir_dev(clfa_nupconv *p, const void *ir, long channel_stride, void *stream) {
   if (int e = obj_error(p)) return e;
   if (!device_rows_ok(ir) || channel_stride < nup_ir_len(p)) return CLFA_INVALID_VALUE;
+  if (p->fade_len) return CLFA_INVALID_OPERATION;   // a fade is pending: the responses are one end of it
   ENTER_DEVICE(p->di.device);
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(p->order.use(s));
-  // h[0 : 2*pts1) in the head's partitions, h[2*pts1 : 2*pts1 + n1*pts1) in the tail's, in stream order
-  if (int e = nup_push_level(p->lv[0], (const float *)ir, channel_stride, s)) return e;
-  return nup_push_level(p->lv[1], (const float *)ir + 2L * p->pts1, channel_stride, s);
+  return nup_push_levels(p, p->first().ringB[0], p->first().ringB[1], (const float *)ir, channel_stride, s);
 }
 
 int clfa_nupconv_push_ir(clfa_nupconv *p, const float *ir) {
   if (int e = obj_error(p)) return e;
   if (!ir) return CLFA_INVALID_VALUE;
+  if (p->fade_len) return CLFA_INVALID_OPERATION;
   ENTER_DEVICE(p->di.device);
   const long len = nup_ir_len(p);
   return push_host(p, ir, sizeof(float) * (size_t)p->channels * len,
                    [&](const void *rows) { return clfa_nupconv_push_ir_dev(p, rows, len, p->stream); });
 }
 
+int clfa_nupconv_push_ir_fade_dev(clfa_nupconv *p, const void *ir, long channel_stride, long fade_blocks, void *stream) {
+  if (int e = obj_error(p)) return e;
+  if (!device_rows_ok(ir) || channel_stride < nup_ir_len(p) || fade_blocks < 1 || fade_blocks > 0x7fffffffL / p->pts0)
+    return CLFA_INVALID_VALUE;
+  if (p->fade_len) return CLFA_INVALID_OPERATION;   // one fade at a time
+  ENTER_DEVICE(p->di.device);
+  hipStream_t s = (hipStream_t)stream;
+  // everything the fade needs is allocated here, so that no process call allocates because of it: refused under capture
+  if (StreamOrder::capturing(s)) return CLFA_INVALID_OPERATION;
+  NupSet &b = p->second();
+  int e;
+  if ((e = nup_alloc_set(p, b)) || (e = p->Y0b.ensure(p->Y0.bytes)) || (e = p->headb.ensure(sizeof(float) * (size_t)p->channels * p->pts0)))
+    return e;
+  HIP_TRY(p->order.use(s));
+  // the rows' spectra into the second set (as push_ir_dev into the first), then that set's history from the rings
+  if ((e = nup_push_levels(p, b.ringB[0], b.ringB[1], (const float *)ir, channel_stride, s)) || (e = nup_prime(p, s))) return e;
+  p->fade_len = fade_blocks;
+  p->fade_done = 0;
+  return CLFA_SUCCESS;
+}
+
+int clfa_nupconv_push_ir_fade(clfa_nupconv *p, const float *ir, long fade_blocks) {
+  if (int e = obj_error(p)) return e;
+  if (!ir || fade_blocks < 1 || fade_blocks > 0x7fffffffL / p->pts0) return CLFA_INVALID_VALUE;
+  if (p->fade_len) return CLFA_INVALID_OPERATION;
+  ENTER_DEVICE(p->di.device);
+  const long len = nup_ir_len(p);
+  return push_host(p, ir, sizeof(float) * (size_t)p->channels * len,
+                   [&](const void *rows) { return clfa_nupconv_push_ir_fade_dev(p, rows, len, fade_blocks, p->stream); });
+}
+
 int clfa_nupconv_process_dev(clfa_nupconv *p, void *out, long out_stride, const void *in, long in_stride, long nblocks,
                              void *stream) {
   if (int e = obj_error(p)) return e;
-  const long pts0 = p->pts0, ch = p->channels, m = p->m;
+  const long pts0 = p->pts0, ch = p->channels;
   long len;
   if (int e = check_blocks_dev(nblocks, pts0, out, out_stride, ch, in, nullptr, in_stride, ch, &len)) return e;
   if (!len) return CLFA_SUCCESS;
   ENTER_DEVICE(p->di.device);
   hipStream_t s = (hipStream_t)stream;
-  // the phase of the schedule is host state, which a replay would not advance
+  // the phase of the schedule (and the progress of a fade) is host state, which a replay would not advance
   if (StreamOrder::capturing(s)) return CLFA_INVALID_OPERATION;
-  // One block: the head's forward transform straight into its ring frame, its multiply-accumulate beside the tail's slice
-  // in one launch of k_nupc_mac, its inverse.  Several blocks: the head through the blocks route over the whole call.  The
-  // arithmetic of a bin is the same on both ways, and both leave the same rings, tails and positions.
-  const bool single = nblocks == 1;
-  if (!single && nblocks > p->hcap) {
-    const int cap = (int)(nblocks < p->bcap ? nblocks : p->bcap);
+  // a fade's blocks run one at a time; what follows the fade in the same call takes the usual route
+  const long fade = p->fade_len - p->fade_done, nf = nblocks < fade ? nblocks : fade, rest = nblocks - nf;
+  if (rest > 1 && rest > p->hcap) {
+    const int cap = (int)(rest < p->bcap ? rest : p->bcap);
     if (cap > p->hcap) {
       const size_t frames = sizeof(cpx) * (size_t)ch * (size_t)cap * (size_t)pts0;
       if (int e = ensure_workspaces({{&p->bX, frames}, {&p->bY, frames}, {&p->btail, sizeof(float) * (size_t)ch * (size_t)pts0}}, s))
@@ -1111,51 +1327,9 @@ int clfa_nupconv_process_dev(clfa_nupconv *p, void *out, long out_stride, const 
   HIP_TRY(p->order.use(s));
   const float *x = (const float *)in;
   float *o = (float *)out;
-  NupLevel &h = p->lv[0], &t = p->lv[1];
-  if (!single)
-    if (int e = nup_head(p, o, out_stride, x, in_stride, nblocks, s)) return e;
-  // the tail, period by period: head blocks [j0, j0 + k) of the call are phases [sa, sb) of period P, in which tail block
-  // P - 1 is multiplied and tail block P - 2 is heard
-  const int hb0 = (int)(pts0 / 2);
-  for (long j0 = 0; j0 < nblocks;) {
-    const long P = p->c / m;
-    const int sa = (int)(p->c % m);
-    const long k = nblocks - j0 < m - sa ? nblocks - j0 : m - sa;
-    const int sb = sa + (int)k, off = sa * (int)pts0, n = (int)(k * pts0);
-    if (single)
-      HIP_TRY(launch_pconvb_forward(h.g.logb, x, in_stride, (cpx *)h.ringA.p + (long)h.w * h.g.bins, 1, h.g.nparts, (int)ch,
-                                    ((uintptr_t)x & 7) == 0 && (in_stride & 1) == 0, (const cpx *)h.half.p, (const cpx *)h.w2f.p, s));
-    // phase 0: the spectrum of the finished block, before this period's samples overwrite the row
-    if (P >= 1 && sa == 0)
-      HIP_TRY(launch_pconvb_forward(t.g.logb, (const float *)p->stage.p, p->pts1, (cpx *)t.ringA.p + (long)t.w * t.g.bins, 1,
-                                    t.g.nparts, (int)ch, 1, (const cpx *)t.half.p, (const cpx *)t.w2f.p, s));
-    HIP_TRY(launch_nupc_stage(x + j0 * pts0, in_stride, (float *)p->stage.p, p->pts1, off, n, (int)ch, s));
-    NupcMacJob jobs[2];
-    int njobs = 0;
-    if (single) jobs[njobs++] = {(const cpx *)h.ringA.p, (const cpx *)h.ringB.p, (cpx *)p->Y0.p, h.w, h.g.bins, h.g.nparts, 0, hb0};
-    if (P >= 1)
-      jobs[njobs++] = {(const cpx *)t.ringA.p, (const cpx *)t.ringB.p, (cpx *)p->Y1.p, t.w, t.g.bins, t.g.nparts, sa * hb0, (sb - sa) * hb0};
-    if (njobs) HIP_TRY(launch_nupc_mac(jobs, njobs, (int)ch, s));
-    if (single) {
-      HIP_TRY(launch_pconvb_inverse(h.g.logb, (const cpx *)p->Y0.p, (const float *)p->tail0[p->hcur].p,
-                                    (float *)p->tail0[p->hcur ^ 1].p, o, out_stride, 1, 1, 1, (int)ch,
-                                    ((uintptr_t)o & 7) == 0 && (out_stride & 1) == 0, (const cpx *)h.half.p, (const cpx *)h.w2i.p, s));
-      p->hcur ^= 1;
-      h.w = (h.w + 1) % h.g.nparts;
-    }
-    HIP_TRY(launch_nupc_mix(o + j0 * pts0, out_stride, (const float *)p->pend.p, p->pts1, off, n, (int)ch, s));
-    // after slice m - 1: the block's samples replace the ones just heard, its spectrum stays in the ring
-    if (P >= 1 && sb == m) {
-      HIP_TRY(launch_pconvb_inverse(t.g.logb, (const cpx *)p->Y1.p, (const float *)p->tail1[p->tcur].p,
-                                    (float *)p->tail1[p->tcur ^ 1].p, (float *)p->pend.p, p->pts1, 1, 1, 1, (int)ch, 1,
-                                    (const cpx *)t.half.p, (const cpx *)t.w2i.p, s));
-      p->tcur ^= 1;
-      t.w = (t.w + 1) % t.g.nparts;
-    }
-    p->c += k;
-    j0 += k;
-  }
-  return CLFA_SUCCESS;
+  for (long j = 0; j < nf; j++)
+    if (int e = nup_fade_block(p, o + j * pts0, out_stride, x + j * pts0, in_stride, s)) return e;
+  return rest ? nup_blocks(p, o + nf * pts0, out_stride, x + nf * pts0, in_stride, rest, s) : CLFA_SUCCESS;
 }
 
 int clfa_nupconv_convolution(clfa_nupconv *p, float *out, const float *in, long nblocks) {
@@ -1169,15 +1343,15 @@ int clfa_nupconv_reset(clfa_nupconv *p, void *stream) {
   ENTER_DEVICE(p->di.device);
   hipStream_t s = (hipStream_t)stream;
   if (StreamOrder::capturing(s)) return CLFA_INVALID_OPERATION;
+  if (p->fade_len) return CLFA_INVALID_OPERATION;   // a fade is pending: finish it first
   HIP_TRY(p->order.use(s));
   // the input history, the tails and the blocks in progress; the responses stay
   for (NupLevel &l : p->lv) {
     HIP_TRY(hipMemsetAsync(l.ringA.p, 0, l.ringA.bytes, s));
     l.w = 0;
   }
-  for (DevBuf *b : {&p->tail0[0], &p->tail0[1], &p->tail1[0], &p->tail1[1], &p->stage, &p->pend})
-    HIP_TRY(hipMemsetAsync(b->p, 0, b->bytes, s));
-  p->hcur = p->tcur = 0;
+  HIP_TRY(hipMemsetAsync(p->stage.p, 0, p->stage.bytes, s));
+  HIP_TRY(p->first().clear_history(s));
   p->c = 0;
   return CLFA_SUCCESS;
 }

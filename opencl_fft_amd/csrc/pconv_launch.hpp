@@ -125,15 +125,21 @@ hipError_t launch_nupc_stage(const float *in, long in_stride, float *stage, int 
 // out = out + pend[off .. off + n): out holds the head's samples
 hipError_t launch_nupc_mix(float *out, long out_stride, const float *pend, int pts1, int off, int n, int channels,
                            hipStream_t s);
+// a fade's block: a = out + pendA[off .. off + n), b = headB + pendB[off .. off + n), out = a + g * (b - a), each operation
+// rounded on its own, g = (float)(n0 + k) / N for sample k of the row; headB: channels x n floats, the second path's head
+hipError_t launch_nupc_fade_mix(float *out, long out_stride, const float *headB, const float *pendA, const float *pendB, int pts1,
+                                int off, int n, int channels, long n0, float N, hipStream_t s);
 // Y (channels x bins complex) items [item0, item0 + nitems) of 16 bytes = the sum over the nparts partitions, ascending, of
-// ring A frame (w - (nparts - 1) + p) mod nparts times ring B frame p: w is the frame that holds the new block.  One or two
-// jobs (the head's block, the tail's slice) side by side in one launch
+// ring A frame (w - (nparts - 1) + p) mod ring times ring B frame p: w is the frame that holds the new block, ring >= nparts
+// the frames ring A holds per channel (it may keep more history than the sum walks).  One or two jobs (the head's block,
+// the tail's slice) side by side in one launch; up to four in a fade (each under both response sets)
 struct NupcMacJob {
-  const cpx *ringA = nullptr, *ringB = nullptr;   // channels x nparts x bins
+  const cpx *ringA = nullptr, *ringB = nullptr;   // channels x ring x bins, channels x nparts x bins
   cpx *Y = nullptr;
-  int w = 0, bins = 0, nparts = 0, item0 = 0, nitems = 0;
+  int w = 0, bins = 0, nparts = 0, ring = 0, item0 = 0, nitems = 0;
 };
 constexpr int kNupcMacDepth = 16;   // partitions whose loads are in flight per lane
+constexpr int kNupcMacJobs = 4;
 hipError_t launch_nupc_mac(const NupcMacJob *jobs, int njobs, int channels, hipStream_t s);
 constexpr int kPconvMaxLogBins = 15;  // pts up to 32768 (the reference harness' largest, csound/tests.py:13)
 // ends of the composed chain used when bins exceed the LDS FFT sizes

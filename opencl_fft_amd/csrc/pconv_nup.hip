@@ -7,6 +7,7 @@
 //                  products of k_pconvb_mac — the bits of Clpconv's blocks route, however the bins are cut into slices.
 //                  A single-block call runs the head's block and the tail's slice in one launch of it
 //   k_nupc_mix     out = head + pending tail output at the stream's position, one float32 addition, the head first
+//   k_nupc_fade_mix  a block of a timed crossfade (clfft_amd.h): both paths' head + pending sums, then a + g * (b - a)
 // The forward and inverse transforms are launch_pconvb_forward / launch_pconvb_inverse with K = 1; calls of several blocks
 // run the head through launch_pconv_blocks.  A new block's spectrum goes straight into ring frame w, the one frame the
 // multiply-accumulate of the block before it does not read; committing it is the host's w + 1.
@@ -58,33 +59,67 @@ __global__ __launch_bounds__(256) void k_nupc_mix(float *out, long out_stride, c
 }
 
 // ---------------------------------------------------------------------------------
+// fade mix: a = out + pendA (the first path, as k_nupc_mix), b = headB + pendB (the second), out = a + g * (b - a) with
+// g = (float)n / N, n = n0 + the sample's index in the row: a division, a subtraction, a multiplication and an addition,
+// each rounded on its own
+// ---------------------------------------------------------------------------------
+template <int V>
+__global__ __launch_bounds__(256) void k_nupc_fade_mix(float *out, long out_stride, const float *__restrict__ headB,
+                                                       const float *__restrict__ pendA, const float *__restrict__ pendB, int pts1,
+                                                       int off, int n, int channels, long n0, float N) {
+#pragma clang fp contract(off)
+  typedef typename RowUnit<V>::type U;
+  const int nu = n / V;
+  const long total = (long)channels * nu;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const int ch = (int)(i / nu), k = (int)(i % nu) * V;
+    U *o = reinterpret_cast<U *>(out + (long)ch * out_stride + k);
+    const U a = *o + *reinterpret_cast<const U *>(pendA + (long)ch * pts1 + off + k);
+    const U b = *reinterpret_cast<const U *>(headB + (long)ch * n + k) + *reinterpret_cast<const U *>(pendB + (long)ch * pts1 + off + k);
+    U g;
+    if constexpr (V == 1) {
+      g = (float)(n0 + k) / N;
+    } else {
+#pragma unroll
+      for (int v = 0; v < V; v++) g[v] = (float)(n0 + k + v) / N;
+    }
+    const U d = b - a;
+    const U gd = g * d;
+    *o = a + gd;
+  }
+}
+
+// ---------------------------------------------------------------------------------
 // multiply-accumulate of ONE block of a level over items [item0, item0 + nitems) of every channel: one lane = (channel,
 // item), the lanes laid over both together, so that a slice of 16 items still fills its waves.  The partitions are one
 // serial chain per lane (the order is the result's bits), so what hides the memory latency is depth: the loads of D
 // partitions are in flight together.  blockIdx.y picks the job: a single-block call runs the head's block (all its items)
-// and the tail's slice side by side in one launch.
+// and the tail's slice side by side in one launch (NJ = 2); a fade's block runs both under both response sets (NJ = 4).
 // ---------------------------------------------------------------------------------
-template <int D>
-__global__ __launch_bounds__(64) void k_nupc_mac(NupcMacJob job0, NupcMacJob job1, int channels) {
-  const NupcMacJob &job = blockIdx.y ? job1 : job0;
+template <int NJ> struct NupcMacJobs { NupcMacJob j[NJ]; };
+
+template <int D, int NJ>
+__global__ __launch_bounds__(64) void k_nupc_mac(NupcMacJobs<NJ> jobs, int channels) {
+  static_assert(NJ == 2 || NJ == kNupcMacJobs, "two jobs, or a fade's four");
+  const NupcMacJob &job = NJ > 2 && blockIdx.y >= 2 ? (blockIdx.y == 3 ? jobs.j[NJ - 1] : jobs.j[NJ - 2]) : (blockIdx.y ? jobs.j[1] : jobs.j[0]);
   const cpx *__restrict__ ringA = job.ringA;
   const cpx *__restrict__ ringB = job.ringB;
   cpx *__restrict__ Y = job.Y;
-  const int w = job.w, bins = job.bins, nparts = job.nparts, item0 = job.item0, nitems = job.nitems;
+  const int w = job.w, bins = job.bins, nparts = job.nparts, ring = job.ring, item0 = job.item0, nitems = job.nitems;
   if (blockIdx.x * 64L >= (long)channels * nitems) return;   // (the grid is the larger job's)
   const int hb = bins >> 1;
   const long total = (long)channels * nitems;
   const long gid = blockIdx.x * 64L + threadIdx.x;
   const long g = gid < total ? gid : total - 1;   // (clamped: straight-line loads; the store is guarded)
   const int ch = (int)(g / nitems), item = item0 + (int)(g % nitems);
-  const cpx2 *ra = reinterpret_cast<const cpx2 *>(ringA + (long)ch * nparts * bins) + item;
+  const cpx2 *ra = reinterpret_cast<const cpx2 *>(ringA + (long)ch * ring * bins) + item;
   const cpx2 *rb = reinterpret_cast<const cpx2 *>(ringB + (long)ch * nparts * bins) + item;
-  // input frame of partition p: block (p - (nparts - 1)) counted from the new one, ring frame (w + that) mod nparts; the
+  // input frame of partition p: block (p - (nparts - 1)) counted from the new one, ring frame (w + that) mod ring; the
   // new block's own spectrum is frame w (p = nparts - 1).  Past the last partition: clamped, never used
   auto frame = [&](int p) -> const cpx2 * {
     p = p < nparts ? p : nparts - 1;
     int f = w - (nparts - 1) + p;
-    f = f < 0 ? f + nparts : f;
+    f = f < 0 ? f + ring : f;
     return ra + (long)f * hb;
   };
   auto resp = [&](int p) -> const cpx2 * { return rb + (long)(p < nparts ? p : nparts - 1) * hb; };
@@ -144,17 +179,38 @@ hipError_t launch_nupc_mix(float *out, long out_stride, const float *pend, int p
   return hipGetLastError();
 }
 
+hipError_t launch_nupc_fade_mix(float *out, long out_stride, const float *headB, const float *pendA, const float *pendB, int pts1,
+                                int off, int n, int channels, long n0, float N, hipStream_t s) {
+  if (n < 1 || (n & 31) || (off & 31) || off + n > pts1 || n0 < 0 || !(N > 0.f)) return hipErrorInvalidValue;
+  const bool v4 = rows_16(out, out_stride) && rows_16(headB, n);   // (the pending rows: as launch_nupc_mix's)
+  const int grid = grid_clamp(((long)channels * (n / (v4 ? 4 : 1)) + 255) / 256, 4096);
+  if (v4)
+    hipLaunchKernelGGL(k_nupc_fade_mix<4>, dim3(grid), dim3(256), 0, s, out, out_stride, headB, pendA, pendB, pts1, off, n, channels, n0, N);
+  else
+    hipLaunchKernelGGL(k_nupc_fade_mix<1>, dim3(grid), dim3(256), 0, s, out, out_stride, headB, pendA, pendB, pts1, off, n, channels, n0, N);
+  return hipGetLastError();
+}
+
 hipError_t launch_nupc_mac(const NupcMacJob *jobs, int njobs, int channels, hipStream_t s) {
-  if (njobs < 1 || njobs > 2) return hipErrorInvalidValue;
+  if (njobs < 1 || njobs > kNupcMacJobs) return hipErrorInvalidValue;
   long blocks = 0;
   for (int i = 0; i < njobs; i++) {
     const NupcMacJob &j = jobs[i];
-    if (j.item0 < 0 || j.nitems < 1 || j.item0 + j.nitems > j.bins / 2 || j.w < 0 || j.w >= j.nparts) return hipErrorInvalidValue;
+    if (j.item0 < 0 || j.nitems < 1 || j.item0 + j.nitems > j.bins / 2 || j.nparts < 1 || j.ring < j.nparts || j.w < 0 || j.w >= j.ring)
+      return hipErrorInvalidValue;
     const long b = ((long)channels * j.nitems + 63) / 64;
     blocks = b > blocks ? b : blocks;
   }
   if (blocks > 0x7fffffffL) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_nupc_mac<kNupcMacDepth>, dim3((unsigned)blocks, njobs), dim3(64), 0, s, jobs[0], jobs[njobs - 1], channels);
+  // (jobs past njobs repeat the last one: blockIdx.y never picks them)
+  if (njobs > 2) {
+    NupcMacJobs<kNupcMacJobs> a;
+    for (int i = 0; i < kNupcMacJobs; i++) a.j[i] = jobs[i < njobs ? i : njobs - 1];
+    hipLaunchKernelGGL((k_nupc_mac<kNupcMacDepth, kNupcMacJobs>), dim3((unsigned)blocks, njobs), dim3(64), 0, s, a, channels);
+  } else {
+    const NupcMacJobs<2> a = {{jobs[0], jobs[njobs - 1]}};
+    hipLaunchKernelGGL((k_nupc_mac<kNupcMacDepth, 2>), dim3((unsigned)blocks, njobs), dim3(64), 0, s, a, channels);
+  }
   return hipGetLastError();
 }
 

@@ -8,8 +8,19 @@ read (the rings of both levels' slices / both whole rings), the rate they give, 
 (bandwidth_probe) to hold them against.  One line per shape records a whole-signal call of 1024 head blocks.
 
     python tools/time_nupconv.py [--periods 4] [--cvs 1048576] [--quick] [--out profiles/nupconv.txt]
+
+--fade: the timed crossfade of response changes (push_ir_fade), one line per shape, in three parts.  The plain path of
+this build against another build of the library (--parent-lib, the parent commit's libclfft_amd.so) in one process, both
+through the C ABI, in four alternating legs each, with two objects of the other build: every leg's median and worst
+phase, so that the difference between the builds' means can be held against what one build's own legs, and its own two
+objects, differ by.  A block of a fade (median, worst phase) against the
+composition it replaces: two Nupconv objects fed alike and the three torch operations of the mix.  And the fade push
+itself (the response transforms and the priming of the second path) beside a plain push.
+
+    python tools/time_nupconv.py --fade [--parent-lib old/libclfft_amd.so] [--out profiles/nupconv_fade.txt]
 """
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -102,23 +113,153 @@ def shape(cvs, pts0, pts1, channels, periods):
     return r
 
 
+class Raw:
+    """a Nupconv of one build of the library through its C ABI: what both builds of an A/B are called through"""
+
+    def __init__(self, lib, cvs, pts0, pts1, channels, stream):
+        self.lib, self.h, self.s = lib, C.c_void_p(), stream
+        assert lib.clfa_nupconv_create(C.byref(self.h), 0, cvs, pts0, pts1, channels) == 0
+
+    def push(self, h):
+        assert self.lib.clfa_nupconv_push_ir_dev(self.h, h.data_ptr(), h.stride(0), self.s) == 0
+
+    def push_fade(self, h, blocks):
+        assert self.lib.clfa_nupconv_push_ir_fade_dev(self.h, h.data_ptr(), h.stride(0), blocks, self.s) == 0
+
+    def run(self, out, x):
+        assert self.lib.clfa_nupconv_process_dev(self.h, out.data_ptr(), out.stride(0), x.data_ptr(), x.stride(0), 1, self.s) == 0
+
+    def position(self):
+        return self.lib.clfa_nupconv_position(self.h)
+
+    def close(self):
+        self.lib.clfa_nupconv_destroy(self.h)
+        self.h = None
+
+
+def other_build(path):
+    """another build of the library, its entry points typed like this one's (those it lacks are simply absent)"""
+    from opencl_fft_amd import _lib
+    lib = C.CDLL(path)
+    for name, res, args in _lib.SYMBOLS:
+        if hasattr(lib, name):
+            f = getattr(lib, name)
+            f.restype, f.argtypes = res, args
+    return lib
+
+
+def leg_stats(t):
+    """t: periods x phases, us -> the leg's median and worst phase (the slowest of the phases' medians over the periods)"""
+    by_phase = np.median(t, axis=0)
+    return {"median": round(float(np.median(t)), 2), "worst_phase": round(float(by_phase.max()), 2),
+            "worst_phase_index": int(by_phase.argmax())}
+
+
+def fade_shape(cvs, pts0, pts1, channels, periods, parent):
+    from opencl_fft_amd import _lib
+    m = pts1 // pts0
+    n = periods * m
+    s = torch.cuda.current_stream().cuda_stream
+    h = torch.rand((channels, cvs), device="cuda") - 0.5
+    h2 = torch.rand((channels, cvs), device="cuda") - 0.5
+    x = torch.rand((channels, pts0), device="cuda") - 0.5
+    out = torch.empty_like(x)
+    r = {"cvs": cvs, "pts0": pts0, "pts1": pts1, "channels": channels, "periods": periods}
+
+    def legs_of(run):
+        return leg_stats(calls(run, n).reshape(periods, m) * 1e3)
+
+    # the plain path: this build and the parent's in alternating legs
+    new = Raw(_lib.lib(), cvs, pts0, pts1, channels, s)
+    new.push(h)
+    builds = {"new": new}
+    if parent is not None:                      # two objects of the parent's: what two objects of ONE build differ by
+        for k in ("parent", "parent_2"):
+            builds[k] = Raw(parent, cvs, pts0, pts1, channels, s)
+            builds[k].push(h)
+    for b in builds.values():
+        calls(lambda: b.run(out, x), 2 * m)
+    plain = {k: [] for k in builds}
+    order = list(builds)
+    for _ in range(4):                          # forwards, backwards, ...: no object always follows the same other
+        for k in order:
+            assert builds[k].position() % m == 0
+            plain[k].append(legs_of(lambda: builds[k].run(out, x)))
+        order.reverse()
+    r["plain_us"] = plain
+    if parent is not None:
+        keys = ("median", "worst_phase")
+        mean = {b: {k: float(np.mean([l[k] for l in plain[b]])) for k in keys} for b in plain}
+        r["parent_leg_spread_us"] = {k: round(max(l[k] for l in plain["parent"]) - min(l[k] for l in plain["parent"]), 2) for k in keys}
+        r["parent_object_spread_us"] = {k: round(abs(mean["parent"][k] - mean["parent_2"][k]), 2) for k in keys}
+        r["new_minus_parent_us"] = {k: round(mean["new"][k] - (mean["parent"][k] + mean["parent_2"][k]) / 2, 2) for k in keys}
+        builds.pop("parent").close()
+        builds.pop("parent_2").close()
+    # a block of a fade against the composition it replaces: two objects fed alike and the mix in three torch operations
+    ca, cb = Raw(_lib.lib(), cvs, pts0, pts1, channels, s), Raw(_lib.lib(), cvs, pts0, pts1, channels, s)
+    ca.push(h)
+    cb.push(h2)
+    ya, yb, d = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
+    g = (torch.arange(pts0, device="cuda", dtype=torch.float32) / float(n * pts0)).expand_as(x).contiguous()
+
+    def composition():
+        ca.run(ya, x)
+        cb.run(yb, x)
+        torch.sub(yb, ya, out=d)
+        d.mul_(g)
+        torch.add(ya, d, out=out)
+
+    new.push_fade(h2, 2 * m)                    # warm-up: the first fade allocates the second set
+    calls(lambda: new.run(out, x), 2 * m)
+    calls(composition, 2 * m)
+    fade, comp = [], []
+    for leg in range(2):
+        assert new.position() % m == 0
+        new.push_fade(h if leg % 2 == 0 else h2, n)
+        fade.append(legs_of(lambda: new.run(out, x)))
+        comp.append(legs_of(composition))
+    r["fade_block_us"], r["composition_block_us"] = fade, comp
+    r["fade_over_composition"] = {k: round(float(np.mean([l[k] for l in fade]) / np.mean([l[k] for l in comp])), 3)
+                                  for k in ("median", "worst_phase")}
+    ca.close()
+    cb.close()
+    # the push: a fade push (response transforms and priming; phases 0, 1, 2 of a period past the third) beside a plain one
+    tf, tp = [], []
+    for k in range(3):
+        tf.append(calls(lambda: new.push_fade(h2 if k % 2 == 0 else h, 1), 1)[0])
+        new.run(out, x)
+    for k in range(3):
+        tp.append(calls(lambda: new.push(h), 1)[0])
+    r["push_ms"] = {"fade": round(float(np.median(tf)), 3), "plain": round(float(np.median(tp)), 3)}
+    r["state_mib_with_second_set"] = round(_lib.lib().clfa_nupconv_state_bytes(new.h) / 2 ** 20, 1)
+    new.close()
+    torch.cuda.synchronize()
+    return r
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--periods", type=int, default=4)
     ap.add_argument("--cvs", type=int, default=1 << 20)
     ap.add_argument("--quick", action="store_true", help="the one- and 16-channel shapes only")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--fade", action="store_true", help="the timed crossfade: plain path A/B, fade block, fade push")
+    ap.add_argument("--parent-lib", default=None, help="--fade: another build of libclfft_amd.so to hold the plain path against")
     a = ap.parse_args()
     assert a.periods >= 3, "at least three periods"
     assert torch.cuda.is_available(), "needs a GPU"
-    lines = [json.dumps({"device": fa.device_name(0), "how": __doc__.split("\n\n")[0].replace("\n", " ")})]
+    lines = [json.dumps({"device": fa.device_name(0), "how": __doc__.split("\n\n")[2 if a.fade else 0].replace("\n", " ")})]
     probe = {k: round(v, 3) for k, v in fa.bandwidth_probe(0, 1 << 30, 100).items()}
     lines.append(json.dumps({"bandwidth_probe_tb_s": probe}))
     print(lines[-1], flush=True)
+    parent = other_build(a.parent_lib) if a.fade and a.parent_lib else None
     for pts0, pts1, channels in SHAPES:
         if a.quick and channels > 16:
             continue
-        lines.append(json.dumps(shape(a.cvs, pts0, pts1, channels, a.periods)))
+        if a.fade:
+            lines.append(json.dumps(fade_shape(a.cvs, pts0, pts1, channels, a.periods, parent)))
+        else:
+            lines.append(json.dumps(shape(a.cvs, pts0, pts1, channels, a.periods)))
         print(lines[-1], flush=True)
     if a.out:
         with open(a.out, "w") as f:
