@@ -61,6 +61,7 @@ typedef struct clfa_dconv clfa_dconv; /* Cldconv object */
 typedef struct clfa_stft clfa_stft;   /* short-time analysis / overlap-add synthesis plan (extension) */
 typedef struct clfa_pconv_matrix clfa_pconv_matrix; /* convolution matrix: inputs mixed into outputs (extension) */
 typedef struct clfa_nupconv clfa_nupconv;           /* non-uniformly partitioned convolution, two levels (extension) */
+typedef struct clfa_nupconv_matrix clfa_nupconv_matrix; /* ... many inputs into many outputs (extension) */
 typedef struct clfa_pvoc clfa_pvoc;   /* phase vocoder on the clfa_stft spectra: (amp, freq) frames both ways (extension) */
 
 /* ---- library / devices ---------------------------------------------------- */
@@ -1088,6 +1089,76 @@ CLFA_API int clfa_nupconv_process_dev(clfa_nupconv *pc, void *out, long out_stri
                                       long nblocks, void *stream);
 CLFA_API int clfa_nupconv_convolution(clfa_nupconv *pc, float *out, const float *in, long nblocks);
 CLFA_API int clfa_nupconv_reset(clfa_nupconv *pc, void *stream);
+
+/* ---- non-uniformly partitioned convolution matrix (extension): many inputs into many outputs at low latency ----------
+ * `inputs` signals mixed into `outputs` signals, y_o = sum_i x_i * h_{o,i}, with long static responses at a latency of pts0
+ * samples: clfa_nupconv's two levels and schedule around clfa_pconv_matrix's sum over inputs.  Geometry as clfa_nupconv:
+ * powers of two with 32 <= pts0 < pts1 <= 4096, m = pts1 / pts0, cvs >= 3 * pts1; the head covers h[0 : 2*pts1) in 2m
+ * partitions of pts0, the tail h[2*pts1 : 2*pts1 + n1*pts1), n1 = floor((cvs - 2*pts1) / pts1), in partitions of pts1, the
+ * remainder of cvs is ignored; inputs >= 1, outputs >= 1.  Anything else: CLFA_INVALID_VALUE from create, the offending
+ * parameter (pts0, pts1, cvs, inputs, outputs) named in the log; the arguments are checked before the device is looked for.
+ * Responses: static; row (o, i) at (o * inputs + i) * row_stride floats, at least 2*pts1 + n1*pts1 floats each.
+ *
+ * Definition, bit for bit, for the input rows counted from creation or the last reset: let yh be what
+ * clfa_pconv_matrix(2*pts1, pts0, inputs, outputs) holding h[:, :, :2*pts1] returns for them, and yt what
+ * clfa_pconv_matrix(cvs - 2*pts1, pts1, inputs, outputs) holding h[:, :, 2*pts1:] returns, each of the two reducing in
+ * S = segments(level) segments in the matrix's documented order: the sequence r = i * nparts + p (p = 0 the oldest input
+ * frame) is cut at floor(s * inputs * nparts / S), every segment is one float32 accumulator per bin summed over its r
+ * ascending, and the segments are added as ((seg_0 + seg_1) + seg_2) + ...  (a matrix object created with
+ * CLFA_PCONV_MATRIX_SEGS = S reduces so).  Then y_o[n] = yh_o[n] + yt_o[n - 2*pts1], one float32 addition with the head
+ * as its first operand; before sample 2*pts1 the delayed tail is +0, and the addition is performed there too.  The
+ * output bits do not depend on how the stream is cut into calls: a call of K blocks equals K calls of one block, in
+ * output and in the state it leaves.  The packed DC / Nyquist rule applies per level, as in clfa_nupconv.
+ * segments(level): the head's count is what the matrix's plan gives for the head's geometry (pts0 bins, 2m partitions,
+ * inputs, outputs) on the device; the tail's is what it gives for one SLICE of the tail (pts0 bins, n1 partitions): that
+ * is what a single-block call offers the multiply-accumulate (a plan of this object's own, from measurement).
+ * CLFA_PCONV_MATRIX_SEGS (1..4096, read at creation) overrides both levels.  The definition goes through this accessor,
+ * not through a plan.
+ *
+ * Schedule: clfa_nupconv's, with the inputs in front of the multiply-accumulate and the outputs behind it.  The phase is
+ * position() mod m; the tail's forward transform (inputs rows) runs at phase 0 into ring frame w; every phase computes one
+ * slice of pts0/2 16-byte items of the tail block for every output; the tail's inverse (outputs rows) runs after phase
+ * m - 1 into the pending row, which is mixed into the head's output.  A call of one block: the stage kernel, the head's
+ * forward into its ring frame, ONE k_nupm_mac launch of two jobs (the head's block, the tail's slice), one k_nupm_reduce
+ * launch where a level has more than one segment, the head's inverse and the mix.  A call of several blocks runs the head
+ * through the matrix's sub-batch launches over the whole call and the tail's slices between two period boundaries in one
+ * launch.
+ *
+ * process_dev: row i of `in` at in + i*in_stride floats, row o of `out` at out + o*out_stride, nblocks*pts0 floats each;
+ * any 4-byte aligned address, strides >= nblocks*pts0; nblocks == 0 succeeds and does nothing.  A bad argument, or an out
+ * that overlaps in even partly: CLFA_INVALID_VALUE, the state untouched.  A call (or a reset) on a capturing stream:
+ * CLFA_INVALID_OPERATION — the phase lives on the host.  One object runs on one stream at a time.  convolution: the same
+ * on packed host rows, blocking.
+ * push_ir / push_ir_dev: both levels' response spectra written in stream order.  At position() % m == 0 a push is exact in
+ * clfa_nupconv's sense: at c = P*m it equals pushing the head object of the definition before its block c and the tail
+ * object before its block P - 1 (block 0 for P = 0).  At another phase the tail block in progress sums its REMAINING
+ * slices with the new responses.  There is no timed crossfade (no push_ir_fade) on this object.
+ * reset: the input history, the overlap-add tails and the blocks in progress are cleared, position() is 0, the responses
+ * stay. */
+CLFA_API int clfa_nupconv_matrix_create(clfa_nupconv_matrix **pc, int device, int cvs, int pts0, int pts1, int inputs,
+                                        int outputs);
+CLFA_API void clfa_nupconv_matrix_destroy(clfa_nupconv_matrix *pc);
+CLFA_API int clfa_nupconv_matrix_get_error(const clfa_nupconv_matrix *pc);
+CLFA_API const char *clfa_nupconv_matrix_get_log(const clfa_nupconv_matrix *pc);
+/* partitions of level 0 (the head: 2m) or 1 (the tail: n1); 0 for another level or a failed object */
+CLFA_API int clfa_nupconv_matrix_nparts(const clfa_nupconv_matrix *pc, int level);
+/* segments of the reduction over (input, partition) of level 0 or 1; 0 for another level or a failed object */
+CLFA_API int clfa_nupconv_matrix_segments(const clfa_nupconv_matrix *pc, int level);
+/* head blocks since creation or the last reset */
+CLFA_API long clfa_nupconv_matrix_position(const clfa_nupconv_matrix *pc);
+/* the state: both levels' rings, responses and tails, the stage rows and the pending tail output */
+CLFA_API size_t clfa_nupconv_matrix_state_bytes(const clfa_nupconv_matrix *pc);
+/* the workspaces: both levels' single-block accumulators and partial sums (allocated at creation) and the head's sub-batch
+ * workspaces (none until a call of several blocks; grown by the call that needs more blocks than any before it) */
+CLFA_API size_t clfa_nupconv_matrix_workspace_bytes(const clfa_nupconv_matrix *pc);
+/* "k_nupm_mac" ("" for a failed object) */
+CLFA_API const char *clfa_nupconv_matrix_kernel_name(const clfa_nupconv_matrix *pc);
+CLFA_API int clfa_nupconv_matrix_push_ir(clfa_nupconv_matrix *pc, const float *ir); /* packed host rows, blocking */
+CLFA_API int clfa_nupconv_matrix_push_ir_dev(clfa_nupconv_matrix *pc, const void *ir, long row_stride, void *stream);
+CLFA_API int clfa_nupconv_matrix_process_dev(clfa_nupconv_matrix *pc, void *out, long out_stride, const void *in,
+                                             long in_stride, long nblocks, void *stream);
+CLFA_API int clfa_nupconv_matrix_convolution(clfa_nupconv_matrix *pc, float *out, const float *in, long nblocks);
+CLFA_API int clfa_nupconv_matrix_reset(clfa_nupconv_matrix *pc, void *stream);
 
 #ifdef __cplusplus
 }

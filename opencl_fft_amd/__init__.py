@@ -10,6 +10,7 @@ meaning and integer OpenCL status codes), over the C ABI of libclfft_amd.so:
     Stft     (extension)        short-time analysis / windowed overlap-add synthesis on the Clrfft layout
     PconvMatrix (extension)     convolution matrix: many inputs mixed into many outputs
     Nupconv  (extension)        non-uniformly partitioned convolution: long responses at low latency
+    NupconvMatrix (extension)   ... many inputs mixed into many outputs, long responses at low latency
     Pvoc     (extension)        phase vocoder on Stft's spectra: (amp, freq) frames both ways
 
 Like the reference, constructors never raise: a failed setup is read back with
@@ -25,7 +26,7 @@ from . import _lib  # noqa: F401
 from ._base import (CL_INVALID_VALUE, CL_SUCCESS, _block_rows, _Handle, _host, _ptr_stream, _row_view,  # noqa: F401
                     _stream_of)
 from ._lib import ClError, check, lib  # noqa: F401  (`lib` here is the one every module calls: _base._pkg)
-from .conv import Cldconv, Clpconv, Nupconv, PconvMatrix, _BlockConv  # noqa: F401
+from .conv import Cldconv, Clpconv, Nupconv, NupconvMatrix, PconvMatrix, _BlockConv  # noqa: F401
 from .fft import (PI, Clcfft, Clrfft, _Plan, bandwidth_probe, bitrev_table, cl_error_string, device_count,  # noqa: F401
                   device_name, r2c_twiddle_table, reorder_device, twiddle_table)
 from .pvoc import Pvoc
@@ -33,4 +34,4 @@ from .stft import Stft, onesided_to_packed, packed_to_onesided
 
 __all__ = ["Clcfft", "Clrfft", "Clpconv", "Cldconv", "ClError", "cl_error_string", "device_count",
            "device_name", "bitrev_table", "twiddle_table", "r2c_twiddle_table", "reorder_device", "PI",
-           "Stft", "packed_to_onesided", "onesided_to_packed", "PconvMatrix", "Nupconv", "Pvoc"]
+           "Stft", "packed_to_onesided", "onesided_to_packed", "PconvMatrix", "Nupconv", "NupconvMatrix", "Pvoc"]

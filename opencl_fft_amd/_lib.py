@@ -97,6 +97,21 @@ SYMBOLS = [
     ("clfa_nupconv_process_dev", C.c_int, [_vp, _vp, C.c_long, _vp, C.c_long, C.c_long, _vp]),
     ("clfa_nupconv_convolution", C.c_int, [_vp, _vp, _vp, C.c_long]),
     ("clfa_nupconv_reset", C.c_int, [_vp, _vp]),
+    ("clfa_nupconv_matrix_create", C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    ("clfa_nupconv_matrix_destroy", None, [_vp]),
+    ("clfa_nupconv_matrix_get_error", C.c_int, [_vp]),
+    ("clfa_nupconv_matrix_get_log", C.c_char_p, [_vp]),
+    ("clfa_nupconv_matrix_nparts", C.c_int, [_vp, C.c_int]),
+    ("clfa_nupconv_matrix_segments", C.c_int, [_vp, C.c_int]),
+    ("clfa_nupconv_matrix_position", C.c_long, [_vp]),
+    ("clfa_nupconv_matrix_state_bytes", C.c_size_t, [_vp]),
+    ("clfa_nupconv_matrix_workspace_bytes", C.c_size_t, [_vp]),
+    ("clfa_nupconv_matrix_kernel_name", C.c_char_p, [_vp]),
+    ("clfa_nupconv_matrix_push_ir", C.c_int, [_vp, _vp]),
+    ("clfa_nupconv_matrix_push_ir_dev", C.c_int, [_vp, _vp, C.c_long, _vp]),
+    ("clfa_nupconv_matrix_process_dev", C.c_int, [_vp, _vp, C.c_long, _vp, C.c_long, C.c_long, _vp]),
+    ("clfa_nupconv_matrix_convolution", C.c_int, [_vp, _vp, _vp, C.c_long]),
+    ("clfa_nupconv_matrix_reset", C.c_int, [_vp, _vp]),
     ("clfa_dconv_create", C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.c_int]),
     ("clfa_dconv_destroy", None, [_vp]),
     ("clfa_dconv_get_error", C.c_int, [_vp]),

@@ -1,5 +1,5 @@
 """The convolutions: Clpconv and Cldconv of the reference's cl_conv.h / cl_dconv.h with what they share (_BlockConv),
-the convolution matrix PconvMatrix and the non-uniformly partitioned convolution Nupconv."""
+the convolution matrix PconvMatrix, the non-uniformly partitioned convolution Nupconv and its matrix form NupconvMatrix."""
 import numpy as np
 
 from ._base import CL_INVALID_VALUE, CL_SUCCESS, _Handle, _Object, _block_rows, _host, _is_f32, _pkg, _ptr_stream, _stream_of
@@ -331,6 +331,88 @@ class Nupconv(_Object):
             return CL_INVALID_VALUE
         return _pkg.lib().clfa_nupconv_process_dev(self._h, out.data_ptr(), so, x.data_ptr(), si, li // self.pts0,
                                                    _stream_of(x, stream))
+
+    def reset(self, stream=None):
+        """forget the input history (position 0); the responses stay.  `stream`: a HIP stream handle, default the
+        current torch stream of the object's device"""
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream().cuda_stream
+        return self._get("reset", stream)
+
+
+class NupconvMatrix(_Object):
+    """Non-uniformly partitioned convolution matrix (extension, clfa_nupconv_matrix in clfft_amd.h): `inputs` signals mixed
+    into `outputs` signals, y_o = sum_i x_i * h_{o,i}, with long static responses at a latency of pts0 samples — Nupconv's
+    two levels and schedule around PconvMatrix's sum over inputs.  The output is, bit for bit, PconvMatrix(2*pts1, pts0)
+    on h[:, :, :2*pts1] plus PconvMatrix(cvs - 2*pts1, pts1) on h[:, :, 2*pts1:] delayed by 2*pts1 samples, each reducing
+    in segments(level) segments.  pts0 < pts1 are powers of two, 32..4096; cvs >= 3 * pts1.  No timed crossfade.  Like the
+    other objects the constructor does not raise: get_error() / get_log()."""
+    _abi = "clfa_nupconv_matrix_"
+
+    def __init__(self, device_id, cvs, pts0, pts1, inputs, outputs):
+        self.cvs, self.pts0, self.pts1 = int(cvs), int(pts0), int(pts1)
+        self.inputs, self.outputs = int(inputs), int(outputs)
+        self._create(_pkg.lib().clfa_nupconv_matrix_create, int(device_id), self.cvs, self.pts0, self.pts1, self.inputs,
+                     self.outputs)
+
+    position = property(lambda s: s._get("position"))
+
+    def nparts(self, level):
+        """partitions of level 0 (the head) or 1 (the tail)"""
+        return self._get("nparts", int(level))
+
+    def segments(self, level):
+        """segments in which level 0 (the head) or 1 (the tail) sums over (input, partition)"""
+        return self._get("segments", int(level))
+
+    def state_bytes(self):
+        return self._get("state_bytes")
+
+    def _need(self):
+        return 2 * self.pts1 + self.nparts(1) * self.pts1
+
+    def push_ir(self, ir):
+        """ir: float32 (outputs, inputs, >= 2*pts1 + nparts(1)*pts1), e.g. rows of cvs samples; blocking.  Exact at
+        position % (pts1 // pts0) == 0; at another phase the tail block in progress mixes both responses."""
+        ir = np.asarray(ir, dtype=np.float32)
+        need = self._need()
+        if ir.ndim != 3 or ir.shape[:2] != (self.outputs, self.inputs) or ir.shape[2] < need:
+            return CL_INVALID_VALUE
+        ir = np.ascontiguousarray(ir[:, :, :need])
+        return _pkg.lib().clfa_nupconv_matrix_push_ir(self._h, ir.ctypes.data)
+
+    def push_ir_device(self, ir, stream=None):
+        """ir: device tensor (outputs, inputs, >= 2*pts1 + nparts(1)*pts1) of float32 whose rows are contiguous and evenly
+        spaced (stride(0) == inputs * stride(1)); the row stride is stride(1).  Asynchronous on `stream`."""
+        need = self._need()
+        if (ir.dim() != 3 or tuple(ir.shape[:2]) != (self.outputs, self.inputs) or ir.shape[2] < need
+                or not _is_f32(ir) or ir.stride(2) != 1):
+            return CL_INVALID_VALUE
+        rs = ir.stride(1) if self.inputs > 1 else (ir.stride(0) if self.outputs > 1 else max(ir.stride(1), need))
+        if self.outputs > 1 and ir.stride(0) != self.inputs * rs:
+            return CL_INVALID_VALUE
+        return _pkg.lib().clfa_nupconv_matrix_push_ir_dev(self._h, ir.data_ptr(), rs, _stream_of(ir, stream))
+
+    def convolution(self, output, input):
+        """whole signals on the host: float32 (inputs, L) -> (outputs, L), L a multiple of pts0; blocking"""
+        output = _host(output, np.float32)
+        a = np.ascontiguousarray(input, dtype=np.float32)
+        if (a.ndim != 2 or a.shape[0] != self.inputs or a.shape[1] % self.pts0
+                or output.shape != (self.outputs, a.shape[1])):
+            return CL_INVALID_VALUE
+        return _pkg.lib().clfa_nupconv_matrix_convolution(self._h, output.ctypes.data, a.ctypes.data, a.shape[1] // self.pts0)
+
+    def process_device(self, out, x, stream=None):
+        """device tensors: x (inputs, L), out (outputs, L) of float32, stride(1) == 1, L a multiple of pts0; the row stride
+        of each is its stride(0) (views into longer rows are fine).  Asynchronous on `stream`; not under graph capture
+        (CL_INVALID_OPERATION: the phase of the schedule lives on the host)."""
+        lo, so = _block_rows(out, self.outputs, self.outputs, False)
+        li, si = _block_rows(x, self.inputs, self.inputs, False)
+        if lo != li or li % self.pts0:
+            return CL_INVALID_VALUE
+        return _pkg.lib().clfa_nupconv_matrix_process_dev(self._h, out.data_ptr(), so, x.data_ptr(), si, li // self.pts0,
+                                                          _stream_of(x, stream))
 
     def reset(self, stream=None):
         """forget the input history (position 0); the responses stay.  `stream`: a HIP stream handle, default the

@@ -1,5 +1,5 @@
 // conv_host.cpp — C ABI of the convolutions (see include/clfft_amd.h): Clpconv and its multi-block route, Cldconv, the
-// convolution matrix and the non-uniformly partitioned convolution.  Shared plumbing: host.hpp, where the staged blocking form lives (staged_call); the rules of a
+// convolution matrix, the non-uniformly partitioned convolution and its matrix form.  Shared plumbing: host.hpp, where the staged blocking form lives (staged_call); the rules of a
 // call's arrays: overlap.hpp.  Every object stages its blocking calls in members in1, in2, out and its responses in ir.
 #include "dconv_launch.hpp"
 #include "fft_launch.hpp"
@@ -1352,6 +1352,324 @@ int clfa_nupconv_reset(clfa_nupconv *p, void *stream) {
   }
   HIP_TRY(hipMemsetAsync(p->stage.p, 0, p->stage.bytes, s));
   HIP_TRY(p->first().clear_history(s));
+  p->c = 0;
+  return CLFA_SUCCESS;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------
+// non-uniformly partitioned convolution matrix (pconv_nupm.hip; a head of many blocks is launch_pconv_matrix)
+// ---------------------------------------------------------------------------------
+
+// one level: its geometry, tables, segments, the inputs' spectra ring (nparts frames per input, the matrix's layout), the
+// outputs x inputs response spectra, the outputs' overlap-add tails (a single block's inverse reads one and writes the
+// other; cur: the one in force) and a single block's accumulators and partial sums
+struct NupmLevel {
+  int logb = 0, bins = 0, nparts = 0, segs = 1;
+  DevBuf half, w2f, w2i;
+  DevBuf ringA, H;
+  DevBuf tail[2];
+  int cur = 0;
+  DevBuf Y, P;
+  int w = 0;
+};
+
+struct clfa_nupconv_matrix {
+  DeviceInfo di;
+  int cvs = 0, pts0 = 0, pts1 = 0, m = 0, inputs = 0, outputs = 0;
+  int err = 0;
+  char log[256];
+  hipStream_t stream = nullptr;
+  NupmLevel lv[2];               // the head (2m partitions of pts0) and the tail (n1 partitions of pts1)
+  DevBuf stage, pend;            // the tail block being collected (inputs x pts1), the finished one being heard (outputs x pts1)
+  DevBuf bX, bY, bP, btail;      // the head's sub-batch workspaces, for hcap blocks (grown by the call that needs more)
+  int hcap = 0, bcap = 1, bkt = 4;
+  DevBuf in1, in2, out;          // staging of the blocking form (conv_arrays; in2 stays empty)
+  DevBuf ir;                     // ... and of push_ir
+  StreamOrder order;
+  long c = 0;                    // head blocks since creation / reset
+};
+
+static BlockShape block_shape(const clfa_nupconv_matrix *p) { return {p->pts0, p->inputs, p->outputs}; }
+static long nupm_ir_len(const clfa_nupconv_matrix *p) { return 2L * p->pts1 + (long)p->lv[1].nparts * p->pts1; }
+
+static int nupm_setup(clfa_nupconv_matrix *p, int device, int cvs, int pts0, int pts1, int inputs, int outputs) {
+  p->log[0] = 0;
+  p->cvs = cvs;
+  p->pts0 = pts0;
+  p->pts1 = pts1;
+  p->inputs = inputs;
+  p->outputs = outputs;
+  const int lo = 1 << kPconvBlocksMinLog, hi = 1 << kPconvBlocksMaxLog;
+  if (!is_pow2(pts0) || pts0 < lo) {
+    snprintf(p->log, sizeof(p->log), "pts0 must be a power of two, %d..%d (got %d)", lo, hi / 2, pts0);
+    return CLFA_INVALID_VALUE;
+  }
+  if (!is_pow2(pts1) || pts1 > hi || pts1 <= pts0) {
+    snprintf(p->log, sizeof(p->log), "pts1 must be a power of two above pts0, at most %d (got pts0 %d, pts1 %d)", hi, pts0, pts1);
+    return CLFA_INVALID_VALUE;
+  }
+  if (cvs / 3 < pts1) {
+    snprintf(p->log, sizeof(p->log), "cvs must be at least 3 * pts1 = %d (got %d)", 3 * pts1, cvs);
+    return CLFA_INVALID_VALUE;
+  }
+  if (inputs < 1) {
+    snprintf(p->log, sizeof(p->log), "inputs must be at least 1 (got %d)", inputs);
+    return CLFA_INVALID_VALUE;
+  }
+  if (outputs < 1) {
+    snprintf(p->log, sizeof(p->log), "outputs must be at least 1 (got %d)", outputs);
+    return CLFA_INVALID_VALUE;
+  }
+  p->m = pts1 / pts0;
+  NupmLevel &h = p->lv[0], &t = p->lv[1];
+  h.logb = ilog2(pts0), h.bins = pts0, h.nparts = 2 * p->m;
+  t.logb = ilog2(pts1), t.bins = pts1, t.nparts = (cvs - 2 * pts1) / pts1;   // floor: remainder samples are dropped
+  int e = device_info(device, p->di);
+  if (e) return e;
+  // each level's segments: the matrix's plan and its tuning switch, as mconv_setup — for the head at its geometry, for the
+  // tail at the geometry of a SLICE (pts0 bins of n1 partitions): a single-block call offers the multiply-accumulate
+  // pts0 / 2 items per output, not pts1 / 2, and with the whole block's count 64 x 64 at 64 / 4096 ran one segment of 3968
+  // terms on 32 waves (896 us per block against 160 for Nupconv on expanded inputs; profiles/HISTORY.md)
+  for (NupmLevel &l : p->lv) {
+    const PconvMatrixPlan pl = pconv_matrix_plan(pts0, l.nparts, inputs, outputs, p->di);
+    l.segs = pl.segs;
+    if (&l == &h) p->bkt = pl.kt;
+    if (const char *env = getenv("CLFA_PCONV_MATRIX_SEGS")) {
+      if (atoi(env) >= 1 && atoi(env) <= 4096) l.segs = atoi(env);
+    }
+  }
+  p->bcap = subbatch_cap(((long)inputs + (long)outputs * h.segs) * pts0 * (long)sizeof(cpx), "CLFA_PCONV_MATRIX_BLOCKS_MAX");
+  ENTER_DEVICE(device);
+  HIP_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
+  for (NupmLevel &l : p->lv) {
+    const size_t frame = sizeof(cpx) * (size_t)l.bins;
+    if ((e = upload_conv_tables(l.bins, l.half, l.w2f, l.w2i))) return e;
+    if ((e = l.ringA.ensure(frame * inputs * l.nparts)) || (e = l.H.ensure(frame * outputs * inputs * l.nparts)) ||
+        (e = l.tail[0].ensure(sizeof(float) * (size_t)outputs * l.bins)) || (e = l.tail[1].ensure(sizeof(float) * (size_t)outputs * l.bins)) ||
+        (e = l.Y.ensure(frame * outputs)) || (l.segs > 1 && (e = l.P.ensure(frame * outputs * (size_t)(l.segs - 1)))))
+      return e;
+    for (DevBuf *b : {&l.ringA, &l.H, &l.tail[0], &l.tail[1]}) HIP_TRY(hipMemsetAsync(b->p, 0, b->bytes, p->stream));
+  }
+  if ((e = p->stage.ensure(sizeof(float) * (size_t)inputs * pts1)) || (e = p->pend.ensure(sizeof(float) * (size_t)outputs * pts1))) return e;
+  HIP_TRY(hipMemsetAsync(p->stage.p, 0, p->stage.bytes, p->stream));
+  HIP_TRY(hipMemsetAsync(p->pend.p, 0, p->pend.bytes, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return CLFA_SUCCESS;
+}
+
+// one block of a level, single-block route.  forward: the inputs' samples -> ring frame w (committing it is the caller's
+// w + 1)
+static int nupm_forward(const clfa_nupconv_matrix *p, const NupmLevel &l, const float *in, long in_stride, hipStream_t s) {
+  HIP_TRY(launch_pconvb_forward(l.logb, in, in_stride, (cpx *)l.ringA.p + (long)l.w * l.bins, 1, l.nparts, p->inputs,
+                                ((uintptr_t)in & 7) == 0 && (in_stride & 1) == 0, (const cpx *)l.half.p, (const cpx *)l.w2f.p, s));
+  return CLFA_SUCCESS;
+}
+// ... the multiply-accumulate of items [item0, item0 + nitems) of the block in frame w
+static NupmMacJob nupm_job(const NupmLevel &l, int item0, int nitems) {
+  return {(const cpx *)l.ringA.p, (const cpx *)l.H.p, (cpx *)l.Y.p, (cpx *)l.P.p, l.w, l.bins, l.nparts, l.segs, item0, nitems};
+}
+// ... inverse transform and overlap-add: Y and the tail in force -> out, the other tail, which comes into force
+static int nupm_inverse(const clfa_nupconv_matrix *p, NupmLevel &l, float *out, long out_stride, hipStream_t s) {
+  HIP_TRY(launch_pconvb_inverse(l.logb, (const cpx *)l.Y.p, (const float *)l.tail[l.cur].p, (float *)l.tail[l.cur ^ 1].p, out, out_stride,
+                                1, 1, 1, p->outputs, ((uintptr_t)out & 7) == 0 && (out_stride & 1) == 0, (const cpx *)l.half.p,
+                                (const cpx *)l.w2i.p, s));
+  l.cur ^= 1;
+  return CLFA_SUCCESS;
+}
+
+// the head's K blocks through the matrix's sub-batch launches, sub-batch by sub-batch, as clfa_pconv_matrix_process_dev
+static int nupm_head(clfa_nupconv_matrix *p, float *out, long out_stride, const float *in, long in_stride, long nblocks, hipStream_t s) {
+  NupmLevel &l = p->lv[0];
+  PconvMatrixArgs a;
+  a.logb = l.logb;
+  a.bins = l.bins;
+  a.nparts = l.nparts;
+  a.inputs = p->inputs;
+  a.outputs = p->outputs;
+  a.plan.kt = p->bkt;
+  a.plan.segs = l.segs;
+  a.cap = p->hcap;
+  a.in_stride = in_stride;
+  a.out_stride = out_stride;
+  a.aligned_in = ((uintptr_t)in & 7) == 0 && (in_stride & 1) == 0;
+  a.aligned_out = ((uintptr_t)out & 7) == 0 && (out_stride & 1) == 0;
+  a.H = (const cpx *)l.H.p;
+  a.ringA = (cpx *)l.ringA.p;
+  a.tail = (float *)l.tail[l.cur].p;
+  a.X = (cpx *)p->bX.p;
+  a.Y = (cpx *)p->bY.p;
+  a.P = (cpx *)p->bP.p;
+  a.tail_ws = (float *)p->btail.p;
+  a.half = (const cpx *)l.half.p;
+  a.w2f = (const cpx *)l.w2f.p;
+  a.w2i = (const cpx *)l.w2i.p;
+  for (long j0 = 0; j0 < nblocks; j0 += a.K) {
+    a.K = (int)(nblocks - j0 < p->hcap ? nblocks - j0 : p->hcap);
+    a.w = l.w;
+    a.in = in + j0 * p->pts0;
+    a.out = out + j0 * p->pts0;
+    HIP_TRY(launch_pconv_matrix(a, s));
+    l.w = (int)((l.w + a.K) % l.nparts);
+  }
+  return CLFA_SUCCESS;
+}
+
+// nblocks >= 1 blocks.  One block: the head's forward transform straight into its ring frame, its multiply-accumulate
+// beside the tail's slice in one launch of k_nupm_mac, the segments' sums, its inverse.  Several blocks: the head through
+// the matrix's launches over the whole call, the tail's slices between two period boundaries in one launch.  The
+// arithmetic of a bin is the same on both ways, and both leave the same rings, tails and positions.
+static int nupm_blocks(clfa_nupconv_matrix *p, float *o, long out_stride, const float *x, long in_stride, long nblocks, hipStream_t s) {
+  const long pts0 = p->pts0, m = p->m;
+  const bool single = nblocks == 1;
+  NupmLevel &h = p->lv[0], &t = p->lv[1];
+  if (!single)
+    if (int e = nupm_head(p, o, out_stride, x, in_stride, nblocks, s)) return e;
+  // the tail, period by period: head blocks [j0, j0 + k) of the call are phases [sa, sb) of period P, in which tail block
+  // P - 1 is multiplied and tail block P - 2 is heard
+  const int hb0 = (int)(pts0 / 2);
+  for (long j0 = 0; j0 < nblocks;) {
+    const long P = p->c / m;
+    const int sa = (int)(p->c % m);
+    const long k = nblocks - j0 < m - sa ? nblocks - j0 : m - sa;
+    const int sb = sa + (int)k, off = sa * (int)pts0, n = (int)(k * pts0);
+    if (single)
+      if (int e = nupm_forward(p, h, x, in_stride, s)) return e;
+    // phase 0: the spectra of the finished block, before this period's samples overwrite the rows
+    if (P >= 1 && sa == 0)
+      if (int e = nupm_forward(p, t, (const float *)p->stage.p, p->pts1, s)) return e;
+    HIP_TRY(launch_nupc_stage(x + j0 * pts0, in_stride, (float *)p->stage.p, p->pts1, off, n, p->inputs, s));
+    NupmMacJob jobs[kNupmMacJobs];
+    int njobs = 0;
+    if (single) jobs[njobs++] = nupm_job(h, 0, hb0);
+    if (P >= 1) jobs[njobs++] = nupm_job(t, sa * hb0, (sb - sa) * hb0);
+    if (njobs) {
+      HIP_TRY(launch_nupm_mac(jobs, njobs, p->inputs, p->outputs, s));
+      HIP_TRY(launch_nupm_reduce(jobs, njobs, p->outputs, s));
+    }
+    if (single) {
+      if (int e = nupm_inverse(p, h, o, out_stride, s)) return e;
+      h.w = (h.w + 1) % h.nparts;
+    }
+    HIP_TRY(launch_nupc_mix(o + j0 * pts0, out_stride, (const float *)p->pend.p, p->pts1, off, n, p->outputs, s));
+    // after slice m - 1: the block's samples replace the ones just heard, its spectra stay in the ring
+    if (P >= 1 && sb == m) {
+      if (int e = nupm_inverse(p, t, (float *)p->pend.p, p->pts1, s)) return e;
+      t.w = (t.w + 1) % t.nparts;
+    }
+    p->c += k;
+    j0 += k;
+  }
+  return CLFA_SUCCESS;
+}
+
+extern "C" {
+
+int clfa_nupconv_matrix_create(clfa_nupconv_matrix **pc, int device, int cvs, int pts0, int pts1, int inputs, int outputs) {
+  return create_object(pc, [&](clfa_nupconv_matrix *p) { return nupm_setup(p, device, cvs, pts0, pts1, inputs, outputs); });
+}
+
+void clfa_nupconv_matrix_destroy(clfa_nupconv_matrix *p) { destroy_object(p); }
+
+int clfa_nupconv_matrix_get_error(const clfa_nupconv_matrix *p) { return p ? p->err : CLFA_INVALID_VALUE; }
+const char *clfa_nupconv_matrix_get_log(const clfa_nupconv_matrix *p) { return p ? p->log : ""; }
+int clfa_nupconv_matrix_nparts(const clfa_nupconv_matrix *p, int level) {
+  return p && !p->err && (level == 0 || level == 1) ? p->lv[level].nparts : 0;
+}
+int clfa_nupconv_matrix_segments(const clfa_nupconv_matrix *p, int level) {
+  return p && !p->err && (level == 0 || level == 1) ? p->lv[level].segs : 0;
+}
+long clfa_nupconv_matrix_position(const clfa_nupconv_matrix *p) { return p ? p->c : 0; }
+size_t clfa_nupconv_matrix_state_bytes(const clfa_nupconv_matrix *p) {
+  if (!p) return 0;
+  size_t n = p->stage.bytes + p->pend.bytes;
+  for (const NupmLevel &l : p->lv) n += l.ringA.bytes + l.H.bytes + l.tail[0].bytes + l.tail[1].bytes;
+  return n;
+}
+size_t clfa_nupconv_matrix_workspace_bytes(const clfa_nupconv_matrix *p) {
+  if (!p) return 0;
+  size_t n = p->bX.bytes + p->bY.bytes + p->bP.bytes + p->btail.bytes;
+  for (const NupmLevel &l : p->lv) n += l.Y.bytes + l.P.bytes;
+  return n;
+}
+const char *clfa_nupconv_matrix_kernel_name(const clfa_nupconv_matrix *p) { return !p || p->err ? "" : "k_nupm_mac"; }
+
+int clfa_nupconv_matrix_push_ir_dev(clfa_nupconv_matrix *p, const void *ir, long row_stride, void *stream) {
+  if (int e = obj_error(p)) return e;
+  if (!device_rows_ok(ir) || row_stride < nupm_ir_len(p)) return CLFA_INVALID_VALUE;
+  ENTER_DEVICE(p->di.device);
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(p->order.use(s));
+  // every partition of every row in one forward launch per level, as clfa_pconv_matrix_push_ir_dev: row (o, i) partition
+  // q -> H frame ((o * inputs + i) * nparts + q); h[0 : 2*pts1) in the head's partitions, what follows in the tail's
+  const float *rows = (const float *)ir;
+  for (int k = 0; k < 2; k++) {
+    const NupmLevel &l = p->lv[k];
+    const float *src = rows + (k ? 2L * p->pts1 : 0);
+    const int aligned = ((uintptr_t)src & 7) == 0 && (row_stride & 1) == 0;
+    HIP_TRY(launch_pconvb_forward(l.logb, src, row_stride, (cpx *)l.H.p, l.nparts, l.nparts, p->outputs * p->inputs, aligned,
+                                  (const cpx *)l.half.p, (const cpx *)l.w2f.p, s));
+  }
+  return CLFA_SUCCESS;
+}
+
+int clfa_nupconv_matrix_push_ir(clfa_nupconv_matrix *p, const float *ir) {
+  if (int e = obj_error(p)) return e;
+  if (!ir) return CLFA_INVALID_VALUE;
+  ENTER_DEVICE(p->di.device);
+  const long len = nupm_ir_len(p);
+  return push_host(p, ir, sizeof(float) * (size_t)p->outputs * p->inputs * len,
+                   [&](const void *rows) { return clfa_nupconv_matrix_push_ir_dev(p, rows, len, p->stream); });
+}
+
+int clfa_nupconv_matrix_process_dev(clfa_nupconv_matrix *p, void *out, long out_stride, const void *in, long in_stride,
+                                    long nblocks, void *stream) {
+  if (int e = obj_error(p)) return e;
+  const long pts0 = p->pts0;
+  long len;
+  if (int e = check_blocks_dev(nblocks, pts0, out, out_stride, p->outputs, in, nullptr, in_stride, p->inputs, &len)) return e;
+  if (!len) return CLFA_SUCCESS;
+  ENTER_DEVICE(p->di.device);
+  hipStream_t s = (hipStream_t)stream;
+  // the phase of the schedule is host state, which a replay would not advance
+  if (StreamOrder::capturing(s)) return CLFA_INVALID_OPERATION;
+  if (nblocks > 1 && nblocks > p->hcap) {
+    const int cap = (int)(nblocks < p->bcap ? nblocks : p->bcap);
+    if (cap > p->hcap) {
+      const size_t frames = sizeof(cpx) * (size_t)cap * (size_t)pts0;
+      if (int e = ensure_workspaces({{&p->bX, frames * p->inputs},
+                                     {&p->bY, frames * p->outputs},
+                                     {&p->bP, frames * p->outputs * (size_t)(p->lv[0].segs - 1)},
+                                     {&p->btail, sizeof(float) * (size_t)p->outputs * (size_t)pts0}},
+                                    s))
+        return e;
+      p->hcap = cap;
+    }
+  }
+  HIP_TRY(p->order.use(s));
+  return nupm_blocks(p, (float *)out, out_stride, (const float *)in, in_stride, nblocks, s);
+}
+
+int clfa_nupconv_matrix_convolution(clfa_nupconv_matrix *p, float *out, const float *in, long nblocks) {
+  return blocks_host(p, out, in, nullptr, nblocks, [&](void *o, long len, const void *i1, const void *) {
+    return clfa_nupconv_matrix_process_dev(p, o, len, i1, len, nblocks, p->stream);
+  });
+}
+
+int clfa_nupconv_matrix_reset(clfa_nupconv_matrix *p, void *stream) {
+  if (int e = obj_error(p)) return e;
+  ENTER_DEVICE(p->di.device);
+  hipStream_t s = (hipStream_t)stream;
+  if (StreamOrder::capturing(s)) return CLFA_INVALID_OPERATION;
+  HIP_TRY(p->order.use(s));
+  // the input history, the tails and the blocks in progress; the responses stay
+  for (NupmLevel &l : p->lv) {
+    for (DevBuf *b : {&l.ringA, &l.tail[0], &l.tail[1]}) HIP_TRY(hipMemsetAsync(b->p, 0, b->bytes, s));
+    l.w = l.cur = 0;
+  }
+  HIP_TRY(hipMemsetAsync(p->stage.p, 0, p->stage.bytes, s));
+  HIP_TRY(hipMemsetAsync(p->pend.p, 0, p->pend.bytes, s));
   p->c = 0;
   return CLFA_SUCCESS;
 }
