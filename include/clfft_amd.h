@@ -508,6 +508,48 @@ CLFA_API int clfa_pvoc_read(clfa_pvoc *pv, const float *frames_in, long Fin, con
 /* op: 0 = scale, 1 = shift, 2 = read; the kernel's name as above ("" for a failed object or an unknown op) */
 CLFA_API const char *clfa_pvoc_ops_kernel_name(const clfa_pvoc *pv, int op, int keepform);
 
+/* ---- analysis of a stored signal at any time points (Csound's pvstanal, mincer, temposcal) ---- */
+/* Every output frame is analysed at its own time point, straight from the signal: the window is laid at starts[g] and once
+ * more one hop earlier, and the frequencies come from the phase difference of those two spectra.  Reading a stored signal
+ * at another speed is then one call (starts[g] = floor(g hop / factor)) followed by the synthesis; the timed read above
+ * can only blend the two frames of the hop grid around a time point.  Stateless: prev, theta and every other state of the
+ * object are untouched, the call allocates nothing and can be captured.
+ *   signal:     `channels` rows of `samples` floats, row c at signal + c * signal_stride; signal_stride >= samples,
+ *               1 <= samples <= 2^31 - 1; any 4-byte aligned address;
+ *   window:     size floats, 4-byte aligned; required (NULL is CLFA_INVALID_VALUE);
+ *   starts:     Fout int32, one per output frame, shared by the channels; any value, in any order;
+ *   frames_out: channels x Fout x (M + 1) x 2 float32, contiguous, 8-byte aligned.
+ * For channel c and output frame g, with s = starts[g] and all index arithmetic in 64 bits:
+ *   x_c[n] is the row's sample for 0 <= n < samples and +0 otherwise;
+ *   a[t] = fl(w[t] * x_c[s - hop + t]) and b[t] = fl(w[t] * x_c[s + t]), t < size: a sample outside the row is multiplied
+ *   by the window like any other (a negative window value gives -0 there);
+ *   PA, PB = what clfa_rfft_transform (size, forward) returns for a and b, zA, zB their bins under the map above;
+ *   the frame is the Analysis formula above with z_f = zB and z_{f-1} = zA:
+ *     amp = |zB[k]|;  d = zB[k] conj(zA[k]) e[k];  dev = atan2f(Im d, Re d) / (2 pi), 0 where d = (0, 0);
+ *     freq = (k + dev size / hop) sr / size.
+ * Equivalently, frame (c, g) is frame 1 of what clfa_pvoc_analyze_dev of a fresh object returns for the two spectra that
+ * clfa_stft_analyze_dev (size, hop, w) gives for the size + hop floats x_c[s - hop .. s + size): the same bits (the kernel
+ * runs the same code).  With starts[g] = g hop every frame g >= 1 is the frame that Stft's and Pvoc's analysis return for
+ * the whole signal; frame 0 differs, because its earlier window lies before the signal and prev plays no part.  A NaN
+ * sample reaches only the frames whose two windows cover it, in its own channel.
+ *
+ * The rules of the stateless frame operations hold: argument checks that need no device come first (on an object whose
+ * creation found no device a bad argument is still CLFA_INVALID_VALUE, a good one the object's error); Fout == 0 succeeds
+ * and does nothing; a NULL or misaligned pointer, samples < 1, signal_stride < samples, or frames_out overlapping the
+ * signal (its whole strided extent), the window or starts, even partly, is CLFA_INVALID_VALUE and writes nothing.
+ * Asynchronous on `stream`, one stream at a time, the current device left as found.  One launch, "k_pvoc_tanal": a
+ * workgroup holds a group of output frames in LDS, transforms both windows there, keeps zA in a second LDS buffer and
+ * writes the frames; no spectra and no gathered copy of the signal in memory, no atomics, no waiting between workgroups.
+ * CLFA_PVOC_OPS_GRID_MAX caps the launch's workgroups as for the other one-launch operations; the result does not depend
+ * on it. */
+CLFA_API int clfa_pvoc_tanal_dev(clfa_pvoc *pv, const void *signal, long signal_stride, long samples, const void *window,
+                                 const void *starts, void *frames_out, long Fout, void *stream);
+/* host arrays, staged, blocking */
+CLFA_API int clfa_pvoc_tanal(clfa_pvoc *pv, const float *signal, long signal_stride, long samples, const float *window,
+                             const int *starts, float *frames_out, long Fout);
+/* "k_pvoc_tanal" ("" for a failed object) */
+CLFA_API const char *clfa_pvoc_tanal_kernel_name(const clfa_pvoc *pv);
+
 /* ---- operations on two streams of (amp, freq) frames: cross, morph, filter, mix, vocode ---- */
 /* Csound's pvscross, pvsmorph, pvsfilter, pvsmix and pvsvoc.  frames_a, frames_b and frames_out: channels x F x (M + 1) x 2
  * float32 in the layout above, 8-byte aligned; p and q: F float32 each, one value per frame, shared by the channels,

@@ -161,6 +161,9 @@ SYMBOLS = [
     ("clfa_pvoc_shift", C.c_int, [_vp, _vp, _vp, C.c_long, _vp, C.c_int, C.c_int, C.c_float, C.c_int]),
     ("clfa_pvoc_read", C.c_int, [_vp, _vp, C.c_long, _vp, _vp, C.c_long]),
     ("clfa_pvoc_ops_kernel_name", C.c_char_p, [_vp, C.c_int, C.c_int]),
+    ("clfa_pvoc_tanal_dev", C.c_int, [_vp, _vp, C.c_long, C.c_long, _vp, _vp, _vp, C.c_long, _vp]),
+    ("clfa_pvoc_tanal", C.c_int, [_vp, _vp, C.c_long, C.c_long, _vp, _vp, _vp, C.c_long]),
+    ("clfa_pvoc_tanal_kernel_name", C.c_char_p, [_vp]),
     ("clfa_pvoc_pair_dev", C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_long, _vp, _vp, C.c_int, _vp]),
     ("clfa_pvoc_pair", C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_long, _vp, _vp, C.c_int]),
     ("clfa_pvoc_pair_kernel_name", C.c_char_p, [_vp, C.c_int]),

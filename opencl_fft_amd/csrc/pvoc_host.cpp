@@ -5,6 +5,7 @@
 #include "fft_route.hpp"
 #include "host.hpp"
 #include "pvoc_launch.hpp"
+#include "tanal_launch.hpp"
 
 using namespace clfa;
 
@@ -440,6 +441,62 @@ const char *clfa_pvoc_ops_kernel_name(const clfa_pvoc *p, int op, int keepform) 
   if (!p || p->err || op < PVOC_SCALE || op > PVOC_READ) return "";
   return op == PVOC_READ ? "k_pvoc_read" : (keepform ? "k_pvoc_formant" : "k_pvoc_map");
 }
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------
+// a stored signal -> frames at given time points (tanal_kernels.hip)
+// ---------------------------------------------------------------------------------
+
+// signal: channels rows of `samples` floats, signal_stride floats apart at the caller's (the overlap rule takes the rows
+// and the gaps between them as one span), packed where the blocking form stages them.  Every start has a meaning, so the
+// blocking form has no values to refuse.
+static int pvoc_tanal_call(clfa_pvoc *p, bool blocking, const void *signal, long signal_stride, long samples,
+                           const void *window, const void *starts, void *out, long Fout, void *stream) {
+  if (int e = pvoc_usable(p)) return e;
+  const bool scalars_ok = samples >= 1 && samples <= 0x7fffffffL && signal_stride >= samples;
+  const size_t row = sizeof(float) * (size_t)(samples > 0 ? samples : 0), pitch = sizeof(float) * (size_t)(signal_stride > 0 ? signal_stride : 0);
+  const PvocArray arrays[] = {{signal, row, 4, false, &clfa_pvoc::ssig, true, (size_t)p->channels, pitch},
+                              {out, pvoc_frame_bytes(p, Fout), 8, true, &clfa_pvoc::sop_out},
+                              {window, sizeof(float) * (size_t)p->size, 4, false, &clfa_pvoc::sshape_tab},
+                              {starts, sizeof(int) * (size_t)Fout, 4, false, &clfa_pvoc::sdelay_tab}};
+  const auto launch = [&](const void *const *d, hipStream_t s) {
+    PvocTanalArgs a;
+    a.logn = ilog2(p->M);
+    a.M = p->M;
+    a.channels = p->channels;
+    a.hop = p->hop;
+    a.Fout = Fout;
+    a.samples = samples;
+    a.stride = blocking ? samples : signal_stride;
+    a.signal = (const float *)d[0];
+    a.out = (cpx *)d[1];
+    a.window = (const float *)d[2];
+    a.starts = (const int *)d[3];
+    a.etab = (const cpx *)p->etab.p;
+    a.half = (const cpx *)p->half.p;
+    a.w2 = (const cpx *)p->w2.p;
+    a.sh = p->sh;
+    a.srs = p->srs;
+    a.grid_max = p->ops_grid_max;
+    return launch_pvoc_tanal(a, p->di, s);
+  };
+  return pvoc_call(p, blocking, stream, scalars_ok, Fout, arrays, CLFA_SUCCESS, pvoc_no_values, launch);
+}
+
+extern "C" {
+
+int clfa_pvoc_tanal_dev(clfa_pvoc *p, const void *signal, long signal_stride, long samples, const void *window,
+                        const void *starts, void *frames_out, long Fout, void *stream) {
+  return pvoc_tanal_call(p, false, signal, signal_stride, samples, window, starts, frames_out, Fout, stream);
+}
+
+int clfa_pvoc_tanal(clfa_pvoc *p, const float *signal, long signal_stride, long samples, const float *window,
+                    const int *starts, float *frames_out, long Fout) {
+  return pvoc_tanal_call(p, true, signal, signal_stride, samples, window, starts, frames_out, Fout, nullptr);
+}
+
+const char *clfa_pvoc_tanal_kernel_name(const clfa_pvoc *p) { return !p || p->err ? "" : "k_pvoc_tanal"; }
 
 }  // extern "C"
 

@@ -16,6 +16,7 @@
 //
 // Every global access is a row of consecutive bins: 8 bytes per lane (a complex bin, or an (amp, freq) pair), 4 in the
 // sums and bases.
+#include "pvoc_analysis.hpp"
 #include "pvoc_device.hpp"
 
 namespace clfa {
@@ -24,15 +25,6 @@ namespace {
 
 constexpr int kPvocWG = 256;    // lanes = bins per workgroup tile
 constexpr int kPvocRun = 4;     // consecutive frames per lane of the analysis
-
-// z[k] of a packed row: bin 0 = (Re P[0], 0), bin M = (Im P[0], 0), bin M/2 conjugated
-__device__ __forceinline__ cpx pvoc_bin(const cpx *__restrict__ row, int k, int M) {
-  const cpx p = row[k == M ? 0 : k];
-  if (k == 0) return mk(p.x, 0.f);
-  if (k == M) return mk(p.y, 0.f);
-  if (k == (M >> 1)) return mk(p.x, -p.y);
-  return p;
-}
 
 // the phase increment of one frame in 2^-32 turn.  Every step rounds on its own: tests/pvoc_model.py restates it bit for
 // bit.  The pragma is what keeps the product and the subtraction apart — HIP's __fmul_rn / __fsub_rn are plain operators,
@@ -66,11 +58,8 @@ __global__ __launch_bounds__(kPvocWG) void k_pvoc_analyze(const cpx *__restrict_
     cpx *out = reinterpret_cast<cpx *>(frames) + (c * F + f0) * (M + 1) + k;
     for (long f = f0; f < f1; f++, out += M + 1) {
       const cpx z = pvoc_bin(rows + f * M, k, M);
-      const float amp = sqrtf(z.x * z.x + z.y * z.y);
-      const float tx = z.x * zp.x + z.y * zp.y, ty = z.y * zp.x - z.x * zp.y;   // z conj(z_prev)
-      const float dx = tx * e.x - ty * e.y, dy = tx * e.y + ty * e.x;
-      const float dev = (dx == 0.f && dy == 0.f) ? 0.f : atan2f(dy, dx) * 0.15915494309189535f;   // turns
-      *out = mk(amp, ((float)k + dev * sh) * srs);
+#include "pvoc_analysis_bin.inc"   // amp and freq of bin k from z, zp and e: the one copy k_pvoc_tanal shares
+      *out = mk(amp, freq);
       zp = z;
     }
     if (f0 == 0) *state = pvoc_bin(rows + (F - 1) * M, k, M);

@@ -94,28 +94,7 @@ __global__ __launch_bounds__(LdsGeom<LOGN>::WG) void k_stft_analyze(const float 
       load_rows(gn < groups ? gn : groups - 1);
     }
     __syncthreads();
-    cpx v[E];
-    pass_gather_padded<LOGN, G::LOGE>(v, t, xb);
-    wg_passes<LOGN, G::LOGE, 0, true>(v, t, s_tab, xb);
-#pragma unroll
-    for (int e = 0; e < E; e++) v[e] = cscale(v[e], 1.0f / (float)N);   // forward real plans scale by 1/M (cl_fft.cpp:39)
-    __syncthreads();
-    dif_scatter_padded<LOGN, G::LOGE>(v, t, xb);
-    __syncthreads();
-    // reference `conv` (cl_fft.cpp:178-191) on the natural-order copy; pair 0 = packed DC / Nyquist, bin N/2 untouched
-#pragma unroll
-    for (int k = 0; k < E / 2; k++) {
-      const int i = t + T * k, j = i == 0 ? N / 2 : N - i;
-      const cpx ci = xb[lds_pad(i)], cj = xb[lds_pad(j)];
-      cpx oi, oj;
-      r2c_pair(ci, cj, s_w2[i], oi, oj);
-      const bool z = i == 0;
-      oi = mk(z ? (ci.x + ci.y) * .5f : oi.x, z ? (ci.x - ci.y) * .5f : oi.y);
-      oj = mk(z ? cj.x : oj.x, z ? cj.y : oj.y);
-      xb[lds_pad(i)] = oi;
-      xb[lds_pad(j)] = oj;
-    }
-    __syncthreads();
+#include "stft_spectrum.inc"   // the pass chain, the scale by 1 / N, the r2c pair map: the spectra are in the slots
     const long base = g * CHUNK, total = (long)nframes * N;
     if (base + CHUNK <= total) {
 #pragma unroll

@@ -146,7 +146,66 @@ class _PvocDelay:
         return out
 
 
-class Pvoc(_Object, _PvocStereo, _PvocDelay):
+class _PvocStored:
+    """The operation of Pvoc that reads a stored signal, not frames (clfa_pvoc_tanal* in clfft_amd.h): the analysis at any
+    time points.  A base of Pvoc, like _PvocStereo: Pvoc supplies the object and the shapes, and its own operations start
+    from spectra or frames."""
+
+    # ---- a stored signal -> frames at any time points (Csound's pvstanal, mincer; stateless; clfft_amd.h) ----
+
+    def tanal_kernel_name(self):
+        """ "k_pvoc_tanal" ("" for a failed object)"""
+        return self._text("tanal_kernel_name")
+
+    @staticmethod
+    def stretch_starts(samples, hop, factor):
+        """the starts of a time stretch by `factor` (2 = twice as long) of a signal of `samples` samples: int32
+        floor(g hop / factor), computed in float64, for g = 0 .. ceil(factor samples / hop) - 1.  ValueError for a factor
+        that is not positive and finite"""
+        factor = float(factor)
+        if not (np.isfinite(factor) and factor > 0):
+            raise ValueError("factor must be positive and finite")
+        n = int(np.ceil(factor * int(samples) / int(hop)))
+        return np.floor(np.arange(max(n, 0), dtype=np.float64) * int(hop) / factor).astype(np.int32)
+
+    def tanal_device(self, signal, window, starts, frames_out, stream=None):
+        """torch: signal float32 (channels, samples) with unit inner stride and any row stride ((samples,) for one
+        channel), window float32 (size,), starts int32 (Fout,) -> frames_out (channels, Fout, size/2 + 1, 2) float32,
+        contiguous (anything else: CL_INVALID_VALUE).  Frame g of every channel is the analysis of the signal under the
+        window laid at starts[g] and, for the phase difference, at starts[g] - hop; samples outside the signal are zero.
+        No state is read or written.  frames_out may overlap none of the inputs.  Asynchronous on `stream`."""
+        if not all(hasattr(t, "data_ptr") for t in (signal, window, starts, frames_out)):
+            return CL_INVALID_VALUE
+        sig = signal.unsqueeze(0) if signal.dim() == 1 and self.channels == 1 else signal
+        Fout = self._frames_shape(frames_out.shape)
+        if (Fout is None or not _dense_f32(frames_out, frames_out.shape) or not _dense_f32(window, (self.size,))
+                or str(starts.dtype) != "torch.int32" or tuple(starts.shape) != (Fout,) or not starts.is_contiguous()
+                or not _is_f32(sig) or sig.dim() != 2 or sig.shape[0] != self.channels or sig.shape[1] < 1
+                or (sig.shape[1] > 1 and sig.stride(1) != 1) or (self.channels > 1 and sig.stride(0) < sig.shape[1])
+                or any(t.device != frames_out.device for t in (signal, window, starts))):
+            return CL_INVALID_VALUE
+        samples = sig.shape[1]
+        return self._get("tanal_dev", sig.data_ptr(), max(sig.stride(0), samples), samples, window.data_ptr(),
+                         starts.data_ptr(), frames_out.data_ptr(), Fout, _stream_of(frames_out, stream))
+
+    def tanal(self, signal, window, starts):
+        """host form of tanal_device, blocking: float32 (channels, samples) (or (samples,) for one channel), window
+        (size,), integer starts (Fout,) -> the frames float32 (.., Fout, size/2 + 1, 2)"""
+        signal = np.ascontiguousarray(signal, dtype=np.float32)
+        window = np.ascontiguousarray(window, dtype=np.float32)
+        starts = np.ascontiguousarray(starts, dtype=np.int32).reshape(-1)
+        full = self._full(signal.shape, 2)
+        if len(full) != 2 or full[0] != self.channels or full[1] < 1:
+            raise ValueError("signal must be (%d, samples)" % self.channels)
+        if window.shape != (self.size,):
+            raise ValueError("window must be (%d,)" % self.size)
+        out = np.zeros(signal.shape[:-1] + (starts.size, self.M + 1, 2), np.float32)
+        check(self._get("tanal", signal.ctypes.data, full[1], full[1], window.ctypes.data, starts.ctypes.data,
+                        out.ctypes.data, starts.size), "Pvoc.tanal")
+        return out
+
+
+class Pvoc(_Object, _PvocStereo, _PvocDelay, _PvocStored):
     """Phase vocoder on the spectra of Stft (extension, clfa_pvoc in clfft_amd.h): analyze() reads (channels, F, size/2)
     complex64 spectra as (channels, F, size/2 + 1, 2) float32 frames of (amp, freq in Hz) per bin, synthesize() turns such
     frames back into spectra.  The object carries the last spectrum (analysis) and an integer phase per bin (synthesis)
@@ -155,6 +214,7 @@ class Pvoc(_Object, _PvocStereo, _PvocDelay):
     describe() turns frames into control values: eight descriptors per frame (the previous frame's amps carried along).
     demix() takes the frames of the left and of the right channel of one recording apart by pan position.
     delay() gives every bin its own delay time and feedback (two histories of the stream carried along, after delay_setup()).
+    tanal() analyses a stored signal at any time points, each frame under a window of its own: the way to another speed.
     Like the other objects the constructor does not raise, and every call returns its status."""
     _abi = "clfa_pvoc_"
 
