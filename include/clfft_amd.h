@@ -1174,9 +1174,49 @@ CLFA_API int clfa_nupconv_reset(clfa_nupconv *pc, void *stream);
  * push_ir / push_ir_dev: both levels' response spectra written in stream order.  At position() % m == 0 a push is exact in
  * clfa_nupconv's sense: at c = P*m it equals pushing the head object of the definition before its block c and the tail
  * object before its block P - 1 (block 0 for P = 0).  At another phase the tail block in progress sums its REMAINING
- * slices with the new responses.  There is no timed crossfade (no push_ir_fade) on this object.
+ * slices with the new responses: push at phase 0, or use the timed crossfade below, which is clean at any phase.
  * reset: the input history, the overlap-add tails and the blocks in progress are cleared, position() is 0, the responses
- * stay. */
+ * stay.
+ *
+ * Timed crossfade (push_ir_fade, push_ir_fade_dev): a change of responses without the step of a plain push, at any phase.
+ * ir, row_stride and the row layout are those of push_ir / push_ir_dev.  Definition (clfa_nupconv's, with rows in place of
+ * channels): let A be the response set in force at the push and B the pushed set; c = position() at the push (any phase);
+ * block 0 the next head block processed; N = fade_blocks * pts0; n a sample's index counted from the first sample of block
+ * 0; yA what this object would have produced without the push; yB what a second clfa_nupconv_matrix of the same geometry
+ * AND THE SAME segments(0), segments(1) would produce if it had held B since its creation or last reset and had received
+ * every input this object has received since then.  Both are complete outputs, head + pending tail, one float32 addition
+ * with the head first.  Then
+ *   for 0 <= n < N the output sample is  yA + g(n) * (yB - yA),  evaluated in float32 in that form (a subtraction, a
+ *     multiplication, an addition, each rounded on its own, no contraction), with  g(n) = (float)n / (float)N  (IEEE
+ *     division, round to nearest): exactly 0 at n = 0, rising linearly to (N-1)/N;
+ *   from sample N on the output is yB, B is in force, fade_remaining() is 0, and the object is in every later bit the
+ *     object that always held B.
+ * The output does not depend on how the stream is cut into calls, during the fade or after it; a fade from A to A gives
+ * the bits of no push at all.
+ * State: the inputs' spectra rings, the stage rows and the forward transforms do not depend on the responses; both paths
+ * share them and they are written once.  What depends on the responses exists twice during a fade: both levels' response
+ * spectra, both levels' overlap-add tail pairs, the pending rows, both levels' single-block accumulators and partial
+ * sums; on top of that a scratch of outputs x pts0 floats for the second path's head output.  All of the second set's
+ * history is recomputed at the push from the rings alone with the plain path's kernels (k_nupm_mac over all items of a
+ * block, k_nupm_reduce, the inverse), hence with its bits — a whole block in one multiply-accumulate has the bits of the
+ * block computed slice by slice, because the segments cut the term sequence, not the bins: with P = c div m and s = c mod
+ * m, the head's tail from head block c - 1 (c >= 1); the tail level's tail from tail block P - 3 (P >= 3); the pending
+ * rows and the tail level's tail from tail block P - 2 (P >= 2); slices 0 .. s-1 of tail block P - 1 (P >= 1, s > 0).  A
+ * block of negative index is not computed: its contribution is the +0 of a cleared row.  For this the tail's ring keeps
+ * n1 + 2 frames per input (the sums walk the newest n1); the head's keeps its 2m, which head block c - 1 finds intact.
+ * When the last fade block has been issued the sets exchange roles on the host, nothing is copied.  The second set is
+ * allocated by the first fade push and kept for the next: A FADE DOUBLES THE RESPONSE MEMORY (the responses of 64 x 64
+ * rows of 2^18 taps are 8 GB), and state_bytes() and workspace_bytes() count the second set from then on; until then they
+ * are those of an object without fades, the tail ring's two more frames apart.
+ * Schedule: a head block of a fade runs the head's forward transform (and the tail's at phase 0), the stage kernel, ONE
+ * k_nupm_mac launch of up to four jobs (head and tail slice under A and under B), ONE k_nupm_reduce launch over the same
+ * jobs, the two head inverses (A's into the output rows, B's into the scratch), k_nupc_fade_mix over the outputs rows
+ * and, after phase m - 1, both tail inverses.  A call of K blocks that meets a fade runs the fade's blocks one at a time
+ * and what follows the fade on the usual route.
+ * Refusals (the state is untouched in each): fade_blocks < 1, fade_blocks * pts0 > 2^31 - 1 or any argument error of
+ * push_ir_dev: CLFA_INVALID_VALUE; a fade push, a plain push_ir / push_ir_dev, or a reset while fade_remaining() > 0:
+ * CLFA_INVALID_OPERATION; a fade push on a capturing stream: CLFA_INVALID_OPERATION.  The argument checks come before
+ * the device is looked at; a failed object answers with its error. */
 CLFA_API int clfa_nupconv_matrix_create(clfa_nupconv_matrix **pc, int device, int cvs, int pts0, int pts1, int inputs,
                                         int outputs);
 CLFA_API void clfa_nupconv_matrix_destroy(clfa_nupconv_matrix *pc);
@@ -1188,15 +1228,22 @@ CLFA_API int clfa_nupconv_matrix_nparts(const clfa_nupconv_matrix *pc, int level
 CLFA_API int clfa_nupconv_matrix_segments(const clfa_nupconv_matrix *pc, int level);
 /* head blocks since creation or the last reset */
 CLFA_API long clfa_nupconv_matrix_position(const clfa_nupconv_matrix *pc);
-/* the state: both levels' rings, responses and tails, the stage rows and the pending tail output */
+/* the state: both levels' rings, responses and tails, the stage rows and the pending tail output (+ a fade's second
+ * responses, tails and pending rows) */
 CLFA_API size_t clfa_nupconv_matrix_state_bytes(const clfa_nupconv_matrix *pc);
 /* the workspaces: both levels' single-block accumulators and partial sums (allocated at creation) and the head's sub-batch
- * workspaces (none until a call of several blocks; grown by the call that needs more blocks than any before it) */
+ * workspaces (none until a call of several blocks; grown by the call that needs more blocks than any before it; + a
+ * fade's second accumulators and partial sums and its head rows) */
 CLFA_API size_t clfa_nupconv_matrix_workspace_bytes(const clfa_nupconv_matrix *pc);
 /* "k_nupm_mac" ("" for a failed object) */
 CLFA_API const char *clfa_nupconv_matrix_kernel_name(const clfa_nupconv_matrix *pc);
 CLFA_API int clfa_nupconv_matrix_push_ir(clfa_nupconv_matrix *pc, const float *ir); /* packed host rows, blocking */
 CLFA_API int clfa_nupconv_matrix_push_ir_dev(clfa_nupconv_matrix *pc, const void *ir, long row_stride, void *stream);
+CLFA_API int clfa_nupconv_matrix_push_ir_fade(clfa_nupconv_matrix *pc, const float *ir, long fade_blocks); /* packed host rows, blocking */
+CLFA_API int clfa_nupconv_matrix_push_ir_fade_dev(clfa_nupconv_matrix *pc, const void *ir, long row_stride, long fade_blocks,
+                                                  void *stream);
+/* head blocks of the fade not yet processed; 0 = none (and for a NULL handle) */
+CLFA_API long clfa_nupconv_matrix_fade_remaining(const clfa_nupconv_matrix *pc);
 CLFA_API int clfa_nupconv_matrix_process_dev(clfa_nupconv_matrix *pc, void *out, long out_stride, const void *in,
                                              long in_stride, long nblocks, void *stream);
 CLFA_API int clfa_nupconv_matrix_convolution(clfa_nupconv_matrix *pc, float *out, const float *in, long nblocks);

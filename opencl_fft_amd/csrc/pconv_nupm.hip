@@ -1,10 +1,11 @@
 // pconv_nupm.hip — the multiply-accumulate of the non-uniformly partitioned convolution matrix (clfa_nupconv_matrix,
 // conv_host.cpp): `inputs` signals into `outputs` signals through outputs x inputs responses held on two levels, a head of
 // small partitions (pts0) and a tail of large ones (pts1 = m * pts0) whose blocks are multiplied in m slices of their bins.
-//   k_nupm_mac     one segment's sum over r = i * nparts + p, ascending, of  A_i[(w - (nparts - 1) + p) mod nparts] (.)
+//   k_nupm_mac     one segment's sum over r = i * nparts + p, ascending, of  A_i[(w - (nparts - 1) + p) mod ring] (.)
 //                  H_{o,i}[nparts - 1 - p]  for ONE block of a level over a range of its 16-byte items: the terms, their
 //                  order and the segments of k_pconvm_mac, hence its bits, however the bins are cut into slices.  A
-//                  single-block call runs the head's block and the tail's slice in one launch of it
+//                  single-block call runs the head's block and the tail's slice in one launch of it; a fade's block runs
+//                  both under both response sets (four jobs)
 //   k_nupm_reduce  Y = ((Y + P[0]) + P[1]) + ... of the jobs with more than one segment, the order of k_pconvm_reduce
 // Everything around them exists: the transforms are launch_pconvb_forward / launch_pconvb_inverse with K = 1, the stage row
 // and the mix are k_nupc_stage / k_nupc_mix (pconv_nup.hip) over inputs / outputs rows, and calls of several blocks run the
@@ -21,7 +22,14 @@ __device__ __forceinline__ cpx2 ld_plain(const cpx2 *p) { return *p; }
 
 }  // namespace
 
-struct NupmMacJobs { NupmMacJob j[kNupmMacJobs]; };
+template <int NJ> struct NupmMacJobs { NupmMacJob j[NJ]; };
+
+// blockIdx.y picks the job (selects, not an index into the kernel's arguments)
+template <int NJ>
+__device__ __forceinline__ const NupmMacJob &nupm_pick(const NupmMacJobs<NJ> &jobs) {
+  static_assert(NJ == 2 || NJ == kNupmMacJobs, "two jobs, or a fade's four");
+  return NJ > 2 && blockIdx.y >= 2 ? (blockIdx.y == 3 ? jobs.j[NJ - 1] : jobs.j[NJ - 2]) : (blockIdx.y ? jobs.j[1] : jobs.j[0]);
+}
 
 // ---------------------------------------------------------------------------------
 // One lane = (segment, output, item), the lanes laid over all three together, so that a slice of 16 items and a handful of
@@ -30,14 +38,15 @@ struct NupmMacJobs { NupmMacJob j[kNupmMacJobs]; };
 // without a division per term, and stays on the last term of the whole sequence once it is there; terms past the end of
 // the segment are loaded (they are the next segment's, valid memory) and dropped by a select.  Response frames are read
 // once per block: non-temporal loads.  Input frames are read by every output: plain loads, which may hit the CU's L1
-// (measured against non-temporal ones: profiles/HISTORY.md).
+// (measured against non-temporal ones: profiles/HISTORY.md).  An input's frames are `ring` apart: the tail's ring keeps
+// more frames than the sum walks.
 // ---------------------------------------------------------------------------------
-template <int D>
-__global__ __launch_bounds__(64) void k_nupm_mac(NupmMacJobs jobs, int inputs, int outputs) {
-  const NupmMacJob &job = blockIdx.y ? jobs.j[1] : jobs.j[0];
+template <int D, int NJ>
+__global__ __launch_bounds__(64) void k_nupm_mac(NupmMacJobs<NJ> jobs, int inputs, int outputs) {
+  const NupmMacJob &job = nupm_pick(jobs);
   const cpx *__restrict__ ringA = job.ringA;
   const cpx *__restrict__ H = job.H;
-  const int w = job.w, bins = job.bins, nparts = job.nparts, segs = job.segs, item0 = job.item0, nitems = job.nitems;
+  const int w = job.w, bins = job.bins, nparts = job.nparts, ring = job.ring, segs = job.segs, item0 = job.item0, nitems = job.nitems;
   const long lanes = (long)segs * outputs * nitems;
   if (blockIdx.x * 64L >= lanes) return;   // (the grid is the larger job's)
   const int hb = bins >> 1;
@@ -55,10 +64,9 @@ __global__ __launch_bounds__(64) void k_nupm_mac(NupmMacJobs jobs, int inputs, i
   int hi = (int)(r0 / nparts), hp = (int)(r0 - (long)hi * nparts);
   auto fetch = [&](cpx2 &x, cpx2 &h) {
     int f = w - (nparts - 1) + hp;
-    f = f < 0 ? f + nparts : f;
-    const long row = (long)hi * nparts;
-    x = ld_plain(xa + (row + f) * hb);
-    h = ld_nt(ha + (row + (nparts - 1 - hp)) * hb);
+    f = f < 0 ? f + ring : f;
+    x = ld_plain(xa + ((long)hi * ring + f) * hb);
+    h = ld_nt(ha + ((long)hi * nparts + (nparts - 1 - hp)) * hb);
     const int more = hr + 1 < total ? 1 : 0;
     hr += more;
     hp += more;
@@ -97,8 +105,9 @@ __global__ __launch_bounds__(64) void k_nupm_mac(NupmMacJobs jobs, int inputs, i
 // ---------------------------------------------------------------------------------
 // the segments' partial sums, added in ascending segment order: Y = ((Y + P[0]) + P[1]) + ..., one lane = (output, item)
 // ---------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_nupm_reduce(NupmMacJobs jobs, int outputs) {
-  const NupmMacJob &job = blockIdx.y ? jobs.j[1] : jobs.j[0];
+template <int NJ>
+__global__ __launch_bounds__(64) void k_nupm_reduce(NupmMacJobs<NJ> jobs, int outputs) {
+  const NupmMacJob &job = nupm_pick(jobs);
   const int segs = job.segs, nitems = job.nitems, hb = job.bins >> 1;
   const long lanes = (long)outputs * nitems;
   const long gid = blockIdx.x * 64L + threadIdx.x;
@@ -129,7 +138,7 @@ __global__ __launch_bounds__(64) void k_nupm_reduce(NupmMacJobs jobs, int output
 // ---------------------------------------------------------------------------------
 static bool nupm_job_ok(const NupmMacJob &j) {
   return j.ringA && j.H && j.Y && j.bins >= 2 && j.item0 >= 0 && j.nitems >= 1 && j.item0 + j.nitems <= j.bins / 2 && j.nparts >= 1 &&
-         j.w >= 0 && j.w < j.nparts && j.segs >= 1 && (j.segs == 1 || j.P);
+         j.ring >= j.nparts && j.w >= 0 && j.w < j.ring && j.segs >= 1 && (j.segs == 1 || j.P);
 }
 
 hipError_t launch_nupm_mac(const NupmMacJob *jobs, int njobs, int inputs, int outputs, hipStream_t s) {
@@ -141,8 +150,15 @@ hipError_t launch_nupm_mac(const NupmMacJob *jobs, int njobs, int inputs, int ou
     blocks = b > blocks ? b : blocks;
   }
   if (blocks > 0x7fffffffL) return hipErrorInvalidValue;
-  const NupmMacJobs a = {{jobs[0], jobs[njobs - 1]}};   // (a job past njobs repeats the last one: blockIdx.y never picks it)
-  hipLaunchKernelGGL((k_nupm_mac<kNupmMacDepth>), dim3((unsigned)blocks, njobs), dim3(64), 0, s, a, inputs, outputs);
+  // (jobs past njobs repeat the last one: blockIdx.y never picks them)
+  if (njobs > 2) {
+    NupmMacJobs<kNupmMacJobs> a;
+    for (int i = 0; i < kNupmMacJobs; i++) a.j[i] = jobs[i < njobs ? i : njobs - 1];
+    hipLaunchKernelGGL((k_nupm_mac<kNupmMacDepth, kNupmMacJobs>), dim3((unsigned)blocks, njobs), dim3(64), 0, s, a, inputs, outputs);
+  } else {
+    const NupmMacJobs<2> a = {{jobs[0], jobs[njobs - 1]}};
+    hipLaunchKernelGGL((k_nupm_mac<kNupmMacDepth, 2>), dim3((unsigned)blocks, njobs), dim3(64), 0, s, a, inputs, outputs);
+  }
   return hipGetLastError();
 }
 
@@ -157,8 +173,14 @@ hipError_t launch_nupm_reduce(const NupmMacJob *jobs, int njobs, int outputs, hi
   }
   if (!blocks) return hipSuccess;
   if (blocks > 0x7fffffffL) return hipErrorInvalidValue;
-  const NupmMacJobs a = {{jobs[0], jobs[njobs - 1]}};
-  hipLaunchKernelGGL(k_nupm_reduce, dim3((unsigned)blocks, njobs), dim3(64), 0, s, a, outputs);
+  if (njobs > 2) {
+    NupmMacJobs<kNupmMacJobs> a;
+    for (int i = 0; i < kNupmMacJobs; i++) a.j[i] = jobs[i < njobs ? i : njobs - 1];
+    hipLaunchKernelGGL(k_nupm_reduce<kNupmMacJobs>, dim3((unsigned)blocks, njobs), dim3(64), 0, s, a, outputs);
+  } else {
+    const NupmMacJobs<2> a = {{jobs[0], jobs[njobs - 1]}};
+    hipLaunchKernelGGL(k_nupm_reduce<2>, dim3((unsigned)blocks, njobs), dim3(64), 0, s, a, outputs);
+  }
   return hipGetLastError();
 }
 

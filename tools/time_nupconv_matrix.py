@@ -9,8 +9,20 @@ figure per shape records a whole-signal call of --signal head blocks.  An object
 would take longer than --leg-budget-s by its first calls, is left out and the line says so: no figure is extrapolated.
 
     python tools/time_nupconv_matrix.py [--periods 3] [--cvs 262144] [--quick] [--out profiles/nupconv_matrix.txt]
+
+--fade: the timed crossfade of response changes (push_ir_fade), one line per shape, in four parts.  The plain path of
+this build against another build of the library (--parent-lib, the parent commit's libclfft_amd.so) in one process, both
+through the C ABI, in four alternating legs each, with two objects of the other build: every leg's median and worst
+phase, so that the difference between the builds' means can be held against what one build's own legs, and its own two
+objects, differ by.  A block of a fade (median, worst phase) against the composition it replaces: two NupconvMatrix
+objects fed alike and the three torch operations of the mix.  The fade push itself (the response transforms and the
+priming of the second set) beside a plain push, median of three.  And the state before and after the first fade,
+against two objects.
+
+    python tools/time_nupconv_matrix.py --fade [--parent-lib old/libclfft_amd.so] [--out profiles/nupconv_matrix_fade.txt]
 """
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -22,6 +34,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import opencl_fft_amd as fa  # noqa: E402
+from time_nupconv import leg_stats, other_build  # noqa: E402  (tools/time_nupconv.py: the A/B of Nupconv's fade)
 
 # pts0, pts1, inputs, outputs
 SHAPES = [(64, 4096, 16, 2), (64, 4096, 4, 4), (64, 4096, 64, 64), (256, 4096, 16, 2), (256, 4096, 4, 4), (256, 4096, 64, 64)]
@@ -120,8 +133,127 @@ def shape(cvs, pts0, pts1, I, O, periods, signal, leg_budget_s):
     return r
 
 
+class Raw:
+    """a NupconvMatrix of one build of the library through its C ABI: what both builds of an A/B are called through"""
+
+    def __init__(self, lib, cvs, pts0, pts1, I, O, stream):
+        self.lib, self.h, self.s = lib, C.c_void_p(), stream
+        assert lib.clfa_nupconv_matrix_create(C.byref(self.h), 0, cvs, pts0, pts1, I, O) == 0
+
+    def push(self, h):
+        assert self.lib.clfa_nupconv_matrix_push_ir_dev(self.h, h.data_ptr(), h.stride(1), self.s) == 0
+
+    def push_fade(self, h, blocks):
+        assert self.lib.clfa_nupconv_matrix_push_ir_fade_dev(self.h, h.data_ptr(), h.stride(1), blocks, self.s) == 0
+
+    def run(self, out, x):
+        assert self.lib.clfa_nupconv_matrix_process_dev(self.h, out.data_ptr(), out.stride(0), x.data_ptr(), x.stride(0), 1, self.s) == 0
+
+    def position(self):
+        return self.lib.clfa_nupconv_matrix_position(self.h)
+
+    def state_mib(self):
+        return round(self.lib.clfa_nupconv_matrix_state_bytes(self.h) / 2 ** 20, 1)
+
+    def close(self):
+        self.lib.clfa_nupconv_matrix_destroy(self.h)
+        self.h = None
+
+
+def fade_shape(cvs, pts0, pts1, I, O, periods, parent, new_position=0):
+    from opencl_fft_amd import _lib
+    m = pts1 // pts0
+    n = periods * m
+    s = torch.cuda.current_stream().cuda_stream
+    h = torch.rand((O, I, cvs), device="cuda") - 0.5
+    h2 = torch.rand((O, I, cvs), device="cuda") - 0.5
+    x = torch.rand((I, pts0), device="cuda") - 0.5
+    out = torch.empty((O, pts0), device="cuda")
+    r = {"cvs": cvs, "pts0": pts0, "pts1": pts1, "inputs": I, "outputs": O, "periods": periods}
+
+    def legs_of(run):
+        return leg_stats(calls(run, n).reshape(periods, m) * 1e3)
+
+    # the plain path: this build and the parent's in alternating legs
+    # (two objects of the parent's: what two objects of ONE build differ by.  new_position: where this build's object
+    # stands in the order of creation and of the first leg — an object's place shows in its times)
+    roles = ["parent", "parent_2"] if parent is not None else []
+    roles.insert(min(new_position, len(roles)), "new")
+    r["order"] = roles
+    builds = {}
+    for k in roles:
+        builds[k] = Raw(_lib.lib() if k == "new" else parent, cvs, pts0, pts1, I, O, s)
+        builds[k].push(h)
+    new = builds["new"]
+    r["segments"] = [_lib.lib().clfa_nupconv_matrix_segments(new.h, k) for k in (0, 1)]
+    for b in builds.values():
+        calls(lambda: b.run(out, x), 2 * m)
+    plain = {k: [] for k in builds}
+    order = list(builds)
+    for _ in range(4):                          # forwards, backwards, ...: no object always follows the same other
+        for k in order:
+            assert builds[k].position() % m == 0
+            plain[k].append(legs_of(lambda: builds[k].run(out, x)))
+        order.reverse()
+    r["plain_us"] = plain
+    if parent is not None:
+        keys = ("median", "worst_phase")
+        mean = {b: {k: float(np.mean([l[k] for l in plain[b]])) for k in keys} for b in plain}
+        r["parent_leg_spread_us"] = {k: round(max(l[k] for l in plain["parent"]) - min(l[k] for l in plain["parent"]), 2) for k in keys}
+        r["parent_object_spread_us"] = {k: round(abs(mean["parent"][k] - mean["parent_2"][k]), 2) for k in keys}
+        r["new_minus_parent_us"] = {k: round(mean["new"][k] - (mean["parent"][k] + mean["parent_2"][k]) / 2, 2) for k in keys}
+        builds.pop("parent").close()
+        builds.pop("parent_2").close()
+    # a block of a fade against the composition it replaces: two objects fed alike and the mix in three torch operations
+    ca, cb = Raw(_lib.lib(), cvs, pts0, pts1, I, O, s), Raw(_lib.lib(), cvs, pts0, pts1, I, O, s)
+    ca.push(h)
+    cb.push(h2)
+    ya, yb, d = torch.empty_like(out), torch.empty_like(out), torch.empty_like(out)
+    g = (torch.arange(pts0, device="cuda", dtype=torch.float32) / float(n * pts0)).expand_as(out).contiguous()
+
+    def composition():
+        ca.run(ya, x)
+        cb.run(yb, x)
+        torch.sub(yb, ya, out=d)
+        d.mul_(g)
+        torch.add(ya, d, out=out)
+
+    r["state_mib"] = {"before_the_first_fade": new.state_mib(), "two_objects": round(ca.state_mib() + cb.state_mib(), 1)}
+    new.push_fade(h2, 2 * m)                    # warm-up: the first fade allocates the second set
+    r["state_mib"]["after_the_first_fade"] = new.state_mib()
+    calls(lambda: new.run(out, x), 2 * m)
+    calls(composition, 2 * m)
+    fade, comp = [], []
+    for leg in range(2):
+        assert new.position() % m == 0
+        new.push_fade(h if leg % 2 == 0 else h2, n)
+        fade.append(legs_of(lambda: new.run(out, x)))
+        comp.append(legs_of(composition))
+    r["fade_block_us"], r["composition_block_us"] = fade, comp
+    r["fade_over_composition"] = {k: round(float(np.mean([l[k] for l in fade]) / np.mean([l[k] for l in comp])), 3)
+                                  for k in ("median", "worst_phase")}
+    ca.close()
+    cb.close()
+    # the push: a fade push (response transforms and priming; phases 0, 1, 2 of a period past the third) beside a plain one
+    tf, tp = [], []
+    for k in range(3):
+        tf.append(calls(lambda: new.push_fade(h2 if k % 2 == 0 else h, 1), 1)[0])
+        new.run(out, x)
+    for k in range(3):
+        tp.append(calls(lambda: new.push(h), 1)[0])
+    r["push_ms"] = {"fade": round(float(np.median(tf)), 3), "plain": round(float(np.median(tp)), 3)}
+    r["block_lasts_us_at_48k"] = round(pts0 / 48e3 * 1e6, 1)
+    new.close()
+    torch.cuda.synchronize()
+    return r
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--fade", action="store_true", help="the timed crossfade: plain path A/B, fade block, fade push, state")
+    ap.add_argument("--parent-lib", default=None, help="--fade: another build of libclfft_amd.so to hold the plain path against")
+    ap.add_argument("--new-position", type=int, default=0, choices=(0, 1, 2),
+                    help="--fade: this build's object is created first (0), between the parent's two (1) or last (2)")
     ap.add_argument("--periods", type=int, default=3)
     ap.add_argument("--cvs", type=int, default=1 << 18)
     ap.add_argument("--signal", type=int, default=256, help="head blocks of the whole-signal call")
@@ -130,14 +262,18 @@ def main():
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
-    lines = [json.dumps({"device": fa.device_name(0), "how": __doc__.split("\n\n")[0].replace("\n", " ")})]
+    lines = [json.dumps({"device": fa.device_name(0), "how": __doc__.split("\n\n")[2 if a.fade else 0].replace("\n", " ")})]
     probe = {k: round(v, 3) for k, v in fa.bandwidth_probe(0, 1 << 30, 100).items()}
     lines.append(json.dumps({"bandwidth_probe_tb_s": probe}))
     print(lines[-1], flush=True)
+    parent = other_build(a.parent_lib) if a.fade and a.parent_lib else None
     for pts0, pts1, I, O in SHAPES:
         if a.quick and I * O > 256:
             continue
-        lines.append(json.dumps(shape(a.cvs, pts0, pts1, I, O, a.periods, a.signal, a.leg_budget_s)))
+        if a.fade:
+            lines.append(json.dumps(fade_shape(a.cvs, pts0, pts1, I, O, a.periods, parent, a.new_position)))
+        else:
+            lines.append(json.dumps(shape(a.cvs, pts0, pts1, I, O, a.periods, a.signal, a.leg_budget_s)))
         print(lines[-1], flush=True)
         if a.out:
             with open(a.out, "w") as f:
