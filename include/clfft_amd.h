@@ -1104,7 +1104,48 @@ CLFA_API const char *clfa_pconv_matrix_kernel_name(const clfa_pconv_matrix *m);
  * Refusals (the state is untouched in each): fade_blocks < 1, fade_blocks * pts0 > 2^31 - 1 or any argument error of
  * push_ir_dev: CLFA_INVALID_VALUE; a fade push, a plain push_ir / push_ir_dev, or a reset while fade_remaining() > 0:
  * CLFA_INVALID_OPERATION; a fade push on a capturing stream: CLFA_INVALID_OPERATION.  The argument checks come before
- * the device is looked at; a failed object answers with its error. */
+ * the device is looked at; a failed object answers with its error.
+ *
+ * Time-varying second input (process_tv_dev, convolution_tv): the response as a live stream, the reference's
+ * convolution(out, in1, in2) — "block t of in2 overwrites partition t mod nparts" — stated for two levels.  With
+ * R1 = n1 + 2 (the tail blocks of one response period), R0 = R1 * m (its head blocks, tv_period()) and
+ * L = R1 * pts1 (the response length push_ir reads), the second input w is a stream of head blocks beside x, and sample j
+ * of w is response sample j mod L.  Let c = position() before the block.  A time-varying block carrying the pts0 samples
+ * w_c does, in this order:
+ *   1. phase 0 (c mod m == 0 and c >= m): with U = c/m - 1 and r = U mod R1, if r >= 2 and every one of the m head blocks
+ *      of tail block U was a time-varying block, tail partition r - 2 becomes the pts1 samples those blocks carried.  The
+ *      step belongs to the finished tail block: whichever block arrives at phase 0 performs it, plain or time-varying;
+ *   2. head partition: with a = c mod R0, if a < 2m head partition a becomes w_c, before this block's
+ *      multiply-accumulate;
+ *   3. staging: w_c is kept as part c mod m of the second input's tail block c div m;
+ *   4. the block is processed exactly as a plain block is.
+ * A plain block (process_dev, or process_tv_dev with in2 == NULL) does step 4 and, at phase 0, step 1; it spoils the tail
+ * block it falls into, whose partition keeps its old content (the opcode's "freeze").  So plain and time-varying calls
+ * mix freely; a partition never written keeps what push_ir put there, or zeros; a plain push_ir between calls overwrites
+ * everything as before; and tail partitions change at phase 0 only: no tail block mixes two responses across its slices.
+ * Definition, bit for bit: take a second plain object of the same geometry that has received the same pushes and inputs,
+ * and keep a response array hc beside it, starting as the pushed responses or zeros.  Before each head block rewrite hc
+ * by steps 1 and 2; whenever it changed, push_ir(hc); then process the block with process_dev.  The time-varying call's
+ * output and every later output are the bits of that object (the re-push of the unchanged partitions gives their old
+ * bits, so a push off phase 0 is harmless there): a rewritten partition is push_ir's forward transform of those samples.
+ * A call of K blocks equals K calls of one block, in output and in the state left, however the stream is cut and however
+ * plain calls are interleaved.
+ * Arguments: rows as process_dev; in2 has its own stride and alignment (any 4-byte aligned address) and may be `in`
+ * itself; in2 == NULL is the plain call.  An out that overlaps in or in2, even partly, or any other bad argument:
+ * CLFA_INVALID_VALUE.  A capturing stream, or a non-NULL in2 while fade_remaining() > 0: CLFA_INVALID_OPERATION (a fade
+ * push AFTER time-varying calls is allowed; later writes go to the set then in force).  Every refusal leaves the state
+ * untouched, and the argument checks come before the device is looked at.  reset clears the second input's staged block
+ * and its completeness count; the responses stay.  The second stage row (channels x pts1 floats) is allocated by the first
+ * time-varying call and counted by state_bytes() from then on; a plain object's figures do not change.
+ * Schedule: a single time-varying block is one launch FEWER than a plain one — k_nupc_fwd transforms x and w_c in one
+ * launch and files both in their stage rows as it loads them (at phase 0 a launch of it for the tail level goes first:
+ * the finished block of x into the input ring and, where step 1 applies, the second input's into its response frame),
+ * then k_nupc_mac, the head inverse, k_nupc_mix and, after phase m - 1, the tail inverse.  A call of several blocks is
+ * cut at a = 2m and at the response period's end: for the blocks with a < 2m the head is clfa_pconv_process_blocks_dev's
+ * time-varying route (the commit launch writes the new frames into the response ring; a second input whose rows lie
+ * otherwise than x's takes a forward launch of its own), for the others its static route; either way one k_nupc_stage2
+ * launch stages both inputs between period boundaries, and the tail keeps one launch of slices there.  The head's
+ * second-input sub-batch workspace is allocated by the first time-varying call and counted by workspace_bytes(). */
 CLFA_API int clfa_nupconv_create(clfa_nupconv **pc, int device, int cvs, int pts0, int pts1, int channels);
 CLFA_API void clfa_nupconv_destroy(clfa_nupconv *pc);
 CLFA_API int clfa_nupconv_get_error(const clfa_nupconv *pc);
@@ -1130,6 +1171,13 @@ CLFA_API long clfa_nupconv_fade_remaining(const clfa_nupconv *pc);
 CLFA_API int clfa_nupconv_process_dev(clfa_nupconv *pc, void *out, long out_stride, const void *in, long in_stride,
                                       long nblocks, void *stream);
 CLFA_API int clfa_nupconv_convolution(clfa_nupconv *pc, float *out, const float *in, long nblocks);
+/* the time-varying second input (above); in2 == NULL: the plain call */
+CLFA_API int clfa_nupconv_process_tv_dev(clfa_nupconv *pc, void *out, long out_stride, const void *in, long in_stride,
+                                         const void *in2, long in2_stride, long nblocks, void *stream);
+CLFA_API int clfa_nupconv_convolution_tv(clfa_nupconv *pc, float *out, const float *in, const float *in2,
+                                         long nblocks); /* packed host rows, blocking */
+/* R0 = (n1 + 2) * m, the head blocks of one response period; 0 for a NULL handle or a failed object */
+CLFA_API long clfa_nupconv_tv_period(const clfa_nupconv *pc);
 CLFA_API int clfa_nupconv_reset(clfa_nupconv *pc, void *stream);
 
 /* ---- non-uniformly partitioned convolution matrix (extension): many inputs into many outputs at low latency ----------

@@ -96,6 +96,9 @@ SYMBOLS = [
     ("clfa_nupconv_fade_remaining", C.c_long, [_vp]),
     ("clfa_nupconv_process_dev", C.c_int, [_vp, _vp, C.c_long, _vp, C.c_long, C.c_long, _vp]),
     ("clfa_nupconv_convolution", C.c_int, [_vp, _vp, _vp, C.c_long]),
+    ("clfa_nupconv_process_tv_dev", C.c_int, [_vp, _vp, C.c_long, _vp, C.c_long, _vp, C.c_long, C.c_long, _vp]),
+    ("clfa_nupconv_convolution_tv", C.c_int, [_vp, _vp, _vp, _vp, C.c_long]),
+    ("clfa_nupconv_tv_period", C.c_long, [_vp]),
     ("clfa_nupconv_reset", C.c_int, [_vp, _vp]),
     ("clfa_nupconv_matrix_create", C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     ("clfa_nupconv_matrix_destroy", None, [_vp]),

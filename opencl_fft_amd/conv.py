@@ -332,6 +332,31 @@ class Nupconv(_Object):
         return _pkg.lib().clfa_nupconv_process_dev(self._h, out.data_ptr(), so, x.data_ptr(), si, li // self.pts0,
                                                    _stream_of(x, stream))
 
+    tv_period = property(lambda s: s._get("tv_period"), doc="head blocks of one response period, (nparts(1) + 2) * pts1 // pts0")
+
+    def convolution_tv(self, output, input, second):
+        """convolution() with a time-varying second input (clfft_amd.h): `second`, shaped as `input`, is the response as
+        a live stream — its sample j is response sample j % (tv_period * pts0); blocking"""
+        output = _host(output, np.float32)
+        a = np.ascontiguousarray(input, dtype=np.float32)
+        b = np.ascontiguousarray(second, dtype=np.float32)
+        if a.ndim == 1:
+            a = a[None, :]
+        if (a.ndim != 2 or a.shape[0] != self.channels or a.shape[1] % self.pts0 or output.size != a.size
+                or b.size != a.size):
+            return CL_INVALID_VALUE
+        return _pkg.lib().clfa_nupconv_convolution_tv(self._h, output.ctypes.data, a.ctypes.data, b.ctypes.data,
+                                                      a.shape[1] // self.pts0)
+
+    def process_tv_device(self, out, x, w, stream=None):
+        """process_device() with a time-varying second input w (clfft_amd.h): device tensors as there, w with its own row
+        stride (w may be x itself).  Not while fade_remaining() > 0 and not under graph capture (CL_INVALID_OPERATION)."""
+        (lo, so), (li, si), (lw, sw) = (_block_rows(t, self.channels, "channels", True) for t in (out, x, w))
+        if lo != li or lw != li or li % self.pts0:
+            return CL_INVALID_VALUE
+        return _pkg.lib().clfa_nupconv_process_tv_dev(self._h, out.data_ptr(), so, x.data_ptr(), si, w.data_ptr(), sw,
+                                                      li // self.pts0, _stream_of(x, stream))
+
     def reset(self, stream=None):
         """forget the input history (position 0); the responses stay.  `stream`: a HIP stream handle, default the
         current torch stream of the object's device"""

@@ -959,12 +959,15 @@ struct clfa_nupconv {
   NupSet &first() { return sets[cur]; }
   NupSet &second() { return sets[cur ^ 1]; }
   DevBuf stage;                  // the tail block being collected
-  DevBuf Y0;                     // a single head block's accumulators (a single block's X is its ring frame w)
+  DevBuf stage2;                 // ... and the second input's (allocated by the first time-varying call)
+  int tv_count = 0;              // time-varying blocks among the head blocks of the tail block being collected
+  DevBuf Y0;                    // a single head block's accumulators (a single block's X is its ring frame w)
   DevBuf Y0b, headb;             // a fade: the second path's head accumulators and head samples (channels x pts0)
   long fade_len = 0, fade_done = 0;   // head blocks of the pending fade (0: none) and how many of them have been processed
   DevBuf bX, bY, btail;          // the head's sub-batch workspaces, for hcap blocks (grown by the call that needs more)
-  int hcap = 0, bcap = 1, bkt = 4;
-  DevBuf in1, in2, out;          // staging of the blocking form (conv_arrays; in2 stays empty)
+  DevBuf bXB;                    // ... and the second input's spectra, for hcap2 blocks (time-varying calls of several blocks)
+  int hcap = 0, hcap2 = 0, bcap = 1, bkt = 4;
+  DevBuf in1, in2, out;          // staging of the blocking forms (conv_arrays; in2: the time-varying second input)
   DevBuf ir;                     // ... and of push_ir
   StreamOrder order;
   long c = 0;                    // head blocks since creation / reset
@@ -1044,8 +1047,11 @@ static int nup_push_level(const NupLevel &l, const DevBuf &ringB, const float *i
   return CLFA_SUCCESS;
 }
 
-// the head's K blocks through the blocks route, sub-batch by sub-batch, as clfa_pconv_process_blocks_dev
-static int nup_head(clfa_nupconv *p, float *out, long out_stride, const float *in, long in_stride, long nblocks, hipStream_t s) {
+// the head's K blocks through the blocks route, sub-batch by sub-batch, as clfa_pconv_process_blocks_dev.  in2: the blocks
+// are time-varying ones at positions pos, pos + 1, ... < n0 of their response period, the time-varying blocks route: block
+// j's second input becomes response frame n0 - 1 - (pos + j) for itself and the blocks after it
+static int nup_head(clfa_nupconv *p, float *out, long out_stride, const float *in, long in_stride, long nblocks, hipStream_t s,
+                    const float *in2 = nullptr, long in2_stride = 0, long pos = 0) {
   NupLevel &l = p->lv[0];
   NupSet &set = p->first();
   PconvBlocks a;
@@ -1065,10 +1071,15 @@ static int nup_head(clfa_nupconv *p, float *out, long out_stride, const float *i
   a.half = (const cpx *)l.half.p;
   a.w2f = (const cpx *)l.w2f.p;
   a.w2i = (const cpx *)l.w2i.p;
+  a.XB = (cpx *)p->bXB.p;
+  a.in2_stride = in2_stride;
+  a.aligned_in2 = ((uintptr_t)in2 & 7) == 0 && (in2_stride & 1) == 0;
   for (long j0 = 0; j0 < nblocks; j0 += a.K) {
     a.K = (int)(nblocks - j0 < p->hcap ? nblocks - j0 : p->hcap);
     a.w = l.w;
     a.in1 = in + j0 * p->pts0;
+    a.in2 = in2 ? in2 + j0 * p->pts0 : nullptr;
+    a.w2 = (int)(l.g.nparts - 1 - (pos + j0));
     a.out = out + j0 * p->pts0;
     HIP_TRY(launch_pconv_blocks(a, s));
     l.w = (int)((l.w + a.K) % l.g.nparts);
@@ -1102,18 +1113,41 @@ static int nup_inverse(const NupLevel &l, const DevBuf &Y, DevBuf (&tails)[2], i
   return CLFA_SUCCESS;
 }
 
+// The time-varying second input (clfft_amd.h), step 1, asked at phase 0 of period P >= 1: the response frame of the tail
+// level that the second input's finished tail block U = P - 1 rewrites, or -1 where it rewrites none — one of its m head
+// blocks was a plain block, or it lies in the two head-covered tail blocks of its response period
+static int nup_tv_frame(const clfa_nupconv *p) {
+  const int n1 = p->lv[1].g.nparts;
+  const long r = (p->c / p->m - 1) % (n1 + 2);
+  return p->tv_count == p->m && r >= 2 ? n1 - 1 - (int)(r - 2) : -1;
+}
+// ... carried out by a plain block: the second stage row -> that frame of the set in force, push_ir's transform
+static int nup_tv_commit(clfa_nupconv *p, hipStream_t s) {
+  const NupLevel &t = p->lv[1];
+  const int fr = nup_tv_frame(p);
+  if (fr >= 0)
+    HIP_TRY(launch_pconvb_forward(t.g.logb, (const float *)p->stage2.p, p->pts1, (cpx *)p->first().ringB[1].p + (long)fr * t.g.bins, 1,
+                                  t.g.nparts, t.g.channels, 1, (const cpx *)t.half.p, (const cpx *)t.w2f.p, s));
+  return CLFA_SUCCESS;
+}
+
 // nblocks >= 1 blocks outside a fade.  One block: the head's forward transform straight into its ring frame, its
 // multiply-accumulate beside the tail's slice in one launch of k_nupc_mac, its inverse.  Several blocks: the head through
 // the blocks route over the whole call.  The arithmetic of a bin is the same on both ways, and both leave the same rings,
-// tails and positions.
-static int nup_blocks(clfa_nupconv *p, float *o, long out_stride, const float *x, long in_stride, long nblocks, hipStream_t s) {
+// tails and positions.  x2 (or NULL): the blocks are time-varying ones, a stretch that lies on one side of a = n0 in its
+// response period — their second input is staged beside x, and before a = n0 the head takes the time-varying blocks route.
+static int nup_blocks(clfa_nupconv *p, float *o, long out_stride, const float *x, long in_stride, long nblocks, hipStream_t s,
+                      const float *x2 = nullptr, long in2_stride = 0) {
   const long pts0 = p->pts0, m = p->m;
   const int ch = p->channels;
   const bool single = nblocks == 1;
   NupLevel &h = p->lv[0], &t = p->lv[1];
   NupSet &a = p->first();
-  if (!single)
-    if (int e = nup_head(p, o, out_stride, x, in_stride, nblocks, s)) return e;
+  if (!single) {
+    const long pos = p->c % ((long)(t.g.nparts + 2) * m);
+    const bool tv = x2 && pos < h.g.nparts;
+    if (int e = nup_head(p, o, out_stride, x, in_stride, nblocks, s, tv ? x2 : nullptr, in2_stride, pos)) return e;
+  }
   // the tail, period by period: head blocks [j0, j0 + k) of the call are phases [sa, sb) of period P, in which tail block
   // P - 1 is multiplied and tail block P - 2 is heard
   const int hb0 = (int)(pts0 / 2);
@@ -1125,9 +1159,18 @@ static int nup_blocks(clfa_nupconv *p, float *o, long out_stride, const float *x
     if (single)
       if (int e = nup_forward(h, x, in_stride, s)) return e;
     // phase 0: the spectrum of the finished block, before this period's samples overwrite the row
-    if (P >= 1 && sa == 0)
+    if (P >= 1 && sa == 0) {
       if (int e = nup_forward(t, (const float *)p->stage.p, p->pts1, s)) return e;
-    HIP_TRY(launch_nupc_stage(x + j0 * pts0, in_stride, (float *)p->stage.p, p->pts1, off, n, ch, s));
+      if (int e = nup_tv_commit(p, s)) return e;
+    }
+    if (sa == 0) p->tv_count = 0;
+    if (x2) {
+      HIP_TRY(launch_nupc_stage2(x + j0 * pts0, in_stride, (float *)p->stage.p, x2 + j0 * pts0, in2_stride, (float *)p->stage2.p,
+                                 p->pts1, off, n, ch, s));
+      p->tv_count += (int)k;
+    } else {
+      HIP_TRY(launch_nupc_stage(x + j0 * pts0, in_stride, (float *)p->stage.p, p->pts1, off, n, ch, s));
+    }
     NupcMacJob jobs[2];
     int njobs = 0;
     if (single) jobs[njobs++] = nup_job(h, a.ringB[0], p->Y0, h.w, 0, hb0);
@@ -1149,6 +1192,87 @@ static int nup_blocks(clfa_nupconv *p, float *o, long out_stride, const float *x
   return CLFA_SUCCESS;
 }
 
+// One time-varying block (clfft_amd.h: the four steps), in one launch fewer than a plain block: k_nupc_fwd transforms both
+// inputs of a level in one launch and files the samples it loads in the stage rows.  At phase 0 the tail level's launch
+// goes first — it reads the stage rows that the head level's launch then overwrites: the finished block of x into the
+// input ring and, where step 1 applies, the second input's into its response frame.  The head level's launch: x into
+// ring frame w, the second input's block into response frame n0 - 1 - a where a = c mod R0 < n0 (otherwise that job only
+// copies).  The rest is the plain block's.
+static int nup_tv_block(clfa_nupconv *p, float *o, long out_stride, const float *x, long in_stride, const float *x2, long in2_stride,
+                        hipStream_t s) {
+  NupLevel &h = p->lv[0], &t = p->lv[1];
+  NupSet &a = p->first();
+  const int ch = p->channels, pts0 = p->pts0, m = p->m, hb0 = pts0 / 2, n0 = h.g.nparts;
+  const long P = p->c / m, R0 = (long)(t.g.nparts + 2) * m, pos = p->c % R0;
+  const int sa = (int)(p->c % m), off = sa * pts0;
+  const auto rows8 = [](const void *q, long stride) { return ((uintptr_t)q & 7) == 0 && (stride & 1) == 0; };
+  if (P >= 1 && sa == 0) {
+    NupcFwdJob jobs[2];
+    int njobs = 0;
+    jobs[njobs++] = {(const float *)p->stage.p, p->pts1, 1, (cpx *)t.ringA.p + (long)t.w * t.g.bins, t.ring, nullptr, 0};
+    const int fr = nup_tv_frame(p);
+    if (fr >= 0) jobs[njobs++] = {(const float *)p->stage2.p, p->pts1, 1, (cpx *)a.ringB[1].p + (long)fr * t.g.bins, t.g.nparts, nullptr, 0};
+    HIP_TRY(launch_nupc_fwd(t.g.logb, jobs, njobs, ch, (const cpx *)t.half.p, (const cpx *)t.w2f.p, s));
+  }
+  if (sa == 0) p->tv_count = 0;
+  const NupcFwdJob jobs0[2] = {
+      {x, in_stride, rows8(x, in_stride), (cpx *)h.ringA.p + (long)h.w * pts0, h.ring, (float *)p->stage.p + off, p->pts1},
+      {x2, in2_stride, rows8(x2, in2_stride), pos < n0 ? (cpx *)a.ringB[0].p + (long)(n0 - 1 - pos) * pts0 : nullptr, n0,
+       (float *)p->stage2.p + off, p->pts1}};
+  HIP_TRY(launch_nupc_fwd(h.g.logb, jobs0, 2, ch, (const cpx *)h.half.p, (const cpx *)h.w2f.p, s));
+  p->tv_count++;
+  NupcMacJob jobs[2];
+  int njobs = 0;
+  jobs[njobs++] = nup_job(h, a.ringB[0], p->Y0, h.w, 0, hb0);
+  if (P >= 1) jobs[njobs++] = nup_job(t, a.ringB[1], a.Y1, t.w, sa * hb0, hb0);
+  HIP_TRY(launch_nupc_mac(jobs, njobs, ch, s));
+  if (int e = nup_inverse(h, p->Y0, a.tail0, a.hcur, o, out_stride, s)) return e;
+  h.w = (h.w + 1) % h.ring;
+  HIP_TRY(launch_nupc_mix(o, out_stride, (const float *)a.pend.p, p->pts1, off, pts0, ch, s));
+  if (P >= 1 && sa == m - 1) {
+    if (int e = nup_inverse(t, a.Y1, a.tail1, a.tcur, (float *)a.pend.p, p->pts1, s)) return e;
+    t.w = (t.w + 1) % t.ring;
+  }
+  p->c++;
+  return CLFA_SUCCESS;
+}
+
+// nblocks >= 1 time-varying blocks outside a fade, cut at a = c mod R0 = n0 and at the response period's end: the blocks
+// with a in [0, n0) rewrite a head partition each, the head's time-varying blocks route; the others, a in [n0, R0), are a
+// static stretch for the head.  A stretch of one block is the single time-varying block.
+static int nup_tv_blocks(clfa_nupconv *p, float *o, long out_stride, const float *x, long in_stride, const float *x2, long in2_stride,
+                         long nblocks, hipStream_t s) {
+  const long pts0 = p->pts0, n0 = p->lv[0].g.nparts, R0 = (long)(p->lv[1].g.nparts + 2) * p->m;
+  for (long j = 0; j < nblocks;) {
+    const long pos = p->c % R0;
+    const long end = pos < n0 ? n0 : R0, k = nblocks - j < end - pos ? nblocks - j : end - pos;
+    if (int e = k == 1 ? nup_tv_block(p, o + j * pts0, out_stride, x + j * pts0, in_stride, x2 + j * pts0, in2_stride, s)
+                       : nup_blocks(p, o + j * pts0, out_stride, x + j * pts0, in_stride, k, s, x2 + j * pts0, in2_stride))
+      return e;
+    j += k;
+  }
+  return CLFA_SUCCESS;
+}
+
+// the head's sub-batch workspaces for a call of `rest` blocks through the blocks route; tv: the second input's as well
+static int nup_ensure_head(clfa_nupconv *p, long rest, hipStream_t s, bool tv = false) {
+  const size_t ch = (size_t)p->channels, pts0 = (size_t)p->pts0;
+  if (rest > 1 && rest > p->hcap) {
+    const int cap = (int)(rest < p->bcap ? rest : p->bcap);
+    if (cap > p->hcap) {
+      const size_t frames = sizeof(cpx) * ch * (size_t)cap * pts0;
+      if (int e = ensure_workspaces({{&p->bX, frames}, {&p->bY, frames}, {&p->btail, sizeof(float) * ch * pts0}}, s)) return e;
+      p->hcap = cap;
+    }
+  }
+  // (the frames of a channel lie hcap frames apart in every workspace of the sub-batch)
+  if (tv && p->hcap2 < p->hcap) {
+    if (int e = ensure_workspaces({{&p->bXB, sizeof(cpx) * ch * (size_t)p->hcap * pts0}}, s)) return e;
+    p->hcap2 = p->hcap;
+  }
+  return CLFA_SUCCESS;
+}
+
 // One head block of a fade, on the single-block route with every response-dependent step run for both sets over the
 // shared rings: the four multiply-accumulates are one launch, the first path's head goes to the output rows and the
 // second's to headb, and k_nupc_fade_mix forms both paths' head + pending sums and a + g * (b - a).  After the fade's last
@@ -1161,8 +1285,11 @@ static int nup_fade_block(clfa_nupconv *p, float *o, long out_stride, const floa
   const long P = p->c / m;
   const int sa = (int)(p->c % m), off = sa * pts0;
   if (int e = nup_forward(h, x, in_stride, s)) return e;
-  if (P >= 1 && sa == 0)
+  if (P >= 1 && sa == 0) {
     if (int e = nup_forward(t, (const float *)p->stage.p, p->pts1, s)) return e;
+    if (int e = nup_tv_commit(p, s)) return e;   // (time-varying blocks before the fade push: into the set in force)
+  }
+  if (sa == 0) p->tv_count = 0;
   HIP_TRY(launch_nupc_stage(x, in_stride, (float *)p->stage.p, p->pts1, off, pts0, ch, s));
   NupcMacJob jobs[kNupcMacJobs];
   int njobs = 0;
@@ -1241,11 +1368,12 @@ int clfa_nupconv_nparts(const clfa_nupconv *p, int level) {
 long clfa_nupconv_position(const clfa_nupconv *p) { return p ? p->c : 0; }
 size_t clfa_nupconv_state_bytes(const clfa_nupconv *p) {
   if (!p) return 0;
-  return p->lv[0].ringA.bytes + p->lv[1].ringA.bytes + p->stage.bytes + p->sets[0].state_bytes() + p->sets[1].state_bytes();
+  return p->lv[0].ringA.bytes + p->lv[1].ringA.bytes + p->stage.bytes + p->stage2.bytes + p->sets[0].state_bytes() +
+         p->sets[1].state_bytes();
 }
 size_t clfa_nupconv_workspace_bytes(const clfa_nupconv *p) {
   return p ? p->Y0.bytes + p->sets[0].Y1.bytes + p->sets[1].Y1.bytes + p->Y0b.bytes + p->headb.bytes + p->bX.bytes + p->bY.bytes +
-                 p->btail.bytes
+                 p->btail.bytes + p->bXB.bytes
            : 0;
 }
 long clfa_nupconv_fade_remaining(const clfa_nupconv *p) { return p ? p->fade_len - p->fade_done : 0; }
@@ -1315,15 +1443,7 @@ int clfa_nupconv_process_dev(clfa_nupconv *p, void *out, long out_stride, const 
   if (StreamOrder::capturing(s)) return CLFA_INVALID_OPERATION;
   // a fade's blocks run one at a time; what follows the fade in the same call takes the usual route
   const long fade = p->fade_len - p->fade_done, nf = nblocks < fade ? nblocks : fade, rest = nblocks - nf;
-  if (rest > 1 && rest > p->hcap) {
-    const int cap = (int)(rest < p->bcap ? rest : p->bcap);
-    if (cap > p->hcap) {
-      const size_t frames = sizeof(cpx) * (size_t)ch * (size_t)cap * (size_t)pts0;
-      if (int e = ensure_workspaces({{&p->bX, frames}, {&p->bY, frames}, {&p->btail, sizeof(float) * (size_t)ch * (size_t)pts0}}, s))
-        return e;
-      p->hcap = cap;
-    }
-  }
+  if (int e = nup_ensure_head(p, rest, s)) return e;
   HIP_TRY(p->order.use(s));
   const float *x = (const float *)in;
   float *o = (float *)out;
@@ -1335,6 +1455,40 @@ int clfa_nupconv_process_dev(clfa_nupconv *p, void *out, long out_stride, const 
 int clfa_nupconv_convolution(clfa_nupconv *p, float *out, const float *in, long nblocks) {
   return blocks_host(p, out, in, nullptr, nblocks, [&](void *o, long len, const void *i1, const void *) {
     return clfa_nupconv_process_dev(p, o, len, i1, len, nblocks, p->stream);
+  });
+}
+
+long clfa_nupconv_tv_period(const clfa_nupconv *p) { return p && !p->err ? (long)(p->lv[1].g.nparts + 2) * p->m : 0; }
+
+int clfa_nupconv_process_tv_dev(clfa_nupconv *p, void *out, long out_stride, const void *in, long in_stride, const void *in2,
+                                long in2_stride, long nblocks, void *stream) {
+  if (!in2) return clfa_nupconv_process_dev(p, out, out_stride, in, in_stride, nblocks, stream);
+  if (int e = obj_error(p)) return e;
+  const long pts0 = p->pts0, ch = p->channels;
+  long len;
+  if (int e = check_blocks_dev(nblocks, pts0, out, out_stride, ch, in, nullptr, in_stride, ch, &len)) return e;
+  if (!len) return CLFA_SUCCESS;
+  // the second input's rows: their own stride, and no byte shared with an output row (the inputs may share theirs)
+  if (!device_rows_ok(in2) || in2_stride < len) return CLFA_INVALID_VALUE;
+  const long sf = (long)sizeof(float);
+  if (rows_overlap(out, out_stride * sf, ch, in2, in2_stride * sf, ch, len * sf)) return CLFA_INVALID_VALUE;
+  if (p->fade_len) return CLFA_INVALID_OPERATION;   // a fade is pending: which set would the blocks rewrite
+  ENTER_DEVICE(p->di.device);
+  hipStream_t s = (hipStream_t)stream;
+  if (StreamOrder::capturing(s)) return CLFA_INVALID_OPERATION;   // (as process_dev)
+  const bool first = !p->stage2.p;
+  if (int e = p->stage2.ensure(p->stage.bytes)) return e;
+  // the longest stretch that takes the blocks route: the n0 head-rewriting blocks of a response period, or the others
+  const long n0 = p->lv[0].g.nparts, stat = clfa_nupconv_tv_period(p) - n0, longest = stat > n0 ? stat : n0;
+  if (int e = nup_ensure_head(p, nblocks < longest ? nblocks : longest, s, true)) return e;
+  HIP_TRY(p->order.use(s));
+  if (first) HIP_TRY(hipMemsetAsync(p->stage2.p, 0, p->stage2.bytes, s));
+  return nup_tv_blocks(p, (float *)out, out_stride, (const float *)in, in_stride, (const float *)in2, in2_stride, nblocks, s);
+}
+
+int clfa_nupconv_convolution_tv(clfa_nupconv *p, float *out, const float *in, const float *in2, long nblocks) {
+  return blocks_host(p, out, in, in2, nblocks, [&](void *o, long len, const void *i1, const void *i2) {
+    return clfa_nupconv_process_tv_dev(p, o, len, i1, len, i2, len, nblocks, p->stream);
   });
 }
 
@@ -1351,6 +1505,9 @@ int clfa_nupconv_reset(clfa_nupconv *p, void *stream) {
     l.w = 0;
   }
   HIP_TRY(hipMemsetAsync(p->stage.p, 0, p->stage.bytes, s));
+  // the second input's block in progress and how much of it is there
+  if (p->stage2.p) HIP_TRY(hipMemsetAsync(p->stage2.p, 0, p->stage2.bytes, s));
+  p->tv_count = 0;
   HIP_TRY(p->first().clear_history(s));
   p->c = 0;
   return CLFA_SUCCESS;

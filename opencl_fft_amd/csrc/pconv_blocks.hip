@@ -21,10 +21,6 @@ namespace clfa {
 
 namespace {
 
-__device__ __forceinline__ cpx ld_pair(const float *p, bool aligned) {
-  if (aligned) return *reinterpret_cast<const cpx *>(p);
-  return mk(p[0], p[1]);
-}
 __device__ __forceinline__ void st_pair(float *p, cpx v, bool aligned) {
   if (aligned) {
     *reinterpret_cast<cpx *>(p) = v;
@@ -45,7 +41,7 @@ __global__ __launch_bounds__(LdsGeom<LOGB>::WG) void k_pconvb_fwd(const float *_
                                                                  int K, int cap, int channels, int aligned,
                                                                  const cpx *__restrict__ tab_g, const cpx *__restrict__ w2_g) {
   using G = LdsGeom<LOGB>;
-  constexpr int N = G::N, E = G::E, T = G::T, WG = G::WG, FPW = G::FPW;
+  constexpr int N = G::N, T = G::T, WG = G::WG, FPW = G::FPW;
   if (blockIdx.y == 1) {
     in = in_b;
     X = XB;
@@ -64,33 +60,7 @@ __global__ __launch_bounds__(LdsGeom<LOGB>::WG) void k_pconvb_fwd(const float *_
     const bool active = r < rows;
     const int ch = active ? (int)(r / K) : 0, j = active ? (int)(r % K) : 0;
     const float *src = in + (long)ch * in_stride + (long)j * N;
-    cpx v[E];
-#pragma unroll
-    for (int e = 0; e < E; e++) {
-      const int p = t + T * e;
-      v[e] = (active && p < N / 2) ? ld_pair(src + 2 * p, aligned) : mk(0.f, 0.f);
-    }
-    wg_passes<LOGB, G::LOGE, 0, true>(v, t, s_tab, xb);
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < E; e++) xb[lds_pad(t + T * e)] = v[e];
-    __syncthreads();
-    if (active) {
-      cpx *x = X + ((long)ch * cap + j) * N;
-      for (int i = t; i < N / 2; i += T) {
-        if (i == 0) {
-          cpx z = xb[0];
-          x[0] = mk((z.x + z.y) * .5f, (z.x - z.y) * .5f);
-          x[N / 2] = xb[lds_pad(N / 2)];
-        } else {
-          cpx oi, oj;
-          r2c_pair(xb[lds_pad(i)], xb[lds_pad(N - i)], w2_g[i], oi, oj);
-          x[i] = oi;
-          x[N - i] = oj;
-        }
-      }
-    }
-    __syncthreads();   // xb is rewritten by the next row of this slot
+    fwd_row<LOGB>(src, aligned, active, X + ((long)ch * cap + j) * N, t, s_tab, xb, w2_g, [](int, cpx) {});
   }
 }
 
@@ -301,7 +271,14 @@ template <int LOGB>
 static hipError_t launch_blocks_one(const PconvBlocks &a, hipStream_t s) {
   const PconvGeom &g = a.g;
   {
-    hipError_t e = fwd_one<LOGB>(a.in1, a.in2, a.in_stride, a.X, a.XB, a.K, a.cap, g.channels, a.aligned_in, a.half, a.w2f, s);
+    // a second input with rows of its own (another stride or alignment) takes a launch of its own
+    const long stride2 = a.in2_stride ? a.in2_stride : a.in_stride;
+    const int aligned2 = a.aligned_in2 < 0 ? a.aligned_in : a.aligned_in2;
+    const bool own = a.in2 && (stride2 != a.in_stride || aligned2 != a.aligned_in);
+    hipError_t e = fwd_one<LOGB>(a.in1, own ? nullptr : a.in2, a.in_stride, a.X, a.XB, a.K, a.cap, g.channels, a.aligned_in, a.half,
+                                 a.w2f, s);
+    if (e == hipSuccess && own)
+      e = fwd_one<LOGB>(a.in2, nullptr, stride2, a.XB, nullptr, a.K, a.cap, g.channels, aligned2, a.half, a.w2f, s);
     if (e != hipSuccess) return e;
   }
   {

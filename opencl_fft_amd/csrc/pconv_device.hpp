@@ -1,11 +1,11 @@
 // pconv_device.hpp — device building blocks of the partitioned-convolution kernels (pconv_chain.hip, pconv_fused.inc,
-// pconv_coop.hip, pconv_blocks.hip, pconv_matrix.hip), each defined once, and the launch plumbing their launchers share.
+// pconv_coop.hip, pconv_blocks.hip, pconv_matrix.hip, pconv_nup.hip), each defined once, and the launch plumbing their launchers share.
 // The rules they carry exist once in the reference too: bin 0 of a packed frame holds DC and Nyquist and is multiplied component-wise; partial sums are added
 // in a fixed ascending order; loads are clamped rather than predicated.
 // Rule for a change here: compile these files before and after and compare them with tools/check_isa.py --same; a
 // helper is used only where the kernel keeps its instructions.  Sites that carry the bin-0 rule in their own words because
 // they did not: the c2r unpack, MAC term and overlap-add of k_pconv_fused and k_pconv_coop, the branch-form r2c pack of
-// k_pconv_fwd / k_pconvb_fwd, and the tail loop of k_pconv_mac.  The same holds for the pass chains of k_pconv_fused and
+// k_pconv_fwd and fwd_row (k_pconvb_fwd, k_nupc_fwd), and the tail loop of k_pconv_mac.  The same holds for the pass chains of k_pconv_fused and
 // k_pconv_coop: each spells its forward and its inverse chain out (compute, barrier, scatter, barrier, gather, predicated on
 // tid < T / work), because a recursive helper in the manner of wg_passes changed the instructions of all 32 instantiations.
 #pragma once
@@ -49,6 +49,53 @@ __device__ __forceinline__ void r2c_pack_pair(cpx ci, cpx cj, cpx w, bool pair0,
     oi = mk((ci.x + ci.y) * .5f, (ci.x - ci.y) * .5f);
     oj = cj;
   }
+}
+
+// ---- one row of N real samples -> its packed spectrum frame (k_pconvb_fwd, k_nupc_fwd) -------------------------------
+// (check_isa.py --same on k_pconvb_fwd with this helper: LOGB 6 and 8 keep their instructions; the other six keep their
+// descriptors and the counts of every floating-point, LDS-read and global-memory instruction, and differ in the order and
+// the registers of the integer address arithmetic — one v_mad_u32_u24 more or fewer, and at LOGB 7 one ds_write2_b64 as
+// two ds_write_b64.  The table must stay an array reference and x a restrict pointer; with the frame computed by a
+// functor hipcc emits a much shorter, different kernel.)
+__device__ __forceinline__ cpx ld_pair(const float *p, bool aligned) {
+  if (aligned) return *reinterpret_cast<const cpx *>(p);
+  return mk(p[0], p[1]);
+}
+// One transform slot of a workgroup (lane t of its T, the slot's LDS row xb, the tables s_tab / w2_g): the samples at src,
+// zero-padded to 2N, forward transform, r2c pack into x[0 .. N).  active: the slot has a row (the barriers are the whole
+// workgroup's; the last one frees xb for the slot's next row).  keep(p, pair): sees pair p < N / 2 of the row as loaded
+template <int LOGB, class Tab, class Keep>
+__device__ __forceinline__ void fwd_row(const float *src, int aligned, bool active, cpx *__restrict__ x, int t, const Tab &s_tab,
+                                        cpx *xb, const cpx *__restrict__ w2_g, Keep keep) {
+  using G = LdsGeom<LOGB>;
+  constexpr int N = G::N, E = G::E, T = G::T;
+  cpx v[E];
+#pragma unroll
+  for (int e = 0; e < E; e++) {
+    const int p = t + T * e;
+    v[e] = (active && p < N / 2) ? ld_pair(src + 2 * p, aligned) : mk(0.f, 0.f);
+    if (active && p < N / 2) keep(p, v[e]);
+  }
+  wg_passes<LOGB, G::LOGE, 0, true>(v, t, s_tab, xb);
+  __syncthreads();
+#pragma unroll
+  for (int e = 0; e < E; e++) xb[lds_pad(t + T * e)] = v[e];
+  __syncthreads();
+  if (active) {
+    for (int i = t; i < N / 2; i += T) {
+      if (i == 0) {
+        cpx z = xb[0];
+        x[0] = mk((z.x + z.y) * .5f, (z.x - z.y) * .5f);
+        x[N / 2] = xb[lds_pad(N / 2)];
+      } else {
+        cpx oi, oj;
+        r2c_pair(xb[lds_pad(i)], xb[lds_pad(N - i)], w2_g[i], oi, oj);
+        x[i] = oi;
+        x[N - i] = oj;
+      }
+    }
+  }
+  __syncthreads();
 }
 
 // ---- packed spectrum -> transform input in natural order (reference c2r, cl_conv_kernels.h:87-100) ------------------

@@ -64,6 +64,8 @@ struct PconvBlocks {
   long in_stride = 0, out_stride = 0;
   float *out = nullptr;
   int aligned_in = 1, aligned_out = 1;   // every row start 8-byte aligned
+  long in2_stride = 0;                   // rows of in2 that lie otherwise than in1's (0 / -1: as in1's): then in2 is
+  int aligned_in2 = -1;                  // transformed by a forward launch of its own
   cpx *ringA = nullptr, *ringB = nullptr;
   float *tail = nullptr;
   cpx *X = nullptr, *XB = nullptr, *Y = nullptr;
@@ -123,6 +125,23 @@ hipError_t launch_pconv_matrix_prime(const PconvMatrixArgs &a, hipStream_t s);
 // point at the first of them (row c at c * stride floats, any 4-byte aligned address and stride).
 hipError_t launch_nupc_stage(const float *in, long in_stride, float *stage, int pts1, int off, int n, int channels,
                              hipStream_t s);
+// ... and two sets of rows (x and a time-varying second input) in one launch, each into its own stage row
+hipError_t launch_nupc_stage2(const float *in, long in_stride, float *stage, const float *in_b, long in_b_stride, float *stage_b,
+                              int pts1, int off, int n, int channels, hipStream_t s);
+// The forward transforms of one level (bins = 1 << logb) for a time-varying block, one or two jobs in one launch: row ch of
+// the job (bins floats at src + ch * stride, any 4-byte aligned address; aligned: every row start 8-byte aligned) ->
+// the packed spectrum at frame + ch * frames * bins, with launch_pconvb_forward's bits.  copy (8-byte aligned, or NULL):
+// the row's samples are stored at copy + ch * copy_stride as they are loaded.  frame == NULL: the job only copies.
+struct NupcFwdJob {
+  const float *src = nullptr;
+  long stride = 0;
+  int aligned = 0;
+  cpx *frame = nullptr;
+  int frames = 0;
+  float *copy = nullptr;
+  long copy_stride = 0;
+};
+hipError_t launch_nupc_fwd(int logb, const NupcFwdJob *jobs, int njobs, int channels, const cpx *half, const cpx *w2f, hipStream_t s);
 // out = out + pend[off .. off + n): out holds the head's samples
 hipError_t launch_nupc_mix(float *out, long out_stride, const float *pend, int pts1, int off, int n, int channels,
                            hipStream_t s);

@@ -2,13 +2,17 @@
 // partitions (pts0) gives the latency; the long tail runs in large partitions (pts1 = m * pts0), and each tail block's
 // multiply-accumulate is spread in m slices of its bins over the m head blocks that pass while its output is not yet needed.
 //   k_nupc_stage   the call's input rows -> the tail's input row (channels x pts1 floats) at the stream's position
+//   k_nupc_stage2  the same for two sets of rows in one launch: x and the time-varying second input
+//   k_nupc_fwd     a time-varying block's forward transforms of one level, two jobs in one launch (x and the second
+//                  input, each with its own rows and destination frame); a job may also file its samples in a stage row
 //   k_nupc_mac     Y = sum_p A[(w - (nparts - 1) + p) mod nparts] (.) B[p] of ONE block of a level over a range of its
 //                  16-byte items: one accumulator per bin over p = 0, 1, ... nparts - 1 with mac_term, the order and the
 //                  products of k_pconvb_mac — the bits of Clpconv's blocks route, however the bins are cut into slices.
 //                  A single-block call runs the head's block and the tail's slice in one launch of it
 //   k_nupc_mix     out = head + pending tail output at the stream's position, one float32 addition, the head first
 //   k_nupc_fade_mix  a block of a timed crossfade (clfft_amd.h): both paths' head + pending sums, then a + g * (b - a)
-// The forward and inverse transforms are launch_pconvb_forward / launch_pconvb_inverse with K = 1; calls of several blocks
+// The forward and inverse transforms are launch_pconvb_forward / launch_pconvb_inverse with K = 1 (a time-varying block's
+// forward transforms: k_nupc_fwd, the same row transform); calls of several blocks
 // run the head through launch_pconv_blocks.  A new block's spectrum goes straight into ring frame w, the one frame the
 // multiply-accumulate of the block before it does not read; committing it is the host's w + 1.
 #include "pconv_device.hpp"
@@ -39,6 +43,71 @@ __global__ __launch_bounds__(256) void k_nupc_stage(const float *__restrict__ in
   for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
     const int ch = (int)(i / nu), k = (int)(i % nu) * V;
     *reinterpret_cast<U *>(stage + (long)ch * pts1 + off + k) = *reinterpret_cast<const U *>(in + (long)ch * in_stride + k);
+  }
+}
+
+// ... two sets of rows in one launch: blockIdx.y = 1 copies in_b -> stage_b
+template <int V>
+__global__ __launch_bounds__(256) void k_nupc_stage2(const float *__restrict__ in, long in_stride, float *__restrict__ stage,
+                                                     const float *__restrict__ in_b, long in_b_stride, float *__restrict__ stage_b,
+                                                     int pts1, int off, int n, int channels) {
+  typedef typename RowUnit<V>::type U;
+  if (blockIdx.y == 1) {
+    in = in_b;
+    in_stride = in_b_stride;
+    stage = stage_b;
+  }
+  const int nu = n / V;
+  const long total = (long)channels * nu;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const int ch = (int)(i / nu), k = (int)(i % nu) * V;
+    *reinterpret_cast<U *>(stage + (long)ch * pts1 + off + k) = *reinterpret_cast<const U *>(in + (long)ch * in_stride + k);
+  }
+}
+
+// ---------------------------------------------------------------------------------
+// forward transforms of one level for a time-varying block: blockIdx.y picks the job, one row per channel.  The row's
+// transform is k_pconvb_fwd's (fwd_row): the bits of launch_pconvb_forward.  A job with a copy destination stores the
+// pairs it loads there (the stage launch folded in); one without a frame only copies.
+// ---------------------------------------------------------------------------------
+template <int LOGB>
+__global__ __launch_bounds__(LdsGeom<LOGB>::WG) void k_nupc_fwd(NupcFwdJob j0, NupcFwdJob j1, int channels,
+                                                               const cpx *__restrict__ tab_g, const cpx *__restrict__ w2_g) {
+  using G = LdsGeom<LOGB>;
+  constexpr int N = G::N, T = G::T, WG = G::WG, FPW = G::FPW;
+  const NupcFwdJob &job = blockIdx.y ? j1 : j0;
+  const float *src0 = job.src;
+  const long stride = job.stride, copy_stride = job.copy_stride;
+  const int aligned = job.aligned;
+  cpx *frame = job.frame;
+  float *copy = job.copy;
+  const long fstride = (long)job.frames * N;
+  const int tid = threadIdx.x;
+  if (!frame) {   // (the whole launch row of workgroups: no barrier is skipped by a part of one)
+    if (copy) {
+      const long total = (long)channels * (N / 2);
+      for (long i = (long)blockIdx.x * WG + tid; i < total; i += (long)gridDim.x * WG) {
+        const int ch = (int)(i / (N / 2)), p = (int)(i % (N / 2));
+        *reinterpret_cast<cpx *>(copy + ch * copy_stride + 2 * p) = ld_pair(src0 + ch * stride + 2 * p, aligned);
+      }
+    }
+    return;
+  }
+  __shared__ cpx s_tab[G::HALF];
+  __shared__ cpx s_x[FPW * G::PADN];
+  const int f = tid / T, t = tid % T;
+  for (int i = tid; i < N / 2; i += WG) s_tab[i] = tab_g[i];
+  __syncthreads();
+  cpx *xb = s_x + f * G::PADN;
+  const long groups = ((long)channels + FPW - 1) / FPW;
+  for (long g = blockIdx.x; g < groups; g += gridDim.x) {
+    const long r = g * FPW + f;
+    const bool active = r < channels;
+    const long ch = active ? r : 0;
+    float *cp = copy ? copy + ch * copy_stride : nullptr;
+    fwd_row<LOGB>(src0 + ch * stride, aligned, active, frame + ch * fstride, t, s_tab, xb, w2_g, [&](int p, cpx v) {
+      if (cp) *reinterpret_cast<cpx *>(cp + 2 * p) = v;
+    });
   }
 }
 
@@ -167,6 +236,33 @@ hipError_t launch_nupc_stage(const float *in, long in_stride, float *stage, int 
   if (v4) hipLaunchKernelGGL(k_nupc_stage<4>, dim3(grid), dim3(256), 0, s, in, in_stride, stage, pts1, off, n, channels);
   else hipLaunchKernelGGL(k_nupc_stage<1>, dim3(grid), dim3(256), 0, s, in, in_stride, stage, pts1, off, n, channels);
   return hipGetLastError();
+}
+
+hipError_t launch_nupc_stage2(const float *in, long in_stride, float *stage, const float *in_b, long in_b_stride, float *stage_b,
+                              int pts1, int off, int n, int channels, hipStream_t s) {
+  if (n < 1 || (n & 31) || (off & 31) || off + n > pts1) return hipErrorInvalidValue;
+  const bool v4 = rows_16(in, in_stride) && rows_16(in_b, in_b_stride);
+  const int grid = grid_clamp(((long)channels * (n / (v4 ? 4 : 1)) + 255) / 256, 4096);
+  if (v4)
+    hipLaunchKernelGGL(k_nupc_stage2<4>, dim3(grid, 2), dim3(256), 0, s, in, in_stride, stage, in_b, in_b_stride, stage_b, pts1, off, n, channels);
+  else
+    hipLaunchKernelGGL(k_nupc_stage2<1>, dim3(grid, 2), dim3(256), 0, s, in, in_stride, stage, in_b, in_b_stride, stage_b, pts1, off, n, channels);
+  return hipGetLastError();
+}
+
+hipError_t launch_nupc_fwd(int logb, const NupcFwdJob *jobs, int njobs, int channels, const cpx *half, const cpx *w2f, hipStream_t s) {
+  if (njobs < 1 || njobs > 2 || channels < 1) return hipErrorInvalidValue;
+  for (int i = 0; i < njobs; i++) {
+    const NupcFwdJob &j = jobs[i];
+    if (!j.src || (!j.frame && !j.copy) || (j.frame && j.frames < 1) || ((uintptr_t)j.copy & 7) || (j.copy_stride & 1))
+      return hipErrorInvalidValue;
+  }
+  return dispatch_logb<kPconvBlocksMinLog, kPconvBlocksMaxLog>(logb, [&](auto L) {
+    using G = LdsGeom<decltype(L)::value>;
+    const int grid = grid_clamp(((long)channels + G::FPW - 1) / G::FPW, 8192);
+    hipLaunchKernelGGL((k_nupc_fwd<decltype(L)::value>), dim3(grid, njobs), dim3(G::WG), 0, s, jobs[0], jobs[njobs - 1], channels, half, w2f);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_nupc_mix(float *out, long out_stride, const float *pend, int pts1, int off, int n, int channels,

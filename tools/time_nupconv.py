@@ -18,6 +18,16 @@ composition it replaces: two Nupconv objects fed alike and the three torch opera
 itself (the response transforms and the priming of the second path) beside a plain push.
 
     python tools/time_nupconv.py --fade [--parent-lib old/libclfft_amd.so] [--out profiles/nupconv_fade.txt]
+
+--tv: the time-varying second input (process_tv_device), one line per shape.  Single-block calls in two alternating legs
+of --periods periods each (at least 4), every time-varying leg begun at the start of a response period, so that its first
+two periods are the blocks that rewrite a head partition (a < 2m) and the rest those that do not: median and worst phase
+of each kind.  Each is held against the same object's plain block (the cost of the second input) and against the only
+other way to a time-varying response at this latency, Clpconv(cvs, pts0).process_device(out, x, w), in the same process.
+A whole-signal call of 1024 head blocks from the start of a response period is held against
+Clpconv.process_blocks_device with two inputs.
+
+    python tools/time_nupconv.py --tv [--out profiles/nupconv_tv.txt]
 """
 import argparse
 import ctypes as C
@@ -109,6 +119,90 @@ def shape(cvs, pts0, pts1, channels, periods):
     r["signal_us_per_block"] = round(float(np.median(t)) * 1e3 / K, 3)
     r["signal_boundaries"] = K // m
     del nup
+    torch.cuda.synchronize()
+    return r
+
+
+def tv_shape(cvs, pts0, pts1, channels, periods):
+    m = pts1 // pts0
+    n = periods * m
+    s = torch.cuda.current_stream().cuda_stream
+    h = torch.rand((channels, cvs), device="cuda") - 0.5
+    x = torch.rand((channels, pts0), device="cuda") - 0.5
+    w = torch.rand((channels, pts0), device="cuda") - 0.5
+    out = torch.empty_like(x)
+    K = 1024
+    xs = torch.rand((channels, K * pts0), device="cuda") - 0.5
+    ws = torch.rand((channels, K * pts0), device="cuda") - 0.5
+    os_ = torch.empty_like(xs)
+    nup = fa.Nupconv(0, cvs, pts0, pts1, channels=channels)
+    assert nup.get_error() == 0, nup.get_log()
+    assert nup.push_ir_device(h, s) == 0
+    base = fa.Clpconv(0, cvs, pts0, channels=channels)
+    assert base.get_cl_err() == 0 and base.push_ir_device(h, s) == 0
+    del h
+    R0 = nup.tv_period
+    assert R0 % m == 0 and n > 2 * m
+
+    def to_period_start():
+        """plain calls of many blocks up to the next multiple of R0"""
+        left = (-nup.position) % R0
+        while left:
+            k = min(left, K)
+            assert nup.process_device(os_[:, :k * pts0], xs[:, :k * pts0], s) == 0
+            left -= k
+
+    def run_tv():
+        assert nup.process_tv_device(out, x, w, s) == 0
+
+    def run_plain():
+        assert nup.process_device(out, x, s) == 0
+
+    def run_base():
+        assert base.process_device(out, x, w, s) == 0
+
+    for f in (run_plain, run_tv, run_base):
+        calls(f, 2 * m)
+    tv, plain, tb = [], [], []
+    for _ in range(2):
+        to_period_start()
+        tv.append(calls(run_tv, n).reshape(periods, m))
+        assert nup.position % m == 0
+        plain.append(calls(run_plain, n).reshape(periods, m))
+        tb.append(calls(run_base, n).reshape(periods, m))
+    rewrite = np.concatenate([t[:2] for t in tv]) * 1e3        # a < 2m: the first two periods of a response period
+    static = np.concatenate([t[2:] for t in tv]) * 1e3
+    plain, tb = np.concatenate(plain) * 1e3, np.concatenate(tb) * 1e3
+
+    def stats(t):
+        by_phase = np.median(t, axis=0)
+        return {"median": round(float(np.median(t)), 2), "worst_phase": round(float(by_phase.max()), 2),
+                "worst_phase_index": int(by_phase.argmax()), "max_single_call": round(float(t.max()), 2)}
+
+    r = {"cvs": cvs, "pts0": pts0, "pts1": pts1, "channels": channels, "periods": periods, "tv_period_blocks": R0,
+         "tv_rewrite_us": stats(rewrite), "tv_static_us": stats(static), "plain_us": stats(plain),
+         "clpconv_tv_us": {"median": round(float(np.median(tb)), 2), "max_single_call": round(float(tb.max()), 2)},
+         "clpconv_kernel": base.kernel_name()}
+    worst = max(r["tv_rewrite_us"]["worst_phase"], r["tv_static_us"]["worst_phase"])
+    r["tv_worst_phase_over_plain_worst_phase"] = round(worst / r["plain_us"]["worst_phase"], 3)
+    r["tv_worst_phase_over_clpconv_tv_median"] = round(worst / r["clpconv_tv_us"]["median"], 3)
+    # a whole signal of 1024 head blocks from the start of a response period, against Clpconv's blocks route with two inputs
+    def run_signal():
+        to_period_start()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        assert nup.process_tv_device(os_, xs, ws, s) == 0
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b)
+
+    t = [run_signal() for _ in range(4)][1:]
+    tbs = calls(lambda: base.process_blocks_device(os_, xs, ws, s), 4)[1:]
+    r["signal_1024_blocks_ms"] = {"nup_tv": round(float(np.median(t)), 3), "clpconv_tv_blocks": round(float(np.median(tbs)), 3)}
+    r["signal_nup_over_clpconv"] = round(float(np.median(t) / np.median(tbs)), 3)
+    r["clpconv_blocks_kernel"] = base.blocks_kernel_name()
+    r["state_mib"] = {"nup": round(nup.state_bytes() / 2 ** 20, 1), "clpconv": round(base.state_bytes() / 2 ** 20, 1)}
+    del nup, base
     torch.cuda.synchronize()
     return r
 
@@ -244,11 +338,13 @@ def main():
     ap.add_argument("--quick", action="store_true", help="the one- and 16-channel shapes only")
     ap.add_argument("--out", default=None)
     ap.add_argument("--fade", action="store_true", help="the timed crossfade: plain path A/B, fade block, fade push")
+    ap.add_argument("--tv", action="store_true", help="the time-varying second input against the plain block and Clpconv")
     ap.add_argument("--parent-lib", default=None, help="--fade: another build of libclfft_amd.so to hold the plain path against")
     a = ap.parse_args()
     assert a.periods >= 3, "at least three periods"
     assert torch.cuda.is_available(), "needs a GPU"
-    lines = [json.dumps({"device": fa.device_name(0), "how": __doc__.split("\n\n")[2 if a.fade else 0].replace("\n", " ")})]
+    assert not a.tv or a.periods >= 4, "--tv: at least four periods (two of each kind of block)"
+    lines = [json.dumps({"device": fa.device_name(0), "how": __doc__.split("\n\n")[4 if a.tv else 2 if a.fade else 0].replace("\n", " ")})]
     probe = {k: round(v, 3) for k, v in fa.bandwidth_probe(0, 1 << 30, 100).items()}
     lines.append(json.dumps({"bandwidth_probe_tb_s": probe}))
     print(lines[-1], flush=True)
@@ -256,7 +352,9 @@ def main():
     for pts0, pts1, channels in SHAPES:
         if a.quick and channels > 16:
             continue
-        if a.fade:
+        if a.tv:
+            lines.append(json.dumps(tv_shape(a.cvs, pts0, pts1, channels, a.periods)))
+        elif a.fade:
             lines.append(json.dumps(fade_shape(a.cvs, pts0, pts1, channels, a.periods, parent)))
         else:
             lines.append(json.dumps(shape(a.cvs, pts0, pts1, channels, a.periods)))
