@@ -77,9 +77,12 @@ PCONV_ROUTES = [
     ("launch chain, four-step", "chain", 32768, 3, 1, 1),
 ]
 # the multi-block call (process_blocks_device): blocks_kernel_name(), pts, nparts, channels, b0
-PCONV_BLOCK_ROUTES = [("loop", 8, 3, 3, 1), ("k_pconvb_mac", 64, 3, 3, 4), ("k_pconvb_mac", 1024, 94, 3, 1)]
+# k_pconvb_mac at every transform size of the route, 32 .. 4096 (one instantiation of the forward and inverse kernels each)
+PCONV_BLOCK_ROUTES = [("loop", 8, 3, 3, 1), ("k_pconvb_mac", 64, 3, 3, 4), ("k_pconvb_mac", 1024, 94, 3, 1),
+                      ("k_pconvb_mac", 32, 5, 3, 6), ("k_pconvb_mac", 128, 3, 3, 4), ("k_pconvb_mac", 256, 5, 1, 1),
+                      ("k_pconvb_mac", 512, 3, 3, 2), ("k_pconvb_mac", 2048, 5, 3, 6), ("k_pconvb_mac", 4096, 3, 3, 1)]
 # the convolution matrix: inputs, outputs, pts, nparts
-MATRIX_GEOMS = [(3, 5, 256, 12), (4, 4, 64, 3)]
+MATRIX_GEOMS = [(3, 5, 256, 12), (4, 4, 64, 3), (2, 3, 128, 5), (3, 2, 2048, 3)]
 
 
 def nblocks_for(nparts, b0):

@@ -46,7 +46,25 @@ def test_oracle_within_the_bar_and_exactly_zero_elsewhere(pts, nparts, channels,
     print("CONV-IMPULSE oracle %dx%d %s b0=%d worst-bin %.3g worst-sample %.3g" % (pts, nparts, "tv" if tv else "static", b0, wb, ws))
 
 
-@pytest.mark.parametrize("pts,nparts,b0", [(8, 4, 1), (8, 4, 5), (64, 3, 4), (2, 1, 2), (256, 5, 2), (32, 5, 6)])
+def test_the_multi_block_table_holds_every_transform_size_of_the_route():
+    """k_pconvb_mac's forward and inverse kernels are one instantiation per size, 32 .. 4096: each has a row, the new ones
+    with 3 or 5 partitions, and the impulse does not always come in block 1"""
+    rows = [r for r in cx.PCONV_BLOCK_ROUTES if r[0] == "k_pconvb_mac"]
+    assert sorted(r[1] for r in rows) == [32, 64, 128, 256, 512, 1024, 2048, 4096]
+    assert ("k_pconvb_mac", 64, 3, 3, 4) in rows and ("k_pconvb_mac", 1024, 94, 3, 1) in rows
+    new = [r for r in rows if r[1] not in (64, 1024)]
+    assert all(r[2] in (3, 5) and r[3] in (1, 3) for r in new) and sum(r[3] == 1 for r in new) == 1
+    assert sum(r[4] != 1 for r in new) >= 2
+    assert {g[2] for g in cx.MATRIX_GEOMS} >= {128, 2048}
+    # every row is one of the oracle's cases below, as it stands
+    assert {r[1:] for r in cx.PCONV_BLOCK_ROUTES} <= set(ORACLE_GEOMS)
+
+
+BLOCK_ROUTE_COMBS = sorted({(pts, nparts, b0) for _, pts, nparts, _, b0 in cx.PCONV_BLOCK_ROUTES if nparts <= 5})
+
+
+@pytest.mark.parametrize("pts,nparts,b0", [(8, 4, 1), (8, 4, 5), (64, 3, 4), (2, 1, 2), (256, 5, 2), (32, 5, 6)]
+                         + [g for g in BLOCK_ROUTE_COMBS if g not in ((64, 3, 4), (32, 5, 6))])
 def test_comb_isolates_partitions_in_the_models(pts, nparts, b0):
     """float64 models, static and time-varying: the pair of partition p in a comb run is the pair of a run with partition p
     alone and is pair_truth (any b0, any p), and everything outside the pairs is exactly zero"""

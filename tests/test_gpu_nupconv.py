@@ -16,6 +16,13 @@ pytestmark = pytest.mark.gpu
 
 CL_INVALID_VALUE, CL_INVALID_OPERATION = -30, -59
 GEOMS = [(32, 64, 1), (32, 256, 3), (64, 4096, 2)]   # pts0, pts1, n1
+# m = 2 at every transform size of the blocks route: with (32, 64, 1) above each size 32 .. 4096 is once the head's and once
+# the tail's (k_pconvb_fwd / k_pconvb_inv, one instantiation per size)
+SIZE_GEOMS = [(64, 128, 2), (128, 256, 3), (256, 512, 1), (512, 1024, 2), (1024, 2048, 3), (2048, 4096, 1)]
+# tails on both sides of k_nupc_mac's prefetch depth of 16 partitions: one short of a pass, a whole pass, one and two whole
+# passes and a partial one after them
+DEPTH_GEOMS = [(32, 64, 15), (32, 64, 16), (32, 64, 17), (32, 64, 33), (32, 256, 17)]
+ALL_GEOMS = GEOMS + SIZE_GEOMS + DEPTH_GEOMS
 
 
 def _cvs(pts1, n1):
@@ -24,10 +31,11 @@ def _cvs(pts1, n1):
 
 @functools.lru_cache(maxsize=None)
 def _signals(pts0, pts1, n1, channels):
-    """(h, x): responses of cvs samples and a signal of 4 m + 3 head blocks (four tail periods and a bit), read-only"""
+    """(h, x): responses of cvs samples and a signal of (n1 + 3) m + 3 head blocks (the tail's ring of n1 + 2 frames wraps),
+    read-only"""
     rng = np.random.default_rng(pts0 + pts1 + 10 * n1 + channels)
     h = rng.random((channels, _cvs(pts1, n1)), dtype=np.float32) - 0.5
-    x = rng.random((channels, (4 * (pts1 // pts0) + 3) * pts0), dtype=np.float32) - 0.5
+    x = rng.random((channels, ((n1 + 3) * (pts1 // pts0) + 3) * pts0), dtype=np.float32) - 0.5
     h.setflags(write=False)
     x.setflags(write=False)
     return h, x
@@ -107,12 +115,12 @@ def _run(p, x, splits):
 
 
 @pytest.mark.parametrize("channels", [1, 3])
-@pytest.mark.parametrize("pts0,pts1,n1", GEOMS)
+@pytest.mark.parametrize("pts0,pts1,n1", ALL_GEOMS)
 def test_bits_of_the_composition_however_the_stream_is_cut(pts0, pts1, n1, channels):
     h, x = _signals(pts0, pts1, n1, channels)
     want = _composition(pts0, pts1, n1, channels)
     m, nblocks = pts1 // pts0, x.shape[1] // pts0
-    assert nblocks >= 3 * m + 1
+    assert nblocks == (n1 + 3) * m + 3 and nblocks - m - 5 > 0
     for splits in ([nblocks], [1] * nblocks, [1, m + 2, 2, 0, nblocks - m - 5]):
         got = _run(_object(pts0, pts1, n1, channels, h), x, splits)
         gg.same(got, want, "pts0 %d pts1 %d n1 %d, %d channels, calls of %s blocks" % (pts0, pts1, n1, channels, splits[:5]))
@@ -130,7 +138,7 @@ def _head_only(pts0, pts1, n1, channels):
     return yh.cpu().numpy()
 
 
-@pytest.mark.parametrize("pts0,pts1,n1", GEOMS)
+@pytest.mark.parametrize("pts0,pts1,n1", ALL_GEOMS)
 def test_against_float64(pts0, pts1, n1):
     """the definition in float64 (tests/nupconv_model.definition over tests/util.pconv_f64) at the project's parity
     criterion, tests/util.TOL"""

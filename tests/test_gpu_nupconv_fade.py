@@ -17,6 +17,9 @@ from tests.test_gpu_nupconv import GEOMS, _cvs, _object, _run
 pytestmark = pytest.mark.gpu
 
 CL_INVALID_VALUE, CL_INVALID_OPERATION = -30, -59
+# the main fade test also at the head and tail sizes no other geometry has (128, 2048), and with tails past the prefetch
+# depth of k_nupc_mac, whose block is the four-job launch during a fade
+FADE_GEOMS = GEOMS + [(128, 256, 3), (1024, 2048, 3), (32, 64, 17), (32, 64, 33)]
 
 
 def _positions(m, n1):
@@ -131,7 +134,7 @@ TABLES = {
 
 
 @pytest.mark.parametrize("channels", [1, 3])
-@pytest.mark.parametrize("pts0,pts1,n1", GEOMS)
+@pytest.mark.parametrize("pts0,pts1,n1", FADE_GEOMS)
 def test_bits_of_the_definition(pts0, pts1, n1, channels):
     hA, hB, _, x = _signals(pts0, pts1, n1, channels)
     yA, yB = _plain(pts0, pts1, n1, channels, 0), _plain(pts0, pts1, n1, channels, 1)

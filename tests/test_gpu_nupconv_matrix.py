@@ -22,6 +22,9 @@ GEOMS = [(32, 64, 1, 2, 3),       # m = 2: the tail's forward and inverse in con
          (64, 4096, 2, 2, 2),     # the largest pts1, a head chain of 128 partitions x 2 inputs
          (32, 256, 3, 1, 4),      # one input
          (32, 256, 3, 4, 1)]      # one output
+# the transform sizes 128 and 2048, which no geometry above has, as head and as tail (this file's two parametrised tests;
+# tests/test_gpu_nupconv_matrix_fade.py keeps GEOMS)
+SIZE_GEOMS = [(128, 512, 2, 2, 2), (512, 2048, 1, 2, 3)]
 SEGMENTED = (32, 256, 11, 3, 2)
 
 
@@ -164,7 +167,7 @@ def _bits_however_cut(monkeypatch, geom, env):
     assert not np.array_equal(got[:, 2 * pts1:3 * pts1], _head_only(monkeypatch, geom, _segs(p))[:, 2 * pts1:3 * pts1])
 
 
-@pytest.mark.parametrize("geom", GEOMS)
+@pytest.mark.parametrize("geom", GEOMS + SIZE_GEOMS)
 def test_bits_of_the_composition_however_the_stream_is_cut(monkeypatch, geom):
     _bits_however_cut(monkeypatch, geom, None)
 
@@ -176,7 +179,7 @@ def test_bits_with_segments_that_cut_inside_an_input(monkeypatch):
     _bits_however_cut(monkeypatch, SEGMENTED, 5)
 
 
-@pytest.mark.parametrize("geom", GEOMS)
+@pytest.mark.parametrize("geom", GEOMS + SIZE_GEOMS)
 def test_against_float64(monkeypatch, geom):
     """each output against the sum over the inputs of the definition in float64 (tests/nupconv_model.definition over
     tests/util.pconv_f64) at the matrix's tolerance for a sum over inputs, util.TOL * inputs"""

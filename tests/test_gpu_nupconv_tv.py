@@ -13,11 +13,15 @@ from opencl_fft_amd._lib import lib
 from tests import gpu_guard as gg
 from tests import util
 from tests.nupconv_tv_model import Composition, NupTvModel
+from tests.test_gpu_nupconv import DEPTH_GEOMS, SIZE_GEOMS
 
 pytestmark = pytest.mark.gpu
 
 CL_INVALID_VALUE, CL_INVALID_OPERATION = -30, -59
 GEOMS = [(32, 64, 1), (32, 256, 3), (64, 4096, 2)]   # pts0, pts1, n1
+# k_nupc_fwd (the forward transform with the stage copy folded in) at every size on both levels, and tails on both sides of
+# k_nupc_mac's prefetch depth: the geometries of tests/test_gpu_nupconv.py
+ALL_GEOMS = GEOMS + SIZE_GEOMS + DEPTH_GEOMS
 
 
 def _cvs(pts1, n1):
@@ -46,7 +50,7 @@ def _signals(pts0, pts1, n1, channels):
 def _object(pts0, pts1, n1, channels, h=None):
     p = fa.Nupconv(0, _cvs(pts1, n1), pts0, pts1, channels=channels)
     assert p.get_error() == 0, p.get_log()
-    assert p.nparts(1) == n1 and p.tv_period == (n1 + 2) * (pts1 // pts0)
+    assert p.nparts(1) == n1 and p.kernel_name() == "k_nupc_mac" and p.tv_period == (n1 + 2) * (pts1 // pts0)
     if h is not None:
         assert p.push_ir(h) == 0
     return p
@@ -109,7 +113,7 @@ def _run(p, x, w, splits, plain=()):
 
 
 @pytest.mark.parametrize("channels", [1, 3])
-@pytest.mark.parametrize("pts0,pts1,n1", GEOMS)
+@pytest.mark.parametrize("pts0,pts1,n1", ALL_GEOMS)
 def test_bits_of_the_push_composition_however_the_stream_is_cut(pts0, pts1, n1, channels):
     h, x, w = _signals(pts0, pts1, n1, channels)
     want = _composition(pts0, pts1, n1, channels)
@@ -150,7 +154,7 @@ def test_static_equivalence_from_block_r0_plus_2m(pts0, pts1, n1, channels):
     assert not np.array_equal(got[:, :first], want[:, :first])
 
 
-@pytest.mark.parametrize("pts0,pts1,n1", GEOMS)
+@pytest.mark.parametrize("pts0,pts1,n1", ALL_GEOMS)
 def test_against_the_float64_model(pts0, pts1, n1):
     """tests/nupconv_tv_model.NupTvModel at the project's parity criterion, tests/util.TOL"""
     channels = 3

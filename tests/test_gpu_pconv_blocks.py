@@ -47,7 +47,8 @@ def _pair(pts, nparts, ch, rng):
 
 @pytest.mark.parametrize("tv", [False, True], ids=["static", "tv"])
 @pytest.mark.parametrize("nparts", [1, 3, 94])
-@pytest.mark.parametrize("pts,ch", [(8, 3), (32, 1), (64, 3), (512, 1), (1024, 3), (4096, 1), (8192, 1)])
+@pytest.mark.parametrize("pts,ch", [(8, 3), (32, 1), (64, 3), (128, 3), (256, 1), (512, 1), (1024, 3), (2048, 3), (4096, 1),
+                                    (8192, 1)])
 def test_blocks_equal_the_single_block_loop(pts, ch, nparts, tv):
     torch = _torch()
     rng = np.random.default_rng(pts * 1000 + nparts * 10 + tv)
