@@ -148,7 +148,30 @@ class Clpconv(_BlockConv):
         return self._text("blocks_kernel_name")
 
 
-class PconvMatrix(_Object):
+class _MatrixRows:
+    """responses of a matrix object as rows: (outputs, inputs, >= self._need()) float32"""
+
+    def _host_rows(self, ir):
+        """the packed rows of a host array of responses, None for a bad one"""
+        ir = np.asarray(ir, dtype=np.float32)
+        need = self._need()
+        if ir.ndim != 3 or ir.shape[:2] != (self.outputs, self.inputs) or ir.shape[2] < need:
+            return None
+        return np.ascontiguousarray(ir[:, :, :need])
+
+    def _device_rows(self, ir, stream):
+        """(row stride, stream) of a device tensor of responses, None for a bad one"""
+        need = self._need()
+        if (ir.dim() != 3 or tuple(ir.shape[:2]) != (self.outputs, self.inputs) or ir.shape[2] < need
+                or not _is_f32(ir) or ir.stride(2) != 1):
+            return None
+        rs = ir.stride(1) if self.inputs > 1 else (ir.stride(0) if self.outputs > 1 else max(ir.stride(1), need))
+        if self.outputs > 1 and ir.stride(0) != self.inputs * rs:
+            return None
+        return rs, _stream_of(ir, stream)
+
+
+class PconvMatrix(_MatrixRows, _Object):
     """Convolution matrix (extension, clfa_pconv_matrix in clfft_amd.h): `inputs` signals mixed into `outputs` signals,
     y_o = sum_i x_i * h_{o,i}, by uniformly partitioned overlap-add convolution with static responses.  Block j of output
     o is the sum over i of what Clpconv(device_id, cvs, pts) holding h_{o,i} returns for block j of input i.  pts is a
@@ -165,23 +188,8 @@ class PconvMatrix(_Object):
     def state_bytes(self):
         return self._get("state_bytes")
 
-    def _host_rows(self, ir):
-        ir = np.asarray(ir, dtype=np.float32)
-        need = self.nparts * self.pts
-        if ir.ndim != 3 or ir.shape[:2] != (self.outputs, self.inputs) or ir.shape[2] < need:
-            return None
-        return np.ascontiguousarray(ir[:, :, :need])
-
-    def _device_rows(self, ir, stream):
-        """(row stride, stream) of a device tensor of responses, None for a bad one"""
-        need = self.nparts * self.pts
-        if (ir.dim() != 3 or tuple(ir.shape[:2]) != (self.outputs, self.inputs) or ir.shape[2] < need
-                or not _is_f32(ir) or ir.stride(2) != 1):
-            return None
-        rs = ir.stride(1) if self.inputs > 1 else (ir.stride(0) if self.outputs > 1 else max(ir.stride(1), need))
-        if self.outputs > 1 and ir.stride(0) != self.inputs * rs:
-            return None
-        return rs, _stream_of(ir, stream)
+    def _need(self):
+        return self.nparts * self.pts
 
     def push_ir(self, ir):
         """ir: float32 (outputs, inputs, >= nparts*pts), e.g. rows of cvs samples (the remainder is ignored)"""
@@ -238,19 +246,8 @@ class PconvMatrix(_Object):
                                                    _stream_of(x, stream))
 
 
-class Nupconv(_Object):
-    """Non-uniformly partitioned convolution (extension, clfa_nupconv in clfft_amd.h): long responses at a latency of
-    pts0 samples.  A head of 2 * pts1 / pts0 partitions of pts0 covers h[:2*pts1]; the tail runs in partitions of pts1,
-    each tail block's work spread over the pts1 / pts0 small blocks that pass while it is not yet needed.  The output is,
-    bit for bit, Clpconv(2*pts1, pts0) on h[:2*pts1] plus Clpconv(cvs - 2*pts1, pts1) on h[2*pts1:] delayed by 2*pts1
-    samples, both through process_blocks_device — not the bits of Clpconv(cvs, pts0).  pts0 < pts1 are powers of two,
-    32..4096; cvs >= 3 * pts1.  Like the other objects the constructor does not raise: get_error() / get_log()."""
-    _abi = "clfa_nupconv_"
-
-    def __init__(self, device_id, cvs, pts0, pts1, channels=1):
-        self.cvs, self.pts0, self.pts1, self.channels = int(cvs), int(pts0), int(pts1), int(channels)
-        self._create(_pkg.lib().clfa_nupconv_create, int(device_id), self.cvs, self.pts0, self.pts1, self.channels)
-
+class _Nup(_Object):
+    """what Nupconv and NupconvMatrix share: two levels, a position, a pending crossfade, reset"""
     position = property(lambda s: s._get("position"))
 
     def nparts(self, level):
@@ -262,6 +259,32 @@ class Nupconv(_Object):
 
     def _need(self):
         return 2 * self.pts1 + self.nparts(1) * self.pts1
+
+    def fade_remaining(self):
+        """head blocks of a pending crossfade that have not been processed yet; 0: none"""
+        return self._get("fade_remaining")
+
+    def reset(self, stream=None):
+        """forget the input history (position 0); the responses stay.  `stream`: a HIP stream handle, default the
+        current torch stream of the object's device"""
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream().cuda_stream
+        return self._get("reset", stream)
+
+
+class Nupconv(_Nup):
+    """Non-uniformly partitioned convolution (extension, clfa_nupconv in clfft_amd.h): long responses at a latency of
+    pts0 samples.  A head of 2 * pts1 / pts0 partitions of pts0 covers h[:2*pts1]; the tail runs in partitions of pts1,
+    each tail block's work spread over the pts1 / pts0 small blocks that pass while it is not yet needed.  The output is,
+    bit for bit, Clpconv(2*pts1, pts0) on h[:2*pts1] plus Clpconv(cvs - 2*pts1, pts1) on h[2*pts1:] delayed by 2*pts1
+    samples, both through process_blocks_device — not the bits of Clpconv(cvs, pts0).  pts0 < pts1 are powers of two,
+    32..4096; cvs >= 3 * pts1.  Like the other objects the constructor does not raise: get_error() / get_log()."""
+    _abi = "clfa_nupconv_"
+
+    def __init__(self, device_id, cvs, pts0, pts1, channels=1):
+        self.cvs, self.pts0, self.pts1, self.channels = int(cvs), int(pts0), int(pts1), int(channels)
+        self._create(_pkg.lib().clfa_nupconv_create, int(device_id), self.cvs, self.pts0, self.pts1, self.channels)
 
     def _host_rows(self, ir):
         """the packed rows of a host array of responses, None for a bad one"""
@@ -306,10 +329,6 @@ class Nupconv(_Object):
         if length < self._need():
             return CL_INVALID_VALUE
         return _pkg.lib().clfa_nupconv_push_ir_fade_dev(self._h, ir.data_ptr(), stride, int(fade_blocks), _stream_of(ir, stream))
-
-    def fade_remaining(self):
-        """head blocks of a pending crossfade that have not been processed yet; 0: none"""
-        return self._get("fade_remaining")
 
     def convolution(self, output, input):
         """whole signals on the host: float32 (channels, L) -> (channels, L) (1-D for one channel), L a multiple of
@@ -357,16 +376,8 @@ class Nupconv(_Object):
         return _pkg.lib().clfa_nupconv_process_tv_dev(self._h, out.data_ptr(), so, x.data_ptr(), si, w.data_ptr(), sw,
                                                       li // self.pts0, _stream_of(x, stream))
 
-    def reset(self, stream=None):
-        """forget the input history (position 0); the responses stay.  `stream`: a HIP stream handle, default the
-        current torch stream of the object's device"""
-        if stream is None:
-            import torch
-            stream = torch.cuda.current_stream().cuda_stream
-        return self._get("reset", stream)
 
-
-class NupconvMatrix(_Object):
+class NupconvMatrix(_MatrixRows, _Nup):
     """Non-uniformly partitioned convolution matrix (extension, clfa_nupconv_matrix in clfft_amd.h): `inputs` signals mixed
     into `outputs` signals, y_o = sum_i x_i * h_{o,i}, with long static responses at a latency of pts0 samples — Nupconv's
     two levels and schedule around PconvMatrix's sum over inputs.  The output is, bit for bit, PconvMatrix(2*pts1, pts0)
@@ -381,40 +392,9 @@ class NupconvMatrix(_Object):
         self._create(_pkg.lib().clfa_nupconv_matrix_create, int(device_id), self.cvs, self.pts0, self.pts1, self.inputs,
                      self.outputs)
 
-    position = property(lambda s: s._get("position"))
-
-    def nparts(self, level):
-        """partitions of level 0 (the head) or 1 (the tail)"""
-        return self._get("nparts", int(level))
-
     def segments(self, level):
         """segments in which level 0 (the head) or 1 (the tail) sums over (input, partition)"""
         return self._get("segments", int(level))
-
-    def state_bytes(self):
-        return self._get("state_bytes")
-
-    def _need(self):
-        return 2 * self.pts1 + self.nparts(1) * self.pts1
-
-    def _host_rows(self, ir):
-        """the packed rows of a host array of responses, None for a bad one"""
-        ir = np.asarray(ir, dtype=np.float32)
-        need = self._need()
-        if ir.ndim != 3 or ir.shape[:2] != (self.outputs, self.inputs) or ir.shape[2] < need:
-            return None
-        return np.ascontiguousarray(ir[:, :, :need])
-
-    def _device_rows(self, ir, stream):
-        """(row stride, stream) of a device tensor of responses, None for a bad one"""
-        need = self._need()
-        if (ir.dim() != 3 or tuple(ir.shape[:2]) != (self.outputs, self.inputs) or ir.shape[2] < need
-                or not _is_f32(ir) or ir.stride(2) != 1):
-            return None
-        rs = ir.stride(1) if self.inputs > 1 else (ir.stride(0) if self.outputs > 1 else max(ir.stride(1), need))
-        if self.outputs > 1 and ir.stride(0) != self.inputs * rs:
-            return None
-        return rs, _stream_of(ir, stream)
 
     def push_ir(self, ir):
         """ir: float32 (outputs, inputs, >= 2*pts1 + nparts(1)*pts1), e.g. rows of cvs samples; blocking.  Exact at
@@ -454,10 +434,6 @@ class NupconvMatrix(_Object):
             return CL_INVALID_VALUE
         return _pkg.lib().clfa_nupconv_matrix_push_ir_fade_dev(self._h, ir.data_ptr(), rows[0], int(fade_blocks), rows[1])
 
-    def fade_remaining(self):
-        """head blocks of a pending crossfade that have not been processed yet; 0: none"""
-        return self._get("fade_remaining")
-
     def convolution(self, output, input):
         """whole signals on the host: float32 (inputs, L) -> (outputs, L), L a multiple of pts0; blocking"""
         output = _host(output, np.float32)
@@ -477,14 +453,6 @@ class NupconvMatrix(_Object):
             return CL_INVALID_VALUE
         return _pkg.lib().clfa_nupconv_matrix_process_dev(self._h, out.data_ptr(), so, x.data_ptr(), si, li // self.pts0,
                                                           _stream_of(x, stream))
-
-    def reset(self, stream=None):
-        """forget the input history (position 0); the responses stay.  `stream`: a HIP stream handle, default the
-        current torch stream of the object's device"""
-        if stream is None:
-            import torch
-            stream = torch.cuda.current_stream().cuda_stream
-        return self._get("reset", stream)
 
 
 class Cldconv(_BlockConv):

@@ -1,5 +1,6 @@
 // clfft_amd.cpp — C ABI of libclfft_amd.so (see include/clfft_amd.h): library, devices, error strings, tables, copy
-// helpers and the FFT plans.  The convolutions are in conv_host.cpp, Stft in stft_host.cpp, what they share in host.hpp.
+// helpers and the FFT plans.  The convolutions are in pconv_host.cpp, dconv_host.cpp, pconv_matrix_host.cpp and
+// nupconv_host.cpp, Stft in stft_host.cpp, what they share in host.hpp.
 //
 // Host side of the hot path: plan objects (the reference's Clcfft / Clrfft instances), exact host tables, H2D/D2H
 // staging for the blocking host-pointer entry points, and the mapping hipError_t -> OpenCL status numbers.  No CPU
@@ -535,7 +536,7 @@ int clfa_fft_run_buffers(clfa_fft *p) {
 #ifndef CLFA_ZEROCOPY_MAX_KIB
 #define CLFA_ZEROCOPY_MAX_KIB 512   // (profiles/host_path_r05.txt: one N = 65536 transform, 512 KiB: 59.5 us this way, 73.5 by copies)
 #endif
-constexpr size_t kZeroCopyMax = (size_t)CLFA_ZEROCOPY_MAX_KIB << 10;   // (the convolutions': conv_host.cpp)
+constexpr size_t kZeroCopyMax = (size_t)CLFA_ZEROCOPY_MAX_KIB << 10;   // (the convolutions': conv_host.hpp)
 
 // ---- pinned arrays for the caller (extension) --------------------------------------------------------------------
 // The reference's transform() copies the caller's array to the device and back with two blocking transfers

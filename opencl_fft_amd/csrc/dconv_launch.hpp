@@ -1,4 +1,4 @@
-// dconv_launch.hpp — the launchers of the direct convolution as conv_host.cpp sees them: the one-block form
+// dconv_launch.hpp — the launchers of the direct convolution as dconv_host.cpp sees them: the one-block form
 // (dconv_block.hip: DconvPlan, launch_dconv_block) and the many-block, many-channel form (dconv_blocks.hip:
 // DconvBlocksPlan, DconvBlocksArgs, launch_dconv_blocks).
 #pragma once

@@ -1,5 +1,5 @@
 // fft_tables.hpp — the exact host tables only the FFT kernels read (four-step, lane-addressed, resident n = 65536, big
-// sizes), built from host.hpp's fill_twiddle; for clfft_amd.cpp and conv_host.cpp, the two files that create FFT plans'
+// sizes), built from host.hpp's fill_twiddle; for clfft_amd.cpp and pconv_host.cpp, the two files that create FFT plans'
 // tables.  The tables every object shares (fill_twiddle, fill_w2, upload_half, upload_w2) stay in host.hpp.
 #pragma once
 #include "fft_launch.hpp"

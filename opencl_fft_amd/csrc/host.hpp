@@ -1,5 +1,6 @@
-// host.hpp — plumbing shared by the host side of the C ABI (clfft_amd.cpp: FFT plans, conv_host.cpp: the
-// convolutions, stft_host.cpp: Stft, pvoc_host.cpp: Pvoc): error mapping, device and stream handling, owned device /
+// host.hpp — plumbing shared by the host side of the C ABI (clfft_amd.cpp: FFT plans, pconv_host.cpp, dconv_host.cpp,
+// pconv_matrix_host.cpp, nupconv_host.cpp: the convolutions over conv_host.hpp, stft_host.cpp: Stft, pvoc_host.cpp:
+// Pvoc): error mapping, device and stream handling, owned device /
 // pinned buffers, numeric switches of the environment, the exact host tables every object needs (the FFT-only ones:
 // fft_tables.hpp), the prelude / creation / destruction every object shares, and the staged blocking form of a call
 // (staged_call) over the description of its arrays (HostArray; its rules: overlap.hpp).  Each *_host.cpp adds the launch

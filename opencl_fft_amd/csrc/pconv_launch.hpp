@@ -1,5 +1,6 @@
 // pconv_launch.hpp — the launchers of the partitioned convolution (pconv_chain.hip, pconv_coop.hip, pconv_blocks.hip,
-// pconv_matrix.hip, pconv_nup.hip, pconv_nupm.hip) as conv_host.cpp sees them: PconvGeom and the per-block launches, the
+// pconv_matrix.hip, pconv_nup.hip, pconv_nupm.hip) as the convolutions' hosts (pconv_host.cpp, pconv_matrix_host.cpp,
+// nupconv_host.cpp) see them: PconvGeom and the per-block launches, the
 // cooperative and the fused block, the many-block sub-batch (PconvBlocks), the convolution matrix (PconvMatrixArgs), the
 // tail level of the non-uniform partitioning (launch_nupc_*), its matrix form (launch_nupm_*) and the ends of the composed
 // chain.

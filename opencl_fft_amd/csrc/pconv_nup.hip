@@ -1,4 +1,4 @@
-// pconv_nup.hip — the kernels of the non-uniformly partitioned convolution (clfa_nupconv, conv_host.cpp): a head of small
+// pconv_nup.hip — the kernels of the non-uniformly partitioned convolution (clfa_nupconv, nupconv_host.cpp): a head of small
 // partitions (pts0) gives the latency; the long tail runs in large partitions (pts1 = m * pts0), and each tail block's
 // multiply-accumulate is spread in m slices of its bins over the m head blocks that pass while its output is not yet needed.
 //   k_nupc_stage   the call's input rows -> the tail's input row (channels x pts1 floats) at the stream's position

@@ -1,5 +1,5 @@
 // pconv_nupm.hip — the multiply-accumulate of the non-uniformly partitioned convolution matrix (clfa_nupconv_matrix,
-// conv_host.cpp): `inputs` signals into `outputs` signals through outputs x inputs responses held on two levels, a head of
+// nupconv_host.cpp): `inputs` signals into `outputs` signals through outputs x inputs responses held on two levels, a head of
 // small partitions (pts0) and a tail of large ones (pts1 = m * pts0) whose blocks are multiplied in m slices of their bins.
 //   k_nupm_mac     one segment's sum over r = i * nparts + p, ascending, of  A_i[(w - (nparts - 1) + p) mod ring] (.)
 //                  H_{o,i}[nparts - 1 - p]  for ONE block of a level over a range of its 16-byte items: the terms, their

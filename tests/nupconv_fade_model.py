@@ -1,5 +1,5 @@
 """float64 model of Nupconv with the timed crossfade of response changes (clfa_nupconv_push_ir_fade, include/clfft_amd.h),
-following the schedule of conv_host.cpp literally: one pair of input-spectra rings shared by both paths, the tail's of
+following the schedule of nupconv_host.cpp literally: one pair of input-spectra rings shared by both paths, the tail's of
 n1 + 2 frames; a second set of everything that depends on the responses, primed at the push from the rings alone; the two
 sets exchanged when the fade's last block has run.  And the definition the fade must meet: two objects fed alike, mixed."""
 import numpy as np

@@ -1,5 +1,5 @@
 """float64 model of NupconvMatrix with the timed crossfade of response changes (clfa_nupconv_matrix_push_ir_fade,
-include/clfft_amd.h), following the schedule of conv_host.cpp literally, segments included: one pair of inputs' spectra
+include/clfft_amd.h), following the schedule of nupconv_host.cpp literally, segments included: one pair of inputs' spectra
 rings shared by both paths, the tail's of n1 + 2 frames per input; a second set of everything that depends on the
 responses, primed at the push from the rings alone; the two sets exchanged when the fade's last block has run.  The
 definition the fade must meet is `mixed` of two tests.nupconv_matrix_model.definition results."""

@@ -1,5 +1,5 @@
 """float64 model of the non-uniformly partitioned convolution matrix (clfa_nupconv_matrix, include/clfft_amd.h) that follows
-the schedule of conv_host.cpp / pconv_nupm.hip literally, head block by head block, segments included; and the definition
+the schedule of nupconv_host.cpp / pconv_nupm.hip literally, head block by head block, segments included; and the definition
 it must meet: two MatrixModel objects, the tail's output delayed by 2 * pts1."""
 import numpy as np
 

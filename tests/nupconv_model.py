@@ -1,5 +1,5 @@
 """float64 model of the non-uniformly partitioned convolution (clfa_nupconv, include/clfft_amd.h) that follows the schedule
-of conv_host.cpp / pconv_nup.hip literally, head block by head block, for the tests; and the definition it must meet."""
+of nupconv_host.cpp / pconv_nup.hip literally, head block by head block, for the tests; and the definition it must meet."""
 import numpy as np
 
 from tests import util

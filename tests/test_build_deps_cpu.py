@@ -12,7 +12,8 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "opencl_fft_amd", "csrc")
-HOST = ["clfft_amd.cpp", "conv_host.cpp", "stft_host.cpp", "pvoc_host.cpp"]
+CONV_HOST = ["pconv_host.cpp", "dconv_host.cpp", "pconv_matrix_host.cpp", "nupconv_host.cpp"]
+HOST = ["clfft_amd.cpp"] + CONV_HOST + ["stft_host.cpp", "pvoc_host.cpp"]
 PVOC = ["pvoc_kernels.hip", "pvoc_ops.hip", "pvoc_pair.hip", "pvoc_time.hip", "pvoc_delay.hip", "pvoc_shape.hip",
         "pvoc_desc.hip", "pvoc_trace.hip", "pvoc_demix.hip", "pvoc_adsyn.hip"]
 # the units that use nothing of the FFT engine (fft_device.hpp)
@@ -58,6 +59,14 @@ def test_inc_file_belongs_to_one_unit(up_to_date, header, unit):
 
 def test_pvoc_launch_header_is_pvoc_only(up_to_date):
     assert recompiled("pvoc_launch.hpp", up_to_date) == set(PVOC) | {"pvoc_host.cpp"}
+
+
+def test_dconv_launch_header_is_dconv_only(up_to_date):
+    assert recompiled("dconv_launch.hpp", up_to_date) == {"dconv_block.hip", "dconv_blocks.hip", "dconv_host.cpp"}
+
+
+def test_conv_host_header_is_the_convolution_hosts(up_to_date):
+    assert recompiled("conv_host.hpp", up_to_date) == set(CONV_HOST)
 
 
 def test_fft_engine_leaves_other_families_alone(up_to_date):
