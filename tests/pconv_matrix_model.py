@@ -2,6 +2,8 @@
 pconv_matrix.hip, for the tests."""
 import numpy as np
 
+from tests import util
+
 
 def seg_bounds(total, segs):
     """the reduction's segments: [floor(s * total / segs), floor((s + 1) * total / segs))"""
@@ -58,3 +60,21 @@ class MatrixModel:
                 self.A[:, (w + m) % P] = X[:, m]
             self.wp = (w + K) % P
         return out
+
+
+def truth_with_push(h1, h2, t_push, x, pts):
+    """the definition with a push before block t_push: block t sums X_i[t - q] H_{o,i}[q] with h1's partitions for
+    t < t_push and h2's after, and every block's second half carries into the next one (the tails are kept)"""
+    X = util._block_spectra64(x.reshape(-1), pts).reshape(x.shape[0], -1, pts + 1)   # inputs x blocks x bins
+    H1 = util._block_spectra64(h1.reshape(-1), pts).reshape(h1.shape[0], h1.shape[1], -1, pts + 1)
+    H2 = util._block_spectra64(h2.reshape(-1), pts).reshape(h2.shape[0], h2.shape[1], -1, pts + 1)
+    n, P = X.shape[1], H1.shape[2]
+    out = []
+    for o in range(h1.shape[0]):
+        Y = np.zeros((n, pts + 1), np.complex128)
+        for t in range(n):
+            H = H1 if t < t_push else H2
+            for q in range(min(P, t + 1)):
+                Y[t] += np.sum(X[:, t - q] * H[o, :, q], axis=0)
+        out.append(util._olap64(Y, pts))
+    return np.stack(out)

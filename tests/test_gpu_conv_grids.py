@@ -61,9 +61,8 @@ import opencl_fft_amd as fa
 from tests import conv_exact as cx
 from tests import gpu_guard as gg
 from tests import util
-from tests.nupconv_fade_model import NupFadeModel, mixed
-from tests.nupconv_model import definition
-from tests.nupconv_tv_model import NupTvModel
+from tests.nupconv_definitions import definition, mixed
+from tests.nupconv_model import NupFadeModel, NupTvModel
 
 pytestmark = pytest.mark.gpu
 

@@ -8,56 +8,31 @@ import numpy as np
 import pytest
 import torch
 
-import opencl_fft_amd as fa
 from opencl_fft_amd._lib import lib
 from tests import gpu_guard as gg
+from tests import nupconv_cases as nc
 from tests import util
-from tests.nupconv_tv_model import Composition, NupTvModel
-from tests.test_gpu_nupconv import DEPTH_GEOMS, SIZE_GEOMS
+from tests.nupconv_definitions import Composition
+from tests.nupconv_model import NupTvModel
 
 pytestmark = pytest.mark.gpu
 
 CL_INVALID_VALUE, CL_INVALID_OPERATION = -30, -59
-GEOMS = [(32, 64, 1), (32, 256, 3), (64, 4096, 2)]   # pts0, pts1, n1
-# k_nupc_fwd (the forward transform with the stage copy folded in) at every size on both levels, and tails on both sides of
-# k_nupc_mac's prefetch depth: the geometries of tests/test_gpu_nupconv.py
-ALL_GEOMS = GEOMS + SIZE_GEOMS + DEPTH_GEOMS
+# GEOMS; k_nupc_fwd (the forward transform with the stage copy folded in) at every size on both levels; tails on both sides
+# of k_nupc_mac's prefetch depth
+GEOMS, ALL_GEOMS = nc.GEOMS, nc.ALL_GEOMS
 
 
-def _cvs(pts1, n1):
-    return 2 * pts1 + n1 * pts1 + 5   # a remainder, ignored
-
-
-def _nblocks(pts0, pts1, n1):
-    m = pts1 // pts0
-    return (n1 + 2) * m + 3 * m + 3   # R0 + 3m + 3: every partition of both levels is rewritten, the first head ones twice
-
-
-@functools.lru_cache(maxsize=None)
 def _signals(pts0, pts1, n1, channels):
-    """(h, x, w): pushed noise responses, the signal and the second input, uniform in [-0.5, 0.5) as the signals of
-    tests/test_gpu_nupconv.py; read-only"""
-    rng = np.random.default_rng(pts0 + pts1 + 10 * n1 + channels + 1)
-    L = _nblocks(pts0, pts1, n1) * pts0
-    out = (rng.random((channels, _cvs(pts1, n1)), dtype=np.float32) - 0.5,
-           rng.random((channels, L), dtype=np.float32) - 0.5,
-           rng.random((channels, L), dtype=np.float32) - 0.5)
-    for a in out:
-        a.setflags(write=False)
-    return out
+    return nc.signals("tv", (pts0, pts1, n1, channels))
 
 
 def _object(pts0, pts1, n1, channels, h=None):
-    p = fa.Nupconv(0, _cvs(pts1, n1), pts0, pts1, channels=channels)
-    assert p.get_error() == 0, p.get_log()
-    assert p.nparts(1) == n1 and p.kernel_name() == "k_nupc_mac" and p.tv_period == (n1 + 2) * (pts1 // pts0)
-    if h is not None:
-        assert p.push_ir(h) == 0
-    return p
+    return nc.make((pts0, pts1, n1, channels), h)
 
 
 class _Plain:
-    """the plain object of the definition on the device, as tests/nupconv_tv_model.Composition drives it"""
+    """the plain object of the definition on the device, as tests/nupconv_definitions.Composition drives it"""
 
     def __init__(self, pts0, pts1, n1, channels, h=None):
         self.p = _object(pts0, pts1, n1, channels, h)
@@ -88,28 +63,7 @@ def _composition(pts0, pts1, n1, channels):
 
 
 def _run(p, x, w, splits, plain=()):
-    """the calls of `splits` blocks each on guarded rows: out at a longer stride, 4 bytes past a 16-byte boundary; x and w
-    at different strides, w 8 bytes past a 16-byte boundary, both unchanged afterwards; nothing written outside out,
-    every element of it written.  The calls whose index is in `plain` go through process_device"""
-    channels, L = x.shape
-    xin = gg.rows(channels, L, L + 4).fill(np.array(x))
-    win = gg.rows(channels, L, L + 7, misalign=2).fill(np.array(w))
-    out = gg.rows(channels, L, L + 9, misalign=1)
-    j, start = 0, p.position
-    for i, n in enumerate(splits):
-        a, b = j * p.pts0, (j + n) * p.pts0
-        if i in plain:
-            assert p.process_device(out.data[:, a:b], xin.data[:, a:b]) == 0
-        else:
-            assert p.process_tv_device(out.data[:, a:b], xin.data[:, a:b], win.data[:, a:b]) == 0
-        j += n
-        assert p.position == start + j
-    torch.cuda.synchronize()
-    assert j * p.pts0 == L
-    out.check_sides("the output rows")
-    assert not out.unwritten(), "an output element was not written"
-    assert xin.unchanged() and win.unchanged(), "an input changed"
-    return out.host()
+    return nc.run(nc.NUPCONV, p, x, splits, w, plain)
 
 
 @pytest.mark.parametrize("channels", [1, 3])
@@ -156,11 +110,11 @@ def test_static_equivalence_from_block_r0_plus_2m(pts0, pts1, n1, channels):
 
 @pytest.mark.parametrize("pts0,pts1,n1", ALL_GEOMS)
 def test_against_the_float64_model(pts0, pts1, n1):
-    """tests/nupconv_tv_model.NupTvModel at the project's parity criterion, tests/util.TOL"""
+    """tests/nupconv_model.NupTvModel at the project's parity criterion, tests/util.TOL"""
     channels = 3
     h, x, w = _signals(pts0, pts1, n1, channels)
     got = _run(_object(pts0, pts1, n1, channels, h), x, w, [x.shape[1] // pts0])
-    model = NupTvModel(_cvs(pts1, n1), pts0, pts1, channels)
+    model = NupTvModel(nc.cvs(pts1, n1), pts0, pts1, channels)
     model.push_ir(h)
     want = model.process(x, w)
     for c in range(channels):

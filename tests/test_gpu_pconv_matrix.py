@@ -9,7 +9,7 @@ import opencl_fft_amd as fa
 from opencl_fft_amd._lib import lib
 from tests import util
 from tests.util import assert_parity
-from tests.test_pconv_matrix_cpu import truth_with_push
+from tests.pconv_matrix_model import truth_with_push
 
 pytestmark = pytest.mark.gpu
 

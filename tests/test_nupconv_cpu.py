@@ -1,13 +1,16 @@
 """Non-uniformly partitioned convolution without a GPU: the new ABI symbols, the Python surface's answers without a
 device, the refusals of create before the device is looked for, and the float64 model of the schedule
-(tests/nupconv_model.py) checked against the definition built from tests/util.pconv_f64."""
+(tests/nupconv_model.py) checked against the definition built from tests/util.pconv_f64
+(tests/nupconv_definitions.py)."""
 import numpy as np
 import pytest
 
 import opencl_fft_amd as fa
 from opencl_fft_amd._lib import lib
-from tests.nupconv_model import NupModel, definition, delayed_tail
-from tests.test_pconv_matrix_cpu import truth_with_push
+from tests import nupconv_cases as nc
+from tests.nupconv_definitions import definition, delayed_tail
+from tests.nupconv_model import NupModel
+from tests.pconv_matrix_model import truth_with_push
 
 CL_DEVICE_NOT_FOUND, CL_INVALID_VALUE = -1, -30
 NAMES = ["clfa_nupconv_create", "clfa_nupconv_destroy", "clfa_nupconv_get_error", "clfa_nupconv_get_log",
@@ -80,19 +83,10 @@ def _streams(rng, cvs, nblocks, pts0, channels):
     return h, x
 
 
-def _run(model, x, splits):
-    out, j = [], 0
-    for n in splits:
-        out.append(model.process(x[:, j * model.pts0:(j + n) * model.pts0]))
-        j += n
-    assert j * model.pts0 == x.shape[1] and model.position == j
-    return np.concatenate(out, axis=1)
-
-
-@pytest.mark.parametrize("pts0,pts1,n1", [(4, 8, 1), (4, 16, 3), (8, 64, 2)])
+@pytest.mark.parametrize("pts0,pts1,n1", nc.MODEL_GEOMS)
 def test_schedule_matches_the_definition(pts0, pts1, n1):
     m, channels = pts1 // pts0, 2
-    cvs = 2 * pts1 + n1 * pts1 + 3            # a remainder, dropped
+    cvs = nc.cvs(pts1, n1, 3)
     nblocks = (n1 + 5) * m + 3                # past the whole response, ending inside a period
     rng = np.random.default_rng(pts0 * 100 + pts1 + n1)
     h, x = _streams(rng, cvs, nblocks, pts0, channels)
@@ -103,7 +97,7 @@ def test_schedule_matches_the_definition(pts0, pts1, n1):
         model = NupModel(cvs, pts0, pts1, channels)
         assert (model.n0, model.n1) == (2 * m, n1)
         model.push_ir(h)
-        got = _run(model, x, splits)
+        got = nc.model_calls(model, x, splits)
         err = np.max(np.abs(got - want)) / peak
         assert err < 1e-12, (splits[:6], err)
     # the tail is silent for 2 * pts1 samples and present after them

@@ -1,14 +1,17 @@
 """Non-uniformly partitioned convolution matrix without a GPU: the new ABI symbols, the Python surface's answers without a
 device, the refusals of create before the device is looked for, and the float64 model of the schedule, segments included
-(tests/nupconv_matrix_model.py), checked against the definition: two MatrixModel objects, the tail delayed by 2 * pts1.
+(tests/nupconv_model.py), checked against the definition: two MatrixModel objects, the tail delayed by 2 * pts1
+(tests/nupconv_definitions.py).
 Every model test also creates the library's object at the model's geometry (scaled to pts0 = 32)."""
 import numpy as np
 import pytest
 
 import opencl_fft_amd as fa
 from opencl_fft_amd._lib import lib
-from tests.nupconv_matrix_model import NupMatrixModel, definition
-from tests.nupconv_model import definition as definition_1x1
+from tests import nupconv_cases as nc
+from tests.nupconv_definitions import definition as definition_1x1
+from tests.nupconv_definitions import matrix_definition as definition
+from tests.nupconv_model import NupMatrixModel
 
 CL_DEVICE_NOT_FOUND, CL_INVALID_VALUE = -1, -30
 NAMES = ["clfa_nupconv_matrix_" + n for n in (
@@ -89,49 +92,28 @@ def _streams(rng, cvs, nblocks, pts0, I, O):
     return h, x
 
 
-def _run(model, x, splits):
-    out, j = [], 0
-    for n in splits:
-        out.append(model.process(x[:, j * model.pts0:(j + n) * model.pts0]))
-        j += n
-    assert j * model.pts0 == x.shape[1] and model.position == j
-    return np.concatenate(out, axis=1)
-
-
 def _library_twin(model, cvs):
     """the library's object at the model's geometry scaled to its smallest partition (pts0 -> 32): it reaches the device
     lookup, and where a device answers it has the model's partitions on both levels"""
     k = 32 // model.pts0
-    p = fa.NupconvMatrix(0, cvs * k, model.pts0 * k, model.pts1 * k, model.I, model.O)
+    p = fa.NupconvMatrix(0, cvs * k, model.pts0 * k, model.pts1 * k, model.rows_in, model.rows_out)
     assert p.get_error() in (0, CL_DEVICE_NOT_FOUND) and p.get_log() == ""
     if p.get_error() == 0:
         assert (p.nparts(0), p.nparts(1)) == (model.n0, model.n1)
 
 
-def _cutting(I, nparts):
-    """a segment count whose cuts fall inside an input's partitions (not all on multiples of nparts); with one
-    partition per input there is no inside: the inputs are cut apart"""
-    total = I * nparts
-    if nparts == 1:
-        return min(2, total)
-    for segs in range(2, total + 1):
-        if any((total * s // segs) % nparts for s in range(1, segs)):
-            return segs
-    raise AssertionError("no segment count cuts inside an input's partitions")
-
-
 @pytest.mark.parametrize("I,O", [(2, 3), (3, 1)])
-@pytest.mark.parametrize("pts0,pts1,n1", [(4, 8, 1), (4, 16, 3), (8, 64, 2)])
+@pytest.mark.parametrize("pts0,pts1,n1", nc.MODEL_GEOMS)
 def test_schedule_matches_the_definition(pts0, pts1, n1, I, O):
     m = pts1 // pts0
-    cvs = 2 * pts1 + n1 * pts1 + 3            # a remainder, dropped
+    cvs = nc.cvs(pts1, n1, 3)
     nblocks = (n1 + 5) * m + 3                # past the whole response, ending inside a period
     rng = np.random.default_rng(pts0 * 100 + pts1 + n1 + 7 * I + O)
     h, x = _streams(rng, cvs, nblocks, pts0, I, O)
     # the definition in the words of util.pconv_f64 as well: the segments change no float64 sum beyond rounding
     sums = np.stack([sum(definition_1x1(h[o, i], x[i], cvs, pts0, pts1) for i in range(I)) for o in range(O)])
     head = [1, m + 2, 2, 0, 2 * m + 1]        # odd calls that cross period boundaries, and an empty one
-    for segs in ((1, 1), (_cutting(I, 2 * m), _cutting(I, n1))):
+    for segs in ((1, 1), (nc.cutting(I, 2 * m), nc.cutting(I, n1))):
         want = definition(h, x, cvs, pts0, pts1, segs)
         peak = np.max(np.abs(want))
         assert np.max(np.abs(want - sums)) < 1e-12 * peak
@@ -140,7 +122,7 @@ def test_schedule_matches_the_definition(pts0, pts1, n1, I, O):
             assert (model.n0, model.n1) == (2 * m, n1)
             _library_twin(model, cvs)
             model.push_ir(h)
-            got = _run(model, x, splits)
+            got = nc.model_calls(model, x, splits)
             err = np.max(np.abs(got - want)) / peak
             assert err < 1e-12, (segs, splits[:6], err)
     # the tail is silent for 2 * pts1 samples and present after them

@@ -1,5 +1,5 @@
 """Nupconv's time-varying second input without a GPU: the new ABI symbols with their bound types, the Python surface and
-its refusals, and the float64 model (tests/nupconv_tv_model.py) against the three properties of the rule: the push
+its refusals, and the float64 model (tests/nupconv_model.NupTvModel) against the three properties of the rule: the push
 composition, static equivalence from head block R0 + 2m on, the closed-form impulse readout; cut-invariance and freeze."""
 import ctypes as C
 import functools
@@ -9,11 +9,12 @@ import pytest
 
 import opencl_fft_amd as fa
 from opencl_fft_amd._lib import lib
-from tests.nupconv_model import NupModel
-from tests.nupconv_tv_model import Composition, NupTvModel, readout, readout_stream
+from tests import nupconv_cases as nc
+from tests.nupconv_definitions import Composition, readout, readout_stream
+from tests.nupconv_model import NupModel, NupTvModel
 
 CL_DEVICE_NOT_FOUND, CL_INVALID_VALUE = -1, -30
-GEOMS = [(32, 64, 1), (32, 256, 3)]   # pts0, pts1, n1
+GEOMS = nc.TV_MODEL_GEOMS   # pts0, pts1, n1
 _vp = C.c_void_p
 
 
@@ -60,17 +61,13 @@ def test_refusals_that_need_no_device():
         assert p.tv_period == ((cvs - 2 * pts1) // pts1 + 2) * (pts1 // pts0)
 
 
-def _cvs(pts1, n1):
-    return 2 * pts1 + n1 * pts1 + 5   # a remainder, dropped
-
-
 @functools.lru_cache(maxsize=None)
 def _case(pts0, pts1, n1, channels=2):
     """(h, x, w): pushed responses, a signal and a second input of R0 + 3m + 3 head blocks, float32 values, read-only"""
     m = pts1 // pts0
     nblocks = (n1 + 2) * m + 3 * m + 3
     rng = np.random.default_rng(pts0 + pts1 + 10 * n1 + channels)
-    out = (rng.random((channels, _cvs(pts1, n1)), dtype=np.float32) - 0.5,
+    out = (rng.random((channels, nc.cvs(pts1, n1)), dtype=np.float32) - 0.5,
            rng.random((channels, nblocks * pts0), dtype=np.float32) - 0.5,
            rng.random((channels, nblocks * pts0), dtype=np.float32) - 0.5)
     for a in out:
@@ -79,22 +76,11 @@ def _case(pts0, pts1, n1, channels=2):
 
 
 def _model(pts0, pts1, n1, channels, h=None):
-    model = NupTvModel(_cvs(pts1, n1), pts0, pts1, channels)
+    model = NupTvModel(nc.cvs(pts1, n1), pts0, pts1, channels)
     assert model.R0 == (n1 + 2) * (pts1 // pts0) and model.L == model.need()
     if h is not None:
         model.push_ir(h)
     return model
-
-
-def _calls(model, x, w, splits, plain=()):
-    """calls of `splits` blocks each; the calls whose index is in `plain` go without the second input"""
-    out, j, n = [], 0, model.pts0
-    for i, k in enumerate(splits):
-        a, b = j * n, (j + k) * n
-        out.append(model.process(x[:, a:b], None if i in plain else w[:, a:b]))
-        j += k
-    assert j * n == x.shape[1]
-    return np.concatenate(out, axis=1)
 
 
 @pytest.mark.parametrize("pts0,pts1,n1", GEOMS)
@@ -102,11 +88,11 @@ def test_the_push_composition_exactly(pts0, pts1, n1):
     h, x, w = _case(pts0, pts1, n1)
     channels, nblocks, m = x.shape[0], x.shape[1] // pts0, pts1 // pts0
     for plain in ((), (3 * m + 1, nblocks - 2)):   # all time-varying; two blocks sent as plain ones
-        comp = Composition(NupModel(_cvs(pts1, n1), pts0, pts1, channels), pts0, pts1, n1, channels, ir=h)
+        comp = Composition(NupModel(nc.cvs(pts1, n1), pts0, pts1, channels), pts0, pts1, n1, channels, ir=h)
         comp.p.push_ir(h)
         want = comp.run(x, w, plain=plain)
         model = _model(pts0, pts1, n1, channels, h)
-        got = _calls(model, x, w, [1] * nblocks, plain=plain)
+        got = nc.model_calls(model, x, [1] * nblocks, w, plain)
         assert np.array_equal(got, want), plain
     # the second input is heard: the object that keeps h returns something else
     still = _model(pts0, pts1, n1, channels, h).process(x)
@@ -117,11 +103,11 @@ def test_the_push_composition_exactly(pts0, pts1, n1):
 def test_cut_invariance(pts0, pts1, n1):
     h, x, w = _case(pts0, pts1, n1)
     channels, nblocks, m = x.shape[0], x.shape[1] // pts0, pts1 // pts0
-    want = _calls(_model(pts0, pts1, n1, channels, h), x, w, [nblocks])
+    want = nc.model_calls(_model(pts0, pts1, n1, channels, h), x, [nblocks], w)
     for splits in ([1] * nblocks, [1, m - 1, 0, 2 * m - m + 3, nblocks - 2 * m - 3]):
         assert sum(splits) == nblocks
         model = _model(pts0, pts1, n1, channels, h)
-        assert np.array_equal(_calls(model, x, w, splits), want), splits[:5]
+        assert np.array_equal(nc.model_calls(model, x, splits, w), want), splits[:5]
         assert model.position == nblocks
 
 
@@ -174,7 +160,7 @@ def test_freeze_a_plain_block_leaves_its_tail_partition_alone():
     for spoil in (U * m, U * m + m - 1):    # the block's first and last head block
         model = _model(pts0, pts1, n1, channels, h)
         splits = [spoil, 1, stop - spoil - 1]
-        _calls(model, x[:, :stop * pts0], w[:, :stop * pts0], splits, plain=(1,))
+        nc.model_calls(model, x[:, :stop * pts0], splits, w[:, :stop * pts0], plain=(1,))
         assert np.array_equal(model.H1[:, 1], H1[:, 1]), spoil
         assert not np.array_equal(model.H1[:, 0], H1[:, 0])   # tail block 2 was whole: partition 0 is the second input's
     model = _model(pts0, pts1, n1, channels, h)

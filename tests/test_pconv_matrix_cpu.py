@@ -6,7 +6,7 @@ import pytest
 import opencl_fft_amd as fa
 from opencl_fft_amd._lib import lib
 from tests import util
-from tests.pconv_matrix_model import MatrixModel, seg_bounds
+from tests.pconv_matrix_model import MatrixModel, seg_bounds, truth_with_push
 
 CL_DEVICE_NOT_FOUND, CL_INVALID_VALUE = -1, -30
 NAMES = ["clfa_pconv_matrix_create", "clfa_pconv_matrix_destroy", "clfa_pconv_matrix_get_error",
@@ -73,24 +73,6 @@ def test_sub_batch_algebra_matches_the_definition(inputs, outputs, nparts, cap, 
     err = np.max(np.abs(got - want)) / np.max(np.abs(want))
     assert err < 1e-12, err
     assert m.wp == sum(splits) % nparts
-
-
-def truth_with_push(h1, h2, t_push, x, pts):
-    """the definition with a push before block t_push: block t sums X_i[t - q] H_{o,i}[q] with h1's partitions for
-    t < t_push and h2's after, and every block's second half carries into the next one (the tails are kept)"""
-    X = util._block_spectra64(x.reshape(-1), pts).reshape(x.shape[0], -1, pts + 1)   # inputs x blocks x bins
-    H1 = util._block_spectra64(h1.reshape(-1), pts).reshape(h1.shape[0], h1.shape[1], -1, pts + 1)
-    H2 = util._block_spectra64(h2.reshape(-1), pts).reshape(h2.shape[0], h2.shape[1], -1, pts + 1)
-    n, P = X.shape[1], H1.shape[2]
-    out = []
-    for o in range(h1.shape[0]):
-        Y = np.zeros((n, pts + 1), np.complex128)
-        for t in range(n):
-            H = H1 if t < t_push else H2
-            for q in range(min(P, t + 1)):
-                Y[t] += np.sum(X[:, t - q] * H[o, :, q], axis=0)
-        out.append(util._olap64(Y, pts))
-    return np.stack(out)
 
 
 def test_push_between_calls_applies_from_the_next_block():
