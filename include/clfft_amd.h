@@ -845,6 +845,71 @@ CLFA_API size_t clfa_pvoc_desc_state_bytes(const clfa_pvoc *pv);
 /* "k_pvoc_desc" ("" for a failed object) */
 CLFA_API const char *clfa_pvoc_desc_kernel_name(const clfa_pvoc *pv);
 
+/* ---- filter bank on (amp, freq) frames: band energies, their log, a DCT of that (mel, MFCC) ---- */
+/* Frames to feature vectors: Csound's mfb and dct, the mel spectrum and the cepstral coefficients computed from it.
+ * frames_in: channels x F x (M + 1) x 2 float32 in the layout above, 8-byte aligned; only the amp column is read.
+ * out: channels x F x N float32, dense, 4-byte aligned, one row per frame; N = B without CLFA_PVOC_BANDS_DCT, N = ncoef
+ * with it.
+ *
+ * THE BANK is configuration of the object, set by clfa_pvoc_bank_setup(pv, nbands, first, count, weights): nbands = B,
+ * 1 <= B <= 256; band b covers the bins first[b] .. first[b] + count[b] - 1 with count[b] >= 1, first[b] >= 0 and
+ * first[b] + count[b] <= M + 1; its weights w_b are count[b] float32, finite and of any sign, the weights of all bands
+ * stored one after the other (host arrays; sum(count) values).  Bands may overlap, repeat, and come in any order.
+ * Anything else is CLFA_INVALID_VALUE and leaves the object as it was.  The setup follows clfa_pvoc_blur_setup's rules:
+ * blocking, refused with CLFA_INVALID_OPERATION while the object's stream is being captured, the new buffers allocated
+ * before the old ones are replaced, and it may be called again.  A bands call before the setup is
+ * CLFA_INVALID_OPERATION.  clfa_pvoc_reset leaves the bank alone: it is configuration, not stream state.
+ * The setup also builds the DCT table, the orthonormal DCT-II: D[q][b] = (float)(s_q cos(pi q (2b + 1) / (2B))) for q, b < B,
+ * evaluated in double, s_0 = sqrt(1 / B), s_q = sqrt(2 / B) for q >= 1.  clfa_pvoc_bank_read_dct (blocking) returns the
+ * table the device uses, B x B; the bits of the results are defined GIVEN THAT TABLE (two libms may differ in the last
+ * place of a double cosine).
+ *
+ * Every float32 operation is rounded on its own (no fused multiply-add); fl() marks a rounding.
+ * Per channel and frame, with a[k] the amp of bin k:
+ *   TERM   x[k] = a[k] without CLFA_PVOC_BANDS_POWER, x[k] = fl(a[k] a[k]) with it; t_b[i] = fl(x[first_b + i] w_b[i]),
+ *          i < count_b.
+ *   BAND   E_b = S16(t_b), the descriptors' TREE SUM at a width that fits a band: for j < 16, p[j] = t[j] (+0 where
+ *          j >= count); then t[j + 16], t[j + 32], ... are added in ascending order, one rounded addition each; while
+ *          more than one value is left, s[i] = fl(s[2i] + s[2i + 1]); E_b is the one value left.  The Nyquist bin is an
+ *          ordinary bin here.
+ *   LOG    (CLFA_PVOC_BANDS_LOG) L_b = logf(fmaxf(E_b, floor)); floor finite and > 0, else CLFA_INVALID_VALUE in both
+ *          forms; a NaN E_b takes the floor (the envelope's rule).  Without the flag floor is not looked at.
+ *   DCT    (CLFA_PVOC_BANDS_DCT, 1 <= ncoef <= B) with v = L where LOG is set, else v = E: C_q = the float32 sum of
+ *          fl(D[q][b] v_b) for q < ncoef, starting from +0 and running in ascending b.  Without the flag ncoef must be 0.
+ * An unknown flag bit is CLFA_INVALID_VALUE.  Nothing above depends on the grid, on the run of frames a workgroup takes
+ * or on which lanes take which band: the rows are the same bits however a stream is cut into calls, on any stream, for
+ * any grid cap and under graph replay.  logf is the device's (about an ulp); tests/test_gpu_pvoc_bank.py judges it as
+ * the envelope tests judge theirs.
+ *
+ * Stateless apart from reading the bank, and a device call allocates nothing.  The rules of the frame operations above
+ * hold: asynchronous on `stream`, capturable, one launch per call, one stream at a time, the current device left as
+ * found; F == 0 succeeds and does nothing.  Argument checks that need no device come first: on an object whose creation
+ * found no device a bad argument is still CLFA_INVALID_VALUE, a call before the setup CLFA_INVALID_OPERATION, and a good
+ * setup or diagnostic the object's error.  Before the setup ncoef is checked against 256 and the output against rows of
+ * one value.  An out that overlaps frames_in, even partly, is CLFA_INVALID_VALUE and nothing is written.
+ * tests/pvoc_bank_model.py restates all of it in numpy.
+ *
+ * Kernel: "k_pvoc_bands" (a workgroup of 256 lanes takes a run of consecutive frames of one channel — 8 up to M = 512,
+ * then 4, 2, 1 — and puts their amps, squared with POWER, into LDS; it is sixteen rows of 16 lanes, a row taking a band at
+ * a time by a schedule computed at the setup, longest band first; lane j walks i = j, j + 16, ..., reads each weight once
+ * for the run and keeps one partial sum per frame, folded with the descriptors' in-wave moves; E goes to LDS, then the
+ * log, then the DCT with a lane per (frame, q) and D from cache).  Each frame is read once.  No atomics, no waiting
+ * between workgroups.  CLFA_PVOC_OPS_GRID_MAX caps its workgroups. */
+enum { CLFA_PVOC_BANDS_POWER = 1, CLFA_PVOC_BANDS_LOG = 2, CLFA_PVOC_BANDS_DCT = 4 };
+CLFA_API int clfa_pvoc_bank_setup(clfa_pvoc *pv, int nbands, const int *first, const int *count, const float *weights);
+/* B of the last successful setup, -1 before */
+CLFA_API int clfa_pvoc_bank_bands(const clfa_pvoc *pv);
+/* diagnostics, blocking: B x B float32, D[q][b] as the device uses it (CLFA_INVALID_OPERATION before the setup) */
+CLFA_API int clfa_pvoc_bank_read_dct(clfa_pvoc *pv, float *host);
+/* the device memory of the bank: bands, schedule, weights, DCT table */
+CLFA_API size_t clfa_pvoc_bank_state_bytes(const clfa_pvoc *pv);
+CLFA_API int clfa_pvoc_bands_dev(clfa_pvoc *pv, const void *frames_in, void *out, long F, int flags, int ncoef, float floor,
+                                 void *stream);
+/* host arrays, copied in and out, blocking */
+CLFA_API int clfa_pvoc_bands(clfa_pvoc *pv, const float *frames_in, float *out, long F, int flags, int ncoef, float floor);
+/* "k_pvoc_bands" ("" for a failed object) */
+CLFA_API const char *clfa_pvoc_bands_kernel_name(const clfa_pvoc *pv);
+
 /* ---- the N loudest bins of every frame: trace, residual, bin list ---- */
 /* Csound's pvstrace with an exact count: the N loudest bins of a range of every frame are kept and the rest of the range
  * is silenced; with CLFA_PVOC_TRACE_RESIDUAL it is the other way round (the noise part of a sines-plus-noise split); and

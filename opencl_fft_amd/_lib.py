@@ -195,6 +195,13 @@ SYMBOLS = [
     ("clfa_pvoc_desc_read_state", C.c_int, [_vp, _vp]),
     ("clfa_pvoc_desc_state_bytes", C.c_size_t, [_vp]),
     ("clfa_pvoc_desc_kernel_name", C.c_char_p, [_vp]),
+    ("clfa_pvoc_bank_setup", C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
+    ("clfa_pvoc_bank_bands", C.c_int, [_vp]),
+    ("clfa_pvoc_bank_read_dct", C.c_int, [_vp, _vp]),
+    ("clfa_pvoc_bank_state_bytes", C.c_size_t, [_vp]),
+    ("clfa_pvoc_bands_dev", C.c_int, [_vp, _vp, _vp, C.c_long, C.c_int, C.c_int, C.c_float, _vp]),
+    ("clfa_pvoc_bands", C.c_int, [_vp, _vp, _vp, C.c_long, C.c_int, C.c_int, C.c_float]),
+    ("clfa_pvoc_bands_kernel_name", C.c_char_p, [_vp]),
     ("clfa_pvoc_trace_dev", C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_long, C.c_int, C.c_int, C.c_int, _vp]),
     ("clfa_pvoc_trace", C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_long, C.c_int, C.c_int, C.c_int]),
     ("clfa_pvoc_trace_kernel_name", C.c_char_p, [_vp]),

@@ -5,7 +5,7 @@
 // fft_tables.hpp), the prelude / creation / destruction every object shares, and the staged blocking form of a call
 // (staged_call) over the description of its arrays (HostArray; its rules: overlap.hpp).  Each *_host.cpp adds the launch
 // headers of its own kernel families (fft_launch.hpp, pconv_launch.hpp, dconv_launch.hpp, stft_launch.hpp, pvoc_launch.hpp,
-// tanal_launch.hpp).
+// tanal_launch.hpp, bank_launch.hpp).
 // Everything here is inline and hidden (-fvisibility=hidden): nothing becomes an exported symbol.
 #pragma once
 #include "../../include/clfft_amd.h"

@@ -5,13 +5,15 @@
 //   kTimeWG, kTimeRun      the item of the kernels along the frames (pvoc_time.hip, pvoc_delay.hip): a tile of bins, a run of frames
 //   pvoc_group_row, pvoc_groups   the group kernels (k_pvoc_desc<W>, k_pvoc_trace<W>): which row of a channel a group of W
 //                          lanes takes of an item, and the items and grid of such a launch
-//   desc_dpp, desc_xor, desc_fold   the in-wave moves and the fold of the descriptors' TREE SUM (k_pvoc_desc<W>, k_pvoc_demix_az<LOGM>)
+//   desc_dpp, desc_xor, desc_fold   the in-wave moves and the fold of the descriptors' TREE SUM (k_pvoc_desc<W>, k_pvoc_demix_az<LOGM>):
+//                          tree_moves.hpp's, included here
 //   pvoc_empty, pvoc_clamp01, pvoc_morph   the frame operations' EMPTY bin, clamp and interpolation rule
 //   pvoc_scale_source      the pitch scale's source map (k_pvoc_map, k_pvoc_formant, k_pvoc_warp)
 //   pvoc_scan              the chunked scan that turns the per-chunk sums of phase increments into the bases the
 //                          chunks start from (k_pvoc_scan on uint32 words, k_adsyn_scan on uint64 ones)
 #pragma once
 #include "pvoc_launch.hpp"
+#include "tree_moves.hpp"
 
 namespace clfa {
 
@@ -87,45 +89,6 @@ static inline PvocGroups pvoc_groups(long rows, int channels, const DeviceInfo &
   q.grid = pvoc_grid(q.items, (long)di.num_cus * 8, grid_max);
   return q;
 }
-
-// The moves of the TREE SUM inside a wave: a DPP move by its control word, and v of lane ^ STEP (quad_perm for ^ 1 and
-// ^ 2, ds_swizzle for ^ 4 and ^ 16, row_ror:8 for ^ 8, ds_bpermute for ^ 32)
-template <int CTRL>
-__device__ __forceinline__ int desc_dpp(int v) {
-  return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true);
-}
-
-// v of lane ^ STEP
-template <int STEP>
-__device__ __forceinline__ int desc_xor_bits(int v) {
-  static_assert(STEP == 1 || STEP == 2 || STEP == 4 || STEP == 8 || STEP == 16 || STEP == 32, "a level of one wave");
-  if constexpr (STEP == 1) return desc_dpp<0xB1>(v);                            // quad_perm [1,0,3,2]
-  else if constexpr (STEP == 2) return desc_dpp<0x4E>(v);                       // quad_perm [2,3,0,1]
-  else if constexpr (STEP == 4) return __builtin_amdgcn_ds_swizzle(v, 0x101F);  // and 0x1f, xor 0x04
-  else if constexpr (STEP == 8) return desc_dpp<0x128>(v);                      // row_ror:8
-  else if constexpr (STEP == 16) return __builtin_amdgcn_ds_swizzle(v, 0x401F); // and 0x1f, xor 0x10
-  else return __shfl_xor(v, 32);
-}
-template <int STEP>
-__device__ __forceinline__ float desc_xor(float v) {
-  return __builtin_bit_cast(float, desc_xor_bits<STEP>(__builtin_bit_cast(int, v)));
-}
-
-
-// One level of the tree on the N values the lane still holds, V[0 .. N): the half that bit STEP of the lane names stays
-// and takes the partner's partial sum, the other half goes to the partner; N / 2 values are left, in V[0 .. N/2).  After
-// the levels of 1 and 2 lanes on four values a lane holds value number desc_bitrev2(lane & 3)
-template <int STEP, int N, int LEN>
-__device__ __forceinline__ void desc_fold(float (&V)[LEN], bool up) {
-#pragma clang fp contract(off)
-  static_assert(N <= LEN, "the values held");
-#pragma unroll
-  for (int i = 0; i < N / 2; i++) {
-    const float keep = up ? V[i + N / 2] : V[i], send = up ? V[i] : V[i + N / 2];
-    V[i] = keep + desc_xor<STEP>(send);
-  }
-}
-__device__ __forceinline__ int desc_bitrev2(int x) { return ((x & 1) << 1) | ((x >> 1) & 1); }
 
 // an EMPTY bin of the frame operations: silent, at its bin centre (cf = sr / size)
 __device__ __forceinline__ cpx pvoc_empty(int j, float cf) {

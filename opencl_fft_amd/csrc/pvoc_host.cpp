@@ -2,6 +2,8 @@
 // The object and its states come first; then what every call shares — the description of its arrays (PvocArray: host.hpp's
 // HostArray, checked by arrays_ok, staged by staged_call), the device form, and pvoc_call, which puts a call's results in
 // the header's order — then one function per family of calls: scalar rules, array list, per-frame value rule, launch.
+#include "bank_launch.hpp"
+#include "bank_plan.hpp"
 #include "fft_route.hpp"
 #include "host.hpp"
 #include "pvoc_launch.hpp"
@@ -56,6 +58,11 @@ struct clfa_pvoc {
   DevBuf dlast, sdesc;
   DevBuf strace_bins;   // the N loudest bins (pvoc_trace.hip): staging of the host form's bin list
   DevBuf sdemix_az;     // the stereo demix (pvoc_demix.hip): staging of the host form's azimuth profile
+  // the filter bank (bank_kernels.hip; clfa_pvoc_bank_setup, bank_B -1 before): the bands, the schedule that deals them to
+  // the kernel's rows (bank_steps: its longest row), the weights and the DCT table, transposed; staging of the host
+  // form's rows.  Configuration, not stream state: clfa_pvoc_reset leaves it alone
+  DevBuf kbands, ksched, kweights, kdct, sbands;
+  int bank_B = -1, bank_steps = 0;
   StreamOrder order;
 };
 
@@ -869,6 +876,117 @@ int clfa_pvoc_desc_read_state(clfa_pvoc *p, float *host) {
 
 size_t clfa_pvoc_desc_state_bytes(const clfa_pvoc *p) { return p ? p->dlast.bytes : 0; }
 const char *clfa_pvoc_desc_kernel_name(const clfa_pvoc *p) { return !p || p->err ? "" : "k_pvoc_desc"; }
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------
+// frames -> band energies, their log, a DCT of that (bank_kernels.hip)
+// ---------------------------------------------------------------------------------
+
+// whether the bank has been set up: asked after the arguments
+static int pvoc_bank_ready(const clfa_pvoc *p) { return p->bank_B < 0 ? CLFA_INVALID_OPERATION : CLFA_SUCCESS; }
+
+// floor is looked at with LOG only; ncoef is 1..B with DCT (before the setup: 1..256, what a setup can make valid), else 0.
+// The output rows hold ncoef values with DCT, else B (before the setup the check takes rows of one value).
+static int pvoc_bands_call(clfa_pvoc *p, bool blocking, const void *in, void *out, long F, int flags, int ncoef, float floor,
+                           void *stream) {
+  if (int e = pvoc_usable(p)) return e;
+  const int all = CLFA_PVOC_BANDS_POWER | CLFA_PVOC_BANDS_LOG | CLFA_PVOC_BANDS_DCT;
+  const bool lg = flags & CLFA_PVOC_BANDS_LOG, dct = flags & CLFA_PVOC_BANDS_DCT;
+  const int B = p->bank_B;
+  const bool scalars_ok = !(flags & ~all) && (!lg || (std::isfinite(floor) && floor > 0.f)) &&
+                          (dct ? ncoef >= 1 && ncoef <= (B >= 0 ? B : kBankMax) : ncoef == 0);
+  const size_t N = dct ? (size_t)(ncoef > 0 ? ncoef : 0) : (size_t)(B > 0 ? B : 1);
+  const PvocArray arrays[] = {{in, pvoc_frame_bytes(p, F), 8, false, &clfa_pvoc::sframes},
+                              {out, sizeof(float) * (size_t)p->channels * (size_t)F * N, 4, true, &clfa_pvoc::sbands}};
+  const auto launch = [&](const void *const *d, hipStream_t s) {
+    BankArgs a;
+    a.M = p->M;
+    a.channels = p->channels;
+    a.F = F;
+    a.in = (const cpx *)d[0];
+    a.out = (float *)d[1];
+    a.B = B;
+    a.steps = p->bank_steps;
+    a.bands = (const int *)p->kbands.p;
+    a.sched = (const int *)p->ksched.p;
+    a.weights = (const float *)p->kweights.p;
+    a.dct_t = (const float *)p->kdct.p;
+    a.power = (flags & CLFA_PVOC_BANDS_POWER) != 0;
+    a.log = lg;
+    a.dct = dct;
+    a.ncoef = ncoef;
+    a.floor = floor;
+    a.grid_max = p->ops_grid_max;
+    return launch_pvoc_bands(a, p->di, s);
+  };
+  return pvoc_call(p, blocking, stream, scalars_ok, F, arrays, pvoc_bank_ready(p), pvoc_no_values, launch);
+}
+
+extern "C" {
+
+int clfa_pvoc_bank_setup(clfa_pvoc *p, int nbands, const int *first, const int *count, const float *weights) {
+  if (int e = pvoc_usable(p)) return e;
+  if (!bank_ok(p->M, nbands, first, count, weights)) return CLFA_INVALID_VALUE;
+  if (p->err) return p->err;
+  ENTER_DEVICE(p->di.device);
+  if (int e = pvoc_quiesce(p)) return e;
+  const std::vector<BankBand> bands = bank_bands(nbands, first, count);
+  const std::vector<int> sched = bank_schedule(nbands, count);
+  const std::vector<float> D = bank_dct(nbands);
+  std::vector<float> Dt(D.size());   // the kernel's lanes of neighbouring q read neighbouring words
+  for (int q = 0; q < nbands; q++)
+    for (int b = 0; b < nbands; b++) Dt[(size_t)b * nbands + q] = D[(size_t)q * nbands + b];
+  const size_t nweights = (size_t)bands.back().woff + bands.back().count;
+  int steps = 0;
+  for (int r = 0; r < kBankRows; r++) steps = std::max(steps, sched[r + 1] - sched[r]);
+  // every buffer first, so that a failed allocation leaves the object as it was
+  DevBuf bufs[4];
+  DevBuf clfa_pvoc::*const mine[4] = {&clfa_pvoc::kbands, &clfa_pvoc::ksched, &clfa_pvoc::kweights, &clfa_pvoc::kdct};
+  const void *src[4] = {bands.data(), sched.data(), weights, Dt.data()};
+  const size_t bytes[4] = {sizeof(BankBand) * bands.size(), sizeof(int) * sched.size(), sizeof(float) * nweights,
+                           sizeof(float) * Dt.size()};
+  for (int i = 0; i < 4; i++)
+    if (int e = upload(bufs[i], src[i], bytes[i])) return e;
+  for (int i = 0; i < 4; i++) {
+    std::swap((p->*mine[i]).p, bufs[i].p);
+    std::swap((p->*mine[i]).bytes, bufs[i].bytes);
+  }
+  p->bank_B = nbands;
+  p->bank_steps = steps;
+  return CLFA_SUCCESS;
+}
+
+int clfa_pvoc_bank_bands(const clfa_pvoc *p) { return p ? p->bank_B : -1; }
+
+// the table the device uses, D[q][b]: the device keeps it transposed
+int clfa_pvoc_bank_read_dct(clfa_pvoc *p, float *host) {
+  if (!p || !host) return CLFA_INVALID_VALUE;
+  if (int e = obj_error(p)) return e;
+  if (int e = pvoc_bank_ready(p)) return e;
+  ENTER_DEVICE(p->di.device);
+  if (int e = pvoc_quiesce(p)) return e;
+  const int B = p->bank_B;
+  std::vector<float> Dt((size_t)B * B);
+  HIP_TRY(hipMemcpy(Dt.data(), p->kdct.p, sizeof(float) * Dt.size(), hipMemcpyDeviceToHost));
+  for (int q = 0; q < B; q++)
+    for (int b = 0; b < B; b++) host[(size_t)q * B + b] = Dt[(size_t)b * B + q];
+  return CLFA_SUCCESS;
+}
+
+size_t clfa_pvoc_bank_state_bytes(const clfa_pvoc *p) {
+  return p ? p->kbands.bytes + p->ksched.bytes + p->kweights.bytes + p->kdct.bytes : 0;
+}
+
+int clfa_pvoc_bands_dev(clfa_pvoc *p, const void *frames_in, void *out, long F, int flags, int ncoef, float floor, void *stream) {
+  return pvoc_bands_call(p, false, frames_in, out, F, flags, ncoef, floor, stream);
+}
+
+int clfa_pvoc_bands(clfa_pvoc *p, const float *frames_in, float *out, long F, int flags, int ncoef, float floor) {
+  return pvoc_bands_call(p, true, frames_in, out, F, flags, ncoef, floor, nullptr);
+}
+
+const char *clfa_pvoc_bands_kernel_name(const clfa_pvoc *p) { return !p || p->err ? "" : "k_pvoc_bands"; }
 
 }  // extern "C"
 

@@ -205,7 +205,109 @@ class _PvocStored:
         return out
 
 
-class Pvoc(_Object, _PvocStereo, _PvocDelay, _PvocStored):
+class _PvocBank:
+    """The operation of Pvoc that turns frames into feature vectors through a bank the object is configured with
+    (clfa_pvoc_bank*, clfa_pvoc_bands* in clfft_amd.h): band energies, their log, a DCT of that — the mel spectrum and the
+    MFCCs.  A base of Pvoc, like _PvocStereo: Pvoc supplies the object and the shapes, and its own operations take their
+    parameters per call, not from a setup."""
+
+    # ---- frames -> band energies, log, DCT (Csound's mfb + dct; stateless apart from the bank; clfft_amd.h) ----
+
+    BANDS_POWER, BANDS_LOG, BANDS_DCT = 1, 2, 4
+
+    def bands_kernel_name(self):
+        """ "k_pvoc_bands" ("" for a failed object)"""
+        return self._text("bands_kernel_name")
+
+    def bank_setup(self, first, count, weights):
+        """sets the bank (blocking): band b covers the bins first[b] .. first[b] + count[b] - 1 of 0 .. size/2 with the
+        float32 weights weights[sum(count[:b]) : sum(count[:b + 1])]; 1..256 bands, which may overlap, repeat and come in
+        any order; finite weights of any sign.  Anything else is CL_INVALID_VALUE and leaves the bank as it was."""
+        try:
+            first = np.ascontiguousarray(first, dtype=np.int32).reshape(-1)
+            count = np.ascontiguousarray(count, dtype=np.int32).reshape(-1)
+            weights = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+        except (TypeError, ValueError, OverflowError):
+            return CL_INVALID_VALUE
+        # the library reads sum(count) weights once every count is >= 1: the array has to hold them
+        if first.size != count.size or ((count >= 1).all() and weights.size != int(count.astype(np.int64).sum())):
+            return CL_INVALID_VALUE
+        return self._get("bank_setup", int(count.size), first.ctypes.data, count.ctypes.data, weights.ctypes.data)
+
+    def bank_bands(self):
+        """the bands of the last bank_setup, -1 before"""
+        return self._get("bank_bands")
+
+    def bank_state_bytes(self):
+        """device memory of the bank: bands, schedule, weights, DCT table"""
+        return self._get("bank_state_bytes")
+
+    def bank_dct(self):
+        """the DCT table the device uses (blocking): float32 (B, B), D[q][b], the orthonormal DCT-II"""
+        B = max(self.bank_bands(), 0)
+        out = np.zeros((B, B), np.float32)
+        check(self._get("bank_read_dct", out.ctypes.data), "Pvoc.bank_dct")
+        return out
+
+    def _bands_flags(self, power, log, ncoef):
+        ncoef = int(ncoef)
+        return ((self.BANDS_POWER if power else 0) | (self.BANDS_LOG if log else 0) | (self.BANDS_DCT if ncoef else 0)), ncoef
+
+    def bands_device(self, frames_in, out, power=False, log=False, ncoef=0, floor=1e-10, stream=None):
+        """torch: frames (channels, F, size/2 + 1, 2) float32, contiguous -> out (channels, F, N) float32, contiguous
+        ((F, N) for one channel): per frame the bank's band energies, the weighted sums of the amps (power: of their
+        squares), each a fixed tree of float32 additions — the same bits on every call; log: their logarithms, an energy
+        below `floor` (or a NaN) taking the floor; ncoef != 0: the first ncoef coefficients of the orthonormal DCT-II of
+        that vector.  N = ncoef where that is set, else the bank's bands.  out may not overlap frames_in.  Asynchronous on
+        `stream`."""
+        F = self._device_frames(frames_in)
+        flags, ncoef = self._bands_flags(power, log, ncoef)
+        shape = self._full(out.shape, 3) if hasattr(out, "data_ptr") else ()
+        N = ncoef if ncoef else self.bank_bands()
+        if (F is None or len(shape) != 3 or shape[:2] != (self.channels, F) or (N >= 1 and shape[2] != N)
+                or not _dense_f32(out, out.shape) or out.device != frames_in.device):
+            return CL_INVALID_VALUE
+        return self._get("bands_dev", frames_in.data_ptr(), out.data_ptr(), F, flags, ncoef, float(floor),
+                         _stream_of(out, stream))
+
+    def bands(self, frames, power=False, log=False, ncoef=0, floor=1e-10):
+        """host form of bands_device, blocking: float32 (channels, F, size/2 + 1, 2) (or (F, size/2 + 1, 2)) -> float32
+        (.., F, N); a floor that is not positive and finite with log, or an ncoef outside 1..bands, raises
+        ClError(CL_INVALID_VALUE)"""
+        flags, ncoef = self._bands_flags(power, log, ncoef)
+        N = ncoef if ncoef else self.bank_bands()
+        frames, F, _, out = self._host_prep(frames, tail=(max(N, 1),))
+        check(self._get("bands", frames.ctypes.data, out.ctypes.data, F, flags, ncoef, float(floor)), "Pvoc.bands")
+        return out
+
+    @staticmethod
+    def mel_bank(size, sr, nbands, fmin=0.0, fmax=None):
+        """(first, count, weights) of nbands HTK-mel triangles for bank_setup: mel = 2595 log10(1 + f / 700), the
+        nbands + 2 edges equally spaced in mel from fmin to fmax (default sr / 2), the weights evaluated in float64 at
+        the bin centres k sr / size, k = 0 .. size/2, and rounded to float32, leading and trailing zeros trimmed.  A
+        band whose triangle reaches no bin centre is the one bin nearest its centre with the weight 0."""
+        size, nbands, sr = int(size), int(nbands), float(sr)
+        fmax = sr / 2 if fmax is None else float(fmax)
+        M = size // 2
+        mel = lambda f: 2595.0 * np.log10(1.0 + np.asarray(f, np.float64) / 700.0)
+        edges = 700.0 * (10.0 ** (np.linspace(mel(fmin), mel(fmax), nbands + 2) / 2595.0) - 1.0)
+        f = np.arange(M + 1, dtype=np.float64) * sr / size
+        first, count, weights = [], [], []
+        for b in range(nbands):
+            lo, mid, hi = edges[b], edges[b + 1], edges[b + 2]
+            w = np.maximum(0.0, np.minimum((f - lo) / (mid - lo), (hi - f) / (hi - mid))).astype(np.float32)
+            nz = np.flatnonzero(w)
+            if nz.size:
+                k0, k1 = int(nz[0]), int(nz[-1])
+            else:
+                k0 = k1 = int(min(max(np.rint(mid * size / sr), 0), M))
+            first.append(k0)
+            count.append(k1 - k0 + 1)
+            weights.append(w[k0:k1 + 1] if nz.size else np.zeros(1, np.float32))
+        return np.array(first, np.int32), np.array(count, np.int32), np.concatenate(weights).astype(np.float32)
+
+
+class Pvoc(_Object, _PvocStereo, _PvocDelay, _PvocStored, _PvocBank):
     """Phase vocoder on the spectra of Stft (extension, clfa_pvoc in clfft_amd.h): analyze() reads (channels, F, size/2)
     complex64 spectra as (channels, F, size/2 + 1, 2) float32 frames of (amp, freq in Hz) per bin, synthesize() turns such
     frames back into spectra.  The object carries the last spectrum (analysis) and an integer phase per bin (synthesis)
@@ -215,6 +317,7 @@ class Pvoc(_Object, _PvocStereo, _PvocDelay, _PvocStored):
     demix() takes the frames of the left and of the right channel of one recording apart by pan position.
     delay() gives every bin its own delay time and feedback (two histories of the stream carried along, after delay_setup()).
     tanal() analyses a stored signal at any time points, each frame under a window of its own: the way to another speed.
+    bands() turns frames into feature vectors: the energies of a bank of bands, their log, a DCT (mel, MFCC; after bank_setup()).
     Like the other objects the constructor does not raise, and every call returns its status."""
     _abi = "clfa_pvoc_"
 
