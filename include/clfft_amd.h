@@ -1018,6 +1018,65 @@ CLFA_API int clfa_pvoc_demix(clfa_pvoc *pv, const float *frames_l, const float *
 /* "k_pvoc_demix", or "k_pvoc_demix_az" for a call with the profile ("" for a failed object) */
 CLFA_API const char *clfa_pvoc_demix_kernel_name(const clfa_pvoc *pv, int with_az);
 
+/* ---- the pitch of every frame from its spectral peaks, and the peak list ---- */
+/* Csound's pvspitch (kfr, kamp pvspitch fsig, kthresh): the fundamental frequency of every frame, by subharmonic
+ * summation on the frame's spectral peaks, and the list of those peaks (amp, true freq) as an output of its own.  The
+ * descriptors' PEAK_FREQ is the loudest bin, which is not the pitch of a voice with a weak or missing fundamental; a
+ * peak's freq column is the phase vocoder's estimate of the partial's true frequency, far finer than a bin.
+ * frames_in: channels x F x (M + 1) x 2 float32 in the layout above, 8-byte aligned.  rows: channels x F x 4 float32,
+ * dense, 4-byte aligned: the columns CLFA_PVOC_PITCH_F0, _SAL, _CONF, _NPEAKS.  peaks: NULL, or channels x F x npeaks x 2
+ * float32 (amp, freq) pairs, dense, 8-byte aligned.  first_bin and nbins select the bins lo = first_bin .. hi =
+ * first_bin + nbins - 1 with 1 <= first_bin, 1 <= nbins and first_bin + nbins <= M, so that every bin of the range has
+ * both neighbours.  1 <= npeaks <= CLFA_PVOC_PITCH_PEAKS_MAX; thresh finite and >= 0; fmin a normal float32 > 0, fmax
+ * finite, fmin <= fmax; 0 <= tol <= 0.5; 0 < decay <= 1.  Anything else, a NaN included, is CLFA_INVALID_VALUE.
+ *
+ * Every float32 operation is rounded on its own (no fused multiply-add); fl() marks a rounding.  Divisions are correctly
+ * rounded, as in the descriptors' CENT.  Per channel and frame, with a[k] the amp and q[k] the freq of bin k:
+ *   PEAK        bin k of lo..hi is a peak iff a[k] > a[k-1] and a[k] >= a[k+1] (the neighbours are read from the frame even
+ *               when they lie outside lo..hi), a[k] >= thresh, and q[k] is finite and q[k] > 0.  A NaN makes its comparison
+ *               false.  Of a plateau only the lowest bin is a peak.
+ *   LIST        the first npeaks peaks in ascending bin order, L of them; (A[i], Q[i]) = (a, q) of list entry i, as bits.
+ *               (A caller who wants the loudest peaks instead runs clfa_pvoc_trace_dev in front.)  peaks, where given,
+ *               receives the pairs of the list and (+0, +0) in the entries from L on.
+ *   CANDIDATES  for every list entry i and every m = 1..CLFA_PVOC_PITCH_DIV, c = fl(Q[i] / (float)m); it is a candidate
+ *               iff fmin <= c <= fmax.
+ *   SCORE       s(c) starts at +0 and takes the list entries j = 0..L-1 in that order.  With w[h-1] =
+ *               (float)pow((double)decay, h - 1), computed on the host: r = fl(Q[j] / c), h = rintf(r); entry j counts iff
+ *               1 <= h <= CLFA_PVOC_PITCH_HARM and fl(fl(|fl(r - h)|) / h) <= tol; if it counts, s = fl(s + fl(A[j] w[h-1])).
+ *               A candidate whose score is a NaN is dropped.  (Subharmonic summation on the peaks; the decay lets the true
+ *               fundamental beat c / 2, which matches the same peaks at higher harmonic numbers.)
+ *   BEST        the candidate that no other candidate beats: d beats c iff s(d) > s(c), or s(d) == s(c) and d > c (of equal
+ *               scores the higher pitch wins).  Two candidates equal in both give the same outputs.
+ *   ROW         F0 = the bits of the best c; SAL = its score; CONF = fl(SAL / TOTAL) with TOTAL the serial sum of
+ *               A[0..L-1] in list order from +0, and CONF = +0 where TOTAL == 0; NPEAKS = (float)L.  With no candidate
+ *               F0, SAL and CONF are +0.
+ * A row is a function of one frame: the outputs are the same bits however a stream is cut into calls, on any stream, for
+ * any grid cap and under graph replay.  The bits are defined given the host's pow (two libms may differ in the last place
+ * of a double power; decay = 1 and the first weight are exact everywhere).
+ *
+ * Stateless: no state of the object is read or written, and a device call allocates nothing.  The rules of the frame
+ * operations above hold: asynchronous on `stream`, capturable, one launch per call, one stream at a time, the current
+ * device left as found; F == 0 succeeds and does nothing.  Argument checks that need no device come first: on an object
+ * whose creation found no device a bad argument is still CLFA_INVALID_VALUE, a good one the object's error.  rows or peaks
+ * overlapping frames_in or each other, even partly, is CLFA_INVALID_VALUE and nothing is written.
+ * tests/pvoc_pitch_model.py restates all of it in numpy.
+ *
+ * Kernel: "k_pvoc_pitch" (a group of W = min(M, 256) lanes owns a frame; the lanes test the bins of the range row by row,
+ * a peak's place in the list is a prefix count in bin order — ballots inside a wave, the waves' counts through LDS — and
+ * the walk stops once npeaks are found; the list goes to LDS; the at most 8 L candidates are dealt to the lanes, each
+ * lane scoring its candidates serially over the list, which fixes the order of the sum; the best is reduced by shuffles
+ * and through LDS).  No atomics, no waiting between workgroups.  CLFA_PVOC_OPS_GRID_MAX caps its workgroups. */
+enum { CLFA_PVOC_PITCH_DIV = 8, CLFA_PVOC_PITCH_HARM = 32, CLFA_PVOC_PITCH_PEAKS_MAX = 32 };
+enum { CLFA_PVOC_PITCH_F0 = 0, CLFA_PVOC_PITCH_SAL = 1, CLFA_PVOC_PITCH_CONF = 2, CLFA_PVOC_PITCH_NPEAKS = 3 };
+CLFA_API int clfa_pvoc_pitch_dev(clfa_pvoc *pv, const void *frames_in, void *rows, void *peaks, long F, int first_bin,
+                                 int nbins, int npeaks, float thresh, float fmin, float fmax, float tol, float decay,
+                                 void *stream);
+/* host arrays, copied in and out, blocking */
+CLFA_API int clfa_pvoc_pitch(clfa_pvoc *pv, const float *frames_in, float *rows, float *peaks, long F, int first_bin,
+                             int nbins, int npeaks, float thresh, float fmin, float fmax, float tol, float decay);
+/* "k_pvoc_pitch" ("" for a failed object) */
+CLFA_API const char *clfa_pvoc_pitch_kernel_name(const clfa_pvoc *pv);
+
 /* ---- convolution matrix (extension: nothing of the reference's) ------------- */
 /* Uniformly partitioned overlap-add convolution of `inputs` signals with an outputs x inputs matrix of static responses:
  * y_o = sum over i of x_i * h_{o,i}.

@@ -1,10 +1,11 @@
 // pvoc_device.hpp — what the Pvoc kernel files share (pvoc_kernels.hip, pvoc_ops.hip, pvoc_pair.hip, pvoc_time.hip,
 // pvoc_delay.hip, pvoc_shape.hip, pvoc_desc.hip, pvoc_trace.hip, pvoc_demix.hip, pvoc_adsyn.hip):
-//   pvoc_item, pvoc_bin    the decoding of a grid-stride item, and the bin a lane of a tile kernel takes of it
-//   pvoc_grid, pvoc_tiles  the cap on a launch's workgroups, and the tiles, items and grid of a tile launch
+//   pvoc_item, pvoc_grid, pvoc_group_row, pvoc_groups   the decoding of a grid-stride item, the cap on a launch's
+//                          workgroups and the group kernels' scheme (k_pvoc_desc<W>, k_pvoc_trace<W>): pvoc_group.hpp's,
+//                          included here, which pitch_kernels.hip shares
+//   pvoc_bin               the bin a lane of a tile kernel takes of an item
+//   pvoc_tiles             the tiles, items and grid of a tile launch
 //   kTimeWG, kTimeRun      the item of the kernels along the frames (pvoc_time.hip, pvoc_delay.hip): a tile of bins, a run of frames
-//   pvoc_group_row, pvoc_groups   the group kernels (k_pvoc_desc<W>, k_pvoc_trace<W>): which row of a channel a group of W
-//                          lanes takes of an item, and the items and grid of such a launch
 //   desc_dpp, desc_xor, desc_fold   the in-wave moves and the fold of the descriptors' TREE SUM (k_pvoc_desc<W>, k_pvoc_demix_az<LOGM>):
 //                          tree_moves.hpp's, included here
 //   pvoc_empty, pvoc_clamp01, pvoc_morph   the frame operations' EMPTY bin, clamp and interpolation rule
@@ -12,6 +13,7 @@
 //   pvoc_scan              the chunked scan that turns the per-chunk sums of phase increments into the bases the
 //                          chunks start from (k_pvoc_scan on uint32 words, k_adsyn_scan on uint64 ones)
 #pragma once
+#include "pvoc_group.hpp"
 #include "pvoc_launch.hpp"
 #include "tree_moves.hpp"
 
@@ -21,14 +23,6 @@ constexpr int kScanBins = 64, kScanSegs = 16;   // the scan's workgroup: a wave 
 constexpr int kTimeWG = 256;   // lanes = bins per workgroup tile (k_pvoc_blur, k_pvoc_freeze, k_pvoc_tail, k_pvoc_fill, k_pvoc_delay)
 constexpr int kTimeRun = 8;    // consecutive frames per item of those
 
-// item -> (outer index c, inner index j < inner, tile), the tile fastest: neighbouring workgroups hold neighbouring rows
-__device__ __forceinline__ void pvoc_item(long item, int tiles, long inner, int &tile, long &j, long &c) {
-  const long rest = item / tiles;
-  tile = (int)(item - rest * tiles);
-  c = rest / inner;
-  j = rest - c * inner;
-}
-
 // The prologue of a tile kernel (a lane per bin, WG bins per tile): the item's (c, j) and the lane's bin k; false where
 // the last tile reaches past bin M
 template <int WG>
@@ -37,12 +31,6 @@ __device__ __forceinline__ bool pvoc_bin(long item, int tiles, long inner, int M
   pvoc_item(item, tiles, inner, tile, j, c);
   k = tile * WG + (int)threadIdx.x;
   return k <= M;
-}
-
-// workgroups of a grid-stride launch: one per item, at most cap, at most grid_max where that is set (> 0)
-static inline int pvoc_grid(long items, long cap, int grid_max) {
-  if (grid_max > 0 && cap > grid_max) cap = grid_max;
-  return (int)(items < cap ? items : cap);
 }
 
 // A tile launch: tiles of `lanes` bins per row of M + 1, `outer` rows (channels x frames, runs, ...), an item per tile,
@@ -57,37 +45,6 @@ static inline PvocTiles pvoc_tiles(int M, int lanes, long outer, const DeviceInf
   t.items = outer * t.tiles;
   t.grid = pvoc_grid(t.items, (long)di.num_cus * per_cu, grid_max);
   return t;
-}
-
-// The group kernels: W = min(M, 256) lanes form a group that owns one row of a channel (a frame, a run of frames),
-// kGroupWG / W groups share a workgroup, and an item is a (channel, kGroupWG / W consecutive rows).
-constexpr int kGroupWG = 256;   // lanes of a workgroup = the largest W
-static inline int pvoc_group_lanes(int M) { return M < kGroupWG ? M : kGroupWG; }
-
-// The prologue of a group kernel: the lane's group g of the workgroup and its place j in it, the item's channel c and
-// the group's row r of that channel (r may lie past the last row: the group then idles along)
-template <int W>
-__device__ __forceinline__ void pvoc_group_row(long item, long rgroups, int &g, int &j, long &r, long &c) {
-  int tile;
-  long rg;
-  g = (int)threadIdx.x / W;
-  j = (int)threadIdx.x & (W - 1);
-  pvoc_item(item, 1, rgroups, tile, rg, c);
-  r = rg * (kGroupWG / W) + g;
-}
-
-// A group launch over `rows` rows per channel: the groups of rows per channel, the items, the grid
-struct PvocGroups {
-  long rgroups, items;
-  int grid;
-};
-template <int W>
-static inline PvocGroups pvoc_groups(long rows, int channels, const DeviceInfo &di, int grid_max) {
-  PvocGroups q;
-  q.rgroups = (rows + kGroupWG / W - 1) / (kGroupWG / W);
-  q.items = (long)channels * q.rgroups;
-  q.grid = pvoc_grid(q.items, (long)di.num_cus * 8, grid_max);
-  return q;
 }
 
 // an EMPTY bin of the frame operations: silent, at its bin centre (cf = sr / size)

@@ -6,6 +6,7 @@
 #include "bank_plan.hpp"
 #include "fft_route.hpp"
 #include "host.hpp"
+#include "pitch_launch.hpp"
 #include "pvoc_launch.hpp"
 #include "tanal_launch.hpp"
 
@@ -58,6 +59,7 @@ struct clfa_pvoc {
   DevBuf dlast, sdesc;
   DevBuf strace_bins;   // the N loudest bins (pvoc_trace.hip): staging of the host form's bin list
   DevBuf sdemix_az;     // the stereo demix (pvoc_demix.hip): staging of the host form's azimuth profile
+  DevBuf spitch_rows, spitch_peaks;   // the pitch (pitch_kernels.hip): staging of the host form's rows and peak list
   // the filter bank (bank_kernels.hip; clfa_pvoc_bank_setup, bank_B -1 before): the bands, the schedule that deals them to
   // the kernel's rows (bank_steps: its longest row), the weights and the DCT table, transposed; staging of the host
   // form's rows.  Configuration, not stream state: clfa_pvoc_reset leaves it alone
@@ -212,7 +214,7 @@ static int pvoc_code(hipError_t e) {
 // ---------------------------------------------------------------------------------
 
 // One array of a call (HostArray, host.hpp; the rules: arrays_ok, overlap.hpp): the outputs are one, or two (trace's
-// frames and bin list, demix's frames and profile); what an op does not look at is not `used`: MIX's p and q, BLUR's q, most tables, a NULL fmod
+// frames and bin list, demix's frames and profile, pitch's rows and peak list); what an op does not look at is not `used`: MIX's p and q, BLUR's q, most tables, a NULL fmod
 using PvocArray = HostArray<clfa_pvoc>;
 
 // The device forms after their checks (chk): the error, else the object's own, else a no-op's success, ahead of any device
@@ -1095,6 +1097,61 @@ int clfa_pvoc_demix(clfa_pvoc *p, const float *frames_l, const float *frames_r, 
 const char *clfa_pvoc_demix_kernel_name(const clfa_pvoc *p, int with_az) {
   return !p || p->err ? "" : (with_az ? "k_pvoc_demix_az" : "k_pvoc_demix");
 }
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------
+// frames -> four values per frame: the pitch from the frame's spectral peaks, and the peak list (pitch_kernels.hip)
+// ---------------------------------------------------------------------------------
+
+// The third call with two outputs: the rows, and the list where `peaks` is given.  All its parameters are scalars, so the
+// blocking form has no values to refuse.  The negated comparisons refuse a NaN.
+static int pvoc_pitch_call(clfa_pvoc *p, bool blocking, const void *in, void *rows, void *peaks, long F, int first_bin,
+                           int nbins, int npeaks, float thresh, float fmin, float fmax, float tol, float decay, void *stream) {
+  if (int e = pvoc_usable(p)) return e;
+  const bool scalars_ok = first_bin >= 1 && nbins >= 1 && (long)first_bin + nbins <= p->M && npeaks >= 1 &&
+                          npeaks <= CLFA_PVOC_PITCH_PEAKS_MAX && thresh >= 0.f && std::isfinite(thresh) &&
+                          std::isnormal(fmin) && fmin > 0.f && std::isfinite(fmax) && fmin <= fmax && tol >= 0.f &&
+                          tol <= 0.5f && decay > 0.f && decay <= 1.f;
+  const size_t frames = (size_t)p->channels * (size_t)(F > 0 ? F : 0);
+  const size_t pbytes = peaks && scalars_ok ? 2 * sizeof(float) * frames * (size_t)npeaks : 0;
+  const PvocArray arrays[] = {{in, pvoc_frame_bytes(p, F), 8, false, &clfa_pvoc::sframes},
+                              {rows, 4 * sizeof(float) * frames, 4, true, &clfa_pvoc::spitch_rows},
+                              {peaks, pbytes, 8, true, &clfa_pvoc::spitch_peaks, peaks != nullptr}};
+  return pvoc_call(p, blocking, stream, scalars_ok, F, arrays, CLFA_SUCCESS, pvoc_no_values, [&](const void *const *d, hipStream_t s) {
+    PvocPitchArgs a;
+    a.M = p->M;
+    a.channels = p->channels;
+    a.F = F;
+    a.grid_max = p->ops_grid_max;
+    a.in = (const cpx *)d[0];
+    a.rows = (float *)d[1];
+    a.peaks = (cpx *)d[2];
+    a.npeaks = npeaks;
+    a.lo = first_bin;
+    a.hi = first_bin + nbins - 1;
+    a.thresh = thresh;
+    a.fmin = fmin;
+    a.fmax = fmax;
+    a.tol = tol;
+    for (int h = 1; h <= CLFA_PVOC_PITCH_HARM; h++) a.weights.w[h - 1] = (float)pow((double)decay, h - 1);
+    return launch_pvoc_pitch(a, p->di, s);
+  });
+}
+
+extern "C" {
+
+int clfa_pvoc_pitch_dev(clfa_pvoc *p, const void *frames_in, void *rows, void *peaks, long F, int first_bin, int nbins,
+                        int npeaks, float thresh, float fmin, float fmax, float tol, float decay, void *stream) {
+  return pvoc_pitch_call(p, false, frames_in, rows, peaks, F, first_bin, nbins, npeaks, thresh, fmin, fmax, tol, decay, stream);
+}
+
+int clfa_pvoc_pitch(clfa_pvoc *p, const float *frames_in, float *rows, float *peaks, long F, int first_bin, int nbins,
+                    int npeaks, float thresh, float fmin, float fmax, float tol, float decay) {
+  return pvoc_pitch_call(p, true, frames_in, rows, peaks, F, first_bin, nbins, npeaks, thresh, fmin, fmax, tol, decay, nullptr);
+}
+
+const char *clfa_pvoc_pitch_kernel_name(const clfa_pvoc *p) { return !p || p->err ? "" : "k_pvoc_pitch"; }
 
 }  // extern "C"
 

@@ -2,7 +2,7 @@
 // synthesis (PvocArgs), the oscillator bank (PvocAdsynArgs), and the operations on (amp, freq) frames, each with its *Args
 // struct over PvocFramesArgs: ops, pair, shape, time, delay, desc, trace, demix.  (The analysis of a stored signal,
 // tanal_kernels.hip, has tanal_launch.hpp: it shares the FFT engine with the Stft kernels, not these launchers; the filter
-// bank, bank_kernels.hip, has bank_launch.hpp.)
+// bank, bank_kernels.hip, has bank_launch.hpp, and the pitch, pitch_kernels.hip, pitch_launch.hpp.)
 #pragma once
 #include <hip/hip_runtime.h>
 

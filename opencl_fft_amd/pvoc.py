@@ -307,7 +307,61 @@ class _PvocBank:
         return np.array(first, np.int32), np.array(count, np.int32), np.concatenate(weights).astype(np.float32)
 
 
-class Pvoc(_Object, _PvocStereo, _PvocDelay, _PvocStored, _PvocBank):
+class _PvocPitch:
+    """The operation of Pvoc that estimates from the frames, not reshapes them (clfa_pvoc_pitch* in clfft_amd.h): the
+    fundamental frequency of every frame from its spectral peaks, and the list of those peaks.  A base of Pvoc, like
+    _PvocStereo: Pvoc supplies the object and the shapes, and its own operations answer with frames, samples or the
+    descriptors' sums."""
+
+    PITCH_F0, PITCH_SAL, PITCH_CONF, PITCH_NPEAKS = range(4)
+    PITCH_PEAKS_MAX = 32
+
+    def pitch_kernel_name(self):
+        """ "k_pvoc_pitch" ("" for a failed object)"""
+        return self._text("pitch_kernel_name")
+
+    def _pitch_range(self, first_bin, nbins):
+        """the bins first_bin .. first_bin + nbins - 1, by default up to size/2 - 1: every bin of it has both neighbours"""
+        first_bin = int(first_bin)
+        return first_bin, self.M - first_bin if nbins is None else int(nbins)
+
+    def pitch_device(self, frames_in, rows, thresh, fmin, fmax, npeaks=16, tol=0.03, decay=0.84, first_bin=1, nbins=None,
+                     peaks_out=None, stream=None):
+        """torch: frames (channels, F, size/2 + 1, 2) float32, contiguous -> rows (channels, F, 4) float32, contiguous
+        ((F, 4) for one channel): per frame the columns PITCH_F0 (the fundamental in Hz, 0 where none is found), PITCH_SAL
+        (its score: the summed amps of the peaks that lie on its harmonics, harmonic h weighted decay ** (h - 1); Csound's
+        kamp), PITCH_CONF (SAL over the summed amps of all the peaks) and PITCH_NPEAKS.  The peaks are the first `npeaks`
+        (1..32) local maxima of the amps of the bins first_bin .. first_bin + nbins - 1 (default: 1 .. size/2 - 1) that
+        reach `thresh` and have a finite freq > 0; the candidates are their freqs over 1..8 inside fmin..fmax; a peak lies
+        on harmonic h of a candidate where its freq is within tol h of h times the candidate (as a ratio).  peaks_out: a
+        float32 device tensor (channels, F, npeaks, 2), contiguous ((F, npeaks, 2) for one channel), that takes the peaks'
+        (amp, freq) pairs in ascending bin order, then zeros.  Asynchronous on `stream`."""
+        F, npeaks = self._device_frames(frames_in), int(npeaks)
+        if F is None or self._full(rows.shape, 3) != (self.channels, F, 4) or not _dense_f32(rows, rows.shape):
+            return CL_INVALID_VALUE
+        peaks = None
+        if peaks_out is not None:
+            if (self._full(peaks_out.shape, 4) != (self.channels, F, npeaks, 2) or not _dense_f32(peaks_out, peaks_out.shape)
+                    or peaks_out.device != rows.device):
+                return CL_INVALID_VALUE
+            peaks = peaks_out.data_ptr()
+        first_bin, nbins = self._pitch_range(first_bin, nbins)
+        return self._get("pitch_dev", frames_in.data_ptr(), rows.data_ptr(), peaks, F, first_bin, nbins, npeaks, float(thresh),
+                         float(fmin), float(fmax), float(tol), float(decay), _stream_of(rows, stream))
+
+    def pitch(self, frames, thresh, fmin, fmax, npeaks=16, tol=0.03, decay=0.84, first_bin=1, nbins=None, peaks=False):
+        """host form of pitch_device, blocking: float32 (channels, F, size/2 + 1, 2) (or (F, size/2 + 1, 2)) -> the rows,
+        float32 (.., F, 4), or (rows, list) with the list float32 (.., F, npeaks, 2) when `peaks` is set"""
+        frames, F, _, out = self._host_prep(frames, tail=(4,))
+        npeaks = int(npeaks)
+        lst = np.zeros(frames.shape[:-2] + (max(npeaks, 0), 2), np.float32) if peaks else None
+        first_bin, nbins = self._pitch_range(first_bin, nbins)
+        check(self._get("pitch", frames.ctypes.data, out.ctypes.data, _data(lst), F, first_bin, nbins, npeaks, float(thresh),
+                        float(fmin), float(fmax), float(tol), float(decay)), "Pvoc.pitch")
+        return out if lst is None else (out, lst)
+
+
+class Pvoc(_Object, _PvocStereo, _PvocDelay, _PvocStored, _PvocBank, _PvocPitch):
     """Phase vocoder on the spectra of Stft (extension, clfa_pvoc in clfft_amd.h): analyze() reads (channels, F, size/2)
     complex64 spectra as (channels, F, size/2 + 1, 2) float32 frames of (amp, freq in Hz) per bin, synthesize() turns such
     frames back into spectra.  The object carries the last spectrum (analysis) and an integer phase per bin (synthesis)
