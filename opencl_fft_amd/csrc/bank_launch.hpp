@@ -1,4 +1,4 @@
-// bank_launch.hpp — the launcher of the filter bank on (amp, freq) frames (bank_kernels.hip) as pvoc_host.cpp sees it:
+// bank_launch.hpp — the launcher of the filter bank on (amp, freq) frames (bank_kernels.hip) as pvoc_rows_host.cpp sees it:
 // BankArgs and launch_pvoc_bands.  A header of its own, like tanal_launch.hpp: the kernel file shares the tree's moves
 // (tree_moves.hpp) with the descriptors and nothing with the launchers of the frame operations (pvoc_launch.hpp).
 #pragma once

@@ -1,6 +1,6 @@
 // bank_plan.hpp — the host side of the filter bank on (amp, freq) frames (clfa_pvoc_bank_setup, include/clfft_amd.h) that
 // needs no device (plain C++: tests/test_pvoc_bank_cpu.py builds it with g++): the validation of a bank, the schedule that
-// deals its bands to the sixteen rows of k_pvoc_bands (bank_kernels.hip), and the DCT table.  pvoc_host.cpp uploads what
+// deals its bands to the sixteen rows of k_pvoc_bands (bank_kernels.hip), and the DCT table.  pvoc_rows_host.cpp uploads what
 // these make.
 #pragma once
 #include <algorithm>

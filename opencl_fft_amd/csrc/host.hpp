@@ -1,11 +1,11 @@
 // host.hpp — plumbing shared by the host side of the C ABI (clfft_amd.cpp: FFT plans, pconv_host.cpp, dconv_host.cpp,
-// pconv_matrix_host.cpp, nupconv_host.cpp: the convolutions over conv_host.hpp, stft_host.cpp: Stft, pvoc_host.cpp:
-// Pvoc): error mapping, device and stream handling, owned device /
-// pinned buffers, numeric switches of the environment, the exact host tables every object needs (the FFT-only ones:
+// pconv_matrix_host.cpp, nupconv_host.cpp: the convolutions over conv_host.hpp, stft_host.cpp: Stft, pvoc_host.cpp,
+// pvoc_frames_host.cpp, pvoc_stream_host.cpp, pvoc_rows_host.cpp, pvoc_signal_host.cpp: Pvoc over pvoc_host.hpp): error
+// mapping, device and stream handling, owned device / pinned buffers, numeric switches of the environment, the exact host tables every object needs (the FFT-only ones:
 // fft_tables.hpp), the prelude / creation / destruction every object shares, and the staged blocking form of a call
 // (staged_call) over the description of its arrays (HostArray; its rules: overlap.hpp).  Each *_host.cpp adds the launch
 // headers of its own kernel families (fft_launch.hpp, pconv_launch.hpp, dconv_launch.hpp, stft_launch.hpp, pvoc_launch.hpp,
-// tanal_launch.hpp, bank_launch.hpp).
+// tanal_launch.hpp, bank_launch.hpp, pitch_launch.hpp).
 // Everything here is inline and hidden (-fvisibility=hidden): nothing becomes an exported symbol.
 #pragma once
 #include "../../include/clfft_amd.h"
@@ -19,6 +19,7 @@
 #include <cstring>
 #include <initializer_list>
 #include <new>
+#include <utility>
 #include <vector>
 
 #include "cpx.hpp"
@@ -184,6 +185,10 @@ struct DevBuf {
     p = nullptr;
     bytes = 0;
   }
+  void swap(DevBuf &o) {
+    std::swap(p, o.p);
+    std::swap(bytes, o.bytes);
+  }
 };
 
 // pinned host memory mapped into the device's address space: kernels read / write it directly over
@@ -317,10 +322,14 @@ constexpr size_t kCallArrays = 5;   // at most so many per call
 // The blocking form around a device form, on the object's device (the caller has entered it): every array the call looks
 // at has its staging buffer, ensured in the order of the list; the inputs are copied in (strided rows packed), dev(d) runs
 // the device work on the staged arrays d[i] (NULL where the call does not look) and the object's stream, every output is
-// copied out (to the caller's strided rows), and the stream is waited for, once.
+// copied out (to the caller's strided rows), and the stream is waited for, once.  A staging buffer holds one array of a
+// call: a list whose used arrays name one buffer twice is an invalid operation.
 template <class T, size_t N, class Dev>
 inline int staged_call(T *p, const HostArray<T> (&arrays)[N], Dev dev) {
   static_assert(N <= kCallArrays, "kCallArrays");
+  for (size_t i = 0; i < N; i++)
+    for (size_t k = 0; k < i; k++)
+      if (arrays[i].used && arrays[k].used && arrays[i].stage == arrays[k].stage) return CLFA_INVALID_OPERATION;
   const void *d[kCallArrays] = {};
   for (size_t i = 0; i < N; i++) {
     const HostArray<T> &a = arrays[i];

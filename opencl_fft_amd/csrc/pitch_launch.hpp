@@ -1,5 +1,5 @@
-// pitch_launch.hpp — the launcher of the pitch estimate on (amp, freq) frames (pitch_kernels.hip) as pvoc_host.cpp sees
-// it: PvocPitchArgs and launch_pvoc_pitch.  A header of its own, like bank_launch.hpp and tanal_launch.hpp: the kernel file
+// pitch_launch.hpp — the launcher of the pitch estimate on (amp, freq) frames (pitch_kernels.hip) as pvoc_rows_host.cpp
+// sees it: PvocPitchArgs and launch_pvoc_pitch.  A header of its own, like bank_launch.hpp and tanal_launch.hpp: the kernel file
 // shares the group scheme (pvoc_group.hpp) with the descriptors and the trace and nothing with the launchers of the frame
 // operations (pvoc_launch.hpp), so an edit there does not rebuild it.
 #pragma once

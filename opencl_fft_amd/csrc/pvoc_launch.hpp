@@ -1,4 +1,4 @@
-// pvoc_launch.hpp — the launchers of the phase vocoder (the ten pvoc_*.hip files) as pvoc_host.cpp sees them: analysis and
+// pvoc_launch.hpp — the launchers of the phase vocoder (the ten pvoc_*.hip files) as the Pvoc host sources see them: analysis and
 // synthesis (PvocArgs), the oscillator bank (PvocAdsynArgs), and the operations on (amp, freq) frames, each with its *Args
 // struct over PvocFramesArgs: ops, pair, shape, time, delay, desc, trace, demix.  (The analysis of a stored signal,
 // tanal_kernels.hip, has tanal_launch.hpp: it shares the FFT engine with the Stft kernels, not these launchers; the filter
@@ -57,7 +57,7 @@ struct PvocAdsynArgs {
 // frames [f0, f0 + nf) of every channel, nf <= the workspace's chunks x kPvocChunk: k_adsyn_sums, k_adsyn_scan, k_adsyn_osc
 hipError_t launch_pvoc_adsyn(const PvocAdsynArgs &a, long f0, long nf, const DeviceInfo &di, hipStream_t s);
 
-// ---- what the launches of the frame operations below share (filled by pvoc_host.cpp's pvoc_frames_args) ----
+// ---- what the launches of the frame operations below share (filled by pvoc_host.hpp's pvoc_frames_args) ----
 struct PvocFramesArgs {
   int M = 0, channels = 0;
   long F = 0;                      // frames per channel of the output (and of every input but the read's)

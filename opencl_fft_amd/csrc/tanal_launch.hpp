@@ -1,5 +1,5 @@
 // tanal_launch.hpp — the launcher of the analysis of a stored signal at given time points (tanal_kernels.hip) as
-// pvoc_host.cpp sees it: PvocTanalArgs and launch_pvoc_tanal.  A header of its own: the kernel file shares the FFT engine
+// pvoc_signal_host.cpp sees it: PvocTanalArgs and launch_pvoc_tanal.  A header of its own: the kernel file shares the FFT engine
 // with stft_kernels.hip and nothing with the launchers of the frame operations (pvoc_launch.hpp).
 #pragma once
 #include <hip/hip_runtime.h>

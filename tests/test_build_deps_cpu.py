@@ -1,5 +1,5 @@
 """What a header edit rebuilds, asked of make (opencl_fft_amd/csrc/Makefile): the objects' dependencies are the
-compiler's own lists (build/<stem>.d, written by -MMD -MP), and the objects are every *.hip of the directory plus the four
+compiler's own lists (build/<stem>.d, written by -MMD -MP), and the objects are every *.hip of the directory plus the
 host sources.  For a header H the sources recompiled after an edit are the `-c <source>` of `make -n -W H` minus those of
 plain `make -n`; no file is touched.  The launch headers are per kernel family, so an edit of one family's header or of
 the FFT engine leaves the other families' objects alone, and a new kernel file cannot be left out of the link."""
@@ -13,12 +13,13 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "opencl_fft_amd", "csrc")
 CONV_HOST = ["pconv_host.cpp", "dconv_host.cpp", "pconv_matrix_host.cpp", "nupconv_host.cpp"]
-HOST = ["clfft_amd.cpp"] + CONV_HOST + ["stft_host.cpp", "pvoc_host.cpp"]
+PVOC_HOST = ["pvoc_host.cpp", "pvoc_frames_host.cpp", "pvoc_stream_host.cpp", "pvoc_rows_host.cpp", "pvoc_signal_host.cpp"]
+HOST = ["clfft_amd.cpp"] + CONV_HOST + ["stft_host.cpp"] + PVOC_HOST
 PVOC = ["pvoc_kernels.hip", "pvoc_ops.hip", "pvoc_pair.hip", "pvoc_time.hip", "pvoc_delay.hip", "pvoc_shape.hip",
         "pvoc_desc.hip", "pvoc_trace.hip", "pvoc_demix.hip", "pvoc_adsyn.hip"]
 # the units that use nothing of the FFT engine (fft_device.hpp)
 NO_ENGINE = ["pvoc_kernels.hip", "pvoc_time.hip", "pvoc_delay.hip", "pvoc_desc.hip", "pvoc_trace.hip", "pvoc_demix.hip",
-             "pvoc_adsyn.hip", "dconv_block.hip", "bandwidth_probe.hip", "pvoc_host.cpp"]
+             "pvoc_adsyn.hip", "dconv_block.hip", "bandwidth_probe.hip"] + PVOC_HOST
 
 
 def units():
@@ -58,7 +59,18 @@ def test_inc_file_belongs_to_one_unit(up_to_date, header, unit):
 
 
 def test_pvoc_launch_header_is_pvoc_only(up_to_date):
-    assert recompiled("pvoc_launch.hpp", up_to_date) == set(PVOC) | {"pvoc_host.cpp"}
+    assert recompiled("pvoc_launch.hpp", up_to_date) == set(PVOC) | set(PVOC_HOST)
+
+
+@pytest.mark.parametrize("header, units", [("bank_launch.hpp", {"bank_kernels.hip", "pvoc_rows_host.cpp"}),
+                                           ("pitch_launch.hpp", {"pitch_kernels.hip", "pvoc_rows_host.cpp"}),
+                                           ("tanal_launch.hpp", {"tanal_kernels.hip", "pvoc_signal_host.cpp"})])
+def test_family_launch_header_is_its_kernel_file_and_one_host_source(up_to_date, header, units):
+    assert recompiled(header, up_to_date) == units
+
+
+def test_pvoc_host_header_is_the_pvoc_hosts(up_to_date):
+    assert recompiled("pvoc_host.hpp", up_to_date) == set(PVOC_HOST)
 
 
 def test_dconv_launch_header_is_dconv_only(up_to_date):
